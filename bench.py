@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- full descriptor chain on a device-resident synthetic DEM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dump-outputs DIR]
 
 A step = one pass of the whole chain (slope -> D8 -> flow accumulation -> river mask -> flow
 distance / river index / HAND -> fused slope+TI+MTI -> GFI -> ln(hl/H) -> downslope) over one
@@ -44,6 +44,52 @@ def pmc_traffic(kernels, size):
         return tot
     except Exception:
         return None
+
+
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files together, headers included
+DUMP_SEED = 20240601             # the cells sampled from rasters larger than the budget
+
+
+def dump_sample(rasters, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: {name: 2-D torch tensor (device or host, any strides)} -> {name: numpy array} holding the same
+    cells of every raster in float32 (float32 rasters, 8/16-bit integers) or float64 (32/64-bit integers): exact
+    values either way.  When every cell fits in `budget` bytes the rasters come whole, shape (H, W); otherwise a
+    fixed sample of cells -- `seed` and the raster's shape decide which, sorted in row-major order -- as 1-D arrays.
+    Call it before anything else writes the rasters."""
+    import torch
+    if not rasters:
+        return {}
+    shapes = {tuple(t.shape) for t in rasters.values()}
+    assert len(shapes) == 1, "rasters of one step share a shape: %s" % shapes
+    H, W = shapes.pop()
+    N = H * W
+
+    def np_dtype(t):
+        return np.float32 if (t.is_floating_point() and t.element_size() <= 4) or t.element_size() <= 2 else np.float64
+    per_cell = sum(np.dtype(np_dtype(t)).itemsize for t in rasters.values())
+    cells = (budget - 256 * len(rasters)) // per_cell  # 256: room for each .npy header
+    out = {}
+    if N <= cells:
+        for name, t in rasters.items():
+            out[name] = t.detach().cpu().numpy().astype(np_dtype(t))
+        return out
+    flat = np.unique(np.random.default_rng([seed, H, W]).integers(0, N, size=cells, dtype=np.int64))
+    for name, t in rasters.items():
+        sel = torch.from_numpy(flat).to(t.device)
+        v = t[sel // W, sel % W]
+        out[name] = v.cpu().numpy().astype(np_dtype(t))
+    return out
+
+
+def write_dump(out_dir, arrays, suffix=""):
+    """arrays from dump_sample -> out_dir/<name><suffix>.npy; returns the file names"""
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for name, a in arrays.items():
+        fn = name + suffix + ".npy"
+        np.save(os.path.join(out_dir, fn), a)
+        names.append(fn)
+    return names
 
 
 def relaunch_under_torchrun(args):
@@ -151,7 +197,13 @@ def main():
                     "collective path even with one rank (rehearsal of the RCCL calls on a 1-GPU box)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL; default) or gloo (rehearsal of N > 1 "
                                                         "with several ranks sharing one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed loop, write the rasters its "
+                    "last step computed as DIR/<name>.npy (float32, or float64 for 32/64-bit integer rasters; exact "
+                    "values): whole when they fit in 64 MB together, else the same fixed, seeded sample of cells from "
+                    "each (1-D, row-major order).  N > 1: every rank writes its own tile as <name>.rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.overlap = not args.no_overlap
     args.size, args.global_dem = default_workload(args.gpus, args.size, args.global_dem)
     args.tune = False if (args.no_placement or args.placement == "off") else (True if args.placement == "own" else "search")
@@ -255,6 +307,9 @@ def main():
             step()
     barrier()
     dt = time.perf_counter() - t0
+    # what the last timed step left in the rasters, before the loops below write them again
+    dump = None if args.dump_outputs is None else dump_sample(
+        {name: t for name, t in rasters.items() if name not in ("a_river", "slope_rad")})  # not written by the step
 
     # ---- second timed loop, same process: the same ops on ONE stream, back to back, each bracketed by HIP events on
     # that stream -> per-op / per-kernel durations that mean something (chain.Chain.ops(serial=True)) ----
@@ -329,6 +384,8 @@ def main():
         out["end_to_end"] = end_to_end(args.e2e_size, args.seed, args.real_rep)
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_n)
+    if dump is not None:
+        write_dump(args.dump_outputs, dump)
     print(json.dumps(out), flush=True)
 
 
@@ -459,6 +516,9 @@ def main_tiled(args, torch, dist, world, rank, local_rank, dev):
         tiling.run_rank(tile, layout, exchange, overlap=args.overlap)
     barrier()
     dt = time.perf_counter() - t0
+    dump = None if args.dump_outputs is None else dump_sample(
+        {name: tile.core(name) for name in ("slope", "fdr", "fac", "river", "fdist", "idx", "hand", "ti", "mti", "gfi",
+                                            "lnhlh", "down")}, budget=DUMP_BUDGET_BYTES // world)
     if use_dist:
         dt = allreduce([dt], dist.ReduceOp.MAX)[0]
     status = tile.ctx.status() & 1
@@ -528,6 +588,8 @@ def main_tiled(args, torch, dist, world, rank, local_rank, dev):
     }
     if rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_n)
+    if dump is not None:
+        write_dump(args.dump_outputs, dump, ".rank%d" % rank if world > 1 else "")
     if use_dist:
         dist.barrier()  # the other ranks wait for rank 0's CPU baseline
     if rank == 0:
@@ -780,6 +842,31 @@ def real_terrain(rep=8, rough_n=4096):
     return out
 
 
+def baseline_library(oracle):
+    """The baseline's -march=native build of the oracle is made on the machine that times it, in oracle/_build when
+    that is possible.  A checkout built earlier by another user may not be writable: then the same Makefile target is
+    built in a private temporary directory and oracle.use_bench_build loads it from there.  Returns that directory
+    (for the caller to remove afterwards) or None."""
+    import subprocess
+    import tempfile
+    so = oracle._SO_BENCH
+    src = os.path.join(os.path.dirname(oracle.__file__), "dt_oracle.c")
+    if os.path.exists(so) and os.path.getmtime(so) >= os.path.getmtime(src):
+        return None
+    bdir = os.path.dirname(so)
+    if os.access(bdir if os.path.isdir(bdir) else os.path.dirname(bdir), os.W_OK) and (
+            not os.path.exists(so) or os.access(so, os.W_OK)):
+        return None
+    tmp = tempfile.mkdtemp(prefix="dt_oracle_bench_")
+    for f in ("Makefile", "dt_oracle.c"):
+        with open(os.path.join(os.path.dirname(oracle.__file__), f), "rb") as i, \
+                open(os.path.join(tmp, f), "wb") as o:
+            o.write(i.read())
+    subprocess.check_call(["make", "-C", tmp, "-s", "bench"])
+    oracle._SO_BENCH = os.path.join(tmp, "_build", os.path.basename(so))
+    return tmp
+
+
 def cpu_baseline(n=3584, seeds=(1,)):
     """the reference's CPU path is its single-threaded `*_sequential_jit` family (Numba is not in
     this image), so the baseline is the oracle -- the same per-cell algorithms restated in C -- built with
@@ -804,6 +891,8 @@ def cpu_baseline(n=3584, seeds=(1,)):
         return time.perf_counter() - t0
 
     ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    so_bench = oracle._SO_BENCH
+    tmp = baseline_library(oracle)
     try:
         oracle.use_bench_build(1)
         t1 = sorted(run(s) for s in seeds)
@@ -811,6 +900,10 @@ def cpu_baseline(n=3584, seeds=(1,)):
         tn = sorted(run(s) for s in (1, 2, 3))
     finally:
         oracle.use_bench_build(None)
+        if tmp is not None:
+            import shutil
+            oracle._SO_BENCH = so_bench
+            shutil.rmtree(tmp, ignore_errors=True)
     med1, medn = t1[len(t1) // 2], tn[len(tn) // 2]
     return {"value": round(n * n / med1 / 1e6, 3), "unit": "Mcells/s", "cores": 1, "kind": "port",
             "all_cores": {"value": round(n * n / medn / 1e6, 3), "unit": "Mcells/s", "cores": ncpu,

@@ -115,3 +115,46 @@ def test_bench_gpus_flag_without_a_launcher_starts_the_ranks_itself():
     assert d["config"]["global_dem"] == "1024x2048" and d["downslope_walks_beyond_halo"] == 0
     _check_common(d, 1024 * 1024)
     assert d["verified"]["cells_drained_through_outlets"] == 1024 * 2048 and "cpu_baseline" in d
+
+
+def _load_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the rasters of the timed step as float32 / float64 .npy files, at most 64 MB; whole rasters
+    when they fit (their checksums are the verified ones), else the same seeded sample of cells from run to run, from
+    schedule to schedule and through the multi-rank path"""
+    import numpy as np
+    names = {"slope", "fdr", "fac", "river", "fdist", "idx", "hand", "ti", "mti", "gfi", "lnhlh", "down"}
+    whole = str(tmp_path / "whole")
+    s = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "1024", "--steps", "3", "--warmup",
+                        "1", "--no-cpu-baseline", "--no-e2e", "--dump-outputs", whole], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
+    assert s.returncode == 0, s.stderr[-2000:]
+    d = json.loads([ln for ln in s.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3
+    w = _load_dump(whole)
+    assert set(w) == names and all(a.shape == (1024, 1024) for a in w.values())
+    for name, a in w.items():
+        assert a.dtype == (np.float64 if name in ("fac", "idx") else np.float32), name
+        if name in ("fac", "idx"):
+            got = int(a.astype(np.int64).sum())
+        elif name in ("fdr", "river"):
+            got = int(a.astype(np.uint8).astype(np.int64).sum())
+        else:
+            got = int(a.view(np.int32).astype(np.int64).sum())
+        assert got == d["verified"]["checksums"][name], name
+    runs = []
+    for i, extra in enumerate(((), ("--no-overlap",), ("--tiled",))):
+        out = str(tmp_path / ("s%d" % i))
+        _run("--no-cpu-baseline", "--no-e2e", "--dump-outputs", out, *extra)
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64_000_000
+        runs.append(_load_dump(out))
+    a = runs[0]
+    n = len(a["slope"])
+    assert set(a) == names and 0 < n < 2048 * 2048 and all(v.shape == (n,) for v in a.values())
+    assert all(a[k].dtype in (np.float32, np.float64) for k in a)
+    for b in runs[1:]:
+        assert set(b) == names and all(np.array_equal(a[k], b[k], equal_nan=True) for k in names)
