@@ -64,6 +64,7 @@ _SIGS = {
     "dt_hand_f64": (ci, [c_f64p, c_i64p, i64, c_f64p]),
     "dt_downslope_f64": (ci, [c_f64p, c_u8p, i64, i64, f64, f64, ci, c_f32p]),
     "dt_gfi_f64h": (ci, [c_f64p, c_i64p, c_i64p, i64, f64, f64, f64, ci, c_f32p]),
+    "dt_d8_f64": (ci, [c_f64p, i64, i64, f64, c_u8p, c_f32p]),
     "dt_confusion_multi": (ci, [c_f64p, c_i8p, i64, f64, c_f64p, ci, ci, c_i64p]),
     "dt_synth_dem": (ci, [u32, i64, i64, i64, i64, i64, i64, ci, c_f32p]),
     # device tier
@@ -143,6 +144,11 @@ _SIGS = {
     "dt_dev_flowacc_finish_flowhand_local_w_a64": (ci, [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dt_dev_i32_to_i64": (ci, [vp, vp, i64, vp]),
     "dt_dev_i64_to_i32": (ci, [vp, vp, i64, vp]),
+    # the resident chain on float64 heights
+    "dt_dev_slope_d8_f64": (ci, [vp, vp, i64, i64, f64, vp, vp]),
+    "dt_dev_slope_twi_f64": (ci, [vp, vp, vp, i64, i64, f64, f64, vp, vp, vp, vp]),
+    "dt_dev_downslope_f64": (ci, [vp, vp, vp, i64, i64, f64, f64, ci, vp]),
+    "dt_dev_hand_gfi_f64": (ci, [vp, vp, vp, vp, i64, i64, f64, f64, f64, vp, vp, vp]),
 }
 
 
@@ -282,3 +288,23 @@ def dem_f32(dem, what="DEM"):
             "DT_ALLOW_DEM_ROUNDING=1 to accept the rounding"
             % (what, a.dtype, k, a.reshape(-1)[k].item(), d32.reshape(-1)[k].item()))
     return d32
+
+
+HEIGHT_TIERS = ("float32", "float64", "auto")
+
+
+def dem_tier(dem, tier="float32", what="DEM"):
+    """A DEM for an entry point with an opt-in float64 tier (chain.run_host, flowdir.d8) -> (array, wide).
+    "float32": dem_f32 (ValueError for heights float32 cannot hold); "float64": the heights as float64, always;
+    "auto": heights() decides, the rule of the drop-in descriptor functions."""
+    if tier not in HEIGHT_TIERS:
+        raise ValueError("heights must be one of %s, not %r" % (HEIGHT_TIERS, tier))
+    if tier == "float32":
+        return dem_f32(dem, what), False
+    if tier == "auto":
+        return heights(dem, what)
+    a = np.asarray(dem)
+    d64 = np.ascontiguousarray(a, dtype=np.float64)
+    if a.dtype.kind in "iu" and a.dtype.itemsize == 8 and not (d64.astype(a.dtype) == a).all():
+        raise ValueError("%s of dtype %s holds values that float64 cannot represent" % (what, a.dtype))
+    return d64, True

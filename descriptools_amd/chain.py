@@ -10,7 +10,7 @@ from . import _lib, placement
 from ._lib import check
 from .device import Context
 
-F32, U8, I8, I32 = np.float32, np.uint8, np.int8, np.int32
+F32, F64, U8, I8, I32 = np.float32, np.float64, np.uint8, np.int8, np.int32
 
 OUTPUTS = (("slope", F32), ("fdr", U8), ("fac", I32), ("river", I8), ("fdist", F32), ("idx", I32),
            ("hand", F32), ("a_river", I32), ("slope_rad", F32), ("ti", F32), ("mti", F32), ("gfi", F32),
@@ -40,6 +40,23 @@ OPS = (
     ("flowhand_gfi_finish", 28, ["k_fh_tile3<false, 1, 5, int>"]),
 )
 
+# The step of a heights="float64" chain (same form as OPS).  The D8 kernel reads the DEM at 8 B/cell and writes the
+# codes and the float32 nodata proxy (1 + 4) that the flow-accumulation / HAND-index kernels read in place of the DEM
+# (they only test it for nodata: unchanged kernels).  Downslope reads dem 8 + fdr 1, writes 4.  The slope stencil
+# reads dem 8 + fac 4 and writes slope + TI + MTI (12).  HAND's last pass writes fdist + idx only (reading fdr 1 +
+# river 1: no heights); a last pass reads dem 8 + idx 4 + fac 4 and writes hand (float64, 8) + GFI + ln(hl/H) (8).
+OPS_F64 = (
+    ("d8", 13, ["k_d8_f64"]),
+    ("downslope", 13, ["k_downslope_win_f64"]),
+    ("flowacc_flowhand_local", 4 + 1 + 4 + 1 + 2, ["k_fa_tile1", "k_fa_reduce", "k_fa_poison", "k_fa3fh1<2>",
+                                                 "k_fh_tile1", "k_fh_ghost_init", "k_fh_node_jump"]),
+    ("slope_twi", 24, ["k_slope_twi_f64<false>"]),
+    ("flowhand_finish", 10, ["k_fh_tile3<false, 1, 5, int>"]),
+    ("hand_gfi", 32, ["k_hand_gfi_f64"]),
+)
+
+HEIGHTS = ("float32", "float64")
+
 
 class Chain:
     """Owns the output rasters of one H x W tile on one device."""
@@ -47,7 +64,7 @@ class Chain:
     def __init__(self, H, W, ctx=None, px=10.0, n_top=0.1, n_gfi=0.4, b=0.1, dz=5.0,
                  river_threshold=None, alloc=None, want_slope_rad=True, side_ctx=None, overlap=True,
                  condition=False, condition_rounds=64, tune_placement=True, release=None, long_walks=False,
-                 external_fdr=False):
+                 external_fdr=False, heights="float32"):
         # external_fdr: the D8 codes are GIVEN (a GIS tool's raster, as the reference's example reads one:
         # Example/example.py:36) -- the step has no D8 op; the caller writes the codes into buf["fdr"] (p("fdr")) first.
         # tune_placement: True (default) -- hand the blocks this chain allocates anyway to their roles by measured
@@ -68,8 +85,21 @@ class Chain:
         # finish_long_walks() -- a synchronisation point -- finishes them, with skip tables (25 B/cell more) only when
         # the raster has enough of them; run_host does this.  False: the plain kernel (the synthetic benchmark terrain
         # has no long walks).
+        # heights: "float32" (the default) -- the DEM given to run / ops / capture is an H x W float32 raster;
+        # "float64" -- an H x W float64 raster (a DEM float32 cannot hold: _lib.heights), every height difference taken
+        # in float64 as the reference takes it in the DEM's own dtype.  buf["hand"] is then float64 (the reference's
+        # HAND dtype on such a DEM); every other output keeps its dtype and meaning.  Out of scope on float64 heights:
+        # conditioning, long_walks (the skip tables are float32), tiling.RankTile / several GPUs.
+        if heights not in HEIGHTS:
+            raise ValueError("heights must be one of %s, not %r" % (HEIGHTS, heights))
+        self.wide = heights == "float64"
+        if self.wide and condition:
+            raise ValueError("condition=True is float32-only: conditioning on float64 heights is not implemented")
+        if self.wide and long_walks is not False:
+            raise ValueError("long_walks is float32-only: the float64 chain walks on its window kernel (long_walks=False)")
         assert long_walks in (False, True, "auto")
         assert not (external_fdr and condition), "conditioning computes the codes itself"
+        self.outputs = tuple((k, F64 if (self.wide and k == "hand") else dt) for k, dt in OUTPUTS)
         self.external_fdr = bool(external_fdr)
         self.long_walks = long_walks
         self._lift = self._lift_q = self._lift_dem = self._lift_tables = None
@@ -86,11 +116,14 @@ class Chain:
         self.river_threshold = self.N // 512 if river_threshold is None else int(river_threshold)
         self.buf = {}
         self._graphs = []
-        for name, dt in OUTPUTS + ((("filled", F32),) if self.condition else ()):
+        for name, dt in self.outputs + ((("filled", F32),) if self.condition else ()):
             self.buf[name] = alloc((H, W), dt) if alloc else self.ctx.empty((H, W), dt)
-        # the D8 kernel's nodata mask (one byte per four cells): what the accumulation pass needs of the DEM
-        self._nodata4 = None
-        if not (self.external_fdr or self.condition):
+        # the D8 kernel's nodata mask (one byte per four cells): what the accumulation pass needs of the DEM; on
+        # float64 heights the float32 nodata proxy the first kernel writes (dt_dev_slope_d8_f64)
+        self._nodata4 = self._proxy = None
+        if self.wide:
+            self._proxy = self.ctx.empty((H, W), F32)
+        elif not (self.external_fdr or self.condition):
             self._nodata4 = self.ctx.empty((int(_lib.lib().dt_nodata_mask_bytes(H, W)),), U8)
         assert tune_placement in (False, True, "search")
         self.placement = {"tuned": False, "why": "tune_placement=False"}
@@ -102,7 +135,7 @@ class Chain:
         conflict class of the device's memory (placement.py; measured with ~100 timed launches of a write-only kernel
         at set-up, skipped for rasters below 64 MiB).  With the chain's own allocator, or an `alloc` that comes with
         a `release`, further candidate blocks are tried when the first twelve are all alike."""
-        four = [name for name, dt in OUTPUTS if np.dtype(dt).itemsize == 4]
+        four = [name for name, dt in self.outputs if np.dtype(dt).itemsize == 4]
         objs = {}
         for name in four:
             b = self.buf[name]
@@ -134,7 +167,8 @@ class Chain:
                 b.free()
             else:
                 self._release(int(b.ptr.value if hasattr(b, "ptr") else b))
-        roles, info = placement.assign(self.ctx, self.N * 4, list(objs), [list(g) for g in WRITE_GROUPS],
+        groups = [[k for k in g if k in four] for g in WRITE_GROUPS]  # (float64 heights: hand has 8-byte cells)
+        roles, info = placement.assign(self.ctx, self.N * 4, list(objs), [g for g in groups if g],
                                        extra_alloc if can_grow else None, extra_release if can_grow else None,
                                        spacer_alloc=spacer_alloc if can_grow else None,
                                        spacer_release=spacer_release if can_grow else None, search=search)
@@ -148,7 +182,7 @@ class Chain:
                     break
         if roles is None:
             return
-        dts = dict(OUTPUTS)
+        dts = dict(self.outputs)
         for name, q in roles.items():
             b = objs[q]
             if hasattr(b, "dtype"):
@@ -212,6 +246,8 @@ class Chain:
         if getattr(self, "_full", None) is None:
             self._full = _lib.Window(H, W, W, 0, 0, H, W, 0)
         full = self._full
+        if self.wide:
+            return self._ops_f64(dem_ptr, want_a_river, side)
         rad = p("slope_rad") if self.want_slope_rad else None
         m4 = self._nodata4.ptr if self._nodata4 is not None else None
         first = ("d8", c, lambda: L.dt_dev_slope_d8_m(c.h, dem_ptr, H, W, self.px, p("fdr"), m4))
@@ -235,6 +271,31 @@ class Chain:
                 c.h, C.byref(full), dem_ptr, p("fdr"), p("river"), p("fac"), self.px, self.n_gfi, self.b, None, None,
                 None, None, None, None, p("fdist"), p("idx"), None, p("hand"),
                 p("a_river") if want_a_river else None, p("gfi"), p("lnhlh"))),
+        ]
+
+    def _ops_f64(self, dem_ptr, want_a_river, side):
+        """ops() of a heights="float64" chain (OPS_F64): the DEM pointer is a float64 raster.  The flow-accumulation /
+        HAND-index kernels are the float32 chain's, reading the nodata proxy in place of the DEM; HAND's last pass
+        writes fdist / idx only, and a pass of its own takes HAND in float64 and GFI / ln(hl/H) from it."""
+        L, c, H, W, p = _lib.lib(), self.ctx, self.H, self.W, self.p
+        prox = self._proxy.ptr
+        rad = p("slope_rad") if self.want_slope_rad else None
+        first = ("d8", c, lambda: L.dt_dev_slope_d8_f64(c.h, dem_ptr, H, W, self.px, p("fdr"), prox))
+        if self.external_fdr:  # the codes are given: the first kernel writes the proxy only
+            first = ("nodata_proxy", c, lambda: L.dt_dev_slope_d8_f64(c.h, dem_ptr, H, W, self.px, None, prox))
+        return [
+            first,
+            ("downslope", side, lambda: L.dt_dev_downslope_f64(side.h, dem_ptr, p("fdr"), H, W, self.px, self.dz, 0,
+                                                               p("down"))),
+            ("flowacc_flowhand_local", c, lambda: L.dt_dev_flowacc_river_flowhand_local(
+                c.h, p("fdr"), prox, H, W, self.river_threshold, p("fac"), p("river"))),
+            ("slope_twi", side, lambda: L.dt_dev_slope_twi_f64(side.h, dem_ptr, p("fac"), H, W, self.px, self.n_top,
+                                                               p("slope"), rad, p("ti"), p("mti"))),
+            ("flowhand_finish", c, lambda: L.dt_dev_flowhand_finish_w(
+                c.h, C.byref(self._full), None, p("fdr"), p("river"), p("fac"), self.px, None, None, None, None, None,
+                None, p("fdist"), p("idx"), None, None, p("a_river") if want_a_river else None)),
+            ("hand_gfi", c, lambda: L.dt_dev_hand_gfi_f64(c.h, dem_ptr, p("idx"), p("fac"), H, W, self.px, self.n_gfi,
+                                                          self.b, p("hand"), p("gfi"), p("lnhlh"))),
         ]
 
     def run(self, dem_ptr, want_a_river=True):
@@ -294,7 +355,7 @@ class Chain:
             if hasattr(b, "free"):
                 b.free()
         self.buf = {}
-        for name in ("_lift", "_lift_q", "_lift_tables", "_nodata4"):
+        for name in ("_lift", "_lift_q", "_lift_tables", "_nodata4", "_proxy"):
             if getattr(self, name) is not None:
                 getattr(self, name).free()
                 setattr(self, name, None)
@@ -324,20 +385,24 @@ class Graph:
         self.chain = None
 
 
-def run_host(dem, px, timings=None, **kw):
+def run_host(dem, px, timings=None, heights="float32", **kw):
     """Convenience: host DEM in, dict of host rasters out (fac / idx widened to int64 on the device).
-    timings (optional dict): filled with the seconds spent per phase (set-up, H2D, host blocks + copies, release)."""
+    timings (optional dict): filled with the seconds spent per phase (set-up, H2D, host blocks + copies, release).
+    heights: "float32" (default) -- float32-exact heights only (_lib.dem_f32: ValueError otherwise); "float64" -- the
+    float64 chain (Chain(heights="float64")): hand comes back as float64, long_walks defaults to False; "auto" -- the
+    float64 chain exactly when float32 cannot hold the DEM (_lib.heights, the drop-in functions' rule)."""
     import time
     t0 = time.perf_counter()
-    dem32 = _lib.dem_f32(dem)
-    H, W = dem32.shape
+    d, wide = _lib.dem_tier(dem, heights)
+    H, W = d.shape
     ctx = Context()
     kw.setdefault("tune_placement", False)  # one step: the ~0.1 s of measurement would buy 0.3 ms
-    kw.setdefault("long_walks", "auto")     # real terrain: long downslope walks are finished with skip tables
-    ch = Chain(H, W, ctx=ctx, px=px, **kw)
+    # real terrain: long downslope walks are finished with skip tables (float32 heights only)
+    kw.setdefault("long_walks", False if wide else "auto")
+    ch = Chain(H, W, ctx=ctx, px=px, heights="float64" if wide else "float32", **kw)
     t1 = time.perf_counter()
-    d_dem = ctx.to_device(dem32)
-    wide = {k: ctx.empty((H, W), np.int64) for k in ("fac", "idx")}  # the reference's dtypes for these are int64
+    d_dem = ctx.to_device(d)
+    widened = {k: ctx.empty((H, W), np.int64) for k in ("fac", "idx")}  # the reference's dtypes for these are int64
     t2 = t3 = t4 = time.perf_counter()
     try:
         ch.run(d_dem.ptr)
@@ -347,10 +412,10 @@ def run_host(dem, px, timings=None, **kw):
         # the cost of this call, not the kernels.  Copies are only enqueued: raster k crosses PCIe while the host
         # block of raster k + 1 is being mapped and touched; one synchronisation at the end.
         out = {}
-        for k, _ in OUTPUTS:
-            if k in wide:
-                check(_lib.lib().dt_dev_i32_to_i64(ctx.h, ch.buf[k].ptr, ch.N, wide[k].ptr))
-                out[k] = wide[k].to_host_async()
+        for k, _ in ch.outputs:
+            if k in widened:
+                check(_lib.lib().dt_dev_i32_to_i64(ctx.h, ch.buf[k].ptr, ch.N, widened[k].ptr))
+                out[k] = widened[k].to_host_async()
             else:
                 out[k] = ch.buf[k].to_host_async()
         t3 = time.perf_counter()
@@ -358,7 +423,7 @@ def run_host(dem, px, timings=None, **kw):
         t4 = time.perf_counter()
     finally:
         d_dem.free()
-        for w_ in wide.values():
+        for w_ in widened.values():
             w_.free()
         ch.free()
         ctx.close()

@@ -1082,6 +1082,44 @@ extern "C" int dt_dev_slope_d8_m(dt_ctx *c, const float *dem, int64_t H, int64_t
   DT_HIP(hipGetLastError());
   return DT_OK;
 }
+// ---- the resident chain on float64 heights ------------------------------------------------------------------------
+extern "C" int dt_dev_slope_d8_f64(dt_ctx *c, const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr,
+                                   float *proxy) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE(dem || H * W == 0, "NULL raster");
+  DT_TRY(dt_launch_d8_f64(c->stream, dem, H, W, px, fdr, nullptr, proxy));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_slope_twi_f64(dt_ctx *c, const double *dem, const int32_t *acc32, int64_t H, int64_t W,
+                                    double px, double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((dem && acc32 && ti && mti) || H * W == 0, "NULL raster");
+  DT_TRY(dt_launch_slope_twi_f64(c->stream, dem, acc32, H, W, px, n_top, slope, slope_rad, ti, mti));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_downslope_f64(dt_ctx *c, const double *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
+                                    double dz, int raw, float *out) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
+  DT_TRY(dt_launch_downslope_win_f64(c->stream, dem, fdr, H, W, px, dz, raw, out));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_hand_gfi_f64(dt_ctx *c, const double *dem, const int32_t *idx32, const int32_t *acc32, int64_t H,
+                                   int64_t W, double px, double n_gfi, double b, double *hand, float *gfi,
+                                   float *lnhlh) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((dem && idx32 && acc32 && hand) || H * W == 0, "NULL raster");
+  DT_TRY(dt_launch_hand_gfi_f64(c->stream, dem, idx32, acc32, H * W, n_gfi, b, px, hand, gfi, lnhlh));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
 extern "C" int dt_dev_flowacc_finish_w(dt_ctx *c, const dt_window *win, const uint8_t *fdr, const float *dem,
                                        const uint64_t *ext_perim, int64_t threshold, int32_t *acc32,
                                        int8_t *river) {
@@ -1671,6 +1709,26 @@ extern "C" int dt_slope_f64(const double *dem, int64_t H, int64_t W, double px, 
   DT_TRY(dt_launch_slope_f64(c->stream, d_d.as<double>(), H, W, px, d_s.as<float>()));
   DT_HIP(hipGetLastError());
   D2H(slope, d_s, n * 4, c);
+  return dt_ctx_sync(c);
+}
+extern "C" int dt_d8_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *slope) {
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  dt_ctx *c;
+  DT_TRY(host_ctx(&c));
+  DT_TRY(dt_check_hw(H, W));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem && fdr, "NULL raster");
+  DevBuf d_d, d_f, d_s;
+  DT_TRY(d_d.alloc(n * 8));
+  DT_TRY(d_f.alloc(n));
+  if (slope) DT_TRY(d_s.alloc(n * 4));
+  H2D(d_d, dem, n * 8, c);
+  DT_TRY(dt_launch_d8_f64(c->stream, d_d.as<double>(), H, W, px, d_f.as<uint8_t>(), slope ? d_s.as<float>() : nullptr,
+                          nullptr));
+  DT_HIP(hipGetLastError());
+  D2H(fdr, d_f, n, c);
+  if (slope) D2H(slope, d_s, n * 4, c);
   return dt_ctx_sync(c);
 }
 extern "C" int dt_hand_f64(const double *dem, const int64_t *idx, int64_t N, double *hand) {

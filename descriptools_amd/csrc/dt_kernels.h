@@ -55,6 +55,16 @@ int dt_launch_downslope_f64(hipStream_t s, const double *dem, const uint8_t *fdr
                             double dz, int raw, float *out);
 int dt_launch_gfi_f64h(hipStream_t s, const double *hand, const int64_t *fac, const int64_t *idx, int64_t n,
                        double expo, double b, double size, int own_area, float *out);
+// the resident chain's float64 tier: D8 + exact slope + nodata proxy and slope + TI + MTI (dt_stencil.hip), windowed
+// downslope and HAND + GFI + ln(hl/H) (dt_wide.hip)
+int dt_launch_d8_f64(hipStream_t s, const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *slope,
+                     float *proxy);
+int dt_launch_slope_twi_f64(hipStream_t s, const double *dem, const int32_t *acc32, int64_t H, int64_t W, double px,
+                            double n_top, float *slope, float *slope_rad, float *ti, float *mti);
+int dt_launch_downslope_win_f64(hipStream_t s, const double *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
+                                double dz, int raw, float *out);
+int dt_launch_hand_gfi_f64(hipStream_t s, const double *dem, const int32_t *idx32, const int32_t *acc32, int64_t n,
+                           double expo, double b, double size, double *hand, float *gfi, float *lnhlh);
 int dt_launch_confusion(hipStream_t s, const double *desc, const int8_t *flood, int64_t n,
                         double nodata, const double *th_host, int nth, int under,
                         unsigned long long *counts4);

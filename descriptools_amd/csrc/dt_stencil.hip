@@ -894,3 +894,219 @@ int dt_launch_stencil(hipStream_t s, const DtWin &w, const float *dem, double px
 #undef DT_GO
   return DT_OK;
 }
+
+// ===========================================================================================
+// The same stencils on float64 heights (the resident chain's heights="float64" tier; dt_capi.hip dt_dev_*_f64).
+//
+// Tile = 64 columns x 16 rows per 256-thread workgroup, staged with its 1-cell halo through LDS as doubles (18 x 66
+// x 8 B = 9.3 KiB: the LDS is not what limits occupancy); every load of a thread is issued before the first LDS
+// store.  Lane tx owns column tx of the tile, wave ty rows 4 ty .. 4 ty + 3 (a wave's row of stores is 64 cells:
+// 256 B of float32, 64 B of codes).  Cells outside the raster are staged as -100, the reference's ring (slope.py:175),
+// so the neighbour rule "nb == -100: skipped" (slope.py:247) covers them.  Heights are the DEM's own values: only
+// z <= -100 is nodata (no NaN / inf sentinel handling).
+// ===========================================================================================
+#define SW_TX 64
+#define SW_TY 16
+#define SW_LDW (SW_TX + 2)
+
+__device__ __forceinline__ void sw_stage(double *t, const double *__restrict__ dem, int H, int W, int x0, int y0) {
+  constexpr int N = (SW_TY + 2) * SW_LDW, NV = (N + 255) / 256;
+  double v[NV];
+#pragma unroll
+  for (int u = 0; u < NV; u++) {
+    const int i = (int)threadIdx.x + 256 * u;
+    const int r = i / SW_LDW, c = i - r * SW_LDW;
+    const int gy = y0 - 1 + r, gx = x0 - 1 + c;
+    v[u] = -100.0;
+    if (i < N && gy >= 0 && gy < H && gx >= 0 && gx < W) v[u] = dem[(long long)gy * W + gx];
+  }
+#pragma unroll
+  for (int u = 0; u < NV; u++) {
+    const int i = (int)threadIdx.x + 256 * u;
+    if (i < N) t[i] = v[u];
+  }
+}
+
+// the eight neighbours of tile cell (r, c) in scan order NW, N, NE, W, E, SW, S, SE
+__device__ __forceinline__ void sw_nbrs(const double *t, int r, int c, double (&nb)[8]) {
+  const double *p = &t[(r + 1) * SW_LDW + c + 1];
+  nb[0] = p[-SW_LDW - 1];
+  nb[1] = p[-SW_LDW];
+  nb[2] = p[-SW_LDW + 1];
+  nb[3] = p[-1];
+  nb[4] = p[1];
+  nb[5] = p[SW_LDW - 1];
+  nb[6] = p[SW_LDW];
+  nb[7] = p[SW_LDW + 1];
+}
+__device__ __forceinline__ bool sw_diag(int k) { return k == 0 || k == 2 || k == 5 || k == 7; }
+
+// Largest cardinal and largest diagonal difference c - nb over the neighbours that count (nb != -100); 0 when none is
+// positive.  A strict `>` skips NaN as the reference's `aux < v` does.  Division by a positive constant is monotone, so
+// the largest quotient of a class is its largest difference divided once.
+__device__ __forceinline__ void sw_class_max(double c, const double (&nb)[8], double &dc, double &dd) {
+  dc = 0.0;
+  dd = 0.0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const double d = c - nb[k];
+    const bool ok = nb[k] != -100.0;
+    if (sw_diag(k)) dd = (ok && d > dd) ? d : dd;
+    else dc = (ok && d > dc) ? d : dc;
+  }
+}
+
+// D8 code of the literal definition (flowdir.d8, N1, with float64 differences): the first neighbour in
+// scan order whose quotient equals the maximum v > 0.  The quotient is not injective (two differences may round to
+// the same value), so a neighbour other than its class's largest difference can still be the first to reach v: it is
+// divided whenever its difference lies within 1e-15 (relative) of the class maximum -- equal float64 quotients of
+// one divisor are within 2^-52 of each other -- which on real terrain is essentially never.
+__device__ __forceinline__ uint32_t sw_d8_code(double c, const double (&nb)[8], double dc, double dd, double qc,
+                                               double qd, double dcard, double ddiag) {
+  const uint8_t CODE[8] = {32, 64, 128, 16, 1, 8, 4, 2};
+  const double v = qc > qd ? qc : qd;
+  uint32_t code = 0u;
+  if (!(v > 0.0)) return 0u;
+#pragma unroll
+  for (int k = 7; k >= 0; k--) {  // backwards: the last assignment is the first match in scan order
+    const bool dg = sw_diag(k);
+    const double best = dg ? dd : dc, q = dg ? qd : qc, d = c - nb[k];
+    if (nb[k] == -100.0 || !(d > 0.0) || q != v) continue;
+    bool hit = d == best;
+    if (!hit && (best == __builtin_inf() || d >= best * (1.0 - 1e-15))) hit = d / (dg ? ddiag : dcard) == v;
+    code = hit ? (uint32_t)CODE[k] : code;
+  }
+  return code;
+}
+
+// D8 (fdr, may be NULL), the exact slope % (may be NULL) and the float32 nodata proxy (may be NULL): -100 where
+// z <= -100, otherwise (float)z kept above -100 (NaN stays NaN).  What the flow-accumulation kernels need of the DEM
+// is exactly that nodata test, so they run unchanged on the proxy.
+__global__ __launch_bounds__(256) void k_d8_f64(const double *__restrict__ dem, int H, int W, double px,
+                                                uint8_t *__restrict__ fdr, float *__restrict__ slope,
+                                                float *__restrict__ proxy) {
+  __shared__ double t[(SW_TY + 2) * SW_LDW];
+  const int x0 = (int)blockIdx.x * SW_TX, y0 = (int)blockIdx.y * SW_TY;
+  sw_stage(t, dem, H, W, x0, y0);
+  __syncthreads();
+  const int tx = (int)threadIdx.x & 63, ty = (int)threadIdx.x >> 6;
+  const int gx = x0 + tx;
+  if (gx >= W) return;
+  const double dcard = px, ddiag = px * sqrt(2.0);
+  const float above = -99.99999237060547f;  // the float32 value next to -100 towards 0
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = ty * 4 + j, gy = y0 + r;
+    if (gy >= H) break;
+    const double c = t[(r + 1) * SW_LDW + tx + 1];
+    const long long o = (long long)gy * W + gx;
+    const bool nod = c <= -100.0;  // slope.py:231
+    double nb[8];
+    sw_nbrs(t, r, tx, nb);
+    double dc, dd;
+    sw_class_max(c, nb, dc, dd);
+    const double qc = dc > 0.0 ? dc / dcard : 0.0, qd = dd > 0.0 ? dd / ddiag : 0.0;
+    if (fdr) {
+      uint32_t code = nod ? 0u : sw_d8_code(c, nb, dc, dd, qc, qd, dcard, ddiag);
+      if (code == 0u && !nod)  // N1 border rule
+        code = gy == H - 1 ? 4u : (gy == 0 ? 64u : (gx == 0 ? 16u : (gx == W - 1 ? 1u : 0u)));
+      fdr[o] = (uint8_t)code;
+    }
+    if (slope) slope[o] = nod ? DT_NODATA : (float)((qc > qd ? qc : qd) * 100.0);  // slope.py:259
+    if (proxy) {
+      const float f = (float)c;
+      proxy[o] = nod ? DT_NODATA : (f <= DT_NODATA ? above : f);
+    }
+  }
+}
+
+// slope + TI + MTI (+ radians) on float64 heights: the float32 kernel's per-cell math (k_slope_twi) from the class
+// maxima of the float64 differences -- the same product-form slope and its rounding test (sd_slope_fast), the same
+// sd_twi_fast and its flags -- and the cold path of k_slope_twi_fix (exact divisions, dt_slope_rad, dt_twi_cell) for
+// the flagged cells, in place: they are a handful per raster.  On heights that are float32 values the class maxima are
+// the float32 kernel's, so every cell takes the same path there and comes out bit for bit the same.
+template <bool W_RAD>
+__global__ __launch_bounds__(256) void k_slope_twi_f64(const double *__restrict__ dem, int H, int W, double px,
+                                                       double kc, double kd, const int32_t *__restrict__ acc32,
+                                                       double n_top, double lnpx2, float *__restrict__ slope,
+                                                       float *__restrict__ slope_rad, float *__restrict__ ti,
+                                                       float *__restrict__ mti, const DtLogEntry *__restrict__ g_tab) {
+  __shared__ double t[(SW_TY + 2) * SW_LDW];
+  const int x0 = (int)blockIdx.x * SW_TX, y0 = (int)blockIdx.y * SW_TY;
+  sw_stage(t, dem, H, W, x0, y0);
+  __syncthreads();
+  const int tx = (int)threadIdx.x & 63, ty = (int)threadIdx.x >> 6;
+  const int gx = x0 + tx;
+  if (gx >= W) return;
+  const double nlnpx2 = n_top * lnpx2;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = ty * 4 + j, gy = y0 + r;
+    if (gy >= H) break;
+    const long long o = (long long)gy * W + gx;
+    const int32_t f = acc32[o];
+    const double c = t[(r + 1) * SW_LDW + tx + 1];
+    double nb[8];
+    sw_nbrs(t, r, tx, nb);
+    double dc, dd;
+    sw_class_max(c, nb, dc, dd);
+    // sd_slope_fast on the class maxima
+    const double qp = dc * kc > dd * kd ? dc * kc : dd * kd;
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(qp);
+    const uint32_t lo = (uint32_t)bits, hi = (uint32_t)(bits >> 32);
+    const bool near_mid = ((lo & 0x1FFFFFFFu) - (0x10000000u - SD_MID)) <= 2u * SD_MID;
+    const bool odd = ((hi >> 20) - 897u) > 253u && bits != 0ull;
+    bool flag = near_mid || odd;
+    float sl = (float)qp, rad = 0.0f, tv, mv;
+    const bool snod = c <= -100.0;  // slope.py:231
+    sl = snod ? DT_NODATA : sl;
+    flag = flag && !snod;
+    const float q = dt_pct_to_tan(sl);
+    const bool rnod = c == -100.0;
+    if (W_RAD) {
+      rad = rnod ? DT_NODATA : (float)dt_atanf_pos(q);
+      flag = flag || (!rnod && !(q >= 0.0f && q < 1e30f));
+    }
+    const bool tnod = f <= -100;  // topoindexes.py:252
+    flag = (sd_twi_fast(f, q, n_top, lnpx2, nlnpx2, tv, mv) && !tnod) || flag;
+    tv = tnod ? DT_NODATA : tv;
+    mv = tnod ? DT_NODATA : mv;
+    if (flag) {  // k_slope_twi_fix's exact path
+      const double dcard = px, ddiag = px * sqrt(2.0);
+      const double qc = dc > 0.0 ? dc / dcard : 0.0, qd = dd > 0.0 ? dd / ddiag : 0.0;
+      sl = snod ? DT_NODATA : (float)((qc > qd ? qc : qd) * 100.0);
+      rad = dt_slope_rad(sl, rnod ? DT_NODATA : 0.0f);
+      dt_twi_cell((int64_t)f, rad, lnpx2, n_top, tv, mv, g_tab);
+    }
+    if (slope) slope[o] = sl;
+    if (W_RAD) slope_rad[o] = rad;
+    ti[o] = tv;
+    mti[o] = mv;
+  }
+}
+
+int dt_launch_d8_f64(hipStream_t s, const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *slope,
+                     float *proxy) {
+  if (H == 0 || W == 0) return DT_OK;
+  const dim3 g((unsigned)((W + SW_TX - 1) / SW_TX), (unsigned)((H + SW_TY - 1) / SW_TY));
+  DT_REQUIRE(g.y < 65536u, "raster too tall for one launch");
+  hipLaunchKernelGGL(k_d8_f64, g, dim3(256), 0, s, dem, (int)H, (int)W, px, fdr, slope, proxy);
+  return DT_OK;
+}
+
+int dt_launch_slope_twi_f64(hipStream_t s, const double *dem, const int32_t *acc32, int64_t H, int64_t W, double px,
+                            double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
+  if (H == 0 || W == 0) return DT_OK;
+  const dim3 g((unsigned)((W + SW_TX - 1) / SW_TX), (unsigned)((H + SW_TY - 1) / SW_TY));
+  DT_REQUIRE(g.y < 65536u, "raster too tall for one launch");
+  // the float32 kernel's constants, computed the same way (launch_slope_twi)
+  const double kc = 100.0 / px, kd = 100.0 / (px * sqrt(2.0)), lnpx2 = log(px * px);
+  const DtLogEntry *g_tab = dt_math_device_table(s);
+  if (slope_rad)
+    hipLaunchKernelGGL(k_slope_twi_f64<true>, g, dim3(256), 0, s, dem, (int)H, (int)W, px, kc, kd, acc32, n_top, lnpx2,
+                       slope, slope_rad, ti, mti, g_tab);
+  else
+    hipLaunchKernelGGL(k_slope_twi_f64<false>, g, dim3(256), 0, s, dem, (int)H, (int)W, px, kc, kd, acc32, n_top,
+                       lnpx2, slope, slope_rad, ti, mti, g_tab);
+  return DT_OK;
+}

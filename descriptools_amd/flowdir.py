@@ -4,15 +4,21 @@ pit; a raster-border cell with no lower neighbour drains outward."""
 import numpy as np
 
 from . import _lib
-from ._lib import c_f32p, c_u8p, check, dem_f32, ptr
+from ._lib import c_f32p, c_f64p, c_u8p, check, dem_f32, ptr
 
 
-def d8(dem, px, return_slope=False):
-    dem32 = dem_f32(dem)
-    H, W = dem32.shape
+def d8(dem, px, return_slope=False, heights="float32"):
+    """heights: "float32" (default) -- float32-exact heights only (ValueError otherwise); "float64" -- the
+    differences taken in float64 (dt_d8_f64; slope as slope.sloper gives it on such a DEM); "auto" -- float64 exactly
+    when float32 cannot hold the DEM (_lib.heights)."""
+    d, wide = _lib.dem_tier(dem, heights)
+    H, W = d.shape
     fdr = np.empty((H, W), np.uint8)
     sl = np.empty((H, W), np.float32) if return_slope else None
-    check(_lib.lib().dt_d8_f32(ptr(dem32, c_f32p), H, W, float(px), ptr(fdr, c_u8p), ptr(sl, c_f32p)))
+    if wide:
+        check(_lib.lib().dt_d8_f64(ptr(d, c_f64p), H, W, float(px), ptr(fdr, c_u8p), ptr(sl, c_f32p)))
+    else:
+        check(_lib.lib().dt_d8_f32(ptr(d, c_f32p), H, W, float(px), ptr(fdr, c_u8p), ptr(sl, c_f32p)))
     return (fdr, sl) if return_slope else fdr
 
 

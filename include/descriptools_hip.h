@@ -190,6 +190,11 @@ int dt_downslope_f64(const double *dem, const uint8_t *fdr, int64_t H, int64_t W
 int dt_gfi_f64h(const double *hand, const int64_t *fac, const int64_t *idx, int64_t N, double n_gfi,
                 double scale_factor, double size, int own_area, float *out);
 
+/* D8 (flowdir.d8's definition, N1) with the differences taken in float64: codes of the first strict maximum of
+ * (z - z_nb) / d in scan order NW, N, NE, W, E, SW, S, SE, the raster-border rule, nodata z <= -100; slope (may be
+ * NULL) as dt_slope_f64 */
+int dt_d8_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *slope);
+
 /* evaluation.binary_map + avaliacao for `nth` thresholds in one pass (evaluation.py:90-171):
  * counts4[t*4 + v] = #cells with binary(desc, th[t]) + remapped(flood) == v, v = 0..3.
  * Cells equal to `nodata_value` (the caller passes desc[0,0], evaluation.py:111) or NaN
@@ -261,6 +266,23 @@ int64_t dt_nodata_mask_bytes(int64_t H, int64_t W);
 int dt_dev_slope_d8_m(dt_ctx *ctx, const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr, uint8_t *nodata4);
 int dt_dev_flowacc_river_flowhand_local_m(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const uint8_t *nodata4,
                                           int64_t H, int64_t W, int64_t threshold, int32_t *acc32, int8_t *river);
+/* The resident chain on float64 heights (descriptools_amd.chain.Chain(heights="float64")); `dem` is an H x W double
+ * raster on the device.  Out of scope: conditioning, ranks (dt_window), the long-walk skip tables.
+ * dt_dev_slope_d8_f64: D8 codes as dt_d8_f64 (fdr may be NULL), and the float32 nodata proxy (may be NULL): -100 where
+ * z <= -100, otherwise (float)z kept above -100 -- what the flow-accumulation / HAND-index entry points
+ * (dt_dev_flowacc_river_flowhand_local, dt_dev_flowhand_finish_w with dem = hand = NULL) need of the DEM.
+ * dt_dev_slope_twi_f64: dt_dev_slope_twi with the slope (slope.py:244-259) taken from float64 differences.
+ * dt_dev_downslope_f64: dt_downslope_f64 on device rasters, staged through LDS windows.
+ * dt_dev_hand_gfi_f64: HAND in float64 (flowhand.py:436-438) from the int32 river index, GFI (A = acc32[idx]) and
+ * ln(hl/H) (the cell's own acc32, 0 -> 1) from it; gfi / lnhlh may be NULL; size = px. */
+int dt_dev_slope_d8_f64(dt_ctx *ctx, const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *proxy);
+int dt_dev_slope_twi_f64(dt_ctx *ctx, const double *dem, const int32_t *acc32, int64_t H, int64_t W, double px,
+                         double n_top, float *slope, float *slope_rad, float *ti, float *mti);
+int dt_dev_downslope_f64(dt_ctx *ctx, const double *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
+                         double elevation_difference, int raw, float *out);
+int dt_dev_hand_gfi_f64(dt_ctx *ctx, const double *dem, const int32_t *idx32, const int32_t *acc32, int64_t H,
+                        int64_t W, double px, double n_gfi, double scale_factor, double *hand, float *gfi,
+                        float *lnhlh);
 int dt_dev_river_mask(dt_ctx *ctx, const int32_t *acc32, int64_t N, int64_t threshold,
                       int8_t *river);
 /* idx32: local flat index of the drained-to river cell (int32), -100 = none; a_river (may be
