@@ -89,12 +89,15 @@ class Chain:
         # "float64" -- an H x W float64 raster (a DEM float32 cannot hold: _lib.heights), every height difference taken
         # in float64 as the reference takes it in the DEM's own dtype.  buf["hand"] is then float64 (the reference's
         # HAND dtype on such a DEM); every other output keeps its dtype and meaning.  Out of scope on float64 heights:
-        # conditioning, long_walks (the skip tables are float32), tiling.RankTile / several GPUs.
+        # condition=True (conditioned codes come in through external_fdr: dt_dev_condition_d8_f64_async), long_walks
+        # (the skip tables are float32), tiling.RankTile / several GPUs.
         if heights not in HEIGHTS:
             raise ValueError("heights must be one of %s, not %r" % (HEIGHTS, heights))
         self.wide = heights == "float64"
         if self.wide and condition:
-            raise ValueError("condition=True is float32-only: conditioning on float64 heights is not implemented")
+            raise ValueError("condition=True is float32-only in Chain: on float64 heights condition the codes with "
+                             "dt_dev_condition_d8_f64_async into Chain(heights=\"float64\", external_fdr=True)'s "
+                             "p(\"fdr\") (INTEGRATION.md), or use run_host(..., heights=\"float64\", condition=True)")
         if self.wide and long_walks is not False:
             raise ValueError("long_walks is float32-only: the float64 chain walks on its window kernel (long_walks=False)")
         assert long_walks in (False, True, "auto")
@@ -390,11 +393,23 @@ def run_host(dem, px, timings=None, heights="float32", **kw):
     timings (optional dict): filled with the seconds spent per phase (set-up, H2D, host blocks + copies, release).
     heights: "float32" (default) -- float32-exact heights only (_lib.dem_f32: ValueError otherwise); "float64" -- the
     float64 chain (Chain(heights="float64")): hand comes back as float64, long_walks defaults to False; "auto" -- the
-    float64 chain exactly when float32 cannot hold the DEM (_lib.heights, the drop-in functions' rule)."""
+    float64 chain exactly when float32 cannot hold the DEM (_lib.heights, the drop-in functions' rule).
+    condition=True on the float64 tier: the codes are conditioned in float64 (dt_dev_condition_d8_f64_async,
+    `condition_rounds` rounds, default 64) and fed to a Chain(heights="float64", external_fdr=True) -- the resident
+    recipe of INTEGRATION.md; the same keys come back as on the float32 tier."""
     import time
     t0 = time.perf_counter()
     d, wide = _lib.dem_tier(dem, heights)
     H, W = d.shape
+    cond64 = None  # the float64 tier's conditioning rounds, when it conditions
+    if wide:  # (out-of-scope arguments are refused before any device work)
+        if kw.get("long_walks", False) is not False:
+            raise ValueError("long_walks is float32-only: the float64 chain walks on its window kernel (long_walks=False)")
+        if kw.pop("condition", False):
+            if kw.get("external_fdr"):
+                raise ValueError("condition=True computes the codes itself: external_fdr must be False")
+            cond64 = int(kw.pop("condition_rounds", 64))
+            kw["external_fdr"] = True
     ctx = Context()
     kw.setdefault("tune_placement", False)  # one step: the ~0.1 s of measurement would buy 0.3 ms
     # real terrain: long downslope walks are finished with skip tables (float32 heights only)
@@ -403,10 +418,16 @@ def run_host(dem, px, timings=None, heights="float32", **kw):
     t1 = time.perf_counter()
     d_dem = ctx.to_device(d)
     widened = {k: ctx.empty((H, W), np.int64) for k in ("fac", "idx")}  # the reference's dtypes for these are int64
+    filled = ctx.empty((H, W), np.float64) if cond64 is not None else None
     t2 = t3 = t4 = time.perf_counter()
     try:
+        if filled is not None:
+            check(_lib.lib().dt_dev_condition_d8_f64_async(ctx.h, d_dem.ptr, H, W, float(px), filled.ptr, ch.p("fdr"),
+                                                           cond64))
         ch.run(d_dem.ptr)
         ch.check_status()  # (condition=True: raises when the budget of conditioning rounds was too small)
+        if filled is not None:
+            filled.free()
         ch.finish_long_walks()
         # rasters come back into page-locked host memory from a recycling pool (device.PinnedPool): the copies are
         # the cost of this call, not the kernels.  Copies are only enqueued: raster k crosses PCIe while the host
@@ -425,6 +446,8 @@ def run_host(dem, px, timings=None, heights="float32", **kw):
         d_dem.free()
         for w_ in widened.values():
             w_.free()
+        if filled is not None:
+            filled.free()
         ch.free()
         ctx.close()
     if timings is not None:

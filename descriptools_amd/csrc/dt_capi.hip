@@ -456,6 +456,39 @@ extern "C" int dt_dev_condition_d8_async(dt_ctx *c, const float *dem, int64_t H,
   return DT_OK;
 }
 
+// ... on float64 heights: dt_dev_condition_d8 / dt_dev_condition_d8_async with a float64 DEM and filled surface
+extern "C" int dt_dev_condition_d8_f64(dt_ctx *c, const double *dem, int64_t H, int64_t W, double px, double *filled,
+                                       uint8_t *fdr, int32_t *info3) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((dem && filled) || H * W == 0, "NULL raster");
+  size_t need = dt_hydro_scratch(H, W);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  int unresolved = 0, rounds[2] = {0, 0};
+  DT_TRY(dt_launch_condition_f64(c->stream, dem, H, W, px, filled, fdr, scr, &unresolved, rounds));
+  DT_HIP(hipGetLastError());
+  if (info3) {
+    info3[0] = unresolved;
+    info3[1] = rounds[0];
+    info3[2] = rounds[1];
+  }
+  return DT_OK;
+}
+
+extern "C" int dt_dev_condition_d8_f64_async(dt_ctx *c, const double *dem, int64_t H, int64_t W, double px,
+                                             double *filled, uint8_t *fdr, int rounds) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((dem && filled && fdr) || H * W == 0, "NULL raster");
+  size_t need = dt_hydro_scratch(H, W);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  DT_TRY(dt_launch_condition_async_f64(c->stream, dem, H, W, px, filled, fdr, scr, rounds, c->status));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
 extern "C" int dt_dev_condition_stage_w(dt_ctx *c, const dt_window *win, int stage, int rounds, const float *dem,
                                         float *filled, uint8_t *fdr, uint32_t *dist, int32_t *flag_dev) {
   DT_CTX(c);
@@ -1956,5 +1989,25 @@ extern "C" int dt_d8_conditioned_f32(const float *dem, int64_t H, int64_t W, dou
   DT_TRY(dt_dev_condition_d8(c, d_dem.as<float>(), H, W, px, d_w.as<float>(), d_f.as<uint8_t>(), info3));
   D2H(fdr, d_f, n, c);
   if (filled) D2H(filled, d_w, n * 4, c);
+  return dt_ctx_sync(c);
+}
+// ... on float64 heights: dt_d8_conditioned_f32's definition with the heights compared in float64
+extern "C" int dt_d8_conditioned_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, double *filled,
+                                     int32_t *info3) {
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  dt_ctx *c;
+  DT_TRY(host_ctx(&c));
+  DT_TRY(dt_check_hw(H, W));
+  size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem && fdr, "NULL raster");
+  DevBuf d_dem, d_w, d_f;
+  DT_TRY(d_dem.alloc(n * 8));
+  DT_TRY(d_w.alloc(n * 8));
+  DT_TRY(d_f.alloc(n));
+  H2D(d_dem, dem, n * 8, c);
+  DT_TRY(dt_dev_condition_d8_f64(c, d_dem.as<double>(), H, W, px, d_w.as<double>(), d_f.as<uint8_t>(), info3));
+  D2H(fdr, d_f, n, c);
+  if (filled) D2H(filled, d_w, n * 8, c);
   return dt_ctx_sync(c);
 }

@@ -62,24 +62,47 @@ __device__ __forceinline__ float hy_max2(float a, float b) {
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+// ... and on float64 heights (the float64 tier, k_fill_relax_f64): the same definitions.  A DPP move shifts 32 bits,
+// so a double crosses lanes as its two halves; gfx950 has no three-operand f64 minimum, so hy_min3 is two v_min_f64.
+__device__ __forceinline__ bool hy_nodata(double z) { return z == (double)DT_NODATA; }
+template <int CTRL>
+__device__ __forceinline__ double hy_dpp_f64(double edge, double v) {
+  const long long e = __double_as_longlong(edge), x = __double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)e, (int)x, CTRL, 0xF, 0xF, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(e >> 32), (int)(x >> 32), CTRL, 0xF, 0xF, false);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+__device__ __forceinline__ double hy_from_prev_lane(double edge, double v) { return hy_dpp_f64<0x138>(edge, v); }
+__device__ __forceinline__ double hy_from_next_lane(double edge, double v) { return hy_dpp_f64<0x130>(edge, v); }
+__device__ __forceinline__ double hy_min2(double a, double b) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ double hy_min3(double a, double b, double c) { return hy_min2(hy_min2(a, b), c); }
+__device__ __forceinline__ double hy_max2(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
 // One directional in-place sweep of the fill over the tile in LDS (see k_fill_relax): BY_ROWS: a lane per column, the
 // sweep walks rows; DIR: +1 from the first line to the last, -1 back.  Direction and strides are template parameters
 // so that every LDS address of a step is the running position plus an immediate offset (with run-time strides a step
 // spent five instructions on address arithmetic).  Returns bit 0: the sweep lowered something; bit 1: on the tile's
-// outer ring -- the cells the neighbouring tiles read as their halo.
-template <bool BY_ROWS, int DIR>
-__device__ __forceinline__ int hy_fill_sweep(float *__restrict__ s_w, const float *__restrict__ s_z, int lane) {
+// outer ring -- the cells the neighbouring tiles read as their halo.  T: float, or double on the float64 tier.
+template <bool BY_ROWS, int DIR, typename T>
+__device__ __forceinline__ int hy_fill_sweep(T *__restrict__ s_w, const T *__restrict__ s_z, int lane) {
   constexpr int SA = BY_ROWS ? DIR * HLS : DIR;  // one step along the sweep
   constexpr int SC = BY_ROWS ? 1 : HLS;          // one lane across it
   constexpr int ZA = BY_ROWS ? DIR * HZS : DIR;
   constexpr int K0 = DIR < 0 ? HT - 1 : 0;
   int p = BY_ROWS ? (K0 + 1) * HLS + lane + 1 : (lane + 1) * HLS + K0 + 1;
   int zi = BY_ROWS ? K0 * HZS + lane : lane * HZS + K0;
-  float up = s_w[p - SA];                              // the line before the tile (halo: nobody writes it)
-  float hl = s_w[p - SA - SC], hr = s_w[p - SA + SC];  // its cells beside lanes 0 / 63
-  float cur = s_w[p], lf = s_w[p - SC], rt = s_w[p + SC];
+  T up = s_w[p - SA];                              // the line before the tile (halo: nobody writes it)
+  T hl = s_w[p - SA - SC], hr = s_w[p - SA + SC];  // its cells beside lanes 0 / 63
+  T cur = s_w[p], lf = s_w[p - SC], rt = s_w[p + SC];
   const bool on_side = lane == 0 || lane == HT - 1;
-  auto *s_wv = (__attribute__((address_space(3))) const float *)s_w;
+  auto *s_wv = (__attribute__((address_space(3))) const T *)s_w;
   asm volatile("" : "+v"(s_wv));
   int ch = 0;
 #pragma unroll 4
@@ -87,12 +110,12 @@ __device__ __forceinline__ int hy_fill_sweep(float *__restrict__ s_w, const floa
     // (through a copy of the base address the compiler cannot see through, made once per sweep: another wave may have
     // lowered the cell since this lane fetched it as the line ahead, and with compile-time strides the compiler would
     // reuse that value -- a store could then RAISE the cell)
-    const float fresh = s_wv[p];
-    const float d0 = s_w[p + SA - SC], d1 = s_w[p + SA], d2 = s_w[p + SA + SC];
-    const float zc = s_z[zi];
-    const float upm = hy_from_prev_lane(hl, up), upp = hy_from_next_lane(hr, up);
-    const float m = hy_min2(hy_min3(hy_min3(upm, up, upp), lf, rt), hy_min3(d0, d1, d2));
-    const float nw = hy_max2(zc, m);
+    const T fresh = s_wv[p];
+    const T d0 = s_w[p + SA - SC], d1 = s_w[p + SA], d2 = s_w[p + SA + SC];
+    const T zc = s_z[zi];
+    const T upm = hy_from_prev_lane(hl, up), upp = hy_from_next_lane(hr, up);
+    const T m = hy_min2(hy_min3(hy_min3(upm, up, upp), lf, rt), hy_min3(d0, d1, d2));
+    const T nw = hy_max2(zc, m);
     const bool valid = !hy_nodata(zc);
     if (valid && nw < fresh) {  // (a value equal to its height cannot get lower: nw >= zc)
       s_w[p] = nw;
@@ -250,6 +273,60 @@ __device__ __forceinline__ void hy_stage2(TA *sa, const TA *__restrict__ a, TA o
   } else {
     hy_stage_slow<TA>(sa, a, w, y0, x0, outside_a);
     hy_stage_slow<TB>(sb, b, w, y0, x0, outside_b);
+  }
+}
+
+// ... on float64 heights (k_fill_relax_f64, k_flat_init_f64): the same window of 8-byte cells.  The core rows go as
+// 16-byte loads of two doubles (eight per thread), the ring as one or two 8-byte loads.  A row of doubles is 8-byte
+// aligned, and global memory takes a 16-byte access there (as it does at 4-byte addresses above).
+typedef double hy_v2d_a8 __attribute__((ext_vector_type(2), aligned(8)));
+struct HyTileRegs64 {
+  hy_v2d_a8 c[8];
+  double r1, r2;
+};
+__device__ __forceinline__ void hy_tile_load64(HyTileRegs64 &t, const double *__restrict__ src, const DtWin &w, int y0,
+                                               int x0) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int i = (int)threadIdx.x + 256 * k;  // 32 pairs of cells per row
+    t.c[k] = *reinterpret_cast<const hy_v2d_a8 *>(src + (long long)(y0 + (i >> 5)) * w.ld + x0 + (i & 31) * 2);
+  }
+  int r, c;
+  hy_ring_cell((int)threadIdx.x, r, c);
+  t.r1 = src[(long long)(y0 - 1 + r) * w.ld + x0 - 1 + c];
+  t.r2 = 0.0;
+  if ((int)threadIdx.x + 256 < 2 * HLD + 2 * HT) {
+    hy_ring_cell((int)threadIdx.x + 256, r, c);
+    t.r2 = src[(long long)(y0 - 1 + r) * w.ld + x0 - 1 + c];
+  }
+}
+// NODATA_INF: a nodata height is stored as +inf (as hy_tile_store)
+template <bool NODATA_INF = false>
+__device__ __forceinline__ void hy_tile_store64(const HyTileRegs64 &t, double *s) {
+  auto f = [&](double v) { return (NODATA_INF && hy_nodata(v)) ? __builtin_inf() : v; };
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int i = (int)threadIdx.x + 256 * k;
+    double *d = s + ((i >> 5) + 1) * HLS + 1 + (i & 31) * 2;
+    d[0] = f(t.c[k].x);
+    d[1] = f(t.c[k].y);
+  }
+  int r, c;
+  hy_ring_cell((int)threadIdx.x, r, c);
+  s[r * HLS + c] = f(t.r1);
+  if ((int)threadIdx.x + 256 < 2 * HLD + 2 * HT) {
+    hy_ring_cell((int)threadIdx.x + 256, r, c);
+    s[r * HLS + c] = f(t.r2);
+  }
+}
+__device__ __forceinline__ void hy_stage64(double *s, const double *__restrict__ src, const DtWin &w, int y0, int x0,
+                                           double outside) {
+  if (hy_tile_fast(src, w, y0, x0)) {
+    HyTileRegs64 t;
+    hy_tile_load64(t, src, w, y0, x0);
+    hy_tile_store64(t, s);
+  } else {
+    hy_stage_slow<double>(s, src, w, y0, x0, outside);
   }
 }
 
@@ -478,6 +555,151 @@ __global__ __launch_bounds__(256) void k_fill_relax(const float *__restrict__ de
   if (threadIdx.x == 0) atomicOr(changed, 1);
 }
 
+// k_fill_relax on float64 heights (the float64 tier): the same round, INIT form, activity flags and coloured rounds,
+// on a float64 surface.  The relaxation takes only min / max of heights and comparisons, so it is exact in float64 as
+// it is in float32, and reaches the same fixed point as a sequential float64 priority flood.  Nodata is a height equal
+// to -100 and +inf stands for "unknown", as on the float32 surface.  The two LDS images take 68.6 KiB (float32: 34.3),
+// so two workgroups fit on a CU where four did; the odd row strides keep the column sweeps free of bank conflicts
+// for ds_read_b64 / ds_write_b64 as well.
+template <bool INIT>
+__global__ __launch_bounds__(256) void k_fill_relax_f64(const double *__restrict__ dem, double *__restrict__ wsurf,
+                                                       DtWin w, int tiles_x, int *__restrict__ changed,
+                                                       const int *__restrict__ prev,
+                                                       const uint8_t *__restrict__ act_prev,
+                                                       uint8_t *__restrict__ act_cur, int tiles_y, int sweeps,
+                                                       int colour) {
+  const int H = w.H, W = w.W;
+  __shared__ double s_w[HLD * HLS];
+  __shared__ double s_z[HT * HZS];
+  if (prev && *prev == 0) return;  // (a plain scalar load: see k_fill_relax)
+  int ty, tx;
+  hy_tile_of_block(colour, tiles_x, ty, tx);
+  const int tile = ty * tiles_x + tx;
+  const int y0 = ty * HT, x0 = tx * HT;
+  if (!hy_tile_active(act_prev, ty, tx, tiles_x, tiles_y)) {
+    if (act_cur && threadIdx.x == 0) act_cur[tile] = 0;
+    return;
+  }
+  const double inf = __builtin_inf();
+  const bool fastio = y0 + HT <= H && x0 + HT <= W;  // block-uniform: a whole tile goes 16 bytes at a time
+  if (INIT) {
+    hy_stage64(s_w, dem, w, y0, x0, inf);  // (cells beyond the raster: +inf, not nodata)
+    __syncthreads();
+    double w0[H_CPT];
+#pragma unroll
+    for (int j = 0; j < H_CPT; j++) {
+      const int c = threadIdx.x + 256 * j;
+      const int ly = c / HT, lx = c % HT;
+      const int y = y0 + ly, x = x0 + lx;
+      const int p = (ly + 1) * HLS + lx + 1;
+      const double z = (y < H && x < W) ? s_w[p] : (double)DT_NODATA;
+      const int gy = w.gy0 + y, gx = w.gx0 + x;
+      bool outlet = gy == 0 || gx == 0 || gy == w.Hg - 1 || gx == w.Wg - 1;
+      outlet = outlet || hy_nodata(s_w[p - HLS - 1]) || hy_nodata(s_w[p - HLS]) || hy_nodata(s_w[p - HLS + 1]) ||
+               hy_nodata(s_w[p - 1]) || hy_nodata(s_w[p + 1]) || hy_nodata(s_w[p + HLS - 1]) ||
+               hy_nodata(s_w[p + HLS]) || hy_nodata(s_w[p + HLS + 1]);
+      w0[j] = (!hy_nodata(z) && outlet) ? z : inf;
+      s_z[ly * HZS + lx] = z;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < HLD * HLS; i += 256) s_w[i] = inf;  // the other tiles' cells: unknown yet
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < H_CPT; j++) {
+      const int c = threadIdx.x + 256 * j;
+      s_w[(c / HT + 1) * HLS + (c % HT) + 1] = w0[j];
+    }
+  } else {
+    // the tile's heights first, in flight while the surface is staged (as k_fill_relax)
+    hy_v2d_a8 z2[8];
+    double z[H_CPT];
+    if (fastio) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const int i = (int)threadIdx.x + 256 * k;
+        z2[k] = *reinterpret_cast<const hy_v2d_a8 *>(dem + (long long)(y0 + (i >> 5)) * w.ld + x0 + (i & 31) * 2);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < H_CPT; j++) {
+        const int c = threadIdx.x + 256 * j;
+        const int y = y0 + c / HT, x = x0 + c % HT;
+        z[j] = (y < H && x < W) ? dem[(long long)y * w.ld + x] : (double)DT_NODATA;
+      }
+    }
+    const bool fast_w = hy_tile_fast(wsurf, w, y0, x0);
+    if (fast_w) {  // nodata -> +inf on the way into LDS
+      HyTileRegs64 t;
+      hy_tile_load64(t, wsurf, w, y0, x0);
+      hy_tile_store64<true>(t, s_w);
+    } else {
+      hy_stage_slow<double>(s_w, wsurf, w, y0, x0, inf);
+    }
+    if (fastio) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const int i = (int)threadIdx.x + 256 * k;
+        double *d = s_z + (i >> 5) * HZS + (i & 31) * 2;
+        d[0] = z2[k].x;
+        d[1] = z2[k].y;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < H_CPT; j++) {
+        const int c = threadIdx.x + 256 * j;
+        s_z[(c / HT) * HZS + (c % HT)] = z[j];
+      }
+    }
+    if (!fast_w) {
+      __syncthreads();
+      for (int i = threadIdx.x; i < HLD * HLS; i += 256)
+        if (hy_nodata(s_w[i])) s_w[i] = inf;  // (the pad column holds garbage nobody reads)
+    }
+  }
+  __syncthreads();
+  // the directional in-place sweeps of k_fill_relax, on doubles
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  int any = 0, open = 0, ring = 0;
+  for (int it = 0; it < sweeps; it++) {
+    int ch;
+    if (wave == 0) ch = hy_fill_sweep<true, 1>(s_w, s_z, lane);
+    else if (wave == 1) ch = hy_fill_sweep<true, -1>(s_w, s_z, lane);
+    else if (wave == 2) ch = hy_fill_sweep<false, 1>(s_w, s_z, lane);
+    else ch = hy_fill_sweep<false, -1>(s_w, s_z, lane);
+    open = __syncthreads_or(ch);
+    if (!open) break;
+    any = 1;
+    ring |= __syncthreads_or(ch & 2);
+  }
+  if (INIT) any = ring = 1;
+  if (act_cur && threadIdx.x == 0) act_cur[tile] = (uint8_t)((ring ? HY_CHANGED : 0) | (open ? HY_OPEN : 0));
+  if (!any) return;
+  if (fastio) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int i = (int)threadIdx.x + 256 * k;
+      const int r = i >> 5, c2 = (i & 31) * 2;
+      const double *sw = s_w + (r + 1) * HLS + 1 + c2, *sz = s_z + r * HZS + c2;
+      hy_v2d_a8 v;
+      v.x = hy_nodata(sz[0]) ? (double)DT_NODATA : sw[0];
+      v.y = hy_nodata(sz[1]) ? (double)DT_NODATA : sw[1];
+      *reinterpret_cast<hy_v2d_a8 *>(wsurf + (long long)(y0 + r) * w.ld + x0 + c2) = v;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < H_CPT; j++) {
+      const int c = threadIdx.x + 256 * j;
+      const int y = y0 + c / HT, x = x0 + c % HT;
+      if (y < H && x < W) {
+        const double zc = s_z[(c / HT) * HZS + (c % HT)];
+        if (!hy_nodata(zc)) wsurf[(long long)y * w.ld + x] = s_w[(c / HT + 1) * HLS + (c % HT) + 1];
+        else if (INIT) wsurf[(long long)y * w.ld + x] = (double)DT_NODATA;
+      }
+    }
+  }
+  if (threadIdx.x == 0) atomicOr(changed, 1);
+}
+
 // D8 code towards neighbour k of the scan order NW N NE W E SW S SE
 __device__ __forceinline__ uint8_t hy_code_of_scan(int k) {
   const uint8_t codes[8] = {32, 64, 128, 16, 1, 8, 4, 2};
@@ -570,6 +792,105 @@ __global__ __launch_bounds__(256) void k_flat_init(const float *__restrict__ wsu
     }
     // (beyond the raster: not nodata -- those cells got their outward code from the stencil --, never equal to anything)
     hy_stage<float>(s_w, wsurf, w, y0, x0, __builtin_inff());
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < H_CPT; j++) {
+      const int c = threadIdx.x + 256 * j;
+      const int ly = c / HT, lx = c % HT;
+      const int y = y0 + ly, x = x0 + lx;
+      if (y >= w.H || x >= w.W) continue;
+      const long long o = (long long)y * w.ld + x;
+      uint32_t code;
+      const uint32_t d = init_cell((ly + 1) * HLS + lx + 1, f[j], &code);
+      if (code) fdr[o] = (uint8_t)code;
+      any |= d == H_INF_DIST ? 1 : 0;
+      dist[o] = d;
+      if (nsame) nsame[o] = (uint8_t)nsame_of((ly + 1) * HLS + lx + 1);
+    }
+  }
+  any = __syncthreads_or(any);
+  // (read as the activity byte of "round -1" by the first relaxation round: the tile itself is open, its neighbours
+  // have something to look at)
+  if (has_flat && threadIdx.x == 0) has_flat[blockIdx.x] = (uint8_t)(any ? (HY_CHANGED | HY_OPEN) : 0);
+}
+
+
+// k_flat_init on a float64 surface (the float64 tier): the same dist, has_flat, nsame and nodata-drain codes.  A kernel
+// of its own, not a shared body: inlining k_flat_init's body from a template changed the float32 kernel's code.
+__global__ __launch_bounds__(256) void k_flat_init_f64(const double *__restrict__ wsurf, uint8_t *__restrict__ fdr,
+                                                      DtWin w, uint32_t *__restrict__ dist, int tiles_x,
+                                                      uint8_t *__restrict__ has_flat, uint8_t *__restrict__ nsame) {
+  __shared__ double s_w[HLD * HLS];
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int y0 = ty * HT, x0 = tx * HT;
+  // a code-less valid cell: distance "infinite", unless it lies next to nodata -- then it drains there right away
+  // (returns the cell's distance; *code != 0: the cell's new D8 code)
+  auto init_cell = [&](int p, uint32_t f, uint32_t *code) -> uint32_t {
+    *code = 0u;
+    if (hy_nodata(s_w[p]) || f != 0u) return 0u;
+    // scan order NW N NE W E SW S SE
+    uint32_t c = 0u;
+    if (hy_nodata(s_w[p - HLS - 1])) c = 32u;
+    else if (hy_nodata(s_w[p - HLS])) c = 64u;
+    else if (hy_nodata(s_w[p - HLS + 1])) c = 128u;
+    else if (hy_nodata(s_w[p - 1])) c = 16u;
+    else if (hy_nodata(s_w[p + 1])) c = 1u;
+    else if (hy_nodata(s_w[p + HLS - 1])) c = 8u;
+    else if (hy_nodata(s_w[p + HLS])) c = 4u;
+    else if (hy_nodata(s_w[p + HLS + 1])) c = 2u;
+    *code = c;
+    return c ? 0u : H_INF_DIST;
+  };
+  auto nsame_of = [&](int p) -> uint32_t {
+    const double wc = s_w[p];
+    if (hy_nodata(wc)) return 0xFFu;
+    return (s_w[p - HLS - 1] == wc ? 0u : 1u) | (s_w[p - HLS] == wc ? 0u : 2u) | (s_w[p - HLS + 1] == wc ? 0u : 4u) |
+           (s_w[p - 1] == wc ? 0u : 8u) | (s_w[p + 1] == wc ? 0u : 16u) | (s_w[p + HLS - 1] == wc ? 0u : 32u) |
+           (s_w[p + HLS] == wc ? 0u : 64u) | (s_w[p + HLS + 1] == wc ? 0u : 128u);
+  };
+  int any = 0;
+  // block-uniform: a whole tile of aligned rows -- four codes per 32-bit load, four distances per 16-byte store
+  const bool fast = y0 + HT <= w.H && x0 + HT <= w.W && (w.ld & 3) == 0 && ((uintptr_t)fdr & 3) == 0;
+  if (fast) {
+    uint32_t f4[4];  // the tile's codes, all loads in flight with the staging's
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int i = (int)threadIdx.x + 256 * k;
+      f4[k] = *reinterpret_cast<const uint32_t *>(fdr + (long long)(y0 + (i >> 4)) * w.ld + x0 + (i & 15) * 4);
+    }
+    hy_stage64(s_w, wsurf, w, y0, x0, __builtin_inf());
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int i = (int)threadIdx.x + 256 * k;
+      const int r = i >> 4, c4 = (i & 15) * 4;
+      const long long o = (long long)(y0 + r) * w.ld + x0 + c4;
+      uint32_t d[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        uint32_t code;
+        d[q] = init_cell((r + 1) * HLS + 1 + c4 + q, (f4[k] >> (8 * q)) & 0xFFu, &code);
+        if (code) fdr[o + q] = (uint8_t)code;
+        any |= d[q] == H_INF_DIST ? 1 : 0;
+      }
+      hy_v4u_a4 v = {d[0], d[1], d[2], d[3]};
+      *reinterpret_cast<hy_v4u_a4 *>(dist + o) = v;
+      if (nsame) {
+        const int p = (r + 1) * HLS + 1 + c4;
+        *reinterpret_cast<uint32_t *>(nsame + o) = nsame_of(p) | (nsame_of(p + 1) << 8) | (nsame_of(p + 2) << 16) |
+                                                   (nsame_of(p + 3) << 24);
+      }
+    }
+  } else {
+    uint8_t f[H_CPT];
+#pragma unroll
+    for (int j = 0; j < H_CPT; j++) {
+      const int c = threadIdx.x + 256 * j;
+      const int y = y0 + c / HT, x = x0 + c % HT;
+      f[j] = (y < w.H && x < w.W) ? fdr[(long long)y * w.ld + x] : (uint8_t)1;
+    }
+    // (beyond the raster: not nodata -- those cells got their outward code from the stencil --, never equal to anything)
+    hy_stage64(s_w, wsurf, w, y0, x0, __builtin_inf());
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < H_CPT; j++) {
@@ -1033,21 +1354,55 @@ static size_t hy_colour_min() {
   const int v = dt_debug_get(DT_DBG_HY_COLOUR_MIN);  // (tests run the coloured form on small rasters)
   return v > 0 ? (size_t)v : (size_t)HY_COLOUR_MIN_TILES;
 }
-static void hy_fill_round(hipStream_t s, bool coloured, int64_t r, const float *dem, float *filled, const DtWin &w,
+// (T = double: the float64 tier's kernel, k_fill_relax_f64, in the same rounds)
+template <bool INIT>
+static void hy_fill_launch(dim3 g, hipStream_t s, const float *dem, float *filled, const DtWin &w, int tiles_x, int *f,
+                           const int *prev, const uint8_t *act_prev, uint8_t *act_cur, int tiles_y, int sweeps,
+                           int colour) {
+  hipLaunchKernelGGL(k_fill_relax<INIT>, g, dim3(256), 0, s, dem, filled, w, tiles_x, f, prev, act_prev, act_cur,
+                     tiles_y, sweeps, colour);
+}
+template <bool INIT>
+static void hy_fill_launch(dim3 g, hipStream_t s, const double *dem, double *filled, const DtWin &w, int tiles_x, int *f,
+                           const int *prev, const uint8_t *act_prev, uint8_t *act_cur, int tiles_y, int sweeps,
+                           int colour) {
+  hipLaunchKernelGGL(k_fill_relax_f64<INIT>, g, dim3(256), 0, s, dem, filled, w, tiles_x, f, prev, act_prev, act_cur,
+                     tiles_y, sweeps, colour);
+}
+template <typename T>
+static void hy_fill_round(hipStream_t s, bool coloured, int64_t r, const T *dem, T *filled, const DtWin &w,
                           int tiles_x, int tiles_y, int *f, const int *prev, uint8_t *act0, uint8_t *act1, int sweeps) {
-  const dim3 b(256);
   if (r == 0) {  // the first round initialises the surface itself (no k_fill_init pass): every tile at once
-    hipLaunchKernelGGL(k_fill_relax<true>, dim3((unsigned)(tiles_x * tiles_y)), b, 0, s, dem, filled, w, tiles_x, f, prev,
-                       (const uint8_t *)nullptr, act0, tiles_y, sweeps, -1);
+    hy_fill_launch<true>(dim3((unsigned)(tiles_x * tiles_y)), s, dem, filled, w, tiles_x, f, prev,
+                         (const uint8_t *)nullptr, act0, tiles_y, sweeps, -1);
   } else if (coloured) {
     for (int c = 0; c < 4; c++)
       if (hy_colour_blocks(c, tiles_x, tiles_y))
-        hipLaunchKernelGGL(k_fill_relax<false>, dim3(hy_colour_blocks(c, tiles_x, tiles_y)), b, 0, s, dem, filled, w,
-                           tiles_x, f, prev, (const uint8_t *)act0, act0, tiles_y, sweeps, c);
+        hy_fill_launch<false>(dim3(hy_colour_blocks(c, tiles_x, tiles_y)), s, dem, filled, w, tiles_x, f, prev,
+                              (const uint8_t *)act0, act0, tiles_y, sweeps, c);
   } else {
-    hipLaunchKernelGGL(k_fill_relax<false>, dim3((unsigned)(tiles_x * tiles_y)), b, 0, s, dem, filled, w, tiles_x, f, prev,
-                       (const uint8_t *)((r - 1) & 1 ? act1 : act0), (r & 1) ? act1 : act0, tiles_y, sweeps, -1);
+    hy_fill_launch<false>(dim3((unsigned)(tiles_x * tiles_y)), s, dem, filled, w, tiles_x, f, prev,
+                          (const uint8_t *)((r - 1) & 1 ? act1 : act0), (r & 1) ? act1 : act0, tiles_y, sweeps, -1);
   }
+}
+// D8 on the filled surface and k_flat_init (the steps between the two relaxations that read heights).  float: the
+// distance raster is not in use yet and lends the D8 kernel its mark / mask workspace -- the hot / cold pair of the
+// chain's first op, 0.40 ms at 16384^2, instead of the generic stencil, 0.55.  double: k_d8_f64 (no workspace).
+static int hy_d8_flat_init(hipStream_t s, const DtWin &w, const float *filled, double px, uint8_t *fdr, uint32_t *dist,
+                           int tiles_x, uint8_t *has_flat, uint8_t *nsame) {
+  const int64_t H = w.H, W = w.W, n = H * W;
+  DT_TRY(dt_launch_stencil(s, w, filled, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr, nullptr,
+                           dt_stencil_aux_bytes(H, W) <= dt_align256((size_t)n * 4) ? (void *)dist : nullptr));
+  hipLaunchKernelGGL(k_flat_init, dim3((unsigned)hy_tiles(H, W)), dim3(256), 0, s, filled, fdr, w, dist, tiles_x,
+                     has_flat, nsame);
+  return DT_OK;
+}
+static int hy_d8_flat_init(hipStream_t s, const DtWin &w, const double *filled, double px, uint8_t *fdr,
+                           uint32_t *dist, int tiles_x, uint8_t *has_flat, uint8_t *nsame) {
+  DT_TRY(dt_launch_d8_f64(s, filled, w.H, w.W, px, fdr, nullptr, nullptr));
+  hipLaunchKernelGGL(k_flat_init_f64, dim3((unsigned)hy_tiles(w.H, w.W)), dim3(256), 0, s, filled, fdr, w, dist,
+                     tiles_x, has_flat, nsame);
+  return DT_OK;
 }
 // ... of the flat distances; has_flat: k_flat_init's per-tile flags, the activity the first round starts from (the
 // coloured form has them copied into act0 beforehand)
@@ -1069,7 +1424,10 @@ static void hy_flat_round(hipStream_t s, bool coloured, int64_t r, const uint8_t
 
 // dem -> filled surface (may alias nothing), D8 codes with flats resolved.  *unresolved_host = flat cells left
 // without a code (0 on any raster: every flat of a filled surface reaches a coded cell).  Synchronous.
-int dt_launch_condition(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, float *filled, uint8_t *fdr,
+// T = double: the float64 tier (dt_launch_condition_f64) -- the same rounds on a float64 surface; from k_flat_init on
+// no kernel reads a height.
+template <typename T>
+static int hy_condition(hipStream_t s, const T *dem, int64_t H, int64_t W, double px, T *filled, uint8_t *fdr,
                         void *scratch, int *unresolved_host, int *rounds_host) {
   const int fill_sweeps = dt_debug_get(DT_DBG_HY_FILL_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FILL_SWEEPS) : HY_FILL_SWEEPS;
   const int flat_sweeps = dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) : HY_FLAT_SWEEPS;
@@ -1093,11 +1451,7 @@ int dt_launch_condition(hipStream_t s, const float *dem, int64_t H, int64_t W, d
     hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, f, prev, act, act1, fill_sweeps);
   }, &r1));
   if (fdr) {
-    // (the distance raster is not in use yet: it lends the D8 kernel its mark / mask workspace -- the hot / cold pair
-    // of the chain's first op, 0.40 ms at 16384^2, instead of the generic stencil, 0.55)
-    DT_TRY(dt_launch_stencil(s, w, filled, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr, nullptr,
-                             dt_stencil_aux_bytes(H, W) <= dt_align256((size_t)n * 4) ? (void *)dist : nullptr));
-    hipLaunchKernelGGL(k_flat_init, gt, b, 0, s, filled, fdr, w, dist, tiles_x, has_flat, nsame);
+    DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, dist, tiles_x, has_flat, nsame));
     // the rounds start from the tiles that have flat cells (and their neighbours), not from every tile
     if (coloured) DT_HIP(hipMemcpyAsync(act, has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
     DT_TRY(hy_iterate(s, flag, max_rounds, [&](int *f, const int *prev, int64_t r) {
@@ -1117,6 +1471,14 @@ int dt_launch_condition(hipStream_t s, const float *dem, int64_t H, int64_t W, d
   }
   return DT_OK;
 }
+int dt_launch_condition(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, float *filled, uint8_t *fdr,
+                        void *scratch, int *unresolved_host, int *rounds_host) {
+  return hy_condition<float>(s, dem, H, W, px, filled, fdr, scratch, unresolved_host, rounds_host);
+}
+int dt_launch_condition_f64(hipStream_t s, const double *dem, int64_t H, int64_t W, double px, double *filled,
+                            uint8_t *fdr, void *scratch, int *unresolved_host, int *rounds_host) {
+  return hy_condition<double>(s, dem, H, W, px, filled, fdr, scratch, unresolved_host, rounds_host);
+}
 
 // The same conditioning without a single host synchronisation (the resident chain's form): a fixed budget of `rounds`
 // fill rounds and `rounds` flat rounds is enqueued; every round records whether it changed anything, a round that
@@ -1124,8 +1486,9 @@ int dt_launch_condition(hipStream_t s, const float *dem, int64_t H, int64_t W, d
 // context when the budget ran out before the fixed point (or a flat cell was left without a code): the rasters are
 // then NOT the conditioned ones -- run again with a larger budget, or use the synchronous form, which iterates to
 // the fixed point whatever it takes.  The bundled Example raster needs 12 rounds, rough 4096^2 terrain a few dozen.
-int dt_launch_condition_async(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, float *filled,
-                              uint8_t *fdr, void *scratch, int rounds, int *status) {
+template <typename T>
+static int hy_condition_async(hipStream_t s, const T *dem, int64_t H, int64_t W, double px, T *filled, uint8_t *fdr,
+                              void *scratch, int rounds, int *status) {
   const int fill_sweeps = dt_debug_get(DT_DBG_HY_FILL_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FILL_SWEEPS) : HY_FILL_SWEEPS;
   const int flat_sweeps = dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) : HY_FLAT_SWEEPS;
   (void)fill_sweeps;
@@ -1148,11 +1511,7 @@ int dt_launch_condition_async(hipStream_t s, const float *dem, int64_t H, int64_
   for (int r = 0; r < rounds; r++)
     hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, flags + r, r ? (const int *)(flags + r - 1) : nullptr,
                   act, act1, fill_sweeps);
-  // (the distance raster is not in use yet: it lends the D8 kernel its mark / mask workspace -- the hot / cold pair
-    // of the chain's first op, 0.40 ms at 16384^2, instead of the generic stencil, 0.55)
-    DT_TRY(dt_launch_stencil(s, w, filled, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr, nullptr,
-                             dt_stencil_aux_bytes(H, W) <= dt_align256((size_t)n * 4) ? (void *)dist : nullptr));
-  hipLaunchKernelGGL(k_flat_init, gt, b, 0, s, filled, fdr, w, dist, tiles_x, has_flat, nsame);
+  DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, dist, tiles_x, has_flat, nsame));
   if (coloured) DT_HIP(hipMemcpyAsync(act, has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
   int *fl2 = flags + rounds;
   for (int r = 0; r < rounds; r++)
@@ -1163,6 +1522,14 @@ int dt_launch_condition_async(hipStream_t s, const float *dem, int64_t H, int64_
   hipLaunchKernelGGL(k_hydro_verdict, dim3(1), dim3(1), 0, s, (const int *)(flags + rounds - 1),
                      (const int *)(fl2 + rounds - 1), (const int *)(flags + 2 * rounds), status);
   return DT_OK;
+}
+int dt_launch_condition_async(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, float *filled,
+                              uint8_t *fdr, void *scratch, int rounds, int *status) {
+  return hy_condition_async<float>(s, dem, H, W, px, filled, fdr, scratch, rounds, status);
+}
+int dt_launch_condition_async_f64(hipStream_t s, const double *dem, int64_t H, int64_t W, double px, double *filled,
+                                  uint8_t *fdr, void *scratch, int rounds, int *status) {
+  return hy_condition_async<double>(s, dem, H, W, px, filled, fdr, scratch, rounds, status);
 }
 
 // ---- the steps on one rank's window of a larger raster (multi-GPU: descriptools_amd/tiling.py iterates them with a

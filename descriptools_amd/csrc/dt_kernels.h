@@ -134,5 +134,10 @@ int dt_launch_condition_stage(hipStream_t s, const DtWin &w, int stage, int roun
                               uint8_t *fdr, uint32_t *dist, int *flag_dev, uint8_t *nsame = nullptr);
 int dt_launch_condition_async(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, float *filled,
                               uint8_t *fdr, void *scratch, int rounds, int *status);
+// ... on float64 heights (a float64 filled surface; the same scratch, rounds and status)
+int dt_launch_condition_f64(hipStream_t s, const double *dem, int64_t H, int64_t W, double px, double *filled,
+                            uint8_t *fdr, void *scratch, int *unresolved_host, int *rounds_host);
+int dt_launch_condition_async_f64(hipStream_t s, const double *dem, int64_t H, int64_t W, double px, double *filled,
+                                  uint8_t *fdr, void *scratch, int rounds, int *status);
 
 int dt_flow_impl();  // 1 global kernels, 2 tile-hierarchical (default)

@@ -4,7 +4,7 @@ pit; a raster-border cell with no lower neighbour drains outward."""
 import numpy as np
 
 from . import _lib
-from ._lib import c_f32p, c_f64p, c_u8p, check, dem_f32, ptr
+from ._lib import c_f32p, c_f64p, c_u8p, check, ptr
 
 
 def d8(dem, px, return_slope=False, heights="float32"):
@@ -22,17 +22,24 @@ def d8(dem, px, return_slope=False, heights="float32"):
     return (fdr, sl) if return_slope else fdr
 
 
-def d8_conditioned(dem, px, return_filled=False):
+def d8_conditioned(dem, px, return_filled=False, heights="float32"):
     """D8 for DEMs with pits and flats (the reference takes such an `fdr` from a GIS tool,
     Example/example.py:36): depressions filled, D8 on the filled surface, flats routed to their nearest outlet
-    (dt_d8_conditioned_f32).  Every valid cell gets a code; no cycles."""
-    dem32 = dem_f32(dem)
-    H, W = dem32.shape
+    (dt_d8_conditioned_f32).  Every valid cell gets a code; no cycles.
+    heights: as in d8 -- "float32" (default) refuses heights float32 cannot hold; "float64" conditions in float64
+    (dt_d8_conditioned_f64: the same definition, heights compared in float64; `filled` comes back as float64);
+    "auto" -- float64 exactly when float32 cannot hold the DEM."""
+    d, wide = _lib.dem_tier(dem, heights)
+    H, W = d.shape
     fdr = np.empty((H, W), np.uint8)
-    filled = np.empty((H, W), np.float32) if return_filled else None
+    filled = np.empty((H, W), np.float64 if wide else np.float32) if return_filled else None
     info = np.zeros(3, np.int32)
-    check(_lib.lib().dt_d8_conditioned_f32(ptr(dem32, c_f32p), H, W, float(px), ptr(fdr, c_u8p), ptr(filled, c_f32p),
-                                           info.ctypes.data_as(_lib.c_i32p)))
+    if wide:
+        check(_lib.lib().dt_d8_conditioned_f64(ptr(d, c_f64p), H, W, float(px), ptr(fdr, c_u8p), ptr(filled, c_f64p),
+                                               info.ctypes.data_as(_lib.c_i32p)))
+    else:
+        check(_lib.lib().dt_d8_conditioned_f32(ptr(d, c_f32p), H, W, float(px), ptr(fdr, c_u8p),
+                                               ptr(filled, c_f32p), info.ctypes.data_as(_lib.c_i32p)))
     if info[0]:
         raise RuntimeError("%d flat cells could not be routed" % int(info[0]))
     return (fdr, filled) if return_filled else fdr

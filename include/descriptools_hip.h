@@ -129,6 +129,10 @@ int dt_d8_f32(const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr, f
  * code (0), fill rounds, flat rounds}. */
 int dt_d8_conditioned_f32(const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *filled,
                           int32_t *info3);
+/* dt_d8_conditioned_f32's definition with the heights compared in float64 (a DEM that float32 cannot hold:
+ * flowdir.d8_conditioned(heights="float64")); filled (may be NULL) receives the float64 filled surface. */
+int dt_d8_conditioned_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, double *filled,
+                          int32_t *info3);
 
 /* Net-new N2: flow accumulation = number of upstream cells excluding self; `dem` may be NULL,
  * otherwise cells with dem <= -100 are set to -100.  Cells on a D8 cycle get -100. */
@@ -244,6 +248,15 @@ int dt_dev_condition_d8(dt_ctx *ctx, const float *dem, int64_t H, int64_t W, dou
  * DT_STATUS_NOT_CONVERGED is raised on the context (dt_ctx_status) when the budget did not reach the fixed point. */
 int dt_dev_condition_d8_async(dt_ctx *ctx, const float *dem, int64_t H, int64_t W, double px, float *filled,
                               uint8_t *fdr, int rounds);
+/* The float64 forms of the two: dt_d8_conditioned_f32's definition with the heights compared in float64; dem and
+ * filled are H x W double rasters on the device, every other argument as in the float32 form (the async form takes
+ * 1..500 rounds and raises DT_STATUS_NOT_CONVERGED when they run out).  The resident float64 chain takes such codes
+ * as external ones: Chain(heights="float64", external_fdr=True), dt_dev_condition_d8_f64_async into its fdr raster
+ * on its context, then run(). */
+int dt_dev_condition_d8_f64(dt_ctx *ctx, const double *dem, int64_t H, int64_t W, double px, double *filled,
+                            uint8_t *fdr, int32_t *info3);
+int dt_dev_condition_d8_f64_async(dt_ctx *ctx, const double *dem, int64_t H, int64_t W, double px, double *filled,
+                                  uint8_t *fdr, int rounds);
 /* acc32: int32 accumulation (H*W < 2^31); dem may be NULL. */
 int dt_dev_flowacc(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
                    int32_t *acc32);
