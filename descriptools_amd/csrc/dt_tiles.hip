@@ -235,6 +235,31 @@ __device__ __forceinline__ unsigned long long fa_rec(uint32_t W_, uint32_t xslot
 #define REC_XSLOT(r) ((uint32_t)(((r) >> 16) & 0xFFFFu))
 #define REC_CODE(r) ((uint32_t)(((r) >> 8) & 0xFFu))
 
+// Feeders of a perimeter cell: an exit of a neighbouring tile enters the tile at the perimeter cell its D8 step lands on,
+// so a perimeter cell's feeders are among its <= 5 neighbours outside the tile -- those whose code points back at it.
+// Neighbour q of the 8 (NW N NE W E SW S SE); FA_BACK packs the code that points back from each, a byte per q.
+#define FA_QDY(q) ((int)((0x22211000u >> (4 * (q))) & 0xFu) - 1)
+#define FA_QDX(q) ((int)((0x21020210u >> (4 * (q))) & 0xFu) - 1)
+__device__ __forceinline__ uint32_t fa_back(int q) {
+  return (uint32_t)((q < 4 ? 0x01080402ull : 0x20408010ull) >> (8 * (q & 3))) & 0xFFu;
+}
+// the codes of the neighbours outside the tile of perimeter slot `slot` that lie in the core (0 elsewhere, and for
+// every q when the slot is not a cell of the core: other ranks' cells arrive as injected inflow)
+__device__ __forceinline__ void fa_nbr_codes(const uint8_t *__restrict__ fdr, const DtWin &w, int y0, int x0, int slot,
+                                             uint32_t (&c2)[8]) {
+  int ply = 0, plx = 0;
+  if (slot < PS) dt_cell_of_slot(slot, ply, plx);
+  const int y = y0 + ply, x = x0 + plx;
+  const bool live = slot < PS && y < w.H && x < w.W;
+#pragma unroll
+  for (int q = 0; q < 8; q++) {
+    const int dy = FA_QDY(q), dx = FA_QDX(q);
+    const int ny = ply + dy, nx = plx + dx;
+    const bool inside = ny >= 0 && ny < TH && nx >= 0 && nx < TW;  // my own tile
+    c2[q] = (live && !inside && dt_in_core(w, y + dy, x + dx)) ? (uint32_t)fdr[(long long)(y + dy) * w.ld + x + dx] : 0u;
+  }
+}
+
 __global__ __launch_bounds__(256, 6) void k_fa_tile1(const uint8_t *__restrict__ fdr, DtWin w, int tiles_x,
                                                     unsigned long long *__restrict__ rec,
                                                     uint16_t *__restrict__ loc16,
@@ -255,22 +280,10 @@ __global__ __launch_bounds__(256, 6) void k_fa_tile1(const uint8_t *__restrict__
   // flight together, before the first barrier (fetched one by one, each behind the test of the previous, the
   // neighbour codes were five dependent memory round trips on the workgroup's path to its barrier).
   const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
-  const int8_t qdy[8] = {-1, -1, -1, 0, 0, 1, 1, 1}, qdx[8] = {-1, 0, 1, -1, 1, -1, 0, 1};  // NW N NE W E SW S SE
   uint32_t c2[8];
+  fa_nbr_codes(fdr, w, y0, x0, threadIdx.x, c2);
   int ply = 0, plx = 0;
   if (threadIdx.x < PS) dt_cell_of_slot(threadIdx.x, ply, plx);
-  {
-    const int y = y0 + ply, x = x0 + plx;
-    const bool live = threadIdx.x < PS && y < w.H && x < w.W;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int dy = qdy[q], dx = qdx[q];
-      const int ny = ply + dy, nx = plx + dx;
-      const bool inside = ny >= 0 && ny < TH && nx >= 0 && nx < TW;  // my own tile
-      // other ranks' cells arrive as injected inflow
-      c2[q] = (live && !inside && dt_in_core(w, y + dy, x + dx)) ? (uint32_t)fdr[(long long)(y + dy) * w.ld + x + dx] : 0u;
-    }
-  }
   {
     uint32_t code = threadIdx.x, e = 0u;
     if (dt_d8_valid(code)) {
@@ -330,16 +343,12 @@ __global__ __launch_bounds__(256, 6) void k_fa_tile1(const uint8_t *__restrict__
     const int y = y0 + ly, x = x0 + lx;
 #pragma unroll
     for (int q = 0; q < 8; q++) fnode[q] = FA_NONE;
-    if (y < w.H && x < w.W) {
-      // neighbour q drains into me iff its code points back at me
-      const uint8_t back[8] = {2, 4, 8, 1, 16, 128, 64, 32};
 #pragma unroll
-      for (int q = 0; q < 8; q++)
-        if (c2[q] == (uint32_t)back[q]) {
-          fnode[q] = dt_node_of(y + qdy[q], x + qdx[q], tiles_x);
-          feeders++;
-        }
-    }
+    for (int q = 0; q < 8; q++)
+      if (c2[q] == fa_back(q)) {  // neighbour q drains into me (c2 is 0 unless my cell is in the core)
+        fnode[q] = dt_node_of(y + FA_QDY(q), x + FA_QDX(q), tiles_x);
+        feeders++;
+      }
   }
   __syncthreads();
   // the staged codes have been consumed: cycle mask and pending counts start at zero (the rounds' first barrier comes
@@ -379,7 +388,7 @@ __global__ __launch_bounds__(256, 6) void k_fa_tile1(const uint8_t *__restrict__
   __syncthreads();
   if (threadIdx.x < PS) {  // pending count of my exit (0 for the rest): k_fa_reduce's countdown word
     state[(size_t)tile * PS + threadIdx.x] = (unsigned long long)s_pend[threadIdx.x] << FA2_SH;
-    ext[(size_t)tile * PS + threadIdx.x] = 0ull;  // inflow accumulator of my entry
+    if (ext) ext[(size_t)tile * PS + threadIdx.x] = 0ull;  // inflow accumulator of my entry (rank path, scatter form)
   }
   // in-tile accumulation (upstream cells of this tile only, <= 4095: 2 bytes per cell, tile-major; 0xFFFF =
   // on an in-tile cycle); pass 3 adds what enters from outside
@@ -397,38 +406,122 @@ __global__ __launch_bounds__(256, 6) void k_fa_tile1(const uint8_t *__restrict__
 // perimeter graph: node id = tile * PS + slot.  entry_of[q] = the entry node exit q feeds (the neighbouring
 // tile's perimeter cell its D8 step lands on), parent[q] = the exit node that entry's in-tile path leads to;
 // rank exits have neither.  Both are written by pass 1 of the tile that is entered.
-// countdown over the reduced forest; A(q) = W(q) + sum of A over the exit nodes feeding
-// q's tile through entry cells whose in-tile path leads to q.  ext[entry] accumulates the inflow
-// arriving at an entry cell from other tiles.
+// Countdown over the reduced forest: A(q) = W(q) + the sum of A over the exit nodes feeding q's tile through entry
+// cells whose in-tile path leads to q; state[q] ends as pending 0 | that sum.  Nothing else is written: pass 3
+// gathers an entry cell's inflow from its feeders' (rec, state) (fa_gather).
+// The kernel is bound by the number of its random 64-bit atomics, not by the depth of the chains, and
+// nine in ten exits are SOURCES (no feeders: A = W, known from pass 1) whose first hops converge onto few parents.  So
+// the sources of a wave combine their first hops by parent: one atomic carries (sum of A) - (k << FA2_SH) for the k
+// sources of the wave that feed that parent, and the lane that sees exactly k pending feeders left retired the node
+// and carries the chain on, one atomic per hop as before.
+// ext != nullptr: the scatter form (DT_DBG_FA_SCATTER, for A/B runs): every exit also adds its total to ext[entry]
+// and sources do not combine.
 __global__ __launch_bounds__(256) void k_fa_reduce(const unsigned long long *__restrict__ rec, int64_t nnodes,
                                                   const uint32_t *__restrict__ entry_of,
                                                   const uint32_t *__restrict__ parent,
                                                   unsigned long long *__restrict__ state,
                                                   unsigned long long *__restrict__ ext) {
-  int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= nnodes) return;
-  unsigned long long r = rec[n];
-  if (REC_CODE(r) == 0) return;  // not an exit node
-  if (state[n] != 0ull) return;  // not a source of the reduced forest (a source's word stays 0)
-  unsigned long long A = REC_W(r);
-  uint32_t e = entry_of[n], p = parent[n];
-  for (int64_t it = 0; it < nnodes; it++) {
-    if (e == FA_NONE) break;  // rank exit: its total stays in (rec, state)
-    atomicAdd(&ext[e], A);
-    if (p == FA_NONE) break;
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (ext) {
+    if (n >= nnodes) return;
+    unsigned long long r = rec[n];
+    if (REC_CODE(r) == 0) return;  // not an exit node
+    if (state[n] != 0ull) return;  // not a source of the reduced forest (a source's word stays 0)
+    unsigned long long A = REC_W(r);
+    uint32_t e = entry_of[n], p = parent[n];
+    for (int64_t it = 0; it < nnodes; it++) {
+      if (e == FA_NONE) break;  // rank exit: its total stays in (rec, state)
+      atomicAdd(&ext[e], A);
+      if (p == FA_NONE) break;
+      // the next hop's operands are fetched while the countdown atomic is in flight
+      unsigned long long rp = rec[p];
+      uint32_t ep = entry_of[p], pp = parent[p];
+      unsigned long long old = atomicAdd(&state[p], A - (1ull << FA2_SH));
+      if ((old >> FA2_SH) != 1ull) break;
+      A = REC_W(rp) + (old & FA2_MASK) + A;
+      e = ep;
+      p = pp;
+    }
+    return;
+  }
+  // a source with a parent (a rank exit has none; nor has an exit whose entry's in-tile path ends in the tile).  A
+  // node that is not a source never shows a zero word: its pending count or its sum (every feeder brings >= 1) is set.
+  uint32_t p = FA_NONE, A = 0u;  // a source's A is its in-tile weight, <= 4096
+  if (n < nnodes) {
+    const unsigned long long r = rec[n];
+    if (REC_CODE(r) != 0 && state[n] == 0ull) {
+      p = parent[n];
+      A = REC_W(r);
+    }
+  }
+  // the whole wave takes part: one round per distinct parent, led by the lowest lane still to go.  The atomics of all
+  // rounds are in flight together; their results are looked at after the last round.
+  const int lane = (int)(threadIdx.x & 63u);
+  bool todo = p != FA_NONE, led = false;
+  uint32_t k = 0u, S = 0u, pp = FA_NONE;
+  unsigned long long rp = 0ull, old = 0ull;
+  for (unsigned long long m = __ballot(todo); m != 0ull; m = __ballot(todo)) {
+    const int lead = __ffsll((long long)m) - 1;
+    const uint32_t pl = (uint32_t)__shfl((int)p, lead);
+    const bool mine = todo && p == pl;
+    uint32_t s = mine ? A : 0u;  // <= 64 * 4096: no carry out of 32 bits
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += (uint32_t)__shfl_xor((int)s, o);
+    const uint32_t km = (uint32_t)__popcll(__ballot(mine));
+    if (lane == lead) {
+      led = true;
+      k = km;
+      S = s;
+      rp = rec[pl];
+      pp = parent[pl];
+      old = atomicAdd(&state[pl], (unsigned long long)s - ((unsigned long long)km << FA2_SH));
+    }
+    todo = todo && !mine;
+  }
+  if (!led || (old >> FA2_SH) != (unsigned long long)k) return;  // not the last feeders of my parent
+  // I retired node p: carry its total on towards the root, one countdown atomic per hop
+  unsigned long long T = REC_W(rp) + (old & FA2_MASK) + S;
+  p = pp;
+  for (int64_t it = 0; it < nnodes && p != FA_NONE; it++) {
     // the next hop's operands are fetched while the countdown atomic is in flight
-    unsigned long long rp = rec[p];
-    uint32_t ep = entry_of[p], pp = parent[p];
-    unsigned long long old = atomicAdd(&state[p], A - (1ull << FA2_SH));
+    rp = rec[p];
+    pp = parent[p];
+    old = atomicAdd(&state[p], T - (1ull << FA2_SH));
     if ((old >> FA2_SH) != 1ull) break;
-    A = REC_W(rp) + (old & FA2_MASK) + A;
-    e = ep;
+    T = REC_W(rp) + (old & FA2_MASK) + T;
     p = pp;
   }
 }
 
-// exit nodes that never resolved sit on a D8 cycle spanning tiles: flag the entry cells they feed so
-// that pass 3 marks the in-tile stretch of the cycle -100 (the oracle's "in-degree never reaches 0").
+// What enters the tile at perimeter slot `slot` from the other tiles of the core: the totals W + sum of the exits of
+// neighbouring tiles that step onto it (c2: fa_nbr_codes), read from their resolved (rec, state) words after the
+// countdown -- consecutive slots of a tile edge are fed by consecutive slots of the neighbouring tile's edge, so these
+// are near-coalesced loads where the scatter form had one random atomic per exit.  A feeder still pending sits on (or
+// below) a D8 cycle spanning tiles: FA_CYCLE, so that pass 3 marks the in-tile stretch of the cycle -100 (the
+// oracle's "in-degree never reaches 0").
+__device__ __forceinline__ unsigned long long fa_gather(const uint32_t (&c2)[8], int y0, int x0, int slot, int tiles_x,
+                                                        const unsigned long long *__restrict__ rec,
+                                                        const unsigned long long *__restrict__ state) {
+  int ly = 0, lx = 0;
+  if (slot < PS) dt_cell_of_slot(slot, ly, lx);
+  unsigned long long sum = 0ull, pend = 0ull;
+#pragma unroll
+  for (int q = 0; q < 8; q++)
+    if (c2[q] == fa_back(q)) {
+      const uint32_t f = dt_node_of(y0 + ly + FA_QDY(q), x0 + lx + FA_QDX(q), tiles_x);
+      const unsigned long long st = state[f];
+      sum += REC_W(rec[f]) + (st & FA2_MASK);
+      pend |= st >> FA2_SH;
+    }
+  return pend ? FA_CYCLE : sum;
+}
+// the inflow word of pass 3 (FA_VALUE | FA_CYCLE): the gathered part, plus what other ranks injected into ext
+__device__ __forceinline__ unsigned long long fa_inflow(unsigned long long g, unsigned long long x) {
+  return (FA_VALUE(g) + FA_VALUE(x)) | ((g | x) & FA_CYCLE);
+}
+
+// scatter form only (the gather form finds these in fa_gather): exit nodes that never resolved sit on a D8 cycle
+// spanning tiles: flag the entry cells they feed so that pass 3 marks the in-tile stretch of the cycle -100.
 __global__ __launch_bounds__(256) void k_fa_poison(const unsigned long long *__restrict__ rec, int64_t nnodes,
                                                   const uint32_t *__restrict__ entry_of,
                                                   const unsigned long long *__restrict__ state,
@@ -442,8 +535,8 @@ __global__ __launch_bounds__(256) void k_fa_poison(const unsigned long long *__r
   atomicOr(&ext[entry_of[n]], FA_CYCLE);
 }
 
-// pass 3: the inflow that enters the tile at a perimeter cell p (ext[p], resolved by pass 2) drains
-// through every cell of p's in-tile path: one lane per entry cell walks that path adding ext[p] to
+// pass 3: the inflow that enters the tile at a perimeter cell p (fa_gather over p's feeders after pass 2, plus ext[p]
+// on the rank path; ext[p] alone in the scatter form: rec == nullptr) drains through every cell of p's in-tile path: one lane per entry cell walks that path adding ext[p] to
 // an LDS delta raster (integer adds: order-free), then delta is added to pass 1's in-tile counts.
 // AccT = int32_t: the accumulation raster of a raster below 2^31 cells (a value that could reach 2^31 raises the
 // context's overflow status instead of wrapping); AccT = int64_t: the reference's own dtype (Example/example.py:39),
@@ -451,6 +544,8 @@ __global__ __launch_bounds__(256) void k_fa_poison(const unsigned long long *__r
 template <bool HAS_DEM, bool W_RIVER, typename AccT>
 __global__ __launch_bounds__(256, sizeof(AccT) == 8 ? 4 : 6) void k_fa_tile3(const uint8_t *__restrict__ fdr,
                                                     const float *__restrict__ dem, DtWin w, int tiles_x,
+                                                    const unsigned long long *__restrict__ rec,
+                                                    const unsigned long long *__restrict__ state,
                                                     const unsigned long long *__restrict__ ext,
                                                     const uint16_t *__restrict__ loc16,
                                                     AccT *__restrict__ acc32, AccT river_thr,
@@ -470,11 +565,13 @@ __global__ __launch_bounds__(256, sizeof(AccT) == 8 ? 4 : 6) void k_fa_tile3(con
   const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;
-  // every global load of the kernel is issued here, before the first wait: the tile's codes, the resolved inflow
-  // of its entries, pass 1's counts and the heights
+  // every global load of the kernel is issued here, before the first wait: the tile's codes, the codes of the
+  // entries' outside neighbours (then their feeders' words), what other ranks injected, pass 1's counts and the heights
   const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
+  uint32_t c2[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  if (rec) fa_nbr_codes(fdr, w, y0, x0, threadIdx.x, c2);
   unsigned long long e = 0ull;
-  if (threadIdx.x < PS) e = ext[(size_t)tile * PS + threadIdx.x];
+  if (threadIdx.x < PS && ext) e = ext[(size_t)tile * PS + threadIdx.x];
   // pass 1's counts and the heights are fetched now, so that their latency hides behind the serial walks.
   // Block-uniform fast form: whole 64-cell rows inside the core, 16-byte aligned rasters -> each lane owns 4
   // groups of 4 consecutive cells (8- and 16-byte loads, 16- and 4-byte stores)
@@ -506,6 +603,7 @@ __global__ __launch_bounds__(256, sizeof(AccT) == 8 ? 4 : 6) void k_fa_tile3(con
       zv[j] = (HAS_DEM && in) ? dem[o] : 0.0f;
     }
   }
+  if (rec) e = fa_inflow(fa_gather(c2, y0, x0, threadIdx.x, tiles_x, rec, state), e);
   dt_tile_put16(s_fdr, v_fdr);
   // No value of this tile can exceed the inflow entering it plus its own 4096 cells.  A tile whose entries bring in
   // >= 2^31 - 4096 in total is "big" (only tiles with an entry of >= 2^22 pay for the 64-bit sum that decides it):
@@ -755,6 +853,15 @@ static FaScratch fa_layout(const DtWin &w, void *scratch) {
   f.loc16 = (uint16_t *)p;
   return f;
 }
+// what pass 3 reads: the feeders' resolved words (rec, state) and, on the rank path, the injected ext; the scatter
+// form (DT_DBG_FA_SCATTER) resolved everything into ext.  The key must not change between phase 1 and phase 2.
+struct FaIn {
+  const unsigned long long *rec, *state, *ext;
+};
+static FaIn fa_inputs(const FaScratch &f, const unsigned long long *ext_perim) {
+  if (dt_debug_get(DT_DBG_FA_SCATTER)) return FaIn{nullptr, nullptr, f.ext};
+  return FaIn{f.rec, f.state, ext_perim ? f.ext : nullptr};
+}
 size_t dt_flowacc_tiled_scratch(int64_t H, int64_t W) {
   int64_t ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
   size_t nn = (size_t)ntiles * PS;
@@ -771,9 +878,11 @@ int dt_launch_fa_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, void *
   DT_REQUIRE(f.nnodes < 0x7FFFFFF0ll, "raster too large for one device tile");
   dim3 gt((unsigned)f.ntiles), b(256), gn((unsigned)((f.nnodes + 255) / 256));
   (void)acc32;  // written by pass 3 only
-  hipLaunchKernelGGL(k_fa_tile1, gt, b, 0, s, fdr, w, f.tiles_x, f.rec, f.loc16, f.state, f.ext, f.entry_of,
-                     f.parent);
-  hipLaunchKernelGGL(k_fa_reduce, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.parent, f.state, f.ext);
+  // ext: the inflow other ranks inject (rank path), or every entry's in the scatter form; zeroed by pass 1
+  const bool scatter = dt_debug_get(DT_DBG_FA_SCATTER) != 0;
+  hipLaunchKernelGGL(k_fa_tile1, gt, b, 0, s, fdr, w, f.tiles_x, f.rec, f.loc16, f.state,
+                     (rank_level || scatter) ? f.ext : nullptr, f.entry_of, f.parent);
+  hipLaunchKernelGGL(k_fa_reduce, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.parent, f.state, scatter ? f.ext : nullptr);
   if (rank_level) {
     hipLaunchKernelGGL(k_fa_nxt_init, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.state, f.nxt);
   }
@@ -794,12 +903,14 @@ int dt_launch_fa_summary(hipStream_t s, const DtWin &w, void *scratch, int64_t *
 // (dt_launch_fa_local with rank_level), then the final tile pass.
 template <typename AccT>
 static void fa_launch_tile3(hipStream_t s, dim3 gt, const DtWin &w, const uint8_t *fdr, const float *dem,
-                            const FaScratch &f, AccT *acc, AccT thr, int8_t *river, int *status) {
+                            const FaScratch &f, const unsigned long long *ext_perim, AccT *acc, AccT thr, int8_t *river,
+                            int *status) {
   dim3 b(256);
-  if (dem && river) hipLaunchKernelGGL((k_fa_tile3<true, true, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, f.ext, f.loc16, acc, thr, river, status);
-  else if (dem) hipLaunchKernelGGL((k_fa_tile3<true, false, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, f.ext, f.loc16, acc, thr, river, status);
-  else if (river) hipLaunchKernelGGL((k_fa_tile3<false, true, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, f.ext, f.loc16, acc, thr, river, status);
-  else hipLaunchKernelGGL((k_fa_tile3<false, false, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, f.ext, f.loc16, acc, thr, river, status);
+  const FaIn in = fa_inputs(f, ext_perim);
+  if (dem && river) hipLaunchKernelGGL((k_fa_tile3<true, true, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, acc, thr, river, status);
+  else if (dem) hipLaunchKernelGGL((k_fa_tile3<true, false, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, acc, thr, river, status);
+  else if (river) hipLaunchKernelGGL((k_fa_tile3<false, true, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, acc, thr, river, status);
+  else hipLaunchKernelGGL((k_fa_tile3<false, false, AccT>), gt, b, 0, s, fdr, dem, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, acc, thr, river, status);
 }
 
 // `acc` is int32_t* (acc64 == 0) or int64_t* (acc64 != 0: rasters of >= 2^31 cells split over ranks)
@@ -814,12 +925,12 @@ int dt_launch_fa_finish(hipStream_t s, const DtWin &w, const uint8_t *fdr, const
     hipLaunchKernelGGL(k_fa_propagate, dim3((unsigned)((P + 255) / 256)), b, 0, s, w, f.tiles_x, f.nnodes, f.nxt,
                        ext_perim, P, f.ext);
   }
-  hipLaunchKernelGGL(k_fa_poison, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.state, f.ext);
+  if (dt_debug_get(DT_DBG_FA_SCATTER)) hipLaunchKernelGGL(k_fa_poison, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.state, f.ext);
   if (acc64) {
-    fa_launch_tile3<long long>(s, gt, w, fdr, dem, f, (long long *)acc, (long long)river_thr, river, status);
+    fa_launch_tile3<long long>(s, gt, w, fdr, dem, f, ext_perim, (long long *)acc, (long long)river_thr, river, status);
   } else {
     int32_t thr = river_thr > 2147483647ll ? 2147483647 : (river_thr < -2147483647ll ? -2147483647 : (int32_t)river_thr);
-    fa_launch_tile3<int32_t>(s, gt, w, fdr, dem, f, (int32_t *)acc, thr, river, status);
+    fa_launch_tile3<int32_t>(s, gt, w, fdr, dem, f, ext_perim, (int32_t *)acc, thr, river, status);
   }
   return DT_OK;
 }
@@ -1279,6 +1390,8 @@ __global__ __launch_bounds__(256, 6) void k_fh_tile1n(const uint8_t *__restrict_
 template <int ND>
 __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
                                                   const uint8_t *__restrict__ nod4, int ldm, DtWin w, int tiles_x,
+                                                  const unsigned long long *__restrict__ rec,
+                                                  const unsigned long long *__restrict__ state,
                                                   const unsigned long long *__restrict__ ext,
                                                   const uint16_t *__restrict__ loc16, int32_t *__restrict__ acc32,
                                                   int32_t river_thr, int8_t *__restrict__ river,
@@ -1298,8 +1411,10 @@ __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ f
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;
   const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
+  uint32_t c2[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // see k_fa_tile3
+  if (rec) fa_nbr_codes(fdr, w, y0, x0, threadIdx.x, c2);
   unsigned long long e = 0ull;
-  if (threadIdx.x < PS) e = ext[(size_t)tile * PS + threadIdx.x];
+  if (threadIdx.x < PS && ext) e = ext[(size_t)tile * PS + threadIdx.x];
   constexpr int VPT = NT / 4 / 256;
   uint2 l4[VPT];
   float4 z4[VPT];
@@ -1316,14 +1431,6 @@ __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ f
       z4[u] = make_float4((m & 1u) ? DT_NODATA : 0.f, (m & 2u) ? DT_NODATA : 0.f, (m & 4u) ? DT_NODATA : 0.f,
                           (m & 8u) ? DT_NODATA : 0.f);
     }
-  }
-  if (threadIdx.x == 0) s_ovf = 0;
-  if (__syncthreads_or(!(e & FA_CYCLE) && FA_VALUE(e) >= (1ull << 22))) {  // see k_fa_tile3
-    if (threadIdx.x == 0) s_in = 0ull;
-    __syncthreads();
-    if (e != 0ull && !(e & FA_CYCLE)) atomicAdd(&s_in, FA_VALUE(e));
-    __syncthreads();
-    if (threadIdx.x == 0 && s_in >= (1ull << 31) - (unsigned long long)NT && status) atomicOr(status, DT_STATUS_ACC_OVERFLOW);
   }
   // successor indices of the 16 cells whose codes this lane fetched (row t / 4, columns 16 (t % 4) ..): straight from
   // its registers, the padded row is contiguous -- four 8-byte stores of indices, four 16-byte stores of zeros
@@ -1346,7 +1453,17 @@ __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ f
       *reinterpret_cast<uint4 *>(&s_delta[pbase + 4 * q]) = make_uint4(0, 0, 0, 0);
     }
   }
-  __syncthreads();
+  // the feeders' words have been in flight behind the staging
+  if (rec) e = fa_inflow(fa_gather(c2, y0, x0, threadIdx.x, tiles_x, rec, state), e);
+  if (threadIdx.x == 0) s_ovf = 0;
+  // (its barrier also publishes the staging)
+  if (__syncthreads_or(!(e & FA_CYCLE) && FA_VALUE(e) >= (1ull << 22))) {  // see k_fa_tile3
+    if (threadIdx.x == 0) s_in = 0ull;
+    __syncthreads();
+    if (e != 0ull && !(e & FA_CYCLE)) atomicAdd(&s_in, FA_VALUE(e));
+    __syncthreads();
+    if (threadIdx.x == 0 && s_in >= (1ull << 31) - (unsigned long long)NT && status) atomicOr(status, DT_STATUS_ACC_OVERFLOW);
+  }
   if (e != 0ull) {
     int ly, lx;
     dt_cell_of_slot(threadIdx.x, ly, lx);
@@ -1873,28 +1990,29 @@ int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *f
     hipLaunchKernelGGL(k_fa_propagate, dim3((unsigned)((P + 255) / 256)), b, 0, s, w, f.tiles_x, f.nnodes, f.nxt,
                        ext_perim, P, f.ext);
   }
-  hipLaunchKernelGGL(k_fa_poison, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.state, f.ext);
+  if (dt_debug_get(DT_DBG_FA_SCATTER)) hipLaunchKernelGGL(k_fa_poison, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.state, f.ext);
   const bool fused = !acc64 && dt_debug_get(DT_DBG_NO_FUSED_FA_FH) == 0 && w.W % TW == 0 && (w.ld & 3) == 0 &&
                      (((uintptr_t)acc | (uintptr_t)dem) & 15) == 0 && ((uintptr_t)river & 3) == 0;
   if (fused) {
+    const FaIn in = fa_inputs(f, ext_perim);
     int32_t thr = river_thr > 2147483647ll ? 2147483647 : (river_thr < -2147483647ll ? -2147483647 : (int32_t)river_thr);
     // the single raster's window starts on the mask's 4-cell grid; a rank's window need not: the DEM there
     const bool use_mask = nod4 != nullptr && w.halo == 0 && w.gx0 == 0 && w.gy0 == 0;
     if (use_mask)
-      hipLaunchKernelGGL(k_fa3fh1<2>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, f.ext, f.loc16, (int32_t *)acc, thr,
+      hipLaunchKernelGGL(k_fa3fh1<2>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, (int32_t *)acc, thr,
                          river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide);
     else if (dem)
-      hipLaunchKernelGGL(k_fa3fh1<1>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, f.ext, f.loc16, (int32_t *)acc, thr,
+      hipLaunchKernelGGL(k_fa3fh1<1>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, (int32_t *)acc, thr,
                          river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide);
     else
-      hipLaunchKernelGGL(k_fa3fh1<0>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, f.ext, f.loc16, (int32_t *)acc, thr,
+      hipLaunchKernelGGL(k_fa3fh1<0>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, (int32_t *)acc, thr,
                          river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide);
   } else {
     if (acc64) {
-      fa_launch_tile3<long long>(s, gt, w, fdr, dem, f, (long long *)acc, (long long)river_thr, river, status);
+      fa_launch_tile3<long long>(s, gt, w, fdr, dem, f, ext_perim, (long long *)acc, (long long)river_thr, river, status);
     } else {
       int32_t thr = river_thr > 2147483647ll ? 2147483647 : (river_thr < -2147483647ll ? -2147483647 : (int32_t)river_thr);
-      fa_launch_tile3<int32_t>(s, gt, w, fdr, dem, f, (int32_t *)acc, thr, river, status);
+      fa_launch_tile3<int32_t>(s, gt, w, fdr, dem, f, ext_perim, (int32_t *)acc, thr, river, status);
     }
     hipLaunchKernelGGL(k_fh_tile1n, gt, b, 0, s, fdr, river, w, h.tiles_x, (uint32_t)h.nnodes, h.nodes, h.cache,
                        h.cache_wide);
