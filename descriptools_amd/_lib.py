@@ -152,6 +152,21 @@ _SIGS = {
     "dt_dev_slope_twi_f64": (ci, [vp, vp, vp, i64, i64, f64, f64, vp, vp, vp, vp]),
     "dt_dev_downslope_f64": (ci, [vp, vp, vp, i64, i64, f64, f64, ci, vp]),
     "dt_dev_hand_gfi_f64": (ci, [vp, vp, vp, vp, i64, i64, f64, f64, f64, vp, vp, vp]),
+    # one rank's step on float64 heights (tiling.RankTile(heights="float64"))
+    "dt_dev_slope_d8_f64_w": (ci, [vp, vp, vp, f64, vp, vp]),
+    "dt_dev_slope_twi_f64_w": (ci, [vp, vp, vp, vp, f64, f64, vp, vp, vp, vp]),
+    "dt_dev_slope_twi_f64_w_a64": (ci, [vp, vp, vp, vp, f64, f64, vp, vp, vp, vp]),
+    "dt_dev_downslope_f64_w": (ci, [vp, vp, vp, vp, f64, f64, ci, vp, vp]),
+    "dt_dev_downslope_walk_seed_f64_w": (ci, [vp, vp, vp, i64, vp, vp, vp]),
+    "dt_dev_downslope_walk_route_f64_w": (ci, [vp, vp, vp, vp, f64, f64, i64, vp, vp, vp, C.c_int32, vp, C.c_int32,
+                                               vp, vp, vp]),
+    "dt_dev_flowhand_zr64_w": (ci, [vp, vp, vp, i64, vp, vp, vp]),
+    "dt_dev_rank_solve_flowhand_f64": (ci, [vp, ci, ci, c_i64p, c_i64p, i64, vp, i64, c_i64p, ci, i64, vp, vp, vp, vp,
+                                            vp, vp, vp]),
+    "dt_hand_f64_table_bytes": (i64, [i64]),
+    "dt_dev_hand_gfi_f64_w": (ci, [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, f64, f64, f64, vp, vp, vp]),
+    "dt_dev_hand_gfi_f64_w_a64": (ci, [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, f64, f64, f64, vp, vp,
+                                       vp]),
 }
 
 

@@ -90,7 +90,7 @@ class Chain:
         # in float64 as the reference takes it in the DEM's own dtype.  buf["hand"] is then float64 (the reference's
         # HAND dtype on such a DEM); every other output keeps its dtype and meaning.  Out of scope on float64 heights:
         # condition=True (conditioned codes come in through external_fdr: dt_dev_condition_d8_f64_async), long_walks
-        # (the skip tables are float32), tiling.RankTile / several GPUs.
+        # (the skip tables are float32).  Several GPUs: tiling.RankTile(heights="float64").
         if heights not in HEIGHTS:
             raise ValueError("heights must be one of %s, not %r" % (HEIGHTS, heights))
         self.wide = heights == "float64"

@@ -1294,6 +1294,138 @@ extern "C" int dt_dev_rank_solve_flowhand(dt_ctx *c, int ty, int tx, const int64
   return DT_OK;
 }
 
+// ---- float64 heights on one rank's window (tiling.RankTile(heights="float64")) ------------------------------------
+extern "C" int dt_dev_slope_d8_f64_w(dt_ctx *c, const dt_window *win, const double *dem, double px, uint8_t *fdr,
+                                     float *proxy) {
+  DT_CTX(c);
+  DtWin w;
+  DT_TRY(dt_convert_window(win, &w));
+  DT_REQUIRE(dem && (fdr || proxy), "NULL raster");
+  DT_TRY(dt_launch_d8_f64_w(c->stream, w, dem, px, fdr, proxy));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+static int dev_slope_twi_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const void *acc, int acc64,
+                               double px, double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
+  DT_CTX(c);
+  DtWin w;
+  DT_TRY(dt_convert_window(win, &w));
+  DT_REQUIRE(dem && acc && ti && mti, "NULL raster");
+  DT_TRY(dt_launch_slope_twi_f64_w(c->stream, w, dem, acc, acc64, px, n_top, slope, slope_rad, ti, mti));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_slope_twi_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const int32_t *acc32,
+                                      double px, double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
+  return dev_slope_twi_f64_w(c, win, dem, acc32, 0, px, n_top, slope, slope_rad, ti, mti);
+}
+extern "C" int dt_dev_slope_twi_f64_w_a64(dt_ctx *c, const dt_window *win, const double *dem, const int64_t *acc64,
+                                          double px, double n_top, float *slope, float *slope_rad, float *ti,
+                                          float *mti) {
+  return dev_slope_twi_f64_w(c, win, dem, acc64, 1, px, n_top, slope, slope_rad, ti, mti);
+}
+extern "C" int dt_dev_downslope_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const uint8_t *fdr,
+                                      double px, double dz, int raw, float *out, int32_t *n_unresolved_dev) {
+  DT_CTX(c);
+  DtWin w;
+  DT_TRY(dt_convert_window(win, &w));
+  DT_REQUIRE(dem && fdr && out, "NULL raster");
+  if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
+  DT_TRY(dt_launch_downslope_win_f64_w(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_downslope_walk_seed_f64_w(dt_ctx *c, const dt_window *win, const double *dem, int64_t n,
+                                                const int32_t *ys, const int32_t *xs, void *rec) {
+  DT_CTX(c);
+  DtWin w;
+  DT_TRY(dt_convert_window(win, &w));
+  DT_REQUIRE(n >= 0, "negative count");
+  DT_REQUIRE(n == 0 || (dem && ys && xs && rec), "NULL pointer");
+  DT_TRY(dt_launch_ds_walk_seed_f64(c->stream, w, dem, n, ys, xs, rec));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_downslope_walk_route_f64_w(dt_ctx *c, const dt_window *win, const double *dem,
+                                                 const uint8_t *fdr, double px, double dz, int64_t n, void *rec,
+                                                 float *out, const int32_t *row_starts, int32_t ty,
+                                                 const int32_t *col_starts, int32_t tx, void *send, int32_t *counts,
+                                                 int32_t *scratch) {
+  DT_CTX(c);
+  DtWin w;
+  DT_TRY(dt_convert_window(win, &w));
+  DT_REQUIRE(n >= 0, "negative count");
+  DT_REQUIRE(ty >= 1 && tx >= 1 && row_starts && col_starts && counts, "layout / counts missing");
+  DT_REQUIRE(n == 0 || (dem && fdr && rec && out && send && scratch), "NULL pointer");
+  DT_TRY(dt_launch_ds_walk_f64(c->stream, w, dem, fdr, px, dz, n, rec, out));
+  DT_TRY(dt_launch_ds_route(c->stream, n, rec, row_starts, ty, col_starts, tx, send, counts, scratch));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_flowhand_zr64_w(dt_ctx *c, const dt_window *win, const double *dem, int64_t n,
+                                      const uint8_t *kind, const int32_t *ref, double *zr64) {
+  DT_CTX(c);
+  DtWin w;
+  DT_TRY(dt_convert_window(win, &w));
+  DT_REQUIRE(n >= 0 && n <= dt_perim_count(w.H, w.W), "bad ring size");
+  DT_REQUIRE(n == 0 || (dem && kind && ref && zr64), "NULL pointer");
+  DT_TRY(dt_launch_fh_zr64_w(c->stream, w, dem, n, kind, ref, zr64));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_rank_solve_flowhand_f64(dt_ctx *c, int ty, int tx, const int64_t *heights, const int64_t *widths,
+                                              int64_t Pmax, const void *rows_dev, int64_t rowbytes,
+                                              const int64_t *field_offsets8, int rank, int64_t P_rank,
+                                              uint8_t *res_ok, int32_t *res_nc, int32_t *res_nd, int64_t *rem_gidx,
+                                              float *rem_zr, int64_t *rem_ar, double *rem_zr64) {
+  DT_CTX(c);
+  DT_REQUIRE(heights && widths && rows_dev && field_offsets8 && res_ok && res_nc && res_nd && rem_gidx && rem_zr &&
+                 rem_ar && rem_zr64, "NULL pointer");
+  DT_REQUIRE(rank >= 0 && rank < ty * tx && P_rank >= 0 && P_rank <= Pmax, "bad rank / ring size");
+  DT_REQUIRE(field_offsets8[7] % 8 == 0 && rowbytes % 8 == 0, "the float64 field must be 8-byte aligned");
+  DT_TRY(dt_scratch2_reserve(c, dt_rank_solve_scratch(ty * tx, Pmax)));
+  DT_TRY(dt_launch_rank_solve_flowhand_f64(c->stream, ty, tx, heights, widths, Pmax, rows_dev, rowbytes,
+                                           field_offsets8, rank, P_rank, c->scratch2, res_ok, res_nc, res_nd,
+                                           (long long *)rem_gidx, rem_zr, (long long *)rem_ar, rem_zr64));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int64_t dt_hand_f64_table_bytes(int64_t n_remote) {
+  return n_remote < 0 ? -1 : dt_hand_f64_table_slots(n_remote) * 16;
+}
+static int dev_hand_gfi_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const int32_t *idx32,
+                              const int64_t *idx64, const void *acc, const void *a_river, int acc64, int64_t n_remote,
+                              const uint8_t *res_ok, const int64_t *rem_gidx, const double *rem_zr64, void *table,
+                              int64_t table_bytes, double px, double n_gfi, double b, double *hand, float *gfi,
+                              float *lnhlh) {
+  DT_CTX(c);
+  DtWin w;
+  DT_TRY(dt_convert_window(win, &w));
+  DT_REQUIRE(dem && (idx32 || idx64) && acc && a_river && hand, "NULL raster");
+  DT_REQUIRE(n_remote >= 0 && (n_remote == 0 || !res_ok || (rem_gidx && rem_zr64)), "incomplete rank-exit results");
+  DT_REQUIRE(table && table_bytes >= dt_hand_f64_table_bytes(n_remote), "river-height table missing or too small");
+  DT_TRY(dt_launch_hand_gfi_f64_w(c->stream, w, dem, idx64 ? nullptr : idx32, idx64, acc, a_river, acc64, n_remote,
+                                  res_ok, rem_gidx, rem_zr64, table, n_gfi, b, px, hand, gfi, lnhlh));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+extern "C" int dt_dev_hand_gfi_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const int32_t *idx32,
+                                     const int64_t *idx64, const int32_t *acc32, const int32_t *a_river32,
+                                     int64_t n_remote, const uint8_t *res_ok, const int64_t *rem_gidx,
+                                     const double *rem_zr64, void *table, int64_t table_bytes, double px,
+                                     double n_gfi, double b, double *hand, float *gfi, float *lnhlh) {
+  return dev_hand_gfi_f64_w(c, win, dem, idx32, idx64, acc32, a_river32, 0, n_remote, res_ok, rem_gidx, rem_zr64,
+                            table, table_bytes, px, n_gfi, b, hand, gfi, lnhlh);
+}
+extern "C" int dt_dev_hand_gfi_f64_w_a64(dt_ctx *c, const dt_window *win, const double *dem, const int32_t *idx32,
+                                         const int64_t *idx64, const int64_t *acc64, const int64_t *a_river64,
+                                         int64_t n_remote, const uint8_t *res_ok, const int64_t *rem_gidx,
+                                         const double *rem_zr64, void *table, int64_t table_bytes, double px,
+                                         double n_gfi, double b, double *hand, float *gfi, float *lnhlh) {
+  return dev_hand_gfi_f64_w(c, win, dem, idx32, idx64, acc64, a_river64, 1, n_remote, res_ok, rem_gidx, rem_zr64,
+                            table, table_bytes, px, n_gfi, b, hand, gfi, lnhlh);
+}
+
 // ---- host tier: H2D, kernels, D2H on a process-wide default context ----------------------------
 static dt_ctx *g_host_ctx = nullptr;
 static std::mutex g_host_mu;  // whole-call granularity, as SURVEY.md 8b (threading) allows

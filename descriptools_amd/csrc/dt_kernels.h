@@ -65,6 +65,24 @@ int dt_launch_downslope_win_f64(hipStream_t s, const double *dem, const uint8_t 
                                 double dz, int raw, float *out);
 int dt_launch_hand_gfi_f64(hipStream_t s, const double *dem, const int32_t *idx32, const int32_t *acc32, int64_t n,
                            double expo, double b, double size, double *hand, float *gfi, float *lnhlh);
+// ... and on one rank's window (tiling.RankTile(heights="float64")): dt_stencil.hip, dt_wide.hip, dt_kernels.hip (walkers),
+// dt_tiles.hip (the rank-level HAND solve with the float64 river height)
+int dt_launch_d8_f64_w(hipStream_t s, const DtWin &w, const double *dem, double px, uint8_t *fdr, float *proxy);
+int dt_launch_slope_twi_f64_w(hipStream_t s, const DtWin &w, const double *dem, const void *acc, int acc64, double px,
+                              double n_top, float *slope, float *slope_rad, float *ti, float *mti);
+int dt_launch_downslope_win_f64_w(hipStream_t s, const DtWin &w, const double *dem, const uint8_t *fdr, double px,
+                                  double dz, int raw, float *out, int *n_unresolved);
+int dt_launch_fh_zr64_w(hipStream_t s, const DtWin &w, const double *dem, int64_t n, const uint8_t *kind,
+                        const int32_t *ref, double *zr64);
+int64_t dt_hand_f64_table_slots(int64_t n_remote);
+int dt_launch_hand_gfi_f64_w(hipStream_t s, const DtWin &w, const double *dem, const int32_t *idx32,
+                             const int64_t *idx64, const void *fac, const void *a_river, int acc64, int64_t n_remote,
+                             const uint8_t *res_ok, const int64_t *rem_gidx, const double *rem_zr64, void *table,
+                             double expo, double b, double size, double *hand, float *gfi, float *lnhlh);
+int dt_launch_ds_walk_f64(hipStream_t s, const DtWin &w, const double *dem, const uint8_t *fdr, double px, double dz,
+                          int64_t n, void *rec, float *out);
+int dt_launch_ds_walk_seed_f64(hipStream_t s, const DtWin &w, const double *dem, int64_t n, const int32_t *ys,
+                               const int32_t *xs, void *rec);
 int dt_launch_confusion(hipStream_t s, const double *desc, const int8_t *flood, int64_t n,
                         double nodata, const double *th_host, int nth, int under,
                         unsigned long long *counts4);
@@ -125,6 +143,10 @@ int dt_launch_rank_solve_flowhand(hipStream_t s, int ty, int tx, const int64_t *
                                   int64_t Pmax, const void *rows, int64_t rowbytes, const int64_t *offs, int rank,
                                   int64_t P_rank, void *scratch, uint8_t *res_ok, int32_t *res_nc,
                                   int32_t *res_nd, long long *gidx, float *zr, long long *ar);
+int dt_launch_rank_solve_flowhand_f64(hipStream_t s, int ty, int tx, const int64_t *heights, const int64_t *widths,
+                                      int64_t Pmax, const void *rows, int64_t rowbytes, const int64_t *offs8, int rank,
+                                      int64_t P_rank, void *scratch, uint8_t *res_ok, int32_t *res_nc,
+                                      int32_t *res_nd, long long *gidx, float *zr, long long *ar, double *zr64);
 
 // hydrological conditioning (dt_hydro.hip): depression filling + flat resolution; synchronous
 size_t dt_hydro_scratch(int64_t H, int64_t W);

@@ -1584,6 +1584,92 @@ int dt_launch_ds_walk_seed(hipStream_t s, const DtWin &w, const float *dem, int6
     hipLaunchKernelGGL(k_ds_walk_seed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dem, w, n, ys, xs, (uint4 *)rec);
   return DT_OK;
 }
+
+// Walkers on float64 heights (tiling.RankTile(heights="float64")): always DSW_SEQ -- the reference's sequential float64
+// path length in r2.x:y, as k_downslope_win_f64 sums it, so no count form and no rounding test -- and the start height
+// as a double: its low word in r1.z, its high word in r2.w (0 in float32 records).  Same 48 bytes, the same flags, so
+// k_dsw_classify / k_dsw_scatter and the exchange are shared.
+__device__ __forceinline__ double dsw_z0_f64(const uint4 &r1, const uint4 &r2) {
+  return __longlong_as_double((long long)(((unsigned long long)r2.w << 32) | (unsigned long long)r1.z));
+}
+__global__ __launch_bounds__(256) void k_ds_walk_f64(const double *__restrict__ dem, const uint8_t *__restrict__ fdr,
+                                                    DtWin w, double px, double dz, int64_t n, uint4 *__restrict__ rec,
+                                                    float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint4 r0 = rec[3 * i], r1 = rec[3 * i + 1];
+  if (r1.w & DSW_DONE) {  // home: as k_ds_walk
+    if (out && !(r1.w & DSW_HOME)) {
+      const int ys = (int)r0.x - w.gy0, xs = (int)r0.y - w.gx0;
+      if (dt_in_core(w, ys, xs)) {
+        out[(long long)ys * w.ld + xs] = __uint_as_float(rec[3 * i + 2].z);
+        r1.w |= DSW_HOME;
+        rec[3 * i + 1] = r1;
+      }
+    }
+    return;
+  }
+  int y = (int)r0.z - w.gy0, x = (int)r0.w - w.gx0;
+  if (!dt_has_code(w, y, x)) return;  // not mine: somebody else's walker
+  const double dcard = px, ddiag = px * sqrt(2.0);
+  const uint4 r2 = rec[3 * i + 2];
+  const double z0 = dsw_z0_f64(r1, r2);
+  double d = __longlong_as_double((long long)(((unsigned long long)r2.y << 32) | (unsigned long long)r2.x));
+  uint32_t loop = r1.x;
+  bool done = false;
+  double drop = loop > 0u ? z0 - dem[(long long)y * w.ld + x] : z0 - z0;
+  while (drop < dz) {
+    if (!dt_has_code(w, y, x)) break;  // the end of my memory: hand over
+    const uint32_t code = fdr[(long long)y * w.ld + x];
+    if (!dt_d8_valid(code)) { done = true; break; }
+    int dy, dx;
+    dt_d8_delta(code, dy, dx);
+    const int ny = y + dy, nx = x + dx;
+    if (!dt_in_global(w, ny, nx)) { done = true; break; }
+    if (!dt_readable(w, ny, nx)) break;
+    const double zt = dem[(long long)ny * w.ld + nx];
+    if (zt == -100.0) { done = true; break; }
+    y = ny;
+    x = nx;
+    d += (dy != 0 && dx != 0) ? ddiag : dcard;
+    drop = z0 - zt;
+    if (++loop == 5000u) { done = true; break; }
+  }
+  if (!(drop < dz)) done = true;
+  r0.z = (uint32_t)(y + w.gy0);
+  r0.w = (uint32_t)(x + w.gx0);
+  rec[3 * i] = r0;
+  rec[3 * i + 1] = make_uint4(loop, 0u, r1.z, DSW_SEQ | (done ? DSW_DONE : 0u));
+  const unsigned long long db = (unsigned long long)__double_as_longlong(d);
+  const float value = d == 0.0 ? 0.0f : (float)(drop / d);
+  rec[3 * i + 2] = make_uint4((uint32_t)db, (uint32_t)(db >> 32), __float_as_uint(value), r2.w);
+}
+int dt_launch_ds_walk_f64(hipStream_t s, const DtWin &w, const double *dem, const uint8_t *fdr, double px, double dz,
+                          int64_t n, void *rec, float *out) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_ds_walk_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dem, fdr, w, px, dz, n,
+                       (uint4 *)rec, out);
+  return DT_OK;
+}
+__global__ __launch_bounds__(256) void k_ds_walk_seed_f64(const double *__restrict__ dem, DtWin w, int64_t n,
+                                                         const int32_t *__restrict__ ys, const int32_t *__restrict__ xs,
+                                                         uint4 *__restrict__ rec) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int y = ys[i], x = xs[i];
+  const uint32_t gy = (uint32_t)(y + w.gy0), gx = (uint32_t)(x + w.gx0);
+  const unsigned long long zb = (unsigned long long)__double_as_longlong(dem[(long long)y * w.ld + x]);
+  rec[3 * i] = make_uint4(gy, gx, gy, gx);
+  rec[3 * i + 1] = make_uint4(0u, 0u, (uint32_t)zb, DSW_SEQ);
+  rec[3 * i + 2] = make_uint4(0u, 0u, 0u, (uint32_t)(zb >> 32));
+}
+int dt_launch_ds_walk_seed_f64(hipStream_t s, const DtWin &w, const double *dem, int64_t n, const int32_t *ys,
+                               const int32_t *xs, void *rec) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_ds_walk_seed_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dem, w, n, ys, xs,
+                       (uint4 *)rec);
+  return DT_OK;
+}
 // workspaces of the long-walk acceleration for an H x W raster: the QUEUE (counter | one entry per two cells) and the
 // TABLES (two ping-pong skip tables and the 8-move table that is kept); dt_downslope_lift_bytes = both, back to back
 static size_t ds_queue_capacity(int64_t H, int64_t W) { return (size_t)((H * W + 1) / 2); }

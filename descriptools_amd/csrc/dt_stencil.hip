@@ -1110,3 +1110,153 @@ int dt_launch_slope_twi_f64(hipStream_t s, const double *dem, const int32_t *acc
                        lnpx2, slope, slope_rad, ti, mti, g_tab);
   return DT_OK;
 }
+
+// ---- the same two stencils on one rank's window of a larger raster (tiling.RankTile(heights="float64")) ----------------
+// The tile is staged from the rank's memory (core + halo, row stride w.ld; pointers at the core origin); a cell outside
+// the GLOBAL raster is staged as -100, the reference's ring, so the result at every cell is the single raster's.  The
+// border rule of D8 looks at the global raster's edges.
+__device__ __forceinline__ void sw_stage_w(double *t, const double *__restrict__ dem, const DtWin &w, int x0, int y0) {
+  constexpr int N = (SW_TY + 2) * SW_LDW, NV = (N + 255) / 256;
+  double v[NV];
+#pragma unroll
+  for (int u = 0; u < NV; u++) {
+    const int i = (int)threadIdx.x + 256 * u;
+    const int r = i / SW_LDW, c = i - r * SW_LDW;
+    const int y = y0 - 1 + r, x = x0 - 1 + c;
+    v[u] = -100.0;
+    if (i < N && dt_readable(w, y, x)) v[u] = dem[(long long)y * w.ld + x];
+  }
+#pragma unroll
+  for (int u = 0; u < NV; u++) {
+    const int i = (int)threadIdx.x + 256 * u;
+    if (i < N) t[i] = v[u];
+  }
+}
+
+// k_d8_f64 on a window (fdr and proxy may each be NULL)
+__global__ __launch_bounds__(256) void k_d8_f64_w(const double *__restrict__ dem, DtWin w, double px,
+                                                  uint8_t *__restrict__ fdr, float *__restrict__ proxy) {
+  __shared__ double t[(SW_TY + 2) * SW_LDW];
+  const int x0 = (int)blockIdx.x * SW_TX, y0 = (int)blockIdx.y * SW_TY;
+  sw_stage_w(t, dem, w, x0, y0);
+  __syncthreads();
+  const int tx = (int)threadIdx.x & 63, ty = (int)threadIdx.x >> 6;
+  const int x = x0 + tx;
+  if (x >= w.W) return;
+  const double dcard = px, ddiag = px * sqrt(2.0);
+  const float above = -99.99999237060547f;  // the float32 value next to -100 towards 0
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = ty * 4 + j, y = y0 + r;
+    if (y >= w.H) break;
+    const double c = t[(r + 1) * SW_LDW + tx + 1];
+    const long long o = (long long)y * w.ld + x;
+    const bool nod = c <= -100.0;  // slope.py:231
+    if (fdr) {
+      double nb[8];
+      sw_nbrs(t, r, tx, nb);
+      double dc, dd;
+      sw_class_max(c, nb, dc, dd);
+      const double qc = dc > 0.0 ? dc / dcard : 0.0, qd = dd > 0.0 ? dd / ddiag : 0.0;
+      uint32_t code = nod ? 0u : sw_d8_code(c, nb, dc, dd, qc, qd, dcard, ddiag);
+      if (code == 0u && !nod) {  // N1 border rule, on the global raster's edges
+        const int gy = w.gy0 + y, gx = w.gx0 + x;
+        code = gy == w.Hg - 1 ? 4u : (gy == 0 ? 64u : (gx == 0 ? 16u : (gx == w.Wg - 1 ? 1u : 0u)));
+      }
+      fdr[o] = (uint8_t)code;
+    }
+    if (proxy) {
+      const float f = (float)c;
+      proxy[o] = nod ? DT_NODATA : (f <= DT_NODATA ? above : f);
+    }
+  }
+}
+
+// k_slope_twi_f64 on a window, on an int32 or int64 accumulation raster (AccT)
+template <bool W_RAD, typename AccT>
+__global__ __launch_bounds__(256) void k_slope_twi_f64_w(const double *__restrict__ dem, DtWin w, double px, double kc,
+                                                         double kd, const AccT *__restrict__ acc, double n_top,
+                                                         double lnpx2, float *__restrict__ slope,
+                                                         float *__restrict__ slope_rad, float *__restrict__ ti,
+                                                         float *__restrict__ mti, const DtLogEntry *__restrict__ g_tab) {
+  __shared__ double t[(SW_TY + 2) * SW_LDW];
+  const int x0 = (int)blockIdx.x * SW_TX, y0 = (int)blockIdx.y * SW_TY;
+  sw_stage_w(t, dem, w, x0, y0);
+  __syncthreads();
+  const int tx = (int)threadIdx.x & 63, ty = (int)threadIdx.x >> 6;
+  const int x = x0 + tx;
+  if (x >= w.W) return;
+  const double nlnpx2 = n_top * lnpx2;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = ty * 4 + j, y = y0 + r;
+    if (y >= w.H) break;
+    const long long o = (long long)y * w.ld + x;
+    const AccT f = acc[o];
+    const double c = t[(r + 1) * SW_LDW + tx + 1];
+    double nb[8];
+    sw_nbrs(t, r, tx, nb);
+    double dc, dd;
+    sw_class_max(c, nb, dc, dd);
+    const double qp = dc * kc > dd * kd ? dc * kc : dd * kd;
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(qp);
+    const uint32_t lo = (uint32_t)bits, hi = (uint32_t)(bits >> 32);
+    const bool near_mid = ((lo & 0x1FFFFFFFu) - (0x10000000u - SD_MID)) <= 2u * SD_MID;
+    const bool odd = ((hi >> 20) - 897u) > 253u && bits != 0ull;
+    bool flag = near_mid || odd;
+    float sl = (float)qp, rad = 0.0f, tv, mv;
+    const bool snod = c <= -100.0;  // slope.py:231
+    sl = snod ? DT_NODATA : sl;
+    flag = flag && !snod;
+    const float q = dt_pct_to_tan(sl);
+    const bool rnod = c == -100.0;
+    if (W_RAD) {
+      rad = rnod ? DT_NODATA : (float)dt_atanf_pos(q);
+      flag = flag || (!rnod && !(q >= 0.0f && q < 1e30f));
+    }
+    const bool tnod = f <= -100;  // topoindexes.py:252
+    flag = (sd_twi_fast(f, q, n_top, lnpx2, nlnpx2, tv, mv) && !tnod) || flag;
+    tv = tnod ? DT_NODATA : tv;
+    mv = tnod ? DT_NODATA : mv;
+    if (flag) {  // k_slope_twi_fix's exact path
+      const double dcard = px, ddiag = px * sqrt(2.0);
+      const double qc = dc > 0.0 ? dc / dcard : 0.0, qd = dd > 0.0 ? dd / ddiag : 0.0;
+      sl = snod ? DT_NODATA : (float)((qc > qd ? qc : qd) * 100.0);
+      rad = dt_slope_rad(sl, rnod ? DT_NODATA : 0.0f);
+      dt_twi_cell((int64_t)f, rad, lnpx2, n_top, tv, mv, g_tab);
+    }
+    if (slope) slope[o] = sl;
+    if (W_RAD) slope_rad[o] = rad;
+    ti[o] = tv;
+    mti[o] = mv;
+  }
+}
+
+int dt_launch_d8_f64_w(hipStream_t s, const DtWin &w, const double *dem, double px, uint8_t *fdr, float *proxy) {
+  if (w.H == 0 || w.W == 0) return DT_OK;
+  const dim3 g((unsigned)((w.W + SW_TX - 1) / SW_TX), (unsigned)((w.H + SW_TY - 1) / SW_TY));
+  DT_REQUIRE(g.y < 65536u, "window too tall for one launch");
+  hipLaunchKernelGGL(k_d8_f64_w, g, dim3(256), 0, s, dem, w, px, fdr, proxy);
+  return DT_OK;
+}
+
+int dt_launch_slope_twi_f64_w(hipStream_t s, const DtWin &w, const double *dem, const void *acc, int acc64, double px,
+                              double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
+  if (w.H == 0 || w.W == 0) return DT_OK;
+  const dim3 g((unsigned)((w.W + SW_TX - 1) / SW_TX), (unsigned)((w.H + SW_TY - 1) / SW_TY));
+  DT_REQUIRE(g.y < 65536u, "window too tall for one launch");
+  const double kc = 100.0 / px, kd = 100.0 / (px * sqrt(2.0)), lnpx2 = log(px * px);
+  const DtLogEntry *g_tab = dt_math_device_table(s);
+#define DT_STW64(R, T) \
+  hipLaunchKernelGGL((k_slope_twi_f64_w<R, T>), g, dim3(256), 0, s, dem, w, px, kc, kd, (const T *)acc, n_top, lnpx2, \
+                     slope, slope_rad, ti, mti, g_tab)
+  if (acc64) {
+    if (slope_rad) DT_STW64(true, int64_t);
+    else DT_STW64(false, int64_t);
+  } else {
+    if (slope_rad) DT_STW64(true, int32_t);
+    else DT_STW64(false, int32_t);
+  }
+#undef DT_STW64
+  return DT_OK;
+}

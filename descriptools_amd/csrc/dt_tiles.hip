@@ -2315,3 +2315,39 @@ int dt_launch_rank_solve_flowhand(hipStream_t s, int ty, int tx, const int64_t *
                      (long long)P_rank, res_ok, res_nc, res_nd, gidx, zr, ar);
   return DT_OK;
 }
+
+// float64 heights (tiling.RankTile(heights="float64")): the rows carry an eighth field, the river cell's height as a
+// double (k_fh_zr64_w); after the solve above, zr64[i] = that field at the entry ring cell i's path ends on (-100: none)
+__global__ __launch_bounds__(256) void k_rk_fh_zr64(RkLayout L, RkRows R, const unsigned long long *__restrict__ nodes,
+                                                   int rank, long long P_rank, double *__restrict__ zr64) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= P_rank) return;
+  double z = -100.0;
+  long long e = rk_step_target(L, rank, i, rk_get<uint8_t>(R, 6, rank, i));
+  if (e >= 0) {
+    unsigned long long wd = nodes[e];
+    uint32_t ptr = (uint32_t)(wd >> 32), ncf = (uint32_t)(wd & 0xFFFFu);
+    if ((ncf & FHT_DONE) && ptr != FHT_DEAD) {
+      int rt = (int)(ptr / (uint32_t)L.Pmax);
+      z = rk_get<double>(R, 7, rt, (long long)ptr - (long long)rt * L.Pmax);
+    }
+  }
+  zr64[i] = z;
+}
+int dt_launch_rank_solve_flowhand_f64(hipStream_t s, int ty, int tx, const int64_t *heights, const int64_t *widths,
+                                      int64_t Pmax, const void *rows, int64_t rowbytes, const int64_t *offs8, int rank,
+                                      int64_t P_rank, void *scratch, uint8_t *res_ok, int32_t *res_nc,
+                                      int32_t *res_nd, long long *gidx, float *zr, long long *ar, double *zr64) {
+  DT_TRY(dt_launch_rank_solve_flowhand(s, ty, tx, heights, widths, Pmax, rows, rowbytes, offs8, rank, P_rank, scratch,
+                                       res_ok, res_nc, res_nd, gidx, zr, ar));
+  RkLayout L;
+  DT_TRY(rk_make_layout(ty, tx, heights, widths, Pmax, &L));
+  RkRows R;
+  R.buf = (const unsigned char *)rows;
+  R.rowbytes = rowbytes;
+  for (int k = 0; k < 8; k++) R.off[k] = offs8[k];
+  if ((size_t)L.nranks * (size_t)Pmax == 0 || P_rank == 0) return DT_OK;
+  hipLaunchKernelGGL(k_rk_fh_zr64, dim3((unsigned)((P_rank + 255) / 256)), dim3(256), 0, s, L, R,
+                     (const unsigned long long *)scratch, rank, (long long)P_rank, zr64);
+  return DT_OK;
+}

@@ -257,6 +257,11 @@ FA_ROW_BYTES = 16
 FH_FIELDS = (("ref", "int32", 0), ("nc", "int32", 4), ("nd", "int32", 8), ("zr", "float32", 12),
              ("ar", "int64", 16), ("kind", "uint8", 24), ("ring", "uint8", 25))
 FH_ROW_BYTES = 32
+# on float64 heights (RankTile(heights="float64")) the HAND row carries the river cell's height as a double as well: the
+# float32 zr cannot give HAND's float64 difference for a river cell on another rank (dt_dev_rank_solve_flowhand_f64)
+FH_FIELDS_F64 = FH_FIELDS + (("zr64", "float64", 32),)
+FH_ROW_BYTES_F64 = 40
+HEIGHTS = ("float32", "float64")
 
 
 class RankTile:
@@ -264,7 +269,7 @@ class RankTile:
 
     def __init__(self, layout, rank, device=0, stream=None, px=10.0, n_top=0.1, n_gfi=0.4, b=0.1, dz=5.0,
                  river_threshold=None, halo=HALO, idx64=None, acc64=None, rasters=None, tune_placement=True,
-                 long_walks=False, emit_walkers=None):
+                 long_walks=False, emit_walkers=None, heights="float32"):
         """acc64: flow accumulation (and the river accumulation payload) as int64 rasters, the reference's dtype --
         the default for a global raster of more than 2^31 cells, where a basin can exceed 32 bits; int32 rasters
         otherwise (exact: an accumulation is at most cells - 1; half the bytes).  rasters: names of the rasters to allocate (default: all).
@@ -277,7 +282,21 @@ class RankTile:
         long_walks, i.e. on real terrain; without it such walks are found by their -50 marks and start again.
         long_walks: downslope with the long-walk workspace (dt_dev_downslope_lift_w: 8 bytes per core cell + 24 per
         cell of core + halo, allocated at the first downslope call) -- for real terrain, where flats and valley floors
-        make walks thousands of moves long; same results."""
+        make walks thousands of moves long; same results.
+        heights: "float32" (the default) or "float64" -- the DEM raster is float64 (a DEM float32 cannot hold), every
+        height difference is taken in float64 and hand is float64: the step gives chain.Chain(heights="float64")'s
+        rasters on the whole raster.  A float32 nodata proxy (written by the first kernel) stands in for the DEM where
+        the flow-accumulation / HAND-index kernels only test for nodata.  Float32-only: long_walks and emit_walkers,
+        conditioning (condition_rank / condition_ranks / cond_*), evaluate_rank."""
+        if heights not in HEIGHTS:
+            raise ValueError("heights must be one of %s, not %r" % (HEIGHTS, heights))
+        self.wide = heights == "float64"
+        if self.wide and long_walks:
+            raise ValueError("long_walks is float32-only: the skip tables hold float32 heights "
+                             "(RankTile(heights=\"float64\") walks with long_walks=False)")
+        if self.wide and emit_walkers:
+            raise ValueError("emit_walkers is float32-only: on float64 heights the walks that leave a rank are "
+                             "found by their -50 marks (finish_downslope)")
         import torch
         from . import _lib
         from .device import Context
@@ -285,6 +304,8 @@ class RankTile:
         self.layout, self.rank, self.halo = layout, rank, halo
         self.long_walks, self._lift_work = bool(long_walks), None
         self.emit_walkers = bool(long_walks) if emit_walkers is None else bool(emit_walkers)
+        # the raster the flow-accumulation / HAND-index kernels test for nodata: the DEM, or its float32 proxy
+        self._zf = "proxy" if self.wide else "dem"
         self._walkers = None
         self.H, self.W = layout.shape(rank)
         self.gy0, self.gx0 = layout.origin(rank)
@@ -320,15 +341,19 @@ class RankTile:
         self._f_fh_finish = getattr(L, "dt_dev_flowhand_finish_w" + sfx)
         self._f_fh_gfi_finish = getattr(L, "dt_dev_flowhand_gfi_finish_w" + sfx)
         self._f_gfi_lnhlh = getattr(L, "dt_dev_gfi_lnhlh" + sfx)
+        if self.wide:
+            self._f_slope_twi = getattr(L, "dt_dev_slope_twi_f64_w" + sfx)
+            self._f_hand_gfi = getattr(L, "dt_dev_hand_gfi_f64_w" + sfx)
+        hdt = torch.float64 if self.wide else torch.float32
         t = {}
         self._on_ts = torch.cuda.stream(self.ts)
         self._on_ts.__enter__()
-        for name, dt in (("dem", torch.float32), ("fdr", torch.uint8), ("fac", self.acc_dtype),
-                         ("river", torch.int8), ("fdist", torch.float32), ("idx", self.idx_dtype),
-                         ("hand", torch.float32), ("a_river", self.acc_dtype), ("slope", torch.float32),
-                         ("ti", torch.float32), ("mti", torch.float32), ("gfi", torch.float32),
-                         ("lnhlh", torch.float32), ("down", torch.float32)):
-            if rasters is None or name in rasters:
+        names = (("dem", hdt), ("fdr", torch.uint8), ("fac", self.acc_dtype), ("river", torch.int8),
+                 ("fdist", torch.float32), ("idx", self.idx_dtype), ("hand", hdt), ("a_river", self.acc_dtype),
+                 ("slope", torch.float32), ("ti", torch.float32), ("mti", torch.float32), ("gfi", torch.float32),
+                 ("lnhlh", torch.float32), ("down", torch.float32))
+        for name, dt in names + ((("proxy", torch.float32),) if self.wide else ()):
+            if rasters is None or name in rasters or name == "proxy":
                 t[name] = torch.zeros((self.He, self.We), dtype=dt, device=self.dev)
         self.t = t
         assert tune_placement in (False, True, "search")
@@ -344,11 +369,12 @@ class RankTile:
         pm = max(perim_count(*layout.shape(r)) for r in range(layout.size))
         self.pmax = pm = (pm + 7) // 8 * 8
         self.fa_row = torch.zeros(FA_ROW_BYTES * pm, dtype=torch.uint8, device=self.dev)
-        self.fh_row = torch.zeros(FH_ROW_BYTES * pm, dtype=torch.uint8, device=self.dev)
+        fh_fields, self._fh_row_bytes = (FH_FIELDS_F64, FH_ROW_BYTES_F64) if self.wide else (FH_FIELDS, FH_ROW_BYTES)
+        self.fh_row = torch.zeros(self._fh_row_bytes * pm, dtype=torch.uint8, device=self.dev)
         self._fa_v = self._row_views(self.fa_row, FA_FIELDS)
-        self._fh_v = self._row_views(self.fh_row, FH_FIELDS)
+        self._fh_v = self._row_views(self.fh_row, fh_fields)
         self._fa_offs = (C.c_int64 * 3)(*[o * pm for _, _, o in FA_FIELDS[:3]])
-        self._fh_offs = (C.c_int64 * 7)(*[o * pm for _, _, o in FH_FIELDS])
+        self._fh_offs = (C.c_int64 * len(fh_fields))(*[o * pm for _, _, o in fh_fields])
         self._heights = (C.c_int64 * layout.ty)(*layout.heights)
         self._widths = (C.c_int64 * layout.tx)(*layout.widths)
         self._ext = torch.zeros(max(self.P, 1), dtype=torch.int64, device=self.dev)
@@ -358,6 +384,9 @@ class RankTile:
                      torch.zeros(max(self.P, 1), dtype=torch.int64, device=self.dev),
                      torch.zeros(max(self.P, 1), dtype=torch.float32, device=self.dev),
                      torch.zeros(max(self.P, 1), dtype=torch.int64, device=self.dev))
+        if self.wide:  # the float64 river heights of the rank exits, and the table the HAND kernel looks them up in
+            self._res_zr64 = torch.zeros(max(self.P, 1), dtype=torch.float64, device=self.dev)
+            self._rtab = torch.empty(int(L.dt_hand_f64_table_bytes(self.P)), dtype=torch.uint8, device=self.dev)
         self._on_ts.__exit__(None, None, None)
         self.ctx.sync()  # the buffers exist and are zero before anybody (any stream) touches them
 
@@ -447,9 +476,11 @@ class RankTile:
         self.ctx.sync()
 
     def set_dem_ext(self, dem_ext):
-        """host array of the extended window (He x We); cells outside the global raster are ignored."""
+        """host array of the extended window (He x We); cells outside the global raster are ignored.  Kept as float64
+        on a heights="float64" tile, rounded to float32 otherwise."""
         with self.on_stream():
-            self.t["dem"].copy_(self.torch.as_tensor(np.ascontiguousarray(dem_ext, np.float32)))
+            dt = np.float64 if self.wide else np.float32
+            self.t["dem"].copy_(self.torch.as_tensor(np.ascontiguousarray(dem_ext, dt)))
         self.ctx.sync()
 
     # ---- local stages ------------------------------------------------------------------------------
@@ -462,13 +493,30 @@ class RankTile:
         y1, x1 = min(self.gy0 + self.H + m, self.layout.Hg), min(self.gx0 + self.W + m, self.layout.Wg)
         win = self._lib.Window(y1 - y0, x1 - x0, self.We, y0, x0, self.layout.Hg, self.layout.Wg, 1)
         off = ((y0 - (self.gy0 - h)) * self.We + (x0 - (self.gx0 - h)))
-        dem = self.t["dem"].data_ptr() + off * 4
+        dem = self.t["dem"].data_ptr() + off * self.t["dem"].element_size()
         fdr = self.t["fdr"].data_ptr() + off
+        if self.wide:  # (and the nodata proxy, over the same window)
+            self._chk(self.L.dt_dev_slope_d8_f64_w(self.ctx.h, C.byref(win), dem, self.px, fdr,
+                                                   self.t["proxy"].data_ptr() + off * 4))
+            return
         self._chk(self.L.dt_dev_slope_d8_w(self.ctx.h, C.byref(win), dem, self.px, None, fdr, None))
 
+    def nodata_proxy(self):
+        """the first stage of a step that starts from the D8 codes the tile holds (d8=False): on float64 heights the
+        float32 nodata proxy of the core (dt_dev_slope_d8_f64_w without codes); nothing on float32 heights"""
+        if self.wide:
+            self._chk(self.L.dt_dev_slope_d8_f64_w(self.ctx.h, C.byref(self.win), self.p("dem"), self.px, None,
+                                                   self.p("proxy")))
+
     # ---- hydrological conditioning (SURVEY.md 8f-4) over ranks: see condition_ranks ------------------------------
+    def _float32_only(self, what):
+        if self.wide:
+            raise ValueError("%s is float32-only: a RankTile(heights=\"float64\") takes conditioned codes from "
+                             "flowdir.d8_conditioned(heights=\"float64\") and runs its step with d8=False" % what)
+
     def cond_alloc(self):
         """the filled surface, the flat distances (extended rasters like the others) and the iteration flag"""
+        self._float32_only("conditioning over ranks")
         tc = self.torch
         if "filled" not in self.t:
             with self.on_stream():
@@ -482,6 +530,7 @@ class RankTile:
 
     def cond_stage(self, stage, rounds=1):
         """dt_dev_condition_stage_m_w on the core window; stages 1 / 3 / 4 start from a zeroed flag"""
+        self._float32_only("conditioning over ranks")
         if stage in (1, 3, 4):
             with self.on_stream():
                 self._cflag.zero_()
@@ -490,12 +539,14 @@ class RankTile:
                                                     self._cflag.data_ptr(), self.p("nsame")))
 
     def cond_flag(self):
+        self._float32_only("conditioning over ranks")
         self.ctx.sync()
         return int(self._cflag.item())
 
     def cond_d8(self):
         """D8 codes of the CORE from the filled surface (its halo comes from the neighbours' exchange); the codes of
         the halo are exchanged afterwards, not recomputed: they are the neighbours' conditioned codes"""
+        self._float32_only("conditioning over ranks")
         self._chk(self.L.dt_dev_slope_d8_w(self.ctx.h, C.byref(self.win), self.p("filled"), self.px, None,
                                            self.p("fdr"), None))
 
@@ -523,7 +574,7 @@ class RankTile:
         with self.on_stream():
             e = tc.as_tensor(ext.view(np.int64), device=self.dev) if ext is not None else None
         self._keep = e
-        self._chk(self._f_fa_finish(self.ctx.h, C.byref(self.win), self.p("fdr"), self.p("dem"),
+        self._chk(self._f_fa_finish(self.ctx.h, C.byref(self.win), self.p("fdr"), self.p(self._zf),
                                     e.data_ptr() if e is not None else None,
                                     self.river_threshold, self.p("fac"), self.p("river")))
 
@@ -542,7 +593,7 @@ class RankTile:
                                                    self._widths, self.pmax, rows.data_ptr(),
                                                    FA_ROW_BYTES * self.pmax, self._fa_offs, self.rank, self.P,
                                                    self._ext.data_ptr()))
-        self._chk(self._f_fa_finish(self.ctx.h, C.byref(self.win), self.p("fdr"), self.p("dem"),
+        self._chk(self._f_fa_finish(self.ctx.h, C.byref(self.win), self.p("fdr"), self.p(self._zf),
                                     self._ext.data_ptr(), self.river_threshold, self.p("fac"), self.p("river")))
 
     def fa_solve_finish_fh_local(self, rows):
@@ -554,11 +605,14 @@ class RankTile:
                                                    FA_ROW_BYTES * self.pmax, self._fa_offs, self.rank, self.P,
                                                    self._ext.data_ptr()))
         v = self._fh_v
-        self._chk(self._f_fa_finish_fh_local(self.ctx.h, C.byref(self.win), self.p("fdr"), self.p("dem"),
+        self._chk(self._f_fa_finish_fh_local(self.ctx.h, C.byref(self.win), self.p("fdr"), self.p(self._zf),
                                              self._ext.data_ptr(), self.river_threshold, self.p("fac"),
                                              self.p("river"), v["kind"].data_ptr(), v["ref"].data_ptr(),
                                              v["nc"].data_ptr(), v["nd"].data_ptr(), v["zr"].data_ptr(),
                                              v["ar"].data_ptr()))
+        if self.wide:  # the river cells' float64 heights into the HAND row (its eighth field)
+            self._chk(self.L.dt_dev_flowhand_zr64_w(self.ctx.h, C.byref(self.win), self.p("dem"), self.P,
+                                                    v["kind"].data_ptr(), v["ref"].data_ptr(), v["zr64"].data_ptr()))
 
     def _idx_args(self):
         """(idx32, idx64) of the windowed HAND calls: the one of the two that matches the idx raster's dtype"""
@@ -570,6 +624,7 @@ class RankTile:
         self.ctx.sync()
         self.t, self._keep, self._keep2, self._keep_rows, self._keep_rows2 = {}, None, None, None, None
         self.fa_row = self.fh_row = self._ext = self._res = self._fa_v = self._fh_v = self._lift_work = None
+        self._res_zr64 = self._rtab = None
         self._walkers = None
         self.side_ctx.close()
         self.ctx.close()
@@ -579,6 +634,9 @@ class RankTile:
         river-accumulation raster is then only an optional by-product)."""
         self._keep_rows2 = rows
         r = self._res
+        if self.wide:
+            self._fh_solve_finish_f64(rows)
+            return
         self._chk(self.L.dt_dev_rank_solve_flowhand(self.ctx.h, self.layout.ty, self.layout.tx, self._heights,
                                                     self._widths, self.pmax, rows.data_ptr(),
                                                     FH_ROW_BYTES * self.pmax, self._fh_offs, self.rank, self.P,
@@ -594,7 +652,27 @@ class RankTile:
                                         *[a.data_ptr() for a in r], self.p("fdist"),
                                         *self._idx_args(), self.p("hand"), self.p("a_river")))
 
+    def _fh_solve_finish_f64(self, rows):
+        """fh_solve_finish of a float64 tile: the rank-level solve with the float64 river heights; HAND's last pass
+        writes fdist, idx and the river-accumulation payload (no heights); a pass of its own takes HAND in float64 from
+        the DEM -- the river cell's height from this rank's memory, or from the solve for a river cell on another rank
+        -- and GFI / ln(hl/H) from it (chain.Chain(heights="float64")'s split of the same work)"""
+        r, L = self._res, self.L
+        self._chk(L.dt_dev_rank_solve_flowhand_f64(self.ctx.h, self.layout.ty, self.layout.tx, self._heights,
+                                                   self._widths, self.pmax, rows.data_ptr(),
+                                                   self._fh_row_bytes * self.pmax, self._fh_offs, self.rank, self.P,
+                                                   *[a.data_ptr() for a in r], self._res_zr64.data_ptr()))
+        self._chk(self._f_fh_finish(self.ctx.h, C.byref(self.win), None, self.p("fdr"), self.p("river"),
+                                    self.p("fac"), self.px, *[a.data_ptr() for a in r], self.p("fdist"),
+                                    *self._idx_args(), None, self.p("a_river")))
+        i32, i64 = self._idx_args()
+        self._chk(self._f_hand_gfi(self.ctx.h, C.byref(self.win), self.p("dem"), i32, i64, self.p("fac"),
+                                   self.p("a_river"), self.P, r[0].data_ptr(), r[3].data_ptr(),
+                                   self._res_zr64.data_ptr(), self._rtab.data_ptr(), self._rtab.numel(), self.px,
+                                   self.n_gfi, self.b, self.p("hand"), self.p("gfi"), self.p("lnhlh")))
+
     def fh_local(self, sync=True):
+        self._float32_only("the host-solved HAND phases (simulate)")
         v = self._fh_v
         kind, ref, nc, nd, zr, ar = v["kind"], v["ref"], v["nc"], v["nd"], v["zr"], v["ar"]
         self._chk(self._f_fh_local(self.ctx.h, C.byref(self.win), self.p("dem"), self.p("fdr"),
@@ -606,6 +684,7 @@ class RankTile:
         return kind, ref, nc, nd, zr, ar
 
     def fh_finish(self, res):
+        self._float32_only("the host-solved HAND phases (simulate)")
         tc = self.torch
         ptrs = [None] * 6
         if res is not None:
@@ -624,6 +703,7 @@ class RankTile:
 
     def gfi(self):
         """GFI + ln(hl/H) over the flat extended rasters (halo cells hold zeros and are never read back)."""
+        self._float32_only("gfi() over the extended rasters (simulate)")
         t, n = self.t, self.He * self.We
         self._chk(self._f_gfi_lnhlh(self.ctx.h, t["hand"].data_ptr(), t["a_river"].data_ptr(),
                                     t["fac"].data_ptr(), n, self.n_gfi, self.b, self.px,
@@ -636,6 +716,10 @@ class RankTile:
         if side:
             self.ctx.fork(self.side_ctx)
             ctx = self.side_ctx
+        if self.wide:
+            self._chk(self.L.dt_dev_downslope_f64_w(ctx.h, C.byref(self.win), self.p("dem"), self.p("fdr"), self.px,
+                                                    self.dz, 0, self.p("down"), self.n_unres.data_ptr()))
+            return
         if self.long_walks and self._lift_work is None:
             nb = int(self.L.dt_downslope_lift_workspace_w(C.byref(self.win)))
             with self.on_stream():
@@ -929,7 +1013,8 @@ def rank_ops(tile, layout, exchange, d8=True):
     kernels (downslope; slope+TI+MTI) are queued between each gather's launch and the wait on it, so they overlap
     the transfer.  Nothing synchronises with the host.  d8=False: the tile already holds its D8 codes, core and halo
     (condition_rank / condition_ranks: the conditioned codes; or a D8 raster from a GIS tool, Example/example.py:36) --
-    the "d8" stage is then a no-op instead of overwriting them with the plain steepest descent."""
+    the "d8" stage is then a no-op instead of overwriting them with the plain steepest descent (on float64 heights it
+    writes the nodata proxy only: RankTile.nodata_proxy)."""
     st = {}
 
     def fa_local():
@@ -950,7 +1035,7 @@ def rank_ops(tile, layout, exchange, d8=True):
         exchange.wait()
         tile.fh_solve_finish(st["fh"], fuse_gfi=True, want_a_river=False)
 
-    calls = (tile.d8 if d8 else (lambda: None), fa_local, fa_gather, tile.downslope, fa_finish_fh_local, fh_gather,
+    calls = (tile.d8 if d8 else tile.nodata_proxy, fa_local, fa_gather, tile.downslope, fa_finish_fh_local, fh_gather,
              tile.slope_twi, fh_finish)
     return [(name, fn) for (name, _), fn in zip(RANK_OPS, calls)]
 
@@ -966,6 +1051,8 @@ def run_rank(tile, layout, exchange, overlap=True, d8=True):
         return
     if d8:
         tile.d8()
+    else:
+        tile.nodata_proxy()
     tile.downslope(side=True)
     tile.fa_local(sync=False)
     tile.fill_ring_codes()
@@ -982,7 +1069,9 @@ def run_rank(tile, layout, exchange, overlap=True, d8=True):
 def simulate(tiles, layout):
     """N logical ranks on ONE device, lock-step, with the all-gathers replaced by list collection and the
     rank-level solves done by the numpy restatement (solve_flowacc / solve_flowhand): what proves
-    tiled == untiled without a multi-GPU node."""
+    tiled == untiled without a multi-GPU node.  Float32 tiles only (simulate_dev runs either)."""
+    for t in tiles:
+        t._float32_only("simulate")
     for t in tiles:
         t.d8()
     fa = [tuple(a.cpu().numpy() for a in t.fa_local()) for t in tiles]
@@ -1012,6 +1101,8 @@ def simulate_dev(tiles, layout, d8=True):
     for t in tiles:
         if d8:
             t.d8()
+        else:
+            t.nodata_proxy()
         t.fa_local(sync=False)
         t.fill_ring_codes()
     rows = gather([t.fa_row for t in tiles])
@@ -1140,7 +1231,9 @@ def finish_downslope(tile, comm, max_iters=200, stats=None):
     the value, the others to the owner of the cell they stand on -- preceded by one tiny all-gather of the counts, the
     iteration's only synchronisation with the host.  The result is the reference's float32 whatever the route: counts
     give it through the rounding-safety test of the count form, and the rare walk that fails the test starts again
-    carrying the reference's own sequential float64 sum.  Returns the number of cells resolved (over all ranks); 0
+    carrying the reference's own sequential float64 sum.  On a heights="float64" tile every walker carries that sum and
+    its float64 start height from the start (dt_dev_downslope_walk_seed_f64_w / _route_f64_w): the result is
+    chain.Chain(heights="float64")'s.  Returns the number of cells resolved (over all ranks); 0
     without any exchange of records when no rank had any.  stats (a dict, optional): filled with the number of
     iterations and this rank's wall-clock seconds per phase."""
     import time
@@ -1164,8 +1257,9 @@ def finish_downslope(tile, comm, max_iters=200, stats=None):
             ys, xs = (tile.core("down") == -50.0).nonzero(as_tuple=True)
             ys, xs = ys.to(i32).contiguous(), xs.to(i32).contiguous()
             rec = tc.empty((int(ys.numel()), WALKER_WORDS), dtype=i32, device=tile.dev)
-            tile._chk(L.dt_dev_downslope_walk_seed_w(tile.ctx.h, C.byref(tile.win), tile.p("dem"), int(ys.numel()),
-                                                     ys.data_ptr(), xs.data_ptr(), rec.data_ptr()))
+            seed = L.dt_dev_downslope_walk_seed_f64_w if tile.wide else L.dt_dev_downslope_walk_seed_w
+            tile._chk(seed(tile.ctx.h, C.byref(tile.win), tile.p("dem"), int(ys.numel()), ys.data_ptr(), xs.data_ptr(),
+                           rec.data_ptr()))
         if getattr(tile, "_route", None) is None:  # the layout's bands on the device, once per tile
             tile._route = (tc.as_tensor(np.asarray(layout.ys, np.int32), device=tile.dev),
                            tc.as_tensor(np.asarray(layout.xs, np.int32), device=tile.dev),
@@ -1184,11 +1278,17 @@ def finish_downslope(tile, comm, max_iters=200, stats=None):
             scratch = tc.empty(n + comm.size, dtype=i32, device=tile.dev)
             # arrivals that are finished are written home, the others advance; then the records are grouped by where
             # they go next and counted -- all on the device (dt_dev_downslope_walk_route_w)
-            tile._chk(L.dt_dev_downslope_walk_route_w(
-                tile.ctx.h, C.byref(tile.win), tile.p("dem"), tile.p("fdr"), tile.px, tile.dz, n, rec.data_ptr(),
-                work.data_ptr() if work is not None else None, work.numel() if work is not None else 0,
-                tile.p("down"), ys_t.data_ptr(), layout.ty, xs_t.data_ptr(), layout.tx, send.data_ptr(),
-                counts.data_ptr(), scratch.data_ptr()))
+            if tile.wide:  # (float64 walkers: the reference's sequential sum, no skip tables)
+                tile._chk(L.dt_dev_downslope_walk_route_f64_w(
+                    tile.ctx.h, C.byref(tile.win), tile.p("dem"), tile.p("fdr"), tile.px, tile.dz, n, rec.data_ptr(),
+                    tile.p("down"), ys_t.data_ptr(), layout.ty, xs_t.data_ptr(), layout.tx, send.data_ptr(),
+                    counts.data_ptr(), scratch.data_ptr()))
+            else:
+                tile._chk(L.dt_dev_downslope_walk_route_w(
+                    tile.ctx.h, C.byref(tile.win), tile.p("dem"), tile.p("fdr"), tile.px, tile.dz, n, rec.data_ptr(),
+                    work.data_ptr() if work is not None else None, work.numel() if work is not None else 0,
+                    tile.p("down"), ys_t.data_ptr(), layout.ty, xs_t.data_ptr(), layout.tx, send.data_ptr(),
+                    counts.data_ptr(), scratch.data_ptr()))
             t1 = time.perf_counter()
             m = comm.all_gather_ints(counts)                    # [size, size + 1] on the host: the one synchronisation
             t2 = time.perf_counter()
@@ -1217,6 +1317,9 @@ def evaluate_rank(tile, flood_core, comm, name="hand", under="under", class_map=
     flood_core: this rank's window of the benchmark flood map (int8 H x W device tensor, contiguous).  Returns
     evaluation.evaluate_resident's dict (+ "class_map": int32 H x W device tensor when asked for)."""
     from . import evaluation
+    if tile.wide:
+        raise ValueError("evaluate_rank is float32-only: evaluation.evaluate_resident reads a float32 raster, and a "
+                         "RankTile(heights=\"float64\") holds a float64 hand")
     tc = tile.torch
     with tile.on_stream():
         x = tile.core(name).contiguous()
@@ -1264,6 +1367,8 @@ def condition_ranks(tiles, exchange, any_flag, rounds=4, max_iter=1 << 30):
     flags (an all-reduce for real ranks).  Returns (cells left without a code -- 0 --, fill iterations, flat
     iterations)."""
     for t in tiles:
+        t._float32_only("condition_ranks")
+    for t in tiles:
         t.cond_alloc()
         t.cond_stage(0)
     exchange("filled")
@@ -1308,6 +1413,7 @@ def condition_rank(tile, layout, group=None, rounds=4):
     the flag per iteration"""
     import torch
     import torch.distributed as dist
+    tile._float32_only("condition_rank")
     cpu = dist.get_backend(group) == "gloo"
 
     def exchange(name):

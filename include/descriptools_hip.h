@@ -280,7 +280,9 @@ int dt_dev_slope_d8_m(dt_ctx *ctx, const float *dem, int64_t H, int64_t W, doubl
 int dt_dev_flowacc_river_flowhand_local_m(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const uint8_t *nodata4,
                                           int64_t H, int64_t W, int64_t threshold, int32_t *acc32, int8_t *river);
 /* The resident chain on float64 heights (descriptools_amd.chain.Chain(heights="float64")); `dem` is an H x W double
- * raster on the device.  Out of scope: conditioning, ranks (dt_window), the long-walk skip tables.
+ * raster on the device.  Conditioning has its own float64 entry points (dt_dev_condition_d8_f64*), ranks their
+ * windowed ones (dt_*_f64_w below: tiling.RankTile(heights="float64")).  Out of scope on float64 heights: the
+ * long-walk skip tables, conditioning over ranks (dt_dev_condition_stage*_w), evaluation of a float64 raster.
  * dt_dev_slope_d8_f64: D8 codes as dt_d8_f64 (fdr may be NULL), and the float32 nodata proxy (may be NULL): -100 where
  * z <= -100, otherwise (float)z kept above -100 -- what the flow-accumulation / HAND-index entry points
  * (dt_dev_flowacc_river_flowhand_local, dt_dev_flowhand_finish_w with dem = hand = NULL) need of the DEM.
@@ -457,6 +459,57 @@ int dt_dev_flowhand_gfi_finish_w(dt_ctx *ctx, const dt_window *win, const float 
                                  const int64_t *rem_gidx, const float *rem_zr, const int64_t *rem_ar,
                                  float *fdist, int32_t *idx32, int64_t *idx64, float *hand, int32_t *a_river,
                                  float *gfi, float *lnhlh);
+
+/* ---- one rank's step on float64 heights (tiling.RankTile(heights="float64")): windowed forms of the float64 chain's
+ * entry points above, with the window semantics of the float32 _w entries (core + halo in the rank's memory, -100 only
+ * outside the GLOBAL raster, no D8 code on the last ring of that memory).  The flow-accumulation / HAND-index entries
+ * (dt_dev_flowacc_*_w, dt_dev_flowhand_*_w with dem = the float32 nodata proxy, hand = NULL) are shared.
+ * dt_dev_slope_d8_f64_w: D8 codes (may be NULL) and the nodata proxy (may be NULL) over the window -- for RankTile.d8
+ *   the core plus the halo minus its outer ring, as dt_dev_slope_d8_w.
+ * dt_dev_slope_twi_f64_w (_a64): dt_dev_slope_twi_w with the slope from float64 differences.
+ * dt_dev_downslope_f64_w: as dt_dev_downslope_w (walks that leave the rank's memory: -50 and *n_unresolved_dev).
+ * dt_dev_downslope_walk_seed_f64_w / dt_dev_downslope_walk_route_f64_w: the walker entries for such walks on float64
+ *   heights.  Records are 48 bytes as above, always flag 1 (words 8-9: the reference's sequential float64 path
+ *   length); the start height is a double: low word in word 6, high word in word 11.
+ * dt_dev_flowhand_zr64_w: after the HAND summary (dt_dev_flowhand_local_w or the fused phase), zr64[i] = the float64
+ *   height of the river cell summary entry i ends on (kind 1), -100 otherwise: the eighth field of the float64 HAND row.
+ * dt_dev_rank_solve_flowhand_f64: dt_dev_rank_solve_flowhand on rows with that eighth field (field_offsets8[7], 8-byte
+ *   aligned); rem_zr64 = the float64 height of the river cell each rank exit's path ends on.
+ * dt_dev_hand_gfi_f64_w (_a64): HAND in float64 from the GLOBAL river index (idx32 or idx64), GFI with A = a_river (the
+ *   river-accumulation payload of dt_dev_flowhand_finish_w) and ln(hl/H) with the cell's own accumulation; the river
+ *   height comes from the rank's memory, or for a river cell on another rank from (rem_gidx, rem_zr64) of the n_remote
+ *   ring cells (res_ok) through `table` (dt_hand_f64_table_bytes(n_remote) bytes of device memory); size = px. */
+int dt_dev_slope_d8_f64_w(dt_ctx *ctx, const dt_window *win, const double *dem, double px, uint8_t *fdr, float *proxy);
+int dt_dev_slope_twi_f64_w(dt_ctx *ctx, const dt_window *win, const double *dem, const int32_t *acc32, double px,
+                           double n_top, float *slope, float *slope_rad, float *ti, float *mti);
+int dt_dev_slope_twi_f64_w_a64(dt_ctx *ctx, const dt_window *win, const double *dem, const int64_t *acc64, double px,
+                               double n_top, float *slope, float *slope_rad, float *ti, float *mti);
+int dt_dev_downslope_f64_w(dt_ctx *ctx, const dt_window *win, const double *dem, const uint8_t *fdr, double px,
+                           double elevation_difference, int raw, float *out, int32_t *n_unresolved_dev);
+int dt_dev_downslope_walk_seed_f64_w(dt_ctx *ctx, const dt_window *win, const double *dem, int64_t n, const int32_t *ys,
+                                     const int32_t *xs, void *records);
+int dt_dev_downslope_walk_route_f64_w(dt_ctx *ctx, const dt_window *win, const double *dem, const uint8_t *fdr,
+                                      double px, double elevation_difference, int64_t n, void *records, float *out,
+                                      const int32_t *row_starts, int32_t ty, const int32_t *col_starts, int32_t tx,
+                                      void *send, int32_t *counts, int32_t *scratch);
+int dt_dev_flowhand_zr64_w(dt_ctx *ctx, const dt_window *win, const double *dem, int64_t n, const uint8_t *kind,
+                           const int32_t *ref, double *zr64);
+int dt_dev_rank_solve_flowhand_f64(dt_ctx *ctx, int ty, int tx, const int64_t *heights, const int64_t *widths,
+                                   int64_t Pmax, const void *rows_dev, int64_t rowbytes,
+                                   const int64_t *field_offsets8, int rank, int64_t P_rank, uint8_t *res_ok,
+                                   int32_t *res_nc, int32_t *res_nd, int64_t *rem_gidx, float *rem_zr,
+                                   int64_t *rem_ar, double *rem_zr64);
+int64_t dt_hand_f64_table_bytes(int64_t n_remote);
+int dt_dev_hand_gfi_f64_w(dt_ctx *ctx, const dt_window *win, const double *dem, const int32_t *idx32,
+                          const int64_t *idx64, const int32_t *acc32, const int32_t *a_river32, int64_t n_remote,
+                          const uint8_t *res_ok, const int64_t *rem_gidx, const double *rem_zr64, void *table,
+                          int64_t table_bytes, double px, double n_gfi, double scale_factor, double *hand, float *gfi,
+                          float *lnhlh);
+int dt_dev_hand_gfi_f64_w_a64(dt_ctx *ctx, const dt_window *win, const double *dem, const int32_t *idx32,
+                              const int64_t *idx64, const int64_t *acc64, const int64_t *a_river64, int64_t n_remote,
+                              const uint8_t *res_ok, const int64_t *rem_gidx, const double *rem_zr64, void *table,
+                              int64_t table_bytes, double px, double n_gfi, double scale_factor, double *hand,
+                              float *gfi, float *lnhlh);
 
 /* ---- the same steps on int64 accumulation rasters (`_a64`).  The reference's flow accumulation is int64 end to
  * end (Example/example.py:39 reads it as int64; topoindexes.py:252-261, gfi.py:141-143 and :432-440 consume it).  On
