@@ -534,6 +534,23 @@ extern "C" int dt_dev_flowacc(dt_ctx *c, const uint8_t *fdr, const float *dem, i
   return DT_OK;
 }
 
+// frac_bits is bounded so that 2^frac_bits and 2^-frac_bits stay finite for every weight that can pass the bound
+#define DT_FRAC_BITS_MAX 2200
+extern "C" int dt_dev_flowacc_weighted(dt_ctx *c, const uint8_t *fdr, const float *dem, const double *w, int64_t H,
+                                       int64_t W, int frac_bits, double *acc) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((fdr && w && acc) || H * W == 0, "NULL raster");
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  if (H * W == 0) return DT_OK;
+  size_t need = dt_flowacc_weighted_scratch(H, W);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  DT_TRY(dt_launch_flowacc_weighted(c->stream, dt_full_window(H, W), fdr, dem, w, frac_bits, scr, need, acc, c->status));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
 extern "C" int dt_dev_river_mask(dt_ctx *c, const int32_t *acc32, int64_t N, int64_t threshold,
                                  int8_t *river) {
   DT_CTX(c);
@@ -1712,6 +1729,35 @@ extern "C" int dt_flowacc_u8(const uint8_t *fdr, const float *dem, int64_t H, in
   DT_TRY(dt_dev_flowacc(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, H, W, d_a32.as<int32_t>()));
   DT_TRY(dt_dev_i32_to_i64(c, d_a32.as<int32_t>(), (int64_t)n, d_a64.as<int64_t>()));
   D2H(acc, d_a64, n * 8, c);
+  return dt_ctx_sync(c);
+}
+
+extern "C" int dt_flowacc_weighted(const uint8_t *fdr, const float *dem, const double *w, int64_t H, int64_t W,
+                                   int frac_bits, double *acc) {
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  dt_ctx *c;
+  DT_TRY(host_ctx(&c));
+  DT_TRY(dt_check_hw(H, W));
+  size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(fdr && w && acc, "NULL raster");
+  DevBuf d_f, d_dem, d_w, d_a;
+  DT_TRY(d_f.alloc(n));
+  DT_TRY(d_w.alloc(n * 8));
+  DT_TRY(d_a.alloc(n * 8));
+  H2D(d_f, fdr, n, c);
+  H2D(d_w, w, n * 8, c);
+  if (dem) {
+    DT_TRY(d_dem.alloc(n * 4));
+    H2D(d_dem, dem, n * 4, c);
+  }
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(c, &st));  // this call's status only
+  DT_TRY(dt_dev_flowacc_weighted(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, d_w.as<double>(), H, W,
+                                 frac_bits, d_a.as<double>()));
+  D2H(acc, d_a, n * 8, c);
+  DT_TRY(dt_ctx_status(c, &st));
+  DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
   return dt_ctx_sync(c);
 }
 

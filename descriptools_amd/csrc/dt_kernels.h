@@ -98,6 +98,11 @@ int dt_launch_fa_summary(hipStream_t s, const DtWin &w, void *scratch, int64_t *
 int dt_launch_fa_finish(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, void *scratch,
                         const unsigned long long *ext_perim, int64_t river_thr, void *acc, int acc64,
                         int8_t *river, int *status = nullptr);
+// weighted flow accumulation (int64 fixed point, 2^-frac_bits units) into a float64 raster; raises
+// DT_STATUS_BAD_WEIGHT on `status` for a weight outside the contract
+size_t dt_flowacc_weighted_scratch(int64_t H, int64_t W);
+int dt_launch_flowacc_weighted(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, const double *wt,
+                               int frac_bits, void *scratch, size_t scratch_bytes, double *acc, int *status);
 size_t dt_flowhand_tiled_scratch(int64_t H, int64_t W);
 // nod4 (optional): the D8 kernel's nodata mask; when the fused kernel runs it replaces the read of `dem`
 int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, void *fa_scratch,

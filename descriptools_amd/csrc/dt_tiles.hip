@@ -936,6 +936,359 @@ int dt_launch_fa_finish(hipStream_t s, const DtWin &w, const uint8_t *fdr, const
 }
 
 // ===========================================================================================
+// Weighted flow accumulation (dt_dev_flowacc_weighted)
+// ===========================================================================================
+// The count passes above on the same tiles, perimeter graph and cycle rules, with a per-cell weight summed instead of
+// 1.  The weights are taken in int64 fixed point, q = rint(w * 2^s), quantised as pass 1 stages them: integer adds
+// are order-free, so the result is deterministic, and the caller's scale keeps every partial sum <= 2^52 (each
+// q <= 2^52 / N), which the countdown word's 54-bit sum field holds as it is and float64 converts without rounding.
+// The count kernels' narrow fields (16-bit LDS receive words, 2-byte in-tile counts, the 32-bit record weight) are
+// all 64-bit here:
+//   pass 1   pointer doubling with one 8-byte receive word per cell (64-bit LDS atomics) and the pointers in a
+//            2-byte array of their own; in-tile sums (self excluded) to 8-byte scratch, tile-major
+//   record   W:56 | flags:8 -- W the exit's in-tile subtree sum, FAW_EXIT, and FAW_SRC for an exit that no
+//            feeder waits at.  A zero-weight subtree can leave a resolved node's word at 0, so "source" cannot be
+//            read off the countdown word as the count path does
+//   pass 2   k_fa_reduce's countdown and combined source hops on 64-bit sums
+//   pass 3   the feeders' resolved words gathered as in fa_gather, the entry walks into a 64-bit delta raster
+//            (bit 63: the cycle mark), and the write of ldexp(sum, -s) as float64
+// A bad weight (negative, not finite, or q over the bound) raises DT_STATUS_BAD_WEIGHT and counts as 0.
+#define FAW_EXIT 1ull
+#define FAW_SRC 2ull
+#define FAW_W(r) ((r) >> 8)
+#define FAW_LOC_CYC (~0ull)       /* in-tile sum of a cell on an in-tile D8 cycle */
+#define FAW_CYC (1ull << 63)      /* delta raster: the cell lies on a D8 cycle spanning tiles */
+
+__device__ __forceinline__ unsigned long long faw_quant(double v, int sbits, unsigned long long qmax, bool &bad) {
+  if (!(v >= 0.0)) {  // negative or NaN
+    bad = true;
+    return 0ull;
+  }
+  const double q = rint(ldexp(v, sbits));  // exact scaling, round half to even
+  if (!(q <= (double)qmax)) {              // inf, or over the bound
+    bad = true;
+    return 0ull;
+  }
+  return (unsigned long long)q;
+}
+
+// 45 KiB of LDS: three tiles per CU
+__global__ __launch_bounds__(256, 3) void k_faw_tile1(const uint8_t *__restrict__ fdr, const double *__restrict__ wt,
+                                                     DtWin w, int tiles_x, int sbits, unsigned long long qmax,
+                                                     unsigned long long *__restrict__ rec,
+                                                     unsigned long long *__restrict__ state,
+                                                     uint32_t *__restrict__ parent,
+                                                     unsigned long long *__restrict__ loc,
+                                                     int *__restrict__ status) {
+  __shared__ __attribute__((aligned(16))) unsigned long long s_val[NT];  // what a cell receives in a round
+  __shared__ __attribute__((aligned(16))) uint16_t s_ptr[NT];            // pointer words (PT_*)
+  __shared__ __attribute__((aligned(16))) uint32_t s_aux[NT / 4 + 256];  // codes, then cycle mask + pending counts
+  uint8_t *s_fdr = reinterpret_cast<uint8_t *>(s_aux);
+  const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int y0 = ty * TH, x0 = tx * TW;
+  const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
+  uint32_t c2[8];
+  fa_nbr_codes(fdr, w, y0, x0, threadIdx.x, c2);
+  // my cells t + 256 j: weights quantised as they arrive (0 outside the core)
+  unsigned long long q[CPT], v[CPT];
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    const int c = threadIdx.x + 256 * j;
+    const int y = y0 + c / TW, x = x0 + c % TW;
+    const double wv = (y < w.H && x < w.W) ? wt[(long long)y * w.ld + x] : 0.0;
+    q[j] = faw_quant(wv, sbits, qmax, bad);
+  }
+  if (bad && status) atomicOr(status, DT_STATUS_BAD_WEIGHT);
+  dt_tile_put16(s_fdr, v_fdr);
+#pragma unroll
+  for (int j = 0; j < CPT; j++) s_val[threadIdx.x + 256 * j] = 0ull;
+  __syncthreads();
+  uint32_t P[CPT];  // my cells' pointer words
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    const int c = threadIdx.x + 256 * j;
+    const uint32_t n = dt_tile_next(s_fdr[c], c / TW, c % TW, y0, x0, w);
+    const bool ex = (n == NX_EXIT || n == NX_REXIT);
+    P[j] = n < NT ? (n | PT_ALIVE) : ((uint32_t)c | (ex ? PT_EXIT : 0u));
+    s_ptr[c] = (uint16_t)P[j];
+    v[j] = q[j];
+  }
+  // the perimeter graph's links, as k_fa_tile1 makes them (parent only: the gather form needs no entry_of)
+  int ply = 0, plx = 0;
+  uint32_t my_code = 0, my_flags = 0, feeders = 0;
+  uint32_t fnode[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) fnode[k] = FA_NONE;
+  if (threadIdx.x < PS) {
+    dt_cell_of_slot(threadIdx.x, ply, plx);
+    const uint32_t code = s_fdr[ply * TW + plx];
+    const uint32_t n = dt_tile_next(code, ply, plx, y0, x0, w);
+    if (n == NX_EXIT || n == NX_REXIT) my_code = code;
+    if (n == NX_REXIT) my_flags = (uint32_t)REC_RANK_EXIT;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if (c2[k] == fa_back(k)) {
+        fnode[k] = dt_node_of(y0 + ply + FA_QDY(k), x0 + plx + FA_QDX(k), tiles_x);
+        feeders++;
+      }
+  }
+  __syncthreads();
+  uint8_t *s_cyc = reinterpret_cast<uint8_t *>(s_aux);
+  uint32_t *s_pend = s_aux + NT / 4;
+  reinterpret_cast<uint4 *>(s_aux)[threadIdx.x] = make_uint4(0, 0, 0, 0);
+  s_aux[NT / 4 + threadIdx.x] = 0u;
+  // pointer doubling (see dt_tile_sums_packed): every alive cell adds its sum to the cell its pointer names and takes
+  // that cell's pointer; the owners then collect what arrived.  Off cycles a sum is <= 2^52; on an in-tile cycle it
+  // may wrap (unsigned, discarded: those cells end up in s_cyc)
+  for (int round = 0; round < 12; round++) {
+    uint32_t np[CPT];
+#pragma unroll
+    for (int j = 0; j < CPT; j++) {
+      np[j] = P[j];
+      if (P[j] & PT_ALIVE) {
+        const uint32_t t = P[j] & PT_IDX;
+        atomicAdd(&s_val[t], v[j]);
+        np[j] = s_ptr[t];
+      }
+    }
+    __syncthreads();
+    uint32_t alive = 0;
+#pragma unroll
+    for (int j = 0; j < CPT; j++) {
+      const int c = threadIdx.x + 256 * j;
+      const unsigned long long r = s_val[c];
+      if (r) {
+        v[j] += r;
+        s_val[c] = 0ull;
+      }
+      if (P[j] & PT_ALIVE) s_ptr[c] = (uint16_t)np[j];
+      P[j] = np[j];
+      alive |= P[j] & PT_ALIVE;
+    }
+    if (!__syncthreads_or((int)(alive != 0u))) break;
+  }
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    if (P[j] & PT_ALIVE) s_cyc[P[j] & PT_IDX] = 1;
+    s_val[threadIdx.x + 256 * j] = v[j];  // the final sums, where the perimeter lanes read them
+  }
+  __syncthreads();
+  unsigned long long wexit = 0ull;
+  if (threadIdx.x < PS) {
+    const int c = ply * TW + plx;
+    const uint32_t p = s_ptr[c];
+    uint32_t xs = X_NONE;
+    if (!(p & PT_ALIVE) && (p & PT_EXIT)) {
+      const uint32_t f = p & PT_IDX;
+      xs = (uint32_t)dt_slot_of((int)f / TW, (int)f % TW);
+    }
+    if (my_code) wexit = s_val[c];  // an exit cell is a terminal: never on an in-tile cycle
+    if (xs != X_NONE && feeders) atomicAdd(&s_pend[xs], feeders);
+    const uint32_t me = (uint32_t)tile * PS + threadIdx.x, par = xs != X_NONE ? (uint32_t)tile * PS + xs : FA_NONE;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if (fnode[k] != FA_NONE) parent[fnode[k]] = par;
+    if (my_flags & (uint32_t)REC_RANK_EXIT) parent[me] = FA_NONE;
+  }
+  __syncthreads();
+  if (threadIdx.x < PS) {
+    const uint32_t pend = s_pend[threadIdx.x];
+    rec[(size_t)tile * PS + threadIdx.x] =
+        (wexit << 8) | (my_code ? FAW_EXIT : 0ull) | (my_code && pend == 0u ? FAW_SRC : 0ull);
+    state[(size_t)tile * PS + threadIdx.x] = (unsigned long long)pend << FA2_SH;
+  }
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    const int c = threadIdx.x + 256 * j;
+    loc[(size_t)tile * NT + c] = s_cyc[c] ? FAW_LOC_CYC : v[j] - q[j];
+  }
+}
+
+// countdown over the reduced forest, k_fa_reduce's gather form on 64-bit weights: sources combine their first hops
+// by parent within a wave, the lane that retires a node carries its total on, one atomic per hop
+__global__ __launch_bounds__(256) void k_faw_reduce(const unsigned long long *__restrict__ rec, int64_t nnodes,
+                                                   const uint32_t *__restrict__ parent,
+                                                   unsigned long long *__restrict__ state) {
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t p = FA_NONE;
+  unsigned long long A = 0ull;
+  if (n < nnodes) {
+    const unsigned long long r = rec[n];
+    if ((r & (FAW_EXIT | FAW_SRC)) == (FAW_EXIT | FAW_SRC)) {
+      p = parent[n];
+      A = FAW_W(r);
+    }
+  }
+  const int lane = (int)(threadIdx.x & 63u);
+  bool todo = p != FA_NONE, led = false;
+  uint32_t k = 0u, pp = FA_NONE;
+  unsigned long long S = 0ull, rp = 0ull, old = 0ull;
+  for (unsigned long long m = __ballot(todo); m != 0ull; m = __ballot(todo)) {
+    const int lead = __ffsll((long long)m) - 1;
+    const uint32_t pl = (uint32_t)__shfl((int)p, lead);
+    const bool mine = todo && p == pl;
+    long long s = mine ? (long long)A : 0ll;  // siblings' subtrees are disjoint: <= 2^52
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const uint32_t km = (uint32_t)__popcll(__ballot(mine));
+    if (lane == lead) {
+      led = true;
+      k = km;
+      S = (unsigned long long)s;
+      rp = rec[pl];
+      pp = parent[pl];
+      old = atomicAdd(&state[pl], S - ((unsigned long long)km << FA2_SH));
+    }
+    todo = todo && !mine;
+  }
+  if (!led || (old >> FA2_SH) != (unsigned long long)k) return;
+  unsigned long long T = FAW_W(rp) + (old & FA2_MASK) + S;
+  p = pp;
+  for (int64_t it = 0; it < nnodes && p != FA_NONE; it++) {
+    rp = rec[p];
+    pp = parent[p];
+    old = atomicAdd(&state[p], T - (1ull << FA2_SH));
+    if ((old >> FA2_SH) != 1ull) break;
+    T = FAW_W(rp) + (old & FA2_MASK) + T;
+    p = pp;
+  }
+}
+
+// pass 3: the inflow entering at every perimeter cell (its feeders' resolved totals; FAW_CYC when one is still
+// pending) walks that cell's in-tile path into a 64-bit delta raster, then in-tile sum + delta -> ldexp(., -s).
+// 42.5 KiB of LDS: three tiles per CU.
+#define P3(c) ((uint32_t)(c) + (((uint32_t)(c) >> 6) << 2))
+#define NT3 (TH * (TW + 4))
+template <bool HAS_DEM>
+__global__ __launch_bounds__(256, 3) void k_faw_tile3(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                                     DtWin w, int tiles_x, const unsigned long long *__restrict__ rec,
+                                                     const unsigned long long *__restrict__ state,
+                                                     const unsigned long long *__restrict__ loc, int sbits,
+                                                     double *__restrict__ acc) {
+  __shared__ uint16_t s_nxt[NT3];
+  __shared__ __attribute__((aligned(16))) unsigned long long s_delta[NT3];
+  uint8_t *s_fdr = reinterpret_cast<uint8_t *>(s_delta);
+  const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int y0 = ty * TH, x0 = tx * TW;
+  const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
+  uint32_t c2[8];
+  fa_nbr_codes(fdr, w, y0, x0, threadIdx.x, c2);
+  unsigned long long lv[CPT];
+  float zv[CPT];
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    const int c = threadIdx.x + 256 * j;
+    const int y = y0 + c / TW, x = x0 + c % TW;
+    lv[j] = loc[(size_t)tile * NT + c];
+    zv[j] = (HAS_DEM && y < w.H && x < w.W) ? dem[(long long)y * w.ld + x] : 0.0f;
+  }
+  unsigned long long e = 0ull;  // what enters at my perimeter cell (fa_gather on the weighted words)
+  {
+    int ly = 0, lx = 0;
+    if (threadIdx.x < PS) dt_cell_of_slot(threadIdx.x, ly, lx);
+    unsigned long long pend = 0ull;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if (c2[k] == fa_back(k)) {
+        const uint32_t f = dt_node_of(y0 + ly + FA_QDY(k), x0 + lx + FA_QDX(k), tiles_x);
+        const unsigned long long st = state[f];
+        e += FAW_W(rec[f]) + (st & FA2_MASK);
+        pend |= st >> FA2_SH;
+      }
+    if (pend) e = FAW_CYC;
+  }
+  dt_tile_put16(s_fdr, v_fdr);
+  __syncthreads();
+  uint32_t nx[CPT];
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    const int c = threadIdx.x + 256 * j;
+    nx[j] = dt_tile_next(s_fdr[c], c / TW, c % TW, y0, x0, w);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    const int c = threadIdx.x + 256 * j;
+    s_nxt[P3(c)] = (uint16_t)(nx[j] < NT ? P3(nx[j]) : nx[j]);  // NX_* sentinels stay (>= 0xFFFD > NT3)
+    s_delta[P3(c)] = 0ull;
+  }
+  __syncthreads();
+  if (e != 0ull) {  // one lane per entry cell walks its in-tile path (at most NT steps: it may run into a cycle)
+    int ly, lx;
+    dt_cell_of_slot(threadIdx.x, ly, lx);
+    uint32_t c = P3(ly * TW + lx);
+    if (e & FAW_CYC) {
+      for (int it = 0; it < NT && c < NT3; it++) {
+        atomicOr(&s_delta[c], FAW_CYC);
+        c = s_nxt[c];
+      }
+    } else {
+      for (int it = 0; it < NT && c < NT3; it++) {
+        atomicAdd(&s_delta[c], e);
+        c = s_nxt[c];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < CPT; j++) {
+    const int c = threadIdx.x + 256 * j;
+    const int y = y0 + c / TW, x = x0 + c % TW;
+    if (y >= w.H || x >= w.W) continue;
+    const unsigned long long d = s_delta[P3(c)];
+    const bool dead = lv[j] == FAW_LOC_CYC || (d & FAW_CYC) || (HAS_DEM && zv[j] <= DT_NODATA);
+    acc[(long long)y * w.ld + x] = dead ? -100.0 : ldexp((double)(lv[j] + d), -sbits);
+  }
+}
+#undef P3
+#undef NT3
+
+struct FawScratch {
+  unsigned long long *rec, *state, *loc;
+  uint32_t *parent;
+  int64_t nnodes, ntiles;
+  int tiles_x;
+};
+static FawScratch faw_layout(const DtWin &w, void *scratch) {
+  FawScratch f;
+  f.tiles_x = (w.W + TW - 1) / TW;
+  f.ntiles = (int64_t)f.tiles_x * ((w.H + TH - 1) / TH);
+  f.nnodes = f.ntiles * PS;
+  char *p = (char *)scratch;
+  const size_t n8 = dt_align256((size_t)f.nnodes * 8), n4 = dt_align256((size_t)f.nnodes * 4);
+  f.rec = (unsigned long long *)p;  p += n8;
+  f.state = (unsigned long long *)p;  p += n8;
+  f.parent = (uint32_t *)p;  p += n4;
+  f.loc = (unsigned long long *)p;
+  return f;
+}
+size_t dt_flowacc_weighted_scratch(int64_t H, int64_t W) {
+  const int64_t ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+  const size_t nn = (size_t)ntiles * PS;
+  return dt_align256(nn * 8) * 2 + dt_align256(nn * 4) + dt_align256((size_t)ntiles * NT * 8);
+}
+
+int dt_launch_flowacc_weighted(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, const double *wt,
+                               int frac_bits, void *scratch, size_t scratch_bytes, double *acc, int *status) {
+  if (w.H == 0 || w.W == 0) return DT_OK;
+  DT_REQUIRE(scratch_bytes >= dt_flowacc_weighted_scratch(w.H, w.W), "scratch too small");
+  FawScratch f = faw_layout(w, scratch);
+  DT_REQUIRE(f.nnodes < 0x7FFFFFF0ll, "raster too large for one device tile");
+  // every q <= 2^52 / N: no partial sum of N of them exceeds 2^52
+  const unsigned long long qmax = (1ull << 52) / (unsigned long long)((int64_t)w.H * w.W);
+  dim3 gt((unsigned)f.ntiles), b(256), gn((unsigned)((f.nnodes + 255) / 256));
+  hipLaunchKernelGGL(k_faw_tile1, gt, b, 0, s, fdr, wt, w, f.tiles_x, frac_bits, qmax, f.rec, f.state, f.parent,
+                     f.loc, status);
+  hipLaunchKernelGGL(k_faw_reduce, gn, b, 0, s, f.rec, f.nnodes, f.parent, f.state);
+  if (dem) hipLaunchKernelGGL(k_faw_tile3<true>, gt, b, 0, s, fdr, dem, w, f.tiles_x, f.rec, f.state, f.loc, frac_bits, acc);
+  else hipLaunchKernelGGL(k_faw_tile3<false>, gt, b, 0, s, fdr, dem, w, f.tiles_x, f.rec, f.state, f.loc, frac_bits, acc);
+  return DT_OK;
+}
+
+// ===========================================================================================
 // Flow distance / drained-to river index / HAND (F3, F4; flowhand.py:566-846, :414-442)
 // ===========================================================================================
 // Word format (LDS per cell, and global per perimeter node; identical to the v1 kernels'):

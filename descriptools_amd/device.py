@@ -179,6 +179,9 @@ class Context:
             raise RuntimeError("hydrological conditioning did not reach its fixed point within the budget of rounds "
                                "(DT_STATUS_NOT_CONVERGED): the rasters of this step are not valid -- raise "
                                "Chain(condition_rounds=...) or use flowdir.d8_conditioned, which iterates to the end")
+        if st & 4:
+            raise ValueError("dt_dev_flowacc_weighted met a weight that is negative, not finite or over the bound of "
+                             "its frac_bits (DT_STATUS_BAD_WEIGHT): the weighted accumulation is not valid")
 
     def fork(self, child):
         """`child`'s stream waits (on the device) for everything enqueued so far on this context's stream."""

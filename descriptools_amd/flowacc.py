@@ -1,9 +1,20 @@
 """Flow accumulation (net-new): number of upstream cells EXCLUDING self, the
-convention of the bundled 12_fac.tif; int64 like the `fac` the reference's callers pass."""
+convention of the bundled 12_fac.tif; int64 like the `fac` the reference's callers pass.
+
+accumulate_weighted sums a weight raster down the same D8 tree instead of counting cells (runoff or rainfall depth,
+per-cell area, a load), in int64 fixed point so that the result is exact and deterministic."""
+import math
+
 import numpy as np
 
 from . import _lib
-from ._lib import c_f32p, c_i64p, c_u8p, check, ptr
+from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, ptr
+
+# every partial sum of quantised weights stays <= 2^52: the countdown's sum field holds it and float64 converts it
+# without rounding
+_SUM_BITS = 52
+# frac_bits is bounded as the C ABI bounds it (dt_dev_flowacc_weighted)
+_FRAC_BITS_MAX = 2200
 
 
 def accumulate(fdr, dem=None):
@@ -15,4 +26,97 @@ def accumulate(fdr, dem=None):
         d = np.where(np.asarray(dem) <= -100, np.float32(-100), np.float32(0)).astype(np.float32)
     acc = np.empty((H, W), np.int64)
     check(_lib.lib().dt_flowacc_u8(ptr(fdr, c_u8p), ptr(d, c_f32p), H, W, ptr(acc, c_i64p)))
+    return acc
+
+
+def _weights_f64(weights, shape=None):
+    """weights -> C-contiguous float64, ValueError for anything outside the contract: real or integer dtype, finite,
+    >= 0, integers <= 2^53 (exact in float64)"""
+    a = np.asarray(weights)
+    if shape is not None and a.shape != shape:
+        raise ValueError("weights have shape %s, the direction raster %s" % (a.shape, shape))
+    if a.dtype.kind not in "biuf":
+        raise ValueError("weights must be of a real or integer dtype, not %s" % a.dtype)
+    if a.dtype.kind in "iu" and a.size:
+        if a.dtype.kind == "i" and int(a.min()) < 0:
+            raise ValueError("weights must be >= 0 (the smallest is %d)" % int(a.min()))
+        if int(a.max()) > 2 ** 53:
+            raise ValueError("integer weights must be <= 2^53 (float64 holds them exactly); the largest is %d"
+                             % int(a.max()))
+    d = np.ascontiguousarray(a, dtype=np.float64)
+    if a.dtype.kind == "f" and d.size:
+        if not np.isfinite(d).all():
+            raise ValueError("weights must be finite (NaN or infinity at flat index %d)"
+                             % int(np.argmin(np.isfinite(d).reshape(-1))))
+        if not (d >= 0).all():
+            raise ValueError("weights must be >= 0 (the smallest is %r)" % float(d.min()))
+    return d
+
+
+def _default_frac_bits(n, wmax):
+    """s = 51 - ceil(log2 n) - e with 2^e <= wmax < 2^(e+1); 0 when every weight is 0"""
+    if wmax == 0:
+        return 0
+    e = math.frexp(wmax)[1] - 1
+    return _SUM_BITS - 1 - (n - 1).bit_length() - e
+
+
+def weight_frac_bits(weights):
+    """The fixed-point scale accumulate_weighted uses by default: the largest s for which every partial sum of the
+    quantised weights rint(w * 2^s) over the raster's N cells stays <= 2^52,
+
+        s = 51 - ceil(log2 N) - e,   2^e <= max(weights) < 2^(e+1)
+
+    (so each weight is held to about 52 - ceil(log2 N) significant bits relative to the largest).  All-zero weights
+    (and an empty raster) give s = 0.  The weights are validated as accumulate_weighted validates them."""
+    d = _weights_f64(weights)
+    if d.size == 0:
+        return 0
+    return _default_frac_bits(d.size, float(d.max()))
+
+
+def accumulate_weighted(fdr, weights, dem=None, frac_bits=None):
+    """Weighted flow accumulation: for every cell c, the sum of the weights of the cells strictly upstream of c on
+    accumulate's D8 tree (self excluded), as float64.  With weights = 1 it is accumulate(fdr, dem) exactly.
+
+    The weights are summed in int64 fixed point, q = rint(w * 2^s) (round half to even), and the sum is scaled back
+    by 2^-s, so the result does not depend on order, tiling or run.  s = frac_bits, by default weight_frac_bits(weights)
+    (the finest scale at which no sum can exceed 2^52; then every sum converts to float64 exactly, and a result is
+    within n_upstream * 2^-(s+1) of the real sum).  Pass frac_bits=0 for integer weights to get exact integer sums;
+    a frac_bits with N * rint(max(weights) * 2^frac_bits) > 2^52 is refused.
+
+    -100 where accumulate(fdr, dem) gives -100: nodata cells (dem <= -100, when dem is given) and cells on a D8
+    cycle.  Nodata cells still pass their weight and their inflow downstream, as they pass their count in
+    accumulate; give them weight 0 to leave them out.  Weights must be finite and >= 0, of any real or integer dtype
+    (integers <= 2^53).  Bad arguments raise ValueError before any library call."""
+    f = np.asarray(fdr)
+    if f.ndim != 2:
+        raise ValueError("fdr must be a 2-D raster, not of shape %s" % (f.shape,))
+    H, W = f.shape
+    w = _weights_f64(weights, f.shape)
+    d = None
+    if dem is not None:
+        dm = np.asarray(dem)
+        if dm.shape != f.shape:
+            raise ValueError("dem has shape %s, the direction raster %s" % (dm.shape, f.shape))
+        d = np.where(dm <= -100, np.float32(-100), np.float32(0)).astype(np.float32)
+    n = H * W
+    wmax = float(w.max()) if n else 0.0
+    if frac_bits is None:
+        s = _default_frac_bits(n, wmax) if n else 0
+    else:
+        if isinstance(frac_bits, (bool, np.bool_)) or not isinstance(frac_bits, (int, np.integer)):
+            raise ValueError("frac_bits must be an integer, not %r" % (frac_bits,))
+        s = int(frac_bits)
+        if not -_FRAC_BITS_MAX <= s <= _FRAC_BITS_MAX:
+            raise ValueError("frac_bits must lie in [%d, %d], not %d" % (-_FRAC_BITS_MAX, _FRAC_BITS_MAX, s))
+        with np.errstate(over="ignore"):
+            qmax = np.rint(np.ldexp(wmax, s))
+        if not np.isfinite(qmax) or n * int(qmax) > 2 ** _SUM_BITS:
+            raise ValueError("frac_bits=%d is too fine for these weights: N * rint(max(weights) * 2^frac_bits) "
+                             "exceeds 2^52 (weight_frac_bits gives %d)" % (s, _default_frac_bits(n, wmax)))
+    fdr8 = np.ascontiguousarray(f, np.uint8)
+    acc = np.empty((H, W), np.float64)
+    check(_lib.lib().dt_flowacc_weighted(ptr(fdr8, c_u8p), ptr(d, c_f32p), ptr(w, c_f64p), H, W, s,
+                                         ptr(acc, c_f64p)))
     return acc

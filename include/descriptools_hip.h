@@ -96,6 +96,9 @@ int dt_graph_destroy(dt_graph *graph);
 /* DT_STATUS_NOT_CONVERGED: dt_dev_condition_d8_async's budget of rounds ran out before the fixed point (or a flat
  * cell was left without a code): the conditioned rasters of that step are not valid. */
 #define DT_STATUS_NOT_CONVERGED 2
+/* DT_STATUS_BAD_WEIGHT: dt_dev_flowacc_weighted met a weight outside its contract (negative, NaN, infinite, or one whose
+ * rint(w * 2^frac_bits) exceeds 2^52 / (H * W)): the weighted accumulation of that call is not valid. */
+#define DT_STATUS_BAD_WEIGHT 4
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
 
@@ -137,6 +140,14 @@ int dt_d8_conditioned_f64(const double *dem, int64_t H, int64_t W, double px, ui
 /* Net-new N2: flow accumulation = number of upstream cells excluding self; `dem` may be NULL,
  * otherwise cells with dem <= -100 are set to -100.  Cells on a D8 cycle get -100. */
 int dt_flowacc_u8(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, int64_t *acc);
+/* Net-new: weighted flow accumulation, acc[c] = 2^-s * sum over the cells u strictly upstream of c of rint(w[u] * 2^s),
+ * s = frac_bits, summed in int64 fixed point (exact and independent of order and tiling), on dt_flowacc_u8's D8 tree;
+ * acc = -100 where dt_flowacc_u8 gives -100.  Nodata cells still pass their weight and inflow downstream, as they
+ * pass their count (a caller who wants them out gives them weight 0).  Every weight must be finite and >= 0 with
+ * H * W * rint(w * 2^frac_bits) <= 2^52 (flowacc.weight_frac_bits picks the largest such frac_bits for a raster);
+ * otherwise the call fails and acc is not valid. */
+int dt_flowacc_weighted(const uint8_t *fdr, const float *dem, const double *w, int64_t H, int64_t W, int frac_bits,
+                        double *acc);
 
 /* flowhand.flow_distance_index_cpu + flow_distance_index_gpu (flowhand.py:476-846, untiled
  * call: out = 0, row_start = col_start = 0, matrix_columns = W) and flowhand.hand_calculator
@@ -260,6 +271,10 @@ int dt_dev_condition_d8_f64_async(dt_ctx *ctx, const double *dem, int64_t H, int
 /* acc32: int32 accumulation (H*W < 2^31); dem may be NULL. */
 int dt_dev_flowacc(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
                    int32_t *acc32);
+/* dt_flowacc_weighted on device rasters (H * W < 2^31, dem may be NULL).  A weight outside the contract raises
+ * DT_STATUS_BAD_WEIGHT on the context (dt_ctx_status) and counts as 0. */
+int dt_dev_flowacc_weighted(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const double *w, int64_t H, int64_t W,
+                            int frac_bits, double *acc);
 /* flow accumulation with the river mask (acc > threshold, Example/example.py:52) written by the
  * same final pass */
 int dt_dev_flowacc_river(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
