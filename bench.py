@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- full descriptor chain on a device-resident synthetic DEM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dump-outputs DIR] [--full]
 
 A step = one pass of the whole chain (slope -> D8 -> flow accumulation -> river mask -> flow
 distance / river index / HAND -> fused slope+TI+MTI -> GFI -> ln(hl/H) -> downslope) over one
@@ -10,8 +10,12 @@ N = 1 runs BASELINE.json configs[2], the 16384^2 DEM its metric is quoted on.  F
 by torch.distributed.run, one rank per GPU) every rank owns one S x S tile of a larger DEM (weak
 scaling).  Rank 0 prints ONE JSON line.
 
-Timing: K steps bracketed by barrier + synchronize on both sides, max over ranks.  Per-op times
-come from HIP events recorded on the stream the kernels run on, inside the same timed region.
+Timing: K steps bracketed by barrier + synchronize on both sides, max over ranks.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline.  --full adds
+everything else, after the timed steps: a second, serial timed loop whose HIP events give per_op / roofline, the
+cross-checks of the rasters the timed step left (verified; N > 1 also the halo and overflow counts), the HBM copy
+ceiling, end_to_end (host-tier API, real terrain, the conditioned chain) and the CPU baseline.
 """
 import argparse
 import ctypes
@@ -158,7 +162,7 @@ def tiled_layout(world, size, global_dem):
             "weak-scaling series: one %dx%d tile per GPU (--size)" % (size, size))
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -188,8 +192,8 @@ def main():
                     "launch (chain.Chain.capture) instead of ~45 kernel launches")
     ap.add_argument("--no-overlap", action="store_true", help="headline loop on ONE stream, kernels back to back "
                     "(default: downslope as a second branch on its own stream beside flow accumulation / HAND, "
-                    "Chain(overlap=True), the fastest correct schedule; per-op times always come from a second, "
-                    "serial timed loop)")
+                    "Chain(overlap=True), the fastest correct schedule; per-op times come from a second, serial timed "
+                    "loop: --full)")
     ap.add_argument("--overlap", action="store_true", help="(default; kept for older command lines)")
     ap.add_argument("--tiled", action="store_true", help="N = 1 through the multi-rank path (1 x 1 layout): "
                                                          "measures what the tiling machinery costs")
@@ -201,6 +205,16 @@ def main():
                     "last step computed as DIR/<name>.npy (float32, or float64 for 32/64-bit integer rasters; exact "
                     "values): whole when they fit in 64 MB together, else the same fixed, seeded sample of cells from "
                     "each (1-D, row-major order).  N > 1: every rank writes its own tile as <name>.rank<r>.npy")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the benchmark measures "
+                    "and checks: the serial timed loop (ms_per_step_serial, per_op, roofline), the cross-checks of the "
+                    "timed step's rasters (verified), the HBM copy ceiling, end_to_end and cpu_baseline, each of them "
+                    "as --no-verify / --no-e2e / --no-cpu-baseline and their sizes select.  Without it a run does only "
+                    "what its headline needs")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -307,48 +321,52 @@ def main():
             step()
     barrier()
     dt = time.perf_counter() - t0
-    # what the last timed step left in the rasters, before the loops below write them again
+    # what the last timed step left in the rasters, before --full's loops write them again
     dump = None if args.dump_outputs is None else dump_sample(
         {name: t for name, t in rasters.items() if name not in ("a_river", "slope_rad")})  # not written by the step
 
-    # ---- second timed loop, same process: the same ops on ONE stream, back to back, each bracketed by HIP events on
-    # that stream -> per-op / per-kernel durations that mean something (chain.Chain.ops(serial=True)) ----
-    calls = ch.ops(dem.data_ptr(), want_a_river=False, serial=True)
-    assert [n for n, _, _ in calls] == [n for n, _, _ in chain.OPS]
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in calls]
-          for _ in range(args.steps)]
-    for _, _, fn in calls:
-        _lib.check(fn())
-    barrier()
-    t1 = time.perf_counter()
-    for k in range(args.steps):
-        for i, (name, octx, fn) in enumerate(calls):
-            ev[k][i][0].record(stream)
+    full = {}  # --full: everything the headline does not need, measured after it
+    if args.full:
+        # ---- second timed loop, same process: the same ops on ONE stream, back to back, each bracketed by HIP events
+        # on that stream -> per-op / per-kernel durations that mean something (chain.Chain.ops(serial=True)) ----
+        calls = ch.ops(dem.data_ptr(), want_a_river=False, serial=True)
+        assert [n for n, _, _ in calls] == [n for n, _, _ in chain.OPS]
+        ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in calls]
+              for _ in range(args.steps)]
+        for _, _, fn in calls:
             _lib.check(fn())
-            ev[k][i][1].record(stream)
-    barrier()
-    dt_serial = time.perf_counter() - t1
-    per_op, roof = per_op_table(ev, chain.OPS, N, S, args.steps)
+        barrier()
+        t1 = time.perf_counter()
+        for k in range(args.steps):
+            for i, (name, octx, fn) in enumerate(calls):
+                ev[k][i][0].record(stream)
+                _lib.check(fn())
+                ev[k][i][1].record(stream)
+        barrier()
+        dt_serial = time.perf_counter() - t1
+        per_op, roof = per_op_table(ev, chain.OPS, N, S, args.steps)
 
-    verified = None if args.no_verify else verify_step(torch, L, _lib, ctx, dem, rasters, ch, H, W)
+        verified = None if args.no_verify else verify_step(torch, L, _lib, ctx, dem, rasters, ch, H, W)
 
-    # practical HBM ceiling of this device: the better of two copies through the same library (float4
-    # grid-stride; 1024 x 4 patches, whose pieces spread a workgroup over more HBM channels)
-    src, dst = alloc((H, W), np.float32), alloc((H, W), np.float32)
-    copy_gbs = 0.0
-    for blocks in (65536, -1):
-        if blocks < 0 and N % 65536 != 0:
-            continue
-        for _ in range(2):
-            _lib.check(L.dt_dev_membench_copy(ctx.h, src.data_ptr(), dst.data_ptr(), N, blocks))
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(5):
-            _lib.check(L.dt_dev_membench_copy(ctx.h, src.data_ptr(), dst.data_ptr(), N, blocks))
-        e1.record(stream)
-        torch.cuda.synchronize()
-        copy_gbs = max(copy_gbs, N * 8 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9)
-    del src, dst
+        # practical HBM ceiling of this device: the better of two copies through the same library (float4
+        # grid-stride; 1024 x 4 patches, whose pieces spread a workgroup over more HBM channels)
+        src, dst = alloc((H, W), np.float32), alloc((H, W), np.float32)
+        copy_gbs = 0.0
+        for blocks in (65536, -1):
+            if blocks < 0 and N % 65536 != 0:
+                continue
+            for _ in range(2):
+                _lib.check(L.dt_dev_membench_copy(ctx.h, src.data_ptr(), dst.data_ptr(), N, blocks))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(5):
+                _lib.check(L.dt_dev_membench_copy(ctx.h, src.data_ptr(), dst.data_ptr(), N, blocks))
+            e1.record(stream)
+            torch.cuda.synchronize()
+            copy_gbs = max(copy_gbs, N * 8 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9)
+        del src, dst
+        full = {"ms_per_step_serial": round(dt_serial / args.steps * 1e3, 3), "roofline": roof, "per_op": per_op,
+                "verified": verified, "hbm_copy_ceiling_GBs": round(copy_gbs, 1)}
 
     sched = ("downslope on a second stream beside flow accumulation / HAND (Chain(overlap=True))" if args.overlap
              else "one stream, kernels back to back (--no-overlap)")
@@ -365,11 +383,7 @@ def main():
                    "parallelism": "single GPU; " + sched
                                   + ("; the step replayed as one HIP graph (--graph)" if args.graph else ""),
                    "placement": ch.placement},
-        "ms_per_step_serial": round(dt_serial / args.steps * 1e3, 3),
-        "roofline": roof,
-        "per_op": per_op,
-        "verified": verified,
-        "hbm_copy_ceiling_GBs": round(copy_gbs, 1),
+        **full,
         "chain_algo_bytes_per_cell": chain.ALGO_BYTES_PER_CELL,
         "chain_frac_of_hbm_peak": round(N * args.steps * chain.ALGO_BYTES_PER_CELL / dt / 1e9 / HBM_PEAK_GBS, 4),
     }
@@ -380,9 +394,9 @@ def main():
     bufs.clear()
     ch.free()
     torch.cuda.empty_cache()
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         out["end_to_end"] = end_to_end(args.e2e_size, args.seed, args.real_rep)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_n)
     if dump is not None:
         write_dump(args.dump_outputs, dump)
@@ -521,39 +535,46 @@ def main_tiled(args, torch, dist, world, rank, local_rank, dev):
                                             "lnhlh", "down")}, budget=DUMP_BUDGET_BYTES // world)
     if use_dist:
         dt = allreduce([dt], dist.ReduceOp.MAX)[0]
-    status = tile.ctx.status() & 1
-    unres = allreduce([tile.unresolved_downslope(), status])
+    full, checks = {}, {}  # --full: everything the headline does not need, measured after it
+    if args.full:
+        status = tile.ctx.status() & 1
+        unres = allreduce([tile.unresolved_downslope(), status])
 
-    # ---- serial loop: the stages of rank_ops() back to back on the context's stream, HIP events around each ----
-    ops = tiling.rank_ops(tile, layout, exchange)
-    kern = {n: k for n, _, k in chain.OPS}
-    op_defs = []
-    for name, bpc in tiling.RANK_OPS:
-        k = {"d8": kern["d8"], "downslope": ["k_downslope_win_r"], "slope_twi": kern["slope_twi"],
-             "flowacc_local": ["k_fa_tile1", "k_fa_reduce", "k_fa_nxt_init", "k_fa_rank_summary"],
-             "flowacc_finish_flowhand_local": ["k_rk_fa_*", "k_fa_propagate", "k_fa_poison", "k_fa3fh1", "k_fh_tile1",
-                                               "k_fh_ghost_init", "k_fh_node_jump", "k_fh_rank_summary"],
-             "flowhand_gfi_solve_finish": ["k_rk_fh_*", "k_fh_ghost_set", "k_fh_tile3"]}.get(name, [])
-        op_defs.append((name, bpc, k))
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in ops]
-          for _ in range(args.steps)]
-    for _, fn in ops:
-        fn()
-    barrier()
-    t1 = time.perf_counter()
-    for k in range(args.steps):
-        for i, (_, fn) in enumerate(ops):
-            ev[k][i][0].record(tile.ts)
+        # ---- serial loop: the stages of rank_ops() back to back on the context's stream, HIP events around each ----
+        ops = tiling.rank_ops(tile, layout, exchange)
+        kern = {n: k for n, _, k in chain.OPS}
+        op_defs = []
+        for name, bpc in tiling.RANK_OPS:
+            k = {"d8": kern["d8"], "downslope": ["k_downslope_win_r"], "slope_twi": kern["slope_twi"],
+                 "flowacc_local": ["k_fa_tile1", "k_fa_reduce", "k_fa_nxt_init", "k_fa_rank_summary"],
+                 "flowacc_finish_flowhand_local": ["k_rk_fa_*", "k_fa_propagate", "k_fa_poison", "k_fa3fh1",
+                                                   "k_fh_tile1", "k_fh_ghost_init", "k_fh_node_jump",
+                                                   "k_fh_rank_summary"],
+                 "flowhand_gfi_solve_finish": ["k_rk_fh_*", "k_fh_ghost_set", "k_fh_tile3"]}.get(name, [])
+            op_defs.append((name, bpc, k))
+        ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in ops]
+              for _ in range(args.steps)]
+        for _, fn in ops:
             fn()
-            ev[k][i][1].record(tile.ts)
-    barrier()
-    dt_serial = time.perf_counter() - t1
-    if use_dist:
-        dt_serial = allreduce([dt_serial], dist.ReduceOp.MAX)[0]
-    per_op, roof = per_op_table(ev, op_defs, TH_ * TW_, -1, args.steps)  # rank 0's own stream and tile
-    roof["note"] += "; N > 1: rank 0's tile, the exchange stages (0 bytes) are the all-gathers' launch and wait"
+        barrier()
+        t1 = time.perf_counter()
+        for k in range(args.steps):
+            for i, (_, fn) in enumerate(ops):
+                ev[k][i][0].record(tile.ts)
+                fn()
+                ev[k][i][1].record(tile.ts)
+        barrier()
+        dt_serial = time.perf_counter() - t1
+        if use_dist:
+            dt_serial = allreduce([dt_serial], dist.ReduceOp.MAX)[0]
+        per_op, roof = per_op_table(ev, op_defs, TH_ * TW_, -1, args.steps)  # rank 0's own stream and tile
+        roof["note"] += "; N > 1: rank 0's tile, the exchange stages (0 bytes) are the all-gathers' launch and wait"
 
-    verified = None if args.no_verify else verify_tiled(torch, tile, layout, allreduce)
+        verified = None if args.no_verify else verify_tiled(torch, tile, layout, allreduce)
+        full = {"ms_per_step_serial": round(dt_serial / args.steps * 1e3, 3), "roofline": roof, "per_op": per_op,
+                "verified": verified}
+        checks = {"downslope_walks_beyond_halo": int(unres[0]),
+                  "accumulation_overflow_ranks": int(unres[1])}  # ranks whose int32 accumulation may have reached 2^31
     cells = layout.Hg * layout.Wg
     sched = ("downslope as a second branch on its own stream" if args.overlap else "one stream per rank (--no-overlap)")
     out = {
@@ -573,20 +594,16 @@ def main_tiled(args, torch, dist, world, rank, local_rank, dev):
                    "parallelism": "%dx%d rank tiles, 64-cell halo, 2 %s all-gathers of ring summaries per "
                                   "step (flow accumulation inflow, HAND rank exits); %s"
                                   % (layout.ty, layout.tx, "gloo (CPU rehearsal)" if cpu_red else "RCCL", sched)},
-        "ms_per_step_serial": round(dt_serial / args.steps * 1e3, 3),
-        "roofline": roof,
-        "per_op": per_op,
-        "verified": verified,
+        **full,
         "chain_algo_bytes_per_cell": chain.ALGO_BYTES_PER_CELL,
         "chain_frac_of_hbm_peak": round(cells * args.steps * chain.ALGO_BYTES_PER_CELL / dt / 1e9 / world
                                         / HBM_PEAK_GBS, 4),
-        "downslope_walks_beyond_halo": int(unres[0]),
-        "accumulation_overflow_ranks": int(unres[1]),  # ranks whose int32 accumulation may have reached 2^31
+        **checks,
         "backend": (dist.get_backend() if use_dist else "none"),
         "ranks": (dist.get_world_size() if use_dist else 1),
         "distinct_gpus": min(world, torch.cuda.device_count()) if not cpu_red else 1,
     }
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_n)
     if dump is not None:
         write_dump(args.dump_outputs, dump, ".rank%d" % rank if world > 1 else "")

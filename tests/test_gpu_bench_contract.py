@@ -1,5 +1,5 @@
 """GPU (-m gpu): bench.py's one-line JSON contract at a small size -- the keys the driver reads, the roofline
-and cpu_baseline objects, and the N = 1 run through the multi-rank path."""
+and cpu_baseline objects of a --full run, the N = 1 run through the multi-rank path, and the plain run's line."""
 import json
 import os
 import subprocess
@@ -38,7 +38,7 @@ def _check_common(d, cells_per_gpu):
 
 
 def test_bench_line_contract():
-    d = _run("--cpu-n", "512", "--e2e-size", "1024", "--real-rep", "2")
+    d = _run("--full", "--cpu-n", "512", "--e2e-size", "1024", "--real-rep", "2")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "end_to_end"):
         assert k in d, k
@@ -74,10 +74,10 @@ def test_bench_line_contract():
 def test_bench_serial_headline_and_graph_replay():
     """--no-overlap: one stream; --graph: the headline loop replays a HIP graph and per-op times still come from the
     serial loop (they used to be zeros)"""
-    d = _run("--no-overlap", "--no-cpu-baseline", "--no-e2e")
+    d = _run("--full", "--no-overlap", "--no-cpu-baseline", "--no-e2e")
     _check_common(d, 2048 * 2048)
     assert "one stream" in d["config"]["parallelism"]
-    g = _run("--graph", "--no-cpu-baseline", "--no-e2e")
+    g = _run("--full", "--graph", "--no-cpu-baseline", "--no-e2e")
     _check_common(g, 2048 * 2048)
     assert all(v["ms"] > 0 for v in g["per_op"].values()) and g["roofline"]["frac"] > 0
     assert g["verified"]["checksums"] == d["verified"]["checksums"]
@@ -86,15 +86,15 @@ def test_bench_serial_headline_and_graph_replay():
 def test_bench_tiled_path_at_one_rank():
     """the N > 1 line's shape, at one rank: per-op events on the rank's stream, roofline of the dominant kernel,
     cpu_baseline on rank 0, cross-checks; the 1 x 1 layout's checksums are the N = 1 run's"""
-    d = _run("--tiled", "--cpu-n", "512")
+    d = _run("--full", "--tiled", "--cpu-n", "512")
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["downslope_walks_beyond_halo"] == 0
     assert "rank tiles" in d["config"]["parallelism"] and d["ranks"] == 1 and d["backend"] == "none"
     _check_common(d, 2048 * 2048)
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
     assert d["verified"]["cells_drained_through_outlets"] == 2048 * 2048
-    one = _run("--no-cpu-baseline", "--no-e2e")
+    one = _run("--full", "--no-cpu-baseline", "--no-e2e")
     assert d["verified"]["checksums"] == one["verified"]["checksums"]
-    f = _run("--force-dist", "--no-cpu-baseline")  # the RCCL collectives with one rank
+    f = _run("--full", "--force-dist", "--no-cpu-baseline")  # the RCCL collectives with one rank
     _check_common(f, 2048 * 2048)
     assert f["backend"] == "nccl" and f["ranks"] == 1 and f["verified"]["checksums"] == d["verified"]["checksums"]
 
@@ -104,8 +104,8 @@ def test_bench_gpus_flag_without_a_launcher_starts_the_ranks_itself():
     as a child torch.distributed.run (here: gloo rehearsal, two ranks sharing the one GPU)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size",
-                          "1024", "--steps", "2", "--warmup", "1", "--cpu-n", "256"], capture_output=True, text=True,
-                         timeout=900,
+                          "1024", "--steps", "2", "--warmup", "1", "--full", "--cpu-n", "256"], capture_output=True,
+                         text=True, timeout=900,
                          cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -130,8 +130,8 @@ def test_bench_dump_outputs(tmp_path):
     names = {"slope", "fdr", "fac", "river", "fdist", "idx", "hand", "ti", "mti", "gfi", "lnhlh", "down"}
     whole = str(tmp_path / "whole")
     s = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "1024", "--steps", "3", "--warmup",
-                        "1", "--no-cpu-baseline", "--no-e2e", "--dump-outputs", whole], capture_output=True, text=True,
-                       timeout=600, cwd=ROOT)
+                        "1", "--full", "--no-cpu-baseline", "--no-e2e", "--dump-outputs", whole], capture_output=True,
+                       text=True, timeout=600, cwd=ROOT)
     assert s.returncode == 0, s.stderr[-2000:]
     d = json.loads([ln for ln in s.stdout.splitlines() if ln.startswith("{")][0])
     assert d["steps"] == 3
@@ -158,3 +158,29 @@ def test_bench_dump_outputs(tmp_path):
     assert all(a[k].dtype in (np.float32, np.float64) for k in a)
     for b in runs[1:]:
         assert set(b) == names and all(np.array_equal(a[k], b[k], equal_nan=True) for k in names)
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """without --full a run measures and checks nothing beyond its headline: the line's headline keys mean what they
+    mean in a --full run, the extras are absent, and --dump-outputs writes what a --full run of the same step writes"""
+    import numpy as np
+    extras = {"ms_per_step_serial", "roofline", "per_op", "verified", "hbm_copy_ceiling_GBs", "end_to_end",
+              "cpu_baseline", "downslope_walks_beyond_halo", "accumulation_overflow_ranks"}
+    plain, full = str(tmp_path / "plain"), str(tmp_path / "full")
+    p = _run("--dump-outputs", plain)
+    f = _run("--full", "--no-cpu-baseline", "--no-e2e", "--dump-outputs", full)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "chain_algo_bytes_per_cell", "chain_frac_of_hbm_peak"):
+        assert k in p, k
+    assert not extras & set(p), extras & set(p)
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "dtype", "data"):
+        assert p[k] == f[k], k
+    for k in ("workload", "global_dem", "parallelism", "river_threshold_cells"):
+        assert p["config"][k] == f["config"][k], k
+    assert p["value"] > 0 and abs(p["value"] - 2048 * 2048 / (p["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * p["value"]
+    a, b = _load_dump(plain), _load_dump(full)
+    assert set(a) == set(b) == {"slope", "fdr", "fac", "river", "fdist", "idx", "hand", "ti", "mti", "gfi", "lnhlh",
+                                "down"}
+    assert all(a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k], equal_nan=True) for k in a)
+    t = _run("--tiled")  # the multi-rank path's plain line
+    assert t["n_gpus"] == 1 and t["value"] > 0 and t["ranks"] == 1 and not extras & set(t), extras & set(t)

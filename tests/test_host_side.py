@@ -146,6 +146,21 @@ def test_bench_gpus8_defaults_to_config5():
     assert (layout.ty, layout.tx) == (1, 2) and layout.shape(1) == (1024, 1024)
 
 
+def test_bench_extras_are_opt_in():
+    """a plain `bench.py --gpus 1 --steps K --warmup W` measures the headline alone; the serial loop, the cross-checks,
+    end_to_end and the CPU baseline run with --full, which the options that trim them go with"""
+    import importlib
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    ap = bench.arg_parser()
+    a = ap.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 5, 2) and a.dump_outputs is None
+    a = ap.parse_args(["--full", "--no-cpu-baseline", "--no-e2e", "--no-verify", "--cpu-n", "512"])
+    assert a.full and a.no_cpu_baseline and a.no_e2e and a.no_verify and a.cpu_n == 512
+
+
 def test_pinned_pool_size_classes_and_cap(monkeypatch):
     """a 1.01 GiB raster must not lock 2 GiB, and the page-locked bytes in callers' hands are capped
     (pure bookkeeping: no allocation happens in this test)"""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects this round's measurement set on the GPU box into gpurun_out/<tag>/ (copied to profiles/<round>/ afterwards):
-#   bench16384.json                           the un-profiled default bench line (headline = overlapped schedule, per-op
+#   bench16384.json                           the un-profiled --full bench line (headline = overlapped schedule, per-op
 #                                             from its serial loop, verification, end_to_end, cpu_baseline)
 #   bench16384_serial.json / _tiled.json      --no-overlap; --tiled (N = 1 through the multi-rank path)
 #   bench16384_kernel_stats.csv               rocprofv3 --kernel-trace --stats of the SERIAL schedule (--no-overlap: a kernel
@@ -19,7 +19,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT profiles/$ROUND
 # placement tuning off in the counter runs: its ~250 probe launches would only pad the traces (which block serves
 # which raster does not change what a kernel moves)
-B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-verify --no-e2e --no-overlap --no-placement"
+B="python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-verify --no-e2e --no-overlap --no-placement"
 pmc_pass $OUT/pmc_fetch FETCH_SIZE -- $B
 pmc_pass $OUT/pmc_write WRITE_SIZE -- $B
 cp $(find $OUT/pmc_fetch -name "*counter_collection.csv" | head -1) $OUT/pmc_fetch_counter_collection.csv
@@ -30,14 +30,14 @@ echo "pmc done"
 pmc_pass $OUT/sq_a SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT -- $B
 pmc_pass $OUT/sq_b SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS -- $B
 echo "sq done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-e2e --no-overlap --no-placement > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-verify --no-e2e --no-overlap --no-placement > $OUT/trace.log 2>&1
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/bench16384_kernel_stats.csv
 python3 tools/sq_summary.py $OUT/sq_a $OUT/sq_b $OUT/bench16384_kernel_stats.csv > $OUT/sq_counters.txt
 echo "trace done"
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench16384.json 2> $OUT/bench16384.err
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench16384.json 2> $OUT/bench16384.err
 echo "bench done"
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-overlap > $OUT/bench16384_serial.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --tiled > $OUT/bench16384_tiled.json 2>/dev/null
+python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-e2e --no-overlap > $OUT/bench16384_serial.json 2>/dev/null
+python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --tiled > $OUT/bench16384_tiled.json 2>/dev/null
 rm -rf $OUT/pmc_fetch $OUT/pmc_write $OUT/sq_a $OUT/sq_b $OUT/trace
 # round 4: the placement study is tools/micro/placement_map (physical blocks, delta scan) and tools/arena_probe.py,
 # run on their own (profiles/r4/placement_map_*.txt, placement_arena_probe.txt); the conditioning and the real-terrain

@@ -1,6 +1,6 @@
 """Build profiles/<round>/<tag>_pmc_traffic.json from two rocprofv3 counter runs
-(`--pmc FETCH_SIZE` and `--pmc WRITE_SIZE`, each of `python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-verify
---no-e2e --no-overlap --no-placement`: the serial schedule).
+(`--pmc FETCH_SIZE` and `--pmc WRITE_SIZE`, each of `python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline
+--no-verify --no-e2e --no-overlap --no-placement`: the serial schedule).
 
     python tools/pmc_traffic.py <fetch_counter_collection.csv> <write_counter_collection.csv> <out.json> [size]
 
@@ -32,7 +32,7 @@ def read(path, counter, steps):
 
 
 def main():
-    steps = 4  # --no-overlap --steps 1 --warmup 1: (warm-up + timed step) of the headline loop and of the per-op loop
+    steps = 4  # --full --no-overlap --steps 1 --warmup 1: (warm-up + timed step) of the headline and of the per-op loop
     fetch, calls = read(sys.argv[1], "FETCH_SIZE", steps)
     write, _ = read(sys.argv[2], "WRITE_SIZE", steps)
     size = int(sys.argv[4]) if len(sys.argv) > 4 else 16384
