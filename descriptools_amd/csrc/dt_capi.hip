@@ -551,6 +551,29 @@ extern "C" int dt_dev_flowacc_weighted(dt_ctx *c, const uint8_t *fdr, const floa
   return DT_OK;
 }
 
+// stream order: flat indices are int64, so the raster may exceed 2^31 cells (the network may not)
+static int dt_check_so(int64_t H, int64_t W) {
+  DT_REQUIRE(H >= 0 && W >= 0, "negative raster shape");
+  DT_REQUIRE(W == 0 || H <= (1ll << 42) / W, "raster too large");
+  return DT_OK;
+}
+
+extern "C" int dt_dev_stream_order(dt_ctx *c, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W,
+                                   int8_t *strahler, int64_t *shreve, int64_t *link) {
+  DT_CTX(c);
+  DT_TRY(dt_check_so(H, W));
+  DT_REQUIRE((fdr && river && strahler) || H * W == 0, "NULL raster");
+  if (H * W == 0) return DT_OK;
+  size_t need = dt_stream_order_scratch(H, W);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  int64_t m = 0;
+  DT_TRY(dt_launch_stream_order(c->stream, fdr, river, H, W, scr, need, strahler, shreve, link,
+                                H * W >= (1ll << 31) ? &m : nullptr));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
 extern "C" int dt_dev_river_mask(dt_ctx *c, const int32_t *acc32, int64_t N, int64_t threshold,
                                  int8_t *river) {
   DT_CTX(c);
@@ -1758,6 +1781,31 @@ extern "C" int dt_flowacc_weighted(const uint8_t *fdr, const float *dem, const d
   D2H(acc, d_a, n * 8, c);
   DT_TRY(dt_ctx_status(c, &st));
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
+  return dt_ctx_sync(c);
+}
+
+extern "C" int dt_stream_order(const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, int8_t *strahler,
+                               int64_t *shreve, int64_t *link) {
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  dt_ctx *c;
+  DT_TRY(host_ctx(&c));
+  DT_TRY(dt_check_so(H, W));
+  size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(fdr && river && strahler, "NULL raster");
+  DevBuf d_f, d_r, d_o, d_s, d_l;
+  DT_TRY(d_f.alloc(n));
+  DT_TRY(d_r.alloc(n));
+  DT_TRY(d_o.alloc(n));
+  if (shreve) DT_TRY(d_s.alloc(n * 8));
+  if (link) DT_TRY(d_l.alloc(n * 8));
+  H2D(d_f, fdr, n, c);
+  H2D(d_r, river, n, c);
+  DT_TRY(dt_dev_stream_order(c, d_f.as<uint8_t>(), d_r.as<int8_t>(), H, W, d_o.as<int8_t>(), d_s.as<int64_t>(),
+                             d_l.as<int64_t>()));
+  D2H(strahler, d_o, n, c);
+  if (shreve) D2H(shreve, d_s, n * 8, c);
+  if (link) D2H(link, d_l, n * 8, c);
   return dt_ctx_sync(c);
 }
 

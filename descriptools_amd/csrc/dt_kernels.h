@@ -168,3 +168,10 @@ int dt_launch_condition_async_f64(hipStream_t s, const double *dem, int64_t H, i
                                   uint8_t *fdr, void *scratch, int rounds, int *status);
 
 int dt_flow_impl();  // 1 global kernels, 2 tile-hierarchical (default)
+
+// stream order (dt_streams.hip): Strahler order, Shreve magnitude and link heads of the network river != 0 on fdr;
+// shreve / link may be NULL.  m_host != NULL (rasters of 2^31 cells or more) reads the network's cell count back and
+// refuses 2^31 or more; otherwise nothing synchronises.
+size_t dt_stream_order_scratch(int64_t H, int64_t W);
+int dt_launch_stream_order(hipStream_t s, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, void *scratch,
+                           size_t scratch_bytes, int8_t *strahler, int64_t *shreve, int64_t *link, int64_t *m_host);

@@ -148,6 +148,18 @@ int dt_flowacc_u8(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, in
  * otherwise the call fails and acc is not valid. */
 int dt_flowacc_weighted(const uint8_t *fdr, const float *dem, const double *w, int64_t H, int64_t W, int frac_bits,
                         double *acc);
+/* Net-new: stream order of the channel network `river` (nonzero = network cell) on the D8 raster `fdr`.  A network
+ * cell c has the edge c -> d when its code is one of the eight D8 codes and points at an in-raster network cell d;
+ * otherwise c is a network outlet.  Its children are the network cells with an edge into it.
+ *   strahler (int8): 0 off the network; 1 with no children; else m + 1 when two or more children have the largest
+ *                    child order m, m when one has.
+ *   shreve (int64):  0 off the network; 1 with no children; else the sum of the children's magnitudes.
+ *   link (int64):    -100 off the network; the flat index y * W + x of the head of the cell's link, where a cell is
+ *                    its own head unless it has exactly one child, whose head it then takes.
+ * Network cells that in-degree peeling never removes (on a D8 cycle of network cells) get -100 in all three.  Results
+ * are exact integers.  shreve and link may be NULL (not written); a network of 2^31 cells or more is refused. */
+int dt_stream_order(const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, int8_t *strahler, int64_t *shreve,
+                    int64_t *link);
 
 /* flowhand.flow_distance_index_cpu + flow_distance_index_gpu (flowhand.py:476-846, untiled
  * call: out = 0, row_start = col_start = 0, matrix_columns = W) and flowhand.hand_calculator
@@ -275,6 +287,10 @@ int dt_dev_flowacc(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H,
  * DT_STATUS_BAD_WEIGHT on the context (dt_ctx_status) and counts as 0. */
 int dt_dev_flowacc_weighted(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const double *w, int64_t H, int64_t W,
                             int frac_bits, double *acc);
+/* dt_stream_order on device rasters, on the context's stream: it does not synchronise (except on rasters of 2^31
+ * cells or more, where it reads the network's size back to refuse 2^31 network cells).  shreve and link may be NULL. */
+int dt_dev_stream_order(dt_ctx *ctx, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, int8_t *strahler,
+                        int64_t *shreve, int64_t *link);
 /* flow accumulation with the river mask (acc > threshold, Example/example.py:52) written by the
  * same final pass */
 int dt_dev_flowacc_river(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
