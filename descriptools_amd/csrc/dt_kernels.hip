@@ -472,8 +472,8 @@ __global__ __launch_bounds__(256) void k_downslope(const float *__restrict__ dem
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (int64_t)H * W) return;
   float z0 = dem[i];
-  if (z0 <= DT_NODATA) {
-    out[i] = DT_NODATA;
+  if (!(z0 > DT_NODATA && z0 < __builtin_inff())) {  // nodata; or NaN / +inf, whose walk never starts (DS_NONFINITE)
+    out[i] = z0 <= DT_NODATA ? DT_NODATA : __builtin_nanf("");
     return;
   }
   const double dcard = px, ddiag = px * sqrt(2.0);
@@ -482,6 +482,10 @@ __global__ __launch_bounds__(256) void k_downslope(const float *__restrict__ dem
   float drop = 0.0f;
   int loop = 0;
   bool failed = false;  // what downslope_gpu alone marks -50 (downslope.py:526-529)
+  // DS_NONFINITE: a NaN or +inf start never enters the reference's loop (z0 - z0 < dz is NaN < dz: false), is not
+  // marked -50, and stores (z0 - z0) / 0 = NaN (downslope.py:468, :532) -- unlike the 0 / 0 of a pit, which goes
+  // through the -50 repair and is defined as 0 here (dt_oracle_downslope).  Every walk kernel starts
+  // from the cells this test and its twins in ds_win_body / dt_wide.hip let through.
   while ((double)drop < dz) {
     bool diag = false;
     int64_t t = dt_step(pos, fdr[pos], H, W, diag);
@@ -948,8 +952,8 @@ __device__ __forceinline__ void ds_win_body(const float *__restrict__ dem,
     const int pos0 = (cy + DW_M) * DW_LD + cx + DW_M;
     float z0 = s_z[pos0];
     long long o = (long long)y0 * w.ld + x0;
-    if (z0 <= DT_NODATA) {
-      out[o] = DT_NODATA;
+    if (!(z0 > DT_NODATA && z0 < __builtin_inff())) {  // nodata; NaN / +inf start: NaN (k_downslope)
+      out[o] = z0 <= DT_NODATA ? DT_NODATA : __builtin_nanf("");
       continue;
     }
     float drop = 0.0f;

@@ -224,6 +224,8 @@ __device__ __forceinline__ void dt_twi_cell(int64_t fac, float srad, double lnpx
 // float32 result (within ~1 float32 ulp of numpy's float32 arctan); -100 where dem == -100.
 __device__ __forceinline__ float dt_slope_rad(float slope_pct, float dem) {
   if (dem == DT_NODATA) return DT_NODATA;
+  // a +inf height's slope: atan(inf) = pi / 2 in float32 (dt_pct_to_tan would give NaN: inf - inf)
+  if (slope_pct == __builtin_inff()) return 1.57079637f;
   float q = dt_pct_to_tan(slope_pct);
   if (q >= 0.0f && q < 1e30f) return (float)dt_atanf_pos(q);
   return (float)dt_fast_atan((double)q);

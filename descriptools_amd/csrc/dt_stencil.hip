@@ -41,9 +41,10 @@ __device__ __forceinline__ int dt_scan_pos(uint32_t code) {
   return (int)((0x21035674u >> (4 * (__ffs((int)code) - 1))) & 0xFu);
 }
 
-// Neighbour heights arrive with nodata (== -100) replaced by +inf (done once per cell when the tile is
-// staged): c - inf = -inf never beats a candidate, which is the reference's "neighbour == -100 skipped"
-// (slope.py:247) without a test per neighbour.  `c` is the centre's original value.
+// Neighbour heights arrive with nodata (== -100) replaced by a NaN of a fixed payload (sd_nod, done once per cell
+// when the tile is staged): c - NaN = NaN never beats a candidate, which is the reference's "neighbour == -100
+// skipped" (slope.py:247) without a test per neighbour; a real NaN or +inf neighbour drops out the same way, as it
+// does in the reference.  `c` is the centre's original value.
 template <bool NEED_CODE, bool NEED_SLOPE>
 __device__ __forceinline__ SlopeCell dt_slope_cell(float c, float nw, float n, float ne, float w,
                                                   float e, float sw, float s, float se,
@@ -163,16 +164,24 @@ __device__ __forceinline__ void sd_tile_origin(int b, int tiles_x, int tiles_y, 
   y0 = tyi * SD_TY;
 }
 
+// The staged stand-in for nodata: a quiet NaN with a payload no arithmetic produces (hardware NaNs are 0x7FC00000),
+// told apart from a real NaN or +inf height by its bits -- so that a NaN centre keeps the reference's answer (slope
+// 0, the border out-code) and a +inf centre its own (slope inf and a code) instead of passing for nodata.
+#define SD_NOD_BITS 0x7FC0D0DAu
+__device__ __forceinline__ float sd_nod() { return __uint_as_float(SD_NOD_BITS); }
+__device__ __forceinline__ float sd_stage_val(float v) { return v == DT_NODATA ? sd_nod() : v; }
+// the centre's own value (-100 for staged nodata)
+__device__ __forceinline__ float sd_centre(float v) { return __float_as_uint(v) == SD_NOD_BITS ? DT_NODATA : v; }
+
 // stage (SD_TY + 2) x (SD_TX + 2) cells; outside the GLOBAL raster = -100 ring (slope.py:175); cells outside
 // the core but inside the global raster come from the halo of the window.  nodata (and everything outside
-// the raster) is staged as +inf: see dt_slope_cell.  The caller synchronises.
+// the raster) is staged as sd_nod(): see dt_slope_cell.  The caller synchronises.
 template <int TX = SD_TX, int TY = SD_TY>
 __device__ __forceinline__ void sd_stage(float *t, const float *__restrict__ dem, const DtWin &w, int x0, int y0,
                                          int vec_ok) {
   const int H = w.H, W = w.W;
   const int ylo = -(w.gy0 > 0 ? 1 : 0), yhi = H + (w.gy0 + H < w.Hg ? 1 : 0);  // readable rows [ylo, yhi)
   const int xlo = -(w.gx0 > 0 ? 1 : 0), xhi = W + (w.gx0 + W < w.Wg ? 1 : 0);
-  const float pinf = __builtin_inff();
   // Block-uniform fast form for tiles whose whole 18 x 258 window is readable: every load of a thread is issued
   // before the first use (five 16-byte loads and one halo value in flight per thread).  The guarded loop below
   // waits for each load before the next: five dependent memory round trips per workgroup, which made every
@@ -198,14 +207,14 @@ __device__ __forceinline__ void sd_stage(float *t, const float *__restrict__ dem
       if (i < (TY + 2) * (TX / 4)) {
         const int r = i / (TX / 4), c4 = i - r * (TX / 4);
         float4 q = v[u];
-        q.x = q.x == DT_NODATA ? pinf : q.x;
-        q.y = q.y == DT_NODATA ? pinf : q.y;
-        q.z = q.z == DT_NODATA ? pinf : q.z;
-        q.w = q.w == DT_NODATA ? pinf : q.w;
+        q.x = sd_stage_val(q.x);
+        q.y = sd_stage_val(q.y);
+        q.z = sd_stage_val(q.z);
+        q.w = sd_stage_val(q.w);
         *reinterpret_cast<float4 *>(&t[r * (TX + 8) + 4 + c4 * 4]) = q;
       }
     }
-    if (threadIdx.x < (TY + 2) * 2) t[hr * (TX + 8) + (hside ? 4 + TX : 3)] = hv == DT_NODATA ? pinf : hv;
+    if (threadIdx.x < (TY + 2) * 2) t[hr * (TX + 8) + (hside ? 4 + TX : 3)] = sd_stage_val(hv);
     return;
   }
   for (int i = threadIdx.x; i < (TY + 2) * (TX / 4); i += 256) {
@@ -223,10 +232,10 @@ __device__ __forceinline__ void sd_stage(float *t, const float *__restrict__ dem
         if (gx + 3 < xhi) v.w = p[3];
       }
     }
-    v.x = v.x == DT_NODATA ? pinf : v.x;
-    v.y = v.y == DT_NODATA ? pinf : v.y;
-    v.z = v.z == DT_NODATA ? pinf : v.z;
-    v.w = v.w == DT_NODATA ? pinf : v.w;
+    v.x = sd_stage_val(v.x);
+    v.y = sd_stage_val(v.y);
+    v.z = sd_stage_val(v.z);
+    v.w = sd_stage_val(v.w);
     *reinterpret_cast<float4 *>(&t[r * (TX + 8) + 4 + c4 * 4]) = v;
   }
   for (int i = threadIdx.x; i < (TY + 2) * 2; i += 256) {
@@ -234,7 +243,7 @@ __device__ __forceinline__ void sd_stage(float *t, const float *__restrict__ dem
     int gy = y0 - 1 + r, gx = side ? x0 + TX : x0 - 1;
     float v = DT_NODATA;
     if (gy >= ylo && gy < yhi && gx >= xlo && gx < xhi) v = dem[(long long)gy * w.ld + gx];
-    t[r * (TX + 8) + (side ? 4 + TX : 3)] = v == DT_NODATA ? pinf : v;
+    t[r * (TX + 8) + (side ? 4 + TX : 3)] = sd_stage_val(v);
   }
 }
 
@@ -249,7 +258,6 @@ __global__ __launch_bounds__(256, 6) void k_stencil(const float *__restrict__ de
   int x0, y0;
   sd_tile_origin(blockIdx.x, tiles_x, tiles_y, x0, y0);
   const int H = w.H, W = w.W;
-  const float pinf = __builtin_inff();
   sd_stage(t, dem, w, x0, y0, vec_ok);
   __syncthreads();
 
@@ -284,7 +292,7 @@ __global__ __launch_bounds__(256, 6) void k_stencil(const float *__restrict__ de
       uint32_t codes = 0;
 #pragma unroll
       for (int k = 0; k < 4; k++) {
-        const float cz = bb[k + 1] == pinf ? DT_NODATA : bb[k + 1];  // the centre's own value
+        const float cz = sd_centre(bb[k + 1]);  // the centre's own value
         SlopeCell sc = dt_slope_cell<W_FDR, (W_SLOPE || W_RAD)>(cz, a[k], a[k + 1], a[k + 2], bb[k],
                                                                        bb[k + 2], cc[k], cc[k + 1], cc[k + 2],
                                                                        inv_card, inv_diag, dcard, ddiag);
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(256, 6) void k_stencil(const float *__restrict__ de
         if (W_FDR) {
           // N1 border rule: a border cell with no lower neighbour drains out of the raster
           int gyy = w.gy0 + gy, gxx = w.gx0 + gx + k;  // global position
-          if (code == 0u && cz > DT_NODATA) {
+          if (code == 0u && !(cz <= DT_NODATA)) {  // (a NaN centre drains out as well)
             if (gyy == w.Hg - 1) code = 4u;
             else if (gyy == 0) code = 64u;
             else if (gxx == 0) code = 16u;
@@ -447,7 +455,6 @@ __global__ __launch_bounds__(256, WX == 1 ? 8 : (WX == 2 ? 7 : 6)) void k_slope_
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
   const int x0 = txi * TX, y0 = tyi * TY;
   const int H = w.H, W = w.W;
-  const float pinf = __builtin_inff();
   sd_stage<TX, TY>(t, dem, w, x0, y0, vec_ok);
   __syncthreads();
 
@@ -499,7 +506,7 @@ __global__ __launch_bounds__(256, WX == 1 ? 8 : (WX == 2 ? 7 : 6)) void k_slope_
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const float c = bb[k + 1];
-      const float cz = c == pinf ? DT_NODATA : c;  // the centre's own value
+      const float cz = sd_centre(c);  // the centre's own value
       float sl, rad = 0.0f, tv, mv;
       bool flag = sd_slope_fast(c, a[k], a[k + 1], a[k + 2], bb[k], bb[k + 2], cc[k], cc[k + 1], cc[k + 2], kc, kd, sl);
       const bool snod = cz <= DT_NODATA;  // slope.py:231
@@ -567,7 +574,6 @@ __global__ __launch_bounds__(256) void k_slope_twi_fix(const float *__restrict__
   const int ntiles = tiles_x * tiles_y;
   const double dcard = px, ddiag = px * sqrt(2.0);
   const double inv_card = 1.0 / dcard, inv_diag = 1.0 / ddiag;
-  const float pinf = __builtin_inff();
   // 256 tile marks per step, one per lane: an unmarked raster costs ceil(ntiles / 256) independent byte loads
   __shared__ uint8_t s_mark[256];
   for (int chunk = blockIdx.x / SD_FIX_SPLIT; chunk * 256 < ntiles; chunk += gridDim.x / SD_FIX_SPLIT) {
@@ -594,7 +600,7 @@ __global__ __launch_bounds__(256) void k_slope_twi_fix(const float *__restrict__
         const int gy = y0 + ry + j, gx = x0 + cx + k;
         if (gy >= w.H || gx >= w.W) continue;
         const float *p = &t[(ry + j + 1) * LDW + 4 + cx + k];  // the centre in the staged tile
-        const float cz = p[0] == pinf ? DT_NODATA : p[0];
+        const float cz = sd_centre(p[0]);
         SlopeCell sc = dt_slope_cell<false, true>(cz, p[-LDW - 1], p[-LDW], p[-LDW + 1], p[-1], p[1],
                                                   p[LDW - 1], p[LDW], p[LDW + 1], inv_card, inv_diag, dcard,
                                                   ddiag);
@@ -647,7 +653,7 @@ __device__ __forceinline__ bool sd_d8_fast(float c, float nw, float n, float ne,
 }
 
 // nod4 (may be NULL): the nodata mask, one 16-bit word per 4 x 4 patch of cells -- bit 4 j + k = cell (4 r + j, 4 i + k)
-// holds the nodata sentinel (z <= -100; a non-finite height counts as nodata here, as for the codes) -- what the flow-accumulation
+// holds the nodata sentinel (z <= -100 and nothing else: NaN and +inf are heights, as in the reference) -- what the flow-accumulation
 // pass needs of the DEM (-100 on nodata cells), so that it reads 0.125 instead of 4 bytes per cell (dt_dev_slope_d8_m /
 // dt_dev_flowacc_river_flowhand_local_m).  A patch is what one thread of this kernel owns: ONE store per thread (four
 // byte stores, a row each, cost this issue-bound kernel 12 %).  ldm = words per row of patches.  Only for a single
@@ -661,7 +667,6 @@ __global__ __launch_bounds__(256, 8) void k_d8(const float *__restrict__ dem, Dt
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
   const int x0 = txi * SD_TX, y0 = tyi * SD_TY;
   const int H = w.H, W = w.W;
-  const float pinf = __builtin_inff();
   sd_stage(t, dem, w, x0, y0, vec_ok);
   __syncthreads();
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -694,7 +699,7 @@ __global__ __launch_bounds__(256, 8) void k_d8(const float *__restrict__ dem, Dt
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const float c = bb[k + 1];
-      const bool nod = !(c < pinf) || c <= DT_NODATA;  // staged nodata (+inf), NaN, or below the sentinel: code 0
+      const bool nod = sd_centre(c) <= DT_NODATA;  // staged nodata or below the sentinel: code 0 (NaN, +inf: not)
       nodmask |= (nod ? 1u : 0u) << (4 * j + k);
       uint32_t code;
       bool flag = sd_d8_fast(c, a[k], a[k + 1], a[k + 2], bb[k], bb[k + 2], cc[k], cc[k + 1], cc[k + 2], code);
@@ -744,7 +749,6 @@ __global__ __launch_bounds__(256) void k_d8_fix(const float *__restrict__ dem, D
   const int ntiles = tiles_x * tiles_y;
   const double dcard = px, ddiag = px * sqrt(2.0);
   const double inv_card = 1.0 / dcard, inv_diag = 1.0 / ddiag;
-  const float pinf = __builtin_inff();
   for (int chunk = blockIdx.x / SD_FIX_SPLIT; chunk * 256 < ntiles; chunk += gridDim.x / SD_FIX_SPLIT) {
     const int mine = chunk * 256 + (int)threadIdx.x;
     const uint8_t m = mine < ntiles ? tile_mark[mine] : (uint8_t)0;
@@ -768,13 +772,13 @@ __global__ __launch_bounds__(256) void k_d8_fix(const float *__restrict__ dem, D
         const int gy = y0 + ry + j, gx = x0 + cx + k;
         if (gy >= w.H || gx >= w.W) continue;
         const float *p = &t[(ry + j + 1) * SD_LDW + 4 + cx + k];
-        const float cz = p[0] == pinf ? DT_NODATA : p[0];
+        const float cz = sd_centre(p[0]);
         SlopeCell sc = dt_slope_cell<true, false>(cz, p[-SD_LDW - 1], p[-SD_LDW], p[-SD_LDW + 1], p[-1], p[1],
                                                   p[SD_LDW - 1], p[SD_LDW], p[SD_LDW + 1], inv_card, inv_diag, dcard,
                                                   ddiag);
         uint32_t code = sc.code;
         const int gyy = w.gy0 + gy, gxx = w.gx0 + gx;
-        if (code == 0u && cz > DT_NODATA) {
+        if (code == 0u && !(cz <= DT_NODATA)) {
           if (gyy == w.Hg - 1) code = 4u;
           else if (gyy == 0) code = 64u;
           else if (gxx == 0) code = 16u;

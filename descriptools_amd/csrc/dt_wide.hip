@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256) void k_downslope_f64(const double *__restrict_
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (int64_t)H * W) return;
   const double z0 = dem[i];
-  if (z0 <= -100.0) {  // downslope.py:460
-    out[i] = DT_NODATA;
+  if (!(z0 > -100.0 && z0 < __builtin_inf())) {  // downslope.py:460; NaN / +inf: NaN (DS_NONFINITE, dt_kernels.hip)
+    out[i] = z0 <= -100.0 ? DT_NODATA : __builtin_nanf("");
     return;
   }
   const double dcard = px, ddiag = px * sqrt(2.0);
@@ -178,6 +178,8 @@ __global__ __launch_bounds__(1024) void k_downslope_win_f64(const double *__rest
     float res;
     if (z0 <= -100.0) {  // downslope.py:460
       res = DT_NODATA;
+    } else if (!(z0 < __builtin_inf())) {  // NaN / +inf start: NaN (DS_NONFINITE, dt_kernels.hip)
+      res = __builtin_nanf("");
     } else {
       int y = y0, x = x0, loop = 0;
       double dist = 0.0, drop = z0 - z0;
@@ -317,6 +319,8 @@ __global__ __launch_bounds__(1024) void k_downslope_win_f64_w(const double *__re
     float res;
     if (z0 <= -100.0) {  // downslope.py:460
       res = DT_NODATA;
+    } else if (!(z0 < __builtin_inf())) {  // NaN / +inf start: NaN (DS_NONFINITE, dt_kernels.hip)
+      res = __builtin_nanf("");
     } else {
       int y = y0, x = x0, loop = 0;
       double dist = 0.0, drop = z0 - z0;

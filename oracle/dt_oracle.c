@@ -556,6 +556,11 @@ int dt_oracle_lnhlh(const float *hand, const int64_t *fac, int64_t N, double n, 
  *   (:310,:312), float64 quotient stored float32 (:352, :366).
  *   0/0 (a walk that never moves for 5000 iterations: a valid-DEM cell with a non-D8
  *   code) is undefined in the reference; the build returns 0.
+ *   A NaN or +inf start cell is different: the device kernel's loop test z0 - z0 < dz
+ *   (downslope.py:468) is NaN < dz, false, so the walk never starts, is not marked -50,
+ *   and the kernel stores (z0 - z0) / 0 = NaN directly (:532), which the sequential
+ *   repair leaves alone.  That NaN is defined IEEE behaviour, not an undefined 0/0 that
+ *   goes through the -50 path, so the build returns NaN there (tests/golden/nonfinite.npz).
  * ---------------------------------------------------------------------------------- */
 int dt_oracle_downslope(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                         double dz, float *out) {
@@ -585,7 +590,9 @@ int dt_oracle_downslope(const float *dem, const uint8_t *fdr, int64_t H, int64_t
       if (++loop == 5000) break;
     }
     volatile float drop = z0 - dem[pos];
-    if (dist == 0.0)
+    if (z0 != z0 || z0 == INFINITY)
+      out[i] = NAN; /* the walk never starts (NaN < dz is false): NaN / 0, not repaired (see above) */
+    else if (dist == 0.0)
       out[i] = 0.0f; /* stopped && dist==0 -> 0 (:307); 0/0 undefined -> 0 */
     else
       out[i] = (float)((double)drop / dist);
@@ -670,7 +677,10 @@ int dt_oracle_downslope_f64(const double *dem, const uint8_t *fdr, int64_t H, in
       if (++loop == 5000) break;
     }
     volatile double drop = z0 - dem[pos];
-    out[i] = dist == 0.0 ? 0.0f : (float)(drop / dist);
+    if (z0 != z0 || z0 == INFINITY)
+      out[i] = NAN; /* NaN or +inf start: NaN / 0, as in dt_oracle_downslope */
+    else
+      out[i] = dist == 0.0 ? 0.0f : (float)(drop / dist);
   }
   return 0;
 }

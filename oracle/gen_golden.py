@@ -18,6 +18,8 @@ fixtures here: int16 Example data and 1/256-m synthetic heights).
 D8 / flow accumulation do not exist in the reference; for the synthetic cases they come from
 the build's own oracle (oracle/dt_oracle.c) and are stored as INPUTS of the golden file.
 """
+import contextlib
+import math
 import os
 import sys
 import time
@@ -129,6 +131,90 @@ def case_f64():
     out = run_chain(dem64, fdr, fac, river, px)
     assert out["hand"].dtype == np.float64
     save("f64", dem=dem64, fdr=fdr, fac=fac, river=river, px=px, n_top=0.1, n_gfi=0.4, b=0.1, dz=5.0, **out)
+
+
+class _IeeeMath:
+    """`math` with IEEE results where Python's raises (log of 0 or of a negative, tan of inf, pow of a negative base):
+    what Numba's device math returns.  Handed to the reference's modules for the non-finite cases only."""
+    ceil, floor = staticmethod(math.ceil), staticmethod(math.floor)
+    sqrt = staticmethod(lambda x: float(np.sqrt(np.float64(x))))
+    log = staticmethod(lambda x: float(np.log(np.float64(x))))
+    tan = staticmethod(lambda x: float(np.tan(np.float64(x))))
+    pow = staticmethod(lambda x, y: float(np.power(np.float64(x), np.float64(y))))
+
+
+@contextlib.contextmanager
+def ieee_math():
+    mods = (R_slope, R_topo, R_flowhand, R_gfi, R_down)
+    for m in mods:
+        m.math = _IeeeMath
+    try:
+        yield
+    finally:
+        for m in mods:
+            m.math = math
+
+
+def nonfinite_dem(H=80, W=100):
+    """Synthetic float32 DEM (1/256-m heights, -100 blobs) with NaN, +inf, -inf and finite below-sentinel heights planted
+    in the interior, on every edge and corner, next to -100 and touching one another."""
+    dem = oracle.synth_dem(8, 1024, 1024, 600, 700, H, W, 8)
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    plant = {nan: [(40, 50), (41, 50), (0, 37), (H - 1, 61), (22, 0), (57, W - 1), (0, 0), (H - 1, W - 1), (12, 13),
+                   (30, 30), (30, 31), (65, 20)],
+             inf: [(50, 70), (0, 80), (70, 0), (H - 1, 5), (30, 32), (66, 20), (20, 88)],
+             -inf: [(60, 60), (10, 45), (0, W - 1), (31, 31), (65, 21)],
+             np.float32(-250): [(15, 15), (H - 1, 90), (31, 30), (20, 89)],
+             np.float32(-9999): [(45, 80), (44, 80), (20, W - 1)]}
+    for v, cells in plant.items():
+        for y, x in cells:
+            dem[y, x] = v
+    # NaN next to a -100 cell: the first blob's border, whichever side it is on
+    ny, nx = np.nonzero(dem == -100)
+    assert len(ny) > 0
+    y, x = int(ny[0]), int(nx[0])
+    for yy, xx in ((y - 1, x), (y, x - 1), (y + 1, x + 1)):
+        if 0 <= yy < H and 0 <= xx < W and dem[yy, xx] != -100:
+            dem[yy, xx] = nan
+    return dem
+
+
+def case_nonfinite():
+    """G-nonfinite: NaN, +inf, -inf and heights below the sentinel in a float32 DEM (the nodata of a GeoTIFF whose
+    nodata value is NaN reaches the chain as NaN).  D8 / accumulation / river from the oracle, descriptors from the
+    reference under IEEE math."""
+    print("nonfinite", flush=True)
+    px, thr = 10.0, 30
+    dem32 = nonfinite_dem()
+    _, fdr = oracle.slope_d8(dem32, px)
+    fac = oracle.flowacc(fdr, dem32)
+    river = (fac > thr).astype(np.int8)
+    with ieee_math():
+        out = run_chain(dem32.astype(np.float64), fdr, fac, river, px)
+    out["hand"] = out["hand"].astype(np.float32)
+    save("nonfinite", dem=dem32, fdr=fdr, fac=fac, river=river, px=px, n_top=0.1, n_gfi=0.4, b=0.1, dz=5.0, **out)
+
+
+def case_nonfinite_f64():
+    """The non-finite DEM as a genuine float64 raster (the sub-float32 ripple of case_f64 on the finite heights above
+    the sentinel; NaN, +-inf and the below-sentinel heights kept)."""
+    print("nonfinite_f64", flush=True)
+    px, thr = 10.0, 30
+    dem32 = nonfinite_dem()
+    H, W = dem32.shape
+    yy, xx = np.mgrid[0:H, 0:W]
+    ripple = 1e-3 * np.sin(0.37 * yy + 0.11 * xx) + 1e-6 * np.cos(1.3 * xx)
+    with np.errstate(invalid="ignore"):
+        plain = np.isfinite(dem32) & (dem32 > -100)
+    dem64 = np.where(plain, dem32.astype(np.float64) + ripple, dem32.astype(np.float64))
+    _, fdr = oracle.slope_d8(dem64.astype(np.float32), px)
+    fac = oracle.flowacc(fdr, dem64.astype(np.float32))
+    river = (fac > thr).astype(np.int8)
+    with ieee_math():
+        out = run_chain(dem64, fdr, fac, river, px)
+    assert out["hand"].dtype == np.float64
+    save("nonfinite_f64", dem=dem64, fdr=fdr, fac=fac, river=river, px=px, n_top=0.1, n_gfi=0.4, b=0.1, dz=5.0,
+         **out)
 
 
 def case_example_windows():
@@ -444,7 +530,7 @@ def case_example_descriptors():
     save("example_desc", **res)
 
 
-CASES = {"f64": case_f64, "shims": case_shims, "example_descriptors": case_example_descriptors, "synth": case_synth, "example_windows": case_example_windows, "edge": case_edge,
+CASES = {"f64": case_f64, "nonfinite": case_nonfinite, "nonfinite_f64": case_nonfinite_f64,"shims": case_shims, "example_descriptors": case_example_descriptors, "synth": case_synth, "example_windows": case_example_windows, "edge": case_edge,
          "eval": case_eval, "example_full": case_example_full}
 
 if __name__ == "__main__":

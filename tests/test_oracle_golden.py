@@ -186,3 +186,92 @@ def test_example_known_answer_oracle():
     # nodata was mapped to -7 and desc[0] == -7 marks it as the nodata value (evaluation.py:111)
     assert np.array_equal(counts[0], g["counts"])
     assert np.array_equal(np.bincount(klass.reshape(-1).astype(np.int64), minlength=4), g["counts"])
+
+
+# ------------------------------------------------------------------------------------------
+# Non-finite heights (tests/golden/nonfinite*.npz, oracle/gen_golden.py nonfinite): NaN, +inf, -inf and finite
+# heights below the sentinel on the border, in the interior and touching one another.  The reference under IEEE math.
+
+def _nonfinite_pits(g):
+    """downslope: the reference's 0/0 at valid-height pits (fdr == 0) is defined as 0 by the build; its
+    NaN at a NaN or +inf start cell is kept (dt_oracle.c, dt_oracle_downslope)."""
+    dem, ref = g["dem"], g["down"]
+    start = np.isnan(dem) | np.isposinf(dem)
+    pit = np.isnan(ref) & ~start
+    assert (g["fdr"][pit] == 0).all() and np.isnan(ref[start]).all()
+    return np.where(pit, 0, ref)
+
+
+def test_nonfinite_fixture_holds_the_special_values():
+    for name in ("nonfinite", "nonfinite_f64"):
+        dem = golden(name)["dem"]
+        H, W = dem.shape
+        nan = np.isnan(dem)
+        for edge in (nan[0], nan[-1], nan[:, 0], nan[:, -1]):
+            assert edge.any()
+        assert nan[0, 0] and nan[-1, -1]
+        assert np.isposinf(dem[1:-1, 1:-1]).any() and np.isposinf(dem[[0, -1]]).any()
+        assert np.isneginf(dem).sum() >= 3 and (dem == -250).any() and (dem == -9999).any()
+        nod = dem == -100
+        near = np.zeros_like(nod)
+        near[1:, :] |= nod[:-1, :]
+        near[:-1, :] |= nod[1:, :]
+        near[:, 1:] |= nod[:, :-1]
+        near[:, :-1] |= nod[:, 1:]
+        assert (nan & near).any()
+
+
+def test_nonfinite_d8_and_flowacc():
+    g = golden("nonfinite")
+    dem = g["dem"]
+    sl, fdr = oracle.slope_d8(dem, float(g["px"]))
+    assert np.array_equal(sl, g["slope"])
+    assert np.array_equal(fdr, g["fdr"])
+    # NaN centre: slope 0, code 0 inside, the out-code on the border; +inf centre: slope inf and a code
+    nan = np.isnan(dem)
+    assert (sl[nan] == 0).all() and (fdr[1:-1, 1:-1][nan[1:-1, 1:-1]] == 0).all()
+    assert (fdr[0][nan[0]] == 64).all() and (fdr[-1][nan[-1]] == 4).all()
+    assert (fdr[1:-1, 0][nan[1:-1, 0]] == 16).all() and (fdr[1:-1, -1][nan[1:-1, -1]] == 1).all()
+    assert np.isposinf(sl[np.isposinf(dem)]).all() and (fdr[np.isposinf(dem)] != 0).all()
+    acc = oracle.flowacc(g["fdr"], dem)
+    assert np.array_equal(acc, g["fac"])
+    assert np.array_equal(acc == -100, dem <= -100)   # the nodata of accumulation is exactly dem <= -100
+
+
+@pytest.mark.parametrize("name", ["nonfinite"])
+def test_nonfinite_descriptors(name):
+    g = golden(name)
+    dem, px = g["dem"], float(g["px"])
+    ti, mti = oracle.twi(g["fac"], g["slope_rad"], px, float(g["n_top"]))
+    assert_float_close(ti, g["ti"], rtol=1e-6, what="ti")
+    assert_float_close(mti, g["mti"], rtol=1e-6, atol=1e-7, what="mti")
+    assert np.array_equal(np.isnan(ti), np.isnan(g["ti"])) and np.array_equal(np.isinf(ti), np.isinf(g["ti"]))
+    fd, idx, hand = oracle.flowhand(dem, g["fdr"], g["river"], px)
+    assert np.array_equal(idx, g["idx"])
+    assert np.array_equal(fd, g["fdist"])
+    assert np.array_equal(hand, g["hand"], equal_nan=True)
+    idx2, _, _ = oracle.flowhand_fast(g["fdr"], g["river"])
+    assert np.array_equal(idx2, idx)
+    out = oracle.gfi(hand, g["fac"], g["idx"], float(g["n_gfi"]), float(g["b"]), px)
+    assert_float_close(out, g["gfi"], rtol=1e-6, atol=1e-7, what="gfi")
+    out = oracle.lnhlh(hand, g["fac"], float(g["n_gfi"]), float(g["b"]), px)
+    assert_float_close(out, g["lnhlh"], rtol=1e-6, atol=1e-7, what="lnhlh")
+    down = oracle.downslope(dem, g["fdr"], px, float(g["dz"]))
+    assert np.array_equal(down, _nonfinite_pits(g), equal_nan=True)
+
+
+def test_nonfinite_f64_descriptors():
+    g = golden("nonfinite_f64")
+    dem, px = g["dem"], float(g["px"])
+    assert np.array_equal(oracle.slope_f64(dem, px), g["slope"])
+    assert np.array_equal(oracle.hand_f64(dem, g["idx"]), g["hand"], equal_nan=True)
+    assert np.array_equal(oracle.downslope_f64(dem, g["fdr"], px, float(g["dz"])), _nonfinite_pits(g),
+                          equal_nan=True)
+    assert_float_close(oracle.gfi_f64h(g["hand"], g["fac"], g["idx"], 0.4, 0.1, px), g["gfi"], rtol=1e-6,
+                       what="gfi")
+    assert_float_close(oracle.lnhlh_f64h(g["hand"], g["fac"], 0.4, 0.1, px), g["lnhlh"], rtol=1e-6, atol=1e-7,
+                       what="lnhlh")
+    # D8 of the float64 tier (the float32-rounded heights' codes are the fixture's inputs)
+    _, fdr = oracle.slope_d8(dem.astype(np.float32), px)
+    assert np.array_equal(fdr, g["fdr"])
+    assert np.array_equal(oracle.flowacc(g["fdr"], dem.astype(np.float32)), g["fac"])
