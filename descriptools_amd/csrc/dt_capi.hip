@@ -1,4 +1,5 @@
 // dt_capi.hip -- extern "C" boundary of libdescriptools_hip.so (see include/descriptools_hip.h).
+#include <cmath>
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -570,6 +571,43 @@ extern "C" int dt_dev_stream_order(dt_ctx *c, const uint8_t *fdr, const int8_t *
   int64_t m = 0;
   DT_TRY(dt_launch_stream_order(c->stream, fdr, river, H, W, scr, need, strahler, shreve, link,
                                 H * W >= (1ll << 31) ? &m : nullptr));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
+// drainage / upslope length: flat indices travel in 31 bits, so the raster has fewer than 2^31 cells
+static int dt_check_ws(int64_t H, int64_t W, double px) {
+  DT_REQUIRE(H >= 0 && W >= 0, "negative raster shape");
+  DT_REQUIRE(W == 0 || H < ((1ll << 31) + W - 1) / W, "raster of 2^31 cells or more");
+  DT_REQUIRE(std::isfinite(px) && px > 0.0, "px must be finite and > 0");
+  return DT_OK;
+}
+
+extern "C" int dt_dev_drainage(dt_ctx *c, const uint8_t *fdr, const float *dem, const int64_t *pour, int64_t H,
+                               int64_t W, double px, int64_t *target, double *length, int64_t *label) {
+  DT_CTX(c);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_REQUIRE(fdr || H * W == 0, "NULL raster");
+  DT_REQUIRE(!label || pour, "label requires pour");
+  if (H * W == 0) return DT_OK;
+  size_t need = dt_drainage_scratch(H, W);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  DT_TRY(dt_launch_drainage(c->stream, fdr, dem, pour, H, W, px, scr, need, target, length, label));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
+extern "C" int dt_dev_upslope_length(dt_ctx *c, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
+                                     double *length) {
+  DT_CTX(c);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_REQUIRE(fdr || H * W == 0, "NULL raster");
+  if (H * W == 0 || !length) return DT_OK;
+  size_t need = dt_upslope_length_scratch(H, W);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  DT_TRY(dt_launch_upslope_length(c->stream, fdr, dem, H, W, px, scr, need, length));
   DT_HIP(hipGetLastError());
   return DT_OK;
 }
@@ -1806,6 +1844,62 @@ extern "C" int dt_stream_order(const uint8_t *fdr, const int8_t *river, int64_t 
   D2H(strahler, d_o, n, c);
   if (shreve) D2H(shreve, d_s, n * 8, c);
   if (link) D2H(link, d_l, n * 8, c);
+  return dt_ctx_sync(c);
+}
+
+extern "C" int dt_drainage(const uint8_t *fdr, const float *dem, const int64_t *pour, int64_t H, int64_t W,
+                           double px, int64_t *target, double *length, int64_t *label) {
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  dt_ctx *c;
+  DT_TRY(host_ctx(&c));
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_REQUIRE(!label || pour, "label requires pour");
+  size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(fdr, "NULL raster");
+  DevBuf d_f, d_dem, d_p, d_t, d_l, d_b;
+  DT_TRY(d_f.alloc(n));
+  H2D(d_f, fdr, n, c);
+  if (dem) {
+    DT_TRY(d_dem.alloc(n * 4));
+    H2D(d_dem, dem, n * 4, c);
+  }
+  if (pour) {
+    DT_TRY(d_p.alloc(n * 8));
+    H2D(d_p, pour, n * 8, c);
+  }
+  if (target) DT_TRY(d_t.alloc(n * 8));
+  if (length) DT_TRY(d_l.alloc(n * 8));
+  if (label) DT_TRY(d_b.alloc(n * 8));
+  DT_TRY(dt_dev_drainage(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, pour ? d_p.as<int64_t>() : nullptr,
+                         H, W, px, target ? d_t.as<int64_t>() : nullptr, length ? d_l.as<double>() : nullptr,
+                         label ? d_b.as<int64_t>() : nullptr));
+  if (target) D2H(target, d_t, n * 8, c);
+  if (length) D2H(length, d_l, n * 8, c);
+  if (label) D2H(label, d_b, n * 8, c);
+  return dt_ctx_sync(c);
+}
+
+extern "C" int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
+                                 double *length) {
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  dt_ctx *c;
+  DT_TRY(host_ctx(&c));
+  DT_TRY(dt_check_ws(H, W, px));
+  size_t n = (size_t)H * W;
+  if (n == 0 || !length) return DT_OK;
+  DT_REQUIRE(fdr, "NULL raster");
+  DevBuf d_f, d_dem, d_l;
+  DT_TRY(d_f.alloc(n));
+  DT_TRY(d_l.alloc(n * 8));
+  H2D(d_f, fdr, n, c);
+  if (dem) {
+    DT_TRY(d_dem.alloc(n * 4));
+    H2D(d_dem, dem, n * 4, c);
+  }
+  DT_TRY(dt_dev_upslope_length(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, H, W, px,
+                               d_l.as<double>()));
+  D2H(length, d_l, n * 8, c);
   return dt_ctx_sync(c);
 }
 

@@ -175,3 +175,13 @@ int dt_flow_impl();  // 1 global kernels, 2 tile-hierarchical (default)
 size_t dt_stream_order_scratch(int64_t H, int64_t W);
 int dt_launch_stream_order(hipStream_t s, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, void *scratch,
                            size_t scratch_bytes, int8_t *strahler, int64_t *shreve, int64_t *link, int64_t *m_host);
+
+// drainage / upslope length (dt_watershed.hip).  dem (nodata mask: <= -100) and pour (> 0: pour point) may be NULL;
+// target / length / label may be NULL (label only with pour).  Nothing synchronises.  H * W < 2^31.
+size_t dt_drainage_scratch(int64_t H, int64_t W);
+size_t dt_upslope_length_scratch(int64_t H, int64_t W);
+int dt_launch_drainage(hipStream_t s, const uint8_t *fdr, const float *dem, const int64_t *pour, int64_t H, int64_t W,
+                       double px, void *scratch, size_t scratch_bytes, int64_t *target, double *length,
+                       int64_t *label);
+int dt_launch_upslope_length(hipStream_t s, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
+                             void *scratch, size_t scratch_bytes, double *length);

@@ -160,6 +160,24 @@ int dt_flowacc_weighted(const uint8_t *fdr, const float *dem, const double *w, i
  * are exact integers.  shreve and link may be NULL (not written); a network of 2^31 cells or more is refused. */
 int dt_stream_order(const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, int8_t *strahler, int64_t *shreve,
                     int64_t *link);
+/* Net-new: drainage on the D8 raster `fdr`.  c -> d is an edge when c's code is one of the eight D8 codes, d lies in
+ * the raster and, when `dem` is given, neither c nor d is nodata (dem <= -100).  A valid cell with no edge is a
+ * terminal.  `pour` (may be NULL): pour[i] > 0 is a pour point, anything else none.
+ *   target (int64): the flat index y * W + x where c's path stops: the first cell on it (c included) with pour > 0
+ *                   when pour is given, else its terminal.
+ *   length (float64): from c to target, float64(n_card) * px + float64(n_diag) * (px * sqrt(2.0)) on the path's
+ *                   exact move counts; 0 when c is its own target.
+ *   label (int64, requires pour): pour[target]; 0 where the path reaches a terminal without meeting a pour point.
+ * target and length are -100 on nodata, where the path enters a D8 cycle before it stops and (with pour) where it
+ * ends at a terminal without meeting a pour point; label is -100 in the first two cases.  Any output may be NULL
+ * (not written).  Rasters of 2^31 cells or more and a px that is not finite and > 0 are refused. */
+int dt_drainage(const uint8_t *fdr, const float *dem, const int64_t *pour, int64_t H, int64_t W, double px,
+                int64_t *target, double *length, int64_t *label);
+/* Net-new: upslope (longest) flow length on dt_drainage's graph without pour points: for every cell c the length of
+ * the longest path that ends at c (0 at a source), longest on the exact order of n_card + n_diag * sqrt(2), as
+ * float64(n_card) * px + float64(n_diag) * (px * sqrt(2.0)).  -100 on nodata and on cells of a D8 cycle; cells that
+ * drain into a cycle get their value.  Same refusals as dt_drainage. */
+int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px, double *length);
 
 /* flowhand.flow_distance_index_cpu + flow_distance_index_gpu (flowhand.py:476-846, untiled
  * call: out = 0, row_start = col_start = 0, matrix_columns = W) and flowhand.hand_calculator
@@ -291,6 +309,12 @@ int dt_dev_flowacc_weighted(dt_ctx *ctx, const uint8_t *fdr, const float *dem, c
  * cells or more, where it reads the network's size back to refuse 2^31 network cells).  shreve and link may be NULL. */
 int dt_dev_stream_order(dt_ctx *ctx, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, int8_t *strahler,
                         int64_t *shreve, int64_t *link);
+/* dt_drainage and dt_upslope_length on device rasters, on the context's stream: they do not synchronise.  dem and
+ * pour may be NULL, so may any output (label requires pour). */
+int dt_dev_drainage(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const int64_t *pour, int64_t H, int64_t W,
+                    double px, int64_t *target, double *length, int64_t *label);
+int dt_dev_upslope_length(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
+                          double *length);
 /* flow accumulation with the river mask (acc > threshold, Example/example.py:52) written by the
  * same final pass */
 int dt_dev_flowacc_river(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
