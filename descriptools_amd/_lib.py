@@ -251,6 +251,26 @@ def as_c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def raster_2d(fdr):
+    """fdr as an array; ValueError unless it is a 2-D raster"""
+    f = np.asarray(fdr)
+    if f.ndim != 2:
+        raise ValueError("fdr must be a 2-D raster, not of shape %s" % (f.shape,))
+    return f
+
+
+def nodata_mask(dem, shape):
+    """The float32 nodata mask the flow ops take from a DEM (-100 where dem <= -100, 0 elsewhere, compared in the
+    DEM's own dtype: NaN is not nodata), or None for dem None; ValueError when dem is not of the direction raster's
+    shape"""
+    if dem is None:
+        return None
+    dm = np.asarray(dem)
+    if dm.shape != shape:
+        raise ValueError("dem has shape %s, the direction raster %s" % (dm.shape, shape))
+    return np.where(dm <= -100, np.float32(-100), np.float32(0)).astype(np.float32)
+
+
 _EXACT_IN_F32 = (np.float32, np.float16, np.int8, np.uint8, np.int16, np.uint16, np.bool_)
 
 

@@ -1504,7 +1504,7 @@ extern "C" int dt_dev_hand_gfi_f64_w_a64(dt_ctx *c, const dt_window *win, const 
                             table, table_bytes, px, n_gfi, b, hand, gfi, lnhlh);
 }
 
-// ---- host tier: H2D, kernels, D2H on a process-wide default context ----------------------------
+// ---- host tier: upload, kernels, download on a process-wide default context ----------------------------
 static dt_ctx *g_host_ctx = nullptr;
 static std::mutex g_host_mu;  // whole-call granularity, as SURVEY.md 8b (threading) allows
 
@@ -1527,6 +1527,22 @@ struct HostBlock {
   bool busy;
 };
 static std::vector<HostBlock> g_blocks;
+static void host_blocks_drop_idle(size_t keep_bytes) {
+  // largest idle blocks go first; the host tier's stream is idle whenever a block is released (a HostCall waits for
+  // it before it releases its blocks)
+  for (;;) {
+    size_t idle = 0;
+    int big = -1;
+    for (size_t i = 0; i < g_blocks.size(); i++)
+      if (!g_blocks[i].busy) {
+        idle += g_blocks[i].bytes;
+        if (big < 0 || g_blocks[i].bytes > g_blocks[(size_t)big].bytes) big = (int)i;
+      }
+    if (idle <= keep_bytes || big < 0) return;
+    (void)hipFree(g_blocks[(size_t)big].p);
+    g_blocks.erase(g_blocks.begin() + big);
+  }
+}
 static void *host_block_take(size_t bytes) {
   int best = -1;
   for (size_t i = 0; i < g_blocks.size(); i++)
@@ -1539,15 +1555,7 @@ static void *host_block_take(size_t bytes) {
   }
   void *p = nullptr;
   if (hipMalloc(&p, bytes) != hipSuccess) {
-    // out of memory: drop every idle block and try once more
-    for (size_t i = 0; i < g_blocks.size();) {
-      if (!g_blocks[i].busy) {
-        (void)hipFree(g_blocks[i].p);
-        g_blocks.erase(g_blocks.begin() + (long)i);
-      } else {
-        i++;
-      }
-    }
+    host_blocks_drop_idle(0);  // out of memory: drop every idle block and try once more
     (void)hipGetLastError();
     if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
   }
@@ -1564,45 +1572,81 @@ static size_t host_cache_budget() {
   }
   return (size_t)mb << 20;
 }
-static void host_blocks_drop_idle(size_t keep_bytes) {
-  // largest idle blocks go first; the host tier's stream is idle whenever a block is released (every dt_<op> ends
-  // with a synchronisation before its DevBufs go out of scope)
-  for (;;) {
-    size_t idle = 0;
-    int big = -1;
-    for (size_t i = 0; i < g_blocks.size(); i++)
-      if (!g_blocks[i].busy) {
-        idle += g_blocks[i].bytes;
-        if (big < 0 || g_blocks[i].bytes > g_blocks[(size_t)big].bytes) big = (int)i;
-      }
-    if (idle <= keep_bytes || big < 0) return;
-    (void)hipFree(g_blocks[(size_t)big].p);
-    g_blocks.erase(g_blocks.begin() + big);
-  }
-}
 static void host_block_release(void *p) {
   for (auto &b : g_blocks)
     if (b.p == p) b.busy = false;
   host_blocks_drop_idle(host_cache_budget());
 }
-// RAII device buffer of the host tier
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) host_block_release(p);
+// One host-tier call: it holds g_host_mu and the host context throughout and owns the call's device blocks.  in()
+// uploads a host array into a new block, out() gives a block that finish() downloads, scratch() one that stays on the
+// device: each returns the typed device pointer, NULL for a NULL host pointer.  rc keeps the first failure (opening
+// the context included) and nothing is enqueued after it: an entry checks it on entry and before its first launch.
+// finish() enqueues the downloads in the order they were asked for and synchronises; an entry that returns before it
+// still waits for its stream (dt_last_error() keeps its message), so nothing enqueued outlives the call or its blocks.
+struct HostCall {
+  std::lock_guard<std::mutex> lk{g_host_mu};  // first member: the blocks are released while it is held
+  dt_ctx *c = nullptr;
+  int rc = host_ctx(&c);
+  ~HostCall() {
+    if (!synced && c) (void)hipStreamSynchronize(c->stream);
+    for (void *p : blocks) host_block_release(p);
   }
-  int alloc(size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    p = host_block_take(bytes);
-    if (!p) {
-      dt_set_error("hipMalloc of %zu bytes failed", bytes);
-      return DT_ENOMEM;
-    }
-    return DT_OK;
+  // a block the call can do without: NULL when none is to be had, and no failure recorded
+  void *workspace(size_t bytes) {
+    void *p = host_block_take(bytes ? bytes : 16);
+    if (p) blocks.push_back(p);
+    return p;
   }
   template <typename T>
-  T *as() {
-    return (T *)p;
+  T *scratch(size_t count) {
+    T *d = rc == DT_OK ? (T *)workspace(count * sizeof(T)) : nullptr;
+    if (!d && rc == DT_OK) {
+      dt_set_error("hipMalloc of %zu bytes failed", count ? count * sizeof(T) : 16);
+      rc = DT_ENOMEM;
+    }
+    return d;
+  }
+  template <typename T>
+  T *in(const T *src, size_t count) {
+    T *d = src ? scratch<T>(count) : nullptr;
+    if (d) copy(d, src, count * sizeof(T), hipMemcpyHostToDevice);
+    return d;
+  }
+  template <typename T>
+  T *out(T *dst, size_t count) {
+    T *d = dst ? scratch<T>(count) : nullptr;
+    if (d) downloads.push_back({dst, d, count * sizeof(T)});
+    return d;
+  }
+  // a download enqueued now, not at finish()
+  template <typename T>
+  int download(T *dst, const T *src, size_t count) {
+    copy(dst, src, count * sizeof(T), hipMemcpyDeviceToHost);
+    return rc;
+  }
+  int finish() {
+    for (const Copy &d : downloads) copy(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost);
+    if (rc != DT_OK) return rc;
+    synced = true;
+    return dt_ctx_sync(c);
+  }
+
+ private:
+  struct Copy {
+    void *dst;
+    const void *src;
+    size_t bytes;
+  };
+  std::vector<void *> blocks;
+  std::vector<Copy> downloads;
+  bool synced = false;
+  void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+    if (rc != DT_OK || bytes == 0) return;
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
+    if (e != hipSuccess) {
+      dt_set_error("hipMemcpyAsync of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+      rc = e == hipErrorOutOfMemory ? DT_ENOMEM : DT_EHIP;
+    }
   }
 };
 extern "C" int dt_host_trim(void) {
@@ -1725,40 +1769,29 @@ extern "C" int dt_host_f32_to_f64(const float *src, double *dst, int64_t n) {
   for (auto &t : th) t.join();
   return DT_OK;
 }
-#define H2D(dst, src, bytes, c) DT_HIP(hipMemcpyAsync((dst).p, (src), (bytes), hipMemcpyHostToDevice, (c)->stream))
-#define D2H(dst, src, bytes, c) DT_HIP(hipMemcpyAsync((dst), (src).p, (bytes), hipMemcpyDeviceToHost, (c)->stream))
-
 extern "C" int dt_synth_dem(uint32_t seed, int64_t Hg, int64_t Wg, int64_t y0, int64_t x0, int64_t h,
                             int64_t w, int nodata_pct, float *out) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
-  size_t n = (size_t)h * w;
-  DevBuf d;
-  DT_TRY(d.alloc(n * 4));
-  DT_TRY(dt_dev_synth_dem(c, seed, Hg, Wg, y0, x0, h, w, nodata_pct, d.as<float>()));
-  D2H(out, d, n * 4, c);
-  return dt_ctx_sync(c);
+  HostCall hc;
+  DT_TRY(hc.rc);
+  float *d = hc.out(out, (size_t)h * w);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_synth_dem(hc.c, seed, Hg, Wg, y0, x0, h, w, nodata_pct, d));
+  return hc.finish();
 }
 
 static int host_slope_d8(const float *dem, int64_t H, int64_t W, double px, float *slope, uint8_t *fdr) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
   DT_REQUIRE(dem || H * W == 0, "dem is NULL");
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
-  DevBuf d_dem, d_sl, d_f;
-  DT_TRY(d_dem.alloc(n * 4));
-  if (slope) DT_TRY(d_sl.alloc(n * 4));
-  if (fdr) DT_TRY(d_f.alloc(n));
-  H2D(d_dem, dem, n * 4, c);
-  DT_TRY(dt_dev_slope_d8(c, d_dem.as<float>(), H, W, px, slope ? d_sl.as<float>() : nullptr,
-                         fdr ? d_f.as<uint8_t>() : nullptr, nullptr));
-  if (slope) D2H(slope, d_sl, n * 4, c);
-  if (fdr) D2H(fdr, d_f, n, c);
-  return dt_ctx_sync(c);
+  const float *d_dem = hc.in(dem, n);
+  float *d_sl = hc.out(slope, n);
+  uint8_t *d_f = hc.out(fdr, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_slope_d8(hc.c, d_dem, H, W, px, d_sl, d_f, nullptr));
+  return hc.finish();
 }
 
 extern "C" int dt_slope_f32(const float *dem, int64_t H, int64_t W, double px, float *slope) {
@@ -1771,246 +1804,168 @@ extern "C" int dt_d8_f32(const float *dem, int64_t H, int64_t W, double px, uint
 }
 
 extern "C" int dt_flowacc_u8(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, int64_t *acc) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(fdr && acc, "NULL raster");
-  DevBuf d_f, d_dem, d_a32, d_a64;
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_a32.alloc(n * 4));
-  DT_TRY(d_a64.alloc(n * 8));
-  H2D(d_f, fdr, n, c);
-  if (dem) {
-    DT_TRY(d_dem.alloc(n * 4));
-    H2D(d_dem, dem, n * 4, c);
-  }
-  DT_TRY(dt_dev_flowacc(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, H, W, d_a32.as<int32_t>()));
-  DT_TRY(dt_dev_i32_to_i64(c, d_a32.as<int32_t>(), (int64_t)n, d_a64.as<int64_t>()));
-  D2H(acc, d_a64, n * 8, c);
-  return dt_ctx_sync(c);
+  const uint8_t *d_f = hc.in(fdr, n);
+  const float *d_dem = hc.in(dem, n);
+  int32_t *d_a32 = hc.scratch<int32_t>(n);
+  int64_t *d_a64 = hc.out(acc, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_flowacc(hc.c, d_f, d_dem, H, W, d_a32));
+  DT_TRY(dt_dev_i32_to_i64(hc.c, d_a32, (int64_t)n, d_a64));
+  return hc.finish();
 }
 
 extern "C" int dt_flowacc_weighted(const uint8_t *fdr, const float *dem, const double *w, int64_t H, int64_t W,
                                    int frac_bits, double *acc) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(fdr && w && acc, "NULL raster");
-  DevBuf d_f, d_dem, d_w, d_a;
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_w.alloc(n * 8));
-  DT_TRY(d_a.alloc(n * 8));
-  H2D(d_f, fdr, n, c);
-  H2D(d_w, w, n * 8, c);
-  if (dem) {
-    DT_TRY(d_dem.alloc(n * 4));
-    H2D(d_dem, dem, n * 4, c);
-  }
+  const uint8_t *d_f = hc.in(fdr, n);
+  const double *d_w = hc.in(w, n);
+  const float *d_dem = hc.in(dem, n);
+  double *d_a = hc.out(acc, n);
+  DT_TRY(hc.rc);
   int32_t st = 0;
-  DT_TRY(dt_ctx_status(c, &st));  // this call's status only
-  DT_TRY(dt_dev_flowacc_weighted(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, d_w.as<double>(), H, W,
-                                 frac_bits, d_a.as<double>()));
-  D2H(acc, d_a, n * 8, c);
-  DT_TRY(dt_ctx_status(c, &st));
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  DT_TRY(dt_dev_flowacc_weighted(hc.c, d_f, d_dem, d_w, H, W, frac_bits, d_a));
+  DT_TRY(dt_ctx_status(hc.c, &st));
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 
 extern "C" int dt_stream_order(const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, int8_t *strahler,
                                int64_t *shreve, int64_t *link) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_so(H, W));
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(fdr && river && strahler, "NULL raster");
-  DevBuf d_f, d_r, d_o, d_s, d_l;
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_r.alloc(n));
-  DT_TRY(d_o.alloc(n));
-  if (shreve) DT_TRY(d_s.alloc(n * 8));
-  if (link) DT_TRY(d_l.alloc(n * 8));
-  H2D(d_f, fdr, n, c);
-  H2D(d_r, river, n, c);
-  DT_TRY(dt_dev_stream_order(c, d_f.as<uint8_t>(), d_r.as<int8_t>(), H, W, d_o.as<int8_t>(), d_s.as<int64_t>(),
-                             d_l.as<int64_t>()));
-  D2H(strahler, d_o, n, c);
-  if (shreve) D2H(shreve, d_s, n * 8, c);
-  if (link) D2H(link, d_l, n * 8, c);
-  return dt_ctx_sync(c);
+  const uint8_t *d_f = hc.in(fdr, n);
+  const int8_t *d_r = hc.in(river, n);
+  int8_t *d_o = hc.out(strahler, n);
+  int64_t *d_s = hc.out(shreve, n);
+  int64_t *d_l = hc.out(link, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_stream_order(hc.c, d_f, d_r, H, W, d_o, d_s, d_l));
+  return hc.finish();
 }
 
 extern "C" int dt_drainage(const uint8_t *fdr, const float *dem, const int64_t *pour, int64_t H, int64_t W,
                            double px, int64_t *target, double *length, int64_t *label) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_ws(H, W, px));
   DT_REQUIRE(!label || pour, "label requires pour");
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(fdr, "NULL raster");
-  DevBuf d_f, d_dem, d_p, d_t, d_l, d_b;
-  DT_TRY(d_f.alloc(n));
-  H2D(d_f, fdr, n, c);
-  if (dem) {
-    DT_TRY(d_dem.alloc(n * 4));
-    H2D(d_dem, dem, n * 4, c);
-  }
-  if (pour) {
-    DT_TRY(d_p.alloc(n * 8));
-    H2D(d_p, pour, n * 8, c);
-  }
-  if (target) DT_TRY(d_t.alloc(n * 8));
-  if (length) DT_TRY(d_l.alloc(n * 8));
-  if (label) DT_TRY(d_b.alloc(n * 8));
-  DT_TRY(dt_dev_drainage(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, pour ? d_p.as<int64_t>() : nullptr,
-                         H, W, px, target ? d_t.as<int64_t>() : nullptr, length ? d_l.as<double>() : nullptr,
-                         label ? d_b.as<int64_t>() : nullptr));
-  if (target) D2H(target, d_t, n * 8, c);
-  if (length) D2H(length, d_l, n * 8, c);
-  if (label) D2H(label, d_b, n * 8, c);
-  return dt_ctx_sync(c);
+  const uint8_t *d_f = hc.in(fdr, n);
+  const float *d_dem = hc.in(dem, n);
+  const int64_t *d_p = hc.in(pour, n);
+  int64_t *d_t = hc.out(target, n);
+  double *d_l = hc.out(length, n);
+  int64_t *d_b = hc.out(label, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_drainage(hc.c, d_f, d_dem, d_p, H, W, px, d_t, d_l, d_b));
+  return hc.finish();
 }
 
 extern "C" int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                                  double *length) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_ws(H, W, px));
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0 || !length) return DT_OK;
   DT_REQUIRE(fdr, "NULL raster");
-  DevBuf d_f, d_dem, d_l;
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_l.alloc(n * 8));
-  H2D(d_f, fdr, n, c);
-  if (dem) {
-    DT_TRY(d_dem.alloc(n * 4));
-    H2D(d_dem, dem, n * 4, c);
-  }
-  DT_TRY(dt_dev_upslope_length(c, d_f.as<uint8_t>(), dem ? d_dem.as<float>() : nullptr, H, W, px,
-                               d_l.as<double>()));
-  D2H(length, d_l, n * 8, c);
-  return dt_ctx_sync(c);
+  const uint8_t *d_f = hc.in(fdr, n);
+  double *d_l = hc.out(length, n);
+  const float *d_dem = hc.in(dem, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_upslope_length(hc.c, d_f, d_dem, H, W, px, d_l));
+  return hc.finish();
 }
 
 extern "C" int dt_flowhand(const float *dem, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W,
                            double px, float *fdist, int64_t *idx, float *hand) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(fdr && river, "NULL raster");
   DT_REQUIRE(!hand || dem, "hand needs dem");
-  DevBuf d_dem, d_f, d_r, d_fd, d_i32, d_i64, d_h;
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_r.alloc(n));
-  H2D(d_f, fdr, n, c);
-  H2D(d_r, river, n, c);
-  if (hand) {
-    DT_TRY(d_dem.alloc(n * 4));
-    H2D(d_dem, dem, n * 4, c);
-    DT_TRY(d_h.alloc(n * 4));
-  }
-  if (fdist) DT_TRY(d_fd.alloc(n * 4));
-  if (idx) {
-    DT_TRY(d_i32.alloc(n * 4));
-    DT_TRY(d_i64.alloc(n * 8));
-  }
-  DT_TRY(dt_dev_flowhand(c, hand ? d_dem.as<float>() : nullptr, d_f.as<uint8_t>(), d_r.as<int8_t>(), nullptr, H,
-                         W, px, fdist ? d_fd.as<float>() : nullptr, idx ? d_i32.as<int32_t>() : nullptr,
-                         hand ? d_h.as<float>() : nullptr, nullptr));
-  if (idx) {
-    DT_TRY(dt_dev_i32_to_i64(c, d_i32.as<int32_t>(), (int64_t)n, d_i64.as<int64_t>()));
-    D2H(idx, d_i64, n * 8, c);
-  }
-  if (fdist) D2H(fdist, d_fd, n * 4, c);
-  if (hand) D2H(hand, d_h, n * 4, c);
-  return dt_ctx_sync(c);
+  const uint8_t *d_f = hc.in(fdr, n);
+  const int8_t *d_r = hc.in(river, n);
+  const float *d_dem = hand ? hc.in(dem, n) : nullptr;
+  int32_t *d_i32 = idx ? hc.scratch<int32_t>(n) : nullptr;
+  int64_t *d_i64 = hc.out(idx, n);
+  float *d_fd = hc.out(fdist, n);
+  float *d_h = hc.out(hand, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_flowhand(hc.c, d_dem, d_f, d_r, nullptr, H, W, px, d_fd, d_i32, d_h, nullptr));
+  if (idx) DT_TRY(dt_dev_i32_to_i64(hc.c, d_i32, (int64_t)n, d_i64));
+  return hc.finish();
 }
 
 extern "C" int dt_twi(const int64_t *fac, const float *slope_rad, int64_t N, double px, double n_top,
                       float *ti, float *mti) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
   if (N == 0) return DT_OK;
   DT_REQUIRE(fac && slope_rad && ti && mti, "NULL raster");
-  size_t n = (size_t)N;
-  DevBuf d_f, d_s, d_t, d_m;
-  DT_TRY(d_f.alloc(n * 8));
-  DT_TRY(d_s.alloc(n * 4));
-  DT_TRY(d_t.alloc(n * 4));
-  DT_TRY(d_m.alloc(n * 4));
-  H2D(d_f, fac, n * 8, c);
-  H2D(d_s, slope_rad, n * 4, c);
-  DT_TRY(dt_launch_twi_i64(c->stream, d_f.as<int64_t>(), d_s.as<float>(), N, px, n_top, d_t.as<float>(),
-                           d_m.as<float>()));
+  const int64_t *d_f = hc.in(fac, N);
+  const float *d_s = hc.in(slope_rad, N);
+  float *d_t = hc.out(ti, N);
+  float *d_m = hc.out(mti, N);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launch_twi_i64(hc.c->stream, d_f, d_s, N, px, n_top, d_t, d_m));
   DT_HIP(hipGetLastError());
-  D2H(ti, d_t, n * 4, c);
-  D2H(mti, d_m, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 
 extern "C" int dt_river_accumulation(const int64_t *fac, const int64_t *idx, int64_t N, int64_t *out) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
   if (N == 0) return DT_OK;
   DT_REQUIRE(fac && idx && out, "NULL raster");
-  size_t n = (size_t)N;
-  DevBuf d_f, d_i, d_a;
-  DT_TRY(d_f.alloc(n * 8));
-  DT_TRY(d_i.alloc(n * 8));
-  DT_TRY(d_a.alloc(n * 8));
-  H2D(d_f, fac, n * 8, c);
-  H2D(d_i, idx, n * 8, c);
-  DT_TRY(dt_launch_river_acc_i64(c->stream, d_f.as<int64_t>(), d_i.as<int64_t>(), N, d_a.as<int64_t>()));
+  const int64_t *d_f = hc.in(fac, N);
+  const int64_t *d_i = hc.in(idx, N);
+  int64_t *d_a = hc.out(out, N);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launch_river_acc_i64(hc.c->stream, d_f, d_i, N, d_a));
   DT_HIP(hipGetLastError());
-  D2H(out, d_a, n * 8, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 
 static int host_gfi(const float *hand, const int64_t *fac, const int64_t *idx, int64_t N, double n_gfi,
                     double b, double size, float *out, int own_cell) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
   if (N == 0) return DT_OK;
   DT_REQUIRE(hand && fac && out, "NULL raster");
-  size_t n = (size_t)N;
-  DevBuf d_h, d_f, d_i, d_a, d_o;
-  DT_TRY(d_h.alloc(n * 4));
-  DT_TRY(d_f.alloc(n * 8));
-  DT_TRY(d_o.alloc(n * 4));
-  H2D(d_h, hand, n * 4, c);
-  H2D(d_f, fac, n * 8, c);
-  const int64_t *area = d_f.as<int64_t>();
-  if (idx) {
-    DT_TRY(d_i.alloc(n * 8));
-    DT_TRY(d_a.alloc(n * 8));
-    H2D(d_i, idx, n * 8, c);
-    DT_TRY(dt_launch_river_acc_i64(c->stream, d_f.as<int64_t>(), d_i.as<int64_t>(), N, d_a.as<int64_t>()));
-    area = d_a.as<int64_t>();
-  }
-  DT_TRY(dt_launch_gfi_i64(c->stream, d_h.as<float>(), area, N, n_gfi, b, size, d_o.as<float>(), own_cell));
+  const float *d_h = hc.in(hand, N);
+  const int64_t *d_f = hc.in(fac, N);
+  float *d_o = hc.out(out, N);
+  const int64_t *d_i = hc.in(idx, N);
+  int64_t *d_a = idx ? hc.scratch<int64_t>(N) : nullptr;
+  DT_TRY(hc.rc);
+  if (idx) DT_TRY(dt_launch_river_acc_i64(hc.c->stream, d_f, d_i, N, d_a));
+  DT_TRY(dt_launch_gfi_i64(hc.c->stream, d_h, idx ? d_a : d_f, N, n_gfi, b, size, d_o, own_cell));
   DT_HIP(hipGetLastError());
-  D2H(out, d_o, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 extern "C" int dt_gfi(const float *hand, const int64_t *fac, const int64_t *idx, int64_t N, double n_gfi,
                       double b, double size, float *gfi) {
@@ -2026,308 +1981,230 @@ extern "C" int dt_gfi_area(const float *hand, const int64_t *area, int64_t N, do
   return host_gfi(hand, area, nullptr, N, n_gfi, b, size, out, zero_guard ? 1 : 0);
 }
 
-extern "C" int dt_hand_f32(const float *dem, const int64_t *idx, int64_t N, float *hand) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+// HAND on the host tier, float32 or float64 heights
+template <typename T>
+static int host_hand(const T *dem, const int64_t *idx, int64_t N, T *hand,
+                     int (*launch)(hipStream_t, const T *, const int64_t *, int64_t, T *)) {
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
   if (N == 0) return DT_OK;
   DT_REQUIRE(dem && idx && hand, "NULL raster");
-  size_t n = (size_t)N;
-  DevBuf d_d, d_i, d_h;
-  DT_TRY(d_d.alloc(n * 4));
-  DT_TRY(d_i.alloc(n * 8));
-  DT_TRY(d_h.alloc(n * 4));
-  H2D(d_d, dem, n * 4, c);
-  H2D(d_i, idx, n * 8, c);
-  DT_TRY(dt_launch_hand_i64(c->stream, d_d.as<float>(), d_i.as<int64_t>(), N, d_h.as<float>()));
+  const T *d_d = hc.in(dem, N);
+  const int64_t *d_i = hc.in(idx, N);
+  T *d_h = hc.out(hand, N);
+  DT_TRY(hc.rc);
+  DT_TRY(launch(hc.c->stream, d_d, d_i, N, d_h));
   DT_HIP(hipGetLastError());
-  D2H(hand, d_h, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
+}
+extern "C" int dt_hand_f32(const float *dem, const int64_t *idx, int64_t N, float *hand) {
+  return host_hand(dem, idx, N, hand, dt_launch_hand_i64);
 }
 
 // ---- heights in float64 (dt_wide.hip): see include/descriptools_hip.h --------------------------------------------
 extern "C" int dt_slope_f64(const double *dem, int64_t H, int64_t W, double px, float *slope) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
   const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(dem && slope, "NULL raster");
-  DevBuf d_d, d_s;
-  DT_TRY(d_d.alloc(n * 8));
-  DT_TRY(d_s.alloc(n * 4));
-  H2D(d_d, dem, n * 8, c);
-  DT_TRY(dt_launch_slope_f64(c->stream, d_d.as<double>(), H, W, px, d_s.as<float>()));
+  const double *d_d = hc.in(dem, n);
+  float *d_s = hc.out(slope, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launch_slope_f64(hc.c->stream, d_d, H, W, px, d_s));
   DT_HIP(hipGetLastError());
-  D2H(slope, d_s, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 extern "C" int dt_d8_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *slope) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
   const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(dem && fdr, "NULL raster");
-  DevBuf d_d, d_f, d_s;
-  DT_TRY(d_d.alloc(n * 8));
-  DT_TRY(d_f.alloc(n));
-  if (slope) DT_TRY(d_s.alloc(n * 4));
-  H2D(d_d, dem, n * 8, c);
-  DT_TRY(dt_launch_d8_f64(c->stream, d_d.as<double>(), H, W, px, d_f.as<uint8_t>(), slope ? d_s.as<float>() : nullptr,
-                          nullptr));
+  const double *d_d = hc.in(dem, n);
+  uint8_t *d_f = hc.out(fdr, n);
+  float *d_s = hc.out(slope, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launch_d8_f64(hc.c->stream, d_d, H, W, px, d_f, d_s, nullptr));
   DT_HIP(hipGetLastError());
-  D2H(fdr, d_f, n, c);
-  if (slope) D2H(slope, d_s, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 extern "C" int dt_hand_f64(const double *dem, const int64_t *idx, int64_t N, double *hand) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
-  DT_REQUIRE(N >= 0, "negative size");
-  if (N == 0) return DT_OK;
-  DT_REQUIRE(dem && idx && hand, "NULL raster");
-  const size_t n = (size_t)N;
-  DevBuf d_d, d_i, d_h;
-  DT_TRY(d_d.alloc(n * 8));
-  DT_TRY(d_i.alloc(n * 8));
-  DT_TRY(d_h.alloc(n * 8));
-  H2D(d_d, dem, n * 8, c);
-  H2D(d_i, idx, n * 8, c);
-  DT_TRY(dt_launch_hand_f64(c->stream, d_d.as<double>(), d_i.as<int64_t>(), N, d_h.as<double>()));
-  DT_HIP(hipGetLastError());
-  D2H(hand, d_h, n * 8, c);
-  return dt_ctx_sync(c);
+  return host_hand(dem, idx, N, hand, dt_launch_hand_f64);
 }
 extern "C" int dt_downslope_f64(const double *dem, const uint8_t *fdr, int64_t H, int64_t W, double px, double dz,
                                 int raw, float *out) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
   const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(dem && fdr && out, "NULL raster");
-  DevBuf d_d, d_f, d_o;
-  DT_TRY(d_d.alloc(n * 8));
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_o.alloc(n * 4));
-  H2D(d_d, dem, n * 8, c);
-  H2D(d_f, fdr, n, c);
-  DT_TRY(dt_launch_downslope_f64(c->stream, d_d.as<double>(), d_f.as<uint8_t>(), H, W, px, dz, raw, d_o.as<float>()));
+  const double *d_d = hc.in(dem, n);
+  const uint8_t *d_f = hc.in(fdr, n);
+  float *d_o = hc.out(out, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launch_downslope_f64(hc.c->stream, d_d, d_f, H, W, px, dz, raw, d_o));
   DT_HIP(hipGetLastError());
-  D2H(out, d_o, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 extern "C" int dt_gfi_f64h(const double *hand, const int64_t *fac, const int64_t *idx, int64_t N, double n_gfi,
                            double b, double size, int own_area, float *out) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
   if (N == 0) return DT_OK;
   DT_REQUIRE(hand && fac && out && (own_area || idx), "NULL raster");
-  const size_t n = (size_t)N;
-  DevBuf d_h, d_f, d_i, d_o;
-  DT_TRY(d_h.alloc(n * 8));
-  DT_TRY(d_f.alloc(n * 8));
-  DT_TRY(d_o.alloc(n * 4));
-  H2D(d_h, hand, n * 8, c);
-  H2D(d_f, fac, n * 8, c);
-  if (!own_area) {
-    DT_TRY(d_i.alloc(n * 8));
-    H2D(d_i, idx, n * 8, c);
-  }
-  DT_TRY(dt_launch_gfi_f64h(c->stream, d_h.as<double>(), d_f.as<int64_t>(), own_area ? nullptr : d_i.as<int64_t>(), N,
-                            n_gfi, b, size, own_area, d_o.as<float>()));
+  const double *d_h = hc.in(hand, N);
+  const int64_t *d_f = hc.in(fac, N);
+  float *d_o = hc.out(out, N);
+  const int64_t *d_i = own_area ? nullptr : hc.in(idx, N);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launch_gfi_f64h(hc.c->stream, d_h, d_f, d_i, N, n_gfi, b, size, own_area, d_o));
   DT_HIP(hipGetLastError());
-  D2H(out, d_o, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 
 extern "C" int dt_downslope(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px, double dz,
                             int raw, float *out) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_TRY(dt_check_hw(H, W));
-  size_t n = (size_t)H * W;
+  const size_t n = (size_t)H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(dem && fdr && out, "NULL raster");
-  DevBuf d_dem, d_f, d_o, d_w;
-  DT_TRY(d_dem.alloc(n * 4));
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_o.alloc(n * 4));
-  H2D(d_dem, dem, n * 4, c);
-  H2D(d_f, fdr, n, c);
+  const float *d_dem = hc.in(dem, n);
+  const uint8_t *d_f = hc.in(fdr, n);
+  float *d_o = hc.out(out, n);
+  DT_TRY(hc.rc);
   // Long walks (real, conditioned rasters walk thousands of moves through flats and along valley floors) are queued;
   // this call is synchronous anyway, so it looks at the queue and allocates the skip tables only for a raster that
   // has enough of them.  The plain kernel when the device has no room for the queue.
   const size_t qb = dt_flow_impl() == 1 ? 0 : (size_t)dt_downslope_queue_workspace(H, W);
-  if (qb && d_w.alloc(qb) == DT_OK) {
-    DT_TRY(dt_dev_downslope_queue(c, d_dem.as<float>(), d_f.as<uint8_t>(), H, W, px, dz, raw, d_o.as<float>(), d_w.p,
-                                  (int64_t)qb));
+  void *d_w = qb ? hc.workspace(qb) : nullptr;
+  if (d_w) {
+    DT_TRY(dt_dev_downslope_queue(hc.c, d_dem, d_f, H, W, px, dz, raw, d_o, d_w, (int64_t)qb));
     int64_t queued = 0;
-    DT_TRY(dt_dev_downslope_queued(c, d_w.p, &queued));
+    DT_TRY(dt_dev_downslope_queued(hc.c, d_w, &queued));
     if (queued > 0) {
-      DevBuf d_t;
       const size_t tb = (size_t)dt_downslope_tables_workspace(H, W);
-      const bool tables = queued >= dt_downslope_tables_threshold(H, W) && d_t.alloc(tb) == DT_OK;
-      DT_TRY(dt_dev_downslope_finish(c, d_dem.as<float>(), d_f.as<uint8_t>(), H, W, px, dz, raw, d_o.as<float>(), d_w.p,
-                                     (int64_t)qb, tables ? d_t.p : nullptr, tables ? (int64_t)tb : 0));
-      D2H(out, d_o, n * 4, c);
-      return dt_ctx_sync(c);  // (d_t lives until here)
+      void *d_t = queued >= dt_downslope_tables_threshold(H, W) ? hc.workspace(tb) : nullptr;
+      DT_TRY(dt_dev_downslope_finish(hc.c, d_dem, d_f, H, W, px, dz, raw, d_o, d_w, (int64_t)qb, d_t,
+                                     d_t ? (int64_t)tb : 0));
     }
   } else {
-    DT_TRY(dt_dev_downslope(c, d_dem.as<float>(), d_f.as<uint8_t>(), H, W, px, dz, raw, d_o.as<float>()));
+    DT_TRY(dt_dev_downslope(hc.c, d_dem, d_f, H, W, px, dz, raw, d_o));
   }
-  D2H(out, d_o, n * 4, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 
 extern "C" int dt_confusion_multi(const double *desc, const int8_t *flood, int64_t N, double nodata_value,
                                   const double *th, int nth, int under, int64_t *counts4) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0 && th && counts4 && nth >= 1, "bad arguments");
-  size_t n = (size_t)N;
-  DevBuf d_d, d_f, d_c;
-  DT_TRY(d_d.alloc(n * 8));
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_c.alloc(sizeof(int64_t) * 4 * 24));
-  if (n) {
-    H2D(d_d, desc, n * 8, c);
-    H2D(d_f, flood, n, c);
-  }
+  const double *d_d = hc.in(desc, N);
+  const int8_t *d_f = hc.in(flood, N);
+  int64_t *d_c = hc.scratch<int64_t>(4 * 24);
+  DT_TRY(hc.rc);
   // more than 24 thresholds: several passes over the resident rasters
   for (int t0 = 0; t0 < nth; t0 += 24) {
     int k = nth - t0 < 24 ? nth - t0 : 24;
-    DT_TRY(dt_dev_confusion_multi(c, d_d.as<double>(), d_f.as<int8_t>(), N, nodata_value, th + t0, k, under,
-                                  d_c.as<int64_t>()));
-    DT_HIP(hipMemcpyAsync(counts4 + (size_t)t0 * 4, d_c.p, sizeof(int64_t) * 4 * k, hipMemcpyDeviceToHost,
-                          c->stream));
-    DT_HIP(hipStreamSynchronize(c->stream));
+    DT_TRY(dt_dev_confusion_multi(hc.c, d_d, d_f, N, nodata_value, th + t0, k, under, d_c));
+    DT_TRY(hc.download(counts4 + (size_t)t0 * 4, d_c, (size_t)k * 4));
   }
-  return DT_OK;
+  return hc.finish();
 }
 
 // ---- evaluation.minMaxScale / binary_map / avaliacao, host tier --------------------------------------
 extern "C" int dt_minmax_scale(const void *x, int is_f32, int64_t N, double mn, double mx, double nodata, void *out) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
   if (N == 0) return DT_OK;
   DT_REQUIRE(x && out, "NULL raster");
-  const size_t es = is_f32 ? 4 : 8, n = (size_t)N;
-  DevBuf d_x, d_o;
-  DT_TRY(d_x.alloc(n * es));
-  DT_TRY(d_o.alloc(n * es));
-  H2D(d_x, x, n * es, c);
-  if (is_f32) DT_TRY(dt_launch_minmax_scale_f32f32(c->stream, d_x.as<float>(), N, (float)mn, (float)mx, (float)nodata,
-                                                   d_o.as<float>()));
-  else DT_TRY(dt_launch_minmax_scale_f64(c->stream, d_x.as<double>(), N, mn, mx, nodata, d_o.as<double>()));
+  if (is_f32) {
+    const float *d_x = hc.in((const float *)x, N);
+    float *d_o = hc.out((float *)out, N);
+    DT_TRY(hc.rc);
+    DT_TRY(dt_launch_minmax_scale_f32f32(hc.c->stream, d_x, N, (float)mn, (float)mx, (float)nodata, d_o));
+  } else {
+    const double *d_x = hc.in((const double *)x, N);
+    double *d_o = hc.out((double *)out, N);
+    DT_TRY(hc.rc);
+    DT_TRY(dt_launch_minmax_scale_f64(hc.c->stream, d_x, N, mn, mx, nodata, d_o));
+  }
   DT_HIP(hipGetLastError());
-  D2H(out, d_o, n * es, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 
 extern "C" int dt_binary_map(const void *desc, int is_f32, int64_t N, double nodata_value, double threshold, int under,
                              uint8_t *binary) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
   if (N == 0) return DT_OK;
   DT_REQUIRE(desc && binary, "NULL raster");
-  const size_t es = is_f32 ? 4 : 8, n = (size_t)N;
-  DevBuf d_d, d_f, d_b, d_c;
-  DT_TRY(d_d.alloc(n * es));
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_b.alloc(n));
-  DT_TRY(d_c.alloc(4 * sizeof(int64_t)));
-  H2D(d_d, desc, n * es, c);
-  DT_HIP(hipMemsetAsync(d_f.p, 0, n, c->stream));
-  if (is_f32) DT_TRY(dt_launch_classify_f32(c->stream, d_d.as<float>(), nullptr, d_f.as<int8_t>(), N, (float)nodata_value,
-                                            (float)threshold, under, 0, d_b.as<uint8_t>(), nullptr,
-                                            d_c.as<unsigned long long>()));
-  else DT_TRY(dt_launch_classify_f64(c->stream, d_d.as<double>(), nullptr, d_f.as<int8_t>(), N, nodata_value, threshold,
-                                     under, 0, d_b.as<uint8_t>(), nullptr, d_c.as<unsigned long long>()));
+  const float *d_d32 = is_f32 ? hc.in((const float *)desc, N) : nullptr;
+  const double *d_d64 = is_f32 ? nullptr : hc.in((const double *)desc, N);
+  int8_t *d_f = hc.scratch<int8_t>(N);
+  uint8_t *d_b = hc.out(binary, N);
+  unsigned long long *d_c = hc.scratch<unsigned long long>(4);
+  DT_TRY(hc.rc);
+  DT_HIP(hipMemsetAsync(d_f, 0, N, hc.c->stream));
+  if (is_f32) DT_TRY(dt_launch_classify_f32(hc.c->stream, d_d32, nullptr, d_f, N, (float)nodata_value,
+                                            (float)threshold, under, 0, d_b, nullptr, d_c));
+  else DT_TRY(dt_launch_classify_f64(hc.c->stream, d_d64, nullptr, d_f, N, nodata_value, threshold, under, 0, d_b,
+                                     nullptr, d_c));
   DT_HIP(hipGetLastError());
-  D2H(binary, d_b, n, c);
-  return dt_ctx_sync(c);
+  return hc.finish();
 }
 
 extern "C" int dt_avaliacao(const int32_t *binary, int8_t *flood, int64_t N, int32_t *klass, int64_t *counts4) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
+  HostCall hc;
+  DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0 && counts4, "bad arguments");
-  const size_t n = (size_t)N;
-  DevBuf d_b, d_f, d_k, d_c;
-  DT_TRY(d_b.alloc(n * 4));
-  DT_TRY(d_f.alloc(n));
-  DT_TRY(d_k.alloc(n * 4));
-  DT_TRY(d_c.alloc(4 * sizeof(int64_t)));
-  if (n) {
-    DT_REQUIRE(binary && flood, "NULL raster");
-    H2D(d_b, binary, n * 4, c);
-    H2D(d_f, flood, n, c);
-  }
-  DT_TRY(dt_launch_classify_f64(c->stream, nullptr, d_b.as<int32_t>(), d_f.as<int8_t>(), N, 0.0, 0.0, 0, 1, nullptr,
-                                klass ? d_k.as<int32_t>() : nullptr, d_c.as<unsigned long long>()));
+  DT_REQUIRE((binary && flood) || N == 0, "NULL raster");
+  const int32_t *d_b = hc.in(binary, N);
+  int8_t *d_f = hc.in(flood, N);
+  int32_t *d_k = hc.scratch<int32_t>(N);
+  int64_t *d_c = hc.out(counts4, 4);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launch_classify_f64(hc.c->stream, nullptr, d_b, d_f, N, 0.0, 0.0, 0, 1, nullptr, klass ? d_k : nullptr,
+                                (unsigned long long *)d_c));
   DT_HIP(hipGetLastError());
-  if (n) {
-    D2H(flood, d_f, n, c);  // the benchmark map comes back remapped (evaluation.py:149-150 mutates it)
-    if (klass) D2H(klass, d_k, n * 4, c);
-  }
-  D2H(counts4, d_c, 4 * sizeof(int64_t), c);
-  return dt_ctx_sync(c);
+  DT_TRY(hc.download(flood, d_f, N));  // the benchmark map comes back remapped (evaluation.py:149-150 mutates it)
+  if (klass) DT_TRY(hc.download(klass, d_k, N));
+  return hc.finish();
 }
 
 // conditioned D8, host tier: dem in, D8 codes (flats resolved on the filled surface) and optionally the filled
-// surface out
+// surface out; the float64 twin compares the heights in float64
+template <typename T>
+static int host_d8_conditioned(const T *dem, int64_t H, int64_t W, double px, uint8_t *fdr, T *filled, int32_t *info3,
+                               int (*condition)(dt_ctx *, const T *, int64_t, int64_t, double, T *, uint8_t *,
+                                                int32_t *)) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem && fdr, "NULL raster");
+  const T *d_dem = hc.in(dem, n);
+  uint8_t *d_f = hc.out(fdr, n);
+  T *d_w = filled ? hc.out(filled, n) : hc.scratch<T>(n);
+  DT_TRY(hc.rc);
+  DT_TRY(condition(hc.c, d_dem, H, W, px, d_w, d_f, info3));
+  return hc.finish();
+}
 extern "C" int dt_d8_conditioned_f32(const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *filled,
                                      int32_t *info3) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
-  DT_TRY(dt_check_hw(H, W));
-  size_t n = (size_t)H * W;
-  if (n == 0) return DT_OK;
-  DT_REQUIRE(dem && fdr, "NULL raster");
-  DevBuf d_dem, d_w, d_f;
-  DT_TRY(d_dem.alloc(n * 4));
-  DT_TRY(d_w.alloc(n * 4));
-  DT_TRY(d_f.alloc(n));
-  H2D(d_dem, dem, n * 4, c);
-  DT_TRY(dt_dev_condition_d8(c, d_dem.as<float>(), H, W, px, d_w.as<float>(), d_f.as<uint8_t>(), info3));
-  D2H(fdr, d_f, n, c);
-  if (filled) D2H(filled, d_w, n * 4, c);
-  return dt_ctx_sync(c);
+  return host_d8_conditioned(dem, H, W, px, fdr, filled, info3, dt_dev_condition_d8);
 }
-// ... on float64 heights: dt_d8_conditioned_f32's definition with the heights compared in float64
 extern "C" int dt_d8_conditioned_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, double *filled,
                                      int32_t *info3) {
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  dt_ctx *c;
-  DT_TRY(host_ctx(&c));
-  DT_TRY(dt_check_hw(H, W));
-  size_t n = (size_t)H * W;
-  if (n == 0) return DT_OK;
-  DT_REQUIRE(dem && fdr, "NULL raster");
-  DevBuf d_dem, d_w, d_f;
-  DT_TRY(d_dem.alloc(n * 8));
-  DT_TRY(d_w.alloc(n * 8));
-  DT_TRY(d_f.alloc(n));
-  H2D(d_dem, dem, n * 8, c);
-  DT_TRY(dt_dev_condition_d8_f64(c, d_dem.as<double>(), H, W, px, d_w.as<double>(), d_f.as<uint8_t>(), info3));
-  D2H(fdr, d_f, n, c);
-  if (filled) D2H(filled, d_w, n * 8, c);
-  return dt_ctx_sync(c);
+  return host_d8_conditioned(dem, H, W, px, fdr, filled, info3, dt_dev_condition_d8_f64);
 }

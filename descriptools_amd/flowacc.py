@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, ptr
+from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, nodata_mask, ptr, raster_2d
 
 # every partial sum of quantised weights stays <= 2^52: the countdown's sum field holds it and float64 converts it
 # without rounding
@@ -18,12 +18,10 @@ _FRAC_BITS_MAX = 2200
 
 
 def accumulate(fdr, dem=None):
-    fdr = np.ascontiguousarray(fdr, np.uint8)
+    f = raster_2d(fdr)
+    d = nodata_mask(dem, f.shape)  # the DEM is only a nodata mask here
+    fdr = np.ascontiguousarray(f, np.uint8)
     H, W = fdr.shape
-    d = None
-    if dem is not None:
-        # the DEM is only a nodata mask here (dem <= -100 -> -100): taken in the raster's own dtype, whatever it is
-        d = np.where(np.asarray(dem) <= -100, np.float32(-100), np.float32(0)).astype(np.float32)
     acc = np.empty((H, W), np.int64)
     check(_lib.lib().dt_flowacc_u8(ptr(fdr, c_u8p), ptr(d, c_f32p), H, W, ptr(acc, c_i64p)))
     return acc
@@ -89,17 +87,10 @@ def accumulate_weighted(fdr, weights, dem=None, frac_bits=None):
     cycle.  Nodata cells still pass their weight and their inflow downstream, as they pass their count in
     accumulate; give them weight 0 to leave them out.  Weights must be finite and >= 0, of any real or integer dtype
     (integers <= 2^53).  Bad arguments raise ValueError before any library call."""
-    f = np.asarray(fdr)
-    if f.ndim != 2:
-        raise ValueError("fdr must be a 2-D raster, not of shape %s" % (f.shape,))
+    f = raster_2d(fdr)
     H, W = f.shape
     w = _weights_f64(weights, f.shape)
-    d = None
-    if dem is not None:
-        dm = np.asarray(dem)
-        if dm.shape != f.shape:
-            raise ValueError("dem has shape %s, the direction raster %s" % (dm.shape, f.shape))
-        d = np.where(dm <= -100, np.float32(-100), np.float32(0)).astype(np.float32)
+    d = nodata_mask(dem, f.shape)
     n = H * W
     wmax = float(w.max()) if n else 0.0
     if frac_bits is None:

@@ -26,16 +26,14 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import c_i8p, c_i64p, c_u8p, check, ptr
+from ._lib import c_i8p, c_i64p, c_u8p, check, ptr, raster_2d
 
 StreamNetwork = namedtuple("StreamNetwork", ["strahler", "shreve", "link"])
 
 
 def _args(fdr, river):
     """(fdr as C-contiguous uint8, river as C-contiguous int8 0/1); ValueError before any library call"""
-    f = np.asarray(fdr)
-    if f.ndim != 2:
-        raise ValueError("fdr must be a 2-D raster, not of shape %s" % (f.shape,))
+    f = raster_2d(fdr)
     r = np.asarray(river)
     if r.shape != f.shape:
         raise ValueError("river has shape %s, the direction raster %s" % (r.shape, f.shape))

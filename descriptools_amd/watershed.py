@@ -26,7 +26,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, ptr
+from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, nodata_mask, ptr, raster_2d
 
 Drainage = namedtuple("Drainage", ["target", "length"])
 
@@ -36,9 +36,7 @@ _MAX_CELLS = 2 ** 31
 def _args(fdr, px, dem=None, pour_points=None):
     """(fdr uint8, px float, dem nodata mask float32 or None, pour labels int64 or None), all C-contiguous;
     ValueError before any library call"""
-    f = np.asarray(fdr)
-    if f.ndim != 2:
-        raise ValueError("fdr must be a 2-D raster, not of shape %s" % (f.shape,))
+    f = raster_2d(fdr)
     if f.size >= _MAX_CELLS:
         raise ValueError("the raster has %d cells; it must have fewer than 2^31" % f.size)
     if isinstance(px, (bool, np.bool_)):
@@ -49,13 +47,7 @@ def _args(fdr, px, dem=None, pour_points=None):
         raise ValueError("px must be a finite number > 0, not %r" % (px,)) from None
     if not (math.isfinite(p) and p > 0):
         raise ValueError("px must be a finite number > 0, not %r" % (px,))
-    d = None
-    if dem is not None:
-        dm = np.asarray(dem)
-        if dm.shape != f.shape:
-            raise ValueError("dem has shape %s, the direction raster %s" % (dm.shape, f.shape))
-        # the DEM is only a nodata mask here (dem <= -100), taken in the raster's own dtype, as accumulate takes it
-        d = np.where(dm <= -100, np.float32(-100), np.float32(0)).astype(np.float32)
+    d = nodata_mask(dem, f.shape)  # the DEM is only a nodata mask here, as accumulate takes it
     pp = None
     if pour_points is not None:
         a = np.asarray(pour_points)

@@ -1,6 +1,6 @@
-"""CPU (not gpu): flowacc.accumulate_weighted refuses bad arguments with ValueError before any library call,
-flowacc.weight_frac_bits follows its documented rule, and the weighted entry points are declared, exported and
-bound."""
+"""CPU (not gpu): flowacc.accumulate_weighted and flowacc.accumulate refuse bad arguments with ValueError before any
+library call, flowacc.weight_frac_bits follows its documented rule, and the weighted entry points are declared,
+exported and bound."""
 import ctypes
 import os
 import re
@@ -71,6 +71,18 @@ def test_bad_shapes_and_frac_bits_refused_before_the_library(no_library):
     # overflow of the scaled maximum itself
     with pytest.raises(ValueError, match="too fine"):
         flowacc.accumulate_weighted(FDR, np.full((5, 7), 1e300), frac_bits=2000)
+
+
+def test_accumulate_refuses_bad_shapes_before_the_library(no_library):
+    # a smaller dem would have the library read H * W float32 cells past the end of its mask
+    with pytest.raises(ValueError, match=re.escape("dem has shape (4, 7), the direction raster (5, 7)")):
+        flowacc.accumulate(FDR, np.zeros((4, 7), np.float32))
+    with pytest.raises(ValueError, match="dem has shape"):
+        flowacc.accumulate(FDR, np.zeros(35, np.float32))
+    with pytest.raises(ValueError, match=re.escape("fdr must be a 2-D raster, not of shape (2, 5, 7)")):
+        flowacc.accumulate(np.ones((2, 5, 7), np.uint8))
+    with pytest.raises(ValueError, match="2-D"):
+        flowacc.accumulate(np.ones(7, np.uint8))
 
 
 def test_frac_bits_at_the_bound_passes_validation(monkeypatch):

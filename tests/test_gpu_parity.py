@@ -155,6 +155,40 @@ def test_golden_eval(dt):
         assert (c2, f2) == (c, f) and np.array_equal(cm2, cm) and np.array_equal(fresh, g["e%d_flood_after" % k])
 
 
+def test_lnhlh_and_confusion_multi_host_entries(dt):
+    """dt_lnhlh and dt_confusion_multi, which no package function calls, against the oracle"""
+    from descriptools_amd import _lib
+    L = _lib.lib()
+    rng = np.random.default_rng(7)
+    H, W = 61, 77
+    hand = (rng.random((H, W)) * 40).astype(np.float32)
+    hand[rng.random((H, W)) < 0.1] = -100
+    fac = rng.integers(0, 500, (H, W)).astype(np.int64)
+    fac[rng.random((H, W)) < 0.2] = 0
+    out = np.full((H, W), 7, np.float32)
+    _lib.check(L.dt_lnhlh(_lib.ptr(hand, _lib.c_f32p), _lib.ptr(fac, _lib.c_i64p), hand.size, 0.4, 0.1, 12.5,
+                          _lib.ptr(out, _lib.c_f32p)))
+    assert_float_close(out, oracle.lnhlh(hand, fac, 0.4, 0.1, 12.5), rtol=1e-5, atol=1e-6, what="dt_lnhlh")
+    # the value at [0] counts as nodata in the oracle: pass it as the nodata value; 30 thresholds take two passes
+    desc = np.floor(rng.random(40000) * 64) / 64
+    desc[rng.random(desc.size) < 0.05] = np.nan
+    desc[0] = 0.5
+    flood = rng.choice(np.array([-100, 0, 1, 2, -1], np.int8), desc.size, p=[0.2, 0.4, 0.3, 0.05, 0.05])
+    th = np.linspace(0.0, 1.0, 30)
+    th[7] = desc[0]
+    for under in (1, 0):
+        counts = np.full((th.size, 4), -1, np.int64)
+        _lib.check(L.dt_confusion_multi(_lib.ptr(desc, _lib.c_f64p), _lib.ptr(flood, _lib.c_i8p), desc.size,
+                                        float(desc[0]), _lib.ptr(th, _lib.c_f64p), th.size, under,
+                                        _lib.ptr(counts, _lib.c_i64p)))
+        assert np.array_equal(counts, oracle.confusion_multi(desc, flood, th, under=bool(under))), under
+    desc0, flood0 = np.zeros(0, np.float64), np.zeros(0, np.int8)
+    counts = np.full((th.size, 4), -1, np.int64)
+    _lib.check(L.dt_confusion_multi(_lib.ptr(desc0, _lib.c_f64p), _lib.ptr(flood0, _lib.c_i8p), 0, 0.0,
+                                    _lib.ptr(th, _lib.c_f64p), th.size, 1, _lib.ptr(counts, _lib.c_i64p)))
+    assert not counts.any(), "N = 0: every count is 0"
+
+
 @pytest.mark.parametrize("seed,H,W,nod", [(1, 257, 300, 0), (2, 512, 512, 4), (3, 1000, 1536, 0),
                                            (4, 33, 1027, 3), (5, 1, 50, 0), (6, 70, 1, 0)])
 def test_oracle_synthetic_chain(dt, seed, H, W, nod):
