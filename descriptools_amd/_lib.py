@@ -151,6 +151,11 @@ _SIGS = {
     "dt_dev_flowacc_river_flowhand_local_m": (ci, [vp, vp, vp, vp, i64, i64, i64, vp, vp]),
     "dt_dev_slope_d8_m": (ci, [vp, vp, i64, i64, f64, vp, vp]),
     "dt_nodata_mask_bytes": (i64, [i64, i64]),
+    "dt_slope_from_d8_ok": (ci, [i64, i64]),
+    "dt_slope_marks_bytes": (i64, [i64, i64]),
+    "dt_dev_slope_d8_ms": (ci, [vp, vp, i64, i64, f64, vp, vp, vp, vp]),
+    "dt_dev_flowacc_river_flowhand_local_ms": (ci, [vp, vp, vp, vp, i64, i64, i64, vp, vp, f64, f64, vp, vp, vp, vp]),
+    "dt_dev_slope_twi_fix": (ci, [vp, vp, vp, i64, i64, f64, f64, vp, vp, vp, vp]),
     "dt_dev_flowacc_finish_flowhand_local_w": (ci, [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dt_dev_flowacc_finish_flowhand_local_w_a64": (ci, [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dt_dev_i32_to_i64": (ci, [vp, vp, i64, vp]),

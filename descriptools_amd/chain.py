@@ -31,6 +31,15 @@ WRITE_GROUPS = (("slope", "ti", "mti"), ("fdist", "idx", "hand", "gfi", "lnhlh")
 # node doubling, 2 B/cell by the unfused definition fdr 1 + river 1).  HAND's last pass with the fused GFI + ln(hl/H)
 # epilogue reads dem 4 + fac 4 and writes fdist, idx, hand, gfi, lnhlh (20).  "d8" writes fdr only: slope comes out of
 # the fused slope+TI+MTI stencil (dem 4 + fac 4 read, slope 4 + TI 4 + MTI 4 written = the north_star's 20 B/cell).
+#
+# That is the step as the profiles/r4 set measured it, and the step of every path that still launches the stencil
+# (external_fdr, condition, want_slope_rad, rows that are not whole 64-cell tiles, the ranks of tiling.py); the tuple
+# stays as it is because tests/test_profiles.py and tools/design_table.py tie it to those profiles.  The plain float32
+# chain (Chain._from_d8) distributes the slope_twi bytes differently since round 6: "d8" runs k_d8_slope and writes the
+# slope on its way (fdr 1 + slope 4 + the marks), "flowacc_flowhand_local" runs k_fa3fh1_twi, which reads that slope (4)
+# and writes TI + MTI (8) beside the accumulation it has in registers, and "slope_twi" is only k_slope_twi_fix over
+# the marked cells (microseconds on terrain): dem 4 + fac 4 are no longer read a second time, and a per-op rate
+# computed from the 20 B/cell of "slope_twi" means nothing for that chain.
 OPS = (
     ("d8", 5, ["k_d8<false>", "k_d8_fix"]),
     ("downslope", 9, ["k_downslope_win<24>"]),
@@ -123,11 +132,15 @@ class Chain:
             self.buf[name] = alloc((H, W), dt) if alloc else self.ctx.empty((H, W), dt)
         # the D8 kernel's nodata mask (one byte per four cells): what the accumulation pass needs of the DEM; on
         # float64 heights the float32 nodata proxy the first kernel writes (dt_dev_slope_d8_f64)
-        self._nodata4 = self._proxy = None
+        self._nodata4 = self._proxy = self._marks = None
         if self.wide:
             self._proxy = self.ctx.empty((H, W), F32)
         elif not (self.external_fdr or self.condition):
             self._nodata4 = self.ctx.empty((int(_lib.lib().dt_nodata_mask_bytes(H, W)),), U8)
+            # slope out of the D8 kernel, TI / MTI out of the last accumulation tile pass (ops()): the cells to redo
+            # exactly are collected in marks of the chain's own, because three calls on two contexts share them
+            if not want_slope_rad and _lib.lib().dt_slope_from_d8_ok(H, W):
+                self._marks = self.ctx.empty((int(_lib.lib().dt_slope_marks_bytes(H, W)),), U8)
         assert tune_placement in (False, True, "search")
         self.placement = {"tuned": False, "why": "tune_placement=False"}
         if tune_placement:
@@ -254,6 +267,25 @@ class Chain:
         rad = p("slope_rad") if self.want_slope_rad else None
         m4 = self._nodata4.ptr if self._nodata4 is not None else None
         first = ("d8", c, lambda: L.dt_dev_slope_d8_m(c.h, dem_ptr, H, W, self.px, p("fdr"), m4))
+        flow = ((lambda: L.dt_dev_flowacc_river_flowhand_local_m(c.h, p("fdr"), dem_ptr, m4, H, W, self.river_threshold,
+                                                                 p("fac"), p("river"))) if m4 is not None else
+                (lambda: L.dt_dev_flowacc_river_flowhand_local(c.h, p("fdr"), dem_ptr, H, W, self.river_threshold,
+                                                               p("fac"), p("river"))))
+        twi = lambda: L.dt_dev_slope_twi(side.h, dem_ptr, p("fac"), H, W, self.px, self.n_top, p("slope"), rad, p("ti"),
+                                         p("mti"))
+        if self._from_d8(dem_ptr):
+            # The same five ops without a slope + TI + MTI pass over the raster: the D8 kernel writes the slope from the
+            # neighbourhood it holds (marking the cells whose float32 slope is not proven), flow accumulation's last
+            # tile pass writes TI / MTI from that slope and the accumulation in its registers (marking the cells its
+            # fast path rejects), and "slope_twi" is the exact recomputation of the marked cells alone -- bit for bit
+            # what dt_dev_slope_twi writes.
+            marks = self._marks.ptr
+            first = ("d8", c, lambda: L.dt_dev_slope_d8_ms(c.h, dem_ptr, H, W, self.px, p("fdr"), m4, p("slope"), marks))
+            flow = lambda: L.dt_dev_flowacc_river_flowhand_local_ms(
+                c.h, p("fdr"), dem_ptr, m4, H, W, self.river_threshold, p("fac"), p("river"), self.px, self.n_top,
+                p("slope"), p("ti"), p("mti"), marks)
+            twi = lambda: L.dt_dev_slope_twi_fix(side.h, dem_ptr, p("fac"), H, W, self.px, self.n_top, p("slope"),
+                                                 p("ti"), p("mti"), marks)
         if self.condition:
             first = ("condition_d8", c, lambda: L.dt_dev_condition_d8_async(c.h, dem_ptr, H, W, self.px, p("filled"),
                                                                              p("fdr"), self.condition_rounds))
@@ -263,18 +295,21 @@ class Chain:
              if self.long_walks is True else
              (lambda: self._queue_downslope(side, dem_ptr)) if self.long_walks == "auto" else
              (lambda: L.dt_dev_downslope(side.h, dem_ptr, p("fdr"), H, W, self.px, self.dz, 0, p("down")))),
-            ("flowacc_flowhand_local", c,
-             (lambda: L.dt_dev_flowacc_river_flowhand_local_m(c.h, p("fdr"), dem_ptr, m4, H, W, self.river_threshold,
-                                                              p("fac"), p("river"))) if m4 is not None else
-             (lambda: L.dt_dev_flowacc_river_flowhand_local(c.h, p("fdr"), dem_ptr, H, W, self.river_threshold,
-                                                            p("fac"), p("river")))),
-            ("slope_twi", side, lambda: L.dt_dev_slope_twi(side.h, dem_ptr, p("fac"), H, W, self.px, self.n_top,
-                                                           p("slope"), rad, p("ti"), p("mti"))),
+            ("flowacc_flowhand_local", c, flow),
+            ("slope_twi", side, twi),
             ("flowhand_gfi_finish", c, lambda: L.dt_dev_flowhand_gfi_finish_w(
                 c.h, C.byref(full), dem_ptr, p("fdr"), p("river"), p("fac"), self.px, self.n_gfi, self.b, None, None,
                 None, None, None, None, p("fdist"), p("idx"), None, p("hand"),
                 p("a_river") if want_a_river else None, p("gfi"), p("lnhlh"))),
         ]
+
+    def _from_d8(self, dem_ptr=None):
+        """does the step take slope from the D8 kernel and TI / MTI from the accumulation pass?  (the plain float32
+        chain without slope_rad, on rows of whole 64-cell tiles and 16-byte aligned rasters; same rasters either way)"""
+        if self._marks is None or self.want_slope_rad or not _lib.lib().dt_slope_from_d8_ok(self.H, self.W):
+            return False  # (asked again: a debug key can take the fused tile pass away after set-up)
+        ptrs = [self.p(k) for k in ("slope", "fac", "ti", "mti", "river", "fdr")] + ([dem_ptr] if dem_ptr else [])
+        return all((int(q.value if hasattr(q, "value") else q) & 15) == 0 for q in ptrs)
 
     def _ops_f64(self, dem_ptr, want_a_river, side):
         """ops() of a heights="float64" chain (OPS_F64): the DEM pointer is a float64 raster.  The flow-accumulation /
@@ -358,7 +393,7 @@ class Chain:
             if hasattr(b, "free"):
                 b.free()
         self.buf = {}
-        for name in ("_lift", "_lift_q", "_lift_tables", "_nodata4", "_proxy"):
+        for name in ("_lift", "_lift_q", "_lift_tables", "_nodata4", "_proxy", "_marks"):
             if getattr(self, name) is not None:
                 getattr(self, name).free()
                 setattr(self, name, None)

@@ -1145,10 +1145,13 @@ extern "C" int dt_dev_flowacc_finish_flowhand_local_w_a64(dt_ctx *c, const dt_wi
 // single raster: flow accumulation (all phases), river mask and HAND's phase 1; dt_dev_flowhand_finish_w /
 // dt_dev_flowhand_gfi_finish_w with the whole raster as the window follow
 static int dev_flowacc_river_flowhand_local(dt_ctx *c, const uint8_t *fdr, const float *dem, const uint8_t *nod4,
-                                           int64_t H, int64_t W, int64_t threshold, int32_t *acc32, int8_t *river) {
+                                           int64_t H, int64_t W, int64_t threshold, int32_t *acc32, int8_t *river,
+                                           const DtTwiEpilogue *twi = nullptr) {
   DT_CTX(c);
   DT_TRY(dt_check_hw(H, W));
   DT_REQUIRE((fdr && acc32 && river) || H * W == 0, "NULL raster");
+  DT_REQUIRE(!twi || H * W == 0 || dt_twi_epilogue_ok(dt_full_window(H, W), acc32, river, twi),
+             "this raster does not take the TI / MTI epilogue (dt_slope_from_d8_ok): use dt_dev_slope_twi");
   size_t need = dt_flowacc_tiled_scratch(H, W), need2 = dt_flowhand_tiled_scratch(H, W);
   DT_TRY(dt_scratch_reset(c, need + need2 + 512));
   void *scr = dt_scratch_take(c, need), *scr2 = dt_scratch_take(c, need2);
@@ -1156,7 +1159,7 @@ static int dev_flowacc_river_flowhand_local(dt_ctx *c, const uint8_t *fdr, const
   DtWin w = dt_full_window(H, W);
   DT_TRY(dt_launch_fa_local(c->stream, w, fdr, scr, need, acc32, 0));
   DT_TRY(dt_launch_fa_finish_fh_local(c->stream, w, fdr, dem, scr, scr2, need2, nullptr, threshold, acc32, 0, river,
-                                      c->status, nod4, dt_nodata4_ld(W)));
+                                      c->status, nod4, dt_nodata4_ld(W), twi));
   DT_HIP(hipGetLastError());
   c->scratch_owner = 2;
   c->owner_h = H;
@@ -1177,6 +1180,36 @@ extern "C" int dt_dev_flowacc_river_flowhand_local_m(dt_ctx *c, const uint8_t *f
   DT_REQUIRE((dem && nodata4) || H * W == 0, "dem and the nodata mask are both required");
   return dev_flowacc_river_flowhand_local(c, fdr, dem, nodata4, H, W, threshold, acc32, river);
 }
+// ... and with TI / MTI out of the last accumulation tile pass: `slope` is the raster dt_dev_slope_d8_ms wrote, `marks`
+// the workspace it was given (the cells whose TI / MTI fast path fails are added to it); dt_dev_slope_twi_fix follows.
+// Only for the shapes dt_slope_from_d8_ok accepts.
+extern "C" int dt_dev_flowacc_river_flowhand_local_ms(dt_ctx *c, const uint8_t *fdr, const float *dem,
+                                                      const uint8_t *nodata4, int64_t H, int64_t W, int64_t threshold,
+                                                      int32_t *acc32, int8_t *river, double px, double n_top,
+                                                      const float *slope, float *ti, float *mti, void *marks) {
+  DT_REQUIRE((dem && nodata4 && slope && ti && mti && marks) || H * W == 0, "NULL raster");
+  const DtTwiEpilogue twi{slope, ti, mti, px, n_top, marks};
+  return dev_flowacc_river_flowhand_local(c, fdr, dem, nodata4, H, W, threshold, acc32, river, &twi);
+}
+// the shapes on which the D8 kernel's slope and the accumulation pass's TI / MTI replace the slope + TI + MTI stencil
+// (rows of whole 64-cell tiles; the rasters and the marks 16-byte aligned), and the bytes of the marks
+extern "C" int dt_slope_from_d8_ok(int64_t H, int64_t W) {
+  return H > 0 && W > 0 && W % 64 == 0 && dt_debug_get(DT_DBG_NO_FUSED_FA_FH) == 0;
+}
+extern "C" int64_t dt_slope_marks_bytes(int64_t H, int64_t W) {
+  return (H < 0 || W < 0) ? -1 : (int64_t)dt_stencil_aux_bytes(H, W);
+}
+// the exact recomputation (k_slope_twi_fix) of slope, TI and MTI on the cells marked by dt_dev_slope_d8_ms and
+// dt_dev_flowacc_river_flowhand_local_ms: microseconds when few are
+extern "C" int dt_dev_slope_twi_fix(dt_ctx *c, const float *dem, const int32_t *acc32, int64_t H, int64_t W, double px,
+                                    double n_top, float *slope, float *ti, float *mti, const void *marks) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((dem && acc32 && slope && ti && mti && marks) || H * W == 0, "NULL raster");
+  DT_TRY(dt_launch_slope_twi_fix(c->stream, dt_full_window(H, W), dem, px, slope, acc32, n_top, ti, mti, (void *)marks));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
 extern "C" int64_t dt_nodata_mask_bytes(int64_t H, int64_t W) {
   return (H < 0 || W < 0) ? -1 : (int64_t)dt_nodata4_bytes(H, W);
 }
@@ -1190,6 +1223,19 @@ extern "C" int dt_dev_slope_d8_m(dt_ctx *c, const float *dem, int64_t H, int64_t
   DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(H, W)));
   DT_TRY(dt_launch_stencil(c->stream, dt_full_window(H, W), dem, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr,
                            nullptr, c->aux, nodata4, dt_nodata4_ld(W)));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+// ... and the slope raster (NULL: dt_dev_slope_d8_m), with the cells whose float32 slope is not proven in `marks`
+// (dt_slope_marks_bytes; dt_dev_flowacc_river_flowhand_local_ms and dt_dev_slope_twi_fix take them from there)
+extern "C" int dt_dev_slope_d8_ms(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr,
+                                  uint8_t *nodata4, float *slope, void *marks) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE((dem && fdr && nodata4 && (marks || !slope)) || H * W == 0, "NULL raster");
+  DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(H, W)));
+  DT_TRY(dt_launch_d8_slope(c->stream, dt_full_window(H, W), dem, px, fdr, slope, c->aux, nodata4, dt_nodata4_ld(W),
+                            marks));
   DT_HIP(hipGetLastError());
   return DT_OK;
 }

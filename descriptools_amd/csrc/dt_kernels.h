@@ -13,6 +13,11 @@ static inline int dt_nodata4_ld(int64_t W) { return (int)((((W + 3) / 4) + 7) & 
 static inline size_t dt_nodata4_bytes(int64_t H, int64_t W) { return (size_t)((H + 3) / 4) * (size_t)dt_nodata4_ld(W) * 2; }
 // workspace (tile marks + lane masks) of the fused slope + TI + MTI launch; see dt_stencil.hip
 size_t dt_stencil_aux_bytes(int64_t H, int64_t W);
+// the float32 chain's D8 + slope kernel and the fix-up of the cells it and the TI / MTI epilogue marked (dt_stencil.hip)
+int dt_launch_d8_slope(hipStream_t s, const DtWin &w, const float *dem, double px, uint8_t *fdr, float *slope,
+                       void *aux, uint8_t *nod4, int ldm, void *smarks);
+int dt_launch_slope_twi_fix(hipStream_t s, const DtWin &w, const float *dem, double px, float *slope,
+                            const int32_t *acc, double n_top, float *ti, float *mti, void *smarks);
 int dt_launch_flowacc(hipStream_t s, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
                       unsigned long long *state, int32_t *acc32);
 int dt_launch_river_mask(hipStream_t s, const int32_t *acc32, int64_t n, int64_t thr, int8_t *river);
@@ -104,11 +109,20 @@ size_t dt_flowacc_weighted_scratch(int64_t H, int64_t W);
 int dt_launch_flowacc_weighted(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, const double *wt,
                                int frac_bits, void *scratch, size_t scratch_bytes, double *acc, int *status);
 size_t dt_flowhand_tiled_scratch(int64_t H, int64_t W);
+// TI / MTI out of flow accumulation's last tile pass (the float32 chain): the slope raster the D8 kernel wrote
+// (dt_launch_d8_slope), the outputs, and the marks (dt_stencil_aux_bytes) that dt_launch_slope_twi_fix consumes
+struct DtTwiEpilogue {
+  const float *slope;
+  float *ti, *mti;
+  double px, n_top;
+  void *marks;
+};
 // nod4 (optional): the D8 kernel's nodata mask; when the fused kernel runs it replaces the read of `dem`
 int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, void *fa_scratch,
                                  void *fh_scratch, size_t fh_bytes, const unsigned long long *ext_perim,
                                  int64_t river_thr, void *acc, int acc64, int8_t *river, int *status,
-                                 const uint8_t *nod4 = nullptr, int ldm = 0);
+                                 const uint8_t *nod4 = nullptr, int ldm = 0, const DtTwiEpilogue *twi = nullptr);
+bool dt_twi_epilogue_ok(const DtWin &w, const void *acc, const int8_t *river, const DtTwiEpilogue *twi);
 int dt_launch_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const int8_t *river, void *scratch,
                        size_t scratch_bytes);
 int dt_launch_fh_summary(hipStream_t s, const DtWin &w, void *scratch, const float *dem, const void *acc, int acc64,

@@ -156,6 +156,36 @@ __device__ __forceinline__ float dt_pct_to_tan(float slope_pct) {
 #define DT_NODATA (-100.0f)
 #endif
 
+// TI / MTI (topoindexes.py:234-295) straight from q = tan(slope angle) = slope % / 100, without the arctangent:
+//   tan(atan q + 0.01) = (q + t) / (1 - q t), t = tan 0.01
+//   TI = ln A - ln(q + t) + ln(1 - q t),  MTI = n ln A - ...,  A = max(fac, 1) px^2
+// Three hardware log2 of mantissas in [0.5, 1) (absolute error <= 6e-8 each) and exact exponents, summed in
+// float64 in the log2 domain: ~2e-7 absolute whatever the magnitudes, accepted only when |TI|, |MTI| >=
+// DT_FAST_MIN (<= 1e-6 relative).  The reference goes through the float32 rounding of the angle
+// (Example/example.py:63), a perturbation of <= 4e-7 absolute for angles <= 1.19 (q <= 2.5); steeper cells, a
+// negative or non-finite q and fac < 0 are flagged.  Returns true when the cell must be redone exactly
+// (fac <= -100, the nodata of topoindexes.py:252, is handled by the caller).
+template <typename AccT>
+__device__ __forceinline__ bool sd_twi_fast(AccT fac, float q, double n, double lnpx2, double nlnpx2, float &ti,
+                                            float &mti) {
+  const float TAN001 = 0.010000333346667207f;
+  const float u = q + TAN001, v = fmaf(-q, TAN001, 1.0f);
+  // fac == 0 -> 1 (topoindexes.py:256): ln 1 = 1 + log2(0.5) = 0.  (An accumulation above 2^24 is rounded to float32
+  // here, 6e-8 relative: within the fast path's error budget for either width.)
+  const float ff = (float)(fac > 1 ? fac : (AccT)1);
+  const float lf = __log2f(__builtin_amdgcn_frexp_mantf(ff));
+  const float l1 = __log2f(__builtin_amdgcn_frexp_mantf(u));
+  const float l2 = __log2f(__builtin_amdgcn_frexp_mantf(v));
+  const int ef = __builtin_amdgcn_frexp_expf(ff);
+  const int e12 = __builtin_amdgcn_frexp_expf(u) - __builtin_amdgcn_frexp_expf(v);
+  const double a2 = (double)ef + (double)lf;            // log2 fac
+  const double s2 = (double)e12 + (double)(l1 - l2);    // log2 tan(angle + 0.01)
+  const double LN2 = 0.6931471805599453;
+  ti = (float)fma(a2 - s2, LN2, lnpx2);
+  mti = (float)fma(fma(n, a2, -s2), LN2, nlnpx2);
+  return !(fac >= 0 && q >= 0.0f && q <= 2.5f && fabsf(ti) >= (float)DT_FAST_MIN && fabsf(mti) >= (float)DT_FAST_MIN);
+}
+
 // ln(x) in float64 without branches, ~2e-13 absolute: dt_fast_log's table with a degree-4 series.  Finite
 // normal x > 0 go through the table; x == 0 gives -inf, x < 0 or NaN gives NaN, +inf gives +inf -- what
 // log / pow of the reference give (gfi.py:292-294: an area of 0 makes GFI -inf, a negative one NaN).

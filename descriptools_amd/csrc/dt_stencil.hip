@@ -389,36 +389,8 @@ __device__ __forceinline__ bool sd_slope_fast(float c, float nw, float n, float 
   return near_mid || odd;
 }
 
-// TI / MTI (topoindexes.py:234-295) straight from q = tan(slope angle) = slope % / 100, without the arctangent:
-//   tan(atan q + 0.01) = (q + t) / (1 - q t), t = tan 0.01
-//   TI = ln A - ln(q + t) + ln(1 - q t),  MTI = n ln A - ...,  A = max(fac, 1) px^2
-// Three hardware log2 of mantissas in [0.5, 1) (absolute error <= 6e-8 each) and exact exponents, summed in
-// float64 in the log2 domain: ~2e-7 absolute whatever the magnitudes, accepted only when |TI|, |MTI| >=
-// DT_FAST_MIN (<= 1e-6 relative).  The reference goes through the float32 rounding of the angle
-// (Example/example.py:63), a perturbation of <= 4e-7 absolute for angles <= 1.19 (q <= 2.5); steeper cells, a
-// negative or non-finite q and fac < 0 are flagged.  Returns true when the cell must be redone exactly
-// (fac <= -100, the nodata of topoindexes.py:252, is handled by the caller).
-template <typename AccT>
-__device__ __forceinline__ bool sd_twi_fast(AccT fac, float q, double n, double lnpx2, double nlnpx2, float &ti,
-                                            float &mti) {
-  const float TAN001 = 0.010000333346667207f;
-  const float u = q + TAN001, v = fmaf(-q, TAN001, 1.0f);
-  // fac == 0 -> 1 (topoindexes.py:256): ln 1 = 1 + log2(0.5) = 0.  (An accumulation above 2^24 is rounded to float32
-  // here, 6e-8 relative: within the fast path's error budget for either width.)
-  const float ff = (float)(fac > 1 ? fac : (AccT)1);
-  const float lf = __log2f(__builtin_amdgcn_frexp_mantf(ff));
-  const float l1 = __log2f(__builtin_amdgcn_frexp_mantf(u));
-  const float l2 = __log2f(__builtin_amdgcn_frexp_mantf(v));
-  const int ef = __builtin_amdgcn_frexp_expf(ff);
-  const int e12 = __builtin_amdgcn_frexp_expf(u) - __builtin_amdgcn_frexp_expf(v);
-  const double a2 = (double)ef + (double)lf;            // log2 fac
-  const double s2 = (double)e12 + (double)(l1 - l2);    // log2 tan(angle + 0.01)
-  const double LN2 = 0.6931471805599453;
-  ti = (float)fma(a2 - s2, LN2, lnpx2);
-  mti = (float)fma(fma(n, a2, -s2), LN2, nlnpx2);
-  return !(fac >= 0 && q >= 0.0f && q <= 2.5f && fabsf(ti) >= (float)DT_FAST_MIN && fabsf(mti) >= (float)DT_FAST_MIN);
-}
-
+// (sd_twi_fast, the float32 fast path of TI / MTI from q = slope % / 100, lives in dt_math.h: flow accumulation's last
+// tile pass evaluates it too, dt_tiles.hip k_fa3fh1_twi)
 typedef float sd_v4f __attribute__((ext_vector_type(4)));
 typedef int sd_v4i __attribute__((ext_vector_type(4)));
 typedef long long sd_v2l __attribute__((ext_vector_type(2)));
@@ -658,87 +630,12 @@ __device__ __forceinline__ bool sd_d8_fast(float c, float nw, float n, float ne,
 // dt_dev_flowacc_river_flowhand_local_m).  A patch is what one thread of this kernel owns: ONE store per thread (four
 // byte stores, a row each, cost this issue-bound kernel 12 %).  ldm = words per row of patches.  Only for a single
 // raster (window origin on the 4-cell grid).
-template <bool NT>
-__global__ __launch_bounds__(256, 8) void k_d8(const float *__restrict__ dem, DtWin w, uint8_t *__restrict__ fdr,
-                                              int tiles_x, int tiles_y, int vec_ok, uint8_t *__restrict__ tile_mark,
-                                              uint16_t *__restrict__ lane_mask, uint8_t *__restrict__ nod4, int ldm) {
-  __shared__ __attribute__((aligned(16))) float t[(SD_TY + 2) * SD_LDW];
-  const int tile = sd_tile_of_block(blockIdx.x, tiles_x * tiles_y);
-  const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-  const int x0 = txi * SD_TX, y0 = tyi * SD_TY;
-  const int H = w.H, W = w.W;
-  sd_stage(t, dem, w, x0, y0, vec_ok);
-  __syncthreads();
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int cx = tx * 4, ry = ty * 4;
-  const int gx = x0 + cx;
-  auto load_row = [&](int lr, float *dst) {
-    const float *row = &t[lr * SD_LDW];
-    float4 m = *reinterpret_cast<const float4 *>(row + 4 + cx);
-    float lh = row[3], rh = row[4 + SD_TX];
-    dst[0] = sd_from_prev_lane(lh, m.w);
-    dst[1] = m.x;
-    dst[2] = m.y;
-    dst[3] = m.z;
-    dst[4] = m.w;
-    dst[5] = sd_from_next_lane(rh, m.x);
-  };
-  const bool full = vec_ok && gx + 3 < W;
-  // block-uniform: does the tile touch the border of the GLOBAL raster?  (only there does the border rule apply;
-  // the kernel is limited by VALU issue and the rule is a sixth of a cell's instructions)
-  const bool on_border = w.gy0 + y0 == 0 || w.gx0 + x0 == 0 || w.gy0 + y0 + SD_TY >= w.Hg || w.gx0 + x0 + SD_TX >= w.Wg;
-  float a[6], bb[6], cc[6];
-  load_row(ry, a);
-  load_row(ry + 1, bb);
-  uint32_t mask = 0, nodmask = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int gy = y0 + ry + j;
-    load_row(ry + 2 + j, cc);
-    uint32_t codes = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const float c = bb[k + 1];
-      const bool nod = sd_centre(c) <= DT_NODATA;  // staged nodata or below the sentinel: code 0 (NaN, +inf: not)
-      nodmask |= (nod ? 1u : 0u) << (4 * j + k);
-      uint32_t code;
-      bool flag = sd_d8_fast(c, a[k], a[k + 1], a[k + 2], bb[k], bb[k + 2], cc[k], cc[k + 1], cc[k + 2], code);
-      if (on_border) {
-        // N1 border rule: a border cell with no lower neighbour drains out of the raster
-        const int gyy = w.gy0 + gy, gxx = w.gx0 + gx + k;
-        const uint32_t out = gyy == w.Hg - 1 ? 4u : (gyy == 0 ? 64u : (gxx == 0 ? 16u : (gxx == w.Wg - 1 ? 1u : 0u)));
-        code = code == 0u ? out : code;
-      }
-      codes |= (nod ? 0u : code) << (8 * k);
-      mask |= ((flag && !nod) ? 1u : 0u) << (4 * j + k);
-    }
-    if (gy < H) {
-      const long long o = (long long)gy * w.ld + gx;
-      if (full) {
-        if (NT) __builtin_nontemporal_store(codes, reinterpret_cast<uint32_t *>(fdr + o));
-        else *reinterpret_cast<uint32_t *>(fdr + o) = codes;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          if (gx + k < W) fdr[o + k] = (uint8_t)(codes >> (8 * k));
-          else mask &= ~(1u << (4 * j + k));
-        }
-      }
-    } else {
-      mask &= ~(0xFu << (4 * j));
-    }
-#pragma unroll
-    for (int q = 0; q < 6; q++) {
-      a[q] = bb[q];
-      bb[q] = cc[q];
-    }
-  }
-  if (nod4 && gx < W && y0 + ry < H)
-    reinterpret_cast<uint16_t *>(nod4)[(long long)((y0 + ry) >> 2) * ldm + (gx >> 2)] = (uint16_t)nodmask;
-  const int any = __syncthreads_or(mask != 0u);
-  if (threadIdx.x == 0) tile_mark[tile] = (uint8_t)(any != 0);
-  if (any) lane_mask[(size_t)tile * 256 + threadIdx.x] = (uint16_t)mask;
-}
+#define SD_D8_SLOPE 0
+#include "dt_d8_kernel.inc"
+#undef SD_D8_SLOPE
+#define SD_D8_SLOPE 1
+#include "dt_d8_kernel.inc"
+#undef SD_D8_SLOPE
 
 __global__ __launch_bounds__(256) void k_d8_fix(const float *__restrict__ dem, DtWin w, double px,
                                                uint8_t *__restrict__ fdr, int tiles_x, int tiles_y, int vec_ok,
@@ -843,6 +740,50 @@ static int launch_slope_twi(hipStream_t s, const DtWin &w, const float *dem, dou
   unsigned fix_blocks = SD_FIX_SPLIT * (unsigned)((ntiles + 255) / 256 < 1024 ? (ntiles + 255) / 256 : 1024);
   hipLaunchKernelGGL((k_slope_twi_fix<AccT, WX>), dim3(fix_blocks), b, 0, s, dem, w, px, slope, slope_rad, acc, n_top,
                      lnpx2, ti, mti, tiles_x, tiles_y, vec_ok, mark, lmask, g_tab);
+  return DT_OK;
+}
+
+// The float32 chain's first kernel and its fix-up: D8 codes, the nodata mask and -- slope != NULL -- the slope raster
+// with its flags in `smarks` (dt_stencil_aux_bytes: the marks of dt_launch_fa_finish_fh_local's TI / MTI epilogue and
+// of dt_launch_slope_twi_fix).  `aux` holds the D8 marks, as in dt_launch_stencil.  A single raster (full window).
+int dt_launch_d8_slope(hipStream_t s, const DtWin &w, const float *dem, double px, uint8_t *fdr, float *slope,
+                       void *aux, uint8_t *nod4, int ldm, void *smarks) {
+  if (w.H == 0 || w.W == 0) return DT_OK;
+  if (!slope) return dt_launch_stencil(s, w, dem, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr, nullptr, aux, nod4, ldm);
+  DT_REQUIRE(aux && smarks && nod4 && fdr, "D8 + slope needs both mark workspaces, the codes and the nodata mask");
+  const int tiles_x = (int)((w.W + SD_TX - 1) / SD_TX), tiles_y = (int)((w.H + SD_TY - 1) / SD_TY);
+  const int64_t ntiles = (int64_t)tiles_x * tiles_y;
+  DT_REQUIRE(ntiles < (1ll << 31), "raster too large for one launch");
+  const int vec_ok = (w.W % 4 == 0) && (w.ld % 4 == 0) && (((uintptr_t)dem | (uintptr_t)slope) & 15) == 0 &&
+                     ((uintptr_t)fdr & 3) == 0;
+  dim3 g((unsigned)ntiles), b(256);
+  uint8_t *mark = (uint8_t *)aux, *smark = (uint8_t *)smarks;
+  uint16_t *lmask = (uint16_t *)((char *)aux + dt_align256((size_t)ntiles));
+  uint16_t *slmask = (uint16_t *)((char *)smarks + dt_align256((size_t)ntiles));
+  const double kc = 100.0 / px, kd = 100.0 / (px * sqrt(2.0));
+  hipLaunchKernelGGL(k_d8_slope, g, b, 0, s, dem, w, fdr, tiles_x, tiles_y, vec_ok, mark, lmask, nod4, ldm, kc, kd, slope,
+                     smark, slmask, dt_debug_get(DT_DBG_TWI_FLAG_ALL) ? 0xFFFFu : 0u);
+  unsigned fix_blocks = SD_FIX_SPLIT * (unsigned)((ntiles + 255) / 256 < 1024 ? (ntiles + 255) / 256 : 1024);
+  hipLaunchKernelGGL(k_d8_fix, dim3(fix_blocks), b, 0, s, dem, w, px, fdr, tiles_x, tiles_y, vec_ok, mark, lmask);
+  return DT_OK;
+}
+
+// k_slope_twi_fix alone over the marks k_d8_slope and k_fa3fh1_twi left in `smarks`: slope, TI and MTI of every marked
+// cell from the DEM and the accumulation with the exact functions (256 x 16 tiles, int32 accumulation)
+int dt_launch_slope_twi_fix(hipStream_t s, const DtWin &w, const float *dem, double px, float *slope,
+                            const int32_t *acc, double n_top, float *ti, float *mti, void *smarks) {
+  if (w.H == 0 || w.W == 0) return DT_OK;
+  DT_REQUIRE(smarks && dem && slope && acc && ti && mti, "NULL pointer");
+  const int tiles_x = (int)((w.W + SD_TX - 1) / SD_TX), tiles_y = (int)((w.H + SD_TY - 1) / SD_TY);
+  const int64_t ntiles = (int64_t)tiles_x * tiles_y;
+  DT_REQUIRE(ntiles < (1ll << 31), "raster too large for one launch");
+  const int vec_ok = (w.W % 4 == 0) && (w.ld % 4 == 0) && ((uintptr_t)dem & 15) == 0;  // (the staging's loads)
+  const uint8_t *mark = (const uint8_t *)smarks;
+  const uint16_t *lmask = (const uint16_t *)((const char *)smarks + dt_align256((size_t)ntiles));
+  unsigned fix_blocks = SD_FIX_SPLIT * (unsigned)((ntiles + 255) / 256 < 1024 ? (ntiles + 255) / 256 : 1024);
+  hipLaunchKernelGGL((k_slope_twi_fix<int32_t, 1>), dim3(fix_blocks), dim3(256), 0, s, dem, w, px, slope, (float *)nullptr,
+                     acc, n_top, log(px * px), ti, mti, tiles_x, tiles_y, vec_ok, mark, lmask,
+                     dt_math_device_table(s));
   return DT_OK;
 }
 

@@ -1740,136 +1740,23 @@ __global__ __launch_bounds__(256, 6) void k_fh_tile1n(const uint8_t *__restrict_
 // half fh_tile1n_body; they run one after the other in the same 25.5 KiB of LDS.
 // ND: where "this cell is nodata" (accumulation -100) comes from -- 0 nowhere, 1 the DEM (4 B/cell read for one bit),
 // 2 the D8 kernel's mask (a 16-bit word per 4 x 4 patch, ldm words per row of patches: round 4, the chain's form)
-template <int ND>
-__global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
-                                                  const uint8_t *__restrict__ nod4, int ldm, DtWin w, int tiles_x,
-                                                  const unsigned long long *__restrict__ rec,
-                                                  const unsigned long long *__restrict__ state,
-                                                  const unsigned long long *__restrict__ ext,
-                                                  const uint16_t *__restrict__ loc16, int32_t *__restrict__ acc32,
-                                                  int32_t river_thr, int8_t *__restrict__ river,
-                                                  int *__restrict__ status, uint32_t nnodes,
-                                                  unsigned long long *__restrict__ nodes,
-                                                  unsigned long long *__restrict__ cache,
-                                                  uint8_t *__restrict__ cache_wide) {
-#define P3(c) ((uint32_t)(c) + (((uint32_t)(c) >> 6) << 2))
-#define NT3 (TH * (TW + 4))
-  __shared__ __attribute__((aligned(16))) unsigned char smem[NT3 * 6];  // 26112 bytes
-  __shared__ unsigned long long s_in;
-  __shared__ int s_ovf;
-  // accumulation half: delta raster + padded successor indices
-  uint32_t *s_delta = reinterpret_cast<uint32_t *>(smem);
-  uint16_t *s_nxt = reinterpret_cast<uint16_t *>(smem + NT3 * 4);
-  const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
-  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const int y0 = ty * TH, x0 = tx * TW;
-  const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
-  uint32_t c2[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // see k_fa_tile3
-  if (rec) fa_nbr_codes(fdr, w, y0, x0, threadIdx.x, c2);
-  unsigned long long e = 0ull;
-  if (threadIdx.x < PS && ext) e = ext[(size_t)tile * PS + threadIdx.x];
-  constexpr int VPT = NT / 4 / 256;
-  uint2 l4[VPT];
-  float4 z4[VPT];
-#pragma unroll
-  for (int u = 0; u < VPT; u++) {
-    int c = 4 * (threadIdx.x + 256 * u);
-    int y = y0 + c / TW;
-    l4[u] = *reinterpret_cast<const uint2 *>(loc16 + (size_t)tile * NT + c);
-    z4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ND == 1 && y < w.H) z4[u] = *reinterpret_cast<const float4 *>(dem + (long long)y * w.ld + x0 + c % TW);
-    if (ND == 2 && y < w.H) {  // the four cells' bits, turned into the sentinel where set: finish() tests z <= -100
-      const uint32_t m = (uint32_t)reinterpret_cast<const uint16_t *>(nod4)[(long long)(y >> 2) * ldm + ((x0 + c % TW) >> 2)] >>
-                         (4 * (y & 3));
-      z4[u] = make_float4((m & 1u) ? DT_NODATA : 0.f, (m & 2u) ? DT_NODATA : 0.f, (m & 4u) ? DT_NODATA : 0.f,
-                          (m & 8u) ? DT_NODATA : 0.f);
-    }
-  }
-  // successor indices of the 16 cells whose codes this lane fetched (row t / 4, columns 16 (t % 4) ..): straight from
-  // its registers, the padded row is contiguous -- four 8-byte stores of indices, four 16-byte stores of zeros
-  {
-    const int ly = (int)threadIdx.x >> 2, lxb = ((int)threadIdx.x & 3) * 16;
-    const uint32_t cv[4] = {v_fdr.x, v_fdr.y, v_fdr.z, v_fdr.w};
-    const bool interior = dt_tile_interior(w, y0, x0);
-    const int pbase = ly * (TW + 4) + lxb;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      uint32_t nn[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const uint32_t code = (cv[q] >> (8 * k)) & 0xFFu;
-        const int lx = lxb + 4 * q + k;
-        const uint32_t n = interior ? dt_tile_next_interior(code, ly, lx) : dt_tile_next(code, ly, lx, y0, x0, w);
-        nn[k] = n < NT ? P3(n) : n;
-      }
-      *reinterpret_cast<uint2 *>(&s_nxt[pbase + 4 * q]) = make_uint2(nn[0] | (nn[1] << 16), nn[2] | (nn[3] << 16));
-      *reinterpret_cast<uint4 *>(&s_delta[pbase + 4 * q]) = make_uint4(0, 0, 0, 0);
-    }
-  }
-  // the feeders' words have been in flight behind the staging
-  if (rec) e = fa_inflow(fa_gather(c2, y0, x0, threadIdx.x, tiles_x, rec, state), e);
-  if (threadIdx.x == 0) s_ovf = 0;
-  // (its barrier also publishes the staging)
-  if (__syncthreads_or(!(e & FA_CYCLE) && FA_VALUE(e) >= (1ull << 22))) {  // see k_fa_tile3
-    if (threadIdx.x == 0) s_in = 0ull;
-    __syncthreads();
-    if (e != 0ull && !(e & FA_CYCLE)) atomicAdd(&s_in, FA_VALUE(e));
-    __syncthreads();
-    if (threadIdx.x == 0 && s_in >= (1ull << 31) - (unsigned long long)NT && status) atomicOr(status, DT_STATUS_ACC_OVERFLOW);
-  }
-  if (e != 0ull) {
-    int ly, lx;
-    dt_cell_of_slot(threadIdx.x, ly, lx);
-    uint32_t c = P3(ly * TW + lx);
-    if (e & FA_CYCLE) {
-      for (int it = 0; it < NT && c < NT3; it++) {
-        atomicOr(&s_delta[c], 0x80000000u);
-        c = s_nxt[c];
-      }
-    } else {
-      const uint32_t add = (uint32_t)e;
-      for (int it = 0; it < NT && c < NT3; it++) {
-        atomicAdd(&s_delta[c], add);
-        c = s_nxt[c];
-      }
-    }
-  }
-  __syncthreads();
-  auto finish = [&](uint32_t l16, uint32_t d, float z) -> int32_t {
-    int32_t v = l16 == 0xFFFFu ? -100 : (int32_t)l16;
-    if (v != -100) v += (int32_t)(d & 0x7FFFFFFFu);
-    if (d & 0x80000000u) v = -100;
-    if (ND != 0 && z <= DT_NODATA) v = -100;
-    return v;
-  };
-  uint32_t riv4[VPT];  // the river mask of the lane's 4 x 4 cells, one byte per cell
-#pragma unroll
-  for (int u = 0; u < VPT; u++) {
-    int c = 4 * (threadIdx.x + 256 * u);
-    int y = y0 + c / TW;
-    riv4[u] = 0u;
-    if (y >= w.H) continue;
-    long long o = (long long)y * w.ld + x0 + c % TW;
-    uint4 d = *reinterpret_cast<const uint4 *>(&s_delta[P3(c)]);
-    int4 v = make_int4(finish(l4[u].x & 0xFFFFu, d.x, z4[u].x), finish(l4[u].x >> 16, d.y, z4[u].y),
-                       finish(l4[u].y & 0xFFFFu, d.z, z4[u].z), finish(l4[u].y >> 16, d.w, z4[u].w));
-    *reinterpret_cast<int4 *>(acc32 + o) = v;
-    riv4[u] = (v.x > river_thr ? 1u : 0u) | (v.y > river_thr ? 0x100u : 0u) | (v.z > river_thr ? 0x10000u : 0u) |
-              (v.w > river_thr ? 0x1000000u : 0u);
-    *reinterpret_cast<uint32_t *>(river + o) = riv4[u];
-  }
-  __syncthreads();  // everybody is done with the delta raster: the same LDS now holds HAND's arrays
-#undef P3
-#undef NT3
-  uint32_t *s_w = reinterpret_cast<uint32_t *>(smem);             // 16 KiB
-  uint8_t *s_fdr = smem + NT * 4;                                  // 4 KiB
-  uint8_t *s_kind = smem + NT * 5;                                 // 4 KiB: first the river mask, then the end kinds
-  uint32_t *s_lut = reinterpret_cast<uint32_t *>(smem + NT * 6);   // 1 KiB of the 1.5 KiB left
-  s_lut[threadIdx.x] = fh_lut_entry(threadIdx.x);
-  dt_tile_put16(s_fdr, v_fdr);
-  __syncthreads();
-  fh_tile1n_body(s_fdr, s_w, s_kind, &s_ovf, s_lut, riv4, w, tile, tiles_x, y0, x0, nnodes, nodes, cache, cache_wide);
-}
+
+// what k_fa3fh1_twi (dt_fa3fh1_kernel.inc) needs beyond k_fa3fh1's arguments
+struct TwiOut {
+  const float *slope;
+  float *ti, *mti;
+  double n_top, lnpx2;
+  uint8_t *tile_mark;   // one byte per 256 x 16 stencil tile
+  uint32_t *lane_mask;  // 16 bits per lane of a stencil tile (bit 4 j + k = cell (j, k) of its patch), as 32-bit words
+  int stiles_x;         // stencil tiles per row
+};
+typedef float fa_v4f __attribute__((ext_vector_type(4)));
+#define FA3_TWI 0
+#include "dt_fa3fh1_kernel.inc"
+#undef FA3_TWI
+#define FA3_TWI 1
+#include "dt_fa3fh1_kernel.inc"
+#undef FA3_TWI
 
 // ghost g of ring cell i: a fixed point (ptr = itself, no moves, not done) until resolved
 __global__ __launch_bounds__(256) void k_fh_ghost_init(unsigned long long *__restrict__ nodes, uint32_t nnodes,
@@ -2323,14 +2210,24 @@ int dt_launch_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const 
   return fh_local_tail(s, w, fdr, river, f);
 }
 
+// the shapes k_fa3fh1_twi takes: what the fused tile pass needs (rows of whole 64-cell tiles, 16-byte aligned rasters)
+// on a single raster, with 16-byte aligned slope / ti / mti
+bool dt_twi_epilogue_ok(const DtWin &w, const void *acc, const int8_t *river, const DtTwiEpilogue *twi) {
+  return dt_debug_get(DT_DBG_NO_FUSED_FA_FH) == 0 && w.W % TW == 0 && (w.ld & 3) == 0 && w.halo == 0 && w.gx0 == 0 &&
+         w.gy0 == 0 && w.ld == w.W && ((uintptr_t)acc & 15) == 0 && ((uintptr_t)river & 3) == 0 && twi->marks &&
+         twi->slope && twi->ti && twi->mti &&
+         (((uintptr_t)twi->slope | (uintptr_t)twi->ti | (uintptr_t)twi->mti | (uintptr_t)twi->marks) & 15) == 0;
+}
+
 // Flow accumulation's phase 2 (inflow from other ranks, poison, last tile pass with the river mask) and HAND's phase 1
-// in one go.  `fa_scratch` holds the state dt_launch_fa_local left, `fh_scratch` receives HAND's.  In the common form
+// in one go.  twi != NULL: the last tile pass also writes TI / MTI from the slope raster (k_fa3fh1_twi; a shape it
+// does not take is an error, the caller asks dt_twi_epilogue_ok first).  `fa_scratch` holds the state dt_launch_fa_local left, `fh_scratch` receives HAND's.  In the common form
 // (int32 accumulation, rows of whole 64-cell tiles, 16-byte aligned rasters) the two tile passes are ONE kernel
 // (k_fa3fh1); otherwise they run one after the other.  Same results either way.
 int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, void *fa_scratch,
                                  void *fh_scratch, size_t fh_bytes, const unsigned long long *ext_perim,
                                  int64_t river_thr, void *acc, int acc64, int8_t *river, int *status,
-                                 const uint8_t *nod4, int ldm) {
+                                 const uint8_t *nod4, int ldm, const DtTwiEpilogue *twi) {
   if (w.H == 0 || w.W == 0) return DT_OK;
   DT_REQUIRE(fh_bytes >= dt_flowhand_tiled_scratch(w.H, w.W), "scratch too small");
   DT_REQUIRE(river != nullptr, "HAND needs the river mask");
@@ -2351,7 +2248,15 @@ int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *f
     int32_t thr = river_thr > 2147483647ll ? 2147483647 : (river_thr < -2147483647ll ? -2147483647 : (int32_t)river_thr);
     // the single raster's window starts on the mask's 4-cell grid; a rank's window need not: the DEM there
     const bool use_mask = nod4 != nullptr && w.halo == 0 && w.gx0 == 0 && w.gy0 == 0;
-    if (use_mask)
+    if (twi) {
+      DT_REQUIRE(dt_twi_epilogue_ok(w, acc, river, twi) && use_mask && !ext_perim,
+                 "the TI / MTI epilogue takes a single raster with its nodata mask (dt_twi_epilogue_ok)");
+      const int64_t stx = (w.W + 255) / 256, sntiles = stx * ((w.H + 15) / 16);  // the stencil's 256 x 16 tiles
+      TwiOut tw{twi->slope, twi->ti, twi->mti, twi->n_top, log(twi->px * twi->px), (uint8_t *)twi->marks,
+                (uint32_t *)((char *)twi->marks + dt_align256((size_t)sntiles)), (int)stx};
+      hipLaunchKernelGGL(k_fa3fh1_twi, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16,
+                         (int32_t *)acc, thr, river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide, tw);
+    } else if (use_mask)
       hipLaunchKernelGGL(k_fa3fh1<2>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, (int32_t *)acc, thr,
                          river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide);
     else if (dem)
@@ -2361,6 +2266,7 @@ int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *f
       hipLaunchKernelGGL(k_fa3fh1<0>, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, (int32_t *)acc, thr,
                          river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide);
   } else {
+    DT_REQUIRE(!twi, "the TI / MTI epilogue needs the fused form of the tile passes (dt_twi_epilogue_ok)");
     if (acc64) {
       fa_launch_tile3<long long>(s, gt, w, fdr, dem, f, ext_perim, (long long *)acc, (long long)river_thr, river, status);
     } else {

@@ -334,6 +334,24 @@ int64_t dt_nodata_mask_bytes(int64_t H, int64_t W);
 int dt_dev_slope_d8_m(dt_ctx *ctx, const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr, uint8_t *nodata4);
 int dt_dev_flowacc_river_flowhand_local_m(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const uint8_t *nodata4,
                                           int64_t H, int64_t W, int64_t threshold, int32_t *acc32, int8_t *river);
+/* Slope out of the D8 kernel and TI / MTI out of the last accumulation tile pass (the float32 resident chain's form: no
+ * slope + TI + MTI pass over the raster).  dt_dev_slope_d8_ms = dt_dev_slope_d8_m that also writes `slope` (NULL: it IS
+ * dt_dev_slope_d8_m) and records the cells whose float32 slope is not proven in `marks` (dt_slope_marks_bytes(H, W) bytes
+ * of device memory, 16-byte aligned); dt_dev_flowacc_river_flowhand_local_ms reads that slope raster, writes ti / mti
+ * beside acc32 and adds the cells whose TI / MTI fast path fails to `marks`; dt_dev_slope_twi_fix then recomputes slope,
+ * ti and mti of the marked cells exactly.  The three calls give bit for bit what dt_dev_slope_twi gives.  Only where
+ * dt_slope_from_d8_ok(H, W) != 0 (rows of whole 64-cell tiles) and the rasters are 16-byte aligned; otherwise
+ * dt_dev_flowacc_river_flowhand_local_ms fails with DT_EINVAL and dt_dev_slope_twi is the way. */
+int dt_slope_from_d8_ok(int64_t H, int64_t W);
+int64_t dt_slope_marks_bytes(int64_t H, int64_t W);
+int dt_dev_slope_d8_ms(dt_ctx *ctx, const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr, uint8_t *nodata4,
+                       float *slope, void *marks);
+int dt_dev_flowacc_river_flowhand_local_ms(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const uint8_t *nodata4,
+                                           int64_t H, int64_t W, int64_t threshold, int32_t *acc32, int8_t *river,
+                                           double px, double n_top, const float *slope, float *ti, float *mti,
+                                           void *marks);
+int dt_dev_slope_twi_fix(dt_ctx *ctx, const float *dem, const int32_t *acc32, int64_t H, int64_t W, double px,
+                         double n_top, float *slope, float *ti, float *mti, const void *marks);
 /* The resident chain on float64 heights (descriptools_amd.chain.Chain(heights="float64")); `dem` is an H x W double
  * raster on the device.  Conditioning has its own float64 entry points (dt_dev_condition_d8_f64*), ranks their
  * windowed ones (dt_*_f64_w below: tiling.RankTile(heights="float64")).  Out of scope on float64 heights: the
