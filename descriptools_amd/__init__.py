@@ -2,7 +2,8 @@
 
 Same module / function names as the reference package (callers import the submodules, as
 Example/example.py:11-16 does): slope, flowhand, topoindexes, gfi, downslope, evaluation, helpers;
-net-new: flowdir (D8), flowacc, chain (device-resident full chain), tiling (multi-GPU).
+net-new: flowdir (D8), flowacc, streams (stream order and links), watershed (basins, flow lengths), reaches (reach
+catchments, stage tables, rating curves, inundation), chain (device-resident full chain), tiling (multi-GPU).
 All compute goes through libdescriptools_hip.so (include/descriptools_hip.h); there is no CPU path.
 """
 __version__ = "0.1.0"

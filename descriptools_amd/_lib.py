@@ -50,6 +50,10 @@ _SIGS = {
     "dt_stream_order": (ci, [c_u8p, c_i8p, i64, i64, c_i8p, c_i64p, c_i64p]),
     "dt_drainage": (ci, [c_u8p, c_f32p, c_i64p, i64, i64, f64, c_i64p, c_f64p, c_i64p]),
     "dt_upslope_length": (ci, [c_u8p, c_f32p, i64, i64, f64, c_f64p]),
+    "dt_reach_catchments": (ci, [c_i64p, c_i64p, i64, i64, c_i32p, c_i32p, c_i64p, i64, c_i64p]),
+    "dt_reach_channels": (ci, [c_u8p, c_i32p, i64, i64, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
+    "dt_reach_tables": (ci, [c_i32p, vp, ci, c_f32p, i64, i64, c_f64p, ci, i64, ci, c_i64p, c_i64p, c_i64p]),
+    "dt_inundate": (ci, [c_i32p, vp, ci, c_f64p, i64, i64, i64, c_f32p]),
     "dt_d8_conditioned_f32": (ci, [c_f32p, i64, i64, f64, c_u8p, c_f32p, c_i32p]),
     "dt_dev_condition_d8": (ci, [vp, vp, i64, i64, f64, vp, vp, c_i32p]),
     "dt_dev_condition_d8_async": (ci, [vp, vp, i64, i64, f64, vp, vp, ci]),
@@ -88,6 +92,10 @@ _SIGS = {
     "dt_dev_stream_order": (ci, [vp, vp, vp, i64, i64, vp, vp, vp]),
     "dt_dev_drainage": (ci, [vp, vp, vp, vp, i64, i64, f64, vp, vp, vp]),
     "dt_dev_upslope_length": (ci, [vp, vp, vp, i64, i64, f64, vp]),
+    "dt_dev_reach_catchments": (ci, [vp, vp, vp, ci, i64, i64, vp, vp, vp, i64, vp]),
+    "dt_dev_reach_channels": (ci, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "dt_dev_reach_tables": (ci, [vp, vp, vp, ci, vp, i64, i64, c_f64p, ci, i64, ci, vp, vp, vp]),
+    "dt_dev_inundate": (ci, [vp, vp, vp, ci, vp, i64, i64, i64, vp]),
     "dt_dev_river_mask": (ci, [vp, vp, i64, i64, vp]),
     "dt_dev_flowacc_river": (ci, [vp, vp, vp, i64, i64, i64, vp, vp]),
     "dt_dev_gfi_lnhlh": (ci, [vp, vp, vp, vp, i64, f64, f64, f64, vp, vp]),

@@ -612,6 +612,92 @@ extern "C" int dt_dev_upslope_length(dt_ctx *c, const uint8_t *fdr, const float 
   return DT_OK;
 }
 
+// reaches: reach ids and flat indices travel in 31 bits
+static int dt_check_reach_count(int64_t R) {
+  DT_REQUIRE(R >= 0 && R < (1ll << 31), "the number of reaches must lie in [0, 2^31)");
+  return DT_OK;
+}
+
+extern "C" int dt_dev_reach_catchments(dt_ctx *c, const int64_t *link, const void *idx, int idx_bytes, int64_t H,
+                                       int64_t W, int32_t *reach, int32_t *catch_, int64_t *heads, int64_t cap,
+                                       int64_t *n_reaches) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  const int64_t N = H * W;
+  DT_REQUIRE(link || N == 0, "NULL raster");
+  DT_REQUIRE(!catch_ || N == 0 || (idx && (idx_bytes == 4 || idx_bytes == 8)),
+             "catch needs idx with an element size of 4 or 8");
+  DT_REQUIRE(cap >= 0, "negative capacity");
+  size_t need = dt_reach_catchments_scratch(N, reach == nullptr);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  DT_TRY(dt_launch_reach_catchments(c->stream, link, idx, idx_bytes, N, scr, need, reach, catch_, heads, cap,
+                                    n_reaches));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
+extern "C" int dt_dev_reach_channels(dt_ctx *c, const uint8_t *fdr, const int32_t *reach, int64_t H, int64_t W,
+                                     int64_t R, int64_t *end, int64_t *down, int64_t *n_cells, int64_t *n_card,
+                                     int64_t *n_diag) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_reach_count(R));
+  if (R == 0) return DT_OK;
+  DT_REQUIRE((fdr && reach) || H * W == 0, "NULL raster");
+  DT_REQUIRE(end && down && n_cells && n_card && n_diag, "NULL output");
+  DT_TRY(dt_launch_reach_channels(c->stream, fdr, reach, H, W, R, end, down, n_cells, n_card, n_diag));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
+// the stages' contract and the bound of frac_bits: N * rint(max(stages[K - 1], 1) * 2^frac_bits) <= 2^52
+static int dt_check_stages(const double *stages, int K, int frac_bits, int64_t N) {
+  DT_REQUIRE(K >= 1 && K <= 1024 && stages, "1..1024 stages per call");
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  DT_REQUIRE(std::isfinite(stages[0]) && stages[0] >= 0.0, "stages must be finite and >= 0");
+  for (int k = 1; k < K; k++)
+    DT_REQUIRE(std::isfinite(stages[k]) && stages[k] > stages[k - 1], "stages must be finite and strictly increasing");
+  const double top = stages[K - 1] > 1.0 ? stages[K - 1] : 1.0;
+  const double q = rint(ldexp(top, frac_bits));
+  DT_REQUIRE(N == 0 || q <= (double)((1ull << 52) / (unsigned long long)N),
+             "frac_bits is too fine: N * rint(max(stages[K - 1], 1) * 2^frac_bits) exceeds 2^52");
+  return DT_OK;
+}
+
+extern "C" int dt_dev_reach_tables(dt_ctx *c, const int32_t *catch_, const void *hand, int hand_bytes,
+                                   const float *slope, int64_t H, int64_t W, const double *stages, int K, int64_t R,
+                                   int frac_bits, int64_t *cells, int64_t *Hq, int64_t *Bq) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_reach_count(R));
+  DT_TRY(dt_check_stages(stages, K, frac_bits, H * W));
+  DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
+  if (R == 0) return DT_OK;
+  DT_REQUIRE((catch_ && hand) || H * W == 0, "NULL raster");
+  DT_REQUIRE(cells && Hq && Bq, "NULL table");
+  size_t need = dt_reach_tables_scratch(K);
+  DT_TRY(dt_scratch_reset(c, need));
+  void *scr = dt_scratch_take(c, need);
+  DT_TRY(dt_launch_reach_tables(c->stream, catch_, hand, hand_bytes, slope, H, W, stages, K, R, frac_bits, scr, need,
+                                cells, Hq, Bq, c->status, dt_debug_get(DT_DBG_RC_SLOTS)));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
+extern "C" int dt_dev_inundate(dt_ctx *c, const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
+                               int64_t H, int64_t W, int64_t R, float *depth) {
+  DT_CTX(c);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_reach_count(R));
+  DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(catch_ && hand && depth && (stage || R == 0), "NULL raster");
+  DT_TRY(dt_launch_inundate(c->stream, catch_, hand, hand_bytes, stage, H * W, R, depth));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
 extern "C" int dt_dev_river_mask(dt_ctx *c, const int32_t *acc32, int64_t N, int64_t threshold,
                                  int8_t *river) {
   DT_CTX(c);
@@ -1938,6 +2024,95 @@ extern "C" int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H
   const float *d_dem = hc.in(dem, n);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_upslope_length(hc.c, d_f, d_dem, H, W, px, d_l));
+  return hc.finish();
+}
+
+extern "C" int dt_reach_catchments(const int64_t *link, const int64_t *idx, int64_t H, int64_t W, int32_t *reach,
+                                   int32_t *catch_, int64_t *heads, int64_t cap, int64_t *n_reaches) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_REQUIRE(n_reaches && cap >= 0 && (heads || cap == 0), "bad arguments");
+  *n_reaches = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(link && (idx || !catch_), "NULL raster");
+  if ((size_t)cap > n) cap = (int64_t)n;
+  const int64_t *d_l = hc.in(link, n);
+  const int64_t *d_i = catch_ ? hc.in(idx, n) : nullptr;
+  int32_t *d_r = hc.out(reach, n);
+  int32_t *d_c = hc.out(catch_, n);
+  int64_t *d_h = cap ? hc.out(heads, (size_t)cap) : nullptr;
+  int64_t *d_n = hc.scratch<int64_t>(1);
+  DT_TRY(hc.rc);
+  if (d_h) DT_HIP(hipMemsetAsync(d_h, 0xFF, (size_t)cap * 8, hc.c->stream));  // -1 beyond the last head
+  DT_TRY(dt_dev_reach_catchments(hc.c, d_l, d_i, 8, H, W, d_r, d_c, d_h, cap, d_n));
+  DT_TRY(hc.download(n_reaches, (const int64_t *)d_n, 1));
+  return hc.finish();
+}
+
+extern "C" int dt_reach_channels(const uint8_t *fdr, const int32_t *reach, int64_t H, int64_t W, int64_t R,
+                                 int64_t *end, int64_t *down, int64_t *n_cells, int64_t *n_card, int64_t *n_diag) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_reach_count(R));
+  if (R == 0) return DT_OK;
+  DT_REQUIRE(end && down && n_cells && n_card && n_diag, "NULL output");
+  const size_t n = (size_t)H * W;
+  DT_REQUIRE((fdr && reach) || n == 0, "NULL raster");
+  const uint8_t *d_f = hc.in(fdr, n);
+  const int32_t *d_r = hc.in(reach, n);
+  int64_t *d_e = hc.out(end, (size_t)R), *d_d = hc.out(down, (size_t)R), *d_n = hc.out(n_cells, (size_t)R);
+  int64_t *d_nc = hc.out(n_card, (size_t)R), *d_nd = hc.out(n_diag, (size_t)R);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_reach_channels(hc.c, d_f, d_r, H, W, R, d_e, d_d, d_n, d_nc, d_nd));
+  return hc.finish();
+}
+
+extern "C" int dt_reach_tables(const int32_t *catch_, const void *hand, int hand_bytes, const float *slope, int64_t H,
+                               int64_t W, const double *stages, int K, int64_t R, int frac_bits, int64_t *cells,
+                               int64_t *Hq, int64_t *Bq) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_reach_count(R));
+  DT_TRY(dt_check_stages(stages, K, frac_bits, H * W));
+  DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
+  if (R == 0) return DT_OK;
+  DT_REQUIRE(cells && Hq && Bq, "NULL table");
+  const size_t n = (size_t)H * W, rk = (size_t)R * (size_t)K;
+  DT_REQUIRE((catch_ && hand) || n == 0, "NULL raster");
+  const int32_t *d_c = hc.in(catch_, n);
+  const unsigned char *d_h = hc.in((const unsigned char *)hand, n * (size_t)hand_bytes);
+  const float *d_s = hc.in(slope, n);
+  int64_t *d_n = hc.out(cells, rk), *d_hq = hc.out(Hq, rk), *d_bq = hc.out(Bq, rk);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  DT_TRY(dt_dev_reach_tables(hc.c, d_c, d_h, hand_bytes, d_s, H, W, stages, K, R, frac_bits, d_n, d_hq, d_bq));
+  DT_TRY(dt_ctx_status(hc.c, &st));
+  DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a bed weight sqrt(1 + (slope / 100)^2) is over the bound of frac_bits");
+  DT_REQUIRE(!(st & DT_STATUS_REACH_RANGE), "a catchment id is >= the number of reaches");
+  return hc.finish();
+}
+
+extern "C" int dt_inundate(const int32_t *catch_, const void *hand, int hand_bytes, const double *stage, int64_t H,
+                           int64_t W, int64_t R, float *depth) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_reach_count(R));
+  DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(catch_ && hand && depth && (stage || R == 0), "NULL raster");
+  const int32_t *d_c = hc.in(catch_, n);
+  const unsigned char *d_h = hc.in((const unsigned char *)hand, n * (size_t)hand_bytes);
+  const double *d_s = hc.in(stage, (size_t)R);
+  float *d_d = hc.out(depth, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_inundate(hc.c, d_c, d_h, hand_bytes, d_s, H, W, R, d_d));
   return hc.finish();
 }
 

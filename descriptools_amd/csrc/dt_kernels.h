@@ -199,3 +199,22 @@ int dt_launch_drainage(hipStream_t s, const uint8_t *fdr, const float *dem, cons
                        int64_t *label);
 int dt_launch_upslope_length(hipStream_t s, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                              void *scratch, size_t scratch_bytes, double *length);
+
+// reaches (dt_reaches.hip): the rank of every link head (reach ids), reach / catchment rasters, per-reach channel
+// counts, stage tables and inundation depth; definitions in include/descriptools_hip.h.  Nothing synchronises.
+// H * W < 2^31.  reach / catch / heads may be NULL (own_reach: reach is NULL and the launcher keeps the head ranks in
+// scratch); idx is int32 (idx_bytes 4) or int64 (8); hand is float32 (hand_bytes 4) or float64 (8); slope may be NULL.
+// slots: 0 the default LDS table, n > 0 at most n slots, < 0 no LDS table (DT_DBG_RC_SLOTS).
+size_t dt_reach_catchments_scratch(int64_t N, int own_reach);
+int dt_launch_reach_catchments(hipStream_t s, const int64_t *link, const void *idx, int idx_bytes, int64_t N,
+                               void *scratch, size_t scratch_bytes, int32_t *reach, int32_t *catch_, int64_t *heads,
+                               int64_t cap, int64_t *n_reaches_dev);
+int dt_launch_reach_channels(hipStream_t s, const uint8_t *fdr, const int32_t *reach, int64_t H, int64_t W, int64_t R,
+                             int64_t *end, int64_t *down, int64_t *n_cells, int64_t *n_card, int64_t *n_diag);
+size_t dt_reach_tables_scratch(int K);
+int dt_launch_reach_tables(hipStream_t s, const int32_t *catch_, const void *hand, int hand_bytes, const float *slope,
+                           int64_t H, int64_t W, const double *stages_host, int K, int64_t R, int frac_bits,
+                           void *scratch, size_t scratch_bytes, int64_t *cells, int64_t *Hq, int64_t *Bq, int *status,
+                           int slots);
+int dt_launch_inundate(hipStream_t s, const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
+                       int64_t N, int64_t R, float *depth);

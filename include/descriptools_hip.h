@@ -99,6 +99,9 @@ int dt_graph_destroy(dt_graph *graph);
 /* DT_STATUS_BAD_WEIGHT: dt_dev_flowacc_weighted met a weight outside its contract (negative, NaN, infinite, or one whose
  * rint(w * 2^frac_bits) exceeds 2^52 / (H * W)): the weighted accumulation of that call is not valid. */
 #define DT_STATUS_BAD_WEIGHT 4
+/* DT_STATUS_REACH_RANGE: dt_dev_reach_tables met a catchment id >= the number of reaches it was given; that cell was
+ * left out of the tables. */
+#define DT_STATUS_REACH_RANGE 8
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
 
@@ -178,6 +181,40 @@ int dt_drainage(const uint8_t *fdr, const float *dem, const int64_t *pour, int64
  * float64(n_card) * px + float64(n_diag) * (px * sqrt(2.0)).  -100 on nodata and on cells of a D8 cycle; cells that
  * drain into a cycle get their value.  Same refusals as dt_drainage. */
 int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px, double *length);
+/* Net-new: reaches (the HAND synthetic-rating-curve method).  Rasters are H x W with fewer than 2^31 cells, flat index
+ * y * W + x; results are exact integers (and depth one float32 rounding), independent of order and run.
+ *
+ * dt_reach_catchments.  `link` as dt_stream_order writes it.  A cell c is a head when link[c] == c; R = the number of
+ * heads; the id of a head is its rank among the heads in ascending flat index, heads[id] that flat index.
+ *   reach (int32): the id of link[c] where link[c] >= 0 (and names a head), -100 elsewhere.
+ *   catch (int32): reach[idx[c]] where 0 <= idx[c] < H * W (idx: the river index dt_flowhand writes), -100 elsewhere.
+ *   heads (int64[cap]): ids >= cap are not written; entries from R on are -1.  *n_reaches = R, whatever cap is, so a
+ *                  caller whose capacity was too small calls again with reach = catch = idx = NULL and cap = R.
+ * reach, catch (then idx too) and heads may be NULL. */
+int dt_reach_catchments(const int64_t *link, const int64_t *idx, int64_t H, int64_t W, int32_t *reach, int32_t *catch_,
+                        int64_t *heads, int64_t cap, int64_t *n_reaches);
+/* dt_reach_channels.  On dt_stream_order's network graph restricted to reach >= 0 (c -> d when c's code is a D8 code
+ * and d is in the raster with reach[d] >= 0), for every reach r < R over its cells, all int64[R]:
+ *   n_cells; n_card / n_diag: the cardinal / diagonal edges leaving its cells (the move out of the link's last cell
+ *   counts for r); end: the flat index where the link's last move lands (the last cell itself when it has no edge);
+ *   down: reach[end] when the last cell has an edge, else -1. */
+int dt_reach_channels(const uint8_t *fdr, const int32_t *reach, int64_t H, int64_t W, int64_t R, int64_t *end,
+                      int64_t *down, int64_t *n_cells, int64_t *n_card, int64_t *n_diag);
+/* dt_reach_tables.  hand is float32 (hand_bytes 4) or float64 (8); slope (float32, percent) may be NULL; stages is
+ * float64[K], 1 <= K <= 1024, finite, stages[0] >= 0, strictly increasing.  A cell takes part when catch[c] = r with
+ * 0 <= r < R and 0 <= hand[c] <= stages[K - 1] (false for NaN and -100); its bin is the smallest k with hand[c] <=
+ * stages[k]; hq = rint(hand * 2^s) and wq = rint(sqrt(1 + t * t) * 2^s), t = slope[c] / 100 where slope[c] is finite
+ * and > 0, else 0 (everywhere without slope), in float64, round half to even, s = frac_bits.  For every reach r and
+ * stage k, over the cells of r with bin <= k (int64[R * K], row r):
+ *   cells = their number, Hq = the sum of hq, Bq = the sum of wq.
+ * H * W * rint(max(stages[K - 1], 1) * 2^s) must be <= 2^52 (refused otherwise).  A bed weight whose wq exceeds
+ * 2^52 / (H * W), or a catch value >= R, fails the call and the tables are not valid. */
+int dt_reach_tables(const int32_t *catch_, const void *hand, int hand_bytes, const float *slope, int64_t H, int64_t W,
+                    const double *stages, int K, int64_t R, int frac_bits, int64_t *cells, int64_t *Hq, int64_t *Bq);
+/* dt_inundate.  depth (float32) = -100 where hand[c] == -100; else float32(stage[r] - float64(hand[c])) when
+ * catch[c] = r with 0 <= r < R, stage[r] (float64[R]) is finite and 0 <= hand[c] <= stage[r]; else 0. */
+int dt_inundate(const int32_t *catch_, const void *hand, int hand_bytes, const double *stage, int64_t H, int64_t W,
+                int64_t R, float *depth);
 
 /* flowhand.flow_distance_index_cpu + flow_distance_index_gpu (flowhand.py:476-846, untiled
  * call: out = 0, row_start = col_start = 0, matrix_columns = W) and flowhand.hand_calculator
@@ -315,6 +352,20 @@ int dt_dev_drainage(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const int
                     double px, int64_t *target, double *length, int64_t *label);
 int dt_dev_upslope_length(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                           double *length);
+/* The reach calls on device rasters, on the context's stream: none synchronises.  idx is int32 (idx_bytes 4, the
+ * resident chain's raster) or int64 (8); n_reaches (may be NULL) is one int64 on the device; heads entries from R on
+ * are left as they were.  dt_dev_reach_tables takes `stages` from the host (they travel as kernel arguments) and the
+ * tables on the device; a bed weight over the bound raises DT_STATUS_BAD_WEIGHT and counts as 0, a catch value >= R
+ * raises DT_STATUS_REACH_RANGE and is left out (dt_ctx_status).  stage is float64[R] on the device. */
+int dt_dev_reach_catchments(dt_ctx *ctx, const int64_t *link, const void *idx, int idx_bytes, int64_t H, int64_t W,
+                            int32_t *reach, int32_t *catch_, int64_t *heads, int64_t cap, int64_t *n_reaches);
+int dt_dev_reach_channels(dt_ctx *ctx, const uint8_t *fdr, const int32_t *reach, int64_t H, int64_t W, int64_t R,
+                          int64_t *end, int64_t *down, int64_t *n_cells, int64_t *n_card, int64_t *n_diag);
+int dt_dev_reach_tables(dt_ctx *ctx, const int32_t *catch_, const void *hand, int hand_bytes, const float *slope,
+                        int64_t H, int64_t W, const double *stages, int K, int64_t R, int frac_bits, int64_t *cells,
+                        int64_t *Hq, int64_t *Bq);
+int dt_dev_inundate(dt_ctx *ctx, const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
+                    int64_t H, int64_t W, int64_t R, float *depth);
 /* flow accumulation with the river mask (acc > threshold, Example/example.py:52) written by the
  * same final pass */
 int dt_dev_flowacc_river(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
