@@ -530,7 +530,130 @@ def case_example_descriptors():
     save("example_desc", **res)
 
 
-CASES = {"f64": case_f64, "nonfinite": case_nonfinite, "nonfinite_f64": case_nonfinite_f64,"shims": case_shims, "example_descriptors": case_example_descriptors, "synth": case_synth, "example_windows": case_example_windows, "edge": case_edge,
+# ------------------------------------------------------------------------------------------
+# The "params" family: the reference off the Example's parameters -- pixel sizes whose products are inexact in float64
+# and exponent / scale / dz sets beside the defaults -- and the hard-case rasters of tests/test_gpu_pixel_size.py.
+# (the pixel sizes and parameter sets are the test module's: T.PXS, T.PARAM_SETS)
+SHARED = ("slope", "slope_rad", "fdist", "idx", "hand")
+PER_SET = ("ti", "mti", "gfi", "lnhlh", "down")
+
+
+def _params_file(name, dem_ref, dem_store, fdr, fac, river, px, set_names, PARAM_SETS):
+    """one raster at one pixel size under several parameter sets: the rasters that do not depend on the set once, the
+    others as <set>__<raster>"""
+    res = {"dem": dem_store, "fdr": fdr, "fac": fac, "river": river, "px": px, "sets": np.array(set_names)}
+    for s in set_names:
+        n_top, n_gfi, b, dz = PARAM_SETS[s]
+        with ieee_math():
+            out = run_chain(dem_ref, fdr, fac, river, px, n_top, n_gfi, b, dz)
+        out["hand"] = out["hand"].astype(np.float32)
+        out["idx"] = out["idx"].astype(np.int32)
+        for k in SHARED:
+            if k in res:
+                assert np.array_equal(res[k], out[k], equal_nan=True), k
+            res[k] = out[k]
+        res[s + "__params"] = np.array([n_top, n_gfi, b, dz])
+        for k in PER_SET:
+            res[s + "__" + k] = out[k]
+    save(name, **res)
+
+
+def slope_scan(px):
+    """Every float32 drop of the binade [1, 2) (the forms scale exactly with powers of two, so this is every normal
+    drop): where does the product form d * fl(100 / dist) round to another float32 than the literal
+    fl(fl(d / dist) * 100)?  -> per class (cardinal, diagonal): number of such drops, the first four of them, and the
+    eight drops that agree but whose product lies nearest a float32 rounding midpoint (bit patterns)."""
+    res = []
+    bits = np.arange(0x3F800000, 0x40000000, dtype=np.uint32)
+    d = bits.view(np.float32).astype(np.float64)
+    for dist in (px, px * np.sqrt(2.0)):
+        q = d * (100.0 / dist)
+        bad = q.astype(np.float32) != ((d / dist) * 100.0).astype(np.float32)
+        lo = np.abs((q.view(np.uint64) & np.uint64(0x1FFFFFFF)).astype(np.int64) - 0x10000000)
+        lo[bad] = 1 << 40
+        near = np.sort(np.argsort(lo, kind="stable")[:8])
+        first = np.zeros(4, np.uint32)
+        first[:min(4, int(bad.sum()))] = bits[bad][:4]
+        res.append((int(bad.sum()), first, bits[near], lo[near]))
+    return res
+
+
+def case_params(rasters=True):
+    print("params", flush=True)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_pixel_size as T
+    PARAM_PXS, PARAM_SETS = T.PXS, T.PARAM_SETS
+    # (1) the offline scan of the slope forms, a golden file of its own: the planted raster of the tests is built from it
+    scan = [slope_scan(px) for px in PARAM_PXS]
+    hard = {"scan_px": np.array(PARAM_PXS)}
+    for c, cls in enumerate(("card", "diag")):
+        hard["scan_%s_mismatches" % cls] = np.array([s[c][0] for s in scan], np.int64)
+        hard["scan_%s_first" % cls] = np.array([s[c][1] for s in scan], np.uint32)
+        hard["scan_%s_bits" % cls] = np.array([s[c][2] for s in scan], np.uint32)
+        hard["scan_%s_ulps" % cls] = np.array([s[c][3] for s in scan], np.int64)
+        print("   scan %s: mismatching drops per px %s, nearest agreeing drops (float64 ulps from the midpoint) %s"
+              % (cls, hard["scan_%s_mismatches" % cls].tolist(), hard["scan_%s_ulps" % cls].tolist()), flush=True)
+    save("params_scan", **hard)
+    hard = {}
+    # (2) a synthetic raster with a nodata blob and a crop of the Example, each at every pixel size under the default
+    # set and one other set in rotation (every set at three pixel sizes at least)
+    names = list(PARAM_SETS)[1:]
+    dem32 = oracle.synth_dem(9, 1024, 1024, 480, 224, 64, 96, 0).copy()
+    dem32[20:31, 50:66] = -100.0
+    ex = np.load(os.path.join(GOLD, "ex_river.npz"))
+    for i, px in enumerate(PARAM_PXS if rasters else ()):
+        _, fdr = oracle.slope_d8(dem32, px)
+        fac = oracle.flowacc(fdr, dem32)
+        river = (fac > 12).astype(np.int8)
+        _params_file("params_syn_%d" % i, dem32.astype(np.float64), dem32, fdr, fac, river, px,
+                     ["default", names[i % 3]], PARAM_SETS)
+        y, x = 40, 24
+        crop = [np.ascontiguousarray(ex[k][y:y + 64, x:x + 96]) for k in ("dem", "fdr", "fac", "river")]
+        _params_file("params_ex_%d" % i, crop[0], crop[0], crop[1], crop[2], crop[3], px,
+                     ["default", names[(i + 2) % 3]], PARAM_SETS)
+    # (3) the hard-case rasters of tests/test_gpu_pixel_size.py, shrunk: the reference itself on the cells where the
+    # cheaper forms disagree with it
+    px = 30.0
+    dem, plants = T.dem_planted(px)
+    rows = 1 + max(y for k, v in plants.items() for y, _ in ([v] if isinstance(v, tuple) else v)) + 3
+    dem = np.ascontiguousarray(dem[:rows])
+    _, fdr = oracle.slope_d8(dem, px)
+    # (the reference is handed float64 copies, see the module docstring: its values hold for float32 heights only
+    # where the height differences are float32-exact; the planted cells are built so, the 50 m cells beside them not)
+    cells = [c for k, v in plants.items() for c in ([v] if isinstance(v, tuple) else v)]
+    hard.update(planted_px=px, planted_dem=dem, planted_fdr=fdr, planted_cells=np.array(cells),
+                planted_slope=R_slope.sloper(dem.astype(np.float64), px).astype(np.float32))
+    for dz in (5.0, 0.3, 0.1):
+        hard["planted_down_%g" % dz] = R_down.downsloper(dem.astype(np.float64), fdr, px, dz).astype(np.float32)
+    full, lanes = T.dem_long_walks()
+    # the first three cardinal-only lanes of ~1536 and ~2048 moves with the walls around them, 2560 columns
+    pick = [l for l in lanes if l[2] == "card"]
+    n_of = lambda l: int(np.median(T.lane_walks(full, oracle.slope_d8(full, 0.1)[1], [l], 5.0)[0][l[0][0], :500]))
+    pick = [l for l in pick if n_of(l) in range(1500, 2100)][:3]
+    rows_ = sorted({r for l in pick for r in (l[0][0] - 1, l[0][0], l[0][0] + 1)})
+    crop = np.ascontiguousarray(full[rows_][:, :2560])
+    hard["long_dem"] = crop
+    for j, px in enumerate((0.1, 1.0 / 3.0)):
+        _, fdr = oracle.slope_d8(crop, px)
+        crop_lanes = [((rows_.index(l[0][0]), None), np.full(2560, rows_.index(l[0][0])), "card") for l in pick]
+        n, nd, drop = T.lane_walks(crop, fdr, crop_lanes, 5.0)
+        o = oracle.downslope(crop, fdr, px, 5.0)
+        bad = (n > 0) & (T.count_form(drop, np.maximum(n, 1), np.maximum(nd, 0), px) != o)
+        sel = np.flatnonzero(bad.reshape(-1))[:24].tolist()
+        sel += [int(crop_lanes[0][0][0]) * 2560 + x for x in (0, 7, 300, 1100, 2000, 2559)]
+        standin_cuda.THREAD_FILTER = sel
+        d = R_down.downsloper(crop.astype(np.float64), fdr, px, 5.0)
+        standin_cuda.THREAD_FILTER = None
+        hard.update({"long_px%d" % j: px, "long_fdr%d" % j: fdr, "long_sel%d" % j: np.array(sel),
+                     "long_divergent%d" % j: int(bad.sum()),
+                     "long_down%d" % j: d.reshape(-1)[sel].astype(np.float32)})
+        print("   long walks px %r: %d divergent cells in the crop, %d walked by the reference; the oracle differs on %d"
+              % (px, int(bad.sum()), len(sel), int((o.reshape(-1)[sel] != hard["long_down%d" % j]).sum())), flush=True)
+    save("params_hard", **hard)
+
+
+
+CASES = {"params": case_params, "params_hard": lambda: case_params(False), "f64": case_f64, "nonfinite": case_nonfinite, "nonfinite_f64": case_nonfinite_f64,"shims": case_shims, "example_descriptors": case_example_descriptors, "synth": case_synth, "example_windows": case_example_windows, "edge": case_edge,
          "eval": case_eval, "example_full": case_example_full}
 
 if __name__ == "__main__":

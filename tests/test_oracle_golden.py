@@ -275,3 +275,93 @@ def test_nonfinite_f64_descriptors():
     _, fdr = oracle.slope_d8(dem.astype(np.float32), px)
     assert np.array_equal(fdr, g["fdr"])
     assert np.array_equal(oracle.flowacc(g["fdr"], dem.astype(np.float32)), g["fac"])
+
+
+# ------------------------------------------------------------------------------------------
+# Off the Example's parameters (tests/golden/params_*.npz, oracle/gen_golden.py params): pixel sizes whose products are
+# inexact in float64 (30, 0.1, 1/3, 30.922..., 2500), exponents of one, a scale factor >= 1 and values of dz that
+# float32 cannot hold -- the same assertions as above: integers, slope, HAND, flow distance and downslope bit for bit,
+# the float descriptors through assert_float_close.
+PARAM_FILES = ["params_syn_%d" % i for i in range(5)] + ["params_ex_%d" % i for i in range(5)]
+
+
+def test_params_cover_the_pixel_sizes_and_sets():
+    pxs, sets = set(), {}
+    for name in PARAM_FILES:
+        g = golden(name)
+        pxs.add(float(g["px"]))
+        for s in g["sets"]:
+            sets.setdefault(tuple(g[str(s) + "__params"]), set()).add(float(g["px"]))
+    assert pxs >= {30.0, 0.1, 1.0 / 3.0, 30.922080775909325, 2500.0}
+    assert len(sets) >= 4 and all(len(v) >= 2 for v in sets.values())
+    assert any(n_top == 1.0 and n_gfi == 1.0 for n_top, n_gfi, b, dz in sets)
+    assert any(b >= 1.0 for n_top, n_gfi, b, dz in sets)
+    assert any(float(np.float32(dz)) != dz for n_top, n_gfi, b, dz in sets)
+
+
+@pytest.mark.parametrize("name", PARAM_FILES)
+def test_params_against_the_reference(name):
+    g = golden(name)
+    dem, px = g["dem"].astype(np.float32), float(g["px"])
+    assert np.array_equal(oracle.slope_d8(dem, px)[0], g["slope"]), "slope must be bit-identical"
+    fd, idx, hand = oracle.flowhand(dem, g["fdr"], g["river"], px)
+    assert np.array_equal(idx, g["idx"])
+    assert np.array_equal(fd, g["fdist"]), "sequential f64 sum: bit-identical"
+    assert np.array_equal(hand, g["hand"])
+    for s in g["sets"]:
+        n_top, n_gfi, b, dz = (float(v) for v in g[str(s) + "__params"])
+        ref = {k: g["%s__%s" % (s, k)] for k in ("ti", "mti", "gfi", "lnhlh", "down")}
+        ti, mti = oracle.twi(g["fac"], g["slope_rad"], px, n_top)
+        assert_float_close(ti, ref["ti"], rtol=1e-6, what="ti")
+        assert_float_close(mti, ref["mti"], rtol=1e-6, atol=1e-7, what="mti")
+        assert_float_close(oracle.gfi(hand, g["fac"], g["idx"], n_gfi, b, px), ref["gfi"], rtol=1e-6, atol=1e-7,
+                           what="gfi")
+        assert_float_close(oracle.lnhlh(hand, g["fac"], n_gfi, b, px), ref["lnhlh"], rtol=1e-6, atol=1e-7,
+                           what="lnhlh")
+        pit = np.isnan(ref["down"])   # the reference's 0 / 0 at valid-DEM pits: defined as 0 (test_downslope)
+        assert (g["fdr"][pit] == 0).all()
+        assert np.array_equal(oracle.downslope(dem, g["fdr"], px, dz), np.where(pit, 0, ref["down"]))
+
+
+def test_params_hard_cases_against_the_reference():
+    """the hard-case rasters of tests/test_gpu_pixel_size.py, shrunk to golden size: the reference's own values on the
+    cells where the product form of the slope and the count form of the walk's length round differently"""
+    g = golden("params_hard")
+    dem, px = g["planted_dem"], float(g["planted_px"])
+    slope, fdr = oracle.slope_d8(dem, px)
+    assert np.array_equal(fdr, g["planted_fdr"])
+    # The golden values are the reference's on a float64 copy: they are those of the float32 raster where the height
+    # differences are exact in float32 -- on the planted cells by construction, on every cell whose descents are exact
+    # for the slope (the 50 m cells beside a planted drop of 24 bits are not).
+    H, W = dem.shape
+    p = np.pad(dem, 1, mode="edge")
+    exact = np.ones((H, W), bool)
+    for dy in (0, 1, 2):
+        for dx in (0, 1, 2):
+            nb = p[dy:dy + H, dx:dx + W]
+            d64 = dem.astype(np.float64) - nb.astype(np.float64)   # (a rise never sets the maximum, however rounded)
+            exact &= (d64 <= 0) | ((dem - nb).astype(np.float64) == d64)
+    ys, xs = g["planted_cells"].T
+    assert exact[ys, xs].all() and exact.mean() > 0.8
+    assert np.array_equal(slope[exact], g["planted_slope"][exact])
+    for dz in (5.0, 0.3, 0.1):
+        assert np.array_equal(oracle.downslope(dem, fdr, px, dz)[ys, xs], g["planted_down_%g" % dz][ys, xs])
+    # the product form is NOT the reference on the planted cells (so the fixture does hold them)
+    product = np.float32(np.float64(dem) * (100.0 / px))
+    assert ((product != slope) & (fdr == 16)).sum() >= 12
+    dem = g["long_dem"]
+    for j in (0, 1):
+        px, sel = float(g["long_px%d" % j]), g["long_sel%d" % j]
+        assert np.array_equal(oracle.slope_d8(dem, px)[1], g["long_fdr%d" % j])
+        down = oracle.downslope(dem, g["long_fdr%d" % j], px, 5.0).reshape(-1)[sel]
+        assert np.array_equal(down, g["long_down%d" % j])
+        # ... and the count form of the path length is not, on the cells picked for that (all cardinal: nd = 0)
+        x = sel % dem.shape[1]
+        row = dem.reshape(-1)
+        count = np.empty(len(sel), np.float32)
+        for i, (s, x0) in enumerate(zip(sel, x)):
+            n = 0
+            while np.float32(row[s] - row[s + n]) < 5.0 and x0 + n < dem.shape[1] - 1 and row[s + n + 1] != -100.0:
+                n += 1
+            count[i] = np.float32(np.float64(np.float32(row[s] - row[s + n])) / (px * n)) if n else 0.0
+        assert (count != down).sum() >= min(8, int(g["long_divergent%d" % j]))
