@@ -612,6 +612,83 @@ extern "C" int dt_dev_upslope_length(dt_ctx *c, const uint8_t *fdr, const float 
   return DT_OK;
 }
 
+// D-infinity: flat indices travel in 32 bits and the kernels' coordinates in int, so fewer than 2^31 cells
+extern "C" int dt_dev_dinf_direction(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
+                                     float *angle, float *slope) {
+  DT_CTX(c);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_REQUIRE((dem && angle) || H * W == 0, "NULL raster");
+  if (H * W == 0) return DT_OK;
+  DT_TRY(dt_launch_dinf_direction(c->stream, dem, fdr, H, W, px, angle, slope));
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
+// the per-lane stack of k_di_flow: dt_debug_set(DT_DBG_DINF_STACK, n), else the environment variable of that name
+static int dt_dinf_stack_cap() {
+  const int v = dt_debug_get(DT_DBG_DINF_STACK);
+  if (v != 0) return v;
+  static int env = -1;
+  if (env < 0) {
+    const char *e = getenv("DT_DBG_DINF_STACK");
+    env = e ? atoi(e) : 0;
+    if (env < 0) env = 0;
+  }
+  return env;
+}
+#define DT_DINF_ROUNDS_MAX 4096
+extern "C" int dt_dev_dinf_accumulate(dt_ctx *c, const float *angle, const double *w, int64_t H, int64_t W,
+                                      int frac_bits, int rounds, double *acc) {
+  DT_CTX(c);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_REQUIRE((angle && acc) || H * W == 0, "NULL raster");
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  DT_REQUIRE(rounds != 0 && rounds >= -DT_DINF_ROUNDS_MAX && rounds <= DT_DINF_ROUNDS_MAX,
+             "rounds must lie in [1, 4096] (or [-4096, -1] to continue)");
+  if (H * W == 0) return DT_OK;
+  const size_t need = dt_dinf_accumulate_scratch(H, W);
+  if (rounds > 0) {
+    DT_TRY(dt_scratch_reset(c, need));
+    void *scr = dt_scratch_take(c, need);
+    DT_TRY(dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, 1, rounds - 1, 1, dt_dinf_stack_cap(), scr,
+                                     need, acc, c->status));
+    c->scratch_owner = 3;
+    c->owner_h = H;
+    c->owner_w = W;
+    c->owner_ptr = (char *)scr;
+    c->owner_in[0] = angle;
+    c->owner_in[1] = w;
+    c->owner_frac = frac_bits;
+  } else {
+    DT_REQUIRE(c->scratch && c->scratch_owner == 3 && c->owner_h == H && c->owner_w == W,
+               "dt_dev_dinf_accumulate cannot continue: no accumulation of this shape was started on this context (or "
+               "another call has used the context's scratch in between)");
+    DT_REQUIRE(c->owner_in[0] == angle && c->owner_in[1] == w && c->owner_frac == frac_bits,
+               "dt_dev_dinf_accumulate continues with another angle raster, weight raster or frac_bits than it was "
+               "started with");
+    DT_TRY(dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, 0, -rounds, 1, dt_dinf_stack_cap(),
+                                     c->owner_ptr, need, acc, c->status));
+  }
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
+
+extern "C" int dt_dev_dinf_accumulate_info(dt_ctx *c, int64_t *info4) {
+  DT_CTX(c);
+  DT_REQUIRE(info4 != nullptr, "info4 is NULL");
+  DT_REQUIRE(c->scratch && c->scratch_owner == 3,
+             "no D-infinity accumulation on this context (or another call has used the context's scratch since)");
+  uint32_t ctl[8];
+  DT_HIP(hipMemcpyAsync(ctl, dt_dinf_accumulate_ctl(c->owner_ptr, c->owner_h, c->owner_w), sizeof(ctl),
+                        hipMemcpyDeviceToHost, c->stream));
+  DT_HIP(hipStreamSynchronize(c->stream));
+  info4[0] = ctl[3];
+  info4[1] = ctl[4];
+  info4[2] = ctl[0];
+  info4[3] = ctl[5];
+  return DT_OK;
+}
+
 // reaches: reach ids and flat indices travel in 31 bits
 static int dt_check_reach_count(int64_t R) {
   DT_REQUIRE(R >= 0 && R < (1ll << 31), "the number of reaches must lie in [0, 2^31)");
@@ -2024,6 +2101,66 @@ extern "C" int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H
   const float *d_dem = hc.in(dem, n);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_upslope_length(hc.c, d_f, d_dem, H, W, px, d_l));
+  return hc.finish();
+}
+
+extern "C" int dt_dinf_direction(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px, float *angle,
+                                 float *slope) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem && angle, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  const uint8_t *d_f = hc.in(fdr, n);
+  float *d_a = hc.out(angle, n);
+  float *d_s = hc.out(slope, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_dinf_direction(hc.c, d_dem, d_f, H, W, px, d_a, d_s));
+  return hc.finish();
+}
+
+// queue rounds between two looks at the queue
+#define DT_DINF_BATCH 32
+extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H, int64_t W, int frac_bits,
+                                  double *acc, int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(angle && acc, "NULL raster");
+  const float *d_a = hc.in(angle, n);
+  const double *d_w = hc.in(w, n);
+  double *d_o = hc.out(acc, n);
+  const size_t need = dt_dinf_accumulate_scratch(H, W);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  const int cap = dt_dinf_stack_cap();
+  uint32_t ctl[8] = {0};
+  for (int start = 1;; start = 0) {
+    DT_TRY(dt_launch_dinf_accumulate(hc.c->stream, d_a, d_w, H, W, frac_bits, start, DT_DINF_BATCH, 0, cap, scr, need,
+                                     d_o, hc.c->status));
+    DT_TRY(hc.download(ctl, dt_dinf_accumulate_ctl(scr, H, W), 8));
+    DT_HIP(hipStreamSynchronize(hc.c->stream));
+    if (ctl[0] == ctl[2]) break;  // everything queued has been drained
+  }
+  DT_TRY(dt_launch_dinf_accumulate(hc.c->stream, d_a, d_w, H, W, frac_bits, 0, 0, 1, cap, scr, need, d_o, hc.c->status));
+  DT_HIP(hipGetLastError());
+  DT_TRY(dt_ctx_status(hc.c, &st));
+  DT_REQUIRE(!(st & DT_STATUS_BAD_ANGLE), "an angle is neither -1, -100 nor in [0, float32(2 pi)]");
+  DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
+  if (info4) {
+    info4[0] = ctl[3];
+    info4[1] = ctl[4];
+    info4[2] = ctl[0];
+    info4[3] = ctl[5];
+  }
   return hc.finish();
 }
 

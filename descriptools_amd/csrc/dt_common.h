@@ -37,7 +37,7 @@ void dt_set_error(const char *fmt, ...);
   } while (0)
 
 // ---- test / experiment knobs (dt_debug_set in the C ABI; all 0 by default) -------------------------
-enum { DT_DBG_TWI_FLAG_ALL = 0, DT_DBG_TWI_PLAIN = 1, DT_DBG_TWI_WX = 2, DT_DBG_TWI_MAP = 3, DT_DBG_DS_MARGIN = 4, DT_DBG_NO_FUSED_FA_FH = 5, DT_DBG_HY_FILL_SWEEPS = 6, DT_DBG_HY_FLAT_SWEEPS = 7, DT_DBG_HY_COLOUR_MIN = 8 /* tiles from which the conditioning rounds are coloured (0: the default; tests) */, DT_DBG_FA_SCATTER = 9 /* flow accumulation: the scatter form of the perimeter graph (A/B) */, DT_DBG_RC_SLOTS = 10 /* reach tables: n > 0 caps the LDS table at n slots (tests), -1 = no LDS table, one global atomic per cell (A/B) */, DT_DBG_COUNT = 11 };
+enum { DT_DBG_TWI_FLAG_ALL = 0, DT_DBG_TWI_PLAIN = 1, DT_DBG_TWI_WX = 2, DT_DBG_TWI_MAP = 3, DT_DBG_DS_MARGIN = 4, DT_DBG_NO_FUSED_FA_FH = 5, DT_DBG_HY_FILL_SWEEPS = 6, DT_DBG_HY_FLAT_SWEEPS = 7, DT_DBG_HY_COLOUR_MIN = 8 /* tiles from which the conditioning rounds are coloured (0: the default; tests) */, DT_DBG_FA_SCATTER = 9 /* flow accumulation: the scatter form of the perimeter graph (A/B) */, DT_DBG_RC_SLOTS = 10 /* reach tables: n > 0 caps the LDS table at n slots (tests), -1 = no LDS table, one global atomic per cell (A/B) */, DT_DBG_DINF_STACK = 11 /* D-infinity accumulation: n > 0: a lane holds at most n complete cells, the one it carries on with included (1: no stack), so that the spill queue and its rounds run (tests); the environment variable DT_DBG_DINF_STACK sets it too */, DT_DBG_COUNT = 12 };
 #define DT_TWI_WX_DEFAULT 1 /* tile geometry of the fused slope + TI + MTI stencil: see k_slope_twi */
 int dt_debug_get(int key);
 
@@ -49,10 +49,12 @@ struct dt_ctx {
   char *scratch;
   size_t scratch_bytes;
   size_t scratch_used;  // bump pointer, reset at the start of every entry point
-  int scratch_owner;    // which two-phase op's state lives in `scratch` (0 none, 1 flow accumulation, 2 HAND):
+  int scratch_owner;    // which multi-call op's state lives in `scratch` (0 none, 1 flow accumulation, 2 HAND, 3 D-inf):
   int64_t owner_h, owner_w;  // set by *_local_w, cleared by every dt_scratch_reset, required by *_finish_w
   char *owner_ptr;      // where in `scratch` that state starts (HAND's follows flow accumulation's when phase 2 of the
   char *owner_ptr2;     // one and phase 1 of the other are fused: owner_ptr2 = HAND's region reserved beside it)
+  const void *owner_in[2];  // D-inf: the angle and weight rasters the accumulation in `scratch` was started on,
+  int owner_frac;           // and its frac_bits: a continuation must name the same
   char *scratch2;       // rank-level solves (must not disturb the two-phase tile scratch)
   size_t scratch2_bytes;
   hipEvent_t ev;        // fork / join with another context's stream (created on first use)

@@ -1,0 +1,520 @@
+// dt_dinf.hip -- D-infinity flow direction and contributing area (Tarboton 1997; net-new, descriptools_amd/dinf.py
+// holds the definition).
+//
+// Direction (k_dinf): a 3 x 3 stencil on an LDS tile of 128 x 8 cells with a one-cell halo, four cells per lane.  The
+// eight triangular facets are evaluated in float64 on the float32 heights; the facet of steepest descent is chosen on
+// its slope alone (strict >, the first facet wins a tie), so the one atan2 of a cell is taken after the choice, on the
+// winning facet.  A neighbour takes part when it is finite and > -100; everything outside the raster is staged as
+// -100.  A valid centre without a winning facet takes the caller's D8 code (when that neighbour is valid) or -1.
+//
+// Accumulation: the drainage graph is a DAG of out-degree <= 2, so the tile passes' pointer doubling (a tree) cannot
+// carry it.  One 64-bit word per cell is the whole state,
+//   bits 0-55 sum (q, then q + what has arrived) | 56-59 pending donors | 60 source | 61, 62 the edge to the first /
+//   second receiver exists (the receiver lies in the raster and is not nodata)
+// k_di_init   gathers each cell's in-degree from the eight neighbours' angles (LDS tile of angles, no atomics),
+//             quantises the weight and writes the word.
+// k_di_flow   the in-degree countdown on the DAG.  A lane that owns a complete cell (pending 0) splits its total T,
+//             m2 = floor(T * P2 / 2^30) to the second receiver and T - m2 to the first, and adds m - 2^56 to each
+//             receiver's word with one returning 64-bit atomic: sum and countdown move together, the arrival that
+//             finds pending == 1 in the value it gets back holds the receiver's complete total, and no fence is
+//             needed (cdna_hip_programming.md Guideline 16: the word is the only thing handed over).  That lane
+//             carries on from the receiver it completed; when it completes both it keeps one and puts the other on a
+//             stack of DI_STACK cells in LDS, and when that is full on a global queue.  Round 0 starts from the
+//             sources (a scan of the raster); every later round drains what the rounds before put on the queue
+//             (k_di_mark moves the window [lo, hi) to the entries written before it ran); a round whose window is
+//             empty returns at once.  A start walks at most DI_MOVES cells in a round and then queues what it holds:
+//             a round lasts as long as its longest walk, and while one lane follows a channel of tens of thousands
+//             of cells everything queued behind it would wait -- bounded walks keep the rounds short (a few hundred
+//             dependent atomics) and the queued work moving.  No lane waits for another, and a lane's storage does
+//             not grow with its path.  A cell is queued only when it is complete and not yet sent on, which happens
+//             once: a queue of N entries cannot overflow.
+// k_di_out    ldexp(T - q, -s) as float64; -100 on nodata and where pending != 0 (on or below a cycle, or -- on the
+//             device tier -- not reached within the budget of rounds, which raises DT_STATUS_NOT_CONVERGED).
+// Integer sums are order-free and the split is a function of the complete T alone, so the result does not depend on
+// the order of arrival, the stack size or the number of rounds.
+#include <cmath>
+
+#include "dt_kernels.h"
+
+#define DI_TX 128
+#define DI_TY 8
+#define DI_LDW (DI_TX + 8)  // LDS row stride in floats; the interior starts at column 4
+#define DI_PI 3.141592653589793
+#define DI_4_OVER_PI 1.2732395447351628  // the float64 nearest 4 / pi
+#define DI_F2PI 6.2831854820251465f      // float32(2 pi)
+
+#define DI_SUM_MASK ((1ull << 56) - 1ull)
+#define DI_ONE_PEND (1ull << 56)
+#define DI_F_SRC (1ull << 60)
+#define DI_F_E0 (1ull << 61)
+#define DI_F_E1 (1ull << 62)
+#define DI_NONE 0xFFFFFFFFu
+#define DI_MOVES 128  // cells one start (a source, a queue entry) may complete in a round before it hands on
+
+// dy / dx of octant k (angle k pi / 4 counter-clockwise from east, rows grow to the south), packed as DT_PK8 packs
+#define DI_DX_PACK DT_PK8(1, 1, 0, -1, -1, -1, 0, 1)
+#define DI_DY_PACK DT_PK8(0, -1, -1, -1, 0, 1, 1, 1)
+
+// finite and > -100 (false for NaN)
+__device__ __forceinline__ bool di_valid(float v) { return v > -100.0f && v < INFINITY; }
+
+// stage (DI_TY + 2) x (DI_TX + 2) cells of src around the tile at (y0, x0); `fill` outside the raster.  The caller
+// synchronises.
+__device__ __forceinline__ void di_stage(float *t, const float *__restrict__ src, int H, int W, int x0, int y0,
+                                         int vec_ok, float fill) {
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    const int i = (int)threadIdx.x + 256 * u;
+    if (i < (DI_TY + 2) * (DI_TX / 4)) {
+      const int r = i / (DI_TX / 4), c4 = i - r * (DI_TX / 4);
+      const int gy = y0 - 1 + r, gx = x0 + c4 * 4;
+      float4 v = make_float4(fill, fill, fill, fill);
+      if (gy >= 0 && gy < H) {
+        const float *p = src + (long long)gy * W + gx;
+        if (vec_ok && gx + 3 < W) {
+          v = *reinterpret_cast<const float4 *>(p);
+        } else {
+          if (gx < W) v.x = p[0];
+          if (gx + 1 < W) v.y = p[1];
+          if (gx + 2 < W) v.z = p[2];
+          if (gx + 3 < W) v.w = p[3];
+        }
+      }
+      *reinterpret_cast<float4 *>(&t[r * DI_LDW + 4 + c4 * 4]) = v;
+    }
+  }
+  if (threadIdx.x < (DI_TY + 2) * 2) {
+    const int r = (int)threadIdx.x >> 1, side = (int)threadIdx.x & 1;
+    const int gy = y0 - 1 + r, gx = side ? x0 + DI_TX : x0 - 1;
+    float v = fill;
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = src[(long long)gy * W + gx];
+    t[r * DI_LDW + (side ? 4 + DI_TX : 3)] = v;
+  }
+}
+
+// the eight neighbours of the lane's cell k (0..3) by octant, from its three rows of six staged values
+__device__ __forceinline__ void di_octants(const float (&a)[6], const float (&b)[6], const float (&c)[6], int k,
+                                           float (&n)[8]) {
+  n[0] = b[k + 2];
+  n[1] = a[k + 2];
+  n[2] = a[k + 1];
+  n[3] = a[k];
+  n[4] = b[k];
+  n[5] = c[k];
+  n[6] = c[k + 1];
+  n[7] = c[k + 2];
+}
+
+__device__ __forceinline__ void di_load_row(const float *t, int lr, int cx, float (&dst)[6]) {
+  const float *row = &t[lr * DI_LDW];
+  const float4 m = *reinterpret_cast<const float4 *>(row + 4 + cx);
+  dst[0] = row[3 + cx];
+  dst[1] = m.x;
+  dst[2] = m.y;
+  dst[3] = m.z;
+  dst[4] = m.w;
+  dst[5] = row[8 + cx];
+}
+
+// ---- direction -----------------------------------------------------------------------------------------------------
+// one cell: e0 and its neighbours by octant; code = the caller's D8 code (0 without one)
+__device__ __forceinline__ void di_cell(float c, const float (&n)[8], double px, double pxd, uint32_t code,
+                                        float &angle, float &slope) {
+  if (c <= DT_NODATA) {
+    angle = DT_NODATA;
+    slope = DT_NODATA;
+    return;
+  }
+  angle = -1.0f;
+  slope = 0.0f;
+  if (!di_valid(c)) return;  // NaN, +inf: no flow
+  const double e0 = (double)c;
+  double best = 0.0, bs1 = 0.0, bs2 = 0.0;
+  int bf = -1, bmode = 0;
+#pragma unroll
+  for (int f = 0; f < 8; f++) {
+    const int o1 = ((f + 1) >> 1 << 1) & 7;  // E N N W W S S E
+    const int o2 = f | 1;                    // NE NE NW NW SW SW SE SE
+    if (!(di_valid(n[o1]) && di_valid(n[o2]))) continue;
+    const double e1 = (double)n[o1], e2 = (double)n[o2];
+    const double s1 = (e0 - e1) / px, s2 = (e1 - e2) / px;
+    double s;
+    int mode;
+    if (s2 < 0.0) {
+      s = s1;
+      mode = 0;
+    } else if (s2 > s1) {
+      s = (e0 - e2) / pxd;
+      mode = 1;
+    } else {
+      s = sqrt(s1 * s1 + s2 * s2);
+      mode = 2;
+    }
+    if (s > best) {
+      best = s;
+      bf = f;
+      bs1 = s1;
+      bs2 = s2;
+      bmode = mode;
+    }
+  }
+  if (bf >= 0) {
+    const double r = bmode == 0 ? 0.0 : (bmode == 1 ? DI_PI / 4 : atan2(bs2, bs1));
+    const double af = (bf & 1) ? -1.0 : 1.0, ac = (double)((bf + 1) >> 1);
+    double a64 = af * r + ac * (DI_PI / 2);
+    if (a64 >= 2 * DI_PI) a64 -= 2 * DI_PI;
+    float a32 = (float)a64;
+    if (a32 >= DI_F2PI) a32 = 0.0f;
+    angle = a32;
+    slope = (float)best;
+    return;
+  }
+  if (dt_d8_valid(code)) {  // a pit, a flat or an edge cell: the caller's D8 code, when it points at a valid cell
+    const int k = (8 - (__ffs((int)code) - 1)) & 7;
+    if (di_valid(n[k])) angle = (float)((double)k * (DI_PI / 4));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_dinf(const float *__restrict__ dem, const uint8_t *__restrict__ fdr, int H,
+                                              int W, int tiles_x, int vec_ok, double px, double pxd,
+                                              float *__restrict__ angle, float *__restrict__ slope) {
+  __shared__ __attribute__((aligned(16))) float t[(DI_TY + 2) * DI_LDW];
+  const int tyi = (int)blockIdx.x / tiles_x, txi = (int)blockIdx.x - tyi * tiles_x;
+  const int x0 = txi * DI_TX, y0 = tyi * DI_TY;
+  di_stage(t, dem, H, W, x0, y0, vec_ok, DT_NODATA);
+  __syncthreads();
+  const int cx = ((int)threadIdx.x & 31) * 4, ly = (int)threadIdx.x >> 5;
+  const int gy = y0 + ly, gx = x0 + cx;
+  if (gy >= H || gx >= W) return;
+  float a[6], b[6], c[6];
+  di_load_row(t, ly, cx, a);
+  di_load_row(t, ly + 1, cx, b);
+  di_load_row(t, ly + 2, cx, c);
+  const long long o = (long long)gy * W + gx;
+  const bool full = vec_ok && gx + 3 < W;
+  uint32_t codes = 0u;
+  if (fdr) {
+    if (full) {
+      codes = *reinterpret_cast<const uint32_t *>(fdr + o);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (gx + k < W) codes |= (uint32_t)fdr[o + k] << (8 * k);
+    }
+  }
+  float ao[4], so[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    float n[8];
+    di_octants(a, b, c, k, n);
+    di_cell(b[k + 1], n, px, pxd, (codes >> (8 * k)) & 0xFFu, ao[k], so[k]);
+  }
+  if (full) {
+    *reinterpret_cast<float4 *>(angle + o) = make_float4(ao[0], ao[1], ao[2], ao[3]);
+    if (slope) *reinterpret_cast<float4 *>(slope + o) = make_float4(so[0], so[1], so[2], so[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (gx + k < W) {
+        angle[o + k] = ao[k];
+        if (slope) slope[o + k] = so[k];
+      }
+    }
+  }
+}
+
+// ---- accumulation --------------------------------------------------------------------------------------------------
+// control words of one accumulation
+enum { DI_C_TAIL = 0, DI_C_LO = 1, DI_C_HI = 2, DI_C_ROUNDS = 3, DI_C_HIGH = 4, DI_C_TWO = 5, DI_C_WORDS = 8 };
+
+// an angle as receivers: kind 0 none (-1, nodata, or a value outside the contract: bad), 1 one receiver (octant k),
+// 2 two (octant k with share 2^30 - p2, octant k + 1 with share p2)
+struct DiDec {
+  int kind, k;
+  uint32_t p2;
+};
+__device__ __forceinline__ DiDec di_decode(float a, bool &bad) {
+  DiDec d = {0, 0, 0u};
+  if (a == -1.0f || a == DT_NODATA) return d;
+  if (!(a >= 0.0f && a <= DI_F2PI)) {  // NaN, another negative, beyond float32(2 pi)
+    bad = true;
+    return d;
+  }
+  const double t = (double)a * DI_4_OVER_PI;
+  const double rt = rint(t);
+  if (fabs(t - rt) <= 0x1p-20) {
+    d.kind = 1;
+    d.k = (int)rt & 7;
+  } else {
+    const double fl = floor(t);
+    d.kind = 2;
+    d.k = (int)fl & 7;
+    d.p2 = (uint32_t)rint((t - fl) * 0x1p30);
+  }
+  return d;
+}
+
+// q = rint(w * 2^s), flowacc_weighted's rule: a weight outside the contract is bad and counts as 0
+__device__ __forceinline__ unsigned long long di_quant(const double *__restrict__ wt, long long c, int sbits,
+                                                       unsigned long long qmax, bool &bad) {
+  const double v = wt ? wt[c] : 1.0;
+  if (!(v >= 0.0)) {
+    bad = true;
+    return 0ull;
+  }
+  const double q = rint(ldexp(v, sbits));
+  if (!(q <= (double)qmax)) {
+    bad = true;
+    return 0ull;
+  }
+  return (unsigned long long)q;
+}
+
+__global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle, const double *__restrict__ wt, int H,
+                                                 int W, int tiles_x, int vec_ok, int sbits, unsigned long long qmax,
+                                                 unsigned long long *__restrict__ word, uint32_t *__restrict__ ctl,
+                                                 int *__restrict__ status) {
+  __shared__ __attribute__((aligned(16))) float t[(DI_TY + 2) * DI_LDW];
+  const int tyi = (int)blockIdx.x / tiles_x, txi = (int)blockIdx.x - tyi * tiles_x;
+  const int x0 = txi * DI_TX, y0 = tyi * DI_TY;
+  di_stage(t, angle, H, W, x0, y0, vec_ok, DT_NODATA);
+  __syncthreads();
+  const int cx = ((int)threadIdx.x & 31) * 4, ly = (int)threadIdx.x >> 5;
+  const int gy = y0 + ly, gx = x0 + cx;
+  bool bad_a = false, bad_w = false;
+  uint32_t two = 0u;
+  if (gy < H && gx < W) {
+    float a[6], b[6], c[6];
+    di_load_row(t, ly, cx, a);
+    di_load_row(t, ly + 1, cx, b);
+    di_load_row(t, ly + 2, cx, c);
+    const long long o = (long long)gy * W + gx;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (gx + k >= W) continue;
+      float n[8];
+      di_octants(a, b, c, k, n);
+      const float me = b[k + 1];
+      unsigned long long wv = 0ull;
+      if (me != DT_NODATA) {
+        bool ignore = false;  // a neighbour's bad angle is reported where it is the centre
+        uint32_t pending = 0u;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          const DiDec d = di_decode(n[j], ignore);
+          const int back = (j + 4) & 7;  // this cell as the neighbour sees it
+          pending += (d.kind >= 1 && d.k == back) || (d.kind == 2 && ((d.k + 1) & 7) == back) ? 1u : 0u;
+        }
+        const DiDec d = di_decode(me, bad_a);
+        wv = di_quant(wt, o + k, sbits, qmax, bad_w) | ((unsigned long long)pending << 56);
+        if (pending == 0u) wv |= DI_F_SRC;
+        if (d.kind >= 1 && n[d.k] != DT_NODATA) wv |= DI_F_E0;
+        if (d.kind == 2 && n[(d.k + 1) & 7] != DT_NODATA) wv |= DI_F_E1;
+        two += d.kind == 2 ? 1u : 0u;
+      }
+      word[o + k] = wv;
+    }
+  }
+  if (status && (bad_a || bad_w))
+    atomicOr(status, (bad_a ? DT_STATUS_BAD_ANGLE : 0) | (bad_w ? DT_STATUS_BAD_WEIGHT : 0));
+  if (two) atomicAdd(&ctl[DI_C_TWO], two);
+}
+
+// the window of the next queue round: what was queued before this kernel ran and has not been drained
+__global__ void k_di_mark(uint32_t *ctl) {
+  const uint32_t lo = ctl[DI_C_HI], hi = ctl[DI_C_TAIL];
+  ctl[DI_C_LO] = lo;
+  ctl[DI_C_HI] = hi;
+  if (hi > lo) {
+    ctl[DI_C_ROUNDS] += 1u;
+    if (hi - lo > ctl[DI_C_HIGH]) ctl[DI_C_HIGH] = hi - lo;
+  }
+}
+
+// floor(T * p2 / 2^30), T < 2^56, p2 < 2^30: the 86-bit product held exactly in two words
+__device__ __forceinline__ unsigned long long di_share(unsigned long long T, uint32_t p2) {
+  const unsigned long long lo = T * (unsigned long long)p2, hi = __umul64hi(T, (unsigned long long)p2);
+  return (hi << 34) | (lo >> 30);
+}
+
+template <bool SCAN>
+__global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle, unsigned long long *word, int H,
+                                                 int W, uint32_t *queue, uint32_t *ctl, int cap, int moves_max) {
+  __shared__ uint32_t s_stack[DI_STACK * 256];
+  const uint32_t lo = SCAN ? 0u : ctl[DI_C_LO], hi = SCAN ? (uint32_t)((long long)H * W) : ctl[DI_C_HI];
+  for (unsigned long long i = (unsigned long long)lo + (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < hi;
+       i += (unsigned long long)gridDim.x * 256ull) {
+    uint32_t c;
+    unsigned long long wv;
+    if (SCAN) {
+      c = (uint32_t)i;
+      wv = word[c];  // a source's word receives nothing; the flag bits of any word never change
+      if (!(wv & DI_F_SRC)) continue;
+    } else {
+      c = queue[i];
+      wv = __hip_atomic_load(&word[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    float ac = angle[c];
+    int sp = 0;
+    for (int moves = 0;;) {  // c is complete, wv is its word and ac its angle
+      uint32_t next = DI_NONE;
+      unsigned long long nextw = 0ull;
+      float nexta = 0.0f;
+      if (wv & (DI_F_E0 | DI_F_E1)) {
+        const unsigned long long T = wv & DI_SUM_MASK;
+        bool ignore = false;
+        const DiDec d = di_decode(ac, ignore);
+        const unsigned long long m2 = d.kind == 2 ? di_share(T, d.p2) : 0ull;
+        const unsigned long long m1 = T - m2;
+        // the receivers' angles are asked for beside the atomics, not after the one that completes a receiver: a
+        // move then costs one memory round trip, not two in a row
+        uint32_t rr[2];
+        float ra[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+          const int k = (d.k + e) & 7;
+          const int dx = (int)((DI_DX_PACK >> (2 * k)) & 3u) - 1, dy = (int)((DI_DY_PACK >> (2 * k)) & 3u) - 1;
+          rr[e] = (uint32_t)((long long)c + (long long)dy * W + dx);
+          ra[e] = (wv & (e ? DI_F_E1 : DI_F_E0)) ? angle[rr[e]] : 0.0f;
+        }
+        // both atomics are in flight before either answer is looked at
+        unsigned long long add[2], old[2] = {0ull, 0ull};
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+          add[e] = (e ? m2 : m1) - DI_ONE_PEND;
+          if (wv & (e ? DI_F_E1 : DI_F_E0)) old[e] = atomicAdd(&word[rr[e]], add[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+          if (((old[e] >> 56) & 0xFull) != 1ull) continue;  // no edge, or donors of the receiver are still to come
+          const uint32_t r = rr[e];
+          if (next == DI_NONE) {
+            next = r;
+            nextw = old[e] + add[e];
+            nexta = ra[e];
+          } else if (sp < cap) {
+            s_stack[sp++ * 256 + threadIdx.x] = r;
+          } else {
+            queue[atomicAdd(&ctl[DI_C_TAIL], 1u)] = r;
+          }
+        }
+      }
+      if (++moves >= moves_max) {  // this entry's share of the round is used up: the next round carries on
+        if (next != DI_NONE) queue[atomicAdd(&ctl[DI_C_TAIL], 1u)] = next;
+        while (sp > 0) queue[atomicAdd(&ctl[DI_C_TAIL], 1u)] = s_stack[--sp * 256 + threadIdx.x];
+        break;
+      }
+      if (next != DI_NONE) {
+        c = next;
+        wv = nextw;
+        ac = nexta;
+      } else if (sp > 0) {
+        c = s_stack[--sp * 256 + threadIdx.x];
+        wv = __hip_atomic_load(&word[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ac = angle[c];
+      } else {
+        break;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_di_out(const float *__restrict__ angle, const double *__restrict__ wt,
+                                                const unsigned long long *__restrict__ word, long long N, int sbits,
+                                                unsigned long long qmax, const uint32_t *__restrict__ ctl,
+                                                double *__restrict__ out, int *__restrict__ status) {
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c == 0 && status && ctl[DI_C_TAIL] != ctl[DI_C_HI]) atomicOr(status, DT_STATUS_NOT_CONVERGED);
+  if (c >= N) return;
+  const unsigned long long wv = word[c];
+  double v = -100.0;
+  if (angle[c] != DT_NODATA && ((wv >> 56) & 0xFull) == 0ull) {
+    bool ignore = false;
+    const unsigned long long q = di_quant(wt, c, sbits, qmax, ignore);
+    v = ldexp((double)(long long)((wv & DI_SUM_MASK) - q), -sbits);
+  }
+  out[c] = v;
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------
+struct DiLayout {
+  uint32_t *ctl;
+  unsigned long long *word;
+  uint32_t *queue;
+  size_t bytes;
+};
+static DiLayout di_layout(int64_t N, char *p) {
+  DiLayout L = {};
+  size_t off = 0;
+  auto take = [&](size_t b) {
+    char *q = p ? p + off : nullptr;
+    off += dt_align256(b);
+    return q;
+  };
+  L.ctl = (uint32_t *)take(sizeof(uint32_t) * DI_C_WORDS);
+  L.word = (unsigned long long *)take((size_t)N * 8);
+  L.queue = (uint32_t *)take((size_t)N * 4);
+  L.bytes = off;
+  return L;
+}
+size_t dt_dinf_accumulate_scratch(int64_t H, int64_t W) { return di_layout(H * W, nullptr).bytes; }
+
+static int di_vec_ok(const void *p, int64_t W) { return W % 4 == 0 && ((uintptr_t)p & 15u) == 0; }
+static unsigned di_tiles(int64_t H, int64_t W, int &tiles_x) {
+  tiles_x = (int)((W + DI_TX - 1) / DI_TX);
+  return (unsigned)(((H + DI_TY - 1) / DI_TY) * tiles_x);
+}
+
+int dt_launch_dinf_direction(hipStream_t s, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
+                             float *angle, float *slope) {
+  if (H == 0 || W == 0) return DT_OK;
+  int tiles_x;
+  const unsigned nt = di_tiles(H, W, tiles_x);
+  const int vec_ok = di_vec_ok(dem, W) && di_vec_ok(angle, W) && (!slope || di_vec_ok(slope, W)) &&
+                     (!fdr || ((uintptr_t)fdr & 3u) == 0);
+  hipLaunchKernelGGL(k_dinf, dim3(nt), dim3(256), 0, s, dem, fdr, (int)H, (int)W, tiles_x, vec_ok, px,
+                     px * std::sqrt(2.0), angle, slope);
+  return DT_OK;
+}
+
+static dim3 di_queue_grid(int64_t N) {
+  const int64_t want = (N + 255) / 256;
+  return dim3((unsigned)(want < 2048 ? want : 2048));
+}
+
+// start != 0: the set-up and round 0 first; then `rounds` queue rounds; finish != 0: k_di_out
+int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *wt, int64_t H, int64_t W, int frac_bits,
+                              int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
+                              double *out, int *status) {
+  if (H == 0 || W == 0) return DT_OK;
+  const int64_t N = H * W;
+  DiLayout L = di_layout(N, (char *)scratch);
+  DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
+  const unsigned long long qmax = (1ull << 52) / (unsigned long long)N;
+  const int cap = stack_cap > 0 && stack_cap - 1 < DI_STACK ? stack_cap - 1 : DI_STACK;  // cells on the stack
+  const dim3 b(256);
+  if (start) {
+    DT_HIP(hipMemsetAsync(L.ctl, 0, sizeof(uint32_t) * DI_C_WORDS, s));
+    int tiles_x;
+    const unsigned nt = di_tiles(H, W, tiles_x);
+    hipLaunchKernelGGL(k_di_init, dim3(nt), b, 0, s, angle, wt, (int)H, (int)W, tiles_x, di_vec_ok(angle, W), frac_bits,
+                       qmax, L.word, L.ctl, status);
+    hipLaunchKernelGGL(k_di_flow<true>, dim3((unsigned)((N + 255) / 256)), b, 0, s, angle, L.word, (int)H, (int)W,
+                       L.queue, L.ctl, cap, DI_MOVES);
+  }
+  const dim3 gq = di_queue_grid(N);
+  for (int r = 0; r < rounds; r++) {
+    hipLaunchKernelGGL(k_di_mark, dim3(1), dim3(1), 0, s, L.ctl);
+    hipLaunchKernelGGL(k_di_flow<false>, gq, b, 0, s, angle, L.word, (int)H, (int)W, L.queue, L.ctl, cap, DI_MOVES);
+  }
+  if (finish)
+    hipLaunchKernelGGL(k_di_out, dim3((unsigned)((N + 255) / 256)), b, 0, s, angle, wt, L.word, (long long)N, frac_bits,
+                       qmax, L.ctl, out, status);
+  return DT_OK;
+}
+
+// the control words of the accumulation in `scratch` (device pointer to DI_C_WORDS uint32: tail, lo, hi, queue rounds
+// that found work, the largest window, two-receiver cells)
+const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W) {
+  return di_layout(H * W, (char *)scratch).ctl;
+}

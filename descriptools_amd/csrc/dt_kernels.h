@@ -218,3 +218,20 @@ int dt_launch_reach_tables(hipStream_t s, const int32_t *catch_, const void *han
                            int slots);
 int dt_launch_inundate(hipStream_t s, const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
                        int64_t N, int64_t R, float *depth);
+
+// D-infinity (dt_dinf.hip): flow angle / slope on the eight triangular facets (fdr, slope may be NULL), and the
+// contributing area of an angle raster (wt may be NULL: 1 everywhere).  The accumulation keeps its state in `scratch`:
+// start != 0 sets it up and runs round 0 (from the sources), `rounds` queue rounds follow, finish != 0 writes `out`
+// (and raises DT_STATUS_NOT_CONVERGED on `status` when queued work is left).  stack_cap: 0 the default (a lane holds the
+// cell it carries on with and DI_STACK more), n > 0: at most n cells, the one it carries on with included, so 1 sends
+// every second completion to the queue (DT_DBG_DINF_STACK).  Nothing synchronises.  H * W < 2^31.
+int dt_launch_dinf_direction(hipStream_t s, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
+                             float *angle, float *slope);
+#define DI_STACK 8
+size_t dt_dinf_accumulate_scratch(int64_t H, int64_t W);
+int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *wt, int64_t H, int64_t W, int frac_bits,
+                              int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
+                              double *out, int *status);
+// the accumulation's control words in `scratch` (8 x uint32 on the device): queued, window lo, window hi, queue rounds
+// that found work, the largest window, two-receiver cells
+const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W);

@@ -1,0 +1,163 @@
+"""D-infinity flow direction and contributing area (net-new; Tarboton 1997, TauDEM's DinfFlowDir / AreaDinf): a flow
+angle on eight triangular facets, the flow of a cell split between the two neighbours that bracket its angle.
+
+Angle convention.  Radians, counter-clockwise from east; rows grow to the south.  Octant k (0..7) is the neighbour at
+angle k pi / 4: E, NE, N, NW, W, SW, S, SE -- the D8 codes 1, 128, 64, 32, 16, 8, 4, 2.  A height is valid when it is
+finite and > -100; <= -100 is nodata, as everywhere in the package; NaN and +inf are not nodata but take part in no
+facet.
+
+flow_direction.  For a valid centre e0 the facets (e1 cardinal, e2 diagonal, ac, af)
+
+    1 (E, NE, 0, +1)  2 (N, NE, 1, -1)  3 (N, NW, 1, +1)  4 (W, NW, 2, -1)
+    5 (W, SW, 2, +1)  6 (S, SW, 3, -1)  7 (S, SE, 3, +1)  8 (E, SE, 4, -1)
+
+are tried in this order, a facet only when both neighbours lie in the raster and are valid, in float64:
+s1 = (e0 - e1) / px, s2 = (e1 - e2) / px; if s2 < 0: r = 0, s = s1; else if s2 > s1: r = pi / 4,
+s = (e0 - e2) / (px * sqrt(2.0)); else r = atan2(s2, s1), s = sqrt(s1 * s1 + s2 * s2).  The facet with the largest s
+wins (strict >, so the first of equals), and s must be > 0.  angle64 = af * r + ac * (pi / 2), less 2 pi when it is
+>= 2 pi; angle = float32(angle64), 0 when that is >= float32(2 pi); slope = float32(s): drop over distance (TauDEM's
+`slp`), not percent.  A valid centre without a winning facet (a pit, a flat, an edge cell without a complete facet)
+takes, when `fdr` is given, holds one of the eight D8 codes there and that neighbour lies in the raster and is valid,
+angle = float32(k pi / 4) of the code's octant with slope 0; otherwise angle = -1 (no flow), slope = 0.  A NaN or +inf
+centre: angle -1, slope 0.  A nodata centre: angle -100, slope -100.  A decision: -inf satisfies <= -100, so a -inf
+centre is nodata (-100 / -100) like everywhere else in the package (_lib.nodata_mask, the D8 kernels), not a
+non-finite centre; as a neighbour it takes part in no facet either way.  Every receiver with a non-zero share is
+strictly lower than the centre.
+
+accumulate.  An angle a >= 0 is decoded as t = float64(a) * 1.2732395447351628 (the float64 nearest 4 / pi): when
+|t - rint(t)| <= 2^-20 the cell has one receiver, octant rint(t) mod 8 (float32(k pi / 4) does not land on k exactly);
+otherwise k = floor(t), P2 = rint((t - k) * 2^30) and the receivers are octant k mod 8 with share 2^30 - P2 and octant
+(k + 1) mod 8 with share P2.  a = -1: no receiver; a = -100: nodata; anything else (NaN, other negatives, beyond
+float32(2 pi)) is refused.  c -> d is an edge for each receiver d that lies in the raster and is not nodata; a share
+that points off the raster or into nodata leaves the domain; a cell with angle -1 still receives.  The sums are int64
+fixed point as in flowacc.accumulate_weighted: q(c) = rint(w(c) * 2^s), T(c) = q(c) + the shares received; a complete
+c sends m2 = floor(T * P2 / 2^30) (the 82-bit product taken exactly) to octant k + 1 and m1 = T - m2 to octant k, so
+mass is conserved and no T exceeds the sum of q <= 2^52.  result(c) = ldexp(T(c) - q(c), -s): self excluded, as in
+flowacc.accumulate; -100 on nodata and on every cell on or downstream of a cycle (its inflow never completes).  The
+result does not depend on order or run.  On angles float32(k pi / 4) made from a D8 raster it is
+flowacc.accumulate(fdr) exactly (frac_bits=0)."""
+import math
+
+import numpy as np
+
+from . import _lib
+from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, ptr
+from .flowacc import _FRAC_BITS_MAX, _SUM_BITS, _default_frac_bits, _weights_f64
+
+F2PI = np.float32(2.0 * math.pi)
+_CELLS_MAX = 2 ** 31
+
+
+class DinfDirection(tuple):
+    """(angle, slope) of flow_direction, both float32"""
+    __slots__ = ()
+
+    def __new__(cls, angle, slope):
+        return tuple.__new__(cls, (angle, slope))
+
+    angle = property(lambda self: self[0])
+    slope = property(lambda self: self[1])
+
+
+def _raster(a, what):
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("%s must be a 2-D raster, not of shape %s" % (what, a.shape))
+    if a.size >= _CELLS_MAX:
+        raise ValueError("%s has %d cells: rasters of 2^31 cells or more are not supported" % (what, a.size))
+    return a
+
+
+def _px(px):
+    try:
+        p = float(px)
+    except (TypeError, ValueError):
+        raise ValueError("px must be a number, not %r" % (px,))
+    if not (math.isfinite(p) and p > 0.0):
+        raise ValueError("px must be finite and > 0, not %r" % (px,))
+    return p
+
+
+def flow_direction(dem, px, fdr=None):
+    """D-infinity angle and slope of `dem` (float32-exact heights; a DEM that float32 cannot hold raises ValueError, as
+    flowdir.d8 does by default) -> DinfDirection(angle float32, slope float32); the module docstring holds the
+    definition.  `fdr` (optional, D8 codes) routes the cells that have no downslope facet.
+
+    With flowdir.d8_conditioned pass the FILLED surface (return_filled=True) together with its fdr: then every flow is
+    to a lower cell or along the conditioned D8 codes, and the drainage graph has no cycle."""
+    d = _raster(dem, "dem")
+    p = _px(px)
+    f = None
+    if fdr is not None:
+        f = np.asarray(fdr)
+        if f.shape != d.shape:
+            raise ValueError("fdr has shape %s, the DEM %s" % (f.shape, d.shape))
+        f = np.ascontiguousarray(f, np.uint8)
+    d = _lib.dem_f32(d)
+    H, W = d.shape
+    angle = np.empty((H, W), np.float32)
+    slope = np.empty((H, W), np.float32)
+    check(_lib.lib().dt_dinf_direction(ptr(d, c_f32p), ptr(f, c_u8p), H, W, p, ptr(angle, c_f32p), ptr(slope, c_f32p)))
+    return DinfDirection(angle, slope)
+
+
+def _angles_f32(angle):
+    a = _raster(angle, "angle")
+    if a.dtype.kind not in "iuf":
+        raise ValueError("angle must be of a real dtype, not %s" % a.dtype)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    ok = (a == np.float32(-1)) | (a == np.float32(-100)) | ((a >= 0) & (a <= F2PI))
+    if not ok.all():
+        k = int(np.argmin(ok.reshape(-1)))
+        raise ValueError("angle %r at flat index %d is neither -1 (no flow), -100 (nodata) nor in [0, float32(2 pi)]"
+                         % (a.reshape(-1)[k].item(), k))
+    return a
+
+
+def _frac_bits(n, wmax, frac_bits):
+    """flowacc.accumulate_weighted's rule for the fixed-point scale"""
+    if frac_bits is None:
+        return _default_frac_bits(n, wmax) if n else 0
+    if isinstance(frac_bits, (bool, np.bool_)) or not isinstance(frac_bits, (int, np.integer)):
+        raise ValueError("frac_bits must be an integer, not %r" % (frac_bits,))
+    s = int(frac_bits)
+    if not -_FRAC_BITS_MAX <= s <= _FRAC_BITS_MAX:
+        raise ValueError("frac_bits must lie in [%d, %d], not %d" % (-_FRAC_BITS_MAX, _FRAC_BITS_MAX, s))
+    with np.errstate(over="ignore"):
+        qmax = np.rint(np.ldexp(wmax, s))
+    if not np.isfinite(qmax) or n * int(qmax) > 2 ** _SUM_BITS:
+        raise ValueError("frac_bits=%d is too fine for these weights: N * rint(max(weights) * 2^frac_bits) "
+                         "exceeds 2^52 (the default is %d)" % (s, _default_frac_bits(n, wmax)))
+    return s
+
+
+def _accumulate(angle, weights, frac_bits):
+    """-> (acc, w or None, s, info): info = {rounds, queue_high, queued, two_receiver_cells}"""
+    a = _angles_f32(angle)
+    H, W = a.shape
+    n = H * W
+    w = None if weights is None else _weights_f64(weights, a.shape)
+    wmax = 1.0 if w is None else (float(w.max()) if n else 0.0)
+    s = _frac_bits(n, wmax, frac_bits)
+    acc = np.empty((H, W), np.float64)
+    info = np.zeros(4, np.int64)
+    check(_lib.lib().dt_dinf_accumulate(ptr(a, c_f32p), ptr(w, c_f64p), H, W, s, ptr(acc, c_f64p), ptr(info, c_i64p)))
+    return acc, w, s, dict(zip(("rounds", "queue_high", "queued", "two_receiver_cells"), (int(v) for v in info)))
+
+
+def accumulate(angle, weights=None, frac_bits=None):
+    """D-infinity contributing area of an angle raster (flow_direction's, or a TauDEM `ang` grid), self excluded, as
+    float64: the number of upslope cells by share (weights None), or the sum of their weights; the module docstring
+    holds the definition.  weights and frac_bits follow flowacc.accumulate_weighted (finite, >= 0; the default
+    frac_bits is flowacc.weight_frac_bits's rule; one with N * rint(max(weights) * 2^frac_bits) > 2^52 is refused).
+    Bad arguments raise ValueError before any library call."""
+    return _accumulate(angle, weights, frac_bits)[0]
+
+
+def specific_catchment_area(angle, px, weights=None, frac_bits=None):
+    """(accumulate(angle, weights, frac_bits) + the cell's own (quantised) weight) * px: contributing area per unit
+    contour length with the cell itself included, TauDEM's `sca` for unit weights; -100 where accumulate gives -100."""
+    p = _px(px)
+    acc, w, s, _ = _accumulate(angle, weights, frac_bits)
+    own = 1.0 if w is None else np.ldexp(np.rint(np.ldexp(w, s)), -s)
+    return np.where(acc == -100.0, -100.0, (acc + own) * p)

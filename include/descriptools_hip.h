@@ -102,6 +102,9 @@ int dt_graph_destroy(dt_graph *graph);
 /* DT_STATUS_REACH_RANGE: dt_dev_reach_tables met a catchment id >= the number of reaches it was given; that cell was
  * left out of the tables. */
 #define DT_STATUS_REACH_RANGE 8
+/* DT_STATUS_BAD_ANGLE: dt_dev_dinf_accumulate met an angle that is neither -1, -100 nor in [0, float32(2 pi)] (NaN
+ * included); that cell was taken as -1 (no receiver). */
+#define DT_STATUS_BAD_ANGLE 16
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
 
@@ -181,6 +184,33 @@ int dt_drainage(const uint8_t *fdr, const float *dem, const int64_t *pour, int64
  * float64(n_card) * px + float64(n_diag) * (px * sqrt(2.0)).  -100 on nodata and on cells of a D8 cycle; cells that
  * drain into a cycle get their value.  Same refusals as dt_drainage. */
 int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px, double *length);
+/* Net-new: D-infinity (Tarboton 1997) flow direction.  angle (float32): radians counter-clockwise from east, rows
+ * growing to the south, so octant k = 0..7 (the neighbour at k pi / 4) is E, NE, N, NW, W, SW, S, SE (D8 codes 1, 128,
+ * 64, 32, 16, 8, 4, 2).  A height is valid when it is finite and > -100.  For a valid centre e0 the eight facets
+ * (e1, e2, ac, af) = (E, NE, 0, +1), (N, NE, 1, -1), (N, NW, 1, +1), (W, NW, 2, -1), (W, SW, 2, +1), (S, SW, 3, -1),
+ * (S, SE, 3, +1), (E, SE, 4, -1) are tried in this order, those with both neighbours in the raster and valid, in
+ * float64: s1 = (e0 - e1) / px, s2 = (e1 - e2) / px; s2 < 0: r = 0, s = s1; else s2 > s1: r = pi / 4, s = (e0 - e2) /
+ * (px * sqrt(2.0)); else r = atan2(s2, s1), s = sqrt(s1 * s1 + s2 * s2).  The largest s > 0 wins (strict >: the first
+ * of equals); angle64 = af * r + ac * (pi / 2), less 2 pi when >= 2 pi; angle = float32(angle64), 0 when that is >=
+ * float32(2 pi); slope = float32(s), drop over distance.  A valid centre without a winning facet: when fdr (may be
+ * NULL) holds a D8 code there whose neighbour is in the raster and valid, angle = float32(k pi / 4) of that octant,
+ * else -1 (no flow); slope 0.  A centre that is NaN or +inf: -1 and 0.  A nodata centre (<= -100): -100 and -100;
+ * -inf is <= -100 and therefore nodata, as in every other entry of this library, not a non-finite centre.
+ * slope may be NULL.  Rasters of 2^31 cells or more and a px that is not finite and > 0 are refused. */
+int dt_dinf_direction(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px, float *angle,
+                      float *slope);
+/* Net-new: D-infinity contributing area of an angle raster (dt_dinf_direction's, or a TauDEM `ang` grid).  An angle
+ * a >= 0 is decoded as t = float64(a) * 1.2732395447351628: when |t - rint(t)| <= 2^-20 the cell has one receiver,
+ * octant rint(t) mod 8; else k = floor(t), P2 = rint((t - k) * 2^30), and its receivers are octant k mod 8 with share
+ * 2^30 - P2 and octant (k + 1) mod 8 with share P2.  -1: no receiver; -100: nodata; anything else fails the call.
+ * c -> d is an edge for each receiver d in the raster that is not nodata (other shares leave the domain).  With
+ * q(c) = rint(w(c) * 2^s), s = frac_bits (w NULL: 1 everywhere; the rules of dt_flowacc_weighted), T(c) = q(c) + what
+ * c receives; a complete c sends m2 = floor(T * P2 / 2^30) to octant k + 1 and T - m2 to octant k.
+ * acc = ldexp(T - q, -s) (self excluded), -100 on nodata and on every cell on or below a cycle.  Exact integer sums:
+ * the result does not depend on order or run.  info4 (may be NULL) = {queue rounds that found work, the largest
+ * number of cells one round drained, cells queued in all, two-receiver cells}. */
+int dt_dinf_accumulate(const float *angle, const double *w, int64_t H, int64_t W, int frac_bits, double *acc,
+                       int64_t *info4);
 /* Net-new: reaches (the HAND synthetic-rating-curve method).  Rasters are H x W with fewer than 2^31 cells, flat index
  * y * W + x; results are exact integers (and depth one float32 rounding), independent of order and run.
  *
@@ -352,6 +382,24 @@ int dt_dev_drainage(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const int
                     double px, int64_t *target, double *length, int64_t *label);
 int dt_dev_upslope_length(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                           double *length);
+/* dt_dinf_direction and dt_dinf_accumulate on device rasters, on the context's stream: neither synchronises.  fdr,
+ * slope and w may be NULL.  dt_dev_dinf_accumulate enqueues round 0 (from the cells without donors) and rounds - 1
+ * rounds that drain the queue of cells handed on (1 <= rounds <= 4096; a round that finds the queue empty returns at
+ * once), then writes acc; when queued work is left it raises DT_STATUS_NOT_CONVERGED (dt_ctx_status) and the cells
+ * not reached hold -100.  A start (a source, a queued cell) completes at most 128 cells in a round before it hands
+ * on, so a raster needs at least its longest flow path / 128 rounds: dt_dev_dinf_accumulate_info says how many found
+ * work.  A call with -4096 <= rounds <= -1 continues that accumulation with -rounds further rounds and writes acc
+ * again; it must name the same angle raster, weight raster, shape and frac_bits (DT_EINVAL otherwise, and when
+ * another call has used the context's scratch since; the rasters' contents must not have changed, which is not
+ * checked).  An angle outside the contract raises DT_STATUS_BAD_ANGLE and counts as -1, a bad weight
+ * DT_STATUS_BAD_WEIGHT and 0. */
+int dt_dev_dinf_direction(dt_ctx *ctx, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
+                          float *angle, float *slope);
+int dt_dev_dinf_accumulate(dt_ctx *ctx, const float *angle, const double *w, int64_t H, int64_t W, int frac_bits,
+                           int rounds, double *acc);
+/* dt_dinf_accumulate's info4 for the accumulation last enqueued on this context (synchronises): what a caller sizes
+ * its budget of rounds with.  DT_EINVAL when another call has used the context's scratch since. */
+int dt_dev_dinf_accumulate_info(dt_ctx *ctx, int64_t *info4);
 /* The reach calls on device rasters, on the context's stream: none synchronises.  idx is int32 (idx_bytes 4, the
  * resident chain's raster) or int64 (8); n_reaches (may be NULL) is one int64 on the device; heads entries from R on
  * are left as they were.  dt_dev_reach_tables takes `stages` from the host (they travel as kernel arguments) and the
