@@ -295,11 +295,6 @@ extern "C" int dt_set_flow_impl(int impl) {
   return DT_OK;
 }
 
-static DtWin dt_full_window(int64_t H, int64_t W) {
-  DtWin w;
-  w.H = (int)H; w.W = (int)W; w.ld = W; w.gy0 = 0; w.gx0 = 0; w.Hg = (int)H; w.Wg = (int)W; w.halo = 0;
-  return w;
-}
 static int dt_convert_window(const dt_window *in, DtWin *out) {
   DT_REQUIRE(in != nullptr, "window is NULL");
   DT_REQUIRE(in->H >= 0 && in->W >= 0 && in->H * in->W < (1ll << 31), "bad core shape");
@@ -926,8 +921,9 @@ extern "C" int dt_dev_downslope_lift(dt_ctx *c, const float *dem, const uint8_t 
   DT_TRY(dt_check_hw(H, W));
   DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
   DT_REQUIRE(work != nullptr && work_bytes >= dt_downslope_lift_workspace(H, W), "downslope workspace missing or too small");
-  DT_TRY(dt_launch_downslope(c->stream, dt_full_window(H, W), dem, fdr, px, dz, raw, out, nullptr, work,
-                             (char *)work + dt_downslope_queue_bytes(H, W), 0));
+  const DtWin w = dt_full_window(H, W);
+  const DtDsLift L = dt_downslope_lift_layout(w, work);
+  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, nullptr, L.qcount, L.tab[0], 0));
   DT_HIP(hipGetLastError());
   return DT_OK;
 }
@@ -1149,8 +1145,9 @@ extern "C" int dt_dev_downslope_lift_w(dt_ctx *c, const dt_window *win, const fl
   DT_REQUIRE(work != nullptr && work_bytes >= (int64_t)dt_downslope_lift_bytes_w(w),
              "downslope workspace missing or too small");
   if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
-  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev, work,
-                             (char *)work + dt_downslope_queue_bytes(w.H, w.W), 0));
+  const DtDsLift L = dt_downslope_lift_layout(w, work);
+  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev, L.qcount, L.tab[0],
+                             0));
   DT_HIP(hipGetLastError());
   return DT_OK;
 }
@@ -1168,9 +1165,9 @@ extern "C" int dt_dev_downslope_emit_w(dt_ctx *c, const dt_window *win, const fl
   DT_REQUIRE(work == nullptr || work_bytes >= (int64_t)dt_downslope_lift_bytes_w(w), "downslope workspace too small");
   DT_REQUIRE(walkers != nullptr && walkers_bytes >= 256 + 48, "walker buffer missing or too small");
   if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
-  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev, work,
-                             work ? (char *)work + dt_downslope_queue_bytes(w.H, w.W) : nullptr, 0, walkers,
-                             (size_t)walkers_bytes));
+  const DtDsLift L = dt_downslope_lift_layout(w, work);  // all null without work
+  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev, L.qcount, L.tab[0], 0,
+                             walkers, (size_t)walkers_bytes));
   DT_HIP(hipGetLastError());
   return DT_OK;
 }

@@ -70,6 +70,56 @@ int dt_scratch_reset(dt_ctx *ctx, size_t total_bytes);
 void *dt_scratch_take(dt_ctx *ctx, size_t bytes);
 static inline size_t dt_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// ---- workspaces ---------------------------------------------------------------------------------
+// A workspace has one layout function: it carves its arrays out of `scratch` with a DtCarver, in order, and records
+// bytes().  Given no memory (nullptr) the same function only sizes, so the size and the pointers cannot disagree.
+struct DtCarver {
+  char *base;  // may be null: sizing only, every pointer handed out is null
+  size_t off = 0;
+  explicit DtCarver(void *p) : base((char *)p) {}
+  void *raw(size_t nbytes) {  // a counter header, a flag block, a pad: rounded up to 256 bytes like every array
+    char *q = base ? base + off : nullptr;
+    off += dt_align256(nbytes);
+    return q;
+  }
+  template <typename T> T *take(size_t count) { return (T *)raw(count * sizeof(T)); }
+  size_t bytes() const { return off; }
+};
+// ceil(log2 N) + 1: the rounds pointer doubling needs on chains of at most N cells
+static inline int dt_doubling_rounds(int64_t N) {
+  int r = 0;
+  while (r < 62 && (1ll << r) < N) r++;
+  return r + 1;
+}
+// blocks of 256 threads that cover n items at one item per thread, at most `cap` (the kernel strides beyond)
+static inline unsigned dt_capped_grid(int64_t n, int64_t cap) {
+  const int64_t want = (n + 255) / 256;
+  return (unsigned)(want < cap ? want : cap);
+}
+
+// exclusive block scan of one 32-bit value per thread (256 threads, s_w: 4 words of LDS); *total = the block's sum
+__device__ __forceinline__ uint32_t dt_block_scan_256(uint32_t v, uint32_t *s_w, uint32_t *total) {
+  const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+  uint32_t x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = (uint32_t)__shfl_up((int)x, o);
+    if (lane >= o) x += t;
+  }
+  if (lane == 63) s_w[wv] = x;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t t = s_w[k];
+    before += k < wv ? t : 0u;
+    all += t;
+  }
+  __syncthreads();
+  *total = all;
+  return before + x - v;
+}
+
 // ---- D8 decoding (flowhand.py:801-824 / downslope.py:490-513) -------------------------------
 // code -> bit index: 1=E 2=SE 4=S 8=SW 16=W 32=NW 64=N 128=NE
 __device__ __forceinline__ bool dt_d8_valid(uint32_t code) {
@@ -85,10 +135,15 @@ __device__ __forceinline__ bool dt_d8_valid(uint32_t code) {
    (uint32_t)((g) + 1) << 12 | (uint32_t)((h) + 1) << 14)
 #define DT_DX_PACK DT_PK8(1, 1, 0, -1, -1, -1, 0, 1)
 #define DT_DY_PACK DT_PK8(0, 1, 1, 1, 0, -1, -1, -1)
-__device__ __forceinline__ void dt_d8_delta(uint32_t code, int &dy, int &dx) {
-  int i = __ffs((int)code) - 1;
+// the step to neighbour i (the bit index of its code)
+__device__ __forceinline__ void dt_nb_delta(int i, int &dy, int &dx) {
   dx = (int)((DT_DX_PACK >> (2 * i)) & 3u) - 1;
   dy = (int)((DT_DY_PACK >> (2 * i)) & 3u) - 1;
+}
+// the code with which neighbour i points back at the centre: the opposite step, E<->W, SE<->NW, S<->N, SW<->NE
+__device__ __forceinline__ uint32_t dt_nb_back_code(int i) { return 1u << ((i + 4) & 7); }
+__device__ __forceinline__ void dt_d8_delta(uint32_t code, int &dy, int &dx) {
+  dt_nb_delta(__ffs((int)code) - 1, dy, dx);
 }
 
 // ---- raster window -------------------------------------------------------------------------------
@@ -102,6 +157,12 @@ struct DtWin {
   int gy0, gx0, Hg, Wg;
   int halo;
 };
+// the window of a single raster
+static inline DtWin dt_full_window(int64_t H, int64_t W) {
+  DtWin w;
+  w.H = (int)H; w.W = (int)W; w.ld = W; w.gy0 = 0; w.gx0 = 0; w.Hg = (int)H; w.Wg = (int)W; w.halo = 0;
+  return w;
+}
 __host__ __device__ __forceinline__ bool dt_in_core(const DtWin &w, int y, int x) {
   return y >= 0 && y < w.H && x >= 0 && x < w.W;
 }

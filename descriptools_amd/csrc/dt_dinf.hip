@@ -443,18 +443,13 @@ struct DiLayout {
   uint32_t *queue;
   size_t bytes;
 };
-static DiLayout di_layout(int64_t N, char *p) {
+static DiLayout di_layout(int64_t N, void *scratch) {
   DiLayout L = {};
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char *q = p ? p + off : nullptr;
-    off += dt_align256(b);
-    return q;
-  };
-  L.ctl = (uint32_t *)take(sizeof(uint32_t) * DI_C_WORDS);
-  L.word = (unsigned long long *)take((size_t)N * 8);
-  L.queue = (uint32_t *)take((size_t)N * 4);
-  L.bytes = off;
+  DtCarver c(scratch);
+  L.ctl = c.take<uint32_t>(DI_C_WORDS);
+  L.word = c.take<unsigned long long>((size_t)N);
+  L.queue = c.take<uint32_t>((size_t)N);
+  L.bytes = c.bytes();
   return L;
 }
 size_t dt_dinf_accumulate_scratch(int64_t H, int64_t W) { return di_layout(H * W, nullptr).bytes; }
@@ -477,18 +472,13 @@ int dt_launch_dinf_direction(hipStream_t s, const float *dem, const uint8_t *fdr
   return DT_OK;
 }
 
-static dim3 di_queue_grid(int64_t N) {
-  const int64_t want = (N + 255) / 256;
-  return dim3((unsigned)(want < 2048 ? want : 2048));
-}
-
 // start != 0: the set-up and round 0 first; then `rounds` queue rounds; finish != 0: k_di_out
 int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *wt, int64_t H, int64_t W, int frac_bits,
                               int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
                               double *out, int *status) {
   if (H == 0 || W == 0) return DT_OK;
   const int64_t N = H * W;
-  DiLayout L = di_layout(N, (char *)scratch);
+  DiLayout L = di_layout(N, scratch);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
   const unsigned long long qmax = (1ull << 52) / (unsigned long long)N;
   const int cap = stack_cap > 0 && stack_cap - 1 < DI_STACK ? stack_cap - 1 : DI_STACK;  // cells on the stack
@@ -502,7 +492,7 @@ int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *w
     hipLaunchKernelGGL(k_di_flow<true>, dim3((unsigned)((N + 255) / 256)), b, 0, s, angle, L.word, (int)H, (int)W,
                        L.queue, L.ctl, cap, DI_MOVES);
   }
-  const dim3 gq = di_queue_grid(N);
+  const dim3 gq(dt_capped_grid(N, 2048));
   for (int r = 0; r < rounds; r++) {
     hipLaunchKernelGGL(k_di_mark, dim3(1), dim3(1), 0, s, L.ctl);
     hipLaunchKernelGGL(k_di_flow<false>, gq, b, 0, s, angle, L.word, (int)H, (int)W, L.queue, L.ctl, cap, DI_MOVES);
@@ -516,5 +506,5 @@ int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *w
 // the control words of the accumulation in `scratch` (device pointer to DI_C_WORDS uint32: tail, lo, hi, queue rounds
 // that found work, the largest window, two-receiver cells)
 const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W) {
-  return di_layout(H * W, (char *)scratch).ctl;
+  return di_layout(H * W, scratch).ctl;
 }

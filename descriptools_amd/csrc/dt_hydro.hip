@@ -1295,11 +1295,25 @@ __global__ __launch_bounds__(256) void k_flat_assign_m(const uint8_t *__restrict
 static size_t hy_tiles(int64_t H, int64_t W) { return (size_t)((W + HT - 1) / HT) * (size_t)((H + HT - 1) / HT); }
 // flags | distance raster | two per-tile activity arrays (the rounds alternate between them) | has_flat per tile
 // | one byte per cell: which neighbours have another height (k_flat_init -> k_flat_relax_m)
-size_t dt_hydro_scratch(int64_t H, int64_t W) {
-  return DT_HYDRO_FLAG_BYTES + dt_align256((size_t)H * W * 4) + 3 * dt_align256(hy_tiles(H, W)) +
-         dt_align256((size_t)H * W);
+struct HyLayout {
+  int *flag;  // the flag block: DT_HYDRO_FLAG_BYTES
+  uint32_t *dist;
+  uint8_t *act, *act1, *has_flat, *nsame;
+  size_t bytes;
+};
+static HyLayout hy_layout(int64_t H, int64_t W, void *scratch) {
+  HyLayout L;
+  DtCarver c(scratch);
+  L.flag = (int *)c.raw(DT_HYDRO_FLAG_BYTES);
+  L.dist = c.take<uint32_t>((size_t)H * W);
+  L.act = c.take<uint8_t>(hy_tiles(H, W));
+  L.act1 = c.take<uint8_t>(hy_tiles(H, W));
+  L.has_flat = c.take<uint8_t>(hy_tiles(H, W));
+  L.nsame = c.take<uint8_t>((size_t)H * W);
+  L.bytes = c.bytes();
+  return L;
 }
-
+size_t dt_hydro_scratch(int64_t H, int64_t W) { return hy_layout(H, W, nullptr).bytes; }
 // raise the context's status when the budget of rounds did not reach the fixed point, or a flat cell got no code
 __global__ void k_hydro_verdict(const int *__restrict__ last_fill, const int *__restrict__ last_flat,
                                 const int *__restrict__ unresolved, int *__restrict__ status) {
@@ -1337,12 +1351,6 @@ static int hy_iterate(hipStream_t s, int *flags, int64_t max_rounds, F round, in
   }
   if (rounds_out) *rounds_out = (int)(rounds > 0x7FFFFFFF ? 0x7FFFFFFF : rounds);
   return DT_OK;
-}
-
-static DtWin hy_full_window(int64_t H, int64_t W) {
-  DtWin w;
-  w.H = (int)H; w.W = (int)W; w.ld = W; w.gy0 = 0; w.gx0 = 0; w.Hg = (int)H; w.Wg = (int)W; w.halo = 0;
-  return w;
 }
 
 // One relaxation round of a single raster.  Rasters of at least HY_COLOUR_MIN_TILES tiles run COLOURED rounds (four
@@ -1388,20 +1396,21 @@ static void hy_fill_round(hipStream_t s, bool coloured, int64_t r, const T *dem,
 // D8 on the filled surface and k_flat_init (the steps between the two relaxations that read heights).  float: the
 // distance raster is not in use yet and lends the D8 kernel its mark / mask workspace -- the hot / cold pair of the
 // chain's first op, 0.40 ms at 16384^2, instead of the generic stencil, 0.55.  double: k_d8_f64 (no workspace).
-static int hy_d8_flat_init(hipStream_t s, const DtWin &w, const float *filled, double px, uint8_t *fdr, uint32_t *dist,
-                           int tiles_x, uint8_t *has_flat, uint8_t *nsame) {
-  const int64_t H = w.H, W = w.W, n = H * W;
+static int hy_d8_flat_init(hipStream_t s, const DtWin &w, const float *filled, double px, uint8_t *fdr,
+                           const HyLayout &L, int tiles_x) {
+  const int64_t H = w.H, W = w.W;
+  const size_t room = (size_t)((char *)L.act - (char *)L.dist);  // the distance raster's, up to the next array
   DT_TRY(dt_launch_stencil(s, w, filled, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr, nullptr,
-                           dt_stencil_aux_bytes(H, W) <= dt_align256((size_t)n * 4) ? (void *)dist : nullptr));
-  hipLaunchKernelGGL(k_flat_init, dim3((unsigned)hy_tiles(H, W)), dim3(256), 0, s, filled, fdr, w, dist, tiles_x,
-                     has_flat, nsame);
+                           dt_stencil_aux_bytes(H, W) <= room ? (void *)L.dist : nullptr));
+  hipLaunchKernelGGL(k_flat_init, dim3((unsigned)hy_tiles(H, W)), dim3(256), 0, s, filled, fdr, w, L.dist, tiles_x,
+                     L.has_flat, L.nsame);
   return DT_OK;
 }
 static int hy_d8_flat_init(hipStream_t s, const DtWin &w, const double *filled, double px, uint8_t *fdr,
-                           uint32_t *dist, int tiles_x, uint8_t *has_flat, uint8_t *nsame) {
+                           const HyLayout &L, int tiles_x) {
   DT_TRY(dt_launch_d8_f64(s, filled, w.H, w.W, px, fdr, nullptr, nullptr));
-  hipLaunchKernelGGL(k_flat_init_f64, dim3((unsigned)hy_tiles(w.H, w.W)), dim3(256), 0, s, filled, fdr, w, dist,
-                     tiles_x, has_flat, nsame);
+  hipLaunchKernelGGL(k_flat_init_f64, dim3((unsigned)hy_tiles(w.H, w.W)), dim3(256), 0, s, filled, fdr, w, L.dist,
+                     tiles_x, L.has_flat, L.nsame);
   return DT_OK;
 }
 // ... of the flat distances; has_flat: k_flat_init's per-tile flags, the activity the first round starts from (the
@@ -1431,37 +1440,31 @@ static int hy_condition(hipStream_t s, const T *dem, int64_t H, int64_t W, doubl
                         void *scratch, int *unresolved_host, int *rounds_host) {
   const int fill_sweeps = dt_debug_get(DT_DBG_HY_FILL_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FILL_SWEEPS) : HY_FILL_SWEEPS;
   const int flat_sweeps = dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) : HY_FLAT_SWEEPS;
-  (void)fill_sweeps;
-  (void)flat_sweeps;
   const int64_t n = H * W;
   if (n == 0) return DT_OK;
-  int *flag = (int *)scratch;
-  uint32_t *dist = (uint32_t *)((char *)scratch + DT_HYDRO_FLAG_BYTES);
-  const DtWin w = hy_full_window(H, W);
+  const HyLayout L = hy_layout(H, W, scratch);
+  const DtWin w = dt_full_window(H, W);
   const int tiles_x = (int)((W + HT - 1) / HT), tiles_y = (int)((H + HT - 1) / HT);
   dim3 gc((unsigned)((n + 255) / 256)), gt((unsigned)(tiles_x * tiles_y)), b(256);
   int r1 = 0, r2 = 0;
   const int64_t max_rounds = n + 8;
-  uint8_t *act = (uint8_t *)scratch + DT_HYDRO_FLAG_BYTES + dt_align256((size_t)n * 4);
-  uint8_t *act1 = act + dt_align256(hy_tiles(H, W));
-  uint8_t *has_flat = act + 2 * dt_align256(hy_tiles(H, W));
-  uint8_t *nsame = has_flat + dt_align256(hy_tiles(H, W));
   const bool coloured = hy_tiles(H, W) >= hy_colour_min();
-  DT_TRY(hy_iterate(s, flag, max_rounds, [&](int *f, const int *prev, int64_t r) {
-    hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, f, prev, act, act1, fill_sweeps);
+  DT_TRY(hy_iterate(s, L.flag, max_rounds, [&](int *f, const int *prev, int64_t r) {
+    hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, f, prev, L.act, L.act1, fill_sweeps);
   }, &r1));
   if (fdr) {
-    DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, dist, tiles_x, has_flat, nsame));
+    DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, L, tiles_x));
     // the rounds start from the tiles that have flat cells (and their neighbours), not from every tile
-    if (coloured) DT_HIP(hipMemcpyAsync(act, has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
-    DT_TRY(hy_iterate(s, flag, max_rounds, [&](int *f, const int *prev, int64_t r) {
-      hy_flat_round(s, coloured, r, nsame, dist, w, tiles_x, tiles_y, f, prev, act, act1, has_flat, flat_sweeps);
+    if (coloured) DT_HIP(hipMemcpyAsync(L.act, L.has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
+    DT_TRY(hy_iterate(s, L.flag, max_rounds, [&](int *f, const int *prev, int64_t r) {
+      hy_flat_round(s, coloured, r, L.nsame, L.dist, w, tiles_x, tiles_y, f, prev, L.act, L.act1, L.has_flat,
+                    flat_sweeps);
     }, &r2));
-    DT_HIP(hipMemsetAsync(flag + 64, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_flat_assign_m, gt, b, 0, s, (const uint8_t *)nsame, dist, w, fdr, flag + 64, tiles_x,
-                       (const uint8_t *)has_flat);
+    DT_HIP(hipMemsetAsync(L.flag + 64, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_flat_assign_m, gt, b, 0, s, (const uint8_t *)L.nsame, L.dist, w, fdr, L.flag + 64, tiles_x,
+                       (const uint8_t *)L.has_flat);
     int u = 0;
-    DT_HIP(hipMemcpyAsync(&u, flag + 64, sizeof(int), hipMemcpyDeviceToHost, s));
+    DT_HIP(hipMemcpyAsync(&u, L.flag + 64, sizeof(int), hipMemcpyDeviceToHost, s));
     DT_HIP(hipStreamSynchronize(s));
     if (unresolved_host) *unresolved_host = u;
   }
@@ -1491,34 +1494,28 @@ static int hy_condition_async(hipStream_t s, const T *dem, int64_t H, int64_t W,
                               void *scratch, int rounds, int *status) {
   const int fill_sweeps = dt_debug_get(DT_DBG_HY_FILL_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FILL_SWEEPS) : HY_FILL_SWEEPS;
   const int flat_sweeps = dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) : HY_FLAT_SWEEPS;
-  (void)fill_sweeps;
-  (void)flat_sweeps;
   const int64_t n = H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(fdr != nullptr, "the asynchronous conditioning writes the D8 codes");
   DT_REQUIRE(rounds >= 1 && rounds <= DT_HYDRO_MAX_ASYNC_ROUNDS, "1..500 rounds");
-  int *flags = (int *)scratch;  // [0, rounds): fill rounds; [rounds, 2 rounds): flat rounds; [2 rounds]: unresolved
-  uint32_t *dist = (uint32_t *)((char *)scratch + DT_HYDRO_FLAG_BYTES);
-  const DtWin w = hy_full_window(H, W);
+  const HyLayout L = hy_layout(H, W, scratch);
+  int *flags = L.flag;  // [0, rounds): fill rounds; [rounds, 2 rounds): flat rounds; [2 rounds]: unresolved
+  const DtWin w = dt_full_window(H, W);
   const int tiles_x = (int)((W + HT - 1) / HT), tiles_y = (int)((H + HT - 1) / HT);
   dim3 gc((unsigned)((n + 255) / 256)), gt((unsigned)(tiles_x * tiles_y)), b(256);
   DT_HIP(hipMemsetAsync(flags, 0, DT_HYDRO_FLAG_BYTES, s));
-  uint8_t *act = (uint8_t *)scratch + DT_HYDRO_FLAG_BYTES + dt_align256((size_t)n * 4);
-  uint8_t *act1 = act + dt_align256(hy_tiles(H, W));
-  uint8_t *has_flat = act + 2 * dt_align256(hy_tiles(H, W));
-  uint8_t *nsame = has_flat + dt_align256(hy_tiles(H, W));
   const bool coloured = hy_tiles(H, W) >= hy_colour_min();
   for (int r = 0; r < rounds; r++)
     hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, flags + r, r ? (const int *)(flags + r - 1) : nullptr,
-                  act, act1, fill_sweeps);
-  DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, dist, tiles_x, has_flat, nsame));
-  if (coloured) DT_HIP(hipMemcpyAsync(act, has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
+                  L.act, L.act1, fill_sweeps);
+  DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, L, tiles_x));
+  if (coloured) DT_HIP(hipMemcpyAsync(L.act, L.has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
   int *fl2 = flags + rounds;
   for (int r = 0; r < rounds; r++)
-    hy_flat_round(s, coloured, r, nsame, dist, w, tiles_x, tiles_y, fl2 + r, r ? (const int *)(fl2 + r - 1) : nullptr, act,
-                  act1, has_flat, flat_sweeps);
-  hipLaunchKernelGGL(k_flat_assign_m, gt, b, 0, s, (const uint8_t *)nsame, dist, w, fdr, flags + 2 * rounds, tiles_x,
-                     (const uint8_t *)has_flat);
+    hy_flat_round(s, coloured, r, L.nsame, L.dist, w, tiles_x, tiles_y, fl2 + r, r ? (const int *)(fl2 + r - 1) : nullptr,
+                  L.act, L.act1, L.has_flat, flat_sweeps);
+  hipLaunchKernelGGL(k_flat_assign_m, gt, b, 0, s, (const uint8_t *)L.nsame, L.dist, w, fdr, flags + 2 * rounds, tiles_x,
+                     (const uint8_t *)L.has_flat);
   hipLaunchKernelGGL(k_hydro_verdict, dim3(1), dim3(1), 0, s, (const int *)(flags + rounds - 1),
                      (const int *)(fl2 + rounds - 1), (const int *)(flags + 2 * rounds), status);
   return DT_OK;

@@ -11,7 +11,21 @@ int dt_launch_stencil(hipStream_t s, const DtWin &w, const float *dem, double px
 // is nodata), ldm words per row of patches
 static inline int dt_nodata4_ld(int64_t W) { return (int)((((W + 3) / 4) + 7) & ~(int64_t)7); }
 static inline size_t dt_nodata4_bytes(int64_t H, int64_t W) { return (size_t)((H + 3) / 4) * (size_t)dt_nodata4_ld(W) * 2; }
-// workspace (tile marks + lane masks) of the fused slope + TI + MTI launch; see dt_stencil.hip
+// workspace of the stencil's hot / fix-up kernel pairs and of the TI / MTI epilogue (dt_tiles.hip): a mark byte and 256
+// 16-bit lane masks per tile of the launch's own geometry; dt_stencil_aux_bytes: the largest geometry of an H x W window
+struct DtStencilAux {
+  uint8_t *mark;
+  uint16_t *lmask;
+  size_t bytes;
+};
+static inline DtStencilAux dt_stencil_aux_layout(int64_t ntiles, void *aux) {
+  DtStencilAux a;
+  DtCarver c(aux);
+  a.mark = c.take<uint8_t>((size_t)ntiles);
+  a.lmask = c.take<uint16_t>((size_t)ntiles * 256);
+  a.bytes = c.bytes();
+  return a;
+}
 size_t dt_stencil_aux_bytes(int64_t H, int64_t W);
 // the float32 chain's D8 + slope kernel and the fix-up of the cells it and the TI / MTI epilogue marked (dt_stencil.hip)
 int dt_launch_d8_slope(hipStream_t s, const DtWin &w, const float *dem, double px, uint8_t *fdr, float *slope,
@@ -35,6 +49,18 @@ int dt_launch_gfi_i64(hipStream_t s, const float *hand, const int64_t *area, int
                       double b, double size, float *out, int own_cell);
 int dt_launch_river_acc_i64(hipStream_t s, const int64_t *fac, const int64_t *idx, int64_t n,
                             int64_t *out);
+// The long-walk workspace of a window (dt_kernels.hip, DsQueue): the QUEUE (a 256-byte counter header | one entry per
+// two core cells), then the TABLES over the window's memory (two ping-pong skip tables, the 8-move table that is kept,
+// which entries exist).  `work` holds both back to back; dt_launch_downslope also takes them at two addresses.
+struct DtDsLift {
+  uint32_t *qcount;  // walks queued: the first word of the header
+  uint4 *qentries;
+  uint32_t qcapacity;
+  uint2 *tab[3];
+  uint8_t *dom;
+  size_t queue_bytes, tables_bytes, bytes;
+};
+DtDsLift dt_downslope_lift_layout(const DtWin &w, void *work);
 size_t dt_downslope_lift_bytes(int64_t H, int64_t W);
 size_t dt_downslope_queue_bytes(int64_t H, int64_t W);
 size_t dt_downslope_tables_bytes(int64_t H, int64_t W);
@@ -187,6 +213,21 @@ int dt_flow_impl();  // 1 global kernels, 2 tile-hierarchical (default)
 // shreve / link may be NULL.  m_host != NULL (rasters of 2^31 cells or more) reads the network's cell count back and
 // refuses 2^31 or more; otherwise nothing synchronises.
 size_t dt_stream_order_scratch(int64_t H, int64_t W);
+// The exclusive scan of per-block counts that stream order and the reach catchments share (kernels in dt_streams.hip):
+// a counting pass covers DT_SCAN_CHUNK cells per block, the scan groups the block counts by the same number, and
+// dt_launch_count_scan leaves offsets[b] = the sum of the counts before block b and meta[0] = the total.
+#define DT_SCAN_CPT 8                      // cells per thread of a counting pass
+#define DT_SCAN_CHUNK (256 * DT_SCAN_CPT)  // cells per block
+static inline int64_t dt_scan_blocks(int64_t n) { return (n + DT_SCAN_CHUNK - 1) / DT_SCAN_CHUNK; }
+struct DtCountScan {
+  int64_t nblk, ng;  // blocks over the cells, groups over the blocks
+  uint32_t *bcount, *gsum;
+  int64_t *offsets, *goff, *meta;
+};
+// the arrays for n cells; `meta` is two words the caller has carved already (stream order keeps two rasters between
+// them and the counts: every array stays at the offset it has always had)
+DtCountScan dt_count_scan_carve(DtCarver &c, int64_t n, int64_t *meta);
+int dt_launch_count_scan(hipStream_t s, const DtCountScan &cs, int64_t nblk);
 int dt_launch_stream_order(hipStream_t s, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, void *scratch,
                            size_t scratch_bytes, int8_t *strahler, int64_t *shreve, int64_t *link, int64_t *m_host);
 

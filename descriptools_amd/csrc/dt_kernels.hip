@@ -1456,19 +1456,10 @@ int dt_launch_ds_walk(hipStream_t s, const DtWin &w, const float *dem, const uin
   if (n <= 0) return DT_OK;
   float dzf = (float)dz;
   if ((double)dzf < dz) dzf = nextafterf(dzf, INFINITY);
-  const uint2 *T = nullptr, *T8 = nullptr;
-  const uint8_t *dom = nullptr;
-  const uint32_t *qc = nullptr;
-  if (work) {
-    const size_t cells = (size_t)(w.H + 2 * (int64_t)w.halo) * (size_t)w.ld;
-    char *t0 = (char *)work + dt_downslope_queue_bytes(w.H, w.W);
-    qc = (const uint32_t *)work;
-    T = (const uint2 *)t0;
-    T8 = (const uint2 *)(t0 + 2 * dt_align256(cells * 8));
-    dom = (const uint8_t *)(t0 + 3 * dt_align256(cells * 8));
-  }
+  const DtDsLift L = dt_downslope_lift_layout(w, work);  // all null without the workspace
   hipLaunchKernelGGL(k_ds_walk, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dem, fdr, w, px, dz, dzf, n, (uint4 *)rec,
-                     T, T8, dom, qc, dt_downslope_lift_min(w.H, w.W), out);
+                     (const uint2 *)L.tab[0], (const uint2 *)L.tab[2], (const uint8_t *)L.dom, (const uint32_t *)L.qcount,
+                     dt_downslope_lift_min(w.H, w.W), out);
   return DT_OK;
 }
 // ---- where the walker records go next (tiling.finish_downslope's exchange, prepared on the device) -------------------
@@ -1674,25 +1665,36 @@ int dt_launch_ds_walk_seed_f64(hipStream_t s, const DtWin &w, const double *dem,
                        (uint4 *)rec);
   return DT_OK;
 }
-// workspaces of the long-walk acceleration for an H x W raster: the QUEUE (counter | one entry per two cells) and the
-// TABLES (two ping-pong skip tables and the 8-move table that is kept); dt_downslope_lift_bytes = both, back to back
-static size_t ds_queue_capacity(int64_t H, int64_t W) { return (size_t)((H * W + 1) / 2); }
-size_t dt_downslope_queue_bytes(int64_t H, int64_t W) { return 256 + dt_align256(ds_queue_capacity(H, W) * 16); }
-size_t dt_downslope_tables_bytes(int64_t H, int64_t W) {
-  return 3 * dt_align256((size_t)H * W * 8) + dt_align256((size_t)H * W);  // three tables | which entries exist
+// the long-walk workspace (DtDsLift, dt_kernels.h): each part is carved in one place, whether the two lie back to back
+// in one block (dt_downslope_lift_layout) or at a caller's own two addresses (dt_launch_downslope)
+static size_t ds_mem_cells(const DtWin &w) { return (size_t)(w.H + 2 * (int64_t)w.halo) * (size_t)w.ld; }
+static void ds_carve_queue(DtCarver &c, const DtWin &w, DtDsLift &L) {
+  L.qcapacity = (uint32_t)(((int64_t)w.H * w.W + 1) / 2);
+  L.qcount = (uint32_t *)c.raw(256);
+  L.qentries = c.take<uint4>(L.qcapacity);
 }
-size_t dt_downslope_lift_bytes(int64_t H, int64_t W) {
-  return dt_downslope_queue_bytes(H, W) + dt_downslope_tables_bytes(H, W);
+static void ds_carve_tables(DtCarver &c, const DtWin &w, DtDsLift &L) {
+  for (int i = 0; i < 3; i++) L.tab[i] = c.take<uint2>(ds_mem_cells(w));
+  L.dom = c.take<uint8_t>(ds_mem_cells(w));
 }
+DtDsLift dt_downslope_lift_layout(const DtWin &w, void *work) {
+  DtDsLift L;
+  DtCarver c(work);
+  ds_carve_queue(c, w, L);
+  L.queue_bytes = c.bytes();
+  ds_carve_tables(c, w, L);
+  L.bytes = c.bytes();
+  L.tables_bytes = L.bytes - L.queue_bytes;
+  return L;
+}
+static DtDsLift ds_sizes(int64_t H, int64_t W) { return dt_downslope_lift_layout(dt_full_window(H, W), nullptr); }
+size_t dt_downslope_queue_bytes(int64_t H, int64_t W) { return ds_sizes(H, W).queue_bytes; }
+size_t dt_downslope_tables_bytes(int64_t H, int64_t W) { return ds_sizes(H, W).tables_bytes; }
+size_t dt_downslope_lift_bytes(int64_t H, int64_t W) { return ds_sizes(H, W).bytes; }
 uint32_t dt_downslope_lift_min(int64_t H, int64_t W) { return (uint32_t)std::max<int64_t>(DS_LIFT_MIN, H * W / 256); }
 // ... of a window: the queue holds core cells, the tables cover the window's memory (core + halo, row stride ld)
-static size_t ds_mem_cells(const DtWin &w) { return (size_t)(w.H + 2 * (int64_t)w.halo) * (size_t)w.ld; }
-size_t dt_downslope_tables_bytes_w(const DtWin &w) {
-  return 3 * dt_align256(ds_mem_cells(w) * 8) + dt_align256(ds_mem_cells(w));
-}
-size_t dt_downslope_lift_bytes_w(const DtWin &w) {
-  return dt_downslope_queue_bytes(w.H, w.W) + dt_downslope_tables_bytes_w(w);
-}
+size_t dt_downslope_tables_bytes_w(const DtWin &w) { return dt_downslope_lift_layout(w, nullptr).tables_bytes; }
+size_t dt_downslope_lift_bytes_w(const DtWin &w) { return dt_downslope_lift_layout(w, nullptr).bytes; }
 // qwork / twork (optional): long walks are queued and finished with skip tables (see DsQueue); in a rank's window the
 // ones that stay in the rank's memory -- the others are counted in n_unresolved as without the workspace.  phase 0: everything; 1: the window kernel with the queue only; 2: the
 // tables (when twork is given; built only if enough walks were queued) and the queued walks -- so that a caller who may
@@ -1714,24 +1716,23 @@ int dt_launch_downslope(hipStream_t s, const DtWin &w, const float *dem, const u
   // are emitted (ranked kernels only)
   DsWalkOut wo;
   if (walkers && walkers_bytes >= 256 + DSW_WORDS * 4) {
-    wo.count = (uint32_t *)walkers;
-    wo.rec = (uint4 *)((char *)walkers + 256);
-    wo.capacity = (uint32_t)std::min<size_t>((walkers_bytes - 256) / (DSW_WORDS * 4), 0x7FFFFFFFu);
+    DtCarver cw(walkers);
+    wo.count = (uint32_t *)cw.raw(256);  // the counter header
+    wo.rec = (uint4 *)((char *)walkers + cw.bytes());  // the records take the rest
+    wo.capacity = (uint32_t)std::min<size_t>((walkers_bytes - cw.bytes()) / (DSW_WORDS * 4), 0x7FFFFFFFu);
     if (phase != 2) DT_HIP(hipMemsetAsync(wo.count, 0, sizeof(uint32_t), s));
   }
-  uint2 *tab[3] = {nullptr, nullptr, nullptr};  // two ping-pong tables and the 8-move table that is kept
+  DtDsLift L = {};  // tab: two ping-pong tables and the 8-move table that is kept
   const bool ranked = !(w.halo == 0 && w.gy0 == 0 && w.gx0 == 0 && w.Hg == w.H && w.Wg == w.W);
   // margin of the LDS window around the 64 x 64 core: walks that reach the window's ring carry on in global memory
   const int m = dt_debug_get(DT_DBG_DS_MARGIN);
   if (qwork && ds_mem_cells(w) < 0x7FFFFFFFull && m != 16 && m != 20) {  // (the A/B margins run without the queue)
-    q.count = (uint32_t *)qwork;
-    q.entries = (uint4 *)((char *)qwork + 256);
-    q.capacity = (uint32_t)ds_queue_capacity(H, W);
-    if (twork) {
-      tab[0] = (uint2 *)twork;
-      tab[1] = (uint2 *)((char *)tab[0] + dt_align256(ds_mem_cells(w) * 8));
-      tab[2] = (uint2 *)((char *)tab[1] + dt_align256(ds_mem_cells(w) * 8));
-    }
+    DtCarver cq(qwork), ct(twork);
+    ds_carve_queue(cq, w, L);
+    ds_carve_tables(ct, w, L);  // all null without twork
+    q.count = L.qcount;
+    q.entries = L.qentries;
+    q.capacity = L.qcapacity;
   }
   DT_REQUIRE(phase == 0 || q.entries, "the phases of the long-walk form need the queue workspace (and a window of < 2^31 cells)");
   if (phase != 2) {
@@ -1759,30 +1760,28 @@ int dt_launch_downslope(hipStream_t s, const DtWin &w, const float *dem, const u
     const dim3 b(256);
     const uint32_t lift_min = dt_downslope_lift_min(H, W);
     uint2 *src = nullptr;
-    uint8_t *dom = nullptr;
-    const unsigned fin_blocks = (unsigned)std::min<size_t>((q.capacity + 255) / 256, 8192);
-    if (tab[0]) {
+    const unsigned fin_blocks = dt_capped_grid(q.capacity, 8192);
+    if (L.tab[0]) {
       // every kernel of the tables returns at once when fewer than lift_min walks were queued
-      // 8 moves per skip for every cell (tab[2], kept) -> 16 -> 32 -> 64 for the queued cells (`dom`)
-      dom = (uint8_t *)tab[2] + dt_align256(ds_mem_cells(w) * 8);
-      DT_HIP(hipMemsetAsync(dom, 0, ds_mem_cells(w), s));
+      // 8 moves per skip for every cell (L.tab[2], kept) -> 16 -> 32 -> 64 for the queued cells (`dom`)
+      DT_HIP(hipMemsetAsync(L.dom, 0, ds_mem_cells(w), s));
       const int rows = (int)(H + 2 * w.halo), cols = (int)(W + 2 * w.halo);
       const int ltx = (cols + 63) / 64, lty = (rows + 63) / 64;
       const dim3 gt((unsigned)(ltx * lty));
       const uint32_t *qc = (const uint32_t *)q.count;
-      if (ranked) hipLaunchKernelGGL(k_ds_lift_init<true>, gt, b, 0, s, dem, fdr, w, tab[2], qc, lift_min, ltx);
-      else hipLaunchKernelGGL(k_ds_lift_init<false>, gt, b, 0, s, dem, fdr, w, tab[2], qc, lift_min, ltx);
-      hipLaunchKernelGGL(k_ds_tab_double<true>, dim3(fin_blocks), b, 0, s, q, (const uint2 *)tab[2], tab[0], dom, (int)w.ld, lift_min);
-      hipLaunchKernelGGL(k_ds_tab_double<false>, dim3(fin_blocks), b, 0, s, q, (const uint2 *)tab[0], tab[1], dom, (int)w.ld, lift_min);
-      hipLaunchKernelGGL(k_ds_tab_double<false>, dim3(fin_blocks), b, 0, s, q, (const uint2 *)tab[1], tab[0], dom, (int)w.ld, lift_min);
-      src = tab[0];
+      if (ranked) hipLaunchKernelGGL(k_ds_lift_init<true>, gt, b, 0, s, dem, fdr, w, L.tab[2], qc, lift_min, ltx);
+      else hipLaunchKernelGGL(k_ds_lift_init<false>, gt, b, 0, s, dem, fdr, w, L.tab[2], qc, lift_min, ltx);
+      hipLaunchKernelGGL(k_ds_tab_double<true>, dim3(fin_blocks), b, 0, s, q, (const uint2 *)L.tab[2], L.tab[0], L.dom, (int)w.ld, lift_min);
+      hipLaunchKernelGGL(k_ds_tab_double<false>, dim3(fin_blocks), b, 0, s, q, (const uint2 *)L.tab[0], L.tab[1], L.dom, (int)w.ld, lift_min);
+      hipLaunchKernelGGL(k_ds_tab_double<false>, dim3(fin_blocks), b, 0, s, q, (const uint2 *)L.tab[1], L.tab[0], L.dom, (int)w.ld, lift_min);
+      src = L.tab[0];
     }
     if (ranked)
       hipLaunchKernelGGL(k_ds_finish<true>, dim3(fin_blocks), b, 0, s, dem, fdr, w, px, dz, dzf, raw, out, q,
-                         (const uint2 *)src, (const uint2 *)tab[2], (const uint8_t *)dom, n_unresolved, lift_min, wo);
+                         (const uint2 *)src, (const uint2 *)L.tab[2], (const uint8_t *)L.dom, n_unresolved, lift_min, wo);
     else
       hipLaunchKernelGGL(k_ds_finish<false>, dim3(fin_blocks), b, 0, s, dem, fdr, w, px, dz, dzf, raw, out, q,
-                         (const uint2 *)src, (const uint2 *)tab[2], (const uint8_t *)dom, n_unresolved, lift_min, DsWalkOut());
+                         (const uint2 *)src, (const uint2 *)L.tab[2], (const uint8_t *)L.dom, n_unresolved, lift_min, DsWalkOut());
   }
   return DT_OK;
 }

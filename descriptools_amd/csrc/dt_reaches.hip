@@ -4,8 +4,8 @@
 // the caller's stream and every sum is an integer sum, so no result depends on order, tiling or run.
 //
 //   catchments  rc_count     heads (link[c] == c) per block of 2048 cells
-//               so_gsum / so_gscan / so_expand   the three scan launches of dt_streams.hip on those block counts:
-//                            heads before each block, R
+//               dt_launch_count_scan   the three scan launches of dt_streams.hip on those block counts: heads
+//                            before each block, R
 //               rc_rank      the rank of every head (block scan again): reach[head], heads[rank]
 //               rc_fill      reach of the other network cells and catch, both through the head's rank
 //   channels    rc_channels  one thread per cell, work only where reach >= 0: 64-bit integer atomics per reach
@@ -22,8 +22,6 @@
 
 #include "dt_kernels.h"
 
-#define RC_CPT 8
-#define RC_CHUNK (256 * RC_CPT)  // = SO_CHUNK: k_so_gsum / k_so_expand group the block counts by it
 #define RC_TW 64
 #define RC_TH 64
 #define RC_SLOTS_MAX 16
@@ -31,44 +29,29 @@
 #define RC_STAGE_CHUNK 128
 #define RC_NONE (-100)
 
-// the scan of per-block counts (dt_streams.hip): offsets[b] = sum of the counts before block b, meta[0] = the total
-__global__ void k_so_gsum(const uint32_t *bcount, int64_t nblk, uint32_t *gsum);
-__global__ void k_so_gscan(const uint32_t *gsum, int64_t ng, int64_t *goff, int64_t *meta);
-__global__ void k_so_expand(const uint32_t *bcount, int64_t nblk, const int64_t *goff, int64_t *offsets);
-
-// exclusive block scan of one 32-bit value per thread (256 threads); *total = the block's sum
-__device__ __forceinline__ uint32_t rc_block_scan(uint32_t v, uint32_t *s_w, uint32_t *total) {
-  const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)x, o);
-    if (lane >= o) x += t;
+// four consecutive heights of an HT raster, 16-byte loads (f a multiple of 4, the raster 16-byte aligned)
+template <typename HT>
+__device__ __forceinline__ void rc_load4(const HT *__restrict__ hand, int64_t f, HT (&hh)[4]) {
+  if (sizeof(HT) == 4) {
+    const float4 q = *reinterpret_cast<const float4 *>(hand + f);
+    hh[0] = (HT)q.x; hh[1] = (HT)q.y; hh[2] = (HT)q.z; hh[3] = (HT)q.w;
+  } else {
+    const double2 q0 = *reinterpret_cast<const double2 *>(hand + f);
+    const double2 q1 = *reinterpret_cast<const double2 *>(hand + f + 2);
+    hh[0] = (HT)q0.x; hh[1] = (HT)q0.y; hh[2] = (HT)q1.x; hh[3] = (HT)q1.y;
   }
-  if (lane == 63) s_w[wv] = x;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint32_t t = s_w[k];
-    before += k < wv ? t : 0u;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
 }
 
 // ---- catchments ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rc_count(const int64_t *__restrict__ link, int64_t N,
                                                   uint32_t *__restrict__ bcount) {
   __shared__ uint32_t s_w[4];
-  const int64_t f0 = (int64_t)blockIdx.x * RC_CHUNK + (int64_t)threadIdx.x * RC_CPT;
+  const int64_t f0 = (int64_t)blockIdx.x * DT_SCAN_CHUNK + (int64_t)threadIdx.x * DT_SCAN_CPT;
   uint32_t v = 0;
 #pragma unroll
-  for (int k = 0; k < RC_CPT; k++) v += (f0 + k < N && link[f0 + k] == f0 + k) ? 1u : 0u;
+  for (int k = 0; k < DT_SCAN_CPT; k++) v += (f0 + k < N && link[f0 + k] == f0 + k) ? 1u : 0u;
   uint32_t total;
-  rc_block_scan(v, s_w, &total);
+  dt_block_scan_256(v, s_w, &total);
   if (threadIdx.x == 0) bcount[blockIdx.x] = total;
 }
 
@@ -76,15 +59,15 @@ __global__ __launch_bounds__(256) void k_rc_rank(const int64_t *__restrict__ lin
                                                  const int64_t *__restrict__ offsets, int32_t *__restrict__ reach,
                                                  int64_t *__restrict__ heads, int64_t cap) {
   __shared__ uint32_t s_w[4];
-  const int64_t f0 = (int64_t)blockIdx.x * RC_CHUNK + (int64_t)threadIdx.x * RC_CPT;
+  const int64_t f0 = (int64_t)blockIdx.x * DT_SCAN_CHUNK + (int64_t)threadIdx.x * DT_SCAN_CPT;
   uint32_t flags = 0;
 #pragma unroll
-  for (int k = 0; k < RC_CPT; k++) flags |= (f0 + k < N && link[f0 + k] == f0 + k) ? 1u << k : 0u;
+  for (int k = 0; k < DT_SCAN_CPT; k++) flags |= (f0 + k < N && link[f0 + k] == f0 + k) ? 1u << k : 0u;
   uint32_t total;
-  const uint32_t ex = rc_block_scan((uint32_t)__popc(flags), s_w, &total);
+  const uint32_t ex = dt_block_scan_256((uint32_t)__popc(flags), s_w, &total);
   int64_t id = offsets[blockIdx.x] + ex;
 #pragma unroll
-  for (int k = 0; k < RC_CPT; k++) {
+  for (int k = 0; k < DT_SCAN_CPT; k++) {
     if (flags & (1u << k)) {
       reach[f0 + k] = (int32_t)id;
       if (heads && id < cap) heads[id] = f0 + k;
@@ -116,30 +99,17 @@ __global__ __launch_bounds__(256) void k_rc_fill(const int64_t *__restrict__ lin
 }
 
 struct RcCatchLayout {
-  int64_t nblk, ng;
-  uint32_t *bcount, *gsum;
-  int64_t *offsets, *goff, *meta;
-  int32_t *reach;
+  DtCountScan scan;
+  int32_t *reach;  // the head ranks, when the caller asks for no reach raster
   size_t bytes;
 };
 
-static RcCatchLayout rc_catch_layout(int64_t N, bool own_reach, char *p) {
+static RcCatchLayout rc_catch_layout(int64_t N, bool own_reach, void *scratch) {
   RcCatchLayout L;
-  L.nblk = (N + RC_CHUNK - 1) / RC_CHUNK;
-  L.ng = (L.nblk + RC_CHUNK - 1) / RC_CHUNK;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char *q = p ? p + off : nullptr;
-    off += dt_align256(b);
-    return q;
-  };
-  L.meta = (int64_t *)take(sizeof(int64_t) * 2);
-  L.bcount = (uint32_t *)take((size_t)L.nblk * 4);
-  L.offsets = (int64_t *)take((size_t)L.nblk * 8);
-  L.gsum = (uint32_t *)take((size_t)L.ng * 4);
-  L.goff = (int64_t *)take((size_t)L.ng * 8);
-  L.reach = own_reach ? (int32_t *)take((size_t)N * 4) : nullptr;
-  L.bytes = off;
+  DtCarver c(scratch);
+  L.scan = dt_count_scan_carve(c, N, c.take<int64_t>(2));
+  L.reach = own_reach ? c.take<int32_t>((size_t)N) : nullptr;
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -152,17 +122,16 @@ int dt_launch_reach_catchments(hipStream_t s, const int64_t *link, const void *i
     if (n_reaches_dev) DT_HIP(hipMemsetAsync(n_reaches_dev, 0, sizeof(int64_t), s));
     return DT_OK;
   }
-  RcCatchLayout L = rc_catch_layout(N, reach == nullptr, (char *)scratch);
+  RcCatchLayout L = rc_catch_layout(N, reach == nullptr, scratch);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
-  dim3 b(256), gr((unsigned)L.nblk), gg((unsigned)L.ng), gc((unsigned)((N + 255) / 256));
-  hipLaunchKernelGGL(k_rc_count, gr, b, 0, s, link, N, L.bcount);
-  hipLaunchKernelGGL(k_so_gsum, gg, b, 0, s, (const uint32_t *)L.bcount, L.nblk, L.gsum);
-  hipLaunchKernelGGL(k_so_gscan, dim3(1), b, 0, s, (const uint32_t *)L.gsum, L.ng, L.goff, L.meta);
-  hipLaunchKernelGGL(k_so_expand, gg, b, 0, s, (const uint32_t *)L.bcount, L.nblk, (const int64_t *)L.goff, L.offsets);
-  if (n_reaches_dev) DT_HIP(hipMemcpyAsync(n_reaches_dev, L.meta, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  const DtCountScan &cs = L.scan;
+  dim3 b(256), gr((unsigned)cs.nblk), gc((unsigned)((N + 255) / 256));
+  hipLaunchKernelGGL(k_rc_count, gr, b, 0, s, link, N, cs.bcount);
+  DT_TRY(dt_launch_count_scan(s, cs, cs.nblk));
+  if (n_reaches_dev) DT_HIP(hipMemcpyAsync(n_reaches_dev, cs.meta, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
   if (!reach && !catch_ && !heads) return DT_OK;
   int32_t *rk = reach ? reach : L.reach;
-  hipLaunchKernelGGL(k_rc_rank, gr, b, 0, s, link, N, (const int64_t *)L.offsets, rk, heads, cap);
+  hipLaunchKernelGGL(k_rc_rank, gr, b, 0, s, link, N, (const int64_t *)cs.offsets, rk, heads, cap);
   if (!reach && !catch_) return DT_OK;
   if (idx_bytes == 4) {
     if (reach) hipLaunchKernelGGL((k_rc_fill<int32_t, true>), gc, b, 0, s, link, (const int32_t *)idx, N, rk, catch_);
@@ -347,14 +316,7 @@ __global__ __launch_bounds__(256) void k_rc_tables(const int32_t *__restrict__ c
     if (VEC) {  // W is a multiple of 4 and the rasters are 16-B aligned
       const int4 v = *reinterpret_cast<const int4 *>(catch_ + f);
       rr[0] = v.x; rr[1] = v.y; rr[2] = v.z; rr[3] = v.w;
-      if (sizeof(HT) == 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(hand + f);
-        hh[0] = (HT)q.x; hh[1] = (HT)q.y; hh[2] = (HT)q.z; hh[3] = (HT)q.w;
-      } else {
-        const double2 q0 = *reinterpret_cast<const double2 *>(hand + f);
-        const double2 q1 = *reinterpret_cast<const double2 *>(hand + f + 2);
-        hh[0] = (HT)q0.x; hh[1] = (HT)q0.y; hh[2] = (HT)q1.x; hh[3] = (HT)q1.y;
-      }
+      rc_load4(hand, f, hh);
       if (SLOPE) {
         const float4 q = *reinterpret_cast<const float4 *>(slope + f);
         ss[0] = q.x; ss[1] = q.y; ss[2] = q.z; ss[3] = q.w;
@@ -547,14 +509,7 @@ __global__ __launch_bounds__(256) void k_rc_inundate(const int32_t *__restrict__
   if (VEC && f + 4 <= N) {
     const int4 v = *reinterpret_cast<const int4 *>(catch_ + f);
     HT hh[4];
-    if (sizeof(HT) == 4) {
-      const float4 q = *reinterpret_cast<const float4 *>(hand + f);
-      hh[0] = (HT)q.x; hh[1] = (HT)q.y; hh[2] = (HT)q.z; hh[3] = (HT)q.w;
-    } else {
-      const double2 q0 = *reinterpret_cast<const double2 *>(hand + f);
-      const double2 q1 = *reinterpret_cast<const double2 *>(hand + f + 2);
-      hh[0] = (HT)q0.x; hh[1] = (HT)q0.y; hh[2] = (HT)q1.x; hh[3] = (HT)q1.y;
-    }
+    rc_load4(hand, f, hh);
     *reinterpret_cast<float4 *>(depth + f) = make_float4(rc_depth(v.x, hh[0], stage, R), rc_depth(v.y, hh[1], stage, R),
                                                          rc_depth(v.z, hh[2], stage, R), rc_depth(v.w, hh[3], stage, R));
     return;

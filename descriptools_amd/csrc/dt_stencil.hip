@@ -687,15 +687,17 @@ __global__ __launch_bounds__(256) void k_d8_fix(const float *__restrict__ dem, D
   }
 }
 
-// bytes of the mark / mask workspace of the fused slope + TI + MTI launch for an H x W window
-size_t dt_stencil_aux_bytes(int64_t H, int64_t W) {
-  int64_t ntiles = 0;  // the largest tile count of the three tile geometries (they differ on ragged rasters)
+// bytes of the mark / mask workspace for an H x W window: DtStencilAux at the largest tile count of the three tile
+// geometries (they differ on ragged rasters)
+static int64_t sd_aux_tiles(int64_t H, int64_t W) {
+  int64_t ntiles = 0;
   for (int wx = 1; wx <= 4; wx *= 2) {
     const int64_t tx = SD_TX * wx, ty = SD_TY / wx, n = ((W + tx - 1) / tx) * ((H + ty - 1) / ty);
     ntiles = n > ntiles ? n : ntiles;
   }
-  return dt_align256((size_t)ntiles) + (size_t)ntiles * 512;
+  return ntiles;
 }
+size_t dt_stencil_aux_bytes(int64_t H, int64_t W) { return dt_stencil_aux_layout(sd_aux_tiles(H, W), nullptr).bytes; }
 
 // the fused slope + TI + MTI pair (hot kernel + fix-up of the flagged cells) for one tile geometry / accumulation width
 template <typename AccT, int WX>
@@ -708,8 +710,9 @@ static int launch_slope_twi(hipStream_t s, const DtWin &w, const float *dem, dou
   DT_REQUIRE(aux != nullptr, "fused TWI needs its mark / mask workspace");
   dim3 g((unsigned)ntiles), b(256);
   const bool ws = slope != nullptr, wr = slope_rad != nullptr;
-  uint8_t *mark = (uint8_t *)aux;
-  uint16_t *lmask = (uint16_t *)((char *)aux + dt_align256((size_t)ntiles));
+  const DtStencilAux A = dt_stencil_aux_layout(ntiles, aux);
+  uint8_t *mark = A.mark;
+  uint16_t *lmask = A.lmask;
   const double kc = 100.0 / px, kd = 100.0 / (px * sqrt(2.0)), lnpx2 = log(px * px);
   const DtLogEntry *g_tab = dt_math_device_table(s);
 #define DT_HOT(S, R, N)                                                                                             \
@@ -737,7 +740,7 @@ static int launch_slope_twi(hipStream_t s, const DtWin &w, const float *dem, dou
   else if (wr) DT_HOT(false, true, 1);
   else DT_HOT(false, false, 1);
 #undef DT_HOT
-  unsigned fix_blocks = SD_FIX_SPLIT * (unsigned)((ntiles + 255) / 256 < 1024 ? (ntiles + 255) / 256 : 1024);
+  unsigned fix_blocks = SD_FIX_SPLIT * dt_capped_grid(ntiles, 1024);
   hipLaunchKernelGGL((k_slope_twi_fix<AccT, WX>), dim3(fix_blocks), b, 0, s, dem, w, px, slope, slope_rad, acc, n_top,
                      lnpx2, ti, mti, tiles_x, tiles_y, vec_ok, mark, lmask, g_tab);
   return DT_OK;
@@ -757,14 +760,12 @@ int dt_launch_d8_slope(hipStream_t s, const DtWin &w, const float *dem, double p
   const int vec_ok = (w.W % 4 == 0) && (w.ld % 4 == 0) && (((uintptr_t)dem | (uintptr_t)slope) & 15) == 0 &&
                      ((uintptr_t)fdr & 3) == 0;
   dim3 g((unsigned)ntiles), b(256);
-  uint8_t *mark = (uint8_t *)aux, *smark = (uint8_t *)smarks;
-  uint16_t *lmask = (uint16_t *)((char *)aux + dt_align256((size_t)ntiles));
-  uint16_t *slmask = (uint16_t *)((char *)smarks + dt_align256((size_t)ntiles));
+  const DtStencilAux A = dt_stencil_aux_layout(ntiles, aux), S = dt_stencil_aux_layout(ntiles, smarks);
   const double kc = 100.0 / px, kd = 100.0 / (px * sqrt(2.0));
-  hipLaunchKernelGGL(k_d8_slope, g, b, 0, s, dem, w, fdr, tiles_x, tiles_y, vec_ok, mark, lmask, nod4, ldm, kc, kd, slope,
-                     smark, slmask, dt_debug_get(DT_DBG_TWI_FLAG_ALL) ? 0xFFFFu : 0u);
-  unsigned fix_blocks = SD_FIX_SPLIT * (unsigned)((ntiles + 255) / 256 < 1024 ? (ntiles + 255) / 256 : 1024);
-  hipLaunchKernelGGL(k_d8_fix, dim3(fix_blocks), b, 0, s, dem, w, px, fdr, tiles_x, tiles_y, vec_ok, mark, lmask);
+  hipLaunchKernelGGL(k_d8_slope, g, b, 0, s, dem, w, fdr, tiles_x, tiles_y, vec_ok, A.mark, A.lmask, nod4, ldm, kc, kd,
+                     slope, S.mark, S.lmask, dt_debug_get(DT_DBG_TWI_FLAG_ALL) ? 0xFFFFu : 0u);
+  unsigned fix_blocks = SD_FIX_SPLIT * dt_capped_grid(ntiles, 1024);
+  hipLaunchKernelGGL(k_d8_fix, dim3(fix_blocks), b, 0, s, dem, w, px, fdr, tiles_x, tiles_y, vec_ok, A.mark, A.lmask);
   return DT_OK;
 }
 
@@ -778,12 +779,11 @@ int dt_launch_slope_twi_fix(hipStream_t s, const DtWin &w, const float *dem, dou
   const int64_t ntiles = (int64_t)tiles_x * tiles_y;
   DT_REQUIRE(ntiles < (1ll << 31), "raster too large for one launch");
   const int vec_ok = (w.W % 4 == 0) && (w.ld % 4 == 0) && ((uintptr_t)dem & 15) == 0;  // (the staging's loads)
-  const uint8_t *mark = (const uint8_t *)smarks;
-  const uint16_t *lmask = (const uint16_t *)((const char *)smarks + dt_align256((size_t)ntiles));
-  unsigned fix_blocks = SD_FIX_SPLIT * (unsigned)((ntiles + 255) / 256 < 1024 ? (ntiles + 255) / 256 : 1024);
+  const DtStencilAux S = dt_stencil_aux_layout(ntiles, smarks);
+  unsigned fix_blocks = SD_FIX_SPLIT * dt_capped_grid(ntiles, 1024);
   hipLaunchKernelGGL((k_slope_twi_fix<int32_t, 1>), dim3(fix_blocks), dim3(256), 0, s, dem, w, px, slope, (float *)nullptr,
-                     acc, n_top, log(px * px), ti, mti, tiles_x, tiles_y, vec_ok, mark, lmask,
-                     dt_math_device_table(s));
+                     acc, n_top, log(px * px), ti, mti, tiles_x, tiles_y, vec_ok, (const uint8_t *)S.mark,
+                     (const uint16_t *)S.lmask, dt_math_device_table(s));
   return DT_OK;
 }
 
@@ -829,11 +829,10 @@ int dt_launch_stencil(hipStream_t s, const DtWin &w, const float *dem, double px
   else if (wf && wr) DT_GO(false, true, true);
   else if (ws) DT_GO(true, false, false);
   else if (wf && aux) {  // D8 alone with a workspace: the hot / cold pair
-    uint8_t *mark = (uint8_t *)aux;
-    uint16_t *lmask = (uint16_t *)((char *)aux + dt_align256((size_t)ntiles));
-    hipLaunchKernelGGL(k_d8<false>, g, b, 0, s, dem, w, fdr, tiles_x, tiles_y, vec_ok, mark, lmask, nod4, ldm);
-    unsigned fix_blocks = SD_FIX_SPLIT * (unsigned)((ntiles + 255) / 256 < 1024 ? (ntiles + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_d8_fix, dim3(fix_blocks), b, 0, s, dem, w, px, fdr, tiles_x, tiles_y, vec_ok, mark, lmask);
+    const DtStencilAux A = dt_stencil_aux_layout(ntiles, aux);
+    hipLaunchKernelGGL(k_d8<false>, g, b, 0, s, dem, w, fdr, tiles_x, tiles_y, vec_ok, A.mark, A.lmask, nod4, ldm);
+    unsigned fix_blocks = SD_FIX_SPLIT * dt_capped_grid(ntiles, 1024);
+    hipLaunchKernelGGL(k_d8_fix, dim3(fix_blocks), b, 0, s, dem, w, px, fdr, tiles_x, tiles_y, vec_ok, A.mark, A.lmask);
   } else if (wf) DT_GO(false, true, false);
   else if (wr) DT_GO(false, false, true);
 #undef DT_GO

@@ -5,8 +5,8 @@
 // threshold), in ten launches plus the pointer-doubling rounds:
 //   so_info     full raster, 2048 cells per block: child count and single-child direction per cell (info byte) from
 //               fdr / river rows staged in LDS with a one-cell halo; network cells per block
-//   so_scan     three launches: exclusive scan of the block counts -> compact id of each block's first network
-//               cell, M
+//   so_scan     three launches (dt_launch_count_scan, shared with dt_reaches.hip): exclusive scan of the block
+//               counts -> compact id of each block's first network cell, M
 //   so_compact  full raster: compact id of each network cell (block scan again); pos, map, cinfo
 //   so_links    compact: down pointer (flagged when it enters a confluence), link pointer J (the single child, or
 //               ~self at a head), countdown word initialised
@@ -27,9 +27,7 @@
 // on a D8 cycle never reaches pending 0: its link's cells come out as -100.
 #include "dt_kernels.h"
 
-#define SO_CPT 8                    // cells per thread in the full-raster passes
-#define SO_CHUNK (256 * SO_CPT)     // cells per block
-#define SO_SEG (SO_CHUNK + 2)       // a staged row segment: the chunk's cells and one halo cell on each side
+#define SO_SEG (DT_SCAN_CHUNK + 2)  // a staged row segment: the chunk's cells and one halo cell on each side
 #define SO_NET 0x80u                // info byte: network cell | child count (bits 0-3) | single child's dir (4-6)
 #define SO_TAIL_J 0x80000000u       // down word: the downstream cell is a confluence (its link ends here)
 #define SO_NONE 0xFFFFFFFFu         // down word: network outlet
@@ -37,40 +35,6 @@
 #define SO_M_SH 32
 #define SO_TIE (1ull << 38)
 #define SO_SUM_MASK 0xFFFFFFFFull
-
-// in-raster neighbour i at (dy, dx) is a child when its code points back at the centre: the code of direction (-dy, -dx)
-__device__ __forceinline__ uint32_t so_back_code(int i) {
-  // neighbour bit index i -> the code whose step is the opposite of i's: E<->W, SE<->NW, S<->N, SW<->NE
-  return 1u << ((i + 4) & 7);
-}
-
-__device__ __forceinline__ void so_delta(int i, int &dy, int &dx) {
-  dx = (int)((DT_DX_PACK >> (2 * i)) & 3u) - 1;
-  dy = (int)((DT_DY_PACK >> (2 * i)) & 3u) - 1;
-}
-
-// exclusive block scan of one 32-bit value per thread (256 threads); *total = the block's sum
-__device__ __forceinline__ uint32_t so_block_scan(uint32_t v, uint32_t *s_w, uint32_t *total) {
-  const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)x, o);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) s_w[wv] = x;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint32_t t = s_w[k];
-    before += k < wv ? t : 0u;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
 
 __device__ __forceinline__ uint32_t so_net_count(uint2 v) {
   return (uint32_t)__popc(v.x & 0x80808080u) + (uint32_t)__popc(v.y & 0x80808080u);
@@ -84,7 +48,7 @@ __global__ __launch_bounds__(256) void k_so_info(const uint8_t *__restrict__ fdr
   __shared__ uint8_t s_r[3][SO_SEG + 2];
   __shared__ uint32_t s_w[4];
   const int64_t N = H * W;
-  const int64_t base = (int64_t)blockIdx.x * SO_CHUNK;
+  const int64_t base = (int64_t)blockIdx.x * DT_SCAN_CHUNK;
   for (int r = 0; r < 3; r++) {
     const int64_t st = base + (int64_t)(r - 1) * W - 1;
     for (int i = threadIdx.x; i < SO_SEG; i += 256) {
@@ -95,12 +59,12 @@ __global__ __launch_bounds__(256) void k_so_info(const uint8_t *__restrict__ fdr
     }
   }
   __syncthreads();
-  const int l0 = (int)threadIdx.x * SO_CPT;
+  const int l0 = (int)threadIdx.x * DT_SCAN_CPT;
   const int64_t f0 = base + l0;
   int64_t x = f0 % W;
   uint32_t word[2] = {0u, 0u}, cnt_net = 0;
 #pragma unroll
-  for (int k = 0; k < SO_CPT; k++) {
+  for (int k = 0; k < DT_SCAN_CPT; k++) {
     const int li = l0 + k + 1;
     uint32_t b = 0;
     if (f0 + k < N && s_r[1][li]) {
@@ -108,9 +72,9 @@ __global__ __launch_bounds__(256) void k_so_info(const uint8_t *__restrict__ fdr
 #pragma unroll
       for (int i = 0; i < 8; i++) {
         int dy, dx;
-        so_delta(i, dy, dx);
+        dt_nb_delta(i, dy, dx);
         const bool xin = x + dx >= 0 && x + dx < W;
-        if (xin && s_r[dy + 1][li + dx] && s_f[dy + 1][li + dx] == so_back_code(i)) {
+        if (xin && s_r[dy + 1][li + dx] && s_f[dy + 1][li + dx] == dt_nb_back_code(i)) {
           cnt++;
           dir = (uint32_t)i;
         }
@@ -123,23 +87,23 @@ __global__ __launch_bounds__(256) void k_so_info(const uint8_t *__restrict__ fdr
   }
   *reinterpret_cast<uint2 *>(info + f0) = make_uint2(word[0], word[1]);
   uint32_t total;
-  so_block_scan(cnt_net, s_w, &total);
+  dt_block_scan_256(cnt_net, s_w, &total);
   if (threadIdx.x == 0) bcount[blockIdx.x] = total;
 }
 
 // ---- so_scan ---------------------------------------------------------------------------------------------------------
-// Exclusive scan of the per-block counts in three steps: so_gsum sums groups of SO_CHUNK counts, so_gscan (one block)
-// scans the group sums, so_expand scans each group again from its group's offset.  offsets[b] = network cells before
-// block b; meta[0] = M.
+// Exclusive scan of the per-block counts in three steps (dt_launch_count_scan): so_gsum sums groups of DT_SCAN_CHUNK
+// counts, so_gscan (one block) scans the group sums, so_expand scans each group again from its group's offset.
+// offsets[b] = the counts before block b (here: network cells); meta[0] = the total (M).
 __global__ __launch_bounds__(256) void k_so_gsum(const uint32_t *__restrict__ bcount, int64_t nblk,
                                                  uint32_t *__restrict__ gsum) {
   __shared__ uint32_t s_w[4];
-  const int64_t b0 = (int64_t)blockIdx.x * SO_CHUNK + (int64_t)threadIdx.x * SO_CPT;
+  const int64_t b0 = (int64_t)blockIdx.x * DT_SCAN_CHUNK + (int64_t)threadIdx.x * DT_SCAN_CPT;
   uint32_t v = 0;
 #pragma unroll
-  for (int k = 0; k < SO_CPT; k++) v += b0 + k < nblk ? bcount[b0 + k] : 0u;
+  for (int k = 0; k < DT_SCAN_CPT; k++) v += b0 + k < nblk ? bcount[b0 + k] : 0u;
   uint32_t total;
-  so_block_scan(v, s_w, &total);
+  dt_block_scan_256(v, s_w, &total);
   if (threadIdx.x == 0) gsum[blockIdx.x] = total;
 }
 
@@ -171,17 +135,17 @@ __global__ __launch_bounds__(256) void k_so_gscan(const uint32_t *__restrict__ g
 __global__ __launch_bounds__(256) void k_so_expand(const uint32_t *__restrict__ bcount, int64_t nblk,
                                                    const int64_t *__restrict__ goff, int64_t *__restrict__ offsets) {
   __shared__ uint32_t s_w[4];
-  const int64_t b0 = (int64_t)blockIdx.x * SO_CHUNK + (int64_t)threadIdx.x * SO_CPT;
-  uint32_t c[SO_CPT], v = 0;
+  const int64_t b0 = (int64_t)blockIdx.x * DT_SCAN_CHUNK + (int64_t)threadIdx.x * DT_SCAN_CPT;
+  uint32_t c[DT_SCAN_CPT], v = 0;
 #pragma unroll
-  for (int k = 0; k < SO_CPT; k++) {
+  for (int k = 0; k < DT_SCAN_CPT; k++) {
     c[k] = b0 + k < nblk ? bcount[b0 + k] : 0u;
     v += c[k];
   }
   uint32_t total;
-  int64_t run = goff[blockIdx.x] + so_block_scan(v, s_w, &total);
+  int64_t run = goff[blockIdx.x] + dt_block_scan_256(v, s_w, &total);
 #pragma unroll
-  for (int k = 0; k < SO_CPT; k++) {
+  for (int k = 0; k < DT_SCAN_CPT; k++) {
     if (b0 + k < nblk) offsets[b0 + k] = run;
     run += c[k];
   }
@@ -192,14 +156,14 @@ __global__ __launch_bounds__(256) void k_so_compact(const uint8_t *__restrict__ 
                                                     int64_t *__restrict__ pos, int32_t *__restrict__ map,
                                                     uint8_t *__restrict__ cinfo) {
   __shared__ uint32_t s_w[4];
-  const int64_t f0 = (int64_t)blockIdx.x * SO_CHUNK + (int64_t)threadIdx.x * SO_CPT;
+  const int64_t f0 = (int64_t)blockIdx.x * DT_SCAN_CHUNK + (int64_t)threadIdx.x * DT_SCAN_CPT;
   const uint2 v = *reinterpret_cast<const uint2 *>(info + f0);
   uint32_t total;
-  const uint32_t ex = so_block_scan(so_net_count(v), s_w, &total);
+  const uint32_t ex = dt_block_scan_256(so_net_count(v), s_w, &total);
   int64_t cid = offsets[blockIdx.x] + ex;
   const uint32_t w2[2] = {v.x, v.y};
 #pragma unroll
-  for (int k = 0; k < SO_CPT; k++) {
+  for (int k = 0; k < DT_SCAN_CPT; k++) {
     const uint32_t b = (w2[k >> 2] >> (8 * (k & 3))) & 0xFFu;
     if (b & SO_NET) {
       pos[cid] = f0 + k;
@@ -237,7 +201,7 @@ __global__ __launch_bounds__(256) void k_so_links(const uint8_t *__restrict__ fd
     int32_t j = ~(int32_t)c;
     if (cnt == 1u) {
       int dy, dx;
-      so_delta((int)((ci >> 4) & 7u), dy, dx);
+      dt_nb_delta((int)((ci >> 4) & 7u), dy, dx);
       j = map[f + dy * W + dx];
     }
     J[c] = j;
@@ -319,17 +283,17 @@ __global__ __launch_bounds__(256) void k_so_scatter(const uint8_t *__restrict__ 
                                                     int8_t *__restrict__ strahler, int64_t *__restrict__ shreve,
                                                     int64_t *__restrict__ link) {
   __shared__ uint32_t s_w[4];
-  const int64_t f0 = (int64_t)blockIdx.x * SO_CHUNK + (int64_t)threadIdx.x * SO_CPT;
+  const int64_t f0 = (int64_t)blockIdx.x * DT_SCAN_CHUNK + (int64_t)threadIdx.x * DT_SCAN_CPT;
   const uint2 v = *reinterpret_cast<const uint2 *>(info + f0);
   uint32_t total;
-  const uint32_t ex = so_block_scan(so_net_count(v), s_w, &total);
+  const uint32_t ex = dt_block_scan_256(so_net_count(v), s_w, &total);
   if (f0 >= N) return;
   int64_t cid = offsets[blockIdx.x] + ex;
   const uint32_t w2[2] = {v.x, v.y};
   uint32_t so[2] = {0u, 0u};
-  int64_t sh[SO_CPT], lk[SO_CPT];
+  int64_t sh[DT_SCAN_CPT], lk[DT_SCAN_CPT];
 #pragma unroll
-  for (int k = 0; k < SO_CPT; k++) {
+  for (int k = 0; k < DT_SCAN_CPT; k++) {
     const uint32_t b = (w2[k >> 2] >> (8 * (k & 3))) & 0xFFu;
     uint32_t o = 0u;
     int64_t s = 0, l = -100;
@@ -350,17 +314,17 @@ __global__ __launch_bounds__(256) void k_so_scatter(const uint8_t *__restrict__ 
     sh[k] = s;
     lk[k] = l;
   }
-  if (VEC && f0 + SO_CPT <= N) {
+  if (VEC && f0 + DT_SCAN_CPT <= N) {
     *reinterpret_cast<uint2 *>(strahler + f0) = make_uint2(so[0], so[1]);
 #pragma unroll
-    for (int k = 0; k < SO_CPT; k += 2) {
+    for (int k = 0; k < DT_SCAN_CPT; k += 2) {
       if (shreve) *reinterpret_cast<longlong2 *>(shreve + f0 + k) = make_longlong2(sh[k], sh[k + 1]);
       if (link) *reinterpret_cast<longlong2 *>(link + f0 + k) = make_longlong2(lk[k], lk[k + 1]);
     }
     return;
   }
 #pragma unroll
-  for (int k = 0; k < SO_CPT; k++) {
+  for (int k = 0; k < DT_SCAN_CPT; k++) {
     if (f0 + k >= N) break;
     strahler[f0 + k] = (int8_t)((so[k >> 2] >> (8 * (k & 3))) & 0xFFu);
     if (shreve) shreve[f0 + k] = sh[k];
@@ -370,53 +334,55 @@ __global__ __launch_bounds__(256) void k_so_scatter(const uint8_t *__restrict__ 
 
 // ---- launcher --------------------------------------------------------------------------------------------------------
 struct SoLayout {
-  int64_t nblk, N;
-  uint8_t *info;
-  int32_t *map;  // compact id per network cell; jpar once so_links has read it
-  uint32_t *bcount, *gsum, *flags;
-  int64_t *offsets, *goff, *meta, *pos;
-  int64_t ng;
-  uint8_t *cinfo;
-  uint32_t *down;
-  int32_t *J;
+  int64_t N;
+  DtCountScan scan;
+  uint32_t *flags, *down;
+  uint8_t *info, *cinfo;
+  int32_t *map, *J;  // map: compact id per network cell; jpar once so_links has read it
+  int64_t *pos;
   unsigned long long *st;
   size_t bytes;
 };
 
-static int so_rounds(int64_t N) {
-  int r = 0;
-  while (r < 62 && (1ll << r) < N) r++;
-  return r + 1;
-}
-
-static SoLayout so_layout(int64_t H, int64_t W, char *p) {
+static SoLayout so_layout(int64_t H, int64_t W, void *scratch) {
   SoLayout L;
   L.N = H * W;
-  L.nblk = (L.N + SO_CHUNK - 1) / SO_CHUNK;
-  L.ng = (L.nblk + SO_CHUNK - 1) / SO_CHUNK;
-  const size_t Np = (size_t)L.nblk * SO_CHUNK;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char *q = p ? p + off : nullptr;
-    off += dt_align256(b);
-    return q;
-  };
-  L.flags = (uint32_t *)take(sizeof(uint32_t) * 64);
-  L.meta = (int64_t *)take(sizeof(int64_t) * 2);
-  L.info = (uint8_t *)take(Np);
-  L.map = (int32_t *)take(Np * 4);
-  L.bcount = (uint32_t *)take((size_t)L.nblk * 4);
-  L.offsets = (int64_t *)take((size_t)L.nblk * 8);
-  L.gsum = (uint32_t *)take((size_t)L.ng * 4);
-  L.goff = (int64_t *)take((size_t)L.ng * 8);
+  const size_t Np = (size_t)dt_scan_blocks(L.N) * DT_SCAN_CHUNK;
+  DtCarver c(scratch);
+  L.flags = c.take<uint32_t>(64);
+  int64_t *meta = c.take<int64_t>(2);
+  L.info = c.take<uint8_t>(Np);
+  L.map = c.take<int32_t>(Np);
+  L.scan = dt_count_scan_carve(c, L.N, meta);
   // compact arrays: M <= N cells (M is on the device only)
-  L.pos = (int64_t *)take((size_t)L.N * 8);
-  L.st = (unsigned long long *)take((size_t)L.N * 8);
-  L.down = (uint32_t *)take((size_t)L.N * 4);
-  L.J = (int32_t *)take((size_t)L.N * 4);
-  L.cinfo = (uint8_t *)take((size_t)L.N);
-  L.bytes = off;
+  L.pos = c.take<int64_t>((size_t)L.N);
+  L.st = c.take<unsigned long long>((size_t)L.N);
+  L.down = c.take<uint32_t>((size_t)L.N);
+  L.J = c.take<int32_t>((size_t)L.N);
+  L.cinfo = c.take<uint8_t>((size_t)L.N);
+  L.bytes = c.bytes();
   return L;
+}
+
+DtCountScan dt_count_scan_carve(DtCarver &c, int64_t n, int64_t *meta) {
+  DtCountScan cs;
+  cs.nblk = dt_scan_blocks(n);
+  cs.ng = dt_scan_blocks(cs.nblk);
+  cs.meta = meta;
+  cs.bcount = c.take<uint32_t>((size_t)cs.nblk);
+  cs.offsets = c.take<int64_t>((size_t)cs.nblk);
+  cs.gsum = c.take<uint32_t>((size_t)cs.ng);
+  cs.goff = c.take<int64_t>((size_t)cs.ng);
+  return cs;
+}
+
+int dt_launch_count_scan(hipStream_t s, const DtCountScan &cs, int64_t nblk) {
+  DT_REQUIRE(nblk <= cs.nblk, "more block counts than the scan was carved for");
+  dim3 b(256), gg((unsigned)cs.ng);
+  hipLaunchKernelGGL(k_so_gsum, gg, b, 0, s, cs.bcount, nblk, cs.gsum);
+  hipLaunchKernelGGL(k_so_gscan, dim3(1), b, 0, s, cs.gsum, cs.ng, cs.goff, cs.meta);
+  hipLaunchKernelGGL(k_so_expand, gg, b, 0, s, cs.bcount, nblk, cs.goff, cs.offsets);
+  return DT_OK;
 }
 
 size_t dt_stream_order_scratch(int64_t H, int64_t W) { return so_layout(H, W, nullptr).bytes; }
@@ -424,35 +390,33 @@ size_t dt_stream_order_scratch(int64_t H, int64_t W) { return so_layout(H, W, nu
 int dt_launch_stream_order(hipStream_t s, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W, void *scratch,
                            size_t scratch_bytes, int8_t *strahler, int64_t *shreve, int64_t *link, int64_t *m_host) {
   if (H == 0 || W == 0) return DT_OK;
-  SoLayout L = so_layout(H, W, (char *)scratch);
+  SoLayout L = so_layout(H, W, scratch);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
-  const int R = so_rounds(L.N);
+  const DtCountScan &cs = L.scan;
+  const int R = dt_doubling_rounds(L.N);
   DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 64, s));
-  dim3 b(256), gr((unsigned)L.nblk), gg((unsigned)L.ng);
-  hipLaunchKernelGGL(k_so_info, gr, b, 0, s, fdr, river, H, W, L.info, L.bcount);
-  hipLaunchKernelGGL(k_so_gsum, gg, b, 0, s, L.bcount, L.nblk, L.gsum);
-  hipLaunchKernelGGL(k_so_gscan, dim3(1), b, 0, s, L.gsum, L.ng, L.goff, L.meta);
-  hipLaunchKernelGGL(k_so_expand, gg, b, 0, s, L.bcount, L.nblk, L.goff, L.offsets);
+  dim3 b(256), gr((unsigned)cs.nblk);
+  hipLaunchKernelGGL(k_so_info, gr, b, 0, s, fdr, river, H, W, L.info, cs.bcount);
+  DT_TRY(dt_launch_count_scan(s, cs, cs.nblk));
   if (m_host) {
     // rasters of 2^31 cells or more: the compact ids are 31-bit, so M is checked before the compact passes
-    DT_HIP(hipMemcpyAsync(m_host, L.meta, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    DT_HIP(hipMemcpyAsync(m_host, cs.meta, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     DT_HIP(hipStreamSynchronize(s));
     DT_REQUIRE(*m_host < (1ll << 31), "the river network has 2^31 cells or more");
   }
-  hipLaunchKernelGGL(k_so_compact, gr, b, 0, s, L.info, L.offsets, L.pos, L.map, L.cinfo);
+  hipLaunchKernelGGL(k_so_compact, gr, b, 0, s, L.info, cs.offsets, L.pos, L.map, L.cinfo);
   // compact passes: a grid that covers M <= N cells at one cell per thread up to 8 blocks per CU, strided beyond
-  const int64_t want = (L.N + 255) / 256;
-  dim3 gc((unsigned)(want < 2048 ? want : 2048));
-  hipLaunchKernelGGL(k_so_links, gc, b, 0, s, fdr, H, W, L.info, L.map, L.meta, L.pos, L.cinfo, L.down, L.J, L.st);
-  for (int r = 0; r < R; r++) hipLaunchKernelGGL(k_so_jump, gc, b, 0, s, L.meta, L.J, L.flags, r);
+  dim3 gc(dt_capped_grid(L.N, 2048));
+  hipLaunchKernelGGL(k_so_links, gc, b, 0, s, fdr, H, W, L.info, L.map, cs.meta, L.pos, L.cinfo, L.down, L.J, L.st);
+  for (int r = 0; r < R; r++) hipLaunchKernelGGL(k_so_jump, gc, b, 0, s, cs.meta, L.J, L.flags, r);
   int32_t *jpar = L.map;
-  hipLaunchKernelGGL(k_so_tails, gc, b, 0, s, L.meta, L.J, L.down, jpar);
-  hipLaunchKernelGGL(k_so_count, gc, b, 0, s, L.meta, L.cinfo, jpar, L.st);
+  hipLaunchKernelGGL(k_so_tails, gc, b, 0, s, cs.meta, L.J, L.down, jpar);
+  hipLaunchKernelGGL(k_so_count, gc, b, 0, s, cs.meta, L.cinfo, jpar, L.st);
   const bool vec = ((uintptr_t)strahler & 7u) == 0 && ((uintptr_t)shreve & 15u) == 0 && ((uintptr_t)link & 15u) == 0;
   if (vec)
-    hipLaunchKernelGGL(k_so_scatter<true>, gr, b, 0, s, L.info, L.offsets, L.N, L.pos, L.J, L.st, strahler, shreve, link);
+    hipLaunchKernelGGL(k_so_scatter<true>, gr, b, 0, s, L.info, cs.offsets, L.N, L.pos, L.J, L.st, strahler, shreve, link);
   else
-    hipLaunchKernelGGL(k_so_scatter<false>, gr, b, 0, s, L.info, L.offsets, L.N, L.pos, L.J, L.st, strahler, shreve,
+    hipLaunchKernelGGL(k_so_scatter<false>, gr, b, 0, s, L.info, cs.offsets, L.N, L.pos, L.J, L.st, strahler, shreve,
                        link);
   return DT_OK;
 }

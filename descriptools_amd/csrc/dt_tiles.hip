@@ -834,23 +834,26 @@ struct FaScratch {
   unsigned long long *rec, *state, *ext;
   uint32_t *entry_of, *parent, *nxt;
   uint16_t *loc16;  // pass 1's in-tile counts, tile-major
+  void *pad;         // 256 bytes nothing reads or writes: kept so that the workspace keeps its size
   int64_t nnodes, ntiles;
   int tiles_x;
+  size_t bytes;
 };
 static FaScratch fa_layout(const DtWin &w, void *scratch) {
   FaScratch f;
   f.tiles_x = (w.W + TW - 1) / TW;
   f.ntiles = (int64_t)f.tiles_x * ((w.H + TH - 1) / TH);
   f.nnodes = f.ntiles * PS;
-  char *p = (char *)scratch;
-  size_t n8 = dt_align256((size_t)f.nnodes * 8), n4 = dt_align256((size_t)f.nnodes * 4);
-  f.rec = (unsigned long long *)p;  p += n8;
-  f.state = (unsigned long long *)p;  p += n8;  // state, ext contiguous: one memset
-  f.ext = (unsigned long long *)p;  p += n8;
-  f.entry_of = (uint32_t *)p;  p += n4;
-  f.parent = (uint32_t *)p;  p += n4;
-  f.nxt = (uint32_t *)p;  p += n4;
-  f.loc16 = (uint16_t *)p;
+  DtCarver c(scratch);
+  f.rec = c.take<unsigned long long>((size_t)f.nnodes);
+  f.state = c.take<unsigned long long>((size_t)f.nnodes);
+  f.ext = c.take<unsigned long long>((size_t)f.nnodes);
+  f.entry_of = c.take<uint32_t>((size_t)f.nnodes);
+  f.parent = c.take<uint32_t>((size_t)f.nnodes);
+  f.nxt = c.take<uint32_t>((size_t)f.nnodes);
+  f.loc16 = c.take<uint16_t>((size_t)f.ntiles * NT);
+  f.pad = c.raw(256);
+  f.bytes = c.bytes();
   return f;
 }
 // what pass 3 reads: the feeders' resolved words (rec, state) and, on the rank path, the injected ext; the scatter
@@ -862,19 +865,15 @@ static FaIn fa_inputs(const FaScratch &f, const unsigned long long *ext_perim) {
   if (dt_debug_get(DT_DBG_FA_SCATTER)) return FaIn{nullptr, nullptr, f.ext};
   return FaIn{f.rec, f.state, ext_perim ? f.ext : nullptr};
 }
-size_t dt_flowacc_tiled_scratch(int64_t H, int64_t W) {
-  int64_t ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  size_t nn = (size_t)ntiles * PS;
-  return dt_align256(nn * 8) * 3 + dt_align256(nn * 4) * 3 + 256 + dt_align256((size_t)ntiles * NT * 2);
-}
+size_t dt_flowacc_tiled_scratch(int64_t H, int64_t W) { return fa_layout(dt_full_window(H, W), nullptr).bytes; }
 
 // phase 1: tile pass + local perimeter graph.  With `rank_level` the entry successor lists are built too
 // (needed for dt_launch_fa_summary and the inflow of dt_launch_fa_finish).
 int dt_launch_fa_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, void *scratch, size_t scratch_bytes,
                        int32_t *acc32, int rank_level) {
   if (w.H == 0 || w.W == 0) return DT_OK;
-  DT_REQUIRE(scratch_bytes >= dt_flowacc_tiled_scratch(w.H, w.W), "scratch too small");
   FaScratch f = fa_layout(w, scratch);
+  DT_REQUIRE(scratch_bytes >= f.bytes, "scratch too small");
   DT_REQUIRE(f.nnodes < 0x7FFFFFF0ll, "raster too large for one device tile");
   dim3 gt((unsigned)f.ntiles), b(256), gn((unsigned)((f.nnodes + 255) / 256));
   (void)acc32;  // written by pass 3 only
@@ -1251,31 +1250,28 @@ struct FawScratch {
   uint32_t *parent;
   int64_t nnodes, ntiles;
   int tiles_x;
+  size_t bytes;
 };
 static FawScratch faw_layout(const DtWin &w, void *scratch) {
   FawScratch f;
   f.tiles_x = (w.W + TW - 1) / TW;
   f.ntiles = (int64_t)f.tiles_x * ((w.H + TH - 1) / TH);
   f.nnodes = f.ntiles * PS;
-  char *p = (char *)scratch;
-  const size_t n8 = dt_align256((size_t)f.nnodes * 8), n4 = dt_align256((size_t)f.nnodes * 4);
-  f.rec = (unsigned long long *)p;  p += n8;
-  f.state = (unsigned long long *)p;  p += n8;
-  f.parent = (uint32_t *)p;  p += n4;
-  f.loc = (unsigned long long *)p;
+  DtCarver c(scratch);
+  f.rec = c.take<unsigned long long>((size_t)f.nnodes);
+  f.state = c.take<unsigned long long>((size_t)f.nnodes);
+  f.parent = c.take<uint32_t>((size_t)f.nnodes);
+  f.loc = c.take<unsigned long long>((size_t)f.ntiles * NT);
+  f.bytes = c.bytes();
   return f;
 }
-size_t dt_flowacc_weighted_scratch(int64_t H, int64_t W) {
-  const int64_t ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  const size_t nn = (size_t)ntiles * PS;
-  return dt_align256(nn * 8) * 2 + dt_align256(nn * 4) + dt_align256((size_t)ntiles * NT * 8);
-}
+size_t dt_flowacc_weighted_scratch(int64_t H, int64_t W) { return faw_layout(dt_full_window(H, W), nullptr).bytes; }
 
 int dt_launch_flowacc_weighted(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, const double *wt,
                                int frac_bits, void *scratch, size_t scratch_bytes, double *acc, int *status) {
   if (w.H == 0 || w.W == 0) return DT_OK;
-  DT_REQUIRE(scratch_bytes >= dt_flowacc_weighted_scratch(w.H, w.W), "scratch too small");
   FawScratch f = faw_layout(w, scratch);
+  DT_REQUIRE(scratch_bytes >= f.bytes, "scratch too small");
   DT_REQUIRE(f.nnodes < 0x7FFFFFF0ll, "raster too large for one device tile");
   // every q <= 2^52 / N: no partial sum of N of them exceeds 2^52
   const unsigned long long qmax = (1ull << 52) / (unsigned long long)((int64_t)w.H * w.W);
@@ -2159,9 +2155,11 @@ __global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restric
 
 struct FhScratch {
   unsigned long long *nodes, *cache;
+  int *flags;           // the node doubling's round flags (fh_local_tail), a 256-byte block
   uint8_t *cache_wide;  // one flag per tile
   int64_t nnodes, ntiles, P;
   int tiles_x;
+  size_t bytes;
 };
 static FhScratch fh_layout(const DtWin &w, void *scratch) {
   FhScratch f;
@@ -2169,32 +2167,30 @@ static FhScratch fh_layout(const DtWin &w, void *scratch) {
   f.ntiles = (int64_t)f.tiles_x * ((w.H + TH - 1) / TH);
   f.nnodes = f.ntiles * PS;
   f.P = dt_perim_count(w.H, w.W);
-  f.nodes = (unsigned long long *)scratch;
-  f.cache = (unsigned long long *)((char *)scratch + dt_align256(((size_t)f.nnodes + (size_t)f.P) * 8));
-  f.cache_wide = (uint8_t *)f.cache + dt_align256((size_t)f.ntiles * NT * 8) + 256;  // after the round flags
+  DtCarver c(scratch);
+  f.nodes = c.take<unsigned long long>((size_t)f.nnodes + (size_t)f.P);
+  f.cache = c.take<unsigned long long>((size_t)f.ntiles * NT);
+  f.flags = (int *)c.raw(256);
+  f.cache_wide = c.take<uint8_t>((size_t)f.ntiles);
+  f.bytes = c.bytes();
   return f;
 }
-size_t dt_flowhand_tiled_scratch(int64_t H, int64_t W) {
-  int64_t ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  return dt_align256(((size_t)ntiles * PS + (size_t)dt_perim_count((int)H, (int)W)) * 8) +
-         dt_align256((size_t)ntiles * NT * 8) + 256 + dt_align256((size_t)ntiles);
-}
+size_t dt_flowhand_tiled_scratch(int64_t H, int64_t W) { return fh_layout(dt_full_window(H, W), nullptr).bytes; }
 
 // what follows the narrow tile pass in phase 1: the 64-bit solve for the tiles it had to give up (usually none: the
 // launch is 2048 workgroups that look at 32 flags each and leave), the ghosts, the perimeter node doubling
 static int fh_local_tail(hipStream_t s, const DtWin &w, const uint8_t *fdr, const int8_t *river, const FhScratch &f) {
-  dim3 gt((unsigned)f.ntiles), b(256), gn((unsigned)((f.nnodes + f.P + 255) / 256));
+  dim3 gt((unsigned)f.ntiles), b(256);
   hipLaunchKernelGGL(k_fh_tile1, dim3(gt.x < 2048u ? gt.x : 2048u), b, 0, s, fdr, river, w, f.tiles_x,
                      (uint32_t)f.nnodes, f.nodes, f.cache, f.cache_wide, 1, (int)f.ntiles);
   hipLaunchKernelGGL(k_fh_ghost_init, dim3((unsigned)((f.P + 255) / 256)), b, 0, s, f.nodes, (uint32_t)f.nnodes, f.P);
   // 8 launches of 3 jumps resolve every chain of <= 20000 moves (each node hop is >= 1 move; the resolved
   // distance at least quadruples per launch: 4^8 > 20000).  HAND's first phase at 16384^2: 1.40 ms with 15 x 1,
   // 1.33 with 10 x 2, 1.30 with 8 x 3 or 7 x 4.
-  int *flags = (int *)((char *)f.cache + dt_align256((size_t)f.ntiles * NT * 8));  // the layout's spare 256 bytes
-  DT_HIP(hipMemsetAsync(flags, 0, 64, s));
-  dim3 gj(gn.x < 4096u ? gn.x : 4096u);  // grid-stride: a quiet round costs a few microseconds
+  DT_HIP(hipMemsetAsync(f.flags, 0, 64, s));
+  dim3 gj(dt_capped_grid(f.nnodes + f.P, 4096));  // grid-stride: a quiet round costs a few microseconds
   for (int r = 0; r < 8; r++)
-    hipLaunchKernelGGL(k_fh_node_jump, gj, b, 0, s, f.nodes, f.nnodes + f.P, flags, r, 3);
+    hipLaunchKernelGGL(k_fh_node_jump, gj, b, 0, s, f.nodes, f.nnodes + f.P, f.flags, r, 3);
   return DT_OK;
 }
 
@@ -2202,8 +2198,8 @@ static int fh_local_tail(hipStream_t s, const DtWin &w, const uint8_t *fdr, cons
 int dt_launch_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const int8_t *river, void *scratch,
                        size_t scratch_bytes) {
   if (w.H == 0 || w.W == 0) return DT_OK;
-  DT_REQUIRE(scratch_bytes >= dt_flowhand_tiled_scratch(w.H, w.W), "scratch too small");
   FhScratch f = fh_layout(w, scratch);
+  DT_REQUIRE(scratch_bytes >= f.bytes, "scratch too small");
   DT_REQUIRE(f.nnodes + f.P < 0x7FFFFFF0ll, "raster too large for one device tile");
   hipLaunchKernelGGL(k_fh_tile1n, dim3((unsigned)f.ntiles), dim3(256), 0, s, fdr, river, w, f.tiles_x,
                      (uint32_t)f.nnodes, f.nodes, f.cache, f.cache_wide);
@@ -2229,10 +2225,10 @@ int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *f
                                  int64_t river_thr, void *acc, int acc64, int8_t *river, int *status,
                                  const uint8_t *nod4, int ldm, const DtTwiEpilogue *twi) {
   if (w.H == 0 || w.W == 0) return DT_OK;
-  DT_REQUIRE(fh_bytes >= dt_flowhand_tiled_scratch(w.H, w.W), "scratch too small");
   DT_REQUIRE(river != nullptr, "HAND needs the river mask");
   FaScratch f = fa_layout(w, fa_scratch);
   FhScratch h = fh_layout(w, fh_scratch);
+  DT_REQUIRE(fh_bytes >= h.bytes, "scratch too small");
   DT_REQUIRE(h.nnodes + h.P < 0x7FFFFFF0ll, "raster too large for one device tile");
   dim3 gt((unsigned)f.ntiles), b(256), gn((unsigned)((f.nnodes + 255) / 256));
   if (ext_perim) {
@@ -2252,8 +2248,8 @@ int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *f
       DT_REQUIRE(dt_twi_epilogue_ok(w, acc, river, twi) && use_mask && !ext_perim,
                  "the TI / MTI epilogue takes a single raster with its nodata mask (dt_twi_epilogue_ok)");
       const int64_t stx = (w.W + 255) / 256, sntiles = stx * ((w.H + 15) / 16);  // the stencil's 256 x 16 tiles
-      TwiOut tw{twi->slope, twi->ti, twi->mti, twi->n_top, log(twi->px * twi->px), (uint8_t *)twi->marks,
-                (uint32_t *)((char *)twi->marks + dt_align256((size_t)sntiles)), (int)stx};
+      const DtStencilAux S = dt_stencil_aux_layout(sntiles, twi->marks);
+      TwiOut tw{twi->slope, twi->ti, twi->mti, twi->n_top, log(twi->px * twi->px), S.mark, (uint32_t *)S.lmask, (int)stx};
       hipLaunchKernelGGL(k_fa3fh1_twi, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16,
                          (int32_t *)acc, thr, river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide, tw);
     } else if (use_mask)
@@ -2464,9 +2460,30 @@ static int rk_make_layout(int ty, int tx, const int64_t *heights, const int64_t 
   return DT_OK;
 }
 
+// the rank solves' workspace over the nn = nranks * Pmax ring cells
+struct RkScratch {
+  unsigned long long *sum, *ext;  // sum, ext, pending contiguous: one memset; HAND keeps its node words in sum
+  uint32_t *pending;
+  int32_t *entry_of, *parent;
+  uint8_t *is_src;
+  void *pad;  // 256 bytes nothing reads or writes: kept so that the workspace keeps its size
+  size_t bytes;
+};
+static RkScratch rk_scratch_layout(size_t nn, void *scratch) {
+  RkScratch ws;
+  DtCarver c(scratch);
+  ws.sum = c.take<unsigned long long>(nn);
+  ws.ext = c.take<unsigned long long>(nn);
+  ws.pending = c.take<uint32_t>(nn);
+  ws.entry_of = c.take<int32_t>(nn);
+  ws.parent = c.take<int32_t>(nn);
+  ws.is_src = c.take<uint8_t>(nn);
+  ws.pad = c.raw(256);
+  ws.bytes = c.bytes();
+  return ws;
+}
 size_t dt_rank_solve_scratch(int nranks, int64_t Pmax) {
-  size_t nn = (size_t)nranks * (size_t)Pmax;
-  return dt_align256(nn * 8) * 2 + dt_align256(nn * 4) * 3 + dt_align256(nn) + 256;
+  return rk_scratch_layout((size_t)nranks * (size_t)Pmax, nullptr).bytes;
 }
 
 // ext_out[i] (device, P_rank entries) = inflow arriving at ring cell i of `rank` (bit 63 = cycle)
@@ -2481,20 +2498,14 @@ int dt_launch_rank_solve_flowacc(hipStream_t s, int ty, int tx, const int64_t *h
   for (int k = 0; k < 8; k++) R.off[k] = k < 3 ? offs[k] : 0;
   size_t nn = (size_t)L.nranks * (size_t)Pmax;
   if (nn == 0) return DT_OK;
-  char *p = (char *)scratch;
-  unsigned long long *sum = (unsigned long long *)p;  p += dt_align256(nn * 8);  // sum, ext, pending: one memset
-  unsigned long long *ext = (unsigned long long *)p;  p += dt_align256(nn * 8);
-  uint32_t *pending = (uint32_t *)p;  p += dt_align256(nn * 4);
-  int32_t *entry_of = (int32_t *)p;  p += dt_align256(nn * 4);
-  int32_t *parent = (int32_t *)p;  p += dt_align256(nn * 4);
-  uint8_t *is_src = (uint8_t *)p;
-  DT_HIP(hipMemsetAsync(sum, 0, dt_align256(nn * 8) * 2 + dt_align256(nn * 4), s));
+  const RkScratch ws = rk_scratch_layout(nn, scratch);
+  DT_HIP(hipMemsetAsync(ws.sum, 0, (size_t)((char *)ws.entry_of - (char *)ws.sum), s));
   dim3 g((unsigned)((nn + 255) / 256)), b(256);
-  hipLaunchKernelGGL(k_rk_fa_link, g, b, 0, s, L, R, entry_of, parent, pending);
-  hipLaunchKernelGGL(k_rk_fa_sources, g, b, 0, s, (long long)nn, entry_of, pending, is_src);
-  hipLaunchKernelGGL(k_rk_fa_reduce, g, b, 0, s, L, R, entry_of, parent, is_src, pending, sum, ext);
-  hipLaunchKernelGGL(k_rk_fa_poison, g, b, 0, s, L, entry_of, pending, ext);
-  DT_HIP(hipMemcpyAsync(ext_out, ext + (size_t)rank * Pmax, (size_t)P_rank * 8, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(k_rk_fa_link, g, b, 0, s, L, R, ws.entry_of, ws.parent, ws.pending);
+  hipLaunchKernelGGL(k_rk_fa_sources, g, b, 0, s, (long long)nn, ws.entry_of, ws.pending, ws.is_src);
+  hipLaunchKernelGGL(k_rk_fa_reduce, g, b, 0, s, L, R, ws.entry_of, ws.parent, ws.is_src, ws.pending, ws.sum, ws.ext);
+  hipLaunchKernelGGL(k_rk_fa_poison, g, b, 0, s, L, ws.entry_of, ws.pending, ws.ext);
+  DT_HIP(hipMemcpyAsync(ext_out, ws.ext + (size_t)rank * Pmax, (size_t)P_rank * 8, hipMemcpyDeviceToDevice, s));
   return DT_OK;
 }
 
@@ -2565,7 +2576,7 @@ int dt_launch_rank_solve_flowhand(hipStream_t s, int ty, int tx, const int64_t *
   size_t nn = (size_t)L.nranks * (size_t)Pmax;
   if (nn == 0 || P_rank == 0) return DT_OK;
   DT_REQUIRE(nn < 0x7FFFFFF0ull, "too many ring cells");
-  unsigned long long *nodes = (unsigned long long *)scratch;
+  unsigned long long *nodes = rk_scratch_layout(nn, scratch).sum;
   dim3 g((unsigned)((nn + 255) / 256)), b(256);
   hipLaunchKernelGGL(k_rk_fh_build, g, b, 0, s, L, R, nodes);
   // every hop between ranks is >= 1 move: 8 launches of three jumps (>= 4 x each) cover the 20000-move cap
@@ -2605,8 +2616,9 @@ int dt_launch_rank_solve_flowhand_f64(hipStream_t s, int ty, int tx, const int64
   R.buf = (const unsigned char *)rows;
   R.rowbytes = rowbytes;
   for (int k = 0; k < 8; k++) R.off[k] = offs8[k];
-  if ((size_t)L.nranks * (size_t)Pmax == 0 || P_rank == 0) return DT_OK;
+  const size_t nn = (size_t)L.nranks * (size_t)Pmax;
+  if (nn == 0 || P_rank == 0) return DT_OK;
   hipLaunchKernelGGL(k_rk_fh_zr64, dim3((unsigned)((P_rank + 255) / 256)), dim3(256), 0, s, L, R,
-                     (const unsigned long long *)scratch, rank, (long long)P_rank, zr64);
+                     (const unsigned long long *)rk_scratch_layout(nn, scratch).sum, rank, (long long)P_rank, zr64);
   return DT_OK;
 }

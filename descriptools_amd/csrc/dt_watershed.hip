@@ -433,13 +433,13 @@ __global__ __launch_bounds__(256) void k_ul_tile3(const uint8_t *__restrict__ fd
       unsigned long long ext = 0ull;
 #pragma unroll
       for (int i = 0; i < 8; i++) {
-        const int dx = (int)((DT_DX_PACK >> (2 * i)) & 3u) - 1;
-        const int dy = (int)((DT_DY_PACK >> (2 * i)) & 3u) - 1;
+        int dy, dx;
+        dt_nb_delta(i, dy, dx);
         const int64_t fy = y + dy, fx = x + dx;
         if (fy < 0 || fy >= H || fx < 0 || fx >= W) continue;
         if ((fy >> 6) == T.ty && (fx >> 6) == T.tx) continue;
         const int64_t f = fy * W + fx;
-        if (fdr[f] != (uint8_t)(1u << ((i + 4) & 7))) continue;  // f's code points back at this cell
+        if (fdr[f] != (uint8_t)dt_nb_back_code(i)) continue;  // f's code points back at this cell
         if (dem && dem[f] <= -100.0f) continue;
         const uint64_t v = ws_add(S[ws_node(fy, fx, TX)], (dy != 0 && dx != 0) ? (1ull << 32) : 1ull, N);
         if (ws_greater(v, ext)) ext = v;
@@ -480,41 +480,24 @@ struct WsLayout {
   size_t bytes;
 };
 
-static WsLayout ws_layout(int64_t H, int64_t W, bool upslope, char *p) {
+static WsLayout ws_layout(int64_t H, int64_t W, bool upslope, void *scratch) {
   WsLayout L = {};
   L.TY = (H + WS_T - 1) / WS_T;
   L.TX = (W + WS_T - 1) / WS_T;
   L.NN = L.TY * L.TX * WS_SLOTS;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char *q = p ? p + off : nullptr;
-    off += dt_align256(b);
-    return q;
-  };
-  L.flags = (uint32_t *)take(sizeof(uint32_t) * 64);
+  DtCarver c(scratch);
+  L.flags = c.take<uint32_t>(64);
   if (upslope) {
     for (int i = 0; i < 2; i++) {
-      L.uptr[i] = (uint32_t *)take((size_t)L.NN * 4);
-      L.uw[i] = (unsigned long long *)take((size_t)L.NN * 8);
+      L.uptr[i] = c.take<uint32_t>((size_t)L.NN);
+      L.uw[i] = c.take<unsigned long long>((size_t)L.NN);
     }
-    L.S = (unsigned long long *)take((size_t)L.NN * 8);
+    L.S = c.take<unsigned long long>((size_t)L.NN);
   } else {
-    for (int i = 0; i < 2; i++) L.rec[i] = (uint4 *)take((size_t)L.NN * 16);
+    for (int i = 0; i < 2; i++) L.rec[i] = c.take<uint4>((size_t)L.NN);
   }
-  L.bytes = off;
+  L.bytes = c.bytes();
   return L;
-}
-
-// ceil(log2 N) + 1 rounds, at least 2
-static int ws_rounds(int64_t N) {
-  int r = 0;
-  while (r < 62 && (1ll << r) < N) r++;
-  return r + 1 < 2 ? 2 : r + 1;
-}
-
-static dim3 ws_node_grid(int64_t NN) {
-  const int64_t want = (NN + 255) / 256;
-  return dim3((unsigned)(want < 8192 ? want : 8192));
 }
 
 size_t dt_drainage_scratch(int64_t H, int64_t W) { return ws_layout(H, W, false, nullptr).bytes; }
@@ -524,15 +507,15 @@ int dt_launch_drainage(hipStream_t s, const uint8_t *fdr, const float *dem, cons
                        double px, void *scratch, size_t scratch_bytes, int64_t *target, double *length,
                        int64_t *label) {
   if (H == 0 || W == 0) return DT_OK;
-  WsLayout L = ws_layout(H, W, false, (char *)scratch);
+  WsLayout L = ws_layout(H, W, false, scratch);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
   const int64_t N = H * W;
-  const int R = ws_rounds(N);
+  const int R = std::max(2, dt_doubling_rounds(N));  // at least 2 rounds
   const double pxd = px * std::sqrt(2.0);
   DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 64, s));
   dim3 b(256), gt((unsigned)(L.TY * L.TX));
   hipLaunchKernelGGL(k_dr_tile1, gt, b, 0, s, fdr, dem, pour, H, W, L.TX, L.rec[0]);
-  const dim3 gn = ws_node_grid(L.NN);
+  const dim3 gn(dt_capped_grid(L.NN, 8192));
   for (int r = 0; r < R; r++)
     hipLaunchKernelGGL(k_dr_node, gn, b, 0, s, L.rec[r & 1], L.rec[(r & 1) ^ 1], L.NN, N, L.flags, r);
   hipLaunchKernelGGL(k_dr_tile3, gt, b, 0, s, fdr, dem, pour, H, W, L.TX, px, pxd, L.rec[0], target, length, label);
@@ -542,15 +525,15 @@ int dt_launch_drainage(hipStream_t s, const uint8_t *fdr, const float *dem, cons
 int dt_launch_upslope_length(hipStream_t s, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                              void *scratch, size_t scratch_bytes, double *length) {
   if (H == 0 || W == 0) return DT_OK;
-  WsLayout L = ws_layout(H, W, true, (char *)scratch);
+  WsLayout L = ws_layout(H, W, true, scratch);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
   const int64_t N = H * W;
-  const int R = ws_rounds(N);
+  const int R = std::max(2, dt_doubling_rounds(N));  // at least 2 rounds
   const double pxd = px * std::sqrt(2.0);
   DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 64, s));
   dim3 b(256), gt((unsigned)(L.TY * L.TX));
   hipLaunchKernelGGL(k_ul_tile1, gt, b, 0, s, fdr, dem, H, W, L.TX, L.uptr[0], L.uw[0], L.S);
-  const dim3 gn = ws_node_grid(L.NN);
+  const dim3 gn(dt_capped_grid(L.NN, 8192));
   for (int r = 0; r < R; r++)
     hipLaunchKernelGGL(k_ul_node, gn, b, 0, s, L.uptr[r & 1], L.uptr[(r & 1) ^ 1], L.uw[r & 1], L.uw[(r & 1) ^ 1],
                        L.S, L.NN, N, L.flags, r);

@@ -213,6 +213,35 @@ def test_white_noise_over_100000_reaches():
           R.inundate(cat, hand.astype(np.float64), stage))
 
 
+def test_count_scan_with_two_groups():
+    """The scan of the per-block head counts (dt_launch_count_scan) at the smallest raster that has two groups: a block
+    covers 2048 cells and a group 2048 blocks, so 2049 x 2048 cells are 2049 blocks, the last one alone in group 1.
+    Sparse heads, among them cell 0, the last cell of block 2047, the first cell of block 2048 and the raster's last
+    cell; exact against numpy.  The third level -- one thread of k_so_gscan owning several groups -- needs more than
+    2^30 cells and stays untested."""
+    from descriptools_amd import reaches
+    H, W = 2049, 2048
+    N, blk = H * W, 2048
+    rng = np.random.default_rng(7)
+    want = np.unique(np.concatenate([[0, 2048 * blk - 1, 2048 * blk, N - 1], rng.integers(0, N, 3000)]))
+    link = np.full(N, -100, np.int64)
+    link[want] = want
+    idx = link.copy()  # the heads drain to themselves, every other cell to no river cell
+    body = want[:-1] + 1  # a second cell on some links, where the next cell is no head itself
+    body = body[link[body] < 0]
+    link[body] = body - 1
+    heads = np.flatnonzero(link == np.arange(N))
+    assert heads.size == want.size and heads[heads >= 2048 * blk].size >= 2
+    rank = np.full(N, -100, np.int32)
+    rank[heads] = np.arange(heads.size, dtype=np.int32)
+    reach = np.where(link >= 0, rank[np.maximum(link, 0)], np.int32(-100)).astype(np.int32)
+    cat = np.where(idx >= 0, reach[np.maximum(idx, 0)], np.int32(-100)).astype(np.int32)
+    got = reaches.catchments(link.reshape(H, W), idx.reshape(H, W))
+    _same("heads", got.heads, heads)
+    _same("reach", got.reach, reach.reshape(H, W))
+    _same("catchment", got.catchment, cat.reshape(H, W))
+
+
 def test_every_cell_in_one_word():
     """2048^2 cells of one reach in one bin: all adds meet in one word and the count is exactly N"""
     n = 2048
