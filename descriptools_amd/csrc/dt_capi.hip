@@ -65,9 +65,7 @@ extern "C" int dt_ctx_create(int device, void *stream, dt_ctx **out) {
   c->scratch = nullptr;
   c->scratch_bytes = 0;
   c->scratch_used = 0;
-  c->scratch_owner = 0;
-  c->owner_h = c->owner_w = 0;
-  c->owner_ptr = c->owner_ptr2 = nullptr;
+  c->claim = DtScratchClaim{};
   c->scratch2 = nullptr;
   c->scratch2_bytes = 0;
   c->ev = nullptr;
@@ -251,8 +249,7 @@ int dt_scratch_reset(dt_ctx *c, size_t total) {
     c->scratch_bytes = total;
   }
   c->scratch_used = 0;
-  c->scratch_owner = 0;  // whatever two-phase state was here is about to be overwritten
-  c->owner_ptr = c->owner_ptr2 = nullptr;
+  c->claim = DtScratchClaim{};  // whatever two-phase state was here is about to be overwritten
   return DT_OK;
 }
 void *dt_scratch_take(dt_ctx *c, size_t bytes) {
@@ -309,13 +306,107 @@ static int dt_convert_window(const dt_window *in, DtWin *out) {
   return DT_OK;
 }
 
+// the shape rules of the entries that take (H, W)
 static int dt_check_hw(int64_t H, int64_t W) {
   DT_REQUIRE(H >= 0 && W >= 0, "negative raster shape");
   DT_REQUIRE(H * W < (1ll << 31), "rasters of >= 2^31 cells must be tiled (one tile per GPU)");
   return DT_OK;
 }
+// stream order: flat indices are int64, so the raster may exceed 2^31 cells (the network may not)
+static int dt_check_so(int64_t H, int64_t W) {
+  DT_REQUIRE(H >= 0 && W >= 0, "negative raster shape");
+  DT_REQUIRE(W == 0 || H <= (1ll << 42) / W, "raster too large");
+  return DT_OK;
+}
+// drainage / upslope length / D-infinity: flat indices travel in 31 or 32 bits and the kernels' coordinates in int, so
+// the raster has fewer than 2^31 cells
+static int dt_check_ws(int64_t H, int64_t W, double px) {
+  DT_REQUIRE(H >= 0 && W >= 0, "negative raster shape");
+  DT_REQUIRE(W == 0 || H < ((1ll << 31) + W - 1) / W, "raster of 2^31 cells or more");
+  DT_REQUIRE(std::isfinite(px) && px > 0.0, "px must be finite and > 0");
+  return DT_OK;
+}
+
+// ---- two-phase scratch: who owns it ------------------------------------------------------------------------------
+// The first phase of a multi-call op claims the scratch it leaves its state in, a later phase asks for the claim back:
+// dt_scratch_reset drops it, so any scratch-using call in between makes the later phase fail instead of reading
+// another op's bytes.  p2: a second region reserved beside the first (HAND's, beside flow accumulation's); in0 / in1 /
+// frac_bits: what a D-infinity continuation must name again.
+static void dt_scratch_claim(dt_ctx *c, DtScratchOwner owner, int64_t H, int64_t W, void *p, void *p2 = nullptr,
+                             const void *in0 = nullptr, const void *in1 = nullptr, int frac_bits = 0) {
+  c->claim = DtScratchClaim{owner, H, W, (char *)p, (char *)p2, {in0, in1}, frac_bits};
+}
+// the claim of `owner` on a raster of w's core shape (w NULL: of any shape), with both regions when `two`; fails with
+// the entry's own message
+static int dt_scratch_claimed(dt_ctx *c, DtScratchOwner owner, const DtWin *w, bool two, const char *msg,
+                              const DtScratchClaim **out) {
+  const DtScratchClaim &k = c->claim;
+  DT_REQUIRE(c->scratch && k.owner == owner && (!w || (k.h == w->H && k.w == w->W)) && (!two || k.ptr2), msg);
+  *out = &k;
+  return DT_OK;
+}
+
+// after a launch: what the launcher returned, then what the runtime says about the launch
+static int dt_launched(int rc) {
+  DT_TRY(rc);
+  DT_HIP(hipGetLastError());
+  return DT_OK;
+}
 
 // ---- device tier ------------------------------------------------------------------------------
+// One device-tier call.  It opens on a context alone, on a context and a raster shape (checked by dt_check_hw, by
+// another rule of that signature, or by dt_check_ws when a pixel size is given; w = the full window), or on a context
+// and a dt_window (w = the converted window).  rc keeps the first failure: an entry opens the call with DT_DEV, which
+// returns it, and checks it again after scratch().  done() closes the call after the last launch.  No state beyond
+// these three members, so an entry on the scaffold runs what it ran written out by hand.
+namespace {
+struct DevCall {
+  dt_ctx *c;
+  DtWin w;
+  int rc;
+  explicit DevCall(dt_ctx *ctx) : c(ctx), w(), rc(open()) {}
+  DevCall(dt_ctx *ctx, int64_t H, int64_t W, int (*rule)(int64_t, int64_t) = dt_check_hw) : DevCall(ctx) {
+    if (rc == DT_OK) rc = rule(H, W);
+    if (rc == DT_OK) w = dt_full_window(H, W);
+  }
+  DevCall(dt_ctx *ctx, int64_t H, int64_t W, double px) : DevCall(ctx) {
+    if (rc == DT_OK) rc = dt_check_ws(H, W, px);
+    if (rc == DT_OK) w = dt_full_window(H, W);
+  }
+  DevCall(dt_ctx *ctx, const dt_window *win) : DevCall(ctx) {
+    if (rc == DT_OK) rc = dt_convert_window(win, &w);
+  }
+  // the context's scratch, reset (which drops any claim) and taken once; `reserve` > bytes asks for a larger block
+  void *scratch(size_t bytes, size_t reserve = 0) {
+    if (rc == DT_OK) rc = dt_scratch_reset(c, reserve > bytes ? reserve : bytes);
+    return rc == DT_OK ? dt_scratch_take(c, bytes) : nullptr;
+  }
+  // two regions side by side in one reservation
+  void scratch(size_t bytes, size_t bytes2, void **p, void **p2) {
+    *p = scratch(bytes, bytes + bytes2 + 512);
+    *p2 = rc == DT_OK ? dt_scratch_take(c, bytes2) : nullptr;
+    if (rc == DT_OK && !(*p && *p2)) {
+      dt_set_error("invalid argument: %s", "scratch reservation failed");
+      rc = DT_EINVAL;
+    }
+  }
+  // after the last launch (`launched`: what it returned)
+  int done(int launched = DT_OK) const { return dt_launched(launched); }
+
+ private:
+  int open() const {
+    DT_CTX(c);
+    return DT_OK;
+  }
+};
+}  // namespace
+// opens the call `d` of an entry; its failure is the entry's
+#define DT_DEV(d, ...)    \
+  DevCall d(__VA_ARGS__); \
+  DT_TRY(d.rc)
+
+// Not on the scaffold, because they enqueue no kernel and would get no shorter: dt_dev_malloc, dt_dev_free, the copies,
+// dt_dev_downslope_queued, dt_dev_dinf_accumulate_info, dt_dev_membench_mix_timed and dt_dev_mem_info.
 extern "C" int dt_dev_malloc(dt_ctx *c, int64_t bytes, void **out) {
   DT_CTX(c);
   DT_REQUIRE(out && bytes >= 0, "bad arguments");
@@ -345,43 +436,33 @@ extern "C" int dt_dev_free(dt_ctx *c, void *p) {
   DT_HIP(hipFree(p));
   return DT_OK;
 }
-extern "C" int dt_dev_h2d(dt_ctx *c, void *dst, const void *src, int64_t bytes) {
+// sync: the host may read dst (or reuse src) on return; otherwise enqueue only (dt_ctx_sync before the host reads dst;
+// dst should be page-locked: dt_host_alloc)
+static int dev_copy(dt_ctx *c, void *dst, const void *src, int64_t bytes, hipMemcpyKind kind, bool sync) {
   DT_CTX(c);
   if (bytes <= 0) return DT_OK;
   DT_REQUIRE(dst && src, "NULL pointer");
-  DT_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-  DT_HIP(hipStreamSynchronize(c->stream));
+  DT_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, kind, c->stream));
+  if (sync) DT_HIP(hipStreamSynchronize(c->stream));
   return DT_OK;
+}
+extern "C" int dt_dev_h2d(dt_ctx *c, void *dst, const void *src, int64_t bytes) {
+  return dev_copy(c, dst, src, bytes, hipMemcpyHostToDevice, true);
 }
 extern "C" int dt_dev_d2h(dt_ctx *c, void *dst, const void *src, int64_t bytes) {
-  DT_CTX(c);
-  if (bytes <= 0) return DT_OK;
-  DT_REQUIRE(dst && src, "NULL pointer");
-  DT_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
-  DT_HIP(hipStreamSynchronize(c->stream));
-  return DT_OK;
+  return dev_copy(c, dst, src, bytes, hipMemcpyDeviceToHost, true);
 }
-
-// enqueue only (dt_ctx_sync before the host reads dst; dst should be page-locked: dt_host_alloc)
 extern "C" int dt_dev_d2h_async(dt_ctx *c, void *dst, const void *src, int64_t bytes) {
-  DT_CTX(c);
-  if (bytes <= 0) return DT_OK;
-  DT_REQUIRE(dst && src, "NULL pointer");
-  DT_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
-  return DT_OK;
+  return dev_copy(c, dst, src, bytes, hipMemcpyDeviceToHost, false);
 }
 
 extern "C" int dt_dev_slope_twi(dt_ctx *c, const float *dem, const int32_t *acc32, int64_t H, int64_t W,
                                 double px, double n_top, float *slope, float *slope_rad, float *ti,
                                 float *mti) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && acc32 && ti && mti) || H * W == 0, "NULL raster");
   DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(H, W)));
-  DT_TRY(dt_launch_stencil(c->stream, dt_full_window(H, W), dem, px, slope, nullptr, slope_rad, acc32, 0, n_top, ti,
-                           mti, c->aux));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_stencil(c->stream, d.w, dem, px, slope, nullptr, slope_rad, acc32, 0, n_top, ti, mti, c->aux));
 }
 
 static int synth_octaves(int64_t Hg, int64_t Wg) {
@@ -396,227 +477,162 @@ static int synth_octaves(int64_t Hg, int64_t Wg) {
 
 extern "C" int dt_dev_synth_dem(dt_ctx *c, uint32_t seed, int64_t Hg, int64_t Wg, int64_t y0,
                                 int64_t x0, int64_t h, int64_t w, int nodata_pct, float *out) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(out || h * w == 0, "out is NULL");
   DT_REQUIRE(Hg > 0 && Wg > 0 && h >= 0 && w >= 0, "bad shape");
-  DT_TRY(dt_launch_synth_dem(c->stream, seed, synth_octaves(Hg, Wg), Hg, y0, x0, h, w, nodata_pct, out));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_synth_dem(c->stream, seed, synth_octaves(Hg, Wg), Hg, y0, x0, h, w, nodata_pct, out));
 }
 
 extern "C" int dt_dev_slope_d8(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px,
                                float *slope, uint8_t *fdr, float *slope_rad) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE(dem || H * W == 0, "dem is NULL");
   DT_REQUIRE(slope || fdr || slope_rad, "no output requested");
   DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(H, W)));
-  DT_TRY(dt_launch_stencil(c->stream, dt_full_window(H, W), dem, px, slope, fdr, slope_rad, nullptr, 0, 0.0, nullptr,
-                           nullptr, c->aux));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_stencil(c->stream, d.w, dem, px, slope, fdr, slope_rad, nullptr, 0, 0.0, nullptr, nullptr,
+                                  c->aux));
 }
 
 // Conditioned D8: fill depressions, D8 on the filled surface, resolve flats.  `filled` (device,
-// H*W floats) receives the filled surface; info3 (host, may be NULL) = {flat cells left without a code (0), fill
-// rounds, flat rounds}.  Synchronous: the fixed-point iterations read a flag back per batch of rounds.
+// H*W heights) receives the filled surface; info3 (host, may be NULL) = {flat cells left without a code (0), fill
+// rounds, flat rounds}.  Synchronous: the fixed-point iterations read a flag back per batch of rounds.  T: float32
+// heights, or a float64 DEM and filled surface, with the launcher for them.
+template <typename T, typename Launch>
+static int dev_condition_d8(dt_ctx *c, const T *dem, int64_t H, int64_t W, double px, T *filled, uint8_t *fdr,
+                            int32_t *info3, Launch launch) {
+  DT_DEV(d, c, H, W);
+  DT_REQUIRE((dem && filled) || H * W == 0, "NULL raster");
+  void *scr = d.scratch(dt_hydro_scratch(H, W));
+  DT_TRY(d.rc);
+  int unresolved = 0, rounds[2] = {0, 0};
+  DT_TRY(d.done(launch(c->stream, dem, H, W, px, filled, fdr, scr, &unresolved, rounds)));
+  if (info3) {
+    info3[0] = unresolved;
+    info3[1] = rounds[0];
+    info3[2] = rounds[1];
+  }
+  return DT_OK;
+}
+template <typename T, typename Launch>
+static int dev_condition_d8_async(dt_ctx *c, const T *dem, int64_t H, int64_t W, double px, T *filled, uint8_t *fdr,
+                                  int rounds, Launch launch) {
+  DT_DEV(d, c, H, W);
+  DT_REQUIRE((dem && filled && fdr) || H * W == 0, "NULL raster");
+  void *scr = d.scratch(dt_hydro_scratch(H, W));
+  DT_TRY(d.rc);
+  return d.done(launch(c->stream, dem, H, W, px, filled, fdr, scr, rounds, c->status));
+}
 extern "C" int dt_dev_condition_d8(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, float *filled,
                                    uint8_t *fdr, int32_t *info3) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && filled) || H * W == 0, "NULL raster");
-  size_t need = dt_hydro_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  int unresolved = 0, rounds[2] = {0, 0};
-  DT_TRY(dt_launch_condition(c->stream, dem, H, W, px, filled, fdr, scr, &unresolved, rounds));
-  DT_HIP(hipGetLastError());
-  if (info3) {
-    info3[0] = unresolved;
-    info3[1] = rounds[0];
-    info3[2] = rounds[1];
-  }
-  return DT_OK;
+  return dev_condition_d8(c, dem, H, W, px, filled, fdr, info3, dt_launch_condition);
 }
-
 extern "C" int dt_dev_condition_d8_async(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, float *filled,
                                          uint8_t *fdr, int rounds) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && filled && fdr) || H * W == 0, "NULL raster");
-  size_t need = dt_hydro_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_condition_async(c->stream, dem, H, W, px, filled, fdr, scr, rounds, c->status));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_condition_d8_async(c, dem, H, W, px, filled, fdr, rounds, dt_launch_condition_async);
 }
-
-// ... on float64 heights: dt_dev_condition_d8 / dt_dev_condition_d8_async with a float64 DEM and filled surface
 extern "C" int dt_dev_condition_d8_f64(dt_ctx *c, const double *dem, int64_t H, int64_t W, double px, double *filled,
                                        uint8_t *fdr, int32_t *info3) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && filled) || H * W == 0, "NULL raster");
-  size_t need = dt_hydro_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  int unresolved = 0, rounds[2] = {0, 0};
-  DT_TRY(dt_launch_condition_f64(c->stream, dem, H, W, px, filled, fdr, scr, &unresolved, rounds));
-  DT_HIP(hipGetLastError());
-  if (info3) {
-    info3[0] = unresolved;
-    info3[1] = rounds[0];
-    info3[2] = rounds[1];
-  }
-  return DT_OK;
+  return dev_condition_d8(c, dem, H, W, px, filled, fdr, info3, dt_launch_condition_f64);
 }
-
 extern "C" int dt_dev_condition_d8_f64_async(dt_ctx *c, const double *dem, int64_t H, int64_t W, double px,
                                              double *filled, uint8_t *fdr, int rounds) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && filled && fdr) || H * W == 0, "NULL raster");
-  size_t need = dt_hydro_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_condition_async_f64(c->stream, dem, H, W, px, filled, fdr, scr, rounds, c->status));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_condition_d8_async(c, dem, H, W, px, filled, fdr, rounds, dt_launch_condition_async_f64);
 }
 
+// ... stage by stage on one rank's window.  With a byte raster `nsame` (laid out like the others, the library's between
+// stage 2 and stage 4) the flat stages work from one byte per cell instead of the surface -- less traffic and LDS per
+// tile visit
 extern "C" int dt_dev_condition_stage_w(dt_ctx *c, const dt_window *win, int stage, int rounds, const float *dem,
                                         float *filled, uint8_t *fdr, uint32_t *dist, int32_t *flag_dev) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
-  DT_TRY(dt_launch_condition_stage(c->stream, w, stage, rounds, dem, filled, fdr, dist, (int *)flag_dev));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_DEV(d, c, win);
+  return d.done(dt_launch_condition_stage(c->stream, d.w, stage, rounds, dem, filled, fdr, dist, (int *)flag_dev));
 }
-
-// ... with a byte raster `nsame` (laid out like the others, the library's between stage 2 and stage 4): the flat stages
-// then work from one byte per cell instead of the surface -- less traffic and LDS per tile visit
 extern "C" int dt_dev_condition_stage_m_w(dt_ctx *c, const dt_window *win, int stage, int rounds, const float *dem,
                                           float *filled, uint8_t *fdr, uint32_t *dist, int32_t *flag_dev,
                                           uint8_t *nsame) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(nsame != nullptr || stage < 2, "the byte raster is missing");
-  DT_TRY(dt_launch_condition_stage(c->stream, w, stage, rounds, dem, filled, fdr, dist, (int *)flag_dev, nsame));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_condition_stage(c->stream, d.w, stage, rounds, dem, filled, fdr, dist, (int *)flag_dev, nsame));
+}
+
+// tiled flow accumulation over the call's full window, all phases (threshold / river: the river mask out of the last
+// pass, 0 / NULL without)
+static int dev_flowacc_tiled(DevCall &d, const uint8_t *fdr, const float *dem, int64_t threshold, int32_t *acc32,
+                             int8_t *river) {
+  const size_t need = dt_flowacc_tiled_scratch(d.w.H, d.w.W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  DT_TRY(dt_launch_fa_local(d.c->stream, d.w, fdr, scr, need, acc32, 0));
+  return d.done(dt_launch_fa_finish(d.c->stream, d.w, fdr, dem, scr, nullptr, threshold, acc32, 0, river));
 }
 
 extern "C" int dt_dev_flowacc(dt_ctx *c, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
                               int32_t *acc32) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((fdr && acc32) || H * W == 0, "NULL raster");
-  if (dt_flow_impl() == 1) {  // v1: one global countdown (kept for A/B runs: DT_FLOW_IMPL=v1)
-    DT_TRY(dt_scratch_reset(c, (size_t)H * W * 8));
-    unsigned long long *state = (unsigned long long *)dt_scratch_take(c, (size_t)H * W * 8);
-    DT_TRY(dt_launch_flowacc(c->stream, fdr, dem, H, W, state, acc32));
-  } else {
-    size_t need = dt_flowacc_tiled_scratch(H, W);
-    DT_TRY(dt_scratch_reset(c, need));
-    void *scr = dt_scratch_take(c, need);
-    DtWin w = dt_full_window(H, W);
-    DT_TRY(dt_launch_fa_local(c->stream, w, fdr, scr, need, acc32, 0));
-    DT_TRY(dt_launch_fa_finish(c->stream, w, fdr, dem, scr, nullptr, 0, acc32, 0, nullptr));
-  }
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  if (dt_flow_impl() != 1) return dev_flowacc_tiled(d, fdr, dem, 0, acc32, nullptr);
+  // v1: one global countdown (kept for A/B runs: DT_FLOW_IMPL=v1)
+  unsigned long long *state = (unsigned long long *)d.scratch((size_t)H * W * 8);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_flowacc(c->stream, fdr, dem, H, W, state, acc32));
 }
 
 // frac_bits is bounded so that 2^frac_bits and 2^-frac_bits stay finite for every weight that can pass the bound
 #define DT_FRAC_BITS_MAX 2200
 extern "C" int dt_dev_flowacc_weighted(dt_ctx *c, const uint8_t *fdr, const float *dem, const double *w, int64_t H,
                                        int64_t W, int frac_bits, double *acc) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((fdr && w && acc) || H * W == 0, "NULL raster");
   DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
   if (H * W == 0) return DT_OK;
-  size_t need = dt_flowacc_weighted_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_flowacc_weighted(c->stream, dt_full_window(H, W), fdr, dem, w, frac_bits, scr, need, acc, c->status));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
-}
-
-// stream order: flat indices are int64, so the raster may exceed 2^31 cells (the network may not)
-static int dt_check_so(int64_t H, int64_t W) {
-  DT_REQUIRE(H >= 0 && W >= 0, "negative raster shape");
-  DT_REQUIRE(W == 0 || H <= (1ll << 42) / W, "raster too large");
-  return DT_OK;
+  const size_t need = dt_flowacc_weighted_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_flowacc_weighted(c->stream, d.w, fdr, dem, w, frac_bits, scr, need, acc, c->status));
 }
 
 extern "C" int dt_dev_stream_order(dt_ctx *c, const uint8_t *fdr, const int8_t *river, int64_t H, int64_t W,
                                    int8_t *strahler, int64_t *shreve, int64_t *link) {
-  DT_CTX(c);
-  DT_TRY(dt_check_so(H, W));
+  DT_DEV(d, c, H, W, dt_check_so);
   DT_REQUIRE((fdr && river && strahler) || H * W == 0, "NULL raster");
   if (H * W == 0) return DT_OK;
-  size_t need = dt_stream_order_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
+  const size_t need = dt_stream_order_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
   int64_t m = 0;
-  DT_TRY(dt_launch_stream_order(c->stream, fdr, river, H, W, scr, need, strahler, shreve, link,
-                                H * W >= (1ll << 31) ? &m : nullptr));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
-}
-
-// drainage / upslope length: flat indices travel in 31 bits, so the raster has fewer than 2^31 cells
-static int dt_check_ws(int64_t H, int64_t W, double px) {
-  DT_REQUIRE(H >= 0 && W >= 0, "negative raster shape");
-  DT_REQUIRE(W == 0 || H < ((1ll << 31) + W - 1) / W, "raster of 2^31 cells or more");
-  DT_REQUIRE(std::isfinite(px) && px > 0.0, "px must be finite and > 0");
-  return DT_OK;
+  return d.done(dt_launch_stream_order(c->stream, fdr, river, H, W, scr, need, strahler, shreve, link,
+                                       H * W >= (1ll << 31) ? &m : nullptr));
 }
 
 extern "C" int dt_dev_drainage(dt_ctx *c, const uint8_t *fdr, const float *dem, const int64_t *pour, int64_t H,
                                int64_t W, double px, int64_t *target, double *length, int64_t *label) {
-  DT_CTX(c);
-  DT_TRY(dt_check_ws(H, W, px));
+  DT_DEV(d, c, H, W, px);
   DT_REQUIRE(fdr || H * W == 0, "NULL raster");
   DT_REQUIRE(!label || pour, "label requires pour");
   if (H * W == 0) return DT_OK;
-  size_t need = dt_drainage_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_drainage(c->stream, fdr, dem, pour, H, W, px, scr, need, target, length, label));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  const size_t need = dt_drainage_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_drainage(c->stream, fdr, dem, pour, H, W, px, scr, need, target, length, label));
 }
 
 extern "C" int dt_dev_upslope_length(dt_ctx *c, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                                      double *length) {
-  DT_CTX(c);
-  DT_TRY(dt_check_ws(H, W, px));
+  DT_DEV(d, c, H, W, px);
   DT_REQUIRE(fdr || H * W == 0, "NULL raster");
   if (H * W == 0 || !length) return DT_OK;
-  size_t need = dt_upslope_length_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_upslope_length(c->stream, fdr, dem, H, W, px, scr, need, length));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  const size_t need = dt_upslope_length_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_upslope_length(c->stream, fdr, dem, H, W, px, scr, need, length));
 }
 
-// D-infinity: flat indices travel in 32 bits and the kernels' coordinates in int, so fewer than 2^31 cells
 extern "C" int dt_dev_dinf_direction(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                                      float *angle, float *slope) {
-  DT_CTX(c);
-  DT_TRY(dt_check_ws(H, W, px));
+  DT_DEV(d, c, H, W, px);
   DT_REQUIRE((dem && angle) || H * W == 0, "NULL raster");
   if (H * W == 0) return DT_OK;
-  DT_TRY(dt_launch_dinf_direction(c->stream, dem, fdr, H, W, px, angle, slope));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_dinf_direction(c->stream, dem, fdr, H, W, px, angle, slope));
 }
 
 // the per-lane stack of k_di_flow: dt_debug_set(DT_DBG_DINF_STACK, n), else the environment variable of that name
@@ -634,8 +650,7 @@ static int dt_dinf_stack_cap() {
 #define DT_DINF_ROUNDS_MAX 4096
 extern "C" int dt_dev_dinf_accumulate(dt_ctx *c, const float *angle, const double *w, int64_t H, int64_t W,
                                       int frac_bits, int rounds, double *acc) {
-  DT_CTX(c);
-  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_DEV(d, c, H, W, 1.0);
   DT_REQUIRE((angle && acc) || H * W == 0, "NULL raster");
   DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
   DT_REQUIRE(rounds != 0 && rounds >= -DT_DINF_ROUNDS_MAX && rounds <= DT_DINF_ROUNDS_MAX,
@@ -643,39 +658,33 @@ extern "C" int dt_dev_dinf_accumulate(dt_ctx *c, const float *angle, const doubl
   if (H * W == 0) return DT_OK;
   const size_t need = dt_dinf_accumulate_scratch(H, W);
   if (rounds > 0) {
-    DT_TRY(dt_scratch_reset(c, need));
-    void *scr = dt_scratch_take(c, need);
+    void *scr = d.scratch(need);
+    DT_TRY(d.rc);
     DT_TRY(dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, 1, rounds - 1, 1, dt_dinf_stack_cap(), scr,
                                      need, acc, c->status));
-    c->scratch_owner = 3;
-    c->owner_h = H;
-    c->owner_w = W;
-    c->owner_ptr = (char *)scr;
-    c->owner_in[0] = angle;
-    c->owner_in[1] = w;
-    c->owner_frac = frac_bits;
-  } else {
-    DT_REQUIRE(c->scratch && c->scratch_owner == 3 && c->owner_h == H && c->owner_w == W,
-               "dt_dev_dinf_accumulate cannot continue: no accumulation of this shape was started on this context (or "
-               "another call has used the context's scratch in between)");
-    DT_REQUIRE(c->owner_in[0] == angle && c->owner_in[1] == w && c->owner_frac == frac_bits,
-               "dt_dev_dinf_accumulate continues with another angle raster, weight raster or frac_bits than it was "
-               "started with");
-    DT_TRY(dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, 0, -rounds, 1, dt_dinf_stack_cap(),
-                                     c->owner_ptr, need, acc, c->status));
+    dt_scratch_claim(c, DT_OWNER_DINF, H, W, scr, nullptr, angle, w, frac_bits);
+    return d.done();
   }
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  const DtScratchClaim *k;
+  DT_TRY(dt_scratch_claimed(c, DT_OWNER_DINF, &d.w, false,
+                            "dt_dev_dinf_accumulate cannot continue: no accumulation of this shape was started on this "
+                            "context (or another call has used the context's scratch in between)", &k));
+  DT_REQUIRE(k->in[0] == angle && k->in[1] == w && k->frac_bits == frac_bits,
+             "dt_dev_dinf_accumulate continues with another angle raster, weight raster or frac_bits than it was "
+             "started with");
+  return d.done(dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, 0, -rounds, 1, dt_dinf_stack_cap(), k->ptr,
+                                          need, acc, c->status));
 }
 
 extern "C" int dt_dev_dinf_accumulate_info(dt_ctx *c, int64_t *info4) {
   DT_CTX(c);
   DT_REQUIRE(info4 != nullptr, "info4 is NULL");
-  DT_REQUIRE(c->scratch && c->scratch_owner == 3,
-             "no D-infinity accumulation on this context (or another call has used the context's scratch since)");
+  const DtScratchClaim *k;
+  DT_TRY(dt_scratch_claimed(c, DT_OWNER_DINF, nullptr, false,
+                            "no D-infinity accumulation on this context (or another call has used the context's scratch "
+                            "since)", &k));
   uint32_t ctl[8];
-  DT_HIP(hipMemcpyAsync(ctl, dt_dinf_accumulate_ctl(c->owner_ptr, c->owner_h, c->owner_w), sizeof(ctl),
-                        hipMemcpyDeviceToHost, c->stream));
+  DT_HIP(hipMemcpyAsync(ctl, dt_dinf_accumulate_ctl(k->ptr, k->h, k->w), sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
   DT_HIP(hipStreamSynchronize(c->stream));
   info4[0] = ctl[3];
   info4[1] = ctl[4];
@@ -693,34 +702,28 @@ static int dt_check_reach_count(int64_t R) {
 extern "C" int dt_dev_reach_catchments(dt_ctx *c, const int64_t *link, const void *idx, int idx_bytes, int64_t H,
                                        int64_t W, int32_t *reach, int32_t *catch_, int64_t *heads, int64_t cap,
                                        int64_t *n_reaches) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   const int64_t N = H * W;
   DT_REQUIRE(link || N == 0, "NULL raster");
   DT_REQUIRE(!catch_ || N == 0 || (idx && (idx_bytes == 4 || idx_bytes == 8)),
              "catch needs idx with an element size of 4 or 8");
   DT_REQUIRE(cap >= 0, "negative capacity");
-  size_t need = dt_reach_catchments_scratch(N, reach == nullptr);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_reach_catchments(c->stream, link, idx, idx_bytes, N, scr, need, reach, catch_, heads, cap,
-                                    n_reaches));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  const size_t need = dt_reach_catchments_scratch(N, reach == nullptr);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_reach_catchments(c->stream, link, idx, idx_bytes, N, scr, need, reach, catch_, heads, cap,
+                                           n_reaches));
 }
 
 extern "C" int dt_dev_reach_channels(dt_ctx *c, const uint8_t *fdr, const int32_t *reach, int64_t H, int64_t W,
                                      int64_t R, int64_t *end, int64_t *down, int64_t *n_cells, int64_t *n_card,
                                      int64_t *n_diag) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_TRY(dt_check_reach_count(R));
   if (R == 0) return DT_OK;
   DT_REQUIRE((fdr && reach) || H * W == 0, "NULL raster");
   DT_REQUIRE(end && down && n_cells && n_card && n_diag, "NULL output");
-  DT_TRY(dt_launch_reach_channels(c->stream, fdr, reach, H, W, R, end, down, n_cells, n_card, n_diag));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_reach_channels(c->stream, fdr, reach, H, W, R, end, down, n_cells, n_card, n_diag));
 }
 
 // the stages' contract and the bound of frac_bits: N * rint(max(stages[K - 1], 1) * 2^frac_bits) <= 2^52
@@ -740,124 +743,102 @@ static int dt_check_stages(const double *stages, int K, int frac_bits, int64_t N
 extern "C" int dt_dev_reach_tables(dt_ctx *c, const int32_t *catch_, const void *hand, int hand_bytes,
                                    const float *slope, int64_t H, int64_t W, const double *stages, int K, int64_t R,
                                    int frac_bits, int64_t *cells, int64_t *Hq, int64_t *Bq) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_TRY(dt_check_reach_count(R));
   DT_TRY(dt_check_stages(stages, K, frac_bits, H * W));
   DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
   if (R == 0) return DT_OK;
   DT_REQUIRE((catch_ && hand) || H * W == 0, "NULL raster");
   DT_REQUIRE(cells && Hq && Bq, "NULL table");
-  size_t need = dt_reach_tables_scratch(K);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_reach_tables(c->stream, catch_, hand, hand_bytes, slope, H, W, stages, K, R, frac_bits, scr, need,
-                                cells, Hq, Bq, c->status, dt_debug_get(DT_DBG_RC_SLOTS)));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  const size_t need = dt_reach_tables_scratch(K);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_reach_tables(c->stream, catch_, hand, hand_bytes, slope, H, W, stages, K, R, frac_bits, scr,
+                                       need, cells, Hq, Bq, c->status, dt_debug_get(DT_DBG_RC_SLOTS)));
 }
 
 extern "C" int dt_dev_inundate(dt_ctx *c, const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
                                int64_t H, int64_t W, int64_t R, float *depth) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_TRY(dt_check_reach_count(R));
   DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
   if (H * W == 0) return DT_OK;
   DT_REQUIRE(catch_ && hand && depth && (stage || R == 0), "NULL raster");
-  DT_TRY(dt_launch_inundate(c->stream, catch_, hand, hand_bytes, stage, H * W, R, depth));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_inundate(c->stream, catch_, hand, hand_bytes, stage, H * W, R, depth));
 }
 
 extern "C" int dt_dev_river_mask(dt_ctx *c, const int32_t *acc32, int64_t N, int64_t threshold,
                                  int8_t *river) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((acc32 && river) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_river_mask(c->stream, acc32, N, threshold, river));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_river_mask(c->stream, acc32, N, threshold, river));
 }
 
+// dt_dev_flowhand, and with `fused` dt_dev_flowhand_gfi: the last tile pass also evaluates gfi.py:268-294 and :404-440
+// from the values it holds in registers
+static int dev_flowhand(dt_ctx *c, const float *dem, const uint8_t *fdr, const int8_t *river, const int32_t *acc32,
+                        int64_t H, int64_t W, double px, double n_gfi, double b, double size, float *fdist,
+                        int32_t *idx32, float *hand, int32_t *a_river, float *gfi, float *lnhlh, bool fused) {
+  DT_DEV(d, c, H, W);
+  if (fused) {
+    DT_REQUIRE((dem && fdr && river && acc32 && gfi && lnhlh) || H * W == 0, "NULL raster");
+  } else {
+    DT_REQUIRE((fdr && river) || H * W == 0, "NULL raster");
+    DT_REQUIRE(!hand || dem, "hand needs dem");
+    DT_REQUIRE(!a_river || acc32, "a_river needs acc32");
+    if (dt_flow_impl() == 1) {
+      unsigned long long *state = (unsigned long long *)d.scratch((size_t)H * W * 8);
+      DT_TRY(d.rc);
+      return d.done(dt_launch_flowhand(c->stream, dem, fdr, river, acc32, H, W, px, state, fdist, idx32, hand, a_river));
+    }
+  }
+  const size_t need = dt_flowhand_tiled_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  DT_TRY(dt_launch_fh_local(c->stream, d.w, fdr, river, scr, need));
+  return d.done(dt_launch_fh_finish(c->stream, d.w, dem, fdr, river, acc32, 0, px, scr, nullptr, nullptr, nullptr, nullptr,
+                                    nullptr, nullptr, fdist, idx32, nullptr, hand, a_river, gfi, lnhlh, n_gfi, b, size));
+}
 extern "C" int dt_dev_flowhand(dt_ctx *c, const float *dem, const uint8_t *fdr, const int8_t *river,
                                const int32_t *acc32, int64_t H, int64_t W, double px, float *fdist,
                                int32_t *idx32, float *hand, int32_t *a_river) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((fdr && river) || H * W == 0, "NULL raster");
-  DT_REQUIRE(!hand || dem, "hand needs dem");
-  DT_REQUIRE(!a_river || acc32, "a_river needs acc32");
-  if (dt_flow_impl() == 1) {
-    DT_TRY(dt_scratch_reset(c, (size_t)H * W * 8));
-    unsigned long long *state = (unsigned long long *)dt_scratch_take(c, (size_t)H * W * 8);
-    DT_TRY(dt_launch_flowhand(c->stream, dem, fdr, river, acc32, H, W, px, state, fdist, idx32, hand, a_river));
-  } else {
-    size_t need = dt_flowhand_tiled_scratch(H, W);
-    DT_TRY(dt_scratch_reset(c, need));
-    void *scr = dt_scratch_take(c, need);
-    DtWin w = dt_full_window(H, W);
-    DT_TRY(dt_launch_fh_local(c->stream, w, fdr, river, scr, need));
-    DT_TRY(dt_launch_fh_finish(c->stream, w, dem, fdr, river, acc32, 0, px, scr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, fdist, idx32, nullptr, hand, a_river));
-  }
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_flowhand(c, dem, fdr, river, acc32, H, W, px, 0.0, 1.0, 1.0, fdist, idx32, hand, a_river, nullptr, nullptr,
+                      false);
 }
-
-// HAND + GFI + ln(hl/H) in one go: the last tile pass of dt_dev_flowhand also evaluates gfi.py:268-294 and
-// :404-440 from the values it holds in registers.  a_river may be NULL (it is only an intermediate).
+// HAND + GFI + ln(hl/H) in one go.  a_river may be NULL (it is only an intermediate).
 extern "C" int dt_dev_flowhand_gfi(dt_ctx *c, const float *dem, const uint8_t *fdr, const int8_t *river,
                                    const int32_t *acc32, int64_t H, int64_t W, double px, double n_gfi,
                                    double b, float *fdist, int32_t *idx32, float *hand, int32_t *a_river,
                                    float *gfi, float *lnhlh) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && fdr && river && acc32 && gfi && lnhlh) || H * W == 0, "NULL raster");
-  size_t need = dt_flowhand_tiled_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DtWin w = dt_full_window(H, W);
-  DT_TRY(dt_launch_fh_local(c->stream, w, fdr, river, scr, need));
-  DT_TRY(dt_launch_fh_finish(c->stream, w, dem, fdr, river, acc32, 0, px, scr, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, fdist, idx32, nullptr, hand, a_river, gfi, lnhlh, n_gfi, b, px));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_flowhand(c, dem, fdr, river, acc32, H, W, px, n_gfi, b, px, fdist, idx32, hand, a_river, gfi, lnhlh, true);
 }
 
 extern "C" int dt_dev_twi(dt_ctx *c, const int32_t *acc32, const float *slope_rad, int64_t N, double px,
                           double n_top, float *ti, float *mti) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((acc32 && slope_rad && ti && mti) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_twi(c->stream, acc32, slope_rad, N, px, n_top, ti, mti));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_twi(c->stream, acc32, slope_rad, N, px, n_top, ti, mti));
 }
 
 extern "C" int dt_dev_gfi(dt_ctx *c, const float *hand, const int32_t *a_river, int64_t N, double n_gfi,
                           double b, double size, float *gfi) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((hand && a_river && gfi) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_gfi(c->stream, hand, a_river, N, n_gfi, b, size, gfi, 0));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_gfi(c->stream, hand, a_river, N, n_gfi, b, size, gfi, 0));
 }
 
 extern "C" int dt_dev_lnhlh(dt_ctx *c, const float *hand, const int32_t *acc32, int64_t N, double n_gfi,
                             double b, double size, float *out) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((hand && acc32 && out) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_gfi(c->stream, hand, acc32, N, n_gfi, b, size, out, 1));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_gfi(c->stream, hand, acc32, N, n_gfi, b, size, out, 1));
 }
 
 static int dev_gfi_lnhlh(dt_ctx *c, const float *hand, const void *a_river, const void *acc, int acc64, int64_t N,
                          double n_gfi, double b, double size, float *gfi, float *lnhlh) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((hand && a_river && acc && gfi && lnhlh) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_gfi_both(c->stream, hand, a_river, acc, acc64, N, n_gfi, b, size, gfi, lnhlh));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_gfi_both(c->stream, hand, a_river, acc, acc64, N, n_gfi, b, size, gfi, lnhlh));
 }
 extern "C" int dt_dev_gfi_lnhlh(dt_ctx *c, const float *hand, const int32_t *a_river, const int32_t *acc32,
                                 int64_t N, double n_gfi, double b, double size, float *gfi, float *lnhlh) {
@@ -870,35 +851,20 @@ extern "C" int dt_dev_gfi_lnhlh_a64(dt_ctx *c, const float *hand, const int64_t 
 
 extern "C" int dt_dev_flowacc_river(dt_ctx *c, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
                                     int64_t threshold, int32_t *acc32, int8_t *river) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((fdr && acc32 && river) || H * W == 0, "NULL raster");
-  if (dt_flow_impl() == 1) {
-    DT_TRY(dt_dev_flowacc(c, fdr, dem, H, W, acc32));
-    return dt_dev_river_mask(c, acc32, H * W, threshold, river);
-  }
-  size_t need = dt_flowacc_tiled_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DtWin w = dt_full_window(H, W);
-  DT_TRY(dt_launch_fa_local(c->stream, w, fdr, scr, need, acc32, 0));
-  DT_TRY(dt_launch_fa_finish(c->stream, w, fdr, dem, scr, nullptr, threshold, acc32, 0, river));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  if (dt_flow_impl() != 1) return dev_flowacc_tiled(d, fdr, dem, threshold, acc32, river);
+  DT_TRY(dt_dev_flowacc(c, fdr, dem, H, W, acc32));
+  return dt_dev_river_mask(c, acc32, H * W, threshold, river);
 }
 
 extern "C" int dt_dev_downslope(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W,
                                 double px, double dz, int raw, float *out) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
-  if (dt_flow_impl() == 1) {  // v1: one thread per cell walking global memory (kept for A/B and verification runs)
-    DT_TRY(dt_launch_downslope_v1(c->stream, dem, fdr, H, W, px, dz, raw, out));
-  } else {
-    DT_TRY(dt_launch_downslope(c->stream, dt_full_window(H, W), dem, fdr, px, dz, raw, out, nullptr));
-  }
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  // v1: one thread per cell walking global memory (kept for A/B and verification runs)
+  if (dt_flow_impl() == 1) return d.done(dt_launch_downslope_v1(c->stream, dem, fdr, H, W, px, dz, raw, out));
+  return d.done(dt_launch_downslope(c->stream, d.w, dem, fdr, px, dz, raw, out, nullptr));
 }
 
 extern "C" int64_t dt_downslope_lift_workspace(int64_t H, int64_t W) {
@@ -913,34 +879,36 @@ extern "C" int64_t dt_downslope_tables_workspace(int64_t H, int64_t W) {
 extern "C" int64_t dt_downslope_tables_threshold(int64_t H, int64_t W) {
   return (H <= 0 || W <= 0) ? 0 : (int64_t)dt_downslope_lift_min(H, W);
 }
-// dt_dev_downslope with the long-walk acceleration (dt_kernels.hip, DsQueue): `work` = dt_downslope_lift_workspace
-// bytes of device memory, the caller's for the duration of the call's kernels
+// dt_dev_downslope with the long-walk acceleration (dt_kernels.hip, DsQueue), by the launcher's phase.  0: everything
+// in one call, qwork = dt_downslope_lift_workspace bytes of device memory (queue | tables), the caller's for the
+// duration of the call's kernels.  1 and 2: the same in two steps, for callers that may synchronise in between and want
+// the 48 bytes per cell of the tables only for rasters that need them: dt_dev_downslope_queue runs the window kernel and
+// queues the long walks (qwork: dt_downslope_queue_workspace bytes), dt_dev_downslope_queued waits and says how many
+// there are, dt_dev_downslope_finish finishes them -- with skip tables when twork (dt_downslope_tables_workspace bytes)
+// is given and at least dt_downslope_tables_threshold walks are queued, move by move otherwise.
+static int dev_downslope_phase(dt_ctx *c, int phase, const float *dem, const uint8_t *fdr, int64_t H, int64_t W,
+                               double px, double dz, int raw, float *out, void *qwork, int64_t qbytes, void *twork,
+                               int64_t tbytes) {
+  DT_DEV(d, c, H, W);
+  DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
+  if (phase == 0) {
+    DT_REQUIRE(qwork != nullptr && qbytes >= dt_downslope_lift_workspace(H, W), "downslope workspace missing or too small");
+    const DtDsLift L = dt_downslope_lift_layout(d.w, qwork);
+    qwork = L.qcount;
+    twork = L.tab[0];
+  } else {
+    DT_REQUIRE(qwork != nullptr && qbytes >= dt_downslope_queue_workspace(H, W), "queue workspace missing or too small");
+    DT_REQUIRE(twork == nullptr || tbytes >= dt_downslope_tables_workspace(H, W), "tables workspace too small");
+  }
+  return d.done(dt_launch_downslope(c->stream, d.w, dem, fdr, px, dz, raw, out, nullptr, qwork, twork, phase));
+}
 extern "C" int dt_dev_downslope_lift(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                                      double dz, int raw, float *out, void *work, int64_t work_bytes) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
-  DT_REQUIRE(work != nullptr && work_bytes >= dt_downslope_lift_workspace(H, W), "downslope workspace missing or too small");
-  const DtWin w = dt_full_window(H, W);
-  const DtDsLift L = dt_downslope_lift_layout(w, work);
-  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, nullptr, L.qcount, L.tab[0], 0));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_downslope_phase(c, 0, dem, fdr, H, W, px, dz, raw, out, work, work_bytes, nullptr, 0);
 }
-// The same in two steps, for callers that may synchronise in between and want the 48 bytes per cell of the tables only
-// for rasters that need them: dt_dev_downslope_queue runs the window kernel and queues the long walks (qwork:
-// dt_downslope_queue_workspace bytes), dt_dev_downslope_queued waits and says how many there are,
-// dt_dev_downslope_finish finishes them -- with skip tables when twork (dt_downslope_tables_workspace bytes) is given
-// and at least dt_downslope_tables_threshold walks are queued, move by move otherwise.
 extern "C" int dt_dev_downslope_queue(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                                       double dz, int raw, float *out, void *qwork, int64_t qbytes) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
-  DT_REQUIRE(qwork != nullptr && qbytes >= dt_downslope_queue_workspace(H, W), "queue workspace missing or too small");
-  DT_TRY(dt_launch_downslope(c->stream, dt_full_window(H, W), dem, fdr, px, dz, raw, out, nullptr, qwork, nullptr, 1));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_downslope_phase(c, 1, dem, fdr, H, W, px, dz, raw, out, qwork, qbytes, nullptr, 0);
 }
 extern "C" int dt_dev_downslope_queued(dt_ctx *c, const void *qwork, int64_t *count) {
   DT_CTX(c);
@@ -954,94 +922,78 @@ extern "C" int dt_dev_downslope_queued(dt_ctx *c, const void *qwork, int64_t *co
 extern "C" int dt_dev_downslope_finish(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                                        double dz, int raw, float *out, void *qwork, int64_t qbytes, void *twork,
                                        int64_t tbytes) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
-  DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
-  DT_REQUIRE(qwork != nullptr && qbytes >= dt_downslope_queue_workspace(H, W), "queue workspace missing or too small");
-  DT_REQUIRE(twork == nullptr || tbytes >= dt_downslope_tables_workspace(H, W), "tables workspace too small");
-  DT_TRY(dt_launch_downslope(c->stream, dt_full_window(H, W), dem, fdr, px, dz, raw, out, nullptr, qwork, twork, 2));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_downslope_phase(c, 2, dem, fdr, H, W, px, dz, raw, out, qwork, qbytes, twork, tbytes);
 }
 
 extern "C" int dt_dev_confusion_multi(dt_ctx *c, const double *desc, const int8_t *flood, int64_t N,
                                       double nodata_value, const double *th_host, int nth, int under,
                                       int64_t *counts4_dev) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(th_host && counts4_dev, "NULL thresholds / counts");
   DT_REQUIRE((desc && flood) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_confusion(c->stream, desc, flood, N, nodata_value, th_host, nth, under,
-                             (unsigned long long *)counts4_dev));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_confusion(c->stream, desc, flood, N, nodata_value, th_host, nth, under,
+                                    (unsigned long long *)counts4_dev));
 }
 
 extern "C" int dt_dev_unique_extremes_f32(dt_ctx *c, const float *x, int64_t N, float *out3_dev) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(x && out3_dev && N >= 0, "bad arguments");
-  DT_TRY(dt_scratch_reset(c, 256));
-  uint32_t *work = (uint32_t *)dt_scratch_take(c, 64);
-  DT_TRY(dt_launch_unique_extremes(c->stream, x, N, work, out3_dev));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  uint32_t *work = (uint32_t *)d.scratch(64, 256);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_unique_extremes(c->stream, x, N, work, out3_dev));
 }
 
 extern "C" int dt_dev_minmax_scale_f32(dt_ctx *c, const float *x, int64_t N, float mn, float mx, float nodata,
                                        double *desc) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((x && desc) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_minmax_scale(c->stream, x, N, mn, mx, nodata, desc));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_minmax_scale(c->stream, x, N, mn, mx, nodata, desc));
 }
 
 extern "C" int dt_dev_minmax_scale_f32_f64(dt_ctx *c, const float *x, int64_t N, double mn, double mx, double nodata,
                                            double *desc) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((x && desc) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_minmax_scale_f32f64(c->stream, x, N, mn, mx, nodata, desc));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_minmax_scale_f32f64(c->stream, x, N, mn, mx, nodata, desc));
 }
 
 extern "C" int dt_dev_classify(dt_ctx *c, const double *desc, int8_t *flood, int64_t N, double nodata_value,
                                double threshold, int under, int remap_flood, uint8_t *binary, int32_t *klass,
                                int64_t *counts4_dev) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(counts4_dev != nullptr, "counts4 is NULL");
   DT_REQUIRE((desc && flood) || N == 0, "NULL raster");
-  DT_TRY(dt_launch_classify_f64(c->stream, desc, nullptr, flood, N, nodata_value, threshold, under, remap_flood,
-                                binary, klass, (unsigned long long *)counts4_dev));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_classify_f64(c->stream, desc, nullptr, flood, N, nodata_value, threshold, under, remap_flood,
+                                       binary, klass, (unsigned long long *)counts4_dev));
 }
 
 extern "C" int dt_dev_membench_copy(dt_ctx *c, const float *a, float *b, int64_t N, int blocks) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(a && b && N >= 0 && blocks != 0, "bad arguments");
-  DT_TRY(dt_launch_membench_copy(c->stream, a, b, N, blocks));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_membench_copy(c->stream, a, b, N, blocks));
 }
 
 extern "C" int dt_dev_membench_mix(dt_ctx *c, const float *r0, const float *r1, float *w0, float *w1, float *w2,
                                    int64_t N, int n_reads, int n_writes, int nontemporal) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE((n_reads < 1 || r0) && (n_reads < 2 || r1) && w0 && (n_writes < 2 || w1) && (n_writes < 3 || w2),
              "NULL stream");
-  DT_TRY(dt_launch_membench_mix(c->stream, r0, r1, w0, w1, w2, N, n_reads, n_writes, nontemporal));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_membench_mix(c->stream, r0, r1, w0, w1, w2, N, n_reads, n_writes, nontemporal));
 }
 
+// *ms is written only when the call succeeds
 extern "C" int dt_dev_membench_mix_timed(dt_ctx *c, const float *r0, const float *r1, float *w0, float *w1, float *w2,
                                          int64_t N, int n_reads, int n_writes, int nontemporal, int reps, double *ms) {
   DT_CTX(c);
   DT_REQUIRE(ms && reps >= 1, "bad arguments");
   DT_TRY(dt_dev_membench_mix(c, r0, r1, w0, w1, w2, N, n_reads, n_writes, nontemporal));
-  hipEvent_t e0, e1;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
   DT_HIP(hipEventCreate(&e0));
-  DT_HIP(hipEventCreate(&e1));
+  const hipError_t created = hipEventCreate(&e1);
+  if (created != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    DT_HIP(created);
+  }
   int rc = DT_OK;
   float t = 0.0f;
   if (hipEventRecord(e0, c->stream) != hipSuccess) rc = DT_EHIP;
@@ -1054,7 +1006,7 @@ extern "C" int dt_dev_membench_mix_timed(dt_ctx *c, const float *r0, const float
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  *ms = (double)t / reps;
+  if (rc == DT_OK) *ms = (double)t / reps;
   return rc;
 }
 extern "C" int dt_dev_mem_info(dt_ctx *c, int64_t *free_bytes, int64_t *total_bytes) {
@@ -1067,16 +1019,12 @@ extern "C" int dt_dev_mem_info(dt_ctx *c, int64_t *free_bytes, int64_t *total_by
 }
 
 extern "C" int dt_dev_i32_to_i64(dt_ctx *c, const int32_t *src, int64_t N, int64_t *dst) {
-  DT_CTX(c);
-  DT_TRY(dt_launch_i32_to_i64(c->stream, src, N, dst));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_DEV(d, c);
+  return d.done(dt_launch_i32_to_i64(c->stream, src, N, dst));
 }
 extern "C" int dt_dev_i64_to_i32(dt_ctx *c, const int64_t *src, int64_t N, int32_t *dst) {
-  DT_CTX(c);
-  DT_TRY(dt_launch_i64_to_i32(c->stream, src, N, dst));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_DEV(d, c);
+  return d.done(dt_launch_i64_to_i32(c->stream, src, N, dst));
 }
 
 // ---- windowed device tier (one rank's core window of a larger raster; multi-GPU) ------------------
@@ -1084,26 +1032,20 @@ extern "C" int64_t dt_perim_cells(int64_t H, int64_t W) { return dt_perim_count(
 
 extern "C" int dt_dev_slope_d8_w(dt_ctx *c, const dt_window *win, const float *dem, double px, float *slope,
                                  uint8_t *fdr, float *slope_rad) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(dem && (slope || fdr || slope_rad), "NULL raster");
-  DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(w.H, w.W)));
-  DT_TRY(dt_launch_stencil(c->stream, w, dem, px, slope, fdr, slope_rad, nullptr, 0, 0.0, nullptr, nullptr, c->aux));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(d.w.H, d.w.W)));
+  return d.done(dt_launch_stencil(c->stream, d.w, dem, px, slope, fdr, slope_rad, nullptr, 0, 0.0, nullptr, nullptr,
+                                  c->aux));
 }
 
 static int dev_slope_twi_w(dt_ctx *c, const dt_window *win, const float *dem, const void *acc, int acc64, double px,
                            double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(dem && acc && ti && mti, "NULL raster");
-  DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(w.H, w.W)));
-  DT_TRY(dt_launch_stencil(c->stream, w, dem, px, slope, nullptr, slope_rad, acc, acc64, n_top, ti, mti, c->aux));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(d.w.H, d.w.W)));
+  return d.done(dt_launch_stencil(c->stream, d.w, dem, px, slope, nullptr, slope_rad, acc, acc64, n_top, ti, mti,
+                                  c->aux));
 }
 extern "C" int dt_dev_slope_twi_w(dt_ctx *c, const dt_window *win, const float *dem, const int32_t *acc32,
                                   double px, double n_top, float *slope, float *slope_rad, float *ti,
@@ -1116,60 +1058,48 @@ extern "C" int dt_dev_slope_twi_w_a64(dt_ctx *c, const dt_window *win, const flo
   return dev_slope_twi_w(c, win, dem, acc64, 1, px, n_top, slope, slope_rad, ti, mti);
 }
 
-extern "C" int dt_dev_downslope_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
-                                  double px, double dz, int raw, float *out, int32_t *n_unresolved_dev) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
-  DT_REQUIRE(dem && fdr && out, "NULL raster");
-  if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
-  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
-}
-
-// dt_dev_downslope_w with the long-walk workspace: the long walks that stay in the rank's memory (core + halo) are
-// queued and finished with skip tables over that memory; the ones that leave it are marked and counted as ever
+// dt_dev_downslope_w in its three forms.  DS_LIFT, with the long-walk workspace `work`: the long walks that stay in the
+// rank's memory (core + halo) are queued and finished with skip tables over that memory; the ones that leave it are
+// marked and counted as ever.  DS_EMIT (work = NULL or the long-walk workspace) also EMITS the walks leaving the rank's
+// memory as walker records: walkers = [count u32, pad to 256 bytes | 48-byte records], see DsWalkOut in dt_kernels.hip.
+// More walks than records fit: the count says so, the cells are marked -50 all the same.
 extern "C" int64_t dt_downslope_lift_workspace_w(const dt_window *win) {
   DtWin w;
   if (dt_convert_window(win, &w) != DT_OK) return -1;
   return (int64_t)dt_downslope_lift_bytes_w(w);
 }
+enum DsForm { DS_PLAIN, DS_LIFT, DS_EMIT };
+static int dev_downslope_w(dt_ctx *c, DsForm form, const dt_window *win, const float *dem, const uint8_t *fdr, double px,
+                           double dz, int raw, float *out, int32_t *n_unresolved_dev, void *work, int64_t work_bytes,
+                           void *walkers, int64_t walkers_bytes) {
+  DT_DEV(d, c, win);
+  DT_REQUIRE(dem && fdr && out, "NULL raster");
+  if (form == DS_LIFT)
+    DT_REQUIRE(work != nullptr && work_bytes >= (int64_t)dt_downslope_lift_bytes_w(d.w),
+               "downslope workspace missing or too small");
+  if (form == DS_EMIT) {
+    DT_REQUIRE(work == nullptr || work_bytes >= (int64_t)dt_downslope_lift_bytes_w(d.w), "downslope workspace too small");
+    DT_REQUIRE(walkers != nullptr && walkers_bytes >= 256 + 48, "walker buffer missing or too small");
+  }
+  if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
+  const DtDsLift L = work ? dt_downslope_lift_layout(d.w, work) : DtDsLift{};  // all null without work
+  return d.done(dt_launch_downslope(c->stream, d.w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev, L.qcount,
+                                    L.tab[0], 0, walkers, (size_t)walkers_bytes));
+}
+extern "C" int dt_dev_downslope_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
+                                  double px, double dz, int raw, float *out, int32_t *n_unresolved_dev) {
+  return dev_downslope_w(c, DS_PLAIN, win, dem, fdr, px, dz, raw, out, n_unresolved_dev, nullptr, 0, nullptr, 0);
+}
 extern "C" int dt_dev_downslope_lift_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
                                        double px, double dz, int raw, float *out, int32_t *n_unresolved_dev,
                                        void *work, int64_t work_bytes) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
-  DT_REQUIRE(dem && fdr && out, "NULL raster");
-  DT_REQUIRE(work != nullptr && work_bytes >= (int64_t)dt_downslope_lift_bytes_w(w),
-             "downslope workspace missing or too small");
-  if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
-  const DtDsLift L = dt_downslope_lift_layout(w, work);
-  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev, L.qcount, L.tab[0],
-                             0));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_downslope_w(c, DS_LIFT, win, dem, fdr, px, dz, raw, out, n_unresolved_dev, work, work_bytes, nullptr, 0);
 }
-
-// dt_dev_downslope_w / _lift_w (work = NULL / the long-walk workspace) that also EMITS the walks leaving the rank's
-// memory as walker records: walkers = [count u32, pad to 256 bytes | 48-byte records], see DsWalkOut in dt_kernels.hip.
-// More walks than records fit: the count says so, the cells are marked -50 all the same.
 extern "C" int dt_dev_downslope_emit_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
                                        double px, double dz, int raw, float *out, int32_t *n_unresolved_dev,
                                        void *work, int64_t work_bytes, void *walkers, int64_t walkers_bytes) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
-  DT_REQUIRE(dem && fdr && out, "NULL raster");
-  DT_REQUIRE(work == nullptr || work_bytes >= (int64_t)dt_downslope_lift_bytes_w(w), "downslope workspace too small");
-  DT_REQUIRE(walkers != nullptr && walkers_bytes >= 256 + 48, "walker buffer missing or too small");
-  if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
-  const DtDsLift L = dt_downslope_lift_layout(w, work);  // all null without work
-  DT_TRY(dt_launch_downslope(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev, L.qcount, L.tab[0], 0,
-                             walkers, (size_t)walkers_bytes));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_downslope_w(c, DS_EMIT, win, dem, fdr, px, dz, raw, out, n_unresolved_dev, work, work_bytes, walkers,
+                         walkers_bytes);
 }
 
 // The walkers standing in this rank's memory advanced in place (k_ds_walk): rec = n records of 48 bytes; work
@@ -1177,15 +1107,11 @@ extern "C" int dt_dev_downslope_emit_w(dt_ctx *c, const dt_window *win, const fl
 // counting walkers across the rank 64 moves at a time).
 extern "C" int dt_dev_downslope_walk_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr, double px,
                                        double dz, int64_t n, void *rec, void *work, int64_t work_bytes) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(n >= 0, "negative count");
   DT_REQUIRE(n == 0 || (dem && fdr && rec), "NULL pointer");
-  DT_REQUIRE(work == nullptr || work_bytes >= (int64_t)dt_downslope_lift_bytes_w(w), "downslope workspace too small");
-  DT_TRY(dt_launch_ds_walk(c->stream, w, dem, fdr, px, dz, n, rec, work));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_REQUIRE(work == nullptr || work_bytes >= (int64_t)dt_downslope_lift_bytes_w(d.w), "downslope workspace too small");
+  return d.done(dt_launch_ds_walk(c->stream, d.w, dem, fdr, px, dz, n, rec, work));
 }
 // One iteration of the walkers' journey, prepared on the device (tiling.finish_downslope): the records that arrived
 // finished are home -- their value goes into `out` (this rank's downslope raster, core origin) -- the others advance like
@@ -1199,69 +1125,66 @@ extern "C" int dt_dev_downslope_walk_route_w(dt_ctx *c, const dt_window *win, co
                                              float *out, const int32_t *row_starts, int32_t ty,
                                              const int32_t *col_starts, int32_t tx, void *send, int32_t *counts,
                                              int32_t *scratch) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(n >= 0, "negative count");
   DT_REQUIRE(ty >= 1 && tx >= 1 && row_starts && col_starts && counts, "layout / counts missing");
   DT_REQUIRE(n == 0 || (dem && fdr && rec && out && send && scratch), "NULL pointer");
-  DT_REQUIRE(work == nullptr || work_bytes >= (int64_t)dt_downslope_lift_bytes_w(w), "downslope workspace too small");
-  DT_TRY(dt_launch_ds_walk(c->stream, w, dem, fdr, px, dz, n, rec, work, out));
-  DT_TRY(dt_launch_ds_route(c->stream, n, rec, row_starts, ty, col_starts, tx, send, counts, scratch));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_REQUIRE(work == nullptr || work_bytes >= (int64_t)dt_downslope_lift_bytes_w(d.w), "downslope workspace too small");
+  DT_TRY(dt_launch_ds_walk(c->stream, d.w, dem, fdr, px, dz, n, rec, work, out));
+  return d.done(dt_launch_ds_route(c->stream, n, rec, row_starts, ty, col_starts, tx, send, counts, scratch));
 }
 // records of walkers at their start cells (core coordinates ys / xs of n cells), no move made: for cells that are
 // marked -50 without a record (emission buffer too small, or a tile without one)
-extern "C" int dt_dev_downslope_walk_seed_w(dt_ctx *c, const dt_window *win, const float *dem, int64_t n,
-                                            const int32_t *ys, const int32_t *xs, void *rec) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+template <typename T, typename Launch>
+static int dev_downslope_walk_seed_w(dt_ctx *c, const dt_window *win, const T *dem, int64_t n, const int32_t *ys,
+                                     const int32_t *xs, void *rec, Launch launch) {
+  DT_DEV(d, c, win);
   DT_REQUIRE(n >= 0, "negative count");
   DT_REQUIRE(n == 0 || (dem && ys && xs && rec), "NULL pointer");
-  DT_TRY(dt_launch_ds_walk_seed(c->stream, w, dem, n, ys, xs, rec));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(launch(c->stream, d.w, dem, n, ys, xs, rec));
+}
+extern "C" int dt_dev_downslope_walk_seed_w(dt_ctx *c, const dt_window *win, const float *dem, int64_t n,
+                                            const int32_t *ys, const int32_t *xs, void *rec) {
+  return dev_downslope_walk_seed_w(c, win, dem, n, ys, xs, rec, dt_launch_ds_walk_seed);
 }
 
 extern "C" int dt_dev_flowacc_local_w(dt_ctx *c, const dt_window *win, const uint8_t *fdr, int32_t *acc32,
                                       int64_t *A_perim, int32_t *xr_perim, uint8_t *code_perim) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(fdr && A_perim && xr_perim && code_perim, "NULL pointer");  // acc32 is not touched by phase 1
   // HAND's workspace is reserved beside flow accumulation's, so that phase 2 can run fused with HAND's phase 1
   // (dt_dev_flowacc_finish_flowhand_local_w) without disturbing the state this call leaves
-  size_t need = dt_flowacc_tiled_scratch(w.H, w.W), need2 = dt_flowhand_tiled_scratch(w.H, w.W);
-  DT_TRY(dt_scratch_reset(c, need + need2 + 512));
-  void *scr = dt_scratch_take(c, need), *scr2 = dt_scratch_take(c, need2);
-  DT_REQUIRE(scr && scr2, "scratch reservation failed");
-  DT_TRY(dt_launch_fa_local(c->stream, w, fdr, scr, need, acc32, 1));
-  DT_TRY(dt_launch_fa_summary(c->stream, w, scr, A_perim, xr_perim, code_perim));
-  DT_HIP(hipGetLastError());
-  c->scratch_owner = 1;
-  c->owner_h = w.H;
-  c->owner_w = w.W;
-  c->owner_ptr = (char *)scr;
-  c->owner_ptr2 = (char *)scr2;
+  const size_t need = dt_flowacc_tiled_scratch(d.w.H, d.w.W);
+  void *scr, *scr2;
+  d.scratch(need, dt_flowhand_tiled_scratch(d.w.H, d.w.W), &scr, &scr2);
+  DT_TRY(d.rc);
+  DT_TRY(dt_launch_fa_local(c->stream, d.w, fdr, scr, need, acc32, 1));
+  DT_TRY(d.done(dt_launch_fa_summary(c->stream, d.w, scr, A_perim, xr_perim, code_perim)));
+  dt_scratch_claim(c, DT_OWNER_FLOWACC, d.w.H, d.w.W, scr, scr2);
   return DT_OK;
 }
 
 // must follow dt_dev_flowacc_local_w on the same context with no other scratch-using call in between
 static int dev_flowacc_finish_w(dt_ctx *c, const dt_window *win, const uint8_t *fdr, const float *dem,
                                 const uint64_t *ext_perim, int64_t threshold, void *acc, int acc64, int8_t *river) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(fdr && acc, "NULL raster");
-  DT_REQUIRE(c->scratch && c->scratch_owner == 1 && c->owner_h == w.H && c->owner_w == w.W,
-             "dt_dev_flowacc_finish_w without a matching dt_dev_flowacc_local_w on this context (another call has "
-             "used the context's scratch in between)");
-  DT_TRY(dt_launch_fa_finish(c->stream, w, fdr, dem, c->owner_ptr, (const unsigned long long *)ext_perim, threshold,
-                             acc, acc64, river, c->status));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  const DtScratchClaim *k;
+  DT_TRY(dt_scratch_claimed(c, DT_OWNER_FLOWACC, &d.w, false,
+                            "dt_dev_flowacc_finish_w without a matching dt_dev_flowacc_local_w on this context (another "
+                            "call has used the context's scratch in between)", &k));
+  return d.done(dt_launch_fa_finish(c->stream, d.w, fdr, dem, k->ptr, (const unsigned long long *)ext_perim, threshold,
+                                    acc, acc64, river, c->status));
+}
+extern "C" int dt_dev_flowacc_finish_w(dt_ctx *c, const dt_window *win, const uint8_t *fdr, const float *dem,
+                                       const uint64_t *ext_perim, int64_t threshold, int32_t *acc32,
+                                       int8_t *river) {
+  return dev_flowacc_finish_w(c, win, fdr, dem, ext_perim, threshold, acc32, 0, river);
+}
+extern "C" int dt_dev_flowacc_finish_w_a64(dt_ctx *c, const dt_window *win, const uint8_t *fdr, const float *dem,
+                                           const uint64_t *ext_perim, int64_t threshold, int64_t *acc64,
+                                           int8_t *river) {
+  return dev_flowacc_finish_w(c, win, fdr, dem, ext_perim, threshold, acc64, 1, river);
 }
 
 // phase 2 of flow accumulation and phase 1 of HAND in one call (the last accumulation tile pass and HAND's first
@@ -1271,21 +1194,17 @@ static int dev_flowacc_finish_fh_local_w(dt_ctx *c, const dt_window *win, const 
                                          const uint64_t *ext_perim, int64_t threshold, void *acc, int acc64,
                                          int8_t *river, uint8_t *kind, int32_t *ref, int32_t *nc, int32_t *nd,
                                          float *zr, int64_t *ar) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(fdr && acc && river && kind && ref && nc && nd && zr && ar, "NULL pointer");
-  DT_REQUIRE(c->scratch && c->scratch_owner == 1 && c->owner_h == w.H && c->owner_w == w.W && c->owner_ptr2,
-             "dt_dev_flowacc_finish_flowhand_local_w without a matching dt_dev_flowacc_local_w on this context (another "
-             "call has used the context's scratch in between)");
-  DT_TRY(dt_launch_fa_finish_fh_local(c->stream, w, fdr, dem, c->owner_ptr, c->owner_ptr2,
-                                      dt_flowhand_tiled_scratch(w.H, w.W), (const unsigned long long *)ext_perim, threshold,
-                                      acc, acc64, river, c->status));
-  DT_TRY(dt_launch_fh_summary(c->stream, w, c->owner_ptr2, dem, acc, acc64, kind, ref, nc, nd, zr, (long long *)ar));
-  DT_HIP(hipGetLastError());
-  c->scratch_owner = 2;
-  c->owner_ptr = c->owner_ptr2;
-  c->owner_ptr2 = nullptr;
+  const DtScratchClaim *k;
+  DT_TRY(dt_scratch_claimed(c, DT_OWNER_FLOWACC, &d.w, true,
+                            "dt_dev_flowacc_finish_flowhand_local_w without a matching dt_dev_flowacc_local_w on this "
+                            "context (another call has used the context's scratch in between)", &k));
+  char *fh = k->ptr2;
+  DT_TRY(dt_launch_fa_finish_fh_local(c->stream, d.w, fdr, dem, k->ptr, fh, dt_flowhand_tiled_scratch(d.w.H, d.w.W),
+                                      (const unsigned long long *)ext_perim, threshold, acc, acc64, river, c->status));
+  DT_TRY(d.done(dt_launch_fh_summary(c->stream, d.w, fh, dem, acc, acc64, kind, ref, nc, nd, zr, (long long *)ar)));
+  dt_scratch_claim(c, DT_OWNER_HAND, d.w.H, d.w.W, fh);  // flow accumulation's second region becomes HAND's
   return DT_OK;
 }
 extern "C" int dt_dev_flowacc_finish_flowhand_local_w(dt_ctx *c, const dt_window *win, const uint8_t *fdr,
@@ -1307,25 +1226,18 @@ extern "C" int dt_dev_flowacc_finish_flowhand_local_w_a64(dt_ctx *c, const dt_wi
 static int dev_flowacc_river_flowhand_local(dt_ctx *c, const uint8_t *fdr, const float *dem, const uint8_t *nod4,
                                            int64_t H, int64_t W, int64_t threshold, int32_t *acc32, int8_t *river,
                                            const DtTwiEpilogue *twi = nullptr) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((fdr && acc32 && river) || H * W == 0, "NULL raster");
-  DT_REQUIRE(!twi || H * W == 0 || dt_twi_epilogue_ok(dt_full_window(H, W), acc32, river, twi),
+  DT_REQUIRE(!twi || H * W == 0 || dt_twi_epilogue_ok(d.w, acc32, river, twi),
              "this raster does not take the TI / MTI epilogue (dt_slope_from_d8_ok): use dt_dev_slope_twi");
-  size_t need = dt_flowacc_tiled_scratch(H, W), need2 = dt_flowhand_tiled_scratch(H, W);
-  DT_TRY(dt_scratch_reset(c, need + need2 + 512));
-  void *scr = dt_scratch_take(c, need), *scr2 = dt_scratch_take(c, need2);
-  DT_REQUIRE(scr && scr2, "scratch reservation failed");
-  DtWin w = dt_full_window(H, W);
-  DT_TRY(dt_launch_fa_local(c->stream, w, fdr, scr, need, acc32, 0));
-  DT_TRY(dt_launch_fa_finish_fh_local(c->stream, w, fdr, dem, scr, scr2, need2, nullptr, threshold, acc32, 0, river,
-                                      c->status, nod4, dt_nodata4_ld(W), twi));
-  DT_HIP(hipGetLastError());
-  c->scratch_owner = 2;
-  c->owner_h = H;
-  c->owner_w = W;
-  c->owner_ptr = (char *)scr2;
-  c->owner_ptr2 = nullptr;
+  const size_t need = dt_flowacc_tiled_scratch(H, W), need2 = dt_flowhand_tiled_scratch(H, W);
+  void *scr, *scr2;
+  d.scratch(need, need2, &scr, &scr2);
+  DT_TRY(d.rc);
+  DT_TRY(dt_launch_fa_local(c->stream, d.w, fdr, scr, need, acc32, 0));
+  DT_TRY(d.done(dt_launch_fa_finish_fh_local(c->stream, d.w, fdr, dem, scr, scr2, need2, nullptr, threshold, acc32, 0,
+                                             river, c->status, nod4, dt_nodata4_ld(W), twi)));
+  dt_scratch_claim(c, DT_OWNER_HAND, H, W, scr2);
   return DT_OK;
 }
 extern "C" int dt_dev_flowacc_river_flowhand_local(dt_ctx *c, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
@@ -1363,12 +1275,9 @@ extern "C" int64_t dt_slope_marks_bytes(int64_t H, int64_t W) {
 // dt_dev_flowacc_river_flowhand_local_ms: microseconds when few are
 extern "C" int dt_dev_slope_twi_fix(dt_ctx *c, const float *dem, const int32_t *acc32, int64_t H, int64_t W, double px,
                                     double n_top, float *slope, float *ti, float *mti, const void *marks) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && acc32 && slope && ti && mti && marks) || H * W == 0, "NULL raster");
-  DT_TRY(dt_launch_slope_twi_fix(c->stream, dt_full_window(H, W), dem, px, slope, acc32, n_top, ti, mti, (void *)marks));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_slope_twi_fix(c->stream, d.w, dem, px, slope, acc32, n_top, ti, mti, (void *)marks));
 }
 extern "C" int64_t dt_nodata_mask_bytes(int64_t H, int64_t W) {
   return (H < 0 || W < 0) ? -1 : (int64_t)dt_nodata4_bytes(H, W);
@@ -1377,95 +1286,59 @@ extern "C" int64_t dt_nodata_mask_bytes(int64_t H, int64_t W) {
 // (bit 4 j + k = cell (4 r + j, 4 i + k) holds the sentinel, z <= -100)
 extern "C" int dt_dev_slope_d8_m(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr,
                                  uint8_t *nodata4) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && fdr && nodata4) || H * W == 0, "NULL raster");
   DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(H, W)));
-  DT_TRY(dt_launch_stencil(c->stream, dt_full_window(H, W), dem, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr,
-                           nullptr, c->aux, nodata4, dt_nodata4_ld(W)));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_stencil(c->stream, d.w, dem, px, nullptr, fdr, nullptr, nullptr, 0, 0.0, nullptr, nullptr,
+                                  c->aux, nodata4, dt_nodata4_ld(W)));
 }
 // ... and the slope raster (NULL: dt_dev_slope_d8_m), with the cells whose float32 slope is not proven in `marks`
 // (dt_slope_marks_bytes; dt_dev_flowacc_river_flowhand_local_ms and dt_dev_slope_twi_fix take them from there)
 extern "C" int dt_dev_slope_d8_ms(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, uint8_t *fdr,
                                   uint8_t *nodata4, float *slope, void *marks) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && fdr && nodata4 && (marks || !slope)) || H * W == 0, "NULL raster");
   DT_TRY(dt_side_reserve(c, &c->aux, &c->aux_bytes, dt_stencil_aux_bytes(H, W)));
-  DT_TRY(dt_launch_d8_slope(c->stream, dt_full_window(H, W), dem, px, fdr, slope, c->aux, nodata4, dt_nodata4_ld(W),
-                            marks));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_d8_slope(c->stream, d.w, dem, px, fdr, slope, c->aux, nodata4, dt_nodata4_ld(W), marks));
 }
 // ---- the resident chain on float64 heights ------------------------------------------------------------------------
 extern "C" int dt_dev_slope_d8_f64(dt_ctx *c, const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr,
                                    float *proxy) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE(dem || H * W == 0, "NULL raster");
-  DT_TRY(dt_launch_d8_f64(c->stream, dem, H, W, px, fdr, nullptr, proxy));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_d8_f64(c->stream, dem, H, W, px, fdr, nullptr, proxy));
 }
 extern "C" int dt_dev_slope_twi_f64(dt_ctx *c, const double *dem, const int32_t *acc32, int64_t H, int64_t W,
                                     double px, double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && acc32 && ti && mti) || H * W == 0, "NULL raster");
-  DT_TRY(dt_launch_slope_twi_f64(c->stream, dem, acc32, H, W, px, n_top, slope, slope_rad, ti, mti));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_slope_twi_f64(c->stream, dem, acc32, H, W, px, n_top, slope, slope_rad, ti, mti));
 }
 extern "C" int dt_dev_downslope_f64(dt_ctx *c, const double *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                                     double dz, int raw, float *out) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && fdr && out) || H * W == 0, "NULL raster");
-  DT_TRY(dt_launch_downslope_win_f64(c->stream, dem, fdr, H, W, px, dz, raw, out));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_downslope_win_f64(c->stream, dem, fdr, H, W, px, dz, raw, out));
 }
 extern "C" int dt_dev_hand_gfi_f64(dt_ctx *c, const double *dem, const int32_t *idx32, const int32_t *acc32, int64_t H,
                                    int64_t W, double px, double n_gfi, double b, double *hand, float *gfi,
                                    float *lnhlh) {
-  DT_CTX(c);
-  DT_TRY(dt_check_hw(H, W));
+  DT_DEV(d, c, H, W);
   DT_REQUIRE((dem && idx32 && acc32 && hand) || H * W == 0, "NULL raster");
-  DT_TRY(dt_launch_hand_gfi_f64(c->stream, dem, idx32, acc32, H * W, n_gfi, b, px, hand, gfi, lnhlh));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
-}
-extern "C" int dt_dev_flowacc_finish_w(dt_ctx *c, const dt_window *win, const uint8_t *fdr, const float *dem,
-                                       const uint64_t *ext_perim, int64_t threshold, int32_t *acc32,
-                                       int8_t *river) {
-  return dev_flowacc_finish_w(c, win, fdr, dem, ext_perim, threshold, acc32, 0, river);
-}
-extern "C" int dt_dev_flowacc_finish_w_a64(dt_ctx *c, const dt_window *win, const uint8_t *fdr, const float *dem,
-                                           const uint64_t *ext_perim, int64_t threshold, int64_t *acc64,
-                                           int8_t *river) {
-  return dev_flowacc_finish_w(c, win, fdr, dem, ext_perim, threshold, acc64, 1, river);
+  return d.done(dt_launch_hand_gfi_f64(c->stream, dem, idx32, acc32, H * W, n_gfi, b, px, hand, gfi, lnhlh));
 }
 
 static int dev_flowhand_local_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
                                 const int8_t *river, const void *acc, int acc64, uint8_t *kind, int32_t *ref,
                                 int32_t *nc, int32_t *nd, float *zr, int64_t *ar) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(fdr && river && kind && ref && nc && nd && zr && ar, "NULL pointer");
-  size_t need = dt_flowhand_tiled_scratch(w.H, w.W);
-  DT_TRY(dt_scratch_reset(c, need));
-  void *scr = dt_scratch_take(c, need);
-  DT_TRY(dt_launch_fh_local(c->stream, w, fdr, river, scr, need));
-  DT_TRY(dt_launch_fh_summary(c->stream, w, scr, dem, acc, acc64, kind, ref, nc, nd, zr, (long long *)ar));
-  DT_HIP(hipGetLastError());
-  c->scratch_owner = 2;
-  c->owner_h = w.H;
-  c->owner_w = w.W;
-  c->owner_ptr = (char *)scr;
-  c->owner_ptr2 = nullptr;
+  const size_t need = dt_flowhand_tiled_scratch(d.w.H, d.w.W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  DT_TRY(dt_launch_fh_local(c->stream, d.w, fdr, river, scr, need));
+  DT_TRY(d.done(dt_launch_fh_summary(c->stream, d.w, scr, dem, acc, acc64, kind, ref, nc, nd, zr, (long long *)ar)));
+  dt_scratch_claim(c, DT_OWNER_HAND, d.w.H, d.w.W, scr);
   return DT_OK;
 }
 extern "C" int dt_dev_flowhand_local_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
@@ -1487,23 +1360,20 @@ static int dev_flowhand_finish_w(dt_ctx *c, const dt_window *win, const float *d
                                  const int64_t *rem_gidx, const float *rem_zr, const int64_t *rem_ar, float *fdist,
                                  int32_t *idx32, int64_t *idx64, float *hand, void *a_river, float *gfi,
                                  float *lnhlh, bool fused) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(fdr && river, "NULL raster");
   DT_REQUIRE(!hand || dem, "hand needs dem");
   DT_REQUIRE(!a_river || acc, "a_river needs the accumulation raster");
   DT_REQUIRE(!fused || (dem && acc && gfi && lnhlh), "NULL raster");
   DT_REQUIRE(!res_ok || (res_nc && res_nd && rem_gidx && rem_zr && rem_ar), "incomplete rank-exit results");
-  DT_REQUIRE(c->scratch && c->scratch_owner == 2 && c->owner_h == w.H && c->owner_w == w.W,
-             "flowhand finish without a matching dt_dev_flowhand_local_w on this context (another call has used the "
-             "context's scratch in between)");
-  DT_TRY(dt_launch_fh_finish(c->stream, w, dem, fdr, river, acc, acc64, px, c->owner_ptr, res_ok, res_nc, res_nd,
-                             (const long long *)rem_gidx, rem_zr, (const long long *)rem_ar, fdist, idx32,
-                             (long long *)idx64, hand, a_river, fused ? gfi : nullptr, fused ? lnhlh : nullptr, n_gfi, b,
-                             px));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  const DtScratchClaim *k;
+  DT_TRY(dt_scratch_claimed(c, DT_OWNER_HAND, &d.w, false,
+                            "flowhand finish without a matching dt_dev_flowhand_local_w on this context (another call "
+                            "has used the context's scratch in between)", &k));
+  return d.done(dt_launch_fh_finish(c->stream, d.w, dem, fdr, river, acc, acc64, px, k->ptr, res_ok, res_nc, res_nd,
+                                    (const long long *)rem_gidx, rem_zr, (const long long *)rem_ar, fdist, idx32,
+                                    (long long *)idx64, hand, a_river, fused ? gfi : nullptr, fused ? lnhlh : nullptr,
+                                    n_gfi, b, px));
 }
 extern "C" int dt_dev_flowhand_finish_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
                                         const int8_t *river, const int32_t *acc32, double px,
@@ -1543,6 +1413,7 @@ extern "C" int dt_dev_flowhand_gfi_finish_w_a64(dt_ctx *c, const dt_window *win,
                                rem_ar, fdist, idx32, idx64, hand, a_river64, gfi, lnhlh, true);
 }
 
+// the rank-level solves: their workspace is scratch2 (they run between the two phases of the tile kernels)
 static int dt_scratch2_reserve(dt_ctx *c, size_t bytes) {
   return dt_side_reserve(c, &c->scratch2, &c->scratch2_bytes, bytes);
 }
@@ -1551,14 +1422,13 @@ extern "C" int dt_dev_rank_solve_flowacc(dt_ctx *c, int ty, int tx, const int64_
                                          int64_t Pmax, const void *rows_dev, int64_t rowbytes,
                                          const int64_t *field_offsets3, int rank, int64_t P_rank,
                                          uint64_t *ext_out_dev) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(heights && widths && rows_dev && field_offsets3 && ext_out_dev, "NULL pointer");
   DT_REQUIRE(rank >= 0 && rank < ty * tx && P_rank >= 0 && P_rank <= Pmax, "bad rank / ring size");
   DT_TRY(dt_scratch2_reserve(c, dt_rank_solve_scratch(ty * tx, Pmax)));
-  DT_TRY(dt_launch_rank_solve_flowacc(c->stream, ty, tx, heights, widths, Pmax, rows_dev, rowbytes, field_offsets3,
-                                      rank, P_rank, c->scratch2, (unsigned long long *)ext_out_dev));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_rank_solve_flowacc(c->stream, ty, tx, heights, widths, Pmax, rows_dev, rowbytes,
+                                             field_offsets3, rank, P_rank, c->scratch2,
+                                             (unsigned long long *)ext_out_dev));
 }
 
 extern "C" int dt_dev_rank_solve_flowhand(dt_ctx *c, int ty, int tx, const int64_t *heights, const int64_t *widths,
@@ -1566,38 +1436,28 @@ extern "C" int dt_dev_rank_solve_flowhand(dt_ctx *c, int ty, int tx, const int64
                                           const int64_t *field_offsets7, int rank, int64_t P_rank,
                                           uint8_t *res_ok, int32_t *res_nc, int32_t *res_nd, int64_t *rem_gidx,
                                           float *rem_zr, int64_t *rem_ar) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(heights && widths && rows_dev && field_offsets7 && res_ok && res_nc && res_nd && rem_gidx && rem_zr &&
                  rem_ar, "NULL pointer");
   DT_REQUIRE(rank >= 0 && rank < ty * tx && P_rank >= 0 && P_rank <= Pmax, "bad rank / ring size");
   DT_TRY(dt_scratch2_reserve(c, dt_rank_solve_scratch(ty * tx, Pmax)));
-  DT_TRY(dt_launch_rank_solve_flowhand(c->stream, ty, tx, heights, widths, Pmax, rows_dev, rowbytes,
-                                       field_offsets7, rank, P_rank, c->scratch2, res_ok, res_nc, res_nd,
-                                       (long long *)rem_gidx, rem_zr, (long long *)rem_ar));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_rank_solve_flowhand(c->stream, ty, tx, heights, widths, Pmax, rows_dev, rowbytes,
+                                              field_offsets7, rank, P_rank, c->scratch2, res_ok, res_nc, res_nd,
+                                              (long long *)rem_gidx, rem_zr, (long long *)rem_ar));
 }
 
 // ---- float64 heights on one rank's window (tiling.RankTile(heights="float64")) ------------------------------------
 extern "C" int dt_dev_slope_d8_f64_w(dt_ctx *c, const dt_window *win, const double *dem, double px, uint8_t *fdr,
                                      float *proxy) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(dem && (fdr || proxy), "NULL raster");
-  DT_TRY(dt_launch_d8_f64_w(c->stream, w, dem, px, fdr, proxy));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_d8_f64_w(c->stream, d.w, dem, px, fdr, proxy));
 }
 static int dev_slope_twi_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const void *acc, int acc64,
                                double px, double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(dem && acc && ti && mti, "NULL raster");
-  DT_TRY(dt_launch_slope_twi_f64_w(c->stream, w, dem, acc, acc64, px, n_top, slope, slope_rad, ti, mti));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_slope_twi_f64_w(c->stream, d.w, dem, acc, acc64, px, n_top, slope, slope_rad, ti, mti));
 }
 extern "C" int dt_dev_slope_twi_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const int32_t *acc32,
                                       double px, double n_top, float *slope, float *slope_rad, float *ti, float *mti) {
@@ -1610,69 +1470,48 @@ extern "C" int dt_dev_slope_twi_f64_w_a64(dt_ctx *c, const dt_window *win, const
 }
 extern "C" int dt_dev_downslope_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const uint8_t *fdr,
                                       double px, double dz, int raw, float *out, int32_t *n_unresolved_dev) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(dem && fdr && out, "NULL raster");
   if (n_unresolved_dev) DT_HIP(hipMemsetAsync(n_unresolved_dev, 0, sizeof(int32_t), c->stream));
-  DT_TRY(dt_launch_downslope_win_f64_w(c->stream, w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_downslope_win_f64_w(c->stream, d.w, dem, fdr, px, dz, raw, out, (int *)n_unresolved_dev));
 }
 extern "C" int dt_dev_downslope_walk_seed_f64_w(dt_ctx *c, const dt_window *win, const double *dem, int64_t n,
                                                 const int32_t *ys, const int32_t *xs, void *rec) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
-  DT_REQUIRE(n >= 0, "negative count");
-  DT_REQUIRE(n == 0 || (dem && ys && xs && rec), "NULL pointer");
-  DT_TRY(dt_launch_ds_walk_seed_f64(c->stream, w, dem, n, ys, xs, rec));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return dev_downslope_walk_seed_w(c, win, dem, n, ys, xs, rec, dt_launch_ds_walk_seed_f64);
 }
 extern "C" int dt_dev_downslope_walk_route_f64_w(dt_ctx *c, const dt_window *win, const double *dem,
                                                  const uint8_t *fdr, double px, double dz, int64_t n, void *rec,
                                                  float *out, const int32_t *row_starts, int32_t ty,
                                                  const int32_t *col_starts, int32_t tx, void *send, int32_t *counts,
                                                  int32_t *scratch) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(n >= 0, "negative count");
   DT_REQUIRE(ty >= 1 && tx >= 1 && row_starts && col_starts && counts, "layout / counts missing");
   DT_REQUIRE(n == 0 || (dem && fdr && rec && out && send && scratch), "NULL pointer");
-  DT_TRY(dt_launch_ds_walk_f64(c->stream, w, dem, fdr, px, dz, n, rec, out));
-  DT_TRY(dt_launch_ds_route(c->stream, n, rec, row_starts, ty, col_starts, tx, send, counts, scratch));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  DT_TRY(dt_launch_ds_walk_f64(c->stream, d.w, dem, fdr, px, dz, n, rec, out));
+  return d.done(dt_launch_ds_route(c->stream, n, rec, row_starts, ty, col_starts, tx, send, counts, scratch));
 }
 extern "C" int dt_dev_flowhand_zr64_w(dt_ctx *c, const dt_window *win, const double *dem, int64_t n,
                                       const uint8_t *kind, const int32_t *ref, double *zr64) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
-  DT_REQUIRE(n >= 0 && n <= dt_perim_count(w.H, w.W), "bad ring size");
+  DT_DEV(d, c, win);
+  DT_REQUIRE(n >= 0 && n <= dt_perim_count(d.w.H, d.w.W), "bad ring size");
   DT_REQUIRE(n == 0 || (dem && kind && ref && zr64), "NULL pointer");
-  DT_TRY(dt_launch_fh_zr64_w(c->stream, w, dem, n, kind, ref, zr64));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_fh_zr64_w(c->stream, d.w, dem, n, kind, ref, zr64));
 }
 extern "C" int dt_dev_rank_solve_flowhand_f64(dt_ctx *c, int ty, int tx, const int64_t *heights, const int64_t *widths,
                                               int64_t Pmax, const void *rows_dev, int64_t rowbytes,
                                               const int64_t *field_offsets8, int rank, int64_t P_rank,
                                               uint8_t *res_ok, int32_t *res_nc, int32_t *res_nd, int64_t *rem_gidx,
                                               float *rem_zr, int64_t *rem_ar, double *rem_zr64) {
-  DT_CTX(c);
+  DT_DEV(d, c);
   DT_REQUIRE(heights && widths && rows_dev && field_offsets8 && res_ok && res_nc && res_nd && rem_gidx && rem_zr &&
                  rem_ar && rem_zr64, "NULL pointer");
   DT_REQUIRE(rank >= 0 && rank < ty * tx && P_rank >= 0 && P_rank <= Pmax, "bad rank / ring size");
   DT_REQUIRE(field_offsets8[7] % 8 == 0 && rowbytes % 8 == 0, "the float64 field must be 8-byte aligned");
   DT_TRY(dt_scratch2_reserve(c, dt_rank_solve_scratch(ty * tx, Pmax)));
-  DT_TRY(dt_launch_rank_solve_flowhand_f64(c->stream, ty, tx, heights, widths, Pmax, rows_dev, rowbytes,
-                                           field_offsets8, rank, P_rank, c->scratch2, res_ok, res_nc, res_nd,
-                                           (long long *)rem_gidx, rem_zr, (long long *)rem_ar, rem_zr64));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_rank_solve_flowhand_f64(c->stream, ty, tx, heights, widths, Pmax, rows_dev, rowbytes,
+                                                  field_offsets8, rank, P_rank, c->scratch2, res_ok, res_nc, res_nd,
+                                                  (long long *)rem_gidx, rem_zr, (long long *)rem_ar, rem_zr64));
 }
 extern "C" int64_t dt_hand_f64_table_bytes(int64_t n_remote) {
   return n_remote < 0 ? -1 : dt_hand_f64_table_slots(n_remote) * 16;
@@ -1682,16 +1521,12 @@ static int dev_hand_gfi_f64_w(dt_ctx *c, const dt_window *win, const double *dem
                               const uint8_t *res_ok, const int64_t *rem_gidx, const double *rem_zr64, void *table,
                               int64_t table_bytes, double px, double n_gfi, double b, double *hand, float *gfi,
                               float *lnhlh) {
-  DT_CTX(c);
-  DtWin w;
-  DT_TRY(dt_convert_window(win, &w));
+  DT_DEV(d, c, win);
   DT_REQUIRE(dem && (idx32 || idx64) && acc && a_river && hand, "NULL raster");
   DT_REQUIRE(n_remote >= 0 && (n_remote == 0 || !res_ok || (rem_gidx && rem_zr64)), "incomplete rank-exit results");
   DT_REQUIRE(table && table_bytes >= dt_hand_f64_table_bytes(n_remote), "river-height table missing or too small");
-  DT_TRY(dt_launch_hand_gfi_f64_w(c->stream, w, dem, idx64 ? nullptr : idx32, idx64, acc, a_river, acc64, n_remote,
-                                  res_ok, rem_gidx, rem_zr64, table, n_gfi, b, px, hand, gfi, lnhlh));
-  DT_HIP(hipGetLastError());
-  return DT_OK;
+  return d.done(dt_launch_hand_gfi_f64_w(c->stream, d.w, dem, idx64 ? nullptr : idx32, idx64, acc, a_river, acc64,
+                                         n_remote, res_ok, rem_gidx, rem_zr64, table, n_gfi, b, px, hand, gfi, lnhlh));
 }
 extern "C" int dt_dev_hand_gfi_f64_w(dt_ctx *c, const dt_window *win, const double *dem, const int32_t *idx32,
                                      const int64_t *idx64, const int32_t *acc32, const int32_t *a_river32,
@@ -2147,8 +1982,8 @@ extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H
     DT_HIP(hipStreamSynchronize(hc.c->stream));
     if (ctl[0] == ctl[2]) break;  // everything queued has been drained
   }
-  DT_TRY(dt_launch_dinf_accumulate(hc.c->stream, d_a, d_w, H, W, frac_bits, 0, 0, 1, cap, scr, need, d_o, hc.c->status));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_dinf_accumulate(hc.c->stream, d_a, d_w, H, W, frac_bits, 0, 0, 1, cap, scr, need, d_o,
+                                               hc.c->status)));
   DT_TRY(dt_ctx_status(hc.c, &st));
   DT_REQUIRE(!(st & DT_STATUS_BAD_ANGLE), "an angle is neither -1, -100 nor in [0, float32(2 pi)]");
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
@@ -2284,8 +2119,7 @@ extern "C" int dt_twi(const int64_t *fac, const float *slope_rad, int64_t N, dou
   float *d_t = hc.out(ti, N);
   float *d_m = hc.out(mti, N);
   DT_TRY(hc.rc);
-  DT_TRY(dt_launch_twi_i64(hc.c->stream, d_f, d_s, N, px, n_top, d_t, d_m));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_twi_i64(hc.c->stream, d_f, d_s, N, px, n_top, d_t, d_m)));
   return hc.finish();
 }
 
@@ -2299,8 +2133,7 @@ extern "C" int dt_river_accumulation(const int64_t *fac, const int64_t *idx, int
   const int64_t *d_i = hc.in(idx, N);
   int64_t *d_a = hc.out(out, N);
   DT_TRY(hc.rc);
-  DT_TRY(dt_launch_river_acc_i64(hc.c->stream, d_f, d_i, N, d_a));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_river_acc_i64(hc.c->stream, d_f, d_i, N, d_a)));
   return hc.finish();
 }
 
@@ -2318,8 +2151,7 @@ static int host_gfi(const float *hand, const int64_t *fac, const int64_t *idx, i
   int64_t *d_a = idx ? hc.scratch<int64_t>(N) : nullptr;
   DT_TRY(hc.rc);
   if (idx) DT_TRY(dt_launch_river_acc_i64(hc.c->stream, d_f, d_i, N, d_a));
-  DT_TRY(dt_launch_gfi_i64(hc.c->stream, d_h, idx ? d_a : d_f, N, n_gfi, b, size, d_o, own_cell));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_gfi_i64(hc.c->stream, d_h, idx ? d_a : d_f, N, n_gfi, b, size, d_o, own_cell)));
   return hc.finish();
 }
 extern "C" int dt_gfi(const float *hand, const int64_t *fac, const int64_t *idx, int64_t N, double n_gfi,
@@ -2349,8 +2181,7 @@ static int host_hand(const T *dem, const int64_t *idx, int64_t N, T *hand,
   const int64_t *d_i = hc.in(idx, N);
   T *d_h = hc.out(hand, N);
   DT_TRY(hc.rc);
-  DT_TRY(launch(hc.c->stream, d_d, d_i, N, d_h));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(launch(hc.c->stream, d_d, d_i, N, d_h)));
   return hc.finish();
 }
 extern "C" int dt_hand_f32(const float *dem, const int64_t *idx, int64_t N, float *hand) {
@@ -2368,8 +2199,7 @@ extern "C" int dt_slope_f64(const double *dem, int64_t H, int64_t W, double px, 
   const double *d_d = hc.in(dem, n);
   float *d_s = hc.out(slope, n);
   DT_TRY(hc.rc);
-  DT_TRY(dt_launch_slope_f64(hc.c->stream, d_d, H, W, px, d_s));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_slope_f64(hc.c->stream, d_d, H, W, px, d_s)));
   return hc.finish();
 }
 extern "C" int dt_d8_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, float *slope) {
@@ -2383,8 +2213,7 @@ extern "C" int dt_d8_f64(const double *dem, int64_t H, int64_t W, double px, uin
   uint8_t *d_f = hc.out(fdr, n);
   float *d_s = hc.out(slope, n);
   DT_TRY(hc.rc);
-  DT_TRY(dt_launch_d8_f64(hc.c->stream, d_d, H, W, px, d_f, d_s, nullptr));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_d8_f64(hc.c->stream, d_d, H, W, px, d_f, d_s, nullptr)));
   return hc.finish();
 }
 extern "C" int dt_hand_f64(const double *dem, const int64_t *idx, int64_t N, double *hand) {
@@ -2402,8 +2231,7 @@ extern "C" int dt_downslope_f64(const double *dem, const uint8_t *fdr, int64_t H
   const uint8_t *d_f = hc.in(fdr, n);
   float *d_o = hc.out(out, n);
   DT_TRY(hc.rc);
-  DT_TRY(dt_launch_downslope_f64(hc.c->stream, d_d, d_f, H, W, px, dz, raw, d_o));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_downslope_f64(hc.c->stream, d_d, d_f, H, W, px, dz, raw, d_o)));
   return hc.finish();
 }
 extern "C" int dt_gfi_f64h(const double *hand, const int64_t *fac, const int64_t *idx, int64_t N, double n_gfi,
@@ -2418,8 +2246,7 @@ extern "C" int dt_gfi_f64h(const double *hand, const int64_t *fac, const int64_t
   float *d_o = hc.out(out, N);
   const int64_t *d_i = own_area ? nullptr : hc.in(idx, N);
   DT_TRY(hc.rc);
-  DT_TRY(dt_launch_gfi_f64h(hc.c->stream, d_h, d_f, d_i, N, n_gfi, b, size, own_area, d_o));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_gfi_f64h(hc.c->stream, d_h, d_f, d_i, N, n_gfi, b, size, own_area, d_o)));
   return hc.finish();
 }
 
@@ -2485,14 +2312,13 @@ extern "C" int dt_minmax_scale(const void *x, int is_f32, int64_t N, double mn, 
     const float *d_x = hc.in((const float *)x, N);
     float *d_o = hc.out((float *)out, N);
     DT_TRY(hc.rc);
-    DT_TRY(dt_launch_minmax_scale_f32f32(hc.c->stream, d_x, N, (float)mn, (float)mx, (float)nodata, d_o));
+    DT_TRY(dt_launched(dt_launch_minmax_scale_f32f32(hc.c->stream, d_x, N, (float)mn, (float)mx, (float)nodata, d_o)));
   } else {
     const double *d_x = hc.in((const double *)x, N);
     double *d_o = hc.out((double *)out, N);
     DT_TRY(hc.rc);
-    DT_TRY(dt_launch_minmax_scale_f64(hc.c->stream, d_x, N, mn, mx, nodata, d_o));
+    DT_TRY(dt_launched(dt_launch_minmax_scale_f64(hc.c->stream, d_x, N, mn, mx, nodata, d_o)));
   }
-  DT_HIP(hipGetLastError());
   return hc.finish();
 }
 
@@ -2510,11 +2336,10 @@ extern "C" int dt_binary_map(const void *desc, int is_f32, int64_t N, double nod
   unsigned long long *d_c = hc.scratch<unsigned long long>(4);
   DT_TRY(hc.rc);
   DT_HIP(hipMemsetAsync(d_f, 0, N, hc.c->stream));
-  if (is_f32) DT_TRY(dt_launch_classify_f32(hc.c->stream, d_d32, nullptr, d_f, N, (float)nodata_value,
-                                            (float)threshold, under, 0, d_b, nullptr, d_c));
-  else DT_TRY(dt_launch_classify_f64(hc.c->stream, d_d64, nullptr, d_f, N, nodata_value, threshold, under, 0, d_b,
-                                     nullptr, d_c));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(is_f32 ? dt_launch_classify_f32(hc.c->stream, d_d32, nullptr, d_f, N, (float)nodata_value,
+                                                     (float)threshold, under, 0, d_b, nullptr, d_c)
+                            : dt_launch_classify_f64(hc.c->stream, d_d64, nullptr, d_f, N, nodata_value, threshold,
+                                                     under, 0, d_b, nullptr, d_c)));
   return hc.finish();
 }
 
@@ -2528,9 +2353,8 @@ extern "C" int dt_avaliacao(const int32_t *binary, int8_t *flood, int64_t N, int
   int32_t *d_k = hc.scratch<int32_t>(N);
   int64_t *d_c = hc.out(counts4, 4);
   DT_TRY(hc.rc);
-  DT_TRY(dt_launch_classify_f64(hc.c->stream, nullptr, d_b, d_f, N, 0.0, 0.0, 0, 1, nullptr, klass ? d_k : nullptr,
-                                (unsigned long long *)d_c));
-  DT_HIP(hipGetLastError());
+  DT_TRY(dt_launched(dt_launch_classify_f64(hc.c->stream, nullptr, d_b, d_f, N, 0.0, 0.0, 0, 1, nullptr,
+                                            klass ? d_k : nullptr, (unsigned long long *)d_c)));
   DT_TRY(hc.download(flood, d_f, N));  // the benchmark map comes back remapped (evaluation.py:149-150 mutates it)
   if (klass) DT_TRY(hc.download(klass, d_k, N));
   return hc.finish();

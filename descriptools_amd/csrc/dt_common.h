@@ -42,6 +42,19 @@ enum { DT_DBG_TWI_FLAG_ALL = 0, DT_DBG_TWI_PLAIN = 1, DT_DBG_TWI_WX = 2, DT_DBG_
 int dt_debug_get(int key);
 
 // ---- context ------------------------------------------------------------------------------
+// Which multi-call op's state lives in the context's `scratch`, and where.  The op's first phase claims it (*_local_w,
+// the first rounds of dt_dev_dinf_accumulate), every dt_scratch_reset drops the claim, the later phases (*_finish_w, a
+// continuation) require it -- dt_scratch_claim / dt_scratch_claimed in dt_capi.hip are the only code that touches it.
+enum DtScratchOwner { DT_OWNER_NONE = 0, DT_OWNER_FLOWACC, DT_OWNER_HAND, DT_OWNER_DINF };
+struct DtScratchClaim {
+  DtScratchOwner owner;
+  int64_t h, w;       // the core shape of the raster the state belongs to
+  char *ptr;          // where in `scratch` that state starts
+  char *ptr2;         // flow accumulation only: HAND's region reserved beside it, for when phase 2 of the one and phase 1
+                      // of the other are fused (the region then becomes HAND's `ptr`)
+  const void *in[2];  // D-infinity only: the angle and weight rasters the accumulation was started on,
+  int frac_bits;      // and its frac_bits: a continuation must name the same
+};
 struct dt_ctx {
   int device;
   hipStream_t stream;
@@ -49,12 +62,7 @@ struct dt_ctx {
   char *scratch;
   size_t scratch_bytes;
   size_t scratch_used;  // bump pointer, reset at the start of every entry point
-  int scratch_owner;    // which multi-call op's state lives in `scratch` (0 none, 1 flow accumulation, 2 HAND, 3 D-inf):
-  int64_t owner_h, owner_w;  // set by *_local_w, cleared by every dt_scratch_reset, required by *_finish_w
-  char *owner_ptr;      // where in `scratch` that state starts (HAND's follows flow accumulation's when phase 2 of the
-  char *owner_ptr2;     // one and phase 1 of the other are fused: owner_ptr2 = HAND's region reserved beside it)
-  const void *owner_in[2];  // D-inf: the angle and weight rasters the accumulation in `scratch` was started on,
-  int owner_frac;           // and its frac_bits: a continuation must name the same
+  DtScratchClaim claim;  // the two-phase state in `scratch`, if any
   char *scratch2;       // rank-level solves (must not disturb the two-phase tile scratch)
   size_t scratch2_bytes;
   hipEvent_t ev;        // fork / join with another context's stream (created on first use)
