@@ -1996,6 +1996,27 @@ extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H
   return hc.finish();
 }
 
+extern "C" int dt_proximity(const int8_t *river, const float *nod, int64_t H, int64_t W, double px, float *distance,
+                            int64_t *indices) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(river && distance && indices, "NULL raster");
+  const int8_t *d_r = hc.in(river, n);
+  const float *d_n = hc.in(nod, n);
+  float *d_d = hc.out(distance, n);
+  int64_t *d_i = hc.out(indices, n);
+  DT_TRY(hc.rc);
+  const size_t need = dt_proximity_scratch(H, W);
+  DT_TRY(dt_scratch_reset(hc.c, need));
+  void *scr = dt_scratch_take(hc.c, need);
+  DT_REQUIRE(scr, "scratch reservation failed");
+  DT_TRY(dt_launched(dt_launch_proximity(hc.c->stream, d_r, d_n, H, W, px, scr, need, d_d, d_i)));
+  return hc.finish();
+}
+
 extern "C" int dt_reach_catchments(const int64_t *link, const int64_t *idx, int64_t H, int64_t W, int32_t *reach,
                                    int32_t *catch_, int64_t *heads, int64_t cap, int64_t *n_reaches) {
   HostCall hc;

@@ -276,3 +276,11 @@ int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *w
 // the accumulation's control words in `scratch` (8 x uint32 on the device): queued, window lo, window hi, queue rounds
 // that found work, the largest window, two-receiver cells
 const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W);
+
+// Euclidean proximity (dt_proximity.hip): for every cell the nearest source (river == 1 and, with nod, nod > -100) by
+// exact squared distance, ties to the smallest flat index -> distance = float32(px * sqrt(float64(d2))) and indices =
+// the source's flat index; -100 where nod <= -100 and when there is no source.  nod may be NULL.  The row pass, the
+// per-level launches of the column pass and their state live in `scratch`; nothing synchronises.  H * W < 2^31.
+size_t dt_proximity_scratch(int64_t H, int64_t W);
+int dt_launch_proximity(hipStream_t s, const int8_t *river, const float *nod, int64_t H, int64_t W, double px,
+                        void *scratch, size_t scratch_bytes, float *distance, int64_t *indices);

@@ -211,6 +211,17 @@ int dt_dinf_direction(const float *dem, const uint8_t *fdr, int64_t H, int64_t W
  * number of cells one round drained, cells queued in all, two-receiver cells}. */
 int dt_dinf_accumulate(const float *angle, const double *w, int64_t H, int64_t W, int frac_bits, double *acc,
                        int64_t *info4);
+/* Net-new: exact Euclidean proximity to the river network.  A source is a cell with river == 1 that is not nodata;
+ * nodata is a cell with nod <= -100, where nod (may be NULL: no nodata) is any float32 raster of the shape: a float32
+ * DEM, or for heights float32 cannot hold the -100 / 0 mask of the DEM's own comparison (descriptools_amd._lib.
+ * nodata_mask).  For a cell c = (y, x) and a source s = (ys, xs), d2 = (y - ys)^2 + (x - xs)^2 in int64; nearest(c) is
+ * the source of smallest d2, among equals the one of smallest flat index ys * W + xs.  indices = that flat index,
+ * distance = float32(px * sqrt(float64(d2))), both operations in float64.  Both are -100 on nodata (which is no
+ * barrier: distances are straight lines over it) and when the raster has no source.  The result is exact and does not
+ * depend on order or run; the work is O(H W log H) whatever the sources.  Rasters of 2^31 cells or more and a px that
+ * is not finite and > 0 are refused.  HAND above the nearest source: dt_hand_f32 / dt_hand_f64 on indices. */
+int dt_proximity(const int8_t *river, const float *nod, int64_t H, int64_t W, double px, float *distance,
+                 int64_t *indices);
 /* Net-new: reaches (the HAND synthetic-rating-curve method).  Rasters are H x W with fewer than 2^31 cells, flat index
  * y * W + x; results are exact integers (and depth one float32 rounding), independent of order and run.
  *
