@@ -39,7 +39,8 @@ WRITE_GROUPS = (("slope", "ti", "mti"), ("fdist", "idx", "hand", "gfi", "lnhlh")
 # slope on its way (fdr 1 + slope 4 + the marks), "flowacc_flowhand_local" runs k_fa3fh1_twi, which reads that slope (4)
 # and writes TI + MTI (8) beside the accumulation it has in registers, and "slope_twi" is only k_slope_twi_fix over
 # the marked cells (microseconds on terrain): dem 4 + fac 4 are no longer read a second time, and a per-op rate
-# computed from the 20 B/cell of "slope_twi" means nothing for that chain.
+# computed from the 20 B/cell of "slope_twi" means nothing for that chain.  The kernel names are the r4
+# profile's, not the live ones: the stencil pair is k_slope_twi<true, false, int> and k_slope_twi_fix<int> today.
 OPS = (
     ("d8", 5, ["k_d8<false>", "k_d8_fix"]),
     ("downslope", 9, ["k_downslope_win<24>"]),
@@ -306,8 +307,8 @@ class Chain:
     def _from_d8(self, dem_ptr=None):
         """does the step take slope from the D8 kernel and TI / MTI from the accumulation pass?  (the plain float32
         chain without slope_rad, on rows of whole 64-cell tiles and 16-byte aligned rasters; same rasters either way)"""
-        if self._marks is None or self.want_slope_rad or not _lib.lib().dt_slope_from_d8_ok(self.H, self.W):
-            return False  # (asked again: a debug key can take the fused tile pass away after set-up)
+        if self._marks is None:  # (allocated only without slope_rad and on a shape dt_slope_from_d8_ok accepts)
+            return False
         ptrs = [self.p(k) for k in ("slope", "fac", "ti", "mti", "river", "fdr")] + ([dem_ptr] if dem_ptr else [])
         return all((int(q.value if hasattr(q, "value") else q) & 15) == 0 for q in ptrs)
 

@@ -30,6 +30,8 @@ static int g_debug[DT_DBG_COUNT] = {0};
 int dt_debug_get(int key) { return (key >= 0 && key < DT_DBG_COUNT) ? g_debug[key] : 0; }
 extern "C" int dt_debug_set(int key, int value) {
   DT_REQUIRE(key >= 0 && key < DT_DBG_COUNT, "unknown debug key");
+  DT_REQUIRE(key < DT_DBG_RETIRED_FIRST || key > DT_DBG_RETIRED_LAST,
+             "this debug key was retired together with the kernel variants it selected (keys 1-7)");
   g_debug[key] = value;
   return DT_OK;
 }
@@ -1266,7 +1268,7 @@ extern "C" int dt_dev_flowacc_river_flowhand_local_ms(dt_ctx *c, const uint8_t *
 // the shapes on which the D8 kernel's slope and the accumulation pass's TI / MTI replace the slope + TI + MTI stencil
 // (rows of whole 64-cell tiles; the rasters and the marks 16-byte aligned), and the bytes of the marks
 extern "C" int dt_slope_from_d8_ok(int64_t H, int64_t W) {
-  return H > 0 && W > 0 && W % 64 == 0 && dt_debug_get(DT_DBG_NO_FUSED_FA_FH) == 0;
+  return H > 0 && W > 0 && W % 64 == 0;
 }
 extern "C" int64_t dt_slope_marks_bytes(int64_t H, int64_t W) {
   return (H < 0 || W < 0) ? -1 : (int64_t)dt_stencil_aux_bytes(H, W);

@@ -37,8 +37,23 @@ void dt_set_error(const char *fmt, ...);
   } while (0)
 
 // ---- test / experiment knobs (dt_debug_set in the C ABI; all 0 by default) -------------------------
-enum { DT_DBG_TWI_FLAG_ALL = 0, DT_DBG_TWI_PLAIN = 1, DT_DBG_TWI_WX = 2, DT_DBG_TWI_MAP = 3, DT_DBG_DS_MARGIN = 4, DT_DBG_NO_FUSED_FA_FH = 5, DT_DBG_HY_FILL_SWEEPS = 6, DT_DBG_HY_FLAT_SWEEPS = 7, DT_DBG_HY_COLOUR_MIN = 8 /* tiles from which the conditioning rounds are coloured (0: the default; tests) */, DT_DBG_FA_SCATTER = 9 /* flow accumulation: the scatter form of the perimeter graph (A/B) */, DT_DBG_RC_SLOTS = 10 /* reach tables: n > 0 caps the LDS table at n slots (tests), -1 = no LDS table, one global atomic per cell (A/B) */, DT_DBG_DINF_STACK = 11 /* D-infinity accumulation: n > 0: a lane holds at most n complete cells, the one it carries on with included (1: no stack), so that the spill queue and its rounds run (tests); the environment variable DT_DBG_DINF_STACK sets it too */, DT_DBG_COUNT = 12 };
-#define DT_TWI_WX_DEFAULT 1 /* tile geometry of the fused slope + TI + MTI stencil: see k_slope_twi */
+// Keys 1-7 (DT_DBG_TWI_PLAIN, DT_DBG_TWI_WX, DT_DBG_TWI_MAP, DT_DBG_DS_MARGIN, DT_DBG_NO_FUSED_FA_FH,
+// DT_DBG_HY_FILL_SWEEPS, DT_DBG_HY_FLAT_SWEEPS) selected kernel variants and sweep counts whose A/B runs are settled
+// (DESIGN.md 4.1, 4.4 and the conditioning section; profiles/ names them); the variants are gone, and dt_debug_set
+// answers those numbers with an error.  The numbers stay unused: tests and tools address the keys by number, and a
+// stale caller must fail instead of switching something else.
+enum {
+  DT_DBG_TWI_FLAG_ALL = 0,  /* the fused slope + TI + MTI stencil sends every cell through its exact path as well (tests) */
+  DT_DBG_RETIRED_FIRST = 1, DT_DBG_RETIRED_LAST = 7,
+  DT_DBG_HY_COLOUR_MIN = 8, /* tiles from which the conditioning rounds are coloured (0: the default; tests) */
+  DT_DBG_FA_SCATTER = 9,    /* flow accumulation: the scatter form of the perimeter graph (A/B) */
+  DT_DBG_RC_SLOTS = 10,     /* reach tables: n > 0 caps the LDS table at n slots (tests), -1 = no LDS table, one global
+                               atomic per cell (A/B) */
+  DT_DBG_DINF_STACK = 11,   /* D-infinity accumulation: n > 0: a lane holds at most n complete cells, the one it carries on
+                               with included (1: no stack), so that the spill queue and its rounds run (tests); the
+                               environment variable DT_DBG_DINF_STACK sets it too */
+  DT_DBG_COUNT = 12
+};
 int dt_debug_get(int key);
 
 // ---- context ------------------------------------------------------------------------------

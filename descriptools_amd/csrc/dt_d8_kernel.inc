@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256, 8) void k_d8(const float *__restrict__ dem, Dt
         if (NT) __builtin_nontemporal_store(codes, reinterpret_cast<uint32_t *>(fdr + o));
         else *reinterpret_cast<uint32_t *>(fdr + o) = codes;
 #if SD_D8_SLOPE
-        sd_store4<1>(slope + o, so[0], so[1], so[2], so[3]);
+        sd_store4(slope + o, so[0], so[1], so[2], so[3]);
 #endif
       } else {
 #pragma unroll

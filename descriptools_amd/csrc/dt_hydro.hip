@@ -338,7 +338,7 @@ __device__ __forceinline__ void hy_stage64(double *s, const double *__restrict__
 // tile that changed is open: round 3's rule.)  act_prev == NULL: the first round of a phase, every tile is visited.
 #define HY_CHANGED 1 /* (round 4, late: only when a cell of the tile's OUTER RING changed -- what its neighbours read) */
 #define HY_OPEN 2
-// rounds of sweeps per visit at most (dt_debug_set(6 / 7, n) overrides: tools/condition_bench.py N sweeps).  Measured,
+// rounds of sweeps per visit at most.  Measured with a debug key that has since been retired,
 // round 4 (profiles/r4/conditioning_sweeps.txt): ONE is best for both relaxations on rough 8192^2 terrain and on the
 // Example (6.8 / 1.08 ms against 8.2 / 1.28 with up to six flat sweeps, 7.4 / 1.14 with two fill sweeps) -- what bounds
 // the number of global rounds is how many tiles a depression or a flat spans, not how far a tile is from its local
@@ -1438,8 +1438,6 @@ static void hy_flat_round(hipStream_t s, bool coloured, int64_t r, const uint8_t
 template <typename T>
 static int hy_condition(hipStream_t s, const T *dem, int64_t H, int64_t W, double px, T *filled, uint8_t *fdr,
                         void *scratch, int *unresolved_host, int *rounds_host) {
-  const int fill_sweeps = dt_debug_get(DT_DBG_HY_FILL_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FILL_SWEEPS) : HY_FILL_SWEEPS;
-  const int flat_sweeps = dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) : HY_FLAT_SWEEPS;
   const int64_t n = H * W;
   if (n == 0) return DT_OK;
   const HyLayout L = hy_layout(H, W, scratch);
@@ -1450,7 +1448,7 @@ static int hy_condition(hipStream_t s, const T *dem, int64_t H, int64_t W, doubl
   const int64_t max_rounds = n + 8;
   const bool coloured = hy_tiles(H, W) >= hy_colour_min();
   DT_TRY(hy_iterate(s, L.flag, max_rounds, [&](int *f, const int *prev, int64_t r) {
-    hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, f, prev, L.act, L.act1, fill_sweeps);
+    hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, f, prev, L.act, L.act1, HY_FILL_SWEEPS);
   }, &r1));
   if (fdr) {
     DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, L, tiles_x));
@@ -1458,7 +1456,7 @@ static int hy_condition(hipStream_t s, const T *dem, int64_t H, int64_t W, doubl
     if (coloured) DT_HIP(hipMemcpyAsync(L.act, L.has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
     DT_TRY(hy_iterate(s, L.flag, max_rounds, [&](int *f, const int *prev, int64_t r) {
       hy_flat_round(s, coloured, r, L.nsame, L.dist, w, tiles_x, tiles_y, f, prev, L.act, L.act1, L.has_flat,
-                    flat_sweeps);
+                    HY_FLAT_SWEEPS);
     }, &r2));
     DT_HIP(hipMemsetAsync(L.flag + 64, 0, sizeof(int), s));
     hipLaunchKernelGGL(k_flat_assign_m, gt, b, 0, s, (const uint8_t *)L.nsame, L.dist, w, fdr, L.flag + 64, tiles_x,
@@ -1492,8 +1490,6 @@ int dt_launch_condition_f64(hipStream_t s, const double *dem, int64_t H, int64_t
 template <typename T>
 static int hy_condition_async(hipStream_t s, const T *dem, int64_t H, int64_t W, double px, T *filled, uint8_t *fdr,
                               void *scratch, int rounds, int *status) {
-  const int fill_sweeps = dt_debug_get(DT_DBG_HY_FILL_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FILL_SWEEPS) : HY_FILL_SWEEPS;
-  const int flat_sweeps = dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) : HY_FLAT_SWEEPS;
   const int64_t n = H * W;
   if (n == 0) return DT_OK;
   DT_REQUIRE(fdr != nullptr, "the asynchronous conditioning writes the D8 codes");
@@ -1507,13 +1503,13 @@ static int hy_condition_async(hipStream_t s, const T *dem, int64_t H, int64_t W,
   const bool coloured = hy_tiles(H, W) >= hy_colour_min();
   for (int r = 0; r < rounds; r++)
     hy_fill_round(s, coloured, r, dem, filled, w, tiles_x, tiles_y, flags + r, r ? (const int *)(flags + r - 1) : nullptr,
-                  L.act, L.act1, fill_sweeps);
+                  L.act, L.act1, HY_FILL_SWEEPS);
   DT_TRY(hy_d8_flat_init(s, w, filled, px, fdr, L, tiles_x));
   if (coloured) DT_HIP(hipMemcpyAsync(L.act, L.has_flat, hy_tiles(H, W), hipMemcpyDeviceToDevice, s));
   int *fl2 = flags + rounds;
   for (int r = 0; r < rounds; r++)
     hy_flat_round(s, coloured, r, L.nsame, L.dist, w, tiles_x, tiles_y, fl2 + r, r ? (const int *)(fl2 + r - 1) : nullptr,
-                  L.act, L.act1, L.has_flat, flat_sweeps);
+                  L.act, L.act1, L.has_flat, HY_FLAT_SWEEPS);
   hipLaunchKernelGGL(k_flat_assign_m, gt, b, 0, s, (const uint8_t *)L.nsame, L.dist, w, fdr, flags + 2 * rounds, tiles_x,
                      (const uint8_t *)L.has_flat);
   hipLaunchKernelGGL(k_hydro_verdict, dim3(1), dim3(1), 0, s, (const int *)(flags + rounds - 1),
@@ -1538,10 +1534,6 @@ int dt_launch_condition_async_f64(hipStream_t s, const double *dem, int64_t H, i
 // leaves there instead of from the surface (k_flat_relax_m / k_flat_assign_m)
 int dt_launch_condition_stage(hipStream_t s, const DtWin &w, int stage, int rounds, const float *dem, float *filled,
                               uint8_t *fdr, uint32_t *dist, int *flag_dev, uint8_t *nsame) {
-  const int fill_sweeps = dt_debug_get(DT_DBG_HY_FILL_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FILL_SWEEPS) : HY_FILL_SWEEPS;
-  const int flat_sweeps = dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) > 0 ? dt_debug_get(DT_DBG_HY_FLAT_SWEEPS) : HY_FLAT_SWEEPS;
-  (void)fill_sweeps;
-  (void)flat_sweeps;
   const int64_t n = (int64_t)w.H * w.W;
   if (n == 0) return DT_OK;
   const int tiles_x = (w.W + HT - 1) / HT, tiles_y = (w.H + HT - 1) / HT;
@@ -1560,7 +1552,7 @@ int dt_launch_condition_stage(hipStream_t s, const DtWin &w, int stage, int roun
           if (hy_colour_blocks(c, tiles_x, tiles_y))
             hipLaunchKernelGGL(k_fill_relax<false>, dim3(hy_colour_blocks(c, tiles_x, tiles_y)), b, 0, s, dem, filled, w,
                                tiles_x, flag_dev, (const int *)nullptr, (const uint8_t *)nullptr, (uint8_t *)nullptr,
-                               tiles_y, fill_sweeps, c);
+                               tiles_y, HY_FILL_SWEEPS, c);
       break;
     case 2:
       DT_REQUIRE(filled && fdr && dist, "NULL pointer");
@@ -1574,11 +1566,11 @@ int dt_launch_condition_stage(hipStream_t s, const DtWin &w, int stage, int roun
             if (nsame)
               hipLaunchKernelGGL(k_flat_relax_m, dim3(hy_colour_blocks(c, tiles_x, tiles_y)), b, 0, s,
                                  (const uint8_t *)nsame, dist, w, tiles_x, flag_dev, (const int *)nullptr,
-                                 (const uint8_t *)nullptr, (uint8_t *)nullptr, tiles_y, flat_sweeps, c);
+                                 (const uint8_t *)nullptr, (uint8_t *)nullptr, tiles_y, HY_FLAT_SWEEPS, c);
             else
               hipLaunchKernelGGL(k_flat_relax, dim3(hy_colour_blocks(c, tiles_x, tiles_y)), b, 0, s, filled, dist, w,
                                  tiles_x, flag_dev, (const int *)nullptr, (const uint8_t *)nullptr, (uint8_t *)nullptr,
-                                 tiles_y, flat_sweeps, c);
+                                 tiles_y, HY_FLAT_SWEEPS, c);
           }
       break;
     case 4:

@@ -12,7 +12,7 @@ int dt_launch_stencil(hipStream_t s, const DtWin &w, const float *dem, double px
 static inline int dt_nodata4_ld(int64_t W) { return (int)((((W + 3) / 4) + 7) & ~(int64_t)7); }
 static inline size_t dt_nodata4_bytes(int64_t H, int64_t W) { return (size_t)((H + 3) / 4) * (size_t)dt_nodata4_ld(W) * 2; }
 // workspace of the stencil's hot / fix-up kernel pairs and of the TI / MTI epilogue (dt_tiles.hip): a mark byte and 256
-// 16-bit lane masks per tile of the launch's own geometry; dt_stencil_aux_bytes: the largest geometry of an H x W window
+// 16-bit lane masks per 256 x 16 tile; dt_stencil_aux_bytes: for the tiles of an H x W window
 struct DtStencilAux {
   uint8_t *mark;
   uint16_t *lmask;

@@ -747,7 +747,7 @@ __device__ __attribute__((noinline)) void ds_finish_overflow(const DtWin &w, con
 // bit-identical to k_downslope.  75 KiB of LDS: two workgroups per CU; workgroups are banded per XCD so
 // overlapping margins come from L2.
 #define DW_CORE 64
-// margin DW_M (template parameter: 24 by default; DT_DBG_DS_MARGIN tries 16 / 20), window DW_WIN = core + 2 margins
+// margin DW_M (a template parameter, always 24: DESIGN.md 4.4), window DW_WIN = core + 2 margins
 // LDS row stride in cells.  Lanes that merged onto one flow path trail each other by a few cells; with a
 // stride of 112 dwords (= 16 mod 32 banks) two cells 2 rows apart in one column share a bank, the common
 // case on south-flowing terrain.  116 = 20 mod 32: same column conflicts only 8 rows apart, the diagonals
@@ -1065,6 +1065,7 @@ __device__ __forceinline__ void ds_win_body(const float *__restrict__ dem,
   }
 }
 
+// (only <24> is launched; the parameter keeps the name the profiles and the benchmark know the kernel by)
 template <int DW_M>
 __global__ __launch_bounds__(1024, 8) void k_downslope_win(const float *__restrict__ dem,
                                                        const uint8_t *__restrict__ fdr, DtWin w, double px, double dz,
@@ -1724,9 +1725,7 @@ int dt_launch_downslope(hipStream_t s, const DtWin &w, const float *dem, const u
   }
   DtDsLift L = {};  // tab: two ping-pong tables and the 8-move table that is kept
   const bool ranked = !(w.halo == 0 && w.gy0 == 0 && w.gx0 == 0 && w.Hg == w.H && w.Wg == w.W);
-  // margin of the LDS window around the 64 x 64 core: walks that reach the window's ring carry on in global memory
-  const int m = dt_debug_get(DT_DBG_DS_MARGIN);
-  if (qwork && ds_mem_cells(w) < 0x7FFFFFFFull && m != 16 && m != 20) {  // (the A/B margins run without the queue)
+  if (qwork && ds_mem_cells(w) < 0x7FFFFFFFull) {
     DtCarver cq(qwork), ct(twork);
     ds_carve_queue(cq, w, L);
     ds_carve_tables(ct, w, L);  // all null without twork
@@ -1737,13 +1736,7 @@ int dt_launch_downslope(hipStream_t s, const DtWin &w, const float *dem, const u
   DT_REQUIRE(phase == 0 || q.entries, "the phases of the long-walk form need the queue workspace (and a window of < 2^31 cells)");
   if (phase != 2) {
     if (q.entries) DT_HIP(hipMemsetAsync(q.count, 0, sizeof(uint32_t), s));
-    if (m == 16)
-      hipLaunchKernelGGL(k_downslope_win<16>, dim3((unsigned)ntiles), dim3(1024), 0, s, dem, fdr, w, px, dz, dzf, raw,
-                         out, tiles_x, (int)ntiles, n_unresolved);
-    else if (m == 20)
-      hipLaunchKernelGGL(k_downslope_win<20>, dim3((unsigned)ntiles), dim3(1024), 0, s, dem, fdr, w, px, dz, dzf, raw,
-                         out, tiles_x, (int)ntiles, n_unresolved);
-    else if (ranked && q.entries)
+    if (ranked && q.entries)
       hipLaunchKernelGGL(k_downslope_win_rq, dim3((unsigned)ntiles), dim3(1024), 0, s, dem, fdr, w, px, dz, dzf, raw,
                          out, tiles_x, (int)ntiles, n_unresolved, q, wo);
     else if (ranked)

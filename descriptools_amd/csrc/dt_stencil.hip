@@ -124,38 +124,6 @@ __device__ __forceinline__ int sd_tile_of_block(int b, int ntiles) {
   int k = j + xcd * (n >> 3);
   return base + (k >= n ? k - n : k);
 }
-// Experimental workgroup -> tile maps of the fused stencil (DT_DBG_TWI_MAP = mode | param << 8), for the placement
-// study of DESIGN.md 6: the band map above makes the eight XCDs sweep eight 4-MiB windows per raster that stay a
-// fixed distance apart; the others change which parts of the rasters are written at the same time.
-//   1  bands without the stagger            2  tile rows dealt round-robin to the XCDs (one moving front per raster)
-//   3  groups of `param` tile rows per XCD, round-robin        4  bands, stagger of xcd * param tiles
-//   5  bands walked in chunks of 256 tiles in a scrambled order (chunk * 5 + 3 xcd mod chunks)
-__device__ __forceinline__ int sd_tile_of_block_x(int b, int tiles_x, int tiles_y, int mode_param) {
-  const int ntiles = tiles_x * tiles_y, mode = mode_param & 0xFF, param = mode_param >> 8;
-  const int xcd = b & 7, j = b >> 3, q = ntiles >> 3;
-  if ((ntiles & 7) != 0 || mode == 0) return sd_tile_of_block(b, ntiles);
-  if (mode == 1) return xcd * q + j;
-  if (mode == 2 || mode == 3) {
-    const int G = mode == 2 ? 1 : (param > 0 ? param : 2);
-    if (tiles_y % (8 * G) != 0) return sd_tile_of_block(b, ntiles);
-    const int jr = j / tiles_x, jc = j - jr * tiles_x;
-    const int row = ((jr / G) * 8 + xcd) * G + jr % G;
-    return row * tiles_x + jc;
-  }
-  if (mode == 4) {
-    int k = j + xcd * param;
-    k %= q;
-    return xcd * q + k;
-  }
-  if (mode == 5) {
-    const int nch = q >> 8;
-    if (nch < 2 || (q & 255) != 0) return sd_tile_of_block(b, ntiles);
-    const int ch = j >> 8, in = j & 255;
-    const int ch2 = (int)(((unsigned)ch * 5u + 3u * (unsigned)xcd) % (unsigned)nch);
-    return xcd * q + ch2 * 256 + in;
-  }
-  return sd_tile_of_block(b, ntiles);
-}
 
 __device__ __forceinline__ void sd_tile_origin(int b, int tiles_x, int tiles_y, int &x0, int &y0) {
   int tile = sd_tile_of_block(b, tiles_x * tiles_y);
@@ -176,7 +144,6 @@ __device__ __forceinline__ float sd_centre(float v) { return __float_as_uint(v) 
 // stage (SD_TY + 2) x (SD_TX + 2) cells; outside the GLOBAL raster = -100 ring (slope.py:175); cells outside
 // the core but inside the global raster come from the halo of the window.  nodata (and everything outside
 // the raster) is staged as sd_nod(): see dt_slope_cell.  The caller synchronises.
-template <int TX = SD_TX, int TY = SD_TY>
 __device__ __forceinline__ void sd_stage(float *t, const float *__restrict__ dem, const DtWin &w, int x0, int y0,
                                          int vec_ok) {
   const int H = w.H, W = w.W;
@@ -186,39 +153,39 @@ __device__ __forceinline__ void sd_stage(float *t, const float *__restrict__ dem
   // before the first use (five 16-byte loads and one halo value in flight per thread).  The guarded loop below
   // waits for each load before the next: five dependent memory round trips per workgroup, which made every
   // stencil kernel latency-bound (the D8-only kernel took as long as the 8 B/cell slope kernel).
-  if (vec_ok && y0 - 1 >= ylo && y0 + TY + 1 <= yhi && x0 - 1 >= xlo && x0 + TX + 1 <= xhi) {
-    constexpr int NV = ((TY + 2) * (TX / 4) + 255) / 256;  // 5
+  if (vec_ok && y0 - 1 >= ylo && y0 + SD_TY + 1 <= yhi && x0 - 1 >= xlo && x0 + SD_TX + 1 <= xhi) {
+    constexpr int NV = ((SD_TY + 2) * (SD_TX / 4) + 255) / 256;  // 5
     float4 v[NV];
     const float *base = dem + (long long)(y0 - 1) * w.ld + x0;
 #pragma unroll
     for (int u = 0; u < NV; u++) {
       const int i = threadIdx.x + 256 * u;
-      if (i < (TY + 2) * (TX / 4)) {
-        const int r = i / (TX / 4), c4 = i - r * (TX / 4);
+      if (i < (SD_TY + 2) * (SD_TX / 4)) {
+        const int r = i / (SD_TX / 4), c4 = i - r * (SD_TX / 4);
         v[u] = *reinterpret_cast<const float4 *>(base + (long long)r * w.ld + c4 * 4);
       }
     }
     float hv = 0.0f;
     const int hr = threadIdx.x >> 1, hside = threadIdx.x & 1;
-    if (threadIdx.x < (TY + 2) * 2) hv = base[(long long)hr * w.ld + (hside ? TX : -1)];
+    if (threadIdx.x < (SD_TY + 2) * 2) hv = base[(long long)hr * w.ld + (hside ? SD_TX : -1)];
 #pragma unroll
     for (int u = 0; u < NV; u++) {
       const int i = threadIdx.x + 256 * u;
-      if (i < (TY + 2) * (TX / 4)) {
-        const int r = i / (TX / 4), c4 = i - r * (TX / 4);
+      if (i < (SD_TY + 2) * (SD_TX / 4)) {
+        const int r = i / (SD_TX / 4), c4 = i - r * (SD_TX / 4);
         float4 q = v[u];
         q.x = sd_stage_val(q.x);
         q.y = sd_stage_val(q.y);
         q.z = sd_stage_val(q.z);
         q.w = sd_stage_val(q.w);
-        *reinterpret_cast<float4 *>(&t[r * (TX + 8) + 4 + c4 * 4]) = q;
+        *reinterpret_cast<float4 *>(&t[r * SD_LDW + 4 + c4 * 4]) = q;
       }
     }
-    if (threadIdx.x < (TY + 2) * 2) t[hr * (TX + 8) + (hside ? 4 + TX : 3)] = sd_stage_val(hv);
+    if (threadIdx.x < (SD_TY + 2) * 2) t[hr * SD_LDW + (hside ? 4 + SD_TX : 3)] = sd_stage_val(hv);
     return;
   }
-  for (int i = threadIdx.x; i < (TY + 2) * (TX / 4); i += 256) {
-    int r = i / (TX / 4), c4 = i - r * (TX / 4);
+  for (int i = threadIdx.x; i < (SD_TY + 2) * (SD_TX / 4); i += 256) {
+    int r = i / (SD_TX / 4), c4 = i - r * (SD_TX / 4);
     int gy = y0 - 1 + r, gx = x0 + c4 * 4;
     float4 v = make_float4(DT_NODATA, DT_NODATA, DT_NODATA, DT_NODATA);
     if (gy >= ylo && gy < yhi) {
@@ -236,14 +203,14 @@ __device__ __forceinline__ void sd_stage(float *t, const float *__restrict__ dem
     v.y = sd_stage_val(v.y);
     v.z = sd_stage_val(v.z);
     v.w = sd_stage_val(v.w);
-    *reinterpret_cast<float4 *>(&t[r * (TX + 8) + 4 + c4 * 4]) = v;
+    *reinterpret_cast<float4 *>(&t[r * SD_LDW + 4 + c4 * 4]) = v;
   }
-  for (int i = threadIdx.x; i < (TY + 2) * 2; i += 256) {
+  for (int i = threadIdx.x; i < (SD_TY + 2) * 2; i += 256) {
     int r = i >> 1, side = i & 1;
-    int gy = y0 - 1 + r, gx = side ? x0 + TX : x0 - 1;
+    int gy = y0 - 1 + r, gx = side ? x0 + SD_TX : x0 - 1;
     float v = DT_NODATA;
     if (gy >= ylo && gy < yhi && gx >= xlo && gx < xhi) v = dem[(long long)gy * w.ld + gx];
-    t[r * (TX + 8) + (side ? 4 + TX : 3)] = sd_stage_val(v);
+    t[r * SD_LDW + (side ? 4 + SD_TX : 3)] = sd_stage_val(v);
   }
 }
 
@@ -394,51 +361,40 @@ __device__ __forceinline__ bool sd_slope_fast(float c, float nw, float n, float 
 typedef float sd_v4f __attribute__((ext_vector_type(4)));
 typedef int sd_v4i __attribute__((ext_vector_type(4)));
 typedef long long sd_v2l __attribute__((ext_vector_type(2)));
-// Cache policy of the fused stencil's streams (POL; DT_DBG_TWI_PLAIN selects it for A/B runs):
-//   0 plain loads, plain stores      1 nt loads, nt stores (the default)      2 nt loads, plain stores
-//   3 nt loads, sc1 stores (write-through: the bytes leave L2 in issue order instead of eviction order)
-//   4 nt loads, sc0 sc1 stores       5 plain loads, nt stores
-template <int POL>
+// The fused stencil's streams are non-temporal, the loads of the accumulation raster and the stores of the outputs:
+// each byte is touched once (0.86 instead of 0.92 ms at 16384^2).
 __device__ __forceinline__ void sd_store4(float *p, float a, float b, float c, float d) {
   sd_v4f v = {a, b, c, d};
-  if (POL == 1 || POL == 5) __builtin_nontemporal_store(v, reinterpret_cast<sd_v4f *>(p));
-  else if (POL == 3) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-  else if (POL == 4) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-  else *reinterpret_cast<sd_v4f *>(p) = v;
+  __builtin_nontemporal_store(v, reinterpret_cast<sd_v4f *>(p));
 }
 
-// WX = waves of a workgroup side by side: the tile is 256 WX columns x 16 / WX rows (256 x 16, 512 x 8 or 1024 x 4;
-// always 4096 cells, one 4 x 4 patch per lane, a wave = 256 columns x 4 rows).  AccT = width of the accumulation raster.
-template <bool W_SLOPE, bool W_RAD, int POL, typename AccT, int WX>
-__global__ __launch_bounds__(256, WX == 1 ? 8 : (WX == 2 ? 7 : 6)) void k_slope_twi(const float *__restrict__ dem, DtWin w, double kc, double kd,
+// The tile is 256 x 16 cells: one 4 x 4 patch per lane, a wave = 256 columns x 4 rows.  AccT = width of the
+// accumulation raster.
+template <bool W_SLOPE, bool W_RAD, typename AccT>
+__global__ __launch_bounds__(256, 8) void k_slope_twi(const float *__restrict__ dem, DtWin w, double kc, double kd,
                                                      float *__restrict__ slope, float *__restrict__ slope_rad,
                                                      const AccT *__restrict__ acc32, double n_top, double lnpx2,
                                                      float *__restrict__ ti, float *__restrict__ mti, int tiles_x,
                                                      int tiles_y, int vec_ok, uint8_t *__restrict__ tile_mark,
-                                                     uint16_t *__restrict__ lane_mask, uint32_t flag_all,
-                                                     int map_mode) {
-  constexpr int TX = SD_TX * WX, TY = SD_TY / WX, LDW = TX + 8;
-  constexpr bool NT = POL >= 1 && POL <= 4;  // non-temporal loads of the accumulation raster
-  __shared__ __attribute__((aligned(16))) float t[(TY + 2) * LDW];
+                                                     uint16_t *__restrict__ lane_mask, uint32_t flag_all) {
+  __shared__ __attribute__((aligned(16))) float t[(SD_TY + 2) * SD_LDW];
   const double nlnpx2 = n_top * lnpx2;
   // (tried: identity and row-interleaved block -> tile maps instead of one band per XCD: 2 % slower)
-  const int tile = map_mode ? sd_tile_of_block_x(blockIdx.x, tiles_x, tiles_y, map_mode)
-                            : sd_tile_of_block(blockIdx.x, tiles_x * tiles_y);
+  const int tile = sd_tile_of_block(blockIdx.x, tiles_x * tiles_y);
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-  const int x0 = txi * TX, y0 = tyi * TY;
+  const int x0 = txi * SD_TX, y0 = tyi * SD_TY;
   const int H = w.H, W = w.W;
-  sd_stage<TX, TY>(t, dem, w, x0, y0, vec_ok);
+  sd_stage(t, dem, w, x0, y0, vec_ok);
   __syncthreads();
 
   const int tx = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int wx0 = (wv % WX) * 256;              // tile column of the wave's first cell
-  const int cx = wx0 + tx * 4, ry = (wv / WX) * 4;  // tile column / row of the lane's 4 x 4 patch
+  const int cx = tx * 4, ry = wv * 4;  // tile column / row of the lane's 4 x 4 patch
   const int gx = x0 + cx;
   // every lane stays active to the end (its neighbours' DPP reads need it); stores are guarded
   auto load_row = [&](int lr, float *dst) {
-    const float *row = &t[lr * LDW];
+    const float *row = &t[lr * SD_LDW];
     float4 m = *reinterpret_cast<const float4 *>(row + 4 + cx);
-    float lh = row[3 + wx0], rh = row[4 + wx0 + 256];  // columns beside the wave: wave-uniform address (broadcast)
+    float lh = row[3], rh = row[4 + SD_TX];  // columns beside the wave: wave-uniform address (broadcast)
     dst[0] = sd_from_prev_lane(lh, m.w);
     dst[1] = m.x;
     dst[2] = m.y;
@@ -460,11 +416,10 @@ __global__ __launch_bounds__(256, WX == 1 ? 8 : (WX == 2 ? 7 : 6)) void k_slope_
       const AccT *pf = acc32 + o;
       if (full && sizeof(AccT) == 8) {
         const sd_v2l *p2 = reinterpret_cast<const sd_v2l *>(pf);
-        sd_v2l a2 = NT ? __builtin_nontemporal_load(p2) : p2[0], b2 = NT ? __builtin_nontemporal_load(p2 + 1) : p2[1];
+        sd_v2l a2 = __builtin_nontemporal_load(p2), b2 = __builtin_nontemporal_load(p2 + 1);
         fv[0] = (AccT)a2.x; fv[1] = (AccT)a2.y; fv[2] = (AccT)b2.x; fv[3] = (AccT)b2.y;
       } else if (full) {
-        sd_v4i f4 = NT ? __builtin_nontemporal_load(reinterpret_cast<const sd_v4i *>(pf))
-                       : *reinterpret_cast<const sd_v4i *>(pf);
+        sd_v4i f4 = __builtin_nontemporal_load(reinterpret_cast<const sd_v4i *>(pf));
         fv[0] = (AccT)f4.x; fv[1] = (AccT)f4.y; fv[2] = (AccT)f4.z; fv[3] = (AccT)f4.w;
       } else {
         if (gx < W) fv[0] = pf[0];
@@ -501,10 +456,10 @@ __global__ __launch_bounds__(256, WX == 1 ? 8 : (WX == 2 ? 7 : 6)) void k_slope_
     }
     if (gy < H) {
       if (full) {
-        if (W_SLOPE) sd_store4<POL>(slope + o, so[0], so[1], so[2], so[3]);
-        if (W_RAD) sd_store4<POL>(slope_rad + o, ro[0], ro[1], ro[2], ro[3]);
-        sd_store4<POL>(ti + o, tio[0], tio[1], tio[2], tio[3]);
-        sd_store4<POL>(mti + o, mtio[0], mtio[1], mtio[2], mtio[3]);
+        if (W_SLOPE) sd_store4(slope + o, so[0], so[1], so[2], so[3]);
+        if (W_RAD) sd_store4(slope_rad + o, ro[0], ro[1], ro[2], ro[3]);
+        sd_store4(ti + o, tio[0], tio[1], tio[2], tio[3]);
+        sd_store4(mti + o, mtio[0], mtio[1], mtio[2], mtio[3]);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -533,7 +488,7 @@ __global__ __launch_bounds__(256, WX == 1 ? 8 : (WX == 2 ? 7 : 6)) void k_slope_
 }
 
 // the cold half: exact recomputation of the flagged cells (a handful per raster)
-template <typename AccT, int WX>
+template <typename AccT>
 __global__ __launch_bounds__(256) void k_slope_twi_fix(const float *__restrict__ dem, DtWin w, double px,
                                                       float *__restrict__ slope, float *__restrict__ slope_rad,
                                                       const AccT *__restrict__ acc32, double n_top, double lnpx2,
@@ -541,8 +496,7 @@ __global__ __launch_bounds__(256) void k_slope_twi_fix(const float *__restrict__
                                                       int tiles_y, int vec_ok, const uint8_t *__restrict__ tile_mark,
                                                       const uint16_t *__restrict__ lane_mask,
                                                       const DtLogEntry *__restrict__ g_tab) {
-  constexpr int TX = SD_TX * WX, TY = SD_TY / WX, LDW = TX + 8;
-  __shared__ __attribute__((aligned(16))) float t[(TY + 2) * LDW];
+  __shared__ __attribute__((aligned(16))) float t[(SD_TY + 2) * SD_LDW];
   const int ntiles = tiles_x * tiles_y;
   const double dcard = px, ddiag = px * sqrt(2.0);
   const double inv_card = 1.0 / dcard, inv_diag = 1.0 / ddiag;
@@ -558,23 +512,22 @@ __global__ __launch_bounds__(256) void k_slope_twi_fix(const float *__restrict__
       if (!s_mark[i]) continue;  // block-uniform
       const int tile = chunk * 256 + i;
       const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-      const int x0 = txi * TX, y0 = tyi * TY;
+      const int x0 = txi * SD_TX, y0 = tyi * SD_TY;
       __syncthreads();  // the previous tile's readers are done with t
-      sd_stage<TX, TY>(t, dem, w, x0, y0, vec_ok);
+      sd_stage(t, dem, w, x0, y0, vec_ok);
       __syncthreads();
       uint32_t mask = lane_mask[(size_t)tile * 256 + threadIdx.x];
-      const int wv = threadIdx.x >> 6;
-      const int cx = (wv % WX) * 256 + (threadIdx.x & 63) * 4, ry = (wv / WX) * 4;
+      const int cx = (threadIdx.x & 63) * 4, ry = (threadIdx.x >> 6) * 4;
       while (mask) {
         const int bit = __ffs((int)mask) - 1;
         mask &= mask - 1u;
         const int j = bit >> 2, k = bit & 3;
         const int gy = y0 + ry + j, gx = x0 + cx + k;
         if (gy >= w.H || gx >= w.W) continue;
-        const float *p = &t[(ry + j + 1) * LDW + 4 + cx + k];  // the centre in the staged tile
+        const float *p = &t[(ry + j + 1) * SD_LDW + 4 + cx + k];  // the centre in the staged tile
         const float cz = sd_centre(p[0]);
-        SlopeCell sc = dt_slope_cell<false, true>(cz, p[-LDW - 1], p[-LDW], p[-LDW + 1], p[-1], p[1],
-                                                  p[LDW - 1], p[LDW], p[LDW + 1], inv_card, inv_diag, dcard,
+        SlopeCell sc = dt_slope_cell<false, true>(cz, p[-SD_LDW - 1], p[-SD_LDW], p[-SD_LDW + 1], p[-1], p[1],
+                                                  p[SD_LDW - 1], p[SD_LDW], p[SD_LDW + 1], inv_card, inv_diag, dcard,
                                                   ddiag);
         const long long o = (long long)gy * w.ld + gx;
         const float rad = dt_slope_rad(sc.slope, cz);
@@ -687,24 +640,15 @@ __global__ __launch_bounds__(256) void k_d8_fix(const float *__restrict__ dem, D
   }
 }
 
-// bytes of the mark / mask workspace for an H x W window: DtStencilAux at the largest tile count of the three tile
-// geometries (they differ on ragged rasters)
-static int64_t sd_aux_tiles(int64_t H, int64_t W) {
-  int64_t ntiles = 0;
-  for (int wx = 1; wx <= 4; wx *= 2) {
-    const int64_t tx = SD_TX * wx, ty = SD_TY / wx, n = ((W + tx - 1) / tx) * ((H + ty - 1) / ty);
-    ntiles = n > ntiles ? n : ntiles;
-  }
-  return ntiles;
-}
+// bytes of the mark / mask workspace for an H x W window: DtStencilAux at its count of 256 x 16 tiles
+static int64_t sd_aux_tiles(int64_t H, int64_t W) { return ((W + SD_TX - 1) / SD_TX) * ((H + SD_TY - 1) / SD_TY); }
 size_t dt_stencil_aux_bytes(int64_t H, int64_t W) { return dt_stencil_aux_layout(sd_aux_tiles(H, W), nullptr).bytes; }
 
-// the fused slope + TI + MTI pair (hot kernel + fix-up of the flagged cells) for one tile geometry / accumulation width
-template <typename AccT, int WX>
+// the fused slope + TI + MTI pair (hot kernel + fix-up of the flagged cells) for one accumulation width
+template <typename AccT>
 static int launch_slope_twi(hipStream_t s, const DtWin &w, const float *dem, double px, float *slope, float *slope_rad,
                             const AccT *acc, double n_top, float *ti, float *mti, void *aux, int vec_ok) {
-  constexpr int TX = SD_TX * WX, TY = SD_TY / WX;
-  const int tiles_x = (int)((w.W + TX - 1) / TX), tiles_y = (int)((w.H + TY - 1) / TY);
+  const int tiles_x = (int)((w.W + SD_TX - 1) / SD_TX), tiles_y = (int)((w.H + SD_TY - 1) / SD_TY);
   const int64_t ntiles = (int64_t)tiles_x * tiles_y;
   DT_REQUIRE(ntiles < (1ll << 31), "raster too large for one launch");
   DT_REQUIRE(aux != nullptr, "fused TWI needs its mark / mask workspace");
@@ -715,33 +659,16 @@ static int launch_slope_twi(hipStream_t s, const DtWin &w, const float *dem, dou
   uint16_t *lmask = A.lmask;
   const double kc = 100.0 / px, kd = 100.0 / (px * sqrt(2.0)), lnpx2 = log(px * px);
   const DtLogEntry *g_tab = dt_math_device_table(s);
-#define DT_HOT(S, R, N)                                                                                             \
-  hipLaunchKernelGGL((k_slope_twi<S, R, N, AccT, WX>), g, b, 0, s, dem, w, kc, kd, slope, slope_rad, acc, n_top, lnpx2, \
-                     ti, mti, tiles_x, tiles_y, vec_ok, mark, lmask, dt_debug_get(DT_DBG_TWI_FLAG_ALL) ? 0xFFFFu : 0u, \
-                     dt_debug_get(DT_DBG_TWI_MAP))
-  // non-temporal loads of the accumulation raster and stores of the outputs (each byte is touched once):
-  // 0.86 instead of 0.92 ms at 16384^2; the knob selects another cache policy (sd_store4) for A/B runs of the
-  // benchmark's form of the kernel (slope + TI + MTI, int32 accumulation, 256 x 16 tiles)
-  const int pol = dt_debug_get(DT_DBG_TWI_PLAIN);
-  bool done = false;
-  if constexpr (WX == 1 && sizeof(AccT) == 4) {
-    if (ws && !wr && pol >= 1 && pol <= 5) {
-      if (pol == 1) DT_HOT(true, false, 0);
-      else if (pol == 2) DT_HOT(true, false, 2);
-      else if (pol == 3) DT_HOT(true, false, 3);
-      else if (pol == 4) DT_HOT(true, false, 4);
-      else DT_HOT(true, false, 5);
-      done = true;
-    }
-  }
-  if (done) {
-  } else if (ws && wr) DT_HOT(true, true, 1);
-  else if (ws) DT_HOT(true, false, 1);
-  else if (wr) DT_HOT(false, true, 1);
-  else DT_HOT(false, false, 1);
+#define DT_HOT(S, R)                                                                                               \
+  hipLaunchKernelGGL((k_slope_twi<S, R, AccT>), g, b, 0, s, dem, w, kc, kd, slope, slope_rad, acc, n_top, lnpx2, ti, \
+                     mti, tiles_x, tiles_y, vec_ok, mark, lmask, dt_debug_get(DT_DBG_TWI_FLAG_ALL) ? 0xFFFFu : 0u)
+  if (ws && wr) DT_HOT(true, true);
+  else if (ws) DT_HOT(true, false);
+  else if (wr) DT_HOT(false, true);
+  else DT_HOT(false, false);
 #undef DT_HOT
   unsigned fix_blocks = SD_FIX_SPLIT * dt_capped_grid(ntiles, 1024);
-  hipLaunchKernelGGL((k_slope_twi_fix<AccT, WX>), dim3(fix_blocks), b, 0, s, dem, w, px, slope, slope_rad, acc, n_top,
+  hipLaunchKernelGGL((k_slope_twi_fix<AccT>), dim3(fix_blocks), b, 0, s, dem, w, px, slope, slope_rad, acc, n_top,
                      lnpx2, ti, mti, tiles_x, tiles_y, vec_ok, mark, lmask, g_tab);
   return DT_OK;
 }
@@ -781,7 +708,7 @@ int dt_launch_slope_twi_fix(hipStream_t s, const DtWin &w, const float *dem, dou
   const int vec_ok = (w.W % 4 == 0) && (w.ld % 4 == 0) && ((uintptr_t)dem & 15) == 0;  // (the staging's loads)
   const DtStencilAux S = dt_stencil_aux_layout(ntiles, smarks);
   unsigned fix_blocks = SD_FIX_SPLIT * dt_capped_grid(ntiles, 1024);
-  hipLaunchKernelGGL((k_slope_twi_fix<int32_t, 1>), dim3(fix_blocks), dim3(256), 0, s, dem, w, px, slope, (float *)nullptr,
+  hipLaunchKernelGGL((k_slope_twi_fix<int32_t>), dim3(fix_blocks), dim3(256), 0, s, dem, w, px, slope, (float *)nullptr,
                      acc, n_top, log(px * px), ti, mti, tiles_x, tiles_y, vec_ok, (const uint8_t *)S.mark,
                      (const uint16_t *)S.lmask, dt_math_device_table(s));
   return DT_OK;
@@ -809,20 +736,9 @@ int dt_launch_stencil(hipStream_t s, const DtWin &w, const float *dem, double px
   hipLaunchKernelGGL((k_stencil<S, F, R>), g, b, 0, s, dem, w, px, slope, fdr, slope_rad, tiles_x, tiles_y, vec_ok)
   if (wt) {
     DT_REQUIRE(acc && mti, "fused TWI needs the accumulation raster, ti and mti");
-    // tile geometry (DT_DBG_TWI_WX: 1, 2 or 4 waves side by side; 0 = default), narrowed for narrow rasters
-    int wx = dt_debug_get(DT_DBG_TWI_WX);
-    if (wx != 1 && wx != 2 && wx != 4) wx = DT_TWI_WX_DEFAULT;
-    while (wx > 1 && W < (int64_t)SD_TX * wx) wx >>= 1;
-    if (acc64) {
-      const long long *a = (const long long *)acc;
-      if (wx == 4) return launch_slope_twi<long long, 4>(s, w, dem, px, slope, slope_rad, a, n_top, ti, mti, aux, vec_ok);
-      if (wx == 2) return launch_slope_twi<long long, 2>(s, w, dem, px, slope, slope_rad, a, n_top, ti, mti, aux, vec_ok);
-      return launch_slope_twi<long long, 1>(s, w, dem, px, slope, slope_rad, a, n_top, ti, mti, aux, vec_ok);
-    }
-    const int32_t *a = (const int32_t *)acc;
-    if (wx == 4) return launch_slope_twi<int32_t, 4>(s, w, dem, px, slope, slope_rad, a, n_top, ti, mti, aux, vec_ok);
-    if (wx == 2) return launch_slope_twi<int32_t, 2>(s, w, dem, px, slope, slope_rad, a, n_top, ti, mti, aux, vec_ok);
-    return launch_slope_twi<int32_t, 1>(s, w, dem, px, slope, slope_rad, a, n_top, ti, mti, aux, vec_ok);
+    if (acc64)
+      return launch_slope_twi(s, w, dem, px, slope, slope_rad, (const long long *)acc, n_top, ti, mti, aux, vec_ok);
+    return launch_slope_twi(s, w, dem, px, slope, slope_rad, (const int32_t *)acc, n_top, ti, mti, aux, vec_ok);
   } else if (ws && wf && wr) DT_GO(true, true, true);
   else if (ws && wf) DT_GO(true, true, false);
   else if (ws && wr) DT_GO(true, false, true);

@@ -2209,7 +2209,7 @@ int dt_launch_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const 
 // the shapes k_fa3fh1_twi takes: what the fused tile pass needs (rows of whole 64-cell tiles, 16-byte aligned rasters)
 // on a single raster, with 16-byte aligned slope / ti / mti
 bool dt_twi_epilogue_ok(const DtWin &w, const void *acc, const int8_t *river, const DtTwiEpilogue *twi) {
-  return dt_debug_get(DT_DBG_NO_FUSED_FA_FH) == 0 && w.W % TW == 0 && (w.ld & 3) == 0 && w.halo == 0 && w.gx0 == 0 &&
+  return w.W % TW == 0 && (w.ld & 3) == 0 && w.halo == 0 && w.gx0 == 0 &&
          w.gy0 == 0 && w.ld == w.W && ((uintptr_t)acc & 15) == 0 && ((uintptr_t)river & 3) == 0 && twi->marks &&
          twi->slope && twi->ti && twi->mti &&
          (((uintptr_t)twi->slope | (uintptr_t)twi->ti | (uintptr_t)twi->mti | (uintptr_t)twi->marks) & 15) == 0;
@@ -2237,7 +2237,7 @@ int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *f
                        ext_perim, P, f.ext);
   }
   if (dt_debug_get(DT_DBG_FA_SCATTER)) hipLaunchKernelGGL(k_fa_poison, gn, b, 0, s, f.rec, f.nnodes, f.entry_of, f.state, f.ext);
-  const bool fused = !acc64 && dt_debug_get(DT_DBG_NO_FUSED_FA_FH) == 0 && w.W % TW == 0 && (w.ld & 3) == 0 &&
+  const bool fused = !acc64 && w.W % TW == 0 && (w.ld & 3) == 0 &&
                      (((uintptr_t)acc | (uintptr_t)dem) & 15) == 0 && ((uintptr_t)river & 3) == 0;
   if (fused) {
     const FaIn in = fa_inputs(f, ext_perim);

@@ -53,11 +53,9 @@ const char *dt_version(void);
  * cross-checks the timed step against impl 1. */
 int dt_set_flow_impl(int impl);
 /* Test knobs, all 0 by default.  key 0 (DT_DBG_TWI_FLAG_ALL): the fused slope + TI + MTI stencil sends every
- * cell through its exact (cold) path as well as the fast one; key 1 (DT_DBG_TWI_PLAIN): default cache policy
- * instead of non-temporal loads / stores in that stencil (A/B timing); key 2 (DT_DBG_TWI_WX): tile geometry of that
- * stencil, 1 / 2 / 4 = tiles of 256 x 16 / 512 x 8 / 1024 x 4 cells (0 = the default); key 3 (DT_DBG_TWI_MAP): experimental
- * workgroup -> tile maps of that stencil; key 4 (DT_DBG_DS_MARGIN): margin of the downslope kernel's LDS window (16 / 20;
- * default 24); key 5 (DT_DBG_NO_FUSED_FA_FH): the last accumulation pass and HAND's first as two kernels (A/B timing). */
+ * cell through its exact (cold) path as well as the fast one; keys 8-11: see csrc/dt_common.h.  Keys 1-7 selected
+ * kernel variants of finished A/B runs and were retired with them: setting one is an error (DT_EINVAL) and changes
+ * nothing. */
 int dt_debug_set(int key, int value);
 
 /* Context = one device + one stream + grow-only scratch.  `stream` may be NULL (the context

@@ -25,7 +25,8 @@ def _check(dem, px):
     return fdr, filled, acc
 
 
-@pytest.mark.parametrize("H,W,seed", [(300, 417, 1), (64, 64, 2), (129, 1000, 3), (1, 77, 4), (50, 1, 5)])
+@pytest.mark.parametrize("H,W,seed", [(300, 417, 1), (64, 64, 2), (129, 1000, 3), (1, 77, 4), (50, 1, 5), (16, 16, 7),
+                                      (32, 32, 8)])
 def test_conditioning_on_rough_synthetic_terrain(H, W, seed):
     """tilted fBm with random pits, noise that breaks the monotone tilt, integer plateaus and nodata blobs"""
     rng = np.random.default_rng(seed)
@@ -101,7 +102,8 @@ def coloured_rounds():
     _lib.check(L.dt_debug_set(8, 0))
 
 
-@pytest.mark.parametrize("H,W,seed", [(300, 417, 1), (64, 64, 2), (129, 1000, 3), (1, 77, 4), (50, 1, 5), (700, 900, 6)])
+@pytest.mark.parametrize("H,W,seed", [(300, 417, 1), (64, 64, 2), (129, 1000, 3), (1, 77, 4), (50, 1, 5), (700, 900, 6),
+                                      (16, 16, 7), (32, 32, 8)])
 def test_coloured_rounds_on_rough_terrain(coloured_rounds, H, W, seed):
     """the coloured rounds reach the same fixed points: rasters of one tile, one row / column of tiles (two of the four
     colours have no tile), odd and even tile counts; synchronous and asynchronous form"""

@@ -57,17 +57,17 @@ def snapshot():
 
 res = {}
 for v in (0, val, 0, val):
-    L.dt_debug_set(key, v)
+    check(L.dt_debug_set(key, v))
     t = timed()
     res.setdefault(v, []).append(t)
     print("key %d = %d: " % (key, v) + "  ".join("%s %.3f" % kv for kv in t.items()), flush=True)
-L.dt_debug_set(key, 0)
+check(L.dt_debug_set(key, 0))
 timed()
 a = snapshot()
-L.dt_debug_set(key, val)
+check(L.dt_debug_set(key, val))
 timed()
 b = snapshot()
-L.dt_debug_set(key, 0)
+check(L.dt_debug_set(key, 0))
 for name in a:
     x, y = a[name], b[name]
     same = torch.equal(x, y) if x.dtype != torch.float32 else torch.equal(x.view(torch.int32), y.view(torch.int32))

@@ -3,9 +3,7 @@
 
   placement_probe.py gens [N]      N generations of the five rasters in ONE process (earlier generations kept alive, so
                                    every generation sits on different physical memory), each timed, the copy kernel
-                                   beside it; PROBE_WX=1 adds the other tile geometries, PROBE_POL=1 the other cache
-                                   policies, PROBE_MAP=1 the experimental workgroup -> tile maps on the same rasters
-                                   (dt_debug_set keys 2 / 1 / 3)
+                                   beside it; PROBE_MIX=1 adds plain read / write mixes on the same rasters
   placement_probe.py pick [K] [heap_gb]
                                    K candidate rasters allocated FIRST in the process: singles / pairs / triples as
                                    plain write streams, then the heap, then the fused stencil on the fastest and on
@@ -70,16 +68,6 @@ def mode_gens(gens):
         ms = timed(run)
         cp = timed(lambda: L.dt_dev_membench_copy(ctx.h, dem.data_ptr(), slope.data_ptr(), n, -1))
         extra = []
-        if os.environ.get("PROBE_WX"):
-            for wx in (2, 4):
-                L.dt_debug_set(2, wx)
-                extra.append("wx%d %.3f" % (wx, timed(run)))
-            L.dt_debug_set(2, 0)
-        if os.environ.get("PROBE_POL"):
-            for pol in (1, 2, 3, 4, 5):
-                L.dt_debug_set(1, pol)
-                extra.append("pol%d %.3f" % (pol, timed(run)))
-            L.dt_debug_set(1, 0)
         if os.environ.get("PROBE_MIX"):  # plain read / write mixes on the same five rasters (dt_dev_membench_mix)
             for nr, nw in ((2, 3), (1, 3), (0, 3), (2, 1), (1, 1), (2, 2)):
                 for nt in (1, 0):
@@ -87,11 +75,6 @@ def mode_gens(gens):
                                                             ti.data_ptr(), mti.data_ptr(), n, nr, nw, nt))
                     extra.append("%dr%dw%s %.3f=%.0f" % (nr, nw, "nt" if nt else "", t, n * 4 * (nr + nw) / t / 1e6))
             _lib.check(L.dt_dev_synth_dem(ctx.h, 1, S, S, 0, 0, S, S, 0, dem.data_ptr()))  # the mixes overwrote nothing of dem, fac
-        if os.environ.get("PROBE_MAP"):  # the experimental workgroup -> tile maps (DT_DBG_TWI_MAP = mode | param << 8)
-            for mode, param in ((1, 0), (2, 0), (3, 2), (3, 4), (3, 8), (4, 37), (4, 101), (4, 1000), (5, 0)):
-                L.dt_debug_set(3, mode | (param << 8))
-                extra.append("m%d.%d %.3f" % (mode, param, timed(run)))
-            L.dt_debug_set(3, 0)
         print("generation %d  slope+ti+mti %.3f ms (%.0f GB/s)   copy %.3f ms   dem at %#x  %s"
               % (g, ms, n * 20 / ms / 1e6, cp, dem.data_ptr(), "  ".join(extra)), flush=True)
     for a, b in ((0, gens - 1), (gens - 1, 0)):  # mixing generations: inputs of one, outputs of another
