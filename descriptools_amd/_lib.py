@@ -52,6 +52,7 @@ _SIGS = {
     "dt_upslope_length": (ci, [c_u8p, c_f32p, i64, i64, f64, c_f64p]),
     "dt_dinf_direction": (ci, [c_f32p, c_u8p, i64, i64, f64, c_f32p, c_f32p]),
     "dt_dinf_accumulate": (ci, [c_f32p, c_f64p, i64, i64, ci, c_f64p, c_i64p]),
+    "dt_dinf_distance_down": (ci, [c_f32p, c_i8p, c_f32p, i64, i64, f64, ci, ci, ci, c_f64p, c_f64p, c_f64p, c_i64p]),
     "dt_proximity": (ci, [c_i8p, c_f32p, i64, i64, f64, c_f32p, c_i64p]),
     "dt_reach_catchments": (ci, [c_i64p, c_i64p, i64, i64, c_i32p, c_i32p, c_i64p, i64, c_i64p]),
     "dt_reach_channels": (ci, [c_u8p, c_i32p, i64, i64, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),

@@ -1998,6 +1998,72 @@ extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H
   return hc.finish();
 }
 
+// rounds of tile visits between two looks at their flags: 8, 16, 32, then 64 (a round that follows a quiet one costs a
+// few microseconds; a path that winds through many tiles wants few host round trips per round)
+// (DT_DINF_DIST_BATCH_MAX, dt_kernels.h: what one launcher call takes)
+#define DT_DINF_DIST_BATCH0 8
+// A private diagnostic, not part of the C ABI (not in descriptools_hip.h, not bound by _lib): the tile visits of the
+// last dt_dinf_distance_down call that THIS THREAD made and that succeeded -- per thread, so that another thread's
+// call cannot land between a call and the question.  tools/dinf_distance_bench.py asks it by name.
+static thread_local int64_t t_dinf_distance_visits = 0;
+extern "C" int64_t dt_dinf_distance_visits_(void) { return t_dinf_distance_visits; }
+extern "C" int dt_dinf_distance_down(const float *angle, const int8_t *river, const float *dem, int64_t H, int64_t W,
+                                     double px, int stat, int check_edges, int visit_limit, double *h, double *v,
+                                     double *s, int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_REQUIRE(stat >= 0 && stat <= 2, "stat is 0 (ave), 1 (min) or 2 (max)");
+  DT_REQUIRE(check_edges == 0 || check_edges == 1, "check_edges is 0 or 1");
+  DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
+  DT_REQUIRE(dem || (!v && !s), "the vertical and the surface distance need heights");
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(angle && river && h, "NULL raster");
+  const bool z = dem && (v || s);
+  const float *d_a = hc.in(angle, n);
+  const int8_t *d_r = hc.in(river, n);
+  const float *d_z = z ? hc.in(dem, n) : nullptr;
+  double *d_h = hc.out(h, n);
+  double *d_v = !z ? nullptr : (v ? hc.out(v, n) : hc.scratch<double>(n));  // the kernel computes both or neither
+  double *d_s = !z ? nullptr : (s ? hc.out(s, n) : hc.scratch<double>(n));
+  const size_t need = dt_dinf_distance_scratch(H, W);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  uint32_t flags[DT_DINF_DIST_BATCH_MAX];
+  int64_t rounds = 0;
+  int batch = DT_DINF_DIST_BATCH0;
+  for (int start = 1;; start = 0) {
+    DT_TRY(dt_launch_dinf_distance(hc.c->stream, d_a, d_r, d_z, H, W, px, stat, check_edges, visit_limit, start,
+                                   batch, 0, scr, need, d_h, d_v, d_s, hc.c->status));
+    DT_TRY(hc.download(flags, dt_dinf_distance_ctl(scr, H, W), (size_t)batch));
+    DT_HIP(hipStreamSynchronize(hc.c->stream));
+    int used = 0;
+    while (used < batch && flags[used]) used++;
+    rounds += used;
+    if (used < batch) break;  // a quiet round: nothing is left that can settle
+    DT_REQUIRE(rounds <= (int64_t)n, "more rounds than cells (a defect: every round but the last settles a cell)");
+    if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
+  }
+  DT_TRY(dt_launched(dt_launch_dinf_distance(hc.c->stream, d_a, d_r, d_z, H, W, px, stat, check_edges, visit_limit, 0,
+                                             0, 1, scr, need, d_h, d_v, d_s, hc.c->status)));
+  uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
+  DT_TRY(hc.download(cnt, dt_dinf_distance_ctl(scr, H, W) + DT_DINF_DIST_BATCH_MAX, 6));
+  DT_TRY(dt_ctx_status(hc.c, &st));  // (synchronises)
+  DT_REQUIRE(!(st & DT_STATUS_BAD_ANGLE), "an angle is neither -1, -100 nor in [0, float32(2 pi)]");
+  if (info4) {
+    info4[0] = rounds;
+    info4[1] = cnt[0];
+    info4[2] = cnt[1];
+    info4[3] = cnt[2];
+  }
+  t_dinf_distance_visits = (int64_t)cnt[4] | (int64_t)cnt[5] << 32;
+  return hc.finish();
+}
+
 extern "C" int dt_proximity(const int8_t *river, const float *nod, int64_t H, int64_t W, double px, float *distance,
                             int64_t *indices) {
   HostCall hc;

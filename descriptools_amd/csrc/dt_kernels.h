@@ -277,6 +277,25 @@ int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *w
 // that found work, the largest window, two-receiver cells
 const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 
+// D-infinity distance down to the stream (dt_dinf_dist.hip; dinf.py holds the definition): the horizontal distance h
+// and, with heights, the vertical drop v and the surface distance s along the D-infinity flow field to the targets
+// (river == 1 and not nodata), stat 0 / 1 / 2 = average / minimum / maximum over the two receivers; the outputs hold
+// -100 where a cell does not reach.  dem NULL: h alone (v and s NULL); otherwise v and s are both given.  The state
+// lives in `scratch`: start != 0 sets it up, `rounds` (0..DT_DINF_DIST_BATCH_MAX) rounds of tile visits follow, round r raising control
+// word r when it settled something (a round that follows a quiet one returns at once), finish != 0 writes -100 on what
+// does not reach and counts the reaching / dead / unsettled cells into control words 64 / 65 / 66 and the tile visits
+// of the call (64 bits) into words 68-69.  visit_limit: 0, or
+// the sweeps a workgroup makes over its tile per visit at most (tests); the result does not depend on it.  An angle
+// outside the contract raises DT_STATUS_BAD_ANGLE on `status`.  Nothing synchronises.  H * W < 2^31.
+#define DT_DINF_DIST_BATCH_MAX 64  // rounds one launcher call takes at most: the flag words of a batch
+size_t dt_dinf_distance_scratch(int64_t H, int64_t W);
+int dt_launch_dinf_distance(hipStream_t s, const float *angle, const int8_t *river, const float *dem, int64_t H,
+                            int64_t W, double px, int stat, int check_edges, int visit_limit, int start, int rounds,
+                            int finish, void *scratch, size_t scratch_bytes, double *h, double *v, double *sf,
+                            int *status);
+// the control words in `scratch` (72 x uint32 on the device)
+const uint32_t *dt_dinf_distance_ctl(void *scratch, int64_t H, int64_t W);
+
 // Euclidean proximity (dt_proximity.hip): for every cell the nearest source (river == 1 and, with nod, nod > -100) by
 // exact squared distance, ties to the smallest flat index -> distance = float32(px * sqrt(float64(d2))) and indices =
 // the source's flat index; -100 where nod <= -100 and when there is no source.  nod may be NULL.  The row pass, the

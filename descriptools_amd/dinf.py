@@ -1,5 +1,6 @@
-"""D-infinity flow direction and contributing area (net-new; Tarboton 1997, TauDEM's DinfFlowDir / AreaDinf): a flow
-angle on eight triangular facets, the flow of a cell split between the two neighbours that bracket its angle.
+"""D-infinity flow direction, contributing area and distance down to the stream (net-new; Tarboton 1997, TauDEM's
+DinfFlowDir / AreaDinf / DinfDistDown): a flow angle on eight triangular facets, the flow of a cell split between the
+two neighbours that bracket its angle.
 
 Angle convention.  Radians, counter-clockwise from east; rows grow to the south.  Octant k (0..7) is the neighbour at
 angle k pi / 4: E, NE, N, NW, W, SW, S, SE -- the D8 codes 1, 128, 64, 32, 16, 8, 4, 2.  A height is valid when it is
@@ -35,17 +36,50 @@ c sends m2 = floor(T * P2 / 2^30) (the 82-bit product taken exactly) to octant k
 mass is conserved and no T exceeds the sum of q <= 2^52.  result(c) = ldexp(T(c) - q(c), -s): self excluded, as in
 flowacc.accumulate; -100 on nodata and on every cell on or downstream of a cycle (its inflow never completes).  The
 result does not depend on order or run.  On angles float32(k pi / 4) made from a D8 raster it is
-flowacc.accumulate(fdr) exactly (frac_bits=0)."""
+flowacc.accumulate(fdr) exactly (frac_bits=0).
+
+distance_down / hand.  The distance from every cell down the D-infinity flow field to the stream, as TauDEM's
+DinfDistDown computes it; TauDEM itself was not at hand when this was written, so what follows is our reading of it
+and, with the numpy reference of the test suite, the definition.  Inputs: `angle` under accumulate's contract and
+decoding; `river`, taken as int8: a TARGET is a cell with river == 1 whose angle is not -100; `px` finite and > 0;
+`dem`, optional float32 heights, taken as given (nodata is decided by `angle` alone).  Three measures: horizontal h,
+vertical v, surface s.  For a hop c -> d at octant k: L = px when k is even, else px * 1.4142135623730951 (one float64
+product); dz = float64(dem[c]) - float64(dem[d]); S = sqrt(L * L + dz * dz).  Every cell is in one of three states,
+reaches / dead / unsettled.  Targets reach, with h = v = s = 0.  A non-target, non-nodata cell without any edge (angle
+-1, or every share pointing off the raster or into nodata) is dead.  Any other cell settles once EVERY receiver it has
+an edge to is settled: with check_edges=True it reaches iff no share of it leaves the domain and every receiver reaches
+(TauDEM's edge-contamination rule), with check_edges=False iff at least one receiver reaches; otherwise it is dead.  A
+cell that never settles (on a cycle, or with a receiver that never settles) stays unsettled in either mode.  For a
+reaching cell the terms t_j = m(d_j) + hop_m(c -> d_j) are taken over its reaching receivers in the order j = 0, 1
+(octant k, octant k + 1).  One term: the value is that term.  Two terms: ave = (float64(w0) * t0 + float64(w1) * t1) *
+2^-30 with w0 = 2^30 - P2, w1 = P2; min = t1 if t1 < t0 else t0; max = t1 if t1 > t0 else t0; the statistic is applied
+to each measure on its own.  All outputs are float64; nodata and every cell that does not reach hold -100; h >= 0 where
+a cell reaches, so h == -100 is the mask.  All arithmetic is IEEE float64 in exactly this association, and a value is a
+pure function of its receivers' final values: the result is unique, independent of schedule, rounds and run, and equal
+to the numpy reference bit for bit.  A non-finite height on a reaching path gives IEEE's inf / NaN in v and s there; h
+is not affected."""
 import math
 
 import numpy as np
 
 from . import _lib
-from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, ptr
+from ._lib import c_f32p, c_f64p, c_i8p, c_i64p, c_u8p, check, ptr
 from .flowacc import _FRAC_BITS_MAX, _SUM_BITS, _default_frac_bits, _weights_f64
 
 F2PI = np.float32(2.0 * math.pi)
 _CELLS_MAX = 2 ** 31
+
+
+class DinfDistance(tuple):
+    """(horizontal, vertical, surface) of distance_down, float64; vertical and surface are None without heights"""
+    __slots__ = ()
+
+    def __new__(cls, horizontal, vertical, surface):
+        return tuple.__new__(cls, (horizontal, vertical, surface))
+
+    horizontal = property(lambda self: self[0])
+    vertical = property(lambda self: self[1])
+    surface = property(lambda self: self[2])
 
 
 class DinfDirection(tuple):
@@ -161,3 +195,54 @@ def specific_catchment_area(angle, px, weights=None, frac_bits=None):
     acc, w, s, _ = _accumulate(angle, weights, frac_bits)
     own = 1.0 if w is None else np.ldexp(np.rint(np.ldexp(w, s)), -s)
     return np.where(acc == -100.0, -100.0, (acc + own) * p)
+
+
+_STATS = {"ave": 0, "min": 1, "max": 2}
+
+
+def _distance_down(angle, river, px, dem, stat, check_edges, visit_limit):
+    """-> (DinfDistance, info): info = {rounds, reach, dead, unsettled}"""
+    a = _angles_f32(angle)
+    p = _px(px)
+    if not isinstance(stat, str) or stat not in _STATS:
+        raise ValueError("stat must be 'ave', 'min' or 'max', not %r" % (stat,))
+    if isinstance(visit_limit, (bool, np.bool_)) or not isinstance(visit_limit, (int, np.integer)) \
+            or not 0 <= int(visit_limit) < 2 ** 31:
+        raise ValueError("_visit_limit must be an integer >= 0, not %r" % (visit_limit,))
+    r = _raster(river, "river")
+    if r.shape != a.shape:
+        raise ValueError("river has shape %s, the angle raster %s" % (r.shape, a.shape))
+    r = np.ascontiguousarray(r, np.int8)
+    d = None
+    if dem is not None:
+        d = _raster(dem, "dem")
+        if d.shape != a.shape:
+            raise ValueError("dem has shape %s, the angle raster %s" % (d.shape, a.shape))
+        d = _lib.dem_f32(d)
+    H, W = a.shape
+    h = np.empty((H, W), np.float64)
+    v = None if d is None else np.empty((H, W), np.float64)
+    s = None if d is None else np.empty((H, W), np.float64)
+    info = np.zeros(4, np.int64)
+    check(_lib.lib().dt_dinf_distance_down(ptr(a, c_f32p), ptr(r, c_i8p), ptr(d, c_f32p), H, W, p, _STATS[stat],
+                                           1 if check_edges else 0, int(visit_limit), ptr(h, c_f64p), ptr(v, c_f64p),
+                                           ptr(s, c_f64p), ptr(info, c_i64p)))
+    return DinfDistance(h, v, s), dict(zip(("rounds", "reach", "dead", "unsettled"), (int(x) for x in info)))
+
+
+def distance_down(angle, river, px, dem=None, stat="ave", check_edges=True, _visit_limit=0):
+    """Distance from every cell down the D-infinity flow field of `angle` to the targets (river == 1 and not nodata)
+    -> DinfDistance(horizontal, vertical, surface), float64, -100 where a cell does not reach a target and on nodata;
+    vertical and surface are None without `dem` (float32-exact heights, as flow_direction).  stat: 'ave' (weighted by
+    the flow shares), 'min' or 'max' over the two receivers; check_edges=True: a cell any of whose flow leaves the
+    domain or ends without reaching a target does not reach.  The module docstring holds the definition.  Bad
+    arguments raise ValueError before any library call."""
+    return _distance_down(angle, river, px, dem, stat, check_edges, _visit_limit)[0]
+
+
+def hand(angle, river, dem, px, stat="ave", check_edges=True, _visit_limit=0):
+    """D-infinity height above the nearest drainage: distance_down's vertical raster (float64, -100 where a cell does
+    not reach the stream and on nodata) -- what reaches.hydraulic_tables and reaches.inundate take as `hand`."""
+    if dem is None:
+        raise ValueError("hand needs the heights (dem)")
+    return _distance_down(angle, river, px, dem, stat, check_edges, _visit_limit)[0].vertical

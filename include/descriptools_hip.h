@@ -209,6 +209,27 @@ int dt_dinf_direction(const float *dem, const uint8_t *fdr, int64_t H, int64_t W
  * number of cells one round drained, cells queued in all, two-receiver cells}. */
 int dt_dinf_accumulate(const float *angle, const double *w, int64_t H, int64_t W, int frac_bits, double *acc,
                        int64_t *info4);
+/* Net-new: D-infinity distance down to the stream (TauDEM's DinfDistDown as we read it; descriptools_amd/dinf.py and
+ * the test suite's numpy reference are the definition).  angle is decoded as in dt_dinf_accumulate (an angle outside
+ * the contract raises DT_STATUS_BAD_ANGLE and fails the call); a target is a cell with river == 1 whose angle is not
+ * -100; dem (may be NULL) holds float32 heights taken as given.  Measures: horizontal h, vertical v, surface s.  A hop
+ * c -> d at octant k has L = px (k even) or px * 1.4142135623730951, dz = (double)dem[c] - (double)dem[d],
+ * S = sqrt(L * L + dz * dz).  Targets reach with h = v = s = 0; a non-target, non-nodata cell without any edge is dead;
+ * any other cell settles once every receiver it has an edge to is settled: with check_edges = 1 it reaches iff no share
+ * leaves the domain and every receiver reaches, with check_edges = 0 iff at least one receiver reaches; else it is
+ * dead; a cell on a cycle, or above one, never settles.  A reaching cell takes the terms t_j = m(d_j) + hop_m(c -> d_j)
+ * over its reaching receivers in the order j = 0, 1: one term is the value; two give, per measure, stat 0 (ave)
+ * ((double)w0 * t0 + (double)w1 * t1) * 2^-30 with w0 = 2^30 - P2, w1 = P2, stat 1 (min) t1 < t0 ? t1 : t0, stat 2 (max)
+ * t1 > t0 ? t1 : t0.  h, v, s are float64 with -100 on nodata and wherever a cell does not reach; IEEE float64 in this
+ * association, a pure function of the receivers' final values: independent of schedule, rounds and run.  dem, v, s and
+ * info4 may be NULL; v or s without dem is DT_EINVAL.  visit_limit: 0, or n >= 1 caps the sweeps a workgroup makes over
+ * its tile per visit (tests: it forces many rounds on small rasters; the outputs do not depend on it).  info4 = {rounds
+ * that settled something, cells that reach, dead cells, unsettled non-nodata cells}.  The call ends when a round
+ * settles nothing: a cycle costs one empty round.  Rasters of 2^31 cells or more and a px that is not finite and > 0
+ * are refused. */
+int dt_dinf_distance_down(const float *angle, const int8_t *river, const float *dem, int64_t H, int64_t W, double px,
+                          int stat, int check_edges, int visit_limit, double *h, double *v, double *s,
+                          int64_t *info4);
 /* Net-new: exact Euclidean proximity to the river network.  A source is a cell with river == 1 that is not nodata;
  * nodata is a cell with nod <= -100, where nod (may be NULL: no nodata) is any float32 raster of the shape: a float32
  * DEM, or for heights float32 cannot hold the -100 / 0 mask of the DEM's own comparison (descriptools_amd._lib.
