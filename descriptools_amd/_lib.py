@@ -58,6 +58,9 @@ _SIGS = {
     "dt_reach_channels": (ci, [c_u8p, c_i32p, i64, i64, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
     "dt_reach_tables": (ci, [c_i32p, vp, ci, c_f32p, i64, i64, c_f64p, ci, i64, ci, c_i64p, c_i64p, c_i64p]),
     "dt_inundate": (ci, [c_i32p, vp, ci, c_f64p, i64, i64, i64, c_f32p]),
+    "dt_regions_label": (ci, [c_u8p, i64, i64, ci, c_i64p, c_i64p]),
+    "dt_regions_select": (ci, [c_u8p, c_u8p, i64, i64, ci, i64, c_u8p]),
+    "dt_inundate_connected": (ci, [c_i32p, vp, ci, c_f64p, c_i8p, i64, i64, i64, ci, c_f32p]),
     "dt_d8_conditioned_f32": (ci, [c_f32p, i64, i64, f64, c_u8p, c_f32p, c_i32p]),
     "dt_dev_condition_d8": (ci, [vp, vp, i64, i64, f64, vp, vp, c_i32p]),
     "dt_dev_condition_d8_async": (ci, [vp, vp, i64, i64, f64, vp, vp, ci]),
@@ -103,6 +106,9 @@ _SIGS = {
     "dt_dev_reach_channels": (ci, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "dt_dev_reach_tables": (ci, [vp, vp, vp, ci, vp, i64, i64, c_f64p, ci, i64, ci, vp, vp, vp]),
     "dt_dev_inundate": (ci, [vp, vp, vp, ci, vp, i64, i64, i64, vp]),
+    "dt_dev_regions_label": (ci, [vp, vp, i64, i64, ci, vp, vp]),
+    "dt_dev_regions_select": (ci, [vp, vp, vp, i64, i64, ci, i64, vp]),
+    "dt_dev_inundate_connected": (ci, [vp, vp, vp, ci, vp, vp, i64, i64, i64, ci, vp]),
     "dt_dev_river_mask": (ci, [vp, vp, i64, i64, vp]),
     "dt_dev_flowacc_river": (ci, [vp, vp, vp, i64, i64, i64, vp, vp]),
     "dt_dev_gfi_lnhlh": (ci, [vp, vp, vp, vp, i64, f64, f64, f64, vp, vp]),

@@ -769,6 +769,54 @@ extern "C" int dt_dev_inundate(dt_ctx *c, const int32_t *catch_, const void *han
   return d.done(dt_launch_inundate(c->stream, catch_, hand, hand_bytes, stage, H * W, R, depth));
 }
 
+// connected regions: flat indices travel in int32
+static int dt_check_regions(int connectivity, int64_t min_cells) {
+  DT_REQUIRE(connectivity == 4 || connectivity == 8, "connectivity must be 4 or 8");
+  DT_REQUIRE(min_cells >= 1, "min_cells must be >= 1");
+  return DT_OK;
+}
+
+extern "C" int dt_dev_regions_label(dt_ctx *c, const uint8_t *mask, int64_t H, int64_t W, int connectivity,
+                                    int64_t *label, int64_t *size) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_regions(connectivity, 1));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(mask && label, "NULL raster");
+  const size_t need = dt_regions_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_regions(c->stream, mask, nullptr, H, W, connectivity, 1, scr, need, label, size, nullptr));
+}
+
+extern "C" int dt_dev_regions_select(dt_ctx *c, const uint8_t *mask, const uint8_t *seeds, int64_t H, int64_t W,
+                                     int connectivity, int64_t min_cells, uint8_t *keep) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_regions(connectivity, min_cells));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(mask && keep, "NULL raster");
+  const size_t need = dt_regions_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_regions(c->stream, mask, seeds, H, W, connectivity, min_cells, scr, need, nullptr, nullptr,
+                                  keep));
+}
+
+extern "C" int dt_dev_inundate_connected(dt_ctx *c, const int32_t *catch_, const void *hand, int hand_bytes,
+                                         const double *stage, const int8_t *river, int64_t H, int64_t W, int64_t R,
+                                         int connectivity, float *depth) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_reach_count(R));
+  DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
+  DT_TRY(dt_check_regions(connectivity, 1));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(catch_ && hand && river && depth && (stage || R == 0), "NULL raster");
+  const size_t need = dt_inundate_connected_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_inundate_connected(c->stream, catch_, hand, hand_bytes, stage, river, H, W, R, connectivity,
+                                             scr, need, depth));
+}
+
 extern "C" int dt_dev_river_mask(dt_ctx *c, const int32_t *acc32, int64_t N, int64_t threshold,
                                  int8_t *river) {
   DT_DEV(d, c);
@@ -2171,6 +2219,62 @@ extern "C" int dt_inundate(const int32_t *catch_, const void *hand, int hand_byt
   float *d_d = hc.out(depth, n);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_inundate(hc.c, d_c, d_h, hand_bytes, d_s, H, W, R, d_d));
+  return hc.finish();
+}
+
+extern "C" int dt_regions_label(const uint8_t *mask, int64_t H, int64_t W, int connectivity, int64_t *label,
+                                int64_t *size) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_TRY(dt_check_regions(connectivity, 1));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(mask && label, "NULL raster");
+  const uint8_t *d_m = hc.in(mask, n);
+  int64_t *d_l = hc.out(label, n);
+  int64_t *d_s = hc.out(size, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_regions_label(hc.c, d_m, H, W, connectivity, d_l, d_s));
+  return hc.finish();
+}
+
+extern "C" int dt_regions_select(const uint8_t *mask, const uint8_t *seeds, int64_t H, int64_t W, int connectivity,
+                                 int64_t min_cells, uint8_t *keep) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_TRY(dt_check_regions(connectivity, min_cells));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(mask && keep, "NULL raster");
+  const uint8_t *d_m = hc.in(mask, n);
+  const uint8_t *d_s = hc.in(seeds, n);
+  uint8_t *d_k = hc.out(keep, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_regions_select(hc.c, d_m, d_s, H, W, connectivity, min_cells, d_k));
+  return hc.finish();
+}
+
+extern "C" int dt_inundate_connected(const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
+                                     const int8_t *river, int64_t H, int64_t W, int64_t R, int connectivity,
+                                     float *depth) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_TRY(dt_check_reach_count(R));
+  DT_REQUIRE(hand_bytes == 4 || hand_bytes == 8, "hand's element size must be 4 or 8");
+  DT_TRY(dt_check_regions(connectivity, 1));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(catch_ && hand && river && depth && (stage || R == 0), "NULL raster");
+  const int32_t *d_c = hc.in(catch_, n);
+  const unsigned char *d_h = hc.in((const unsigned char *)hand, n * (size_t)hand_bytes);
+  const double *d_s = hc.in(stage, (size_t)R);
+  const int8_t *d_r = hc.in(river, n);
+  float *d_d = hc.out(depth, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_inundate_connected(hc.c, d_c, d_h, hand_bytes, d_s, d_r, H, W, R, connectivity, d_d));
   return hc.finish();
 }
 

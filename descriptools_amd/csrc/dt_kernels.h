@@ -303,3 +303,18 @@ const uint32_t *dt_dinf_distance_ctl(void *scratch, int64_t H, int64_t W);
 size_t dt_proximity_scratch(int64_t H, int64_t W);
 int dt_launch_proximity(hipStream_t s, const int8_t *river, const float *nod, int64_t H, int64_t W, double px,
                         void *scratch, size_t scratch_bytes, float *distance, int64_t *indices);
+
+// Connected regions (dt_regions.hip; regions.py holds the definition): label = the smallest flat index of the cell's
+// region of mask != 0 under connectivity 4 or 8 (-100 on background), size = its cell count (0 on background), keep =
+// foreground, seeded (seeds NULL: every region is) and size >= min_cells.  label, size and keep may each be NULL (seeds
+// count only with keep).  dt_launch_inundate_connected: dt_launch_inundate's depth, 0 on the wet cells whose wet region
+// holds no wet cell with river == 1.  The union-find plane, the counts and the masks live in `scratch`; 3 to 5 launches
+// whatever the rasters hold; nothing synchronises.  H * W < 2^31.
+size_t dt_regions_scratch(int64_t H, int64_t W);
+size_t dt_inundate_connected_scratch(int64_t H, int64_t W);
+int dt_launch_regions(hipStream_t s, const uint8_t *mask, const uint8_t *seeds, int64_t H, int64_t W, int connectivity,
+                      int64_t min_cells, void *scratch, size_t scratch_bytes, int64_t *label, int64_t *size,
+                      uint8_t *keep);
+int dt_launch_inundate_connected(hipStream_t s, const int32_t *catch_, const void *hand, int hand_bytes,
+                                 const double *stage, const int8_t *river, int64_t H, int64_t W, int64_t R,
+                                 int connectivity, void *scratch, size_t scratch_bytes, float *depth);

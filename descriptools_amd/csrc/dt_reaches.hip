@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "dt_kernels.h"
+#include "dt_reach_wet.h"
 
 #define RC_TW 64
 #define RC_TH 64
@@ -490,14 +491,11 @@ int dt_launch_reach_tables(hipStream_t s, const int32_t *catch_, const void *han
 }
 
 // ---- inundation ------------------------------------------------------------------------------------------------------
+// (the predicate and the depth: dt_reach_wet.h, shared with connected inundation in dt_regions.hip)
 template <typename HT>
 __device__ __forceinline__ float rc_depth(int32_t r, HT hv, const double *__restrict__ stage, int64_t R) {
-  const double h = (double)hv;
-  if (h == -100.0) return DT_NODATA;
-  if (r < 0 || r >= R) return 0.f;
-  const double st = __ldg(&stage[r]);
-  if (!(fabs(st) <= 1.7976931348623157e308)) return 0.f;  // NaN or infinite
-  return (h >= 0.0 && h <= st) ? (float)(st - h) : 0.f;
+  bool wet;
+  return dt_rc_depth(r, hv, stage, R, wet);
 }
 
 template <typename HT, bool VEC>

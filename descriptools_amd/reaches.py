@@ -34,6 +34,10 @@ row-major, flat index y * W + x, N = H * W < 2^31.
   slope raster); every sum then converts to float64 exactly.  The default is the finest such s.
 * Inundation.  depth[c] (float32) = -100 where hand[c] == -100; else float32(stage[r] - float64(hand[c])) when
   catchment[c] = r in range, stage[r] is finite and 0 <= hand[c] <= stage[r]; else 0.
+* Connected inundation.  A cell is wet exactly when it gets the value of inundation's third clause (catchment in range,
+  stage finite, 0 <= hand <= stage: a cell with hand == stage is wet with depth 0).  The seeds are the wet cells with
+  river == 1 (river as int8, as flowhand.flow_hand_index takes it).  depth[c] is inundation's value, except that a wet
+  cell whose wet region (regions.py, connectivity 8 or 4) holds no seed gets 0; cells with hand == -100 keep -100.
 * Rating curves (numpy on the R x K tables).  With channel length L, bed slope S0 and Manning's n per reach (scalars
   broadcast): A = volume / L, Rh = volume / bed_area, Q = A * Rh**(2/3) * sqrt(S0) / n; 0 where cells == 0; NaN where
   L == 0, S0 is not > 0 or n is not > 0.
@@ -48,7 +52,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import c_f32p, c_f64p, c_i32p, c_i64p, c_u8p, check, ptr, raster_2d
+from ._lib import c_f32p, c_f64p, c_i8p, c_i32p, c_i64p, c_u8p, check, ptr, raster_2d
 from .flowacc import _FRAC_BITS_MAX, _SUM_BITS, _default_frac_bits
 
 Catchments = namedtuple("Catchments", ["reach", "catchment", "heads"])
@@ -294,4 +298,26 @@ def inundate(catchment, hand, stage):
     depth = np.empty((H, W), np.float32)
     check(_lib.lib().dt_inundate(ptr(cat, c_i32p), h.ctypes.data_as(C.c_void_p), hb, ptr(sg, c_f64p), H, W, sg.size,
                                  ptr(depth, c_f32p)))
+    return depth
+
+
+def inundate_connected(catchment, hand, stage, river, connectivity=8):
+    """inundate kept to the wet regions that hold a river cell: the depth (float32 raster) of inundate, 0 on the wet
+    cells without a wet path (under `connectivity`, 8 or 4) to a wet cell with river == 1; see the module docstring."""
+    cat = _ids32(catchment, "catchment")
+    h, hb = _hand(hand, cat.shape)
+    try:
+        sg = np.ascontiguousarray(stage, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("stage must be a 1-D array of numbers") from None
+    if sg.ndim != 1 or sg.size >= 2 ** 31:
+        raise ValueError("stage must be a 1-D array with one value per reach, not of shape %s" % (sg.shape,))
+    rv = _raster(river, "river", cat.shape, kinds="biu", dtype=np.int8)
+    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) \
+            or int(connectivity) not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8, not %r" % (connectivity,))
+    H, W = cat.shape
+    depth = np.empty((H, W), np.float32)
+    check(_lib.lib().dt_inundate_connected(ptr(cat, c_i32p), h.ctypes.data_as(C.c_void_p), hb, ptr(sg, c_f64p),
+                                           ptr(rv, c_i8p), H, W, sg.size, int(connectivity), ptr(depth, c_f32p)))
     return depth

@@ -275,6 +275,25 @@ int dt_reach_tables(const int32_t *catch_, const void *hand, int hand_bytes, con
  * catch[c] = r with 0 <= r < R, stage[r] (float64[R]) is finite and 0 <= hand[c] <= stage[r]; else 0. */
 int dt_inundate(const int32_t *catch_, const void *hand, int hand_bytes, const double *stage, int64_t H, int64_t W,
                 int64_t R, float *depth);
+/* Net-new: connected regions of a mask.  mask (and seeds) are uint8 rasters, foreground = non-zero; connectivity is 8
+ * (the eight neighbours) or 4 (the cardinal ones); two foreground cells are in one region when a chain of adjacent
+ * foreground cells joins them.  H * W < 2^31.
+ *   label (int64): the smallest flat index y * W + x among the cells of the cell's region; -100 on background.
+ *   size  (int64, may be NULL): the number of cells of the cell's region; 0 on background.
+ *   keep  (uint8): 1 when the cell is foreground, seeds is NULL or one of its region's own cells has seeds != 0 (a seed
+ *          on background seeds nothing), and size >= min_cells (>= 1); else 0.
+ * All are functions of the inputs alone, identical in every bit from run to run.  The kernels work on tiles of
+ * DT_REGIONS_TILE x DT_REGIONS_TILE cells.  A connectivity other than 4 or 8 and min_cells < 1 are DT_EINVAL. */
+#define DT_REGIONS_TILE 64
+int dt_regions_label(const uint8_t *mask, int64_t H, int64_t W, int connectivity, int64_t *label, int64_t *size);
+int dt_regions_select(const uint8_t *mask, const uint8_t *seeds, int64_t H, int64_t W, int connectivity,
+                      int64_t min_cells, uint8_t *keep);
+/* dt_inundate kept to the wet regions that touch the channel.  A cell is wet exactly when dt_inundate gives it the value
+ * of its third clause (catch in range, stage finite, 0 <= hand <= stage: a cell with hand == stage is wet at depth 0);
+ * the seeds are the wet cells with river == 1.  depth = dt_inundate's value, except 0 on a wet cell whose wet region
+ * (under `connectivity`) holds no seed; cells with hand == -100 keep -100. */
+int dt_inundate_connected(const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
+                          const int8_t *river, int64_t H, int64_t W, int64_t R, int connectivity, float *depth);
 
 /* flowhand.flow_distance_index_cpu + flow_distance_index_gpu (flowhand.py:476-846, untiled
  * call: out = 0, row_start = col_start = 0, matrix_columns = W) and flowhand.hand_calculator
@@ -444,6 +463,16 @@ int dt_dev_reach_tables(dt_ctx *ctx, const int32_t *catch_, const void *hand, in
                         int64_t *Hq, int64_t *Bq);
 int dt_dev_inundate(dt_ctx *ctx, const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
                     int64_t H, int64_t W, int64_t R, float *depth);
+/* dt_regions_label, dt_regions_select and dt_inundate_connected on device rasters (rows x cols = H x W), on the
+ * context's stream: three to five launches whatever the rasters hold, none synchronises.  The workspace (12 bytes per
+ * cell, 14 for the inundation) is the context's scratch; nothing is kept between calls.  size and seeds may be NULL. */
+int dt_dev_regions_label(dt_ctx *ctx, const uint8_t *mask, int64_t rows, int64_t cols, int connectivity,
+                         int64_t *label, int64_t *size);
+int dt_dev_regions_select(dt_ctx *ctx, const uint8_t *mask, const uint8_t *seeds, int64_t rows, int64_t cols,
+                          int connectivity, int64_t min_cells, uint8_t *keep);
+int dt_dev_inundate_connected(dt_ctx *ctx, const int32_t *catch_, const void *hand, int hand_bytes,
+                              const double *stage, const int8_t *river, int64_t rows, int64_t cols, int64_t R,
+                              int connectivity, float *depth);
 /* flow accumulation with the river mask (acc > threshold, Example/example.py:52) written by the
  * same final pass */
 int dt_dev_flowacc_river(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
