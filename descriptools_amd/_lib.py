@@ -277,14 +277,6 @@ def as_c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def raster_2d(fdr):
-    """fdr as an array; ValueError unless it is a 2-D raster"""
-    f = np.asarray(fdr)
-    if f.ndim != 2:
-        raise ValueError("fdr must be a 2-D raster, not of shape %s" % (f.shape,))
-    return f
-
-
 def nodata_mask(dem, shape):
     """The float32 nodata mask the flow ops take from a DEM (-100 where dem <= -100, 0 elsewhere, compared in the
     DEM's own dtype: NaN is not nodata), or None for dem None; ValueError when dem is not of the direction raster's

@@ -62,12 +62,11 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 from ._lib import c_f32p, c_f64p, c_i8p, c_i64p, c_u8p, check, ptr
-from .flowacc import _FRAC_BITS_MAX, _SUM_BITS, _default_frac_bits, _weights_f64
+from .flowacc import _weights_f64
 
 F2PI = np.float32(2.0 * math.pi)
-_CELLS_MAX = 2 ** 31
 
 
 class DinfDistance(tuple):
@@ -93,25 +92,6 @@ class DinfDirection(tuple):
     slope = property(lambda self: self[1])
 
 
-def _raster(a, what):
-    a = np.asarray(a)
-    if a.ndim != 2:
-        raise ValueError("%s must be a 2-D raster, not of shape %s" % (what, a.shape))
-    if a.size >= _CELLS_MAX:
-        raise ValueError("%s has %d cells: rasters of 2^31 cells or more are not supported" % (what, a.size))
-    return a
-
-
-def _px(px):
-    try:
-        p = float(px)
-    except (TypeError, ValueError):
-        raise ValueError("px must be a number, not %r" % (px,))
-    if not (math.isfinite(p) and p > 0.0):
-        raise ValueError("px must be finite and > 0, not %r" % (px,))
-    return p
-
-
 def flow_direction(dem, px, fdr=None):
     """D-infinity angle and slope of `dem` (float32-exact heights; a DEM that float32 cannot hold raises ValueError, as
     flowdir.d8 does by default) -> DinfDirection(angle float32, slope float32); the module docstring holds the
@@ -119,14 +99,9 @@ def flow_direction(dem, px, fdr=None):
 
     With flowdir.d8_conditioned pass the FILLED surface (return_filled=True) together with its fdr: then every flow is
     to a lower cell or along the conditioned D8 codes, and the drainage graph has no cycle."""
-    d = _raster(dem, "dem")
-    p = _px(px)
-    f = None
-    if fdr is not None:
-        f = np.asarray(fdr)
-        if f.shape != d.shape:
-            raise ValueError("fdr has shape %s, the DEM %s" % (f.shape, d.shape))
-        f = np.ascontiguousarray(f, np.uint8)
+    d = _args.raster(dem, "dem")
+    p = _args.pixel_size(px)
+    f = None if fdr is None else _args.raster(fdr, "fdr", d.shape, "the DEM", dtype=np.uint8)
     d = _lib.dem_f32(d)
     H, W = d.shape
     angle = np.empty((H, W), np.float32)
@@ -136,33 +111,13 @@ def flow_direction(dem, px, fdr=None):
 
 
 def _angles_f32(angle):
-    a = _raster(angle, "angle")
-    if a.dtype.kind not in "iuf":
-        raise ValueError("angle must be of a real dtype, not %s" % a.dtype)
-    a = np.ascontiguousarray(a, dtype=np.float32)
+    a = _args.raster(angle, "angle", kinds="iuf", dtype=np.float32)
     ok = (a == np.float32(-1)) | (a == np.float32(-100)) | ((a >= 0) & (a <= F2PI))
     if not ok.all():
         k = int(np.argmin(ok.reshape(-1)))
         raise ValueError("angle %r at flat index %d is neither -1 (no flow), -100 (nodata) nor in [0, float32(2 pi)]"
                          % (a.reshape(-1)[k].item(), k))
     return a
-
-
-def _frac_bits(n, wmax, frac_bits):
-    """flowacc.accumulate_weighted's rule for the fixed-point scale"""
-    if frac_bits is None:
-        return _default_frac_bits(n, wmax) if n else 0
-    if isinstance(frac_bits, (bool, np.bool_)) or not isinstance(frac_bits, (int, np.integer)):
-        raise ValueError("frac_bits must be an integer, not %r" % (frac_bits,))
-    s = int(frac_bits)
-    if not -_FRAC_BITS_MAX <= s <= _FRAC_BITS_MAX:
-        raise ValueError("frac_bits must lie in [%d, %d], not %d" % (-_FRAC_BITS_MAX, _FRAC_BITS_MAX, s))
-    with np.errstate(over="ignore"):
-        qmax = np.rint(np.ldexp(wmax, s))
-    if not np.isfinite(qmax) or n * int(qmax) > 2 ** _SUM_BITS:
-        raise ValueError("frac_bits=%d is too fine for these weights: N * rint(max(weights) * 2^frac_bits) "
-                         "exceeds 2^52 (the default is %d)" % (s, _default_frac_bits(n, wmax)))
-    return s
 
 
 def _accumulate(angle, weights, frac_bits):
@@ -172,7 +127,8 @@ def _accumulate(angle, weights, frac_bits):
     n = H * W
     w = None if weights is None else _weights_f64(weights, a.shape)
     wmax = 1.0 if w is None else (float(w.max()) if n else 0.0)
-    s = _frac_bits(n, wmax, frac_bits)
+    s = _args.frac_bits(n, wmax, frac_bits, " for these weights: N * rint(max(weights) * 2^frac_bits)",
+                        "the default is")
     acc = np.empty((H, W), np.float64)
     info = np.zeros(4, np.int64)
     check(_lib.lib().dt_dinf_accumulate(ptr(a, c_f32p), ptr(w, c_f64p), H, W, s, ptr(acc, c_f64p), ptr(info, c_i64p)))
@@ -191,7 +147,7 @@ def accumulate(angle, weights=None, frac_bits=None):
 def specific_catchment_area(angle, px, weights=None, frac_bits=None):
     """(accumulate(angle, weights, frac_bits) + the cell's own (quantised) weight) * px: contributing area per unit
     contour length with the cell itself included, TauDEM's `sca` for unit weights; -100 where accumulate gives -100."""
-    p = _px(px)
+    p = _args.pixel_size(px)
     acc, w, s, _ = _accumulate(angle, weights, frac_bits)
     own = 1.0 if w is None else np.ldexp(np.rint(np.ldexp(w, s)), -s)
     return np.where(acc == -100.0, -100.0, (acc + own) * p)
@@ -203,29 +159,19 @@ _STATS = {"ave": 0, "min": 1, "max": 2}
 def _distance_down(angle, river, px, dem, stat, check_edges, visit_limit):
     """-> (DinfDistance, info): info = {rounds, reach, dead, unsettled}"""
     a = _angles_f32(angle)
-    p = _px(px)
+    p = _args.pixel_size(px)
     if not isinstance(stat, str) or stat not in _STATS:
         raise ValueError("stat must be 'ave', 'min' or 'max', not %r" % (stat,))
-    if isinstance(visit_limit, (bool, np.bool_)) or not isinstance(visit_limit, (int, np.integer)) \
-            or not 0 <= int(visit_limit) < 2 ** 31:
-        raise ValueError("_visit_limit must be an integer >= 0, not %r" % (visit_limit,))
-    r = _raster(river, "river")
-    if r.shape != a.shape:
-        raise ValueError("river has shape %s, the angle raster %s" % (r.shape, a.shape))
-    r = np.ascontiguousarray(r, np.int8)
-    d = None
-    if dem is not None:
-        d = _raster(dem, "dem")
-        if d.shape != a.shape:
-            raise ValueError("dem has shape %s, the angle raster %s" % (d.shape, a.shape))
-        d = _lib.dem_f32(d)
+    limit = _args.integer(visit_limit, "_visit_limit", 0, 2 ** 31 - 1)
+    r = _args.raster(river, "river", a.shape, "the angle raster", dtype=np.int8)
+    d = None if dem is None else _lib.dem_f32(_args.raster(dem, "dem", a.shape, "the angle raster"))
     H, W = a.shape
     h = np.empty((H, W), np.float64)
     v = None if d is None else np.empty((H, W), np.float64)
     s = None if d is None else np.empty((H, W), np.float64)
     info = np.zeros(4, np.int64)
     check(_lib.lib().dt_dinf_distance_down(ptr(a, c_f32p), ptr(r, c_i8p), ptr(d, c_f32p), H, W, p, _STATS[stat],
-                                           1 if check_edges else 0, int(visit_limit), ptr(h, c_f64p), ptr(v, c_f64p),
+                                           1 if check_edges else 0, limit, ptr(h, c_f64p), ptr(v, c_f64p),
                                            ptr(s, c_f64p), ptr(info, c_i64p)))
     return DinfDistance(h, v, s), dict(zip(("rounds", "reach", "dead", "unsettled"), (int(x) for x in info)))
 

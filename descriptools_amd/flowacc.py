@@ -3,24 +3,15 @@ convention of the bundled 12_fac.tif; int64 like the `fac` the reference's calle
 
 accumulate_weighted sums a weight raster down the same D8 tree instead of counting cells (runoff or rainfall depth,
 per-cell area, a load), in int64 fixed point so that the result is exact and deterministic."""
-import math
-
 import numpy as np
 
-from . import _lib
-from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, nodata_mask, ptr, raster_2d
-
-# every partial sum of quantised weights stays <= 2^52: the countdown's sum field holds it and float64 converts it
-# without rounding
-_SUM_BITS = 52
-# frac_bits is bounded as the C ABI bounds it (dt_dev_flowacc_weighted)
-_FRAC_BITS_MAX = 2200
+from . import _args, _lib
+from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, nodata_mask, ptr
 
 
 def accumulate(fdr, dem=None):
-    f = raster_2d(fdr)
-    d = nodata_mask(dem, f.shape)  # the DEM is only a nodata mask here
-    fdr = np.ascontiguousarray(f, np.uint8)
+    fdr = _args.raster(fdr, "fdr", cap=False, dtype=np.uint8)  # the size limit is the library's (dt_check_hw)
+    d = nodata_mask(dem, fdr.shape)  # the DEM is only a nodata mask here
     H, W = fdr.shape
     acc = np.empty((H, W), np.int64)
     check(_lib.lib().dt_flowacc_u8(ptr(fdr, c_u8p), ptr(d, c_f32p), H, W, ptr(acc, c_i64p)))
@@ -51,14 +42,6 @@ def _weights_f64(weights, shape=None):
     return d
 
 
-def _default_frac_bits(n, wmax):
-    """s = 51 - ceil(log2 n) - e with 2^e <= wmax < 2^(e+1); 0 when every weight is 0"""
-    if wmax == 0:
-        return 0
-    e = math.frexp(wmax)[1] - 1
-    return _SUM_BITS - 1 - (n - 1).bit_length() - e
-
-
 def weight_frac_bits(weights):
     """The fixed-point scale accumulate_weighted uses by default: the largest s for which every partial sum of the
     quantised weights rint(w * 2^s) over the raster's N cells stays <= 2^52,
@@ -70,7 +53,7 @@ def weight_frac_bits(weights):
     d = _weights_f64(weights)
     if d.size == 0:
         return 0
-    return _default_frac_bits(d.size, float(d.max()))
+    return _args._default_frac_bits(d.size, float(d.max()))
 
 
 def accumulate_weighted(fdr, weights, dem=None, frac_bits=None):
@@ -87,27 +70,14 @@ def accumulate_weighted(fdr, weights, dem=None, frac_bits=None):
     cycle.  Nodata cells still pass their weight and their inflow downstream, as they pass their count in
     accumulate; give them weight 0 to leave them out.  Weights must be finite and >= 0, of any real or integer dtype
     (integers <= 2^53).  Bad arguments raise ValueError before any library call."""
-    f = raster_2d(fdr)
+    f = _args.raster(fdr, "fdr", cap=False, dtype=np.uint8)
     H, W = f.shape
     w = _weights_f64(weights, f.shape)
     d = nodata_mask(dem, f.shape)
     n = H * W
-    wmax = float(w.max()) if n else 0.0
-    if frac_bits is None:
-        s = _default_frac_bits(n, wmax) if n else 0
-    else:
-        if isinstance(frac_bits, (bool, np.bool_)) or not isinstance(frac_bits, (int, np.integer)):
-            raise ValueError("frac_bits must be an integer, not %r" % (frac_bits,))
-        s = int(frac_bits)
-        if not -_FRAC_BITS_MAX <= s <= _FRAC_BITS_MAX:
-            raise ValueError("frac_bits must lie in [%d, %d], not %d" % (-_FRAC_BITS_MAX, _FRAC_BITS_MAX, s))
-        with np.errstate(over="ignore"):
-            qmax = np.rint(np.ldexp(wmax, s))
-        if not np.isfinite(qmax) or n * int(qmax) > 2 ** _SUM_BITS:
-            raise ValueError("frac_bits=%d is too fine for these weights: N * rint(max(weights) * 2^frac_bits) "
-                             "exceeds 2^52 (weight_frac_bits gives %d)" % (s, _default_frac_bits(n, wmax)))
-    fdr8 = np.ascontiguousarray(f, np.uint8)
+    s = _args.frac_bits(n, float(w.max()) if n else 0.0, frac_bits,
+                        " for these weights: N * rint(max(weights) * 2^frac_bits)", "weight_frac_bits gives")
     acc = np.empty((H, W), np.float64)
-    check(_lib.lib().dt_flowacc_weighted(ptr(fdr8, c_u8p), ptr(d, c_f32p), ptr(w, c_f64p), H, W, s,
+    check(_lib.lib().dt_flowacc_weighted(ptr(f, c_u8p), ptr(d, c_f32p), ptr(w, c_f64p), H, W, s,
                                          ptr(acc, c_f64p)))
     return acc

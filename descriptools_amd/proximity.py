@@ -30,10 +30,9 @@ euclidean_hand's indices are the documented way to the Euclidean variants of eve
 gfi.gfi_calculator(hand, fac, indices, ...), gfi.river_accumulation(fac, indices), reaches.catchments(link, indices)."""
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 from ._lib import c_f32p, c_i8p, c_i64p, check, ptr
 from .device import host_empty
-from .dinf import _px, _raster
 from .flowhand import hand_calculator
 
 
@@ -51,8 +50,8 @@ class Proximity(tuple):
 def nearest_river(river, px, dem=None):
     """Euclidean distance to, and flat index of, the nearest river cell -> Proximity(distance float32, indices int64);
     the module docstring holds the definition.  `dem` (optional) only says which cells are nodata."""
-    r = _raster(river, "river")
-    p = _px(px)
+    r = _args.raster(river, "river")
+    p = _args.pixel_size(px)
     if dem is not None and np.shape(dem) != r.shape:
         raise ValueError("dem has shape %s, river %s" % (np.shape(dem), r.shape))
     nod = None

@@ -51,73 +51,49 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
-from ._lib import c_f32p, c_f64p, c_i8p, c_i32p, c_i64p, c_u8p, check, ptr, raster_2d
-from .flowacc import _FRAC_BITS_MAX, _SUM_BITS, _default_frac_bits
+from . import _args, _lib
+from ._lib import c_f32p, c_f64p, c_i8p, c_i32p, c_i64p, c_u8p, check, ptr
 
 Catchments = namedtuple("Catchments", ["reach", "catchment", "heads"])
 Channels = namedtuple("Channels", ["end", "down", "n_cells", "n_card", "n_diag", "length"])
 HydraulicTables = namedtuple("HydraulicTables", ["stages", "cells", "area", "volume", "bed_area", "frac_bits"])
 
-_MAX_CELLS = 2 ** 31
 _MAX_STAGES = 1024
 _HEADS_CAP = 1 << 20  # heads asked for in the first call; a network with more links takes a second, lighter call
 
 
-def _raster(a, what, shape=None, kinds="iu", dtype=None):
-    """a as a C-contiguous 2-D raster of `dtype`; ValueError for another rank, shape, kind of dtype or 2^31 cells"""
-    r = np.asarray(a)
-    if r.ndim != 2:
-        raise ValueError("%s must be a 2-D raster, not of shape %s" % (what, r.shape))
-    if shape is not None and r.shape != shape:
-        raise ValueError("%s has shape %s, expected %s" % (what, r.shape, shape))
-    if r.size >= _MAX_CELLS:
-        raise ValueError("the raster has %d cells; it must have fewer than 2^31" % r.size)
-    if r.dtype.kind not in kinds:
-        raise ValueError("%s must be of %s dtype, not %s"
-                         % (what, "an integer" if kinds == "iu" else "a real or integer", r.dtype))
-    return r if dtype is None else np.ascontiguousarray(r, dtype)
-
-
-def _ids(a, what, shape=None):
+def _ids(a, what, shape=None, other=None):
     """an id / index raster (reach, catchment, link, indices) as int64 or int32 without wrapping"""
-    r = _raster(a, what, shape)
+    r = _args.raster(a, what, shape, other, kinds="iu")
     if r.dtype.kind == "u" and r.size and int(r.max()) > np.iinfo(np.int64).max:
         raise ValueError("%s holds values beyond int64" % what)
     return r
 
 
-def _ids32(a, what, shape=None):
-    r = _ids(a, what, shape)
+def _ids32(a, what, shape=None, other=None):
+    r = _ids(a, what, shape, other)
     if r.dtype != np.int32 and r.size and (int(r.max()) >= 2 ** 31 or int(r.min()) < -2 ** 31):
         raise ValueError("%s holds values that do not fit int32" % what)
     return np.ascontiguousarray(r, np.int32)
 
 
-def _px(px):
-    if isinstance(px, (bool, np.bool_)):
-        raise ValueError("px must be a finite number > 0, not %r" % (px,))
-    try:
-        p = float(px)
-    except (TypeError, ValueError):
-        raise ValueError("px must be a finite number > 0, not %r" % (px,)) from None
-    if not (math.isfinite(p) and p > 0):
-        raise ValueError("px must be a finite number > 0, not %r" % (px,))
-    return p
-
-
-def _n_reaches(n):
-    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) < 2 ** 31:
-        raise ValueError("n_reaches must be an integer in [0, 2^31), not %r" % (n,))
-    return int(n)
-
-
 def _hand(hand, shape):
     """(array, element size): float32 and float64 as they are, anything else real or integer as float64"""
-    h = _raster(hand, "hand", shape, kinds="biuf")
+    h = _args.raster(hand, "hand", shape, "the catchment raster", kinds="biuf")
     if h.dtype == np.float32:
         return np.ascontiguousarray(h), 4
     return np.ascontiguousarray(h, np.float64), 8
+
+
+def _stage(stage):
+    """the stage per reach as C-contiguous float64[R]"""
+    try:
+        sg = np.ascontiguousarray(stage, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("stage must be a 1-D array of numbers") from None
+    if sg.ndim != 1 or sg.size >= 2 ** 31:
+        raise ValueError("stage must be a 1-D array with one value per reach, not of shape %s" % (sg.shape,))
+    return sg
 
 
 def _stages(stages):
@@ -151,7 +127,7 @@ def catchments(link, indices):
     """Catchments(reach, catchment, heads) of the link raster of streams.stream_network and the river index of
     flowhand.flow_hand_index: reach and catchment int32 rasters, heads int64[R] (see the module docstring)."""
     lk = _ids(link, "link")
-    ix = _ids(indices, "indices", lk.shape)
+    ix = _ids(indices, "indices", lk.shape, "the link raster")
     lk = np.ascontiguousarray(lk, np.int64)
     ix = np.ascontiguousarray(ix, np.int64)
     H, W = lk.shape
@@ -174,11 +150,10 @@ def catchments(link, indices):
 def channels(fdr, reach, px, n_reaches):
     """Channels(end, down, n_cells, n_card, n_diag, length) of every reach: int64[R] each, length float64[R] (see the
     module docstring)."""
-    f = raster_2d(fdr)
-    rc = _ids32(reach, "reach", f.shape)
-    p = _px(px)
-    R = _n_reaches(n_reaches)
-    f = np.ascontiguousarray(f, np.uint8)
+    f = _args.raster(fdr, "fdr", dtype=np.uint8)
+    rc = _ids32(reach, "reach", f.shape, "the direction raster")
+    p = _args.pixel_size(px)
+    R = _args.integer(n_reaches, "n_reaches", 0, 2 ** 31 - 1)
     H, W = f.shape
     out = [np.empty(R, np.int64) for _ in range(5)]
     check(_lib.lib().dt_reach_channels(ptr(f, c_u8p), ptr(rc, c_i32p), H, W, R, *[ptr(o, c_i64p) for o in out]))
@@ -193,30 +168,18 @@ def hydraulic_tables(catchment, hand, px, stages, n_reaches, slope=None, frac_bi
     bed area (float64[R, K]); see the module docstring.  slope: float32 percent (slope.sloper), optional."""
     cat = _ids32(catchment, "catchment")
     h, hb = _hand(hand, cat.shape)
-    p = _px(px)
+    p = _args.pixel_size(px)
     st = _stages(stages)
-    R = _n_reaches(n_reaches)
+    R = _args.integer(n_reaches, "n_reaches", 0, 2 ** 31 - 1)
     sl = None
     wmax = 1.0
     if slope is not None:
-        sl = _raster(slope, "slope", cat.shape, kinds="biuf", dtype=np.float32)
+        sl = _args.raster(slope, "slope", cat.shape, "the catchment raster", kinds="biuf", dtype=np.float32)
         wmax = bed_weight_max(sl)
     H, W = cat.shape
     n = H * W
-    top = max(float(st[-1]), wmax)
-    if frac_bits is None:
-        s = _default_frac_bits(n, top) if n else 0
-    else:
-        if isinstance(frac_bits, (bool, np.bool_)) or not isinstance(frac_bits, (int, np.integer)):
-            raise ValueError("frac_bits must be an integer, not %r" % (frac_bits,))
-        s = int(frac_bits)
-        if not -_FRAC_BITS_MAX <= s <= _FRAC_BITS_MAX:
-            raise ValueError("frac_bits must lie in [%d, %d], not %d" % (-_FRAC_BITS_MAX, _FRAC_BITS_MAX, s))
-        with np.errstate(over="ignore"):
-            qmax = np.rint(np.ldexp(top, s))
-        if not np.isfinite(qmax) or n * int(qmax) > 2 ** _SUM_BITS:
-            raise ValueError("frac_bits=%d is too fine: N * rint(max(stages[K-1], wmax) * 2^frac_bits) exceeds 2^52 "
-                             "(the default is %d)" % (s, _default_frac_bits(n, top)))
+    s = _args.frac_bits(n, max(float(st[-1]), wmax), frac_bits,
+                        ": N * rint(max(stages[K-1], wmax) * 2^frac_bits)", "the default is")
     K = st.size
     cells = np.zeros((R, K), np.int64)
     hq = np.zeros((R, K), np.int64)
@@ -288,12 +251,7 @@ def inundate(catchment, hand, stage):
     """Inundation depth (float32 raster) for a stage per reach (float64[R]); see the module docstring."""
     cat = _ids32(catchment, "catchment")
     h, hb = _hand(hand, cat.shape)
-    try:
-        sg = np.ascontiguousarray(stage, np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("stage must be a 1-D array of numbers") from None
-    if sg.ndim != 1 or sg.size >= 2 ** 31:
-        raise ValueError("stage must be a 1-D array with one value per reach, not of shape %s" % (sg.shape,))
+    sg = _stage(stage)
     H, W = cat.shape
     depth = np.empty((H, W), np.float32)
     check(_lib.lib().dt_inundate(ptr(cat, c_i32p), h.ctypes.data_as(C.c_void_p), hb, ptr(sg, c_f64p), H, W, sg.size,
@@ -306,18 +264,11 @@ def inundate_connected(catchment, hand, stage, river, connectivity=8):
     cells without a wet path (under `connectivity`, 8 or 4) to a wet cell with river == 1; see the module docstring."""
     cat = _ids32(catchment, "catchment")
     h, hb = _hand(hand, cat.shape)
-    try:
-        sg = np.ascontiguousarray(stage, np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("stage must be a 1-D array of numbers") from None
-    if sg.ndim != 1 or sg.size >= 2 ** 31:
-        raise ValueError("stage must be a 1-D array with one value per reach, not of shape %s" % (sg.shape,))
-    rv = _raster(river, "river", cat.shape, kinds="biu", dtype=np.int8)
-    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) \
-            or int(connectivity) not in (4, 8):
-        raise ValueError("connectivity must be 4 or 8, not %r" % (connectivity,))
+    sg = _stage(stage)
+    rv = _args.raster(river, "river", cat.shape, "the catchment raster", kinds="biu", dtype=np.int8)
+    cn = _args.connectivity(connectivity)
     H, W = cat.shape
     depth = np.empty((H, W), np.float32)
     check(_lib.lib().dt_inundate_connected(ptr(cat, c_i32p), h.ctypes.data_as(C.c_void_p), hb, ptr(sg, c_f64p),
-                                           ptr(rv, c_i8p), H, W, sg.size, int(connectivity), ptr(depth, c_f32p)))
+                                           ptr(rv, c_i8p), H, W, sg.size, cn, ptr(depth, c_f32p)))
     return depth

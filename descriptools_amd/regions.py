@@ -24,50 +24,31 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 from ._lib import c_i64p, c_u8p, check, ptr
 from .device import host_empty
 
 Regions = namedtuple("Regions", ["label", "size"])
 
 TILE = 64  # DT_REGIONS_TILE: the edge of the tiles the kernels solve in LDS (tests place cells on their seams)
-_MAX_CELLS = 2 ** 31
 
 
 def _mask(a, what, shape=None):
     """a as uint8(a != 0), C-contiguous; ValueError unless it is a 2-D bool / integer raster of fewer than 2^31 cells
-    (and of `shape`)"""
-    m = np.asarray(a)
-    if m.ndim != 2:
-        raise ValueError("%s must be a 2-D raster, not of shape %s" % (what, m.shape))
-    if shape is not None and m.shape != shape:
-        raise ValueError("%s has shape %s, the mask %s" % (what, m.shape, shape))
-    if m.dtype.kind not in "biu":
-        raise ValueError("%s must be of bool or integer dtype, not %s (compare first: river == 1, depth > 0)"
-                         % (what, m.dtype))
-    if m.size >= _MAX_CELLS:
-        raise ValueError("the raster has %d cells; it must have fewer than 2^31" % m.size)
-    return np.ascontiguousarray(m != 0, np.uint8)
-
-
-def _connectivity(connectivity):
-    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) \
-            or int(connectivity) not in (4, 8):
-        raise ValueError("connectivity must be 4 or 8, not %r" % (connectivity,))
-    return int(connectivity)
+    (and of `shape`).  A float raster is refused: compare first, river == 1 or depth > 0"""
+    return np.ascontiguousarray(_args.raster(a, what, shape, "the mask", kinds="biu") != 0, np.uint8)
 
 
 def _min_cells(min_cells):
-    if isinstance(min_cells, (bool, np.bool_)) or not isinstance(min_cells, (int, np.integer)) or int(min_cells) < 1:
-        raise ValueError("min_cells must be an integer >= 1, not %r" % (min_cells,))
-    return min(int(min_cells), _MAX_CELLS)  # no region has 2^31 cells: every larger bound keeps nothing either
+    # no region has 2^31 cells: every larger bound keeps nothing either
+    return min(_args.integer(min_cells, "min_cells", 1), _args.MAX_CELLS)
 
 
 def label(mask, connectivity=8, sizes=False):
     """The int64 label raster of mask != 0 (the smallest flat index of the cell's region, -100 on background), or with
     sizes=True Regions(label, size); see the module docstring."""
     m = _mask(mask, "mask")
-    cn = _connectivity(connectivity)
+    cn = _args.connectivity(connectivity)
     H, W = m.shape
     lab = host_empty((H, W), np.int64)
     size = host_empty((H, W), np.int64) if sizes else None
@@ -87,10 +68,10 @@ def connected(mask, seeds, connectivity=8, min_cells=1):
     cells, 0 elsewhere; see the module docstring."""
     m = _mask(mask, "mask")
     s = _mask(seeds, "seeds", m.shape)
-    return _select(m, s, _connectivity(connectivity), _min_cells(min_cells))
+    return _select(m, s, _args.connectivity(connectivity), _min_cells(min_cells))
 
 
 def sieve(mask, min_cells, connectivity=8):
     """uint8 raster: 1 on the foreground cells whose region has at least min_cells cells, 0 elsewhere."""
     m = _mask(mask, "mask")
-    return _select(m, None, _connectivity(connectivity), _min_cells(min_cells))
+    return _select(m, None, _args.connectivity(connectivity), _min_cells(min_cells))

@@ -25,28 +25,25 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
-from ._lib import c_i8p, c_i64p, c_u8p, check, ptr, raster_2d
+from . import _args, _lib
+from ._lib import c_i8p, c_i64p, c_u8p, check, ptr
 
 StreamNetwork = namedtuple("StreamNetwork", ["strahler", "shreve", "link"])
 
 
-def _args(fdr, river):
-    """(fdr as C-contiguous uint8, river as C-contiguous int8 0/1); ValueError before any library call"""
-    f = raster_2d(fdr)
-    r = np.asarray(river)
-    if r.shape != f.shape:
-        raise ValueError("river has shape %s, the direction raster %s" % (r.shape, f.shape))
-    if r.dtype.kind not in "biu":
-        raise ValueError("river must be of a bool or integer dtype, not %s" % r.dtype)
-    return np.ascontiguousarray(f, np.uint8), np.ascontiguousarray(r != 0, np.int8)
+def _checked(fdr, river):
+    """(fdr as C-contiguous uint8, river as C-contiguous int8 0/1); ValueError before any library call.  No cap on
+    the cells here: the size limit is the library's (dt_check_so)"""
+    f = _args.raster(fdr, "fdr", cap=False, dtype=np.uint8)
+    r = _args.raster(river, "river", f.shape, "the direction raster", cap=False, kinds="biu")
+    return f, np.ascontiguousarray(r != 0, np.int8)
 
 
 def stream_network(fdr, river):
     """Strahler order (int8), Shreve magnitude (int64) and link head (int64 flat index) of every cell of the network
     river != 0 on the D8 raster fdr, as StreamNetwork(strahler, shreve, link).  See the module docstring for the
     definition: 0 / 0 / -100 off the network, -100 / -100 / -100 on D8 cycles of network cells."""
-    f, r = _args(fdr, river)
+    f, r = _checked(fdr, river)
     H, W = f.shape
     so = np.empty((H, W), np.int8)
     sh = np.empty((H, W), np.int64)
@@ -58,7 +55,7 @@ def stream_network(fdr, river):
 
 def strahler(fdr, river):
     """Strahler order (int8) of the network river != 0 on fdr: 0 off the network, -100 on D8 cycles"""
-    f, r = _args(fdr, river)
+    f, r = _checked(fdr, river)
     H, W = f.shape
     so = np.empty((H, W), np.int8)
     check(_lib.lib().dt_stream_order(ptr(f, c_u8p), ptr(r, c_i8p), H, W, ptr(so, c_i8p), None, None))

@@ -20,47 +20,31 @@ pour_points of a non-integer dtype or with negative labels, px that is not finit
 more.
 
 Users of a resident chain call dt_dev_drainage / dt_dev_upslope_length on chain.p("fdr")."""
-import math
 from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
-from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, nodata_mask, ptr, raster_2d
+from . import _args, _lib
+from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, check, nodata_mask, ptr
 
 Drainage = namedtuple("Drainage", ["target", "length"])
 
-_MAX_CELLS = 2 ** 31
 
-
-def _args(fdr, px, dem=None, pour_points=None):
+def _checked(fdr, px, dem=None, pour_points=None):
     """(fdr uint8, px float, dem nodata mask float32 or None, pour labels int64 or None), all C-contiguous;
     ValueError before any library call"""
-    f = raster_2d(fdr)
-    if f.size >= _MAX_CELLS:
-        raise ValueError("the raster has %d cells; it must have fewer than 2^31" % f.size)
-    if isinstance(px, (bool, np.bool_)):
-        raise ValueError("px must be a finite number > 0, not %r" % (px,))
-    try:
-        p = float(px)
-    except (TypeError, ValueError):
-        raise ValueError("px must be a finite number > 0, not %r" % (px,)) from None
-    if not (math.isfinite(p) and p > 0):
-        raise ValueError("px must be a finite number > 0, not %r" % (px,))
+    f = _args.raster(fdr, "fdr", dtype=np.uint8)
+    p = _args.pixel_size(px)
     d = nodata_mask(dem, f.shape)  # the DEM is only a nodata mask here, as accumulate takes it
     pp = None
     if pour_points is not None:
-        a = np.asarray(pour_points)
-        if a.shape != f.shape:
-            raise ValueError("pour_points have shape %s, the direction raster %s" % (a.shape, f.shape))
-        if a.dtype.kind not in "iu":
-            raise ValueError("pour_points must be of an integer dtype, not %s" % a.dtype)
+        a = _args.raster(pour_points, "pour_points", f.shape, "the direction raster", kinds="iu")
         if a.size and a.dtype.kind == "i" and int(a.min()) < 0:
             raise ValueError("pour point labels must be >= 0 (the smallest is %d)" % int(a.min()))
         if a.size and int(a.max()) > np.iinfo(np.int64).max:
             raise ValueError("pour point labels must fit int64 (the largest is %d)" % int(a.max()))
         pp = np.ascontiguousarray(a, np.int64)
-    return np.ascontiguousarray(f, np.uint8), p, d, pp
+    return f, p, d, pp
 
 
 def drainage(fdr, px=1.0, dem=None, pour_points=None):
@@ -71,7 +55,7 @@ def drainage(fdr, px=1.0, dem=None, pour_points=None):
     target, 0 when c is its own target.  Both are -100 on nodata, where the path enters a D8 cycle before it stops,
     and (with pour_points) where the path ends at a terminal without meeting a pour point.  Pour points on nodata
     cells are ignored."""
-    f, p, d, pp = _args(fdr, px, dem, pour_points)
+    f, p, d, pp = _checked(fdr, px, dem, pour_points)
     H, W = f.shape
     tg = np.empty((H, W), np.int64)
     ln = np.empty((H, W), np.float64)
@@ -83,7 +67,7 @@ def drainage(fdr, px=1.0, dem=None, pour_points=None):
 def basins(fdr, dem=None):
     """Basin label (int64) of every cell: the flat index y * W + x of its outlet (drainage(...).target without pour
     points, the convention streams uses for link heads); -100 on nodata and where the path enters a D8 cycle."""
-    f, p, d, _ = _args(fdr, 1.0, dem)
+    f, p, d, _ = _checked(fdr, 1.0, dem)
     H, W = f.shape
     tg = np.empty((H, W), np.int64)
     check(_lib.lib().dt_drainage(ptr(f, c_u8p), ptr(d, c_f32p), None, H, W, p, ptr(tg, c_i64p), None, None))
@@ -94,7 +78,7 @@ def watersheds(fdr, pour_points, dem=None):
     """Watershed label (int64) of every cell: the label of the first pour point (label > 0) on its path, gathered on
     the device; 0 where the path reaches a terminal without meeting a pour point; -100 on nodata and where the path
     enters a D8 cycle first.  Pour points on nodata cells are ignored."""
-    f, p, d, pp = _args(fdr, 1.0, dem, pour_points)
+    f, p, d, pp = _checked(fdr, 1.0, dem, pour_points)
     H, W = f.shape
     lb = np.empty((H, W), np.int64)
     check(_lib.lib().dt_drainage(ptr(f, c_u8p), ptr(d, c_f32p), ptr(pp, c_i64p), H, W, p, None, None,
@@ -108,7 +92,7 @@ def upslope_length(fdr, px=1.0, dem=None):
     "Longest" is the exact order of n_card + n_diag * sqrt(2) on the integer move counts (two distinct count pairs
     never tie); the result is the length formula on the winning pair.  -100 on nodata and on cells of a D8 cycle;
     cells that drain into a cycle get their value."""
-    f, p, d, _ = _args(fdr, px, dem)
+    f, p, d, _ = _checked(fdr, px, dem)
     H, W = f.shape
     out = np.empty((H, W), np.float64)
     check(_lib.lib().dt_upslope_length(ptr(f, c_u8p), ptr(d, c_f32p), H, W, p, ptr(out, c_f64p)))

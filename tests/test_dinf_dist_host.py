@@ -47,7 +47,7 @@ def test_value_errors_before_any_library_call(monkeypatch):
             f(dem=np.zeros((5, 7), np.float32))
         with pytest.raises(ValueError, match="2-D"):
             f(dem=np.zeros(30, np.float32))
-        for px in (0.0, -1.0, float("nan"), float("inf"), "wide"):
+        for px in (0.0, -1.0, float("nan"), float("inf"), "wide", True, "a"):
             with pytest.raises(ValueError, match="px"):
                 f(px=px)
         for stat in ("mean", "AVE", 0, None):

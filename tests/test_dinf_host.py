@@ -28,7 +28,7 @@ def test_value_errors_before_any_library_call():
         dinf.flow_direction(dem, 10.0, fdr=np.ones((5, 7), np.uint8))
     with pytest.raises(ValueError, match="shape"):
         dinf.accumulate(_ang(), weights=np.ones((6, 5)))
-    for px in (0.0, -1.0, float("nan"), float("inf"), "wide"):
+    for px in (0.0, -1.0, float("nan"), float("inf"), "wide", True, "a"):
         with pytest.raises(ValueError, match="px"):
             dinf.flow_direction(dem, px)
         with pytest.raises(ValueError, match="px"):

@@ -95,7 +95,7 @@ def test_value_errors_before_any_library_call(no_library):
             proximity.nearest_river(river, 10.0, dem=other)
         with pytest.raises(ValueError, match="shape"):
             proximity.euclidean_hand(other, river, 10.0)
-    for px in (0.0, -1.0, float("nan"), float("inf"), "wide", None):
+    for px in (0.0, -1.0, float("nan"), float("inf"), "wide", None, True, "a"):
         with pytest.raises(ValueError, match="px"):
             proximity.nearest_river(river, px)
         with pytest.raises(ValueError, match="px"):

@@ -14,18 +14,15 @@ tools/dinf_distance_bench.py --profile-only` (one call of each op), summarised b
 grouped into calls at each k_dd_init, per call the span from the first launch to the last end, the three kernels'
 totals and the rounds one by one (four launches, one per colour, each); the accumulation's k_di_* and the flow-path
 kernels of flow_hand_index beside them.  Prints one JSON line (and writes it to --out)."""
-import argparse
 import ctypes
 import csv
 import glob
 import json
 import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
+import numpy as np
+
+import _bench
 
 TILE = 32
 # what one tile visit moves: the state and the height of tile and halo always; beside them at most the three values of
@@ -78,17 +75,12 @@ def summarise_trace(d, out_txt):
     return spans
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, default=16384)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--seed", type=int, default=1)
+def main(argv=None):
+    ap = _bench.parser(steps=5, warmup=1)
     ap.add_argument("--profile-only", action="store_true", help="one call of each op and nothing else (for rocprofv3)")
     ap.add_argument("--trace", default=None, help="summarise the kernel trace under this directory and exit")
     ap.add_argument("--times", default=None, help="with --trace: the text file to write")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.trace:
         spans = summarise_trace(a.trace, a.times)
         if a.out and os.path.exists(a.out):
@@ -96,44 +88,26 @@ def main():
             res["device_span_ms_by_call"] = spans
             res["device_span_note"] = ("rocprofv3 --kernel-trace run of --profile-only: first k_dd_init launch to "
                                        "k_dd_final end, calls in the order check_edges True, False")
-            with open(a.out, "w") as f:
-                f.write(json.dumps(res) + "\n")
+            _bench.emit(res, a.out, show=False)
         return
 
     import torch
     from descriptools_amd import _lib, dinf, flowhand
-    from descriptools_amd.device import Context
 
     H = W = a.size
     N = H * W
     px = 10.0
     L = _lib.lib()
-    st = torch.cuda.Stream()
-    ctx = Context(0, st.cuda_stream)
-    dev = torch.device("cuda", 0)
+    ctx, st, dev = _bench.device()
     with torch.cuda.stream(st):
-        dem_d = torch.empty((H, W), dtype=torch.float32, device=dev)
-        fdr_d = torch.empty((H, W), dtype=torch.uint8, device=dev)
-        slope_d = torch.empty((H, W), dtype=torch.float32, device=dev)
+        dem_d, fdr_d = _bench.terrain(ctx, st, dev, a.size, a.seed, ("dem", "fdr"), px).values()
         angle_d = torch.empty((H, W), dtype=torch.float32, device=dev)
-        _lib.check(L.dt_dev_synth_dem(ctx.h, a.seed, H, W, 0, 0, H, W, 0, dem_d.data_ptr()))
-        _lib.check(L.dt_dev_slope_d8(ctx.h, dem_d.data_ptr(), H, W, px, slope_d.data_ptr(), fdr_d.data_ptr(), None))
         _lib.check(L.dt_dev_dinf_direction(ctx.h, dem_d.data_ptr(), None, H, W, px, angle_d.data_ptr(), None))
         ctx.sync()
         dem, fdr, angle = dem_d.cpu().numpy(), fdr_d.cpu().numpy(), angle_d.cpu().numpy()
-    del dem_d, fdr_d, slope_d, angle_d
+    del dem_d, fdr_d, angle_d
     ctx.close()
     torch.cuda.empty_cache()
-
-    def timed(fn, steps, warmup):
-        for _ in range(warmup):
-            fn()
-        t = []
-        for _ in range(steps):
-            t0 = time.perf_counter()
-            fn()
-            t.append((time.perf_counter() - t0) * 1e3)
-        return t
 
     fac = dinf.accumulate(angle)
     river = (fac > N / 512).astype(np.int8)
@@ -157,26 +131,22 @@ def main():
     if a.profile_only:
         for _, fn in ops:
             fn()
-        print(json.dumps({"tool": "dinf_distance_bench", "profile_only": True, "modes": modes}))
+        _bench.emit({"tool": "dinf_distance_bench", "profile_only": True, "modes": modes}, None)
         return
-    t = {name: timed(fn, a.steps, a.warmup) for name, fn in ops}
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    t = {name: _bench.timed(fn, a.steps, a.warmup) for name, fn in ops}
+    med = {k: _bench.median(v) for k, v in t.items()}
     res = {"tool": "dinf_distance_bench", "size": [H, W], "seed": a.seed, "px": px, "stat": "ave", "steps": a.steps,
            "warmup": a.warmup,
            "timing": "wall clock of the whole host-tier call (uploads, kernels, downloads), median",
            "river_cells": int(river.sum()), "non_nodata_cells": int((angle != -100).sum()),
            "ms": {k: round(v, 2) for k, v in med.items()},
-           "ms_min_max": {k: [round(min(v), 2), round(max(v), 2)] for k, v in t.items()},
+           "ms_min_max": {k: _bench.summary(v, 2)[1] for k, v in t.items()},
            "modes": modes, "tile": [TILE, TILE], "tiles": tiles,
            "bytes_per_tile_visit_min_max": [VISIT_BYTES_MIN, VISIT_BYTES_MAX],
            "host_bytes_per_cell": {"distance_down": [4 + 1 + 4, 24], "dinf_accumulate": [4, 8],
                                    "flow_hand_index": [4 + 1 + 1, 4 + 8 + 4]},
            "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    _bench.emit(res, a.out)
 
 
 if __name__ == "__main__":

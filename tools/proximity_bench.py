@@ -9,64 +9,24 @@ These are host-tier calls: each time is the wall clock of the whole call, upload
 from running this tool under `rocprofv3 --kernel-trace --stats` (k_px_mark / k_px_carry / k_px_row: the row pass,
 k_px_col: the column pass, one launch per level).  (b) and (c) are checked against their closed forms.  Prints one JSON
 line (and writes it to --out)."""
-import argparse
-import json
-import os
-import sys
-import time
+import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from descriptools_amd import _lib, flowhand, proximity  # noqa: E402
-from descriptools_amd.device import Context  # noqa: E402
+import _bench
+from descriptools_amd import flowhand, proximity
 
 
-def terrain(H, W, seed, px):
-    """(dem float32, fdr uint8, river int8) of the benchmark terrain, as host arrays"""
-    L = _lib.lib()
-    st = torch.cuda.Stream()
-    ctx = Context(0, st.cuda_stream)
-    dev = torch.device("cuda", 0)
-    with torch.cuda.stream(st):
-        dem = torch.empty((H, W), dtype=torch.float32, device=dev)
-        fdr = torch.empty((H, W), dtype=torch.uint8, device=dev)
-        slope = torch.empty((H, W), dtype=torch.float32, device=dev)
-        fac = torch.empty((H, W), dtype=torch.int32, device=dev)
-        _lib.check(L.dt_dev_synth_dem(ctx.h, seed, H, W, 0, 0, H, W, 0, dem.data_ptr()))
-        _lib.check(L.dt_dev_slope_d8(ctx.h, dem.data_ptr(), H, W, px, slope.data_ptr(), fdr.data_ptr(), None))
-        _lib.check(L.dt_dev_flowacc(ctx.h, fdr.data_ptr(), None, H, W, fac.data_ptr()))
-        ctx.sync()
-        river = (fac > (H * W) // 512).to(torch.int8)
-        out = dem.cpu().numpy(), fdr.cpu().numpy(), river.cpu().numpy()
-    ctx.close()
-    return out
-
-
-def timed(fn, steps, warmup):
-    for _ in range(warmup):
-        fn()
-    t = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        fn()
-        t.append((time.perf_counter() - t0) * 1e3)
-    return t
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, default=16384)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+def main(argv=None):
+    a = _bench.parser(steps=5, warmup=1).parse_args(argv)
     H = W = a.size
     px = 10.0
-    dem, fdr, network = terrain(H, W, a.seed, px)
+    # the benchmark terrain as host arrays: dem float32, fdr uint8, river int8
+    ctx, st, dev = _bench.device()
+    with torch.cuda.stream(st):
+        ter = _bench.terrain(ctx, st, dev, a.size, a.seed, ("dem", "fdr", "river"), px)
+        dem, fdr, network = (r.cpu().numpy() for r in ter.values())
+    del ter
+    ctx.close()
     corner = np.zeros((H, W), np.int8)
     corner[0, 0] = 1
     every = np.ones((H, W), np.int8)
@@ -88,22 +48,18 @@ def main():
            ("nearest_river_every_cell", lambda: proximity.nearest_river(every, px)),
            ("euclidean_hand_network", lambda: proximity.euclidean_hand(dem, network, px)),
            ("flow_hand_index_network", lambda: flowhand.flow_hand_index(dem, fdr, network, px)))
-    t = {name: timed(fn, a.steps, a.warmup) for name, fn in ops}
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    t = {name: _bench.timed(fn, a.steps, a.warmup) for name, fn in ops}
+    med = {k: _bench.median(v) for k, v in t.items()}
     res = {"tool": "proximity_bench", "size": [H, W], "seed": a.seed, "px": px, "steps": a.steps, "warmup": a.warmup,
            "timing": "wall clock of the whole host-tier call (uploads, kernels, downloads), median",
            "network_cells": int(network.sum()), "ms": {k: round(v, 2) for k, v in med.items()},
-           "ms_min_max": {k: [round(min(v), 2), round(max(v), 2)] for k, v in t.items()},
+           "ms_min_max": {k: _bench.summary(v, 2)[1] for k, v in t.items()},
            "one_corner_over_network": round(med["nearest_river_one_corner"] / med["nearest_river_network"], 3),
            "every_cell_over_network": round(med["nearest_river_every_cell"] / med["nearest_river_network"], 3),
            "euclidean_hand_over_flow_hand_index": round(med["euclidean_hand_network"] / med["flow_hand_index_network"],
                                                         3),
            "scratch_bytes_per_cell": 8, "closed_forms_checked": True, "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    _bench.emit(res, a.out)
 
 
 if __name__ == "__main__":

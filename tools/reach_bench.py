@@ -6,35 +6,22 @@ river = fac > N/512 and a dense one, fac > 1000.  K = 84 stages of one foot.  Af
 number of reaches R and the bytes each entry moves per cell.  The tables entry is timed four ways: with and without
 the slope raster, and (--ab) without its LDS table, one global atomic per cell (DT_DBG_RC_SLOTS = -1), and with the
 table capped at 4 slots.  Prints one JSON line (and writes it to --out when given)."""
-import argparse
-import json
-import os
-import sys
+import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from descriptools_amd import _lib, chain  # noqa: E402
-from descriptools_amd.device import Context  # noqa: E402
-from descriptools_amd.flowacc import _default_frac_bits  # noqa: E402
-from descriptools_amd.reaches import bed_weight_max  # noqa: E402
+import _bench
+from descriptools_amd import _args, _lib, chain
+from descriptools_amd.reaches import bed_weight_max
 
 DT_DBG_RC_SLOTS = 10
 HEADS_CAP = 1 << 22
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, default=16384)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--seed", type=int, default=1)
+def main(argv=None):
+    ap = _bench.parser(steps=20, warmup=3)
     ap.add_argument("--stages", type=int, default=84)
     ap.add_argument("--ab", action="store_true", help="also time the tables without and with a capped LDS table")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     H = W = a.size
     N = H * W
     px = 10.0
@@ -42,14 +29,11 @@ def main():
     stages = np.arange(K) * 0.3048
     st_p = stages.ctypes.data_as(_lib.c_f64p)
     L = _lib.lib()
-    st = torch.cuda.Stream()
-    ctx = Context(0, st.cuda_stream)
-    dev = torch.device("cuda", 0)
+    ctx, st, dev = _bench.device()
     thr = {"chain": N // 512, "dense": 1000}
     stats = {}
     with torch.cuda.stream(st):
-        dem = torch.empty((H, W), dtype=torch.float32, device=dev)
-        _lib.check(L.dt_dev_synth_dem(ctx.h, a.seed, H, W, 0, 0, H, W, 0, dem.data_ptr()))
+        dem = _bench.terrain(ctx, st, dev, a.size, a.seed, ("dem",))["dem"]
         so = torch.empty((H, W), dtype=torch.int8, device=dev)
         lk = torch.empty((H, W), dtype=torch.int64, device=dev)
         reach = torch.empty((H, W), dtype=torch.int32, device=dev)
@@ -71,7 +55,7 @@ def main():
             ctx.sync()
             R = int(n_d.item())
             wmax = bed_weight_max(ch.buf["slope"].to_host(pinned=True))
-            s = _default_frac_bits(N, max(float(stages[-1]), wmax))
+            s = _args._default_frac_bits(N, max(float(stages[-1]), wmax))
             cha = [torch.empty(max(R, 1), dtype=torch.int64, device=dev) for _ in range(5)]
             tab = [torch.empty((max(R, 1), K), dtype=torch.int64, device=dev) for _ in range(3)]
             stage = torch.full((max(R, 1),), float(stages[K // 2]), dtype=torch.float64, device=dev)
@@ -103,40 +87,24 @@ def main():
                 ops["tables_slope_no_lds"] = (with_slots(-1, True), 12)
                 ops["tables_slope_4_slots"] = (with_slots(4, True), 12)
                 ops["tables_no_lds"] = (with_slots(-1, False), 8)
-            for _ in range(a.warmup):
-                for f, _b in ops.values():
-                    f()
-            ctx.sync()
-            assert ctx.status() == 0
-            t = {o: [] for o in ops}
-            for _ in range(a.steps):
-                for o, (f, _b) in ops.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(st)
-                    f()
-                    e1.record(st)
-                    ctx.sync()
-                    t[o].append(e0.elapsed_time(e1))
+            t = _bench.events(ctx, st, {o: f for o, (f, _b) in ops.items()}, a.steps, a.warmup)
+            assert ctx.status() == 0  # the bits are sticky: the warm-up's too
             tables()
             ctx.sync()
             taking = int(tab[0][:R, K - 1].sum()) if R else 0
             stats[k] = {"threshold": v, "R": R, "frac_bits": s, "cells_in_tables": taking,
                         "network_cells": int((reach >= 0).sum()), "wet_cells": int((depth > 0).sum())}
             for o, (f, b) in ops.items():
-                ms = float(np.median(t[o]))
-                stats[k][o] = {"ms": round(ms, 3), "ms_min_max": [round(min(t[o]), 3), round(max(t[o]), 3)],
-                               "bytes_per_cell": b, "GBs": round(b * N / ms / 1e6, 1)}
+                ms, ms_min_max = _bench.summary(t[o])
+                stats[k][o] = {"ms": ms, "ms_min_max": ms_min_max, "bytes_per_cell": b,
+                               "GBs": round(b * N / _bench.median(t[o]) / 1e6, 1)}
             del cha, tab, stage
             ch.free()
     res = {"tool": "reach_bench", "size": [H, W], "seed": a.seed, "px": px, "stages": K, "steps": a.steps,
            "warmup": a.warmup,
            "timing": "median of HIP events around each entry on its stream, entries alternating",
            "scratch_bytes": int(L.dt_ctx_scratch_bytes(ctx.h)), "runs": stats, "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    _bench.emit(res, a.out)
     ctx.close()
 
 

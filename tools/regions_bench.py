@@ -10,69 +10,29 @@ the kernels alone.  Both are the median of --steps after --warmup.  The algorith
 1 B read + 8 B label written per cell, plus what the union-find plane costs (4 B written by the local pass, 4 B read by
 the flatten pass, the seam pass's reads aside).  (c) is checked against its closed form, (a) and (b) against each other
 between the tiers.  Nothing is gated.  Prints one JSON line (and writes it to --out)."""
-import argparse
-import json
-import os
-import sys
-import time
+import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from descriptools_amd import _lib, reaches, regions  # noqa: E402
-from descriptools_amd.device import Context  # noqa: E402
+import _bench
+from descriptools_amd import _lib, reaches, regions
 
 
-def timed(fn, steps, warmup):
-    for _ in range(warmup):
-        fn()
-    t = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        fn()
-        t.append((time.perf_counter() - t0) * 1e3)
-    return t
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, default=16384)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--seed", type=int, default=1)
+def main(argv=None):
+    ap = _bench.parser(steps=5, warmup=1)
     ap.add_argument("--level", type=float, default=3.0, help="the wet mask is hand <= level (and hand >= 0)")
     ap.add_argument("--no-host", action="store_true", help="device-tier times only")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     H = W = a.size
     N = H * W
     px = 10.0
     L = _lib.lib()
-    st = torch.cuda.Stream()
-    ctx = Context(0, st.cuda_stream)
-    dev = torch.device("cuda", 0)
+    ctx, st, dev = _bench.device()
     res = {"tool": "regions_bench", "size": [H, W], "seed": a.seed, "level": a.level, "steps": a.steps,
            "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "scratch_bytes_per_cell": 12,
            "algorithmic_bytes_per_cell": {"label": 1 + 8, "plane_P": 4 + 4}}
     with torch.cuda.stream(st):
         # the benchmark terrain, its river network, the flow-path HAND and one catchment for the whole raster
-        dem = torch.empty((H, W), dtype=torch.float32, device=dev)
-        fdr = torch.empty((H, W), dtype=torch.uint8, device=dev)
-        slope = torch.empty((H, W), dtype=torch.float32, device=dev)
-        fac = torch.empty((H, W), dtype=torch.int32, device=dev)
-        _lib.check(L.dt_dev_synth_dem(ctx.h, a.seed, H, W, 0, 0, H, W, 0, dem.data_ptr()))
-        _lib.check(L.dt_dev_slope_d8(ctx.h, dem.data_ptr(), H, W, px, slope.data_ptr(), fdr.data_ptr(), None))
-        _lib.check(L.dt_dev_flowacc(ctx.h, fdr.data_ptr(), None, H, W, fac.data_ptr()))
-        ctx.sync()
-        river = (fac > N // 512).to(torch.int8)
-        del slope, fac
-        hand = torch.empty((H, W), dtype=torch.float32, device=dev)
-        _lib.check(L.dt_dev_flowhand(ctx.h, dem.data_ptr(), fdr.data_ptr(), river.data_ptr(), None, H, W, px, None, None,
-                                     hand.data_ptr(), None))
-        ctx.sync()
-        del dem, fdr
+        river, hand = _bench.terrain(ctx, st, dev, a.size, a.seed, ("river", "hand"), px).values()
         gen = torch.Generator(device=dev)
         gen.manual_seed(a.seed)
         masks = {"wet": ((hand >= 0) & (hand <= a.level)).to(torch.uint8),
@@ -88,18 +48,8 @@ def main():
         res["foreground_cells"] = {k: int(m.sum().item()) for k, m in masks.items()}
         res["seed_cells"] = int(seeds.sum().item())
 
-        def device_ms(call):
-            for _ in range(a.warmup):
-                _lib.check(call())
-            t = []
-            for _ in range(a.steps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st)
-                _lib.check(call())
-                e1.record(st)
-                e1.synchronize()
-                t.append(e0.elapsed_time(e1))
-            return t
+        def device_ms(call):  # one entry at a time: its warm-up, then its steps
+            return _bench.events(ctx, st, {"call": lambda: _lib.check(call())}, a.steps, a.warmup)["call"]
 
         dev_t = {}
         for name, m in masks.items():
@@ -128,10 +78,10 @@ def main():
         host_seeds, host_hand, host_river = seeds.cpu().numpy(), hand.cpu().numpy(), river.cpu().numpy()
         dev_label_wet, dev_keep_wet = label.cpu().numpy(), keep.cpu().numpy()
     ctx.close()
-    res["device_ms"] = {k: round(float(np.median(v)), 3) for k, v in dev_t.items()}
-    res["device_ms_min_max"] = {k: [round(min(v), 3), round(max(v), 3)] for k, v in dev_t.items()}
+    res["device_ms"] = {k: _bench.summary(v)[0] for k, v in dev_t.items()}
+    res["device_ms_min_max"] = {k: _bench.summary(v)[1] for k, v in dev_t.items()}
     res["device_GBps_algorithmic_label"] = {
-        k: round(N * 9 / (float(np.median(v)) * 1e-3) / 1e9, 1) for k, v in dev_t.items() if k.startswith("label_")}
+        k: round(N * 9 / (_bench.median(v) * 1e-3) / 1e9, 1) for k, v in dev_t.items() if k.startswith("label_")}
     del masks, seeds, hand, river, label, keep, depth, cat
     torch.cuda.empty_cache()
     if not a.no_host:
@@ -145,15 +95,11 @@ def main():
         ops += [("inundate_connected_wet_8",
                  lambda: reaches.inundate_connected(cat_h, host_hand, [a.level], host_river)),
                 ("inundate_wet", lambda: reaches.inundate(cat_h, host_hand, [a.level]))]
-        t = {name: timed(fn, a.steps, a.warmup) for name, fn in ops}
-        res["host_ms"] = {k: round(float(np.median(v)), 2) for k, v in t.items()}
-        res["host_ms_min_max"] = {k: [round(min(v), 2), round(max(v), 2)] for k, v in t.items()}
+        t = {name: _bench.timed(fn, a.steps, a.warmup) for name, fn in ops}
+        res["host_ms"] = {k: _bench.summary(v, 2)[0] for k, v in t.items()}
+        res["host_ms_min_max"] = {k: _bench.summary(v, 2)[1] for k, v in t.items()}
         res["host_timing"] = "wall clock of the whole host-tier call (mask != 0, uploads, kernels, downloads), median"
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    _bench.emit(res, a.out)
 
 
 if __name__ == "__main__":
