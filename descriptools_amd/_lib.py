@@ -15,6 +15,7 @@ _lib = None
 c_f32p = C.POINTER(C.c_float)
 c_f64p = C.POINTER(C.c_double)
 c_u8p = C.POINTER(C.c_uint8)
+c_u16p = C.POINTER(C.c_uint16)
 c_i8p = C.POINTER(C.c_int8)
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
@@ -53,6 +54,8 @@ _SIGS = {
     "dt_dinf_direction": (ci, [c_f32p, c_u8p, i64, i64, f64, c_f32p, c_f32p]),
     "dt_dinf_accumulate": (ci, [c_f32p, c_f64p, i64, i64, ci, c_f64p, c_i64p]),
     "dt_dinf_distance_down": (ci, [c_f32p, c_i8p, c_f32p, i64, i64, f64, ci, ci, ci, c_f64p, c_f64p, c_f64p, c_i64p]),
+    "dt_mfd_shares": (ci, [c_f32p, c_u8p, i64, i64, f64, ci, c_u16p]),
+    "dt_mfd_accumulate": (ci, [c_u16p, c_f64p, i64, i64, ci, c_f64p, c_i64p]),
     "dt_proximity": (ci, [c_i8p, c_f32p, i64, i64, f64, c_f32p, c_i64p]),
     "dt_reach_catchments": (ci, [c_i64p, c_i64p, i64, i64, c_i32p, c_i32p, c_i64p, i64, c_i64p]),
     "dt_reach_channels": (ci, [c_u8p, c_i32p, i64, i64, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
@@ -102,6 +105,9 @@ _SIGS = {
     "dt_dev_dinf_direction": (ci, [vp, vp, vp, i64, i64, f64, vp, vp]),
     "dt_dev_dinf_accumulate": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
     "dt_dev_dinf_accumulate_info": (ci, [vp, c_i64p]),
+    "dt_dev_mfd_shares": (ci, [vp, vp, vp, i64, i64, f64, ci, vp]),
+    "dt_dev_mfd_accumulate": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
+    "dt_dev_mfd_accumulate_info": (ci, [vp, c_i64p]),
     "dt_dev_reach_catchments": (ci, [vp, vp, vp, ci, i64, i64, vp, vp, vp, i64, vp]),
     "dt_dev_reach_channels": (ci, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "dt_dev_reach_tables": (ci, [vp, vp, vp, ci, vp, i64, i64, c_f64p, ci, i64, ci, vp, vp, vp]),

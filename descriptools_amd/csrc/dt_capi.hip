@@ -408,7 +408,8 @@ struct DevCall {
   DT_TRY(d.rc)
 
 // Not on the scaffold, because they enqueue no kernel and would get no shorter: dt_dev_malloc, dt_dev_free, the copies,
-// dt_dev_downslope_queued, dt_dev_dinf_accumulate_info, dt_dev_membench_mix_timed and dt_dev_mem_info.
+// dt_dev_downslope_queued, dt_dev_dinf_accumulate_info, dt_dev_mfd_accumulate_info, dt_dev_membench_mix_timed and
+// dt_dev_mem_info.
 extern "C" int dt_dev_malloc(dt_ctx *c, int64_t bytes, void **out) {
   DT_CTX(c);
   DT_REQUIRE(out && bytes >= 0, "bad arguments");
@@ -687,6 +688,63 @@ extern "C" int dt_dev_dinf_accumulate_info(dt_ctx *c, int64_t *info4) {
                             "since)", &k));
   uint32_t ctl[8];
   DT_HIP(hipMemcpyAsync(ctl, dt_dinf_accumulate_ctl(k->ptr, k->h, k->w), sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+  DT_HIP(hipStreamSynchronize(c->stream));
+  info4[0] = ctl[3];
+  info4[1] = ctl[4];
+  info4[2] = ctl[0];
+  info4[3] = ctl[5];
+  return DT_OK;
+}
+
+static int dt_check_mfd_exponent(double exponent) {
+  DT_REQUIRE(std::isfinite(exponent) && exponent >= 0.0 && exponent <= 64.0, "exponent must be finite and in [0, 64]");
+  return DT_OK;
+}
+extern "C" int dt_dev_mfd_shares(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double exponent,
+                                 int contour, uint16_t *shares) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_mfd_exponent(exponent));
+  DT_REQUIRE((dem && shares) || H * W == 0, "NULL raster");
+  if (H * W == 0) return DT_OK;
+  return d.done(dt_launch_mfd_shares(c->stream, dem, fdr, H, W, exponent, contour, shares));
+}
+
+extern "C" int dt_dev_mfd_accumulate(dt_ctx *c, const uint16_t *shares, const double *w, int64_t H, int64_t W,
+                                     int frac_bits, int rounds, double *acc) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_REQUIRE((shares && acc) || H * W == 0, "NULL raster");
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  DT_REQUIRE(rounds != 0 && rounds >= -DT_DINF_ROUNDS_MAX && rounds <= DT_DINF_ROUNDS_MAX,
+             "rounds must lie in [1, 4096] (or [-4096, -1] to continue)");
+  if (H * W == 0) return DT_OK;
+  const size_t need = dt_mfd_accumulate_scratch(H, W);
+  if (rounds > 0) {
+    void *scr = d.scratch(need);
+    DT_TRY(d.rc);
+    DT_TRY(dt_launch_mfd_accumulate(c->stream, shares, w, H, W, frac_bits, 1, rounds - 1, 1, scr, need, acc, c->status));
+    dt_scratch_claim(c, DT_OWNER_MFD, H, W, scr, nullptr, shares, w, frac_bits);
+    return d.done();
+  }
+  const DtScratchClaim *k;
+  DT_TRY(dt_scratch_claimed(c, DT_OWNER_MFD, &d.w, false,
+                            "dt_dev_mfd_accumulate cannot continue: no accumulation of this shape was started on this "
+                            "context (or another call has used the context's scratch in between)", &k));
+  DT_REQUIRE(k->in[0] == shares && k->in[1] == w && k->frac_bits == frac_bits,
+             "dt_dev_mfd_accumulate continues with another share raster, weight raster or frac_bits than it was "
+             "started with");
+  return d.done(dt_launch_mfd_accumulate(c->stream, shares, w, H, W, frac_bits, 0, -rounds, 1, k->ptr, need, acc,
+                                         c->status));
+}
+
+extern "C" int dt_dev_mfd_accumulate_info(dt_ctx *c, int64_t *info4) {
+  DT_CTX(c);
+  DT_REQUIRE(info4 != nullptr, "info4 is NULL");
+  const DtScratchClaim *k;
+  DT_TRY(dt_scratch_claimed(c, DT_OWNER_MFD, nullptr, false,
+                            "no MFD accumulation on this context (or another call has used the context's scratch since)",
+                            &k));
+  uint32_t ctl[8];
+  DT_HIP(hipMemcpyAsync(ctl, dt_mfd_accumulate_ctl(k->ptr, k->h, k->w), sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
   DT_HIP(hipStreamSynchronize(c->stream));
   info4[0] = ctl[3];
   info4[1] = ctl[4];
@@ -2036,6 +2094,64 @@ extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H
                                                hc.c->status)));
   DT_TRY(dt_ctx_status(hc.c, &st));
   DT_REQUIRE(!(st & DT_STATUS_BAD_ANGLE), "an angle is neither -1, -100 nor in [0, float32(2 pi)]");
+  DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
+  if (info4) {
+    info4[0] = ctl[3];
+    info4[1] = ctl[4];
+    info4[2] = ctl[0];
+    info4[3] = ctl[5];
+  }
+  return hc.finish();
+}
+
+extern "C" int dt_mfd_shares(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double exponent, int contour,
+                             uint16_t *shares) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_TRY(dt_check_mfd_exponent(exponent));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem && shares, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  const uint8_t *d_f = hc.in(fdr, n);
+  uint16_t *d_s = hc.out(shares, n * 8);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_mfd_shares(hc.c, d_dem, d_f, H, W, exponent, contour, d_s));
+  return hc.finish();
+}
+
+extern "C" int dt_mfd_accumulate(const uint16_t *shares, const double *w, int64_t H, int64_t W, int frac_bits,
+                                 double *acc, int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(shares && acc, "NULL raster");
+  const uint16_t *d_s = hc.in(shares, n * 8);
+  const double *d_w = hc.in(w, n);
+  double *d_o = hc.out(acc, n);
+  const size_t need = dt_mfd_accumulate_scratch(H, W);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  uint32_t ctl[8] = {0};
+  for (int start = 1;; start = 0) {
+    DT_TRY(dt_launch_mfd_accumulate(hc.c->stream, d_s, d_w, H, W, frac_bits, start, DT_DINF_BATCH, 0, scr, need, d_o,
+                                    hc.c->status));
+    DT_TRY(hc.download(ctl, dt_mfd_accumulate_ctl(scr, H, W), 8));
+    DT_HIP(hipStreamSynchronize(hc.c->stream));
+    if (ctl[0] == ctl[2]) break;  // everything queued has been drained
+  }
+  DT_TRY(dt_launched(dt_launch_mfd_accumulate(hc.c->stream, d_s, d_w, H, W, frac_bits, 0, 0, 1, scr, need, d_o,
+                                              hc.c->status)));
+  DT_TRY(dt_ctx_status(hc.c, &st));
+  DT_REQUIRE(!(st & DT_STATUS_BAD_SHARES),
+             "a share word is not eight 0xFFFF and has a slot above 32768 or a sum that is neither 0 nor 32768");
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
   if (info4) {
     info4[0] = ctl[3];

@@ -60,14 +60,14 @@ int dt_debug_get(int key);
 // Which multi-call op's state lives in the context's `scratch`, and where.  The op's first phase claims it (*_local_w,
 // the first rounds of dt_dev_dinf_accumulate), every dt_scratch_reset drops the claim, the later phases (*_finish_w, a
 // continuation) require it -- dt_scratch_claim / dt_scratch_claimed in dt_capi.hip are the only code that touches it.
-enum DtScratchOwner { DT_OWNER_NONE = 0, DT_OWNER_FLOWACC, DT_OWNER_HAND, DT_OWNER_DINF };
+enum DtScratchOwner { DT_OWNER_NONE = 0, DT_OWNER_FLOWACC, DT_OWNER_HAND, DT_OWNER_DINF, DT_OWNER_MFD };
 struct DtScratchClaim {
   DtScratchOwner owner;
   int64_t h, w;       // the core shape of the raster the state belongs to
   char *ptr;          // where in `scratch` that state starts
   char *ptr2;         // flow accumulation only: HAND's region reserved beside it, for when phase 2 of the one and phase 1
                       // of the other are fused (the region then becomes HAND's `ptr`)
-  const void *in[2];  // D-infinity only: the angle and weight rasters the accumulation was started on,
+  const void *in[2];  // D-infinity, MFD: the angle (share) and weight rasters the accumulation was started on,
   int frac_bits;      // and its frac_bits: a continuation must name the same
 };
 struct dt_ctx {

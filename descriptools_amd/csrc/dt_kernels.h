@@ -296,6 +296,22 @@ int dt_launch_dinf_distance(hipStream_t s, const float *angle, const int8_t *riv
 // the control words in `scratch` (72 x uint32 on the device)
 const uint32_t *dt_dinf_distance_ctl(void *scratch, int64_t H, int64_t W);
 
+// Multiple flow direction (dt_mfd.hip; mfd.py holds the definition): the share raster of a DEM (eight uint16 per cell
+// by octant, units of 2^-15, 16-byte aligned; fdr may be NULL; exponent in [0, 64]), and the contributing area of a
+// share raster (wt may be NULL: 1 everywhere).  The accumulation keeps its state in `scratch` and takes start, rounds
+// and finish as dt_launch_dinf_accumulate does; a share word outside the contract raises DT_STATUS_BAD_SHARES on
+// `status`.  The environment variable DT_DBG_MFD_STACK = n > 0 caps the complete cells a lane holds at n, the one it
+// carries on with included (tests).  Nothing synchronises.  H * W < 2^31.
+int dt_launch_mfd_shares(hipStream_t s, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double exponent,
+                         int contour, uint16_t *shares);
+size_t dt_mfd_accumulate_scratch(int64_t H, int64_t W);
+int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double *wt, int64_t H, int64_t W,
+                             int frac_bits, int start, int rounds, int finish, void *scratch, size_t scratch_bytes,
+                             double *out, int *status);
+// the accumulation's control words in `scratch` (8 x uint32 on the device): queued, window lo, window hi, queue rounds
+// that found work, the largest window, cells with two or more receivers
+const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W);
+
 // Euclidean proximity (dt_proximity.hip): for every cell the nearest source (river == 1 and, with nod, nod > -100) by
 // exact squared distance, ties to the smallest flat index -> distance = float32(px * sqrt(float64(d2))) and indices =
 // the source's flat index; -100 where nod <= -100 and when there is no source.  nod may be NULL.  The row pass, the

@@ -103,6 +103,9 @@ int dt_graph_destroy(dt_graph *graph);
 /* DT_STATUS_BAD_ANGLE: dt_dev_dinf_accumulate met an angle that is neither -1, -100 nor in [0, float32(2 pi)] (NaN
  * included); that cell was taken as -1 (no receiver). */
 #define DT_STATUS_BAD_ANGLE 16
+/* DT_STATUS_BAD_SHARES: dt_dev_mfd_accumulate met a share word outside its contract (not eight 0xFFFF, and a slot above
+ * 32768 or slots that sum to neither 0 nor 32768); that cell was taken as having no receiver. */
+#define DT_STATUS_BAD_SHARES 32
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
 
@@ -230,6 +233,31 @@ int dt_dinf_accumulate(const float *angle, const double *w, int64_t H, int64_t W
 int dt_dinf_distance_down(const float *angle, const int8_t *river, const float *dem, int64_t H, int64_t W, double px,
                           int stat, int check_edges, int visit_limit, double *h, double *v, double *s,
                           int64_t *info4);
+/* Net-new: multiple-flow-direction (MFD; Quinn et al. 1991, Freeman 1991, Holmgren 1994) flow shares of a DEM
+ * (descriptools_amd/mfd.py holds the full definition).  shares is uint16[H][W][8], 16-byte aligned; the last axis is
+ * the octant as in dt_dinf_direction (E, NE, N, NW, W, SW, S, SE), the unit 2^-15.  A height is valid when it is finite
+ * and > -100.  A nodata centre (<= -100, -inf included) stores eight 0xFFFF, a NaN or +inf centre eight zeros.  The
+ * receivers of a valid centre z0 are the neighbours in the raster that are valid and strictly lower; in float64, in
+ * octant order: d = z0 - z_k, g = d (k even) or d / 1.4142135623730951 (k odd), u = g / max g, f = u^p (p integer-valued:
+ * p successive products from 1.0; otherwise pow(u, p)), with contour != 0 times 0.5 (k even) or 0.35355339059327373
+ * (k odd); F = the sum of the f in octant order, r = f / F.  The main receiver has the largest f (the first of equals);
+ * every other stores floor(ldexp(r, 15)) and the main one 32768 less their sum, so a cell's shares sum to 32768.  A
+ * valid centre without a lower neighbour: when fdr (may be NULL) holds a D8 code there whose neighbour is in the raster
+ * and valid, 32768 in that octant; else eight zeros.  The pixel size cancels out of every share.  exponent must be
+ * finite and in [0, 64]; rasters of 2^31 cells or more are refused. */
+int dt_mfd_shares(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double exponent, int contour,
+                  uint16_t *shares);
+/* Net-new: MFD contributing area of a share raster (dt_mfd_shares', or any raster under its contract: a word of eight
+ * 0xFFFF is nodata; in any other every slot is <= 32768 and the slots sum to 0 or 32768; anything else fails the call).
+ * c -> d is an edge for each octant k with P_k > 0 whose neighbour d is in the raster and not nodata (other shares leave
+ * the domain); the main receiver is the slot with the largest P, the first of equals.  With q(c) = rint(w(c) * 2^s),
+ * s = frac_bits (w NULL: 1 everywhere; the rules of dt_flowacc_weighted), T(c) = q(c) + what c receives; a complete c
+ * sends m_k = floor(T * P_k / 2^15) to every other receiver k and T less their sum to the main one.
+ * acc = ldexp(T - q, -s) (self excluded), -100 on nodata and on every cell on or below a cycle.  Exact integer sums: the
+ * result does not depend on order or run.  info4 (may be NULL) = {queue rounds that found work, the largest number of
+ * cells one round drained, cells queued in all, cells with two or more receivers}. */
+int dt_mfd_accumulate(const uint16_t *shares, const double *w, int64_t H, int64_t W, int frac_bits, double *acc,
+                      int64_t *info4);
 /* Net-new: exact Euclidean proximity to the river network.  A source is a cell with river == 1 that is not nodata;
  * nodata is a cell with nod <= -100, where nod (may be NULL: no nodata) is any float32 raster of the shape: a float32
  * DEM, or for heights float32 cannot hold the -100 / 0 mask of the DEM's own comparison (descriptools_amd._lib.
@@ -449,6 +477,20 @@ int dt_dev_dinf_accumulate(dt_ctx *ctx, const float *angle, const double *w, int
 /* dt_dinf_accumulate's info4 for the accumulation last enqueued on this context (synchronises): what a caller sizes
  * its budget of rounds with.  DT_EINVAL when another call has used the context's scratch since. */
 int dt_dev_dinf_accumulate_info(dt_ctx *ctx, int64_t *info4);
+/* dt_mfd_shares and dt_mfd_accumulate on device rasters (rows x cols = H x W), on the context's stream: neither
+ * synchronises.  fdr and w may be NULL; the share raster is 16-byte aligned.  dt_dev_mfd_accumulate takes its budget of
+ * rounds as
+ * dt_dev_dinf_accumulate does: round 0 and rounds - 1 queue rounds (1 <= rounds <= 4096), DT_STATUS_NOT_CONVERGED when
+ * queued work is left, and -4096 <= rounds <= -1 continues with -rounds further rounds on the same share raster,
+ * weight raster, shape and frac_bits (DT_EINVAL otherwise, and when another call has used the context's scratch
+ * since).  A share word outside the contract raises DT_STATUS_BAD_SHARES and counts as no receiver, a bad weight
+ * DT_STATUS_BAD_WEIGHT and 0.  dt_dev_mfd_accumulate_info: dt_mfd_accumulate's info4 for the accumulation last enqueued
+ * on this context (synchronises). */
+int dt_dev_mfd_shares(dt_ctx *ctx, const float *dem, const uint8_t *fdr, int64_t rows, int64_t cols, double exponent,
+                      int contour, uint16_t *shares);
+int dt_dev_mfd_accumulate(dt_ctx *ctx, const uint16_t *shares, const double *w, int64_t rows, int64_t cols,
+                          int frac_bits, int rounds, double *acc);
+int dt_dev_mfd_accumulate_info(dt_ctx *ctx, int64_t *info4);
 /* The reach calls on device rasters, on the context's stream: none synchronises.  idx is int32 (idx_bytes 4, the
  * resident chain's raster) or int64 (8); n_reaches (may be NULL) is one int64 on the device; heads entries from R on
  * are left as they were.  dt_dev_reach_tables takes `stages` from the host (they travel as kernel arguments) and the
