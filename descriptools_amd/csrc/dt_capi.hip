@@ -1043,6 +1043,11 @@ extern "C" int dt_dev_confusion_multi(dt_ctx *c, const double *desc, const int8_
                                     (unsigned long long *)counts4_dev));
 }
 
+// out3 = {smallest, second-smallest distinct, largest} value of x: np.unique(x)[0], [1], [-1] with one documented
+// difference, the NaN rule.  np.unique sorts NaN last, so one NaN cell would make the largest value NaN and the raster
+// impossible to scale; here NaN cells are skipped (a HAND with NaN cells still calibrates).  A slot that has no value
+// is NaN: the second when all values are equal or N == 1, all three when N == 0 or every cell is NaN.  -inf and +inf
+// are values.  -0.0 and +0.0 are one value, as for np.unique; which zero is returned for it is not specified.
 extern "C" int dt_dev_unique_extremes_f32(dt_ctx *c, const float *x, int64_t N, float *out3_dev) {
   DT_DEV(d, c);
   DT_REQUIRE(x && out3_dev && N >= 0, "bad arguments");
@@ -2611,24 +2616,33 @@ extern "C" int dt_confusion_multi(const double *desc, const int8_t *flood, int64
 }
 
 // ---- evaluation.minMaxScale / binary_map / avaliacao, host tier --------------------------------------
-extern "C" int dt_minmax_scale(const void *x, int is_f32, int64_t N, double mn, double mx, double nodata, void *out) {
+// minMaxScale with the denominator mx - mn given (numpy subtracts the scalars from each other before they meet the
+// raster); cell_bytes 2 / 4 / 8: a float16 / float32 / float64 raster in and out, computed in that type
+extern "C" int dt_minmax_scale_den(const void *x, int cell_bytes, int64_t N, double mn, double den, double nodata,
+                                   void *out) {
   HostCall hc;
   DT_TRY(hc.rc);
   DT_REQUIRE(N >= 0, "negative size");
+  DT_REQUIRE(cell_bytes == 2 || cell_bytes == 4 || cell_bytes == 8, "cell_bytes is 2, 4 or 8");
   if (N == 0) return DT_OK;
   DT_REQUIRE(x && out, "NULL raster");
-  if (is_f32) {
-    const float *d_x = hc.in((const float *)x, N);
-    float *d_o = hc.out((float *)out, N);
-    DT_TRY(hc.rc);
-    DT_TRY(dt_launched(dt_launch_minmax_scale_f32f32(hc.c->stream, d_x, N, (float)mn, (float)mx, (float)nodata, d_o)));
-  } else {
-    const double *d_x = hc.in((const double *)x, N);
-    double *d_o = hc.out((double *)out, N);
-    DT_TRY(hc.rc);
-    DT_TRY(dt_launched(dt_launch_minmax_scale_f64(hc.c->stream, d_x, N, mn, mx, nodata, d_o)));
-  }
+  const size_t bytes = (size_t)N * cell_bytes;
+  const uint8_t *d_x = hc.in((const uint8_t *)x, bytes);
+  uint8_t *d_o = hc.out((uint8_t *)out, bytes);
+  DT_TRY(hc.rc);
+  hipStream_t s = hc.c->stream;
+  DT_TRY(dt_launched(
+      cell_bytes == 2   ? dt_launch_minmax_scale_f16(s, d_x, N, (float)mn, (float)den, (float)nodata, d_o)
+      : cell_bytes == 4 ? dt_launch_minmax_scale_den_f32(s, (const float *)d_x, N, (float)mn, (float)den, (float)nodata,
+                                                         (float *)d_o)
+                        : dt_launch_minmax_scale_den_f64(s, (const double *)d_x, N, mn, den, nodata, (double *)d_o)));
   return hc.finish();
+}
+
+// mn and mx given in the raster's own type: the denominator is T(mx) - T(mn)
+extern "C" int dt_minmax_scale(const void *x, int is_f32, int64_t N, double mn, double mx, double nodata, void *out) {
+  if (is_f32) return dt_minmax_scale_den(x, 4, N, (float)mn, (double)((float)mx - (float)mn), nodata, out);
+  return dt_minmax_scale_den(x, 8, N, mn, mx - mn, nodata, out);
 }
 
 extern "C" int dt_binary_map(const void *desc, int is_f32, int64_t N, double nodata_value, double threshold, int under,

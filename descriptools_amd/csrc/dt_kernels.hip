@@ -1975,8 +1975,7 @@ int dt_launch_minmax_scale(hipStream_t s, const float *x, int64_t n, float mn, f
 // ===========================================================================================
 // evaluation.minMaxScale / binary_map / avaliacao as kernels (E1-E3, evaluation.py:5-9, 90-123, 126-171)
 // ===========================================================================================
-// minMaxScale in the arithmetic numpy would use for the raster's dtype (T = float for a float32 raster,
-// double for integer / float64 rasters): NaN where x == nodata or x is NaN, else (x - mn) / (mx - mn)
+// minMaxScale of a TI raster in T arithmetic: NaN where x == nodata or x is NaN, else (x - mn) / (mx - mn)
 template <typename TI, typename T>
 __global__ __launch_bounds__(256) void k_minmax_scale_t(const TI *__restrict__ x, int64_t n, T mn, T mx, T nodata,
                                                        T *__restrict__ out) {
@@ -1985,24 +1984,52 @@ __global__ __launch_bounds__(256) void k_minmax_scale_t(const TI *__restrict__ x
   T v = (T)x[i];
   out[i] = (v == nodata || v != v) ? (T)NAN : (v - mn) / (mx - mn);
 }
-int dt_launch_minmax_scale_f32f32(hipStream_t s, const float *x, int64_t n, float mn, float mx, float nodata,
-                                  float *out) {
-  if (n) hipLaunchKernelGGL((k_minmax_scale_t<float, float>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n,
-                            mn, mx, nodata, out);
-  return DT_OK;
-}
-int dt_launch_minmax_scale_f64(hipStream_t s, const double *x, int64_t n, double mn, double mx, double nodata,
-                               double *out) {
-  if (n) hipLaunchKernelGGL((k_minmax_scale_t<double, double>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x,
-                            n, mn, mx, nodata, out);
-  return DT_OK;
-}
 // float32 raster scaled in float64 (an integer-valued HAND kept as float32 on the device: numpy scales the
 // example's int16 HAND in float64)
 int dt_launch_minmax_scale_f32f64(hipStream_t s, const float *x, int64_t n, double mn, double mx, double nodata,
                                   double *out) {
   if (n) hipLaunchKernelGGL((k_minmax_scale_t<float, double>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x,
                             n, mn, mx, nodata, out);
+  return DT_OK;
+}
+
+// minMaxScale with the denominator given: numpy subtracts the two scalars from each other BEFORE they meet the raster
+// (mx - mn in the scalars' own arithmetic, then rounded to the raster's), which is not T(mx) - T(mn) in general
+template <typename T>
+__global__ __launch_bounds__(256) void k_minmax_scale_den(const T *__restrict__ x, int64_t n, T mn, T den, T nodata,
+                                                         T *__restrict__ out) {
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const T v = x[i];
+  out[i] = (v == nodata || v != v) ? (T)NAN : (v - mn) / den;
+}
+int dt_launch_minmax_scale_den_f32(hipStream_t s, const float *x, int64_t n, float mn, float den, float nodata,
+                                   float *out) {
+  if (n) hipLaunchKernelGGL(k_minmax_scale_den<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, mn, den,
+                            nodata, out);
+  return DT_OK;
+}
+int dt_launch_minmax_scale_den_f64(hipStream_t s, const double *x, int64_t n, double mn, double den, double nodata,
+                                   double *out) {
+  if (n) hipLaunchKernelGGL(k_minmax_scale_den<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, mn, den,
+                            nodata, out);
+  return DT_OK;
+}
+// float16 raster scaled in float16, as numpy scales it beside Python numbers: the difference and the quotient are each
+// rounded to float16.  Both are computed in float32 from float16 operands and then rounded, which is the correctly
+// rounded float16 result (24 >= 2 * 11 + 2 significand bits: the double rounding is innocuous).  mn and den = mx - mn
+// arrive as float16 values (the host rounds them the way numpy's weak scalars are).
+__global__ __launch_bounds__(256) void k_minmax_scale_h(const _Float16 *__restrict__ x, int64_t n, float mn, float den,
+                                                       float nodata, _Float16 *__restrict__ out) {
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float v = (float)x[i];
+  const _Float16 d = (_Float16)(v - mn);
+  out[i] = (v == nodata || v != v) ? (_Float16)NAN : (_Float16)((float)d / den);
+}
+int dt_launch_minmax_scale_f16(hipStream_t s, const void *x, int64_t n, float mn, float den, float nodata, void *out) {
+  if (n) hipLaunchKernelGGL(k_minmax_scale_h, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const _Float16 *)x, n,
+                            mn, den, nodata, (_Float16 *)out);
   return DT_OK;
 }
 

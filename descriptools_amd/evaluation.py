@@ -1,10 +1,11 @@
 """Flood-map evaluation -- replacement of descriptools/evaluation.py.
 
 Every raster-returning function is an H2D -> kernel -> D2H shim like the other modules: `minMaxScale`
-(k_minmax_scale_t), `binary_map` and `avaliacao` (k_classify).  `calibration` -- 61 x (binary_map + avaliacao) in
-the reference -- runs as 5 multi-threshold confusion-count passes over rasters uploaded once (k_confusion); counts
-are exact integers, so the returned threshold is identical.  The numpy dtype rules of the reference's expressions
-are kept at the boundary (which arithmetic a float32 / integer raster is scaled and compared in, int64 maps out,
+(k_minmax_scale_den, float16: k_minmax_scale_h), `binary_map` and `avaliacao` (k_classify).  `calibration` -- 61 x
+(binary_map + avaliacao) in the reference -- runs as 5 multi-threshold confusion-count passes over rasters uploaded
+once (k_confusion); counts are exact integers, so the returned threshold is identical.  The numpy dtype rules of the
+reference's expressions are kept at the boundary (which arithmetic a float16 / float32 / integer raster is scaled and
+compared in, Python numbers rounded to the raster's dtype as numpy's weak scalars are, int64 maps out,
 the in-place remap of the benchmark map)."""
 import numpy as np
 
@@ -14,31 +15,74 @@ from .device import Context
 
 
 def _float_view(mat, *scalars):
-    """(contiguous float array, is_f32): the float dtype numpy's expressions give a raster of this dtype when
-    combined with `scalars` -- float32 rasters stay float32 unless a float64 numpy scalar is involved (Python
-    numbers are weak), every other dtype is computed in float64."""
+    """(contiguous float array, its dtype): the float dtype numpy's expressions give a raster of this dtype when
+    combined with `scalars` -- float16 and float32 rasters keep their dtype beside Python numbers (which are weak)
+    and are promoted by numpy float scalars, every other dtype is computed in float64."""
     mat = np.asarray(mat)
-    base = np.float32 if mat.dtype in (np.float32, np.float16) else np.float64
+    base = mat.dtype if mat.dtype in (np.float16, np.float32) else np.float64
     rt = np.result_type(base, *scalars)
-    rt = np.float32 if rt == np.float32 else np.float64
-    return np.ascontiguousarray(mat, rt), rt == np.float32
+    rt = np.dtype(rt if rt in (np.float16, np.float32) else np.float64)
+    return np.ascontiguousarray(mat, rt), rt
+
+
+def _weak(value, raster_dtype, rt):
+    """the scalar as numpy compares it with a float raster computed in `rt`: rounded to the raster's dtype if it is a
+    Python number, promoted (compared exactly) if it is a numpy scalar -- NaN, which equals nothing, when the exact
+    comparison value is not a value of `rt`"""
+    if np.dtype(raster_dtype).kind != 'f':
+        return float(value)
+    with np.errstate(over='ignore'):
+        v = np.asarray(value).astype(np.result_type(raster_dtype, value))
+        return float(v) if float(v.astype(rt)) == float(v) or v != v else float('nan')
+
+
+def _float_dtype(*args):
+    rt = np.result_type(*args)
+    return np.dtype(rt if rt in (np.float16, np.float32) else np.float64)
+
+
+def _scale_call(x, mn, den, nodata):
+    out = np.empty_like(x)
+    check(_lib.lib().dt_minmax_scale_den(x.ctypes.data_as(C.c_void_p), x.dtype.itemsize, x.size, mn, den, nodata,
+                                         out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def minMaxScale(mat, mn, mx, nodata):
-    """evaluation.py:5-9 on the GPU: NaN where mat == nodata (or mat is NaN), (mat - mn) / (mx - mn) elsewhere."""
-    x, is_f32 = _float_view(mat, mn, mx)
-    out = np.empty_like(x)
-    check(_lib.lib().dt_minmax_scale(x.ctypes.data_as(C.c_void_p), int(is_f32), x.size, float(mn), float(mx),
-                                     float(nodata), out.ctypes.data_as(C.c_void_p)))
-    return out
+    """evaluation.py:5-9 on the GPU: NaN where mat == nodata (or mat is NaN), (mat - mn) / (mx - mn) elsewhere, in
+    numpy's dtypes: the difference in the dtype the raster and mn give, the denominator subtracted between the scalars
+    themselves and then rounded to the result's dtype, float16 rasters scaled in float16 beside Python numbers."""
+    mat = np.asarray(mat)
+    with np.errstate(over='ignore', invalid='ignore'):
+        den = mx - mn
+        dt_diff = _float_dtype(mat.dtype if mat.dtype.kind == 'f' else np.float64, mn)
+        rt = _float_dtype(dt_diff, den)
+        mn_v, den_v = float(np.asarray(mn).astype(dt_diff)), float(np.asarray(den).astype(rt))
+    x = np.ascontiguousarray(mat, dt_diff)
+    nod = _weak(nodata, mat.dtype, dt_diff)
+    if dt_diff == rt:
+        return _scale_call(x, mn_v, den_v, nod)
+    # the difference is rounded in its own dtype and widened for the division: (x - mn) / 1, then (d - 0) / den, exact
+    return _scale_call(_scale_call(x, mn_v, 1.0, nod).astype(rt), 0.0, den_v, float('nan'))
+
+
+def _compare_view(descriptor_matrix, threshold):
+    """(contiguous float32 / float64 raster, is_f32, threshold) for the comparison kernels: a float16 raster is compared
+    on its exactly widened float32 values with the threshold numpy would use -- rounded to float16 when it is a Python
+    number"""
+    desc, rt = _float_view(descriptor_matrix, threshold)
+    if rt == np.float16:
+        with np.errstate(over='ignore'):
+            return desc.astype(np.float32), True, float(np.float16(threshold))
+    return desc, rt == np.float32, float(threshold)
 
 
 def binary_map(descriptor_matrix, threshold, under):
     """evaluation.py:90-123 on the GPU; int64 map out; the value at [0, 0] counts as nodata (:111)."""
-    desc, is_f32 = _float_view(descriptor_matrix, threshold)
+    desc, is_f32, threshold = _compare_view(descriptor_matrix, threshold)
     first = float(desc.reshape(-1)[0]) if desc.size else 0.0
     out = np.empty(desc.shape, np.uint8)
-    check(_lib.lib().dt_binary_map(desc.ctypes.data_as(C.c_void_p), int(is_f32), desc.size, first, float(threshold),
+    check(_lib.lib().dt_binary_map(desc.ctypes.data_as(C.c_void_p), int(is_f32), desc.size, first, threshold,
                                    1 if under == 'under' else 0, ptr(out, c_u8p)))
     return out.astype(np.int64)
 
@@ -59,7 +103,9 @@ def fit(count):
 def avaliacao(descriptor_flood_map, comparison_flood_map):
     """evaluation.py:126-171 on the GPU.  Like the reference it rewrites comparison_flood_map in place
     (1 -> 2, -100 -> 0: the kernel's remapped copy is written back into the caller's array); returns
-    (correctness, fit, class map = descriptor map + remapped benchmark map)."""
+    (correctness, fit, class map = descriptor map + remapped benchmark map).  The classes are counted by value
+    (cells whose sum is 0, 1, 2, 3); the reference counts by position in np.unique's output, which is undefined on maps
+    whose sums leave 0..3 (a benchmark value other than -100, 0, 1), so only the class map is comparable there."""
     b32 = np.ascontiguousarray(descriptor_flood_map, np.int32)
     cmp8 = np.ascontiguousarray(comparison_flood_map, np.int8)
     klass = np.empty(b32.shape, np.int32)
@@ -78,7 +124,8 @@ class _Calibrator:
 
     def __init__(self, descriptor_matrix, comparison_matrix, under):
         desc = np.asarray(descriptor_matrix)
-        self.f32 = desc.dtype == np.float32
+        # numpy compares a float32 / float16 raster with a Python float in the raster's dtype
+        self.round_to = desc.dtype.type if desc.dtype in (np.float16, np.float32) else None
         self.nodata = float(desc.reshape(-1)[0]) if desc.size else 0.0
         d64 = np.ascontiguousarray(desc, np.float64)
         cmp8 = np.ascontiguousarray(comparison_matrix, np.int8)
@@ -91,8 +138,8 @@ class _Calibrator:
 
     def fits(self, thresholds):
         th = np.asarray(thresholds, np.float64)
-        if self.f32:  # numpy compares a float32 raster with a Python float in float32
-            th = th.astype(np.float32).astype(np.float64)
+        if self.round_to is not None:
+            th = th.astype(self.round_to).astype(np.float64)
         th = np.ascontiguousarray(th)
         check(_lib.lib().dt_dev_confusion_multi(self.ctx.h, self.d_desc.ptr, self.d_cmp.ptr, self.n,
                                                 self.nodata, ptr(th, c_f64p), len(th), self.under,
@@ -152,12 +199,15 @@ def calibration(descriptor_matrix, comparison_matrix, under):
 
 def combine_extremes(per_rank):
     """np.unique extremes of a raster split over ranks from each rank's (smallest, second-smallest
-    distinct, largest): the global second-smallest is the smallest candidate above the global minimum."""
+    distinct, largest): the global second-smallest is the smallest candidate above the global minimum.  NaN cells are
+    no values (dt_dev_unique_extremes_f32 skips them): a rank's slot is NaN when it has no such value, and so is the
+    result's."""
     a = np.asarray(per_rank, np.float64).reshape(-1, 3)
+    if np.isnan(a[:, 0]).all():  # no rank holds a value
+        return np.full(3, np.nan, np.float32)
     lo = np.nanmin(a[:, 0])
     cand = np.where(a[:, 0] > lo, a[:, 0], a[:, 1])
-    return np.array([lo, np.nanmin(cand) if np.isfinite(cand).any() else np.nan, np.nanmax(a[:, 2])],
-                    np.float32)
+    return np.array([lo, np.nan if np.isnan(cand).all() else np.nanmin(cand), np.nanmax(a[:, 2])], np.float32)
 
 
 def evaluate_resident(ctx, x_ptr, flood_ptr, n, under='under', nodata=-100.0, desc_ptr=None,

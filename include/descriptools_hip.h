@@ -394,6 +394,11 @@ int dt_confusion_multi(const double *desc, const int8_t *flood, int64_t N, doubl
 /* evaluation.minMaxScale (evaluation.py:5-9): out = NaN where x == nodata or x is NaN, else (x - mn) / (mx - mn),
  * in float32 for a float32 raster (is_f32) and float64 otherwise -- numpy's arithmetic for those dtypes. */
 int dt_minmax_scale(const void *x, int is_f32, int64_t N, double mn, double mx, double nodata, void *out);
+/* the same with the denominator den = mx - mn given, in the raster's own float type (cell_bytes 2 / 4 / 8: float16 /
+ * float32 / float64 in and out): numpy subtracts the two scalars from each other before they meet the raster, so the
+ * denominator is not T(mx) - T(mn) in general.  A float16 raster is scaled as numpy scales it: the difference and the
+ * quotient are each rounded to float16. */
+int dt_minmax_scale_den(const void *x, int cell_bytes, int64_t N, double mn, double den, double nodata, void *out);
 /* evaluation.binary_map (evaluation.py:90-123): binary = 1 where desc <= threshold ('under') or >= threshold,
  * 0 elsewhere, where desc is NaN and where desc == nodata_value (the caller passes desc[0, 0], :111). */
 int dt_binary_map(const void *desc, int is_f32, int64_t N, double nodata_value, double threshold, int under,

@@ -371,6 +371,137 @@ def case_eval():
     save("eval", **res)
 
 
+def save_stable(name, **arrs):
+    """save() whose file does not depend on the day it is written: np.savez stamps every member with the current
+    time, this writes the same members with a fixed date, in the order given"""
+    import zipfile
+    path = os.path.join(GOLD, name + ".npz")
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key, val in arrs.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w") as fid:
+                np.lib.format.write_array(fid, np.asanyarray(val), allow_pickle=False)
+    print("  wrote %s (%.1f KB)" % (path, os.path.getsize(path) / 1024), flush=True)
+
+
+def case_eval_edge():
+    """G-eval-edge: evaluation.py at the edges eval.npz leaves out -- float32 / float64 / float16 descriptors, a
+    valid first cell shared with many cells, 'over' on a descriptor with negative values, thresholds that hit data
+    values exactly, every coarse winner, a first-stage tie, a benchmark map without a flooded cell."""
+    print("eval_edge", flush=True)
+    res, names = {}, []
+
+    def fit_at(desc, flood, th, under):
+        return R_eval.avaliacao(R_eval.binary_map(desc, th, under), flood.copy())[1]
+
+    def run(key, raw, flood, under, coarse=None, full=True):
+        el = np.unique(raw[raw == raw])
+        mn, mx = el[1], el[-1]
+        desc = R_eval.minMaxScale(raw, mn, mx, -100)
+        assert desc.dtype == (raw.dtype if raw.dtype.kind == "f" else np.float64)
+        res.update({key + "_raw": raw, key + "_flood": flood, key + "_under": under, key + "_mn": mn, key + "_mx": mx,
+                    key + "_desc": desc})
+        names.append(key)
+        try:
+            th = R_eval.calibration(desc, flood.copy(), under)
+        except Exception as e:  # the reference's own failure is the recorded result
+            res[key + "_error"] = type(e).__name__
+            print("   %-6s %s %s: raises %s" % (key, raw.dtype, under, type(e).__name__), flush=True)
+            return desc, None
+        f3 = [fit_at(desc, flood, t, under) for t in (0.25, 0.5, 0.75)]
+        won = (75 if f3[2] > f3[0] else 25) if f3[2] > f3[1] else (50 if f3[1] > f3[0] else 25)
+        assert coarse is None or won == coarse, (key, won, f3)
+        binary = R_eval.binary_map(desc, th, under)
+        fl2 = flood.copy()
+        c, f, cm = R_eval.avaliacao(binary, fl2)
+        counts = np.bincount(cm.reshape(-1).astype(np.int64), minlength=4)
+        assert len(counts) == 4 and (counts.min() > 0 or not full), (key, counts)
+        res.update({key + "_th": th, key + "_coarse": won, key + "_binary": binary.astype(np.int8), key + "_c": c,
+                    key + "_f": f, key + "_class": cm.astype(np.int8), key + "_counts": counts,
+                    key + "_flood_after": fl2})
+        print("   %-6s %s %s: coarse %d th %r counts %s" % (key, raw.dtype, under, won, th, counts.tolist()), flush=True)
+        return desc, th
+
+    def bench(rng, wet, noise=0.03, holes=0.05):
+        flood = (wet ^ (rng.random(wet.shape) < noise)).astype(np.int8)
+        flood[rng.random(wet.shape) < holes] = -100
+        return flood
+
+    def heights(rng, shape, lo, hi, dtype, nan=0.02):
+        raw = (lo + (hi - lo) * rng.random(shape)).astype(dtype)
+        raw[rng.random(shape) < 0.05] = -100
+        raw[rng.random(shape) < nan] = np.nan
+        raw[0, 0] = -100
+        raw[0, 1], raw[0, 2] = lo, hi  # the extremes are what the scaling says they are
+        return raw
+
+    def scaled(raw):
+        v = raw[(raw == raw) & (raw != -100)].astype(np.float64)
+        return (raw.astype(np.float64) - v.min()) / (v.max() - v.min())
+
+    # float32 continuous, 'under', best fit near 0.5
+    rng = np.random.default_rng(11)
+    raw = heights(rng, (40, 48), 0.0, 37.5, np.float32)
+    run("f32", raw, bench(rng, scaled(raw) <= 0.52), "under", coarse=50)
+    # float64 continuous, 'under', best fit near 0.12
+    rng = np.random.default_rng(12)
+    raw = heights(rng, (24, 40), 0.0, 211.0, np.float64)
+    run("f64", raw, bench(rng, scaled(raw) <= 0.12), "under", coarse=25)
+    # float16: the reference scales and compares in float16 (thresholds rounded to float16)
+    rng = np.random.default_rng(13)
+    raw = heights(rng, (48, 64), 0.0, 50.0, np.float16)
+    desc, th = run("f16", raw, bench(rng, scaled(raw) <= 0.3), "under", coarse=25)
+    assert desc.dtype == np.float16
+    wide = R_eval.binary_map(desc.astype(np.float32), th, "under")
+    assert (wide != res["f16_binary"]).any(), "float16 case: the float32 comparison must give another map"
+    # river corner: int16 HAND whose first cell is a river cell (0), like a third of the raster
+    rng = np.random.default_rng(14)
+    raw = rng.integers(0, 90, size=(64, 96)).astype(np.int16)
+    raw[rng.random(raw.shape) < 0.3] = 0
+    raw[rng.random(raw.shape) < 0.05] = -100
+    raw[0, 0] = 0
+    desc, th = run("river", raw, bench(rng, raw <= 20, holes=0.0), "under")
+    assert desc[0, 0] == 0.0 and (desc == 0.0).sum() > 1000 and res["river_binary"][raw == 0].sum() == 0
+    # 'over' on a descriptor that grows with flooding and holds negative values (GFI-like), best fit near 0.8
+    rng = np.random.default_rng(15)
+    raw = heights(rng, (40, 48), -8.0, 6.0, np.float32)
+    run("over", raw, bench(rng, scaled(raw) >= 0.8), "over", coarse=75)
+    # quantised to k/100: every stage compares cells with thresholds they equal exactly
+    rng = np.random.default_rng(16)
+    raw = rng.integers(0, 101, size=(64, 96)).astype(np.int16)
+    raw[rng.random(raw.shape) < 0.05] = -100
+    raw[0, 0], raw[0, 1], raw[0, 2] = -100, 0, 100
+    desc, th = run("quant", raw, bench(rng, (raw >= 0) & (raw <= 43)), "under", coarse=50)
+    assert (desc == th).sum() > 10 and all((desc == t).sum() > 10 for t in (0.25, 0.5, 0.75, 0.4, 0.43))
+    # first-stage tie: no cell between 0.45 and 0.65, so 0.50 and 0.60 fit equally and '>=' moves on to 0.60
+    rng = np.random.default_rng(17)
+    raw = heights(rng, (40, 48), 0.0, 100.0, np.float32)
+    gap = (raw > 45.0) & (raw < 65.0)
+    raw[gap] = (raw[gap] + 25.0).astype(np.float32)
+    desc, th = run("tie", raw, bench(rng, scaled(raw) <= 0.55), "under", coarse=50)
+    assert fit_at(desc, res["tie_flood"], 0.5, "under") == fit_at(desc, res["tie_flood"], 0.6, "under") and th >= 0.6
+    # a benchmark map without a flooded cell.  The fit is 0 / (false alarms): 0.0 wherever the descriptor floods a
+    # cell, so the search runs through (the first stage's '>=' walks to its last candidate) ...
+    rng = np.random.default_rng(18)
+    raw = heights(rng, (24, 40), 0.0, 20.0, np.float32, nan=0.0)
+    flood = np.zeros(raw.shape, np.int8)
+    flood[rng.random(raw.shape) < 0.05] = -100
+    run("dry", raw, flood, "under", full=False)
+    assert "dry_error" not in res and res["dry_c"] != res["dry_c"] and res["dry_f"] == 0.0
+    # ... and 0 / 0 = NaN only where the descriptor floods nothing either: 'over' on a raster whose only cell above
+    # 0.04 is the first cell, which counts as nodata -- every fit is NaN and the reference's search has no threshold
+    raw = (rng.random((24, 40)) * 4.0).astype(np.float32)
+    raw[0, 0], raw[0, 1] = 100.0, 0.0
+    raw[rng.random(raw.shape) < 0.05] = -100
+    run("drynan", raw, flood, "over")
+    assert res["drynan_error"] == "UnboundLocalError"
+    assert {res[k + "_coarse"] for k in names if k + "_coarse" in res} == {25, 50, 75}
+    res["names"] = np.array(names)
+    save_stable("eval_edge", **res)
+
+
 def case_example_full():
     """The reference's only known-answer test: HAND -> minMaxScale -> calibration -> binary_map ->
     avaliacao must reproduce Example/output/hand_class.tif (example.py:82-147).  ~5 min."""
@@ -654,7 +785,7 @@ def case_params(rasters=True):
 
 
 CASES = {"params": case_params, "params_hard": lambda: case_params(False), "f64": case_f64, "nonfinite": case_nonfinite, "nonfinite_f64": case_nonfinite_f64,"shims": case_shims, "example_descriptors": case_example_descriptors, "synth": case_synth, "example_windows": case_example_windows, "edge": case_edge,
-         "eval": case_eval, "example_full": case_example_full}
+         "eval": case_eval, "eval_edge": case_eval_edge, "example_full": case_example_full}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or ["edge", "eval", "synth", "example_windows"]
