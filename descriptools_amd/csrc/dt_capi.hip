@@ -408,7 +408,7 @@ struct DevCall {
   DT_TRY(d.rc)
 
 // Not on the scaffold, because they enqueue no kernel and would get no shorter: dt_dev_malloc, dt_dev_free, the copies,
-// dt_dev_downslope_queued, dt_dev_dinf_accumulate_info, dt_dev_mfd_accumulate_info, dt_dev_membench_mix_timed and
+// dt_dev_downslope_queued, the two *_accumulate_info entries (dev_countdown_info), dt_dev_membench_mix_timed and
 // dt_dev_mem_info.
 extern "C" int dt_dev_malloc(dt_ctx *c, int64_t bytes, void **out) {
   DT_CTX(c);
@@ -638,62 +638,90 @@ extern "C" int dt_dev_dinf_direction(dt_ctx *c, const float *dem, const uint8_t 
   return d.done(dt_launch_dinf_direction(c->stream, dem, fdr, H, W, px, angle, slope));
 }
 
-// the per-lane stack of k_di_flow: dt_debug_set(DT_DBG_DINF_STACK, n), else the environment variable of that name
-static int dt_dinf_stack_cap() {
-  const int v = dt_debug_get(DT_DBG_DINF_STACK);
+// ---- countdown accumulations (D-infinity, MFD; dt_countdown.h) ----
+// A stack-cap knob (the launchers' stack_cap): dt_debug_set(KEY, n) when the knob has a key (KEY >= 0) and it is set,
+// else the environment variable `name`, read once
+template <int KEY>
+static int dt_stack_cap(const char *name) {
+  const int v = KEY >= 0 ? dt_debug_get(KEY) : 0;
   if (v != 0) return v;
   static int env = -1;
   if (env < 0) {
-    const char *e = getenv("DT_DBG_DINF_STACK");
+    const char *e = getenv(name);
     env = e ? atoi(e) : 0;
     if (env < 0) env = 0;
   }
   return env;
 }
-#define DT_DINF_ROUNDS_MAX 4096
-extern "C" int dt_dev_dinf_accumulate(dt_ctx *c, const float *angle, const double *w, int64_t H, int64_t W,
-                                      int frac_bits, int rounds, double *acc) {
-  DT_DEV(d, c, H, W, 1.0);
-  DT_REQUIRE((angle && acc) || H * W == 0, "NULL raster");
-  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
-  DT_REQUIRE(rounds != 0 && rounds >= -DT_DINF_ROUNDS_MAX && rounds <= DT_DINF_ROUNDS_MAX,
-             "rounds must lie in [1, 4096] (or [-4096, -1] to continue)");
-  if (H * W == 0) return DT_OK;
-  const size_t need = dt_dinf_accumulate_scratch(H, W);
-  if (rounds > 0) {
-    void *scr = d.scratch(need);
-    DT_TRY(d.rc);
-    DT_TRY(dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, 1, rounds - 1, 1, dt_dinf_stack_cap(), scr,
-                                     need, acc, c->status));
-    dt_scratch_claim(c, DT_OWNER_DINF, H, W, scr, nullptr, angle, w, frac_bits);
-    return d.done();
-  }
-  const DtScratchClaim *k;
-  DT_TRY(dt_scratch_claimed(c, DT_OWNER_DINF, &d.w, false,
-                            "dt_dev_dinf_accumulate cannot continue: no accumulation of this shape was started on this "
-                            "context (or another call has used the context's scratch in between)", &k));
-  DT_REQUIRE(k->in[0] == angle && k->in[1] == w && k->frac_bits == frac_bits,
-             "dt_dev_dinf_accumulate continues with another angle raster, weight raster or frac_bits than it was "
-             "started with");
-  return d.done(dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, 0, -rounds, 1, dt_dinf_stack_cap(), k->ptr,
-                                          need, acc, c->status));
-}
-
-extern "C" int dt_dev_dinf_accumulate_info(dt_ctx *c, int64_t *info4) {
-  DT_CTX(c);
-  DT_REQUIRE(info4 != nullptr, "info4 is NULL");
-  const DtScratchClaim *k;
-  DT_TRY(dt_scratch_claimed(c, DT_OWNER_DINF, nullptr, false,
-                            "no D-infinity accumulation on this context (or another call has used the context's scratch "
-                            "since)", &k));
-  uint32_t ctl[8];
-  DT_HIP(hipMemcpyAsync(ctl, dt_dinf_accumulate_ctl(k->ptr, k->h, k->w), sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-  DT_HIP(hipStreamSynchronize(c->stream));
+static int dt_dinf_stack_cap() { return dt_stack_cap<DT_DBG_DINF_STACK>("DT_DBG_DINF_STACK"); }
+static int dt_mfd_stack_cap() { return dt_stack_cap<-1>("DT_DBG_MFD_STACK"); }
+// info4 of the control words: queue rounds that found work, the largest window, queued, cells with >= 2 receivers
+static void dt_countdown_info4(const uint32_t *ctl, int64_t *info4) {
   info4[0] = ctl[3];
   info4[1] = ctl[4];
   info4[2] = ctl[0];
   info4[3] = ctl[5];
+}
+
+// Start (rounds > 0: round 0 and rounds - 1 queue rounds) or continue (rounds < 0: -rounds queue rounds) an
+// accumulation on the rasters `in` (an `raster` raster, in the messages of `entry`) and w, each time with the out step.
+// launch(start, rounds, scr, need) is the op's launcher on them, `scratch` its size function.
+#define DT_DINF_ROUNDS_MAX 4096
+template <typename Launch>
+static int dev_countdown(dt_ctx *c, DtScratchOwner owner, const char *entry, const char *raster, const void *in,
+                         const double *w, int64_t H, int64_t W, int frac_bits, int rounds, double *acc,
+                         size_t (*scratch)(int64_t, int64_t), Launch launch) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_REQUIRE((in && acc) || H * W == 0, "NULL raster");
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  DT_REQUIRE(rounds != 0 && rounds >= -DT_DINF_ROUNDS_MAX && rounds <= DT_DINF_ROUNDS_MAX,
+             "rounds must lie in [1, 4096] (or [-4096, -1] to continue)");
+  if (H * W == 0) return DT_OK;
+  const size_t need = scratch(H, W);
+  if (rounds > 0) {
+    void *scr = d.scratch(need);
+    DT_TRY(d.rc);
+    DT_TRY(launch(1, rounds - 1, scr, need));
+    dt_scratch_claim(c, owner, H, W, scr, nullptr, in, w, frac_bits);
+    return d.done();
+  }
+  char msg[256];
+  const DtScratchClaim *k;
+  snprintf(msg, sizeof(msg), "%s cannot continue: no accumulation of this shape was started on this context (or "
+           "another call has used the context's scratch in between)", entry);
+  DT_TRY(dt_scratch_claimed(c, owner, &d.w, false, msg, &k));
+  snprintf(msg, sizeof(msg), "%s continues with another %s raster, weight raster or frac_bits than it was started with",
+           entry, raster);
+  DT_REQUIRE(k->in[0] == in && k->in[1] == w && k->frac_bits == frac_bits, msg);
+  return d.done(launch(0, -rounds, k->ptr, need));
+}
+// info4 of the `name` accumulation last enqueued on the context, from its control words (synchronises)
+static int dev_countdown_info(dt_ctx *c, DtScratchOwner owner, const char *name,
+                              const uint32_t *(*ctl_of)(void *, int64_t, int64_t), int64_t *info4) {
+  DT_CTX(c);
+  DT_REQUIRE(info4 != nullptr, "info4 is NULL");
+  char msg[128];
+  const DtScratchClaim *k;
+  snprintf(msg, sizeof(msg), "no %s accumulation on this context (or another call has used the context's scratch "
+           "since)", name);
+  DT_TRY(dt_scratch_claimed(c, owner, nullptr, false, msg, &k));
+  uint32_t ctl[8];
+  DT_HIP(hipMemcpyAsync(ctl, ctl_of(k->ptr, k->h, k->w), sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+  DT_HIP(hipStreamSynchronize(c->stream));
+  dt_countdown_info4(ctl, info4);
   return DT_OK;
+}
+
+extern "C" int dt_dev_dinf_accumulate(dt_ctx *c, const float *angle, const double *w, int64_t H, int64_t W,
+                                      int frac_bits, int rounds, double *acc) {
+  return dev_countdown(c, DT_OWNER_DINF, "dt_dev_dinf_accumulate", "angle", angle, w, H, W, frac_bits, rounds, acc,
+                       dt_dinf_accumulate_scratch, [&](int start, int n, void *scr, size_t need) {
+                         return dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, start, n, 1,
+                                                          dt_dinf_stack_cap(), scr, need, acc, c->status);
+                       });
+}
+extern "C" int dt_dev_dinf_accumulate_info(dt_ctx *c, int64_t *info4) {
+  return dev_countdown_info(c, DT_OWNER_DINF, "D-infinity", dt_dinf_accumulate_ctl, info4);
 }
 
 static int dt_check_mfd_exponent(double exponent) {
@@ -711,46 +739,14 @@ extern "C" int dt_dev_mfd_shares(dt_ctx *c, const float *dem, const uint8_t *fdr
 
 extern "C" int dt_dev_mfd_accumulate(dt_ctx *c, const uint16_t *shares, const double *w, int64_t H, int64_t W,
                                      int frac_bits, int rounds, double *acc) {
-  DT_DEV(d, c, H, W, 1.0);
-  DT_REQUIRE((shares && acc) || H * W == 0, "NULL raster");
-  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
-  DT_REQUIRE(rounds != 0 && rounds >= -DT_DINF_ROUNDS_MAX && rounds <= DT_DINF_ROUNDS_MAX,
-             "rounds must lie in [1, 4096] (or [-4096, -1] to continue)");
-  if (H * W == 0) return DT_OK;
-  const size_t need = dt_mfd_accumulate_scratch(H, W);
-  if (rounds > 0) {
-    void *scr = d.scratch(need);
-    DT_TRY(d.rc);
-    DT_TRY(dt_launch_mfd_accumulate(c->stream, shares, w, H, W, frac_bits, 1, rounds - 1, 1, scr, need, acc, c->status));
-    dt_scratch_claim(c, DT_OWNER_MFD, H, W, scr, nullptr, shares, w, frac_bits);
-    return d.done();
-  }
-  const DtScratchClaim *k;
-  DT_TRY(dt_scratch_claimed(c, DT_OWNER_MFD, &d.w, false,
-                            "dt_dev_mfd_accumulate cannot continue: no accumulation of this shape was started on this "
-                            "context (or another call has used the context's scratch in between)", &k));
-  DT_REQUIRE(k->in[0] == shares && k->in[1] == w && k->frac_bits == frac_bits,
-             "dt_dev_mfd_accumulate continues with another share raster, weight raster or frac_bits than it was "
-             "started with");
-  return d.done(dt_launch_mfd_accumulate(c->stream, shares, w, H, W, frac_bits, 0, -rounds, 1, k->ptr, need, acc,
-                                         c->status));
+  return dev_countdown(c, DT_OWNER_MFD, "dt_dev_mfd_accumulate", "share", shares, w, H, W, frac_bits, rounds, acc,
+                       dt_mfd_accumulate_scratch, [&](int start, int n, void *scr, size_t need) {
+                         return dt_launch_mfd_accumulate(c->stream, shares, w, H, W, frac_bits, start, n, 1,
+                                                         dt_mfd_stack_cap(), scr, need, acc, c->status);
+                       });
 }
-
 extern "C" int dt_dev_mfd_accumulate_info(dt_ctx *c, int64_t *info4) {
-  DT_CTX(c);
-  DT_REQUIRE(info4 != nullptr, "info4 is NULL");
-  const DtScratchClaim *k;
-  DT_TRY(dt_scratch_claimed(c, DT_OWNER_MFD, nullptr, false,
-                            "no MFD accumulation on this context (or another call has used the context's scratch since)",
-                            &k));
-  uint32_t ctl[8];
-  DT_HIP(hipMemcpyAsync(ctl, dt_mfd_accumulate_ctl(k->ptr, k->h, k->w), sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-  DT_HIP(hipStreamSynchronize(c->stream));
-  info4[0] = ctl[3];
-  info4[1] = ctl[4];
-  info4[2] = ctl[0];
-  info4[3] = ctl[5];
-  return DT_OK;
+  return dev_countdown_info(c, DT_OWNER_MFD, "MFD", dt_mfd_accumulate_ctl, info4);
 }
 
 // reaches: reach ids and flat indices travel in 31 bits
@@ -2066,8 +2062,26 @@ extern "C" int dt_dinf_direction(const float *dem, const uint8_t *fdr, int64_t H
   return hc.finish();
 }
 
-// queue rounds between two looks at the queue
+// The rounds of a countdown accumulation on the host tier: round 0, then batches of DT_DINF_BATCH queue rounds until a
+// look at the control words (d_ctl) finds everything queued drained, then the out step.  launch(start, rounds, finish)
+// is the op's launcher on the call's rasters.  *st: the status bits this call raised; info4: dt_countdown_info4's.
 #define DT_DINF_BATCH 32
+template <typename Launch>
+static int host_countdown(HostCall &hc, const uint32_t *d_ctl, int32_t *st, int64_t *info4, Launch launch) {
+  DT_TRY(dt_ctx_status(hc.c, st));  // this call's status only
+  uint32_t ctl[8] = {0};
+  for (int start = 1;; start = 0) {
+    DT_TRY(launch(start, DT_DINF_BATCH, 0));
+    DT_TRY(hc.download(ctl, d_ctl, 8));
+    DT_HIP(hipStreamSynchronize(hc.c->stream));
+    if (ctl[0] == ctl[2]) break;  // everything queued has been drained
+  }
+  DT_TRY(dt_launched(launch(0, 0, 1)));
+  DT_TRY(dt_ctx_status(hc.c, st));
+  dt_countdown_info4(ctl, info4);
+  return DT_OK;
+}
+
 extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H, int64_t W, int frac_bits,
                                   double *acc, int64_t *info4) {
   HostCall hc;
@@ -2085,27 +2099,15 @@ extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H
   char *scr = hc.scratch<char>(need);
   DT_TRY(hc.rc);
   int32_t st = 0;
-  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  int64_t got[4];
   const int cap = dt_dinf_stack_cap();
-  uint32_t ctl[8] = {0};
-  for (int start = 1;; start = 0) {
-    DT_TRY(dt_launch_dinf_accumulate(hc.c->stream, d_a, d_w, H, W, frac_bits, start, DT_DINF_BATCH, 0, cap, scr, need,
-                                     d_o, hc.c->status));
-    DT_TRY(hc.download(ctl, dt_dinf_accumulate_ctl(scr, H, W), 8));
-    DT_HIP(hipStreamSynchronize(hc.c->stream));
-    if (ctl[0] == ctl[2]) break;  // everything queued has been drained
-  }
-  DT_TRY(dt_launched(dt_launch_dinf_accumulate(hc.c->stream, d_a, d_w, H, W, frac_bits, 0, 0, 1, cap, scr, need, d_o,
-                                               hc.c->status)));
-  DT_TRY(dt_ctx_status(hc.c, &st));
+  DT_TRY(host_countdown(hc, dt_dinf_accumulate_ctl(scr, H, W), &st, got, [&](int start, int rounds, int finish) {
+    return dt_launch_dinf_accumulate(hc.c->stream, d_a, d_w, H, W, frac_bits, start, rounds, finish, cap, scr, need,
+                                     d_o, hc.c->status);
+  }));
   DT_REQUIRE(!(st & DT_STATUS_BAD_ANGLE), "an angle is neither -1, -100 nor in [0, float32(2 pi)]");
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
-  if (info4) {
-    info4[0] = ctl[3];
-    info4[1] = ctl[4];
-    info4[2] = ctl[0];
-    info4[3] = ctl[5];
-  }
+  if (info4) memcpy(info4, got, sizeof(got));
   return hc.finish();
 }
 
@@ -2143,27 +2145,16 @@ extern "C" int dt_mfd_accumulate(const uint16_t *shares, const double *w, int64_
   char *scr = hc.scratch<char>(need);
   DT_TRY(hc.rc);
   int32_t st = 0;
-  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
-  uint32_t ctl[8] = {0};
-  for (int start = 1;; start = 0) {
-    DT_TRY(dt_launch_mfd_accumulate(hc.c->stream, d_s, d_w, H, W, frac_bits, start, DT_DINF_BATCH, 0, scr, need, d_o,
-                                    hc.c->status));
-    DT_TRY(hc.download(ctl, dt_mfd_accumulate_ctl(scr, H, W), 8));
-    DT_HIP(hipStreamSynchronize(hc.c->stream));
-    if (ctl[0] == ctl[2]) break;  // everything queued has been drained
-  }
-  DT_TRY(dt_launched(dt_launch_mfd_accumulate(hc.c->stream, d_s, d_w, H, W, frac_bits, 0, 0, 1, scr, need, d_o,
-                                              hc.c->status)));
-  DT_TRY(dt_ctx_status(hc.c, &st));
+  int64_t got[4];
+  const int cap = dt_mfd_stack_cap();
+  DT_TRY(host_countdown(hc, dt_mfd_accumulate_ctl(scr, H, W), &st, got, [&](int start, int rounds, int finish) {
+    return dt_launch_mfd_accumulate(hc.c->stream, d_s, d_w, H, W, frac_bits, start, rounds, finish, cap, scr, need, d_o,
+                                    hc.c->status);
+  }));
   DT_REQUIRE(!(st & DT_STATUS_BAD_SHARES),
              "a share word is not eight 0xFFFF and has a slot above 32768 or a sum that is neither 0 nor 32768");
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
-  if (info4) {
-    info4[0] = ctl[3];
-    info4[1] = ctl[4];
-    info4[2] = ctl[0];
-    info4[3] = ctl[5];
-  }
+  if (info4) memcpy(info4, got, sizeof(got));
   return hc.finish();
 }
 

@@ -1,0 +1,121 @@
+// dt_countdown.h -- the in-degree countdown on a drainage DAG that D-infinity (dt_dinf.hip, out-degree <= 2) and MFD
+// (dt_mfd.hip, out-degree <= 8) accumulate with: the state word, the control words, the workspace, the mark and out
+// steps and the host sequence.  What differs between the ops stays in their files: how a cell's in-degree is gathered
+// (the init kernel), how a complete cell splits its total and what a lane does with the cells it completes (the flow
+// kernel).
+//
+// One 64-bit word per cell is the whole state,
+//   bits 0-55 sum (q, then q + what has arrived) | 56-59 pending donors | 60 source | 61, 62 the op's own flags
+// (the pointer doubling of the tile passes carries a tree, not a DAG, so it cannot be used here).
+// init   gathers each cell's in-degree from its eight neighbours (no atomics), quantises the weight (cd_quant) and
+//        writes the word; a cell without donors is a source.
+// flow   a lane that owns a complete cell (pending 0) splits its total T among the receivers and adds m - 2^56 to each
+//        receiver's word with one returning 64-bit atomic: sum and countdown move together, the arrival that finds
+//        pending == 1 in the value it gets back holds the receiver's complete total, and no fence is needed (the word
+//        is the only thing handed over).  That lane carries on from a receiver it completed and keeps the others in LDS;
+//        what LDS cannot hold goes on a global queue.  Round 0 starts from the sources (a scan of the raster); every
+//        later round drains what the rounds before put on the queue: k_cd_mark moves the window [lo, hi) to the entries
+//        written before it ran, and a round whose window is empty returns at once.  A start (a source, a queue entry)
+//        completes a bounded number of cells in a round and then queues what it holds: a round lasts as long as its
+//        longest walk, and bounded walks keep the rounds short and the queued work moving.  No lane waits for another,
+//        and every loop is bounded by its trip count.  A cell is queued only when it is complete and not yet sent on,
+//        which happens once: a queue of N entries cannot overflow.  (MFD's mf_enqueue guards the queue store with the
+//        queue's length all the same and k_mf_flow clamps its window to it; D-infinity's stores are unguarded.  The
+//        asymmetry is known and deliberate for now: the flow kernels are not to change with this header.)
+// out    ldexp(T - q, -s) as float64 (cd_result); -100 on nodata and where pending != 0 (on or below a cycle, or -- on
+//        the device tier -- not reached within the budget of rounds); tail != hi means queued work is left, which
+//        raises DT_STATUS_NOT_CONVERGED (cd_not_converged).
+// Integer sums are order-free and the split is a function of the complete T alone, so the result does not depend on
+// the order of arrival, on how many cells a lane holds or on the number of rounds.
+#pragma once
+#include <cmath>
+
+#include "dt_kernels.h"
+
+#define CD_SUM_MASK ((1ull << 56) - 1ull)
+#define CD_ONE_PEND (1ull << 56)
+#define CD_F_SRC (1ull << 60)
+#define CD_NONE 0xFFFFFFFFu
+
+// control words of one accumulation: the queue's tail, the window [lo, hi) of the current queue round, queue rounds
+// that found work, the largest window, cells with two or more receivers
+enum { CD_C_TAIL = 0, CD_C_LO = 1, CD_C_HI = 2, CD_C_ROUNDS = 3, CD_C_HIGH = 4, CD_C_MULTI = 5, CD_C_WORDS = 8 };
+
+// donors of the word's cell that have not arrived yet
+__device__ __forceinline__ unsigned long long cd_pending(unsigned long long wv) { return (wv >> 56) & 0xFull; }
+
+// q = rint(w * 2^s), flowacc_weighted's rule: a weight outside the contract is bad and counts as 0
+__device__ __forceinline__ unsigned long long cd_quant(const double *__restrict__ wt, long long c, int sbits,
+                                                       unsigned long long qmax, bool &bad) {
+  const double v = wt ? wt[c] : 1.0;
+  if (!(v >= 0.0)) {
+    bad = true;
+    return 0ull;
+  }
+  const double q = rint(ldexp(v, sbits));
+  if (!(q <= (double)qmax)) {
+    bad = true;
+    return 0ull;
+  }
+  return (unsigned long long)q;
+}
+
+// the out kernels, one lane of them (`first`): queued work is left
+__device__ __forceinline__ void cd_not_converged(bool first, const uint32_t *__restrict__ ctl,
+                                                 int *__restrict__ status) {
+  if (first && status && ctl[CD_C_TAIL] != ctl[CD_C_HI]) atomicOr(status, DT_STATUS_NOT_CONVERGED);
+}
+// the result of a complete cell: what arrived, its own q (cd_quant's, taken again) excluded
+__device__ __forceinline__ double cd_result(unsigned long long wv, unsigned long long q, int sbits) {
+  return ldexp((double)(long long)((wv & CD_SUM_MASK) - q), -sbits);
+}
+
+// the workspace: control words, one word and one queue slot per cell and, with `edges`, one byte per cell
+struct CdLayout {
+  uint32_t *ctl;
+  unsigned long long *word;
+  uint32_t *queue;
+  uint8_t *edges;
+  size_t bytes;
+};
+static inline CdLayout cd_layout(int64_t N, void *scratch, bool edges) {
+  CdLayout L = {};
+  DtCarver c(scratch);
+  L.ctl = c.take<uint32_t>(CD_C_WORDS);
+  L.word = c.take<unsigned long long>((size_t)N);
+  L.queue = c.take<uint32_t>((size_t)N);
+  if (edges) L.edges = c.take<uint8_t>((size_t)N);
+  L.bytes = c.bytes();
+  return L;
+}
+
+// the largest weight word: N of them sum to at most 2^52
+static inline unsigned long long cd_qmax(int64_t N) { return (1ull << 52) / (unsigned long long)N; }
+// complete cells a lane holds in LDS beside the one it carries on with: `stack`, or n - 1 with stack_cap = n > 0
+static inline int cd_stack_cap(int stack_cap, int stack) {
+  return stack_cap > 0 && stack_cap - 1 < stack ? stack_cap - 1 : stack;
+}
+
+// k_cd_mark (dt_countdown.hip): the window of the next queue round
+void cd_launch_mark(hipStream_t s, uint32_t *ctl);
+
+// start != 0: the control words are cleared, init() and round 0, flow(true, one lane per cell); then `rounds` queue
+// rounds, each k_cd_mark and flow(false, a capped grid); finish != 0: out(one lane per cell).  The three launch the
+// op's own kernels on `s`.  Nothing synchronises.
+template <typename Init, typename Flow, typename Out>
+static int cd_run(hipStream_t s, int64_t N, uint32_t *ctl, int start, int rounds, int finish, Init init, Flow flow,
+                  Out out) {
+  const dim3 cells((unsigned)((N + 255) / 256));
+  if (start) {
+    DT_HIP(hipMemsetAsync(ctl, 0, sizeof(uint32_t) * CD_C_WORDS, s));
+    init();
+    flow(true, cells);
+  }
+  const dim3 gq(dt_capped_grid(N, 2048));
+  for (int r = 0; r < rounds; r++) {
+    cd_launch_mark(s, ctl);
+    flow(false, gq);
+  }
+  if (finish) out(cells);
+  return DT_OK;
+}

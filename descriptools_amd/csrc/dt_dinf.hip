@@ -7,45 +7,25 @@
 // winning facet.  A neighbour takes part when it is finite and > -100; everything outside the raster is staged as
 // -100.  A valid centre without a winning facet takes the caller's D8 code (when that neighbour is valid) or -1.
 //
-// Accumulation: the drainage graph is a DAG of out-degree <= 2, so the tile passes' pointer doubling (a tree) cannot
-// carry it.  One 64-bit word per cell is the whole state,
-//   bits 0-55 sum (q, then q + what has arrived) | 56-59 pending donors | 60 source | 61, 62 the edge to the first /
-//   second receiver exists (the receiver lies in the raster and is not nodata)
-// k_di_init   gathers each cell's in-degree from the eight neighbours' angles (LDS tile of angles, no atomics),
-//             quantises the weight and writes the word.
-// k_di_flow   the in-degree countdown on the DAG.  A lane that owns a complete cell (pending 0) splits its total T,
-//             m2 = floor(T * P2 / 2^30) to the second receiver and T - m2 to the first, and adds m - 2^56 to each
-//             receiver's word with one returning 64-bit atomic: sum and countdown move together, the arrival that
-//             finds pending == 1 in the value it gets back holds the receiver's complete total, and no fence is
-//             needed (cdna_hip_programming.md Guideline 16: the word is the only thing handed over).  That lane
-//             carries on from the receiver it completed; when it completes both it keeps one and puts the other on a
-//             stack of DI_STACK cells in LDS, and when that is full on a global queue.  Round 0 starts from the
-//             sources (a scan of the raster); every later round drains what the rounds before put on the queue
-//             (k_di_mark moves the window [lo, hi) to the entries written before it ran); a round whose window is
-//             empty returns at once.  A start walks at most DI_MOVES cells in a round and then queues what it holds:
-//             a round lasts as long as its longest walk, and while one lane follows a channel of tens of thousands
-//             of cells everything queued behind it would wait -- bounded walks keep the rounds short (a few hundred
-//             dependent atomics) and the queued work moving.  No lane waits for another, and a lane's storage does
-//             not grow with its path.  A cell is queued only when it is complete and not yet sent on, which happens
-//             once: a queue of N entries cannot overflow.
-// k_di_out    ldexp(T - q, -s) as float64; -100 on nodata and where pending != 0 (on or below a cycle, or -- on the
-//             device tier -- not reached within the budget of rounds, which raises DT_STATUS_NOT_CONVERGED).
-// Integer sums are order-free and the split is a function of the complete T alone, so the result does not depend on
-// the order of arrival, the stack size or the number of rounds.
+// Accumulation: the in-degree countdown of dt_countdown.h (the protocol is written out there) on a DAG of out-degree
+// <= 2.  The word's own flags: 61, 62 the edge to the first / second receiver exists (the receiver lies in the raster
+// and is not nodata).
+// k_di_init   gathers each cell's in-degree from the eight neighbours' angles (LDS tile of angles, no atomics).
+// k_di_flow   a complete cell sends m2 = floor(T * P2 / 2^30) to the second receiver and T - m2 to the first.  A lane
+//             that completes both receivers keeps one and puts the other on a STACK of DI_STACK cells in LDS (last in,
+//             first out: it follows one branch to its end), and when that is full on the queue.  A start walks at most
+//             DI_MOVES = 128 cells in a round: while one lane follows a channel of tens of thousands of cells
+//             everything queued behind it would wait (measured: DESIGN.md 4.11).  The receivers' angles are asked for
+//             beside the atomics.
+// k_di_out    nodata is read from the angle raster.
 #include <cmath>
 
+#include "dt_countdown.h"
 #include "dt_dinf_common.h"
 
-#define DI_SUM_MASK ((1ull << 56) - 1ull)
-#define DI_ONE_PEND (1ull << 56)
-#define DI_F_SRC (1ull << 60)
 #define DI_F_E0 (1ull << 61)
 #define DI_F_E1 (1ull << 62)
-#define DI_NONE 0xFFFFFFFFu
 #define DI_MOVES 128  // cells one start (a source, a queue entry) may complete in a round before it hands on
-
-// finite and > -100 (false for NaN)
-__device__ __forceinline__ bool di_valid(float v) { return v > -100.0f && v < INFINITY; }
 
 // ---- direction -----------------------------------------------------------------------------------------------------
 // one cell: e0 and its neighbours by octant; code = the caller's D8 code (0 without one)
@@ -123,16 +103,7 @@ __global__ __launch_bounds__(256) void k_dinf(const float *__restrict__ dem, con
   di_load_row(t, ly + 2, cx, c);
   const long long o = (long long)gy * W + gx;
   const bool full = vec_ok && gx + 3 < W;
-  uint32_t codes = 0u;
-  if (fdr) {
-    if (full) {
-      codes = *reinterpret_cast<const uint32_t *>(fdr + o);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-        if (gx + k < W) codes |= (uint32_t)fdr[o + k] << (8 * k);
-    }
-  }
+  const uint32_t codes = di_load_codes(fdr, o, gx, W, full);
   float ao[4], so[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -155,25 +126,6 @@ __global__ __launch_bounds__(256) void k_dinf(const float *__restrict__ dem, con
 }
 
 // ---- accumulation --------------------------------------------------------------------------------------------------
-// control words of one accumulation
-enum { DI_C_TAIL = 0, DI_C_LO = 1, DI_C_HI = 2, DI_C_ROUNDS = 3, DI_C_HIGH = 4, DI_C_TWO = 5, DI_C_WORDS = 8 };
-
-// q = rint(w * 2^s), flowacc_weighted's rule: a weight outside the contract is bad and counts as 0
-__device__ __forceinline__ unsigned long long di_quant(const double *__restrict__ wt, long long c, int sbits,
-                                                       unsigned long long qmax, bool &bad) {
-  const double v = wt ? wt[c] : 1.0;
-  if (!(v >= 0.0)) {
-    bad = true;
-    return 0ull;
-  }
-  const double q = rint(ldexp(v, sbits));
-  if (!(q <= (double)qmax)) {
-    bad = true;
-    return 0ull;
-  }
-  return (unsigned long long)q;
-}
-
 __global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle, const double *__restrict__ wt, int H,
                                                  int W, int tiles_x, int vec_ok, int sbits, unsigned long long qmax,
                                                  unsigned long long *__restrict__ word, uint32_t *__restrict__ ctl,
@@ -210,8 +162,8 @@ __global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle
           pending += (d.kind >= 1 && d.k == back) || (d.kind == 2 && ((d.k + 1) & 7) == back) ? 1u : 0u;
         }
         const DiDec d = di_decode(me, bad_a);
-        wv = di_quant(wt, o + k, sbits, qmax, bad_w) | ((unsigned long long)pending << 56);
-        if (pending == 0u) wv |= DI_F_SRC;
+        wv = cd_quant(wt, o + k, sbits, qmax, bad_w) | ((unsigned long long)pending << 56);
+        if (pending == 0u) wv |= CD_F_SRC;
         if (d.kind >= 1 && n[d.k] != DT_NODATA) wv |= DI_F_E0;
         if (d.kind == 2 && n[(d.k + 1) & 7] != DT_NODATA) wv |= DI_F_E1;
         two += d.kind == 2 ? 1u : 0u;
@@ -221,18 +173,7 @@ __global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle
   }
   if (status && (bad_a || bad_w))
     atomicOr(status, (bad_a ? DT_STATUS_BAD_ANGLE : 0) | (bad_w ? DT_STATUS_BAD_WEIGHT : 0));
-  if (two) atomicAdd(&ctl[DI_C_TWO], two);
-}
-
-// the window of the next queue round: what was queued before this kernel ran and has not been drained
-__global__ void k_di_mark(uint32_t *ctl) {
-  const uint32_t lo = ctl[DI_C_HI], hi = ctl[DI_C_TAIL];
-  ctl[DI_C_LO] = lo;
-  ctl[DI_C_HI] = hi;
-  if (hi > lo) {
-    ctl[DI_C_ROUNDS] += 1u;
-    if (hi - lo > ctl[DI_C_HIGH]) ctl[DI_C_HIGH] = hi - lo;
-  }
+  if (two) atomicAdd(&ctl[CD_C_MULTI], two);
 }
 
 // floor(T * p2 / 2^30), T < 2^56, p2 < 2^30: the 86-bit product held exactly in two words
@@ -245,7 +186,7 @@ template <bool SCAN>
 __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle, unsigned long long *word, int H,
                                                  int W, uint32_t *queue, uint32_t *ctl, int cap, int moves_max) {
   __shared__ uint32_t s_stack[DI_STACK * 256];
-  const uint32_t lo = SCAN ? 0u : ctl[DI_C_LO], hi = SCAN ? (uint32_t)((long long)H * W) : ctl[DI_C_HI];
+  const uint32_t lo = SCAN ? 0u : ctl[CD_C_LO], hi = SCAN ? (uint32_t)((long long)H * W) : ctl[CD_C_HI];
   for (unsigned long long i = (unsigned long long)lo + (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < hi;
        i += (unsigned long long)gridDim.x * 256ull) {
     uint32_t c;
@@ -253,7 +194,7 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
     if (SCAN) {
       c = (uint32_t)i;
       wv = word[c];  // a source's word receives nothing; the flag bits of any word never change
-      if (!(wv & DI_F_SRC)) continue;
+      if (!(wv & CD_F_SRC)) continue;
     } else {
       c = queue[i];
       wv = __hip_atomic_load(&word[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -261,11 +202,11 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
     float ac = angle[c];
     int sp = 0;
     for (int moves = 0;;) {  // c is complete, wv is its word and ac its angle
-      uint32_t next = DI_NONE;
+      uint32_t next = CD_NONE;
       unsigned long long nextw = 0ull;
       float nexta = 0.0f;
       if (wv & (DI_F_E0 | DI_F_E1)) {
-        const unsigned long long T = wv & DI_SUM_MASK;
+        const unsigned long long T = wv & CD_SUM_MASK;
         bool ignore = false;
         const DiDec d = di_decode(ac, ignore);
         const unsigned long long m2 = d.kind == 2 ? di_share(T, d.p2) : 0ull;
@@ -285,30 +226,30 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
         unsigned long long add[2], old[2] = {0ull, 0ull};
 #pragma unroll
         for (int e = 0; e < 2; e++) {
-          add[e] = (e ? m2 : m1) - DI_ONE_PEND;
+          add[e] = (e ? m2 : m1) - CD_ONE_PEND;
           if (wv & (e ? DI_F_E1 : DI_F_E0)) old[e] = atomicAdd(&word[rr[e]], add[e]);
         }
 #pragma unroll
         for (int e = 0; e < 2; e++) {
-          if (((old[e] >> 56) & 0xFull) != 1ull) continue;  // no edge, or donors of the receiver are still to come
+          if (cd_pending(old[e]) != 1ull) continue;  // no edge, or donors of the receiver are still to come
           const uint32_t r = rr[e];
-          if (next == DI_NONE) {
+          if (next == CD_NONE) {
             next = r;
             nextw = old[e] + add[e];
             nexta = ra[e];
           } else if (sp < cap) {
             s_stack[sp++ * 256 + threadIdx.x] = r;
           } else {
-            queue[atomicAdd(&ctl[DI_C_TAIL], 1u)] = r;
+            queue[atomicAdd(&ctl[CD_C_TAIL], 1u)] = r;
           }
         }
       }
       if (++moves >= moves_max) {  // this entry's share of the round is used up: the next round carries on
-        if (next != DI_NONE) queue[atomicAdd(&ctl[DI_C_TAIL], 1u)] = next;
-        while (sp > 0) queue[atomicAdd(&ctl[DI_C_TAIL], 1u)] = s_stack[--sp * 256 + threadIdx.x];
+        if (next != CD_NONE) queue[atomicAdd(&ctl[CD_C_TAIL], 1u)] = next;
+        while (sp > 0) queue[atomicAdd(&ctl[CD_C_TAIL], 1u)] = s_stack[--sp * 256 + threadIdx.x];
         break;
       }
-      if (next != DI_NONE) {
+      if (next != CD_NONE) {
         c = next;
         wv = nextw;
         ac = nexta;
@@ -328,40 +269,22 @@ __global__ __launch_bounds__(256) void k_di_out(const float *__restrict__ angle,
                                                 unsigned long long qmax, const uint32_t *__restrict__ ctl,
                                                 double *__restrict__ out, int *__restrict__ status) {
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (c == 0 && status && ctl[DI_C_TAIL] != ctl[DI_C_HI]) atomicOr(status, DT_STATUS_NOT_CONVERGED);
+  cd_not_converged(c == 0, ctl, status);
   if (c >= N) return;
   const unsigned long long wv = word[c];
   double v = -100.0;
-  if (angle[c] != DT_NODATA && ((wv >> 56) & 0xFull) == 0ull) {
+  if (angle[c] != DT_NODATA && cd_pending(wv) == 0ull) {
     bool ignore = false;
-    const unsigned long long q = di_quant(wt, c, sbits, qmax, ignore);
-    v = ldexp((double)(long long)((wv & DI_SUM_MASK) - q), -sbits);
+    v = cd_result(wv, cd_quant(wt, c, sbits, qmax, ignore), sbits);
   }
   out[c] = v;
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
-struct DiLayout {
-  uint32_t *ctl;
-  unsigned long long *word;
-  uint32_t *queue;
-  size_t bytes;
-};
-static DiLayout di_layout(int64_t N, void *scratch) {
-  DiLayout L = {};
-  DtCarver c(scratch);
-  L.ctl = c.take<uint32_t>(DI_C_WORDS);
-  L.word = c.take<unsigned long long>((size_t)N);
-  L.queue = c.take<uint32_t>((size_t)N);
-  L.bytes = c.bytes();
-  return L;
-}
-size_t dt_dinf_accumulate_scratch(int64_t H, int64_t W) { return di_layout(H * W, nullptr).bytes; }
-
-static int di_vec_ok(const void *p, int64_t W) { return W % 4 == 0 && ((uintptr_t)p & 15u) == 0; }
-static unsigned di_tiles(int64_t H, int64_t W, int &tiles_x) {
-  tiles_x = (int)((W + DI_TX - 1) / DI_TX);
-  return (unsigned)(((H + DI_TY - 1) / DI_TY) * tiles_x);
+size_t dt_dinf_accumulate_scratch(int64_t H, int64_t W) { return cd_layout(H * W, nullptr, false).bytes; }
+// the control words of the accumulation in `scratch` (device pointer to CD_C_WORDS uint32)
+const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W) {
+  return cd_layout(H * W, scratch, false).ctl;
 }
 
 int dt_launch_dinf_direction(hipStream_t s, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
@@ -376,39 +299,30 @@ int dt_launch_dinf_direction(hipStream_t s, const float *dem, const uint8_t *fdr
   return DT_OK;
 }
 
-// start != 0: the set-up and round 0 first; then `rounds` queue rounds; finish != 0: k_di_out
+// start, rounds and finish: cd_run's
 int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *wt, int64_t H, int64_t W, int frac_bits,
                               int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
                               double *out, int *status) {
   if (H == 0 || W == 0) return DT_OK;
   const int64_t N = H * W;
-  DiLayout L = di_layout(N, scratch);
+  const CdLayout L = cd_layout(N, scratch, false);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
-  const unsigned long long qmax = (1ull << 52) / (unsigned long long)N;
-  const int cap = stack_cap > 0 && stack_cap - 1 < DI_STACK ? stack_cap - 1 : DI_STACK;  // cells on the stack
+  const unsigned long long qmax = cd_qmax(N);
+  const int cap = cd_stack_cap(stack_cap, DI_STACK);
   const dim3 b(256);
-  if (start) {
-    DT_HIP(hipMemsetAsync(L.ctl, 0, sizeof(uint32_t) * DI_C_WORDS, s));
-    int tiles_x;
-    const unsigned nt = di_tiles(H, W, tiles_x);
-    hipLaunchKernelGGL(k_di_init, dim3(nt), b, 0, s, angle, wt, (int)H, (int)W, tiles_x, di_vec_ok(angle, W), frac_bits,
-                       qmax, L.word, L.ctl, status);
-    hipLaunchKernelGGL(k_di_flow<true>, dim3((unsigned)((N + 255) / 256)), b, 0, s, angle, L.word, (int)H, (int)W,
-                       L.queue, L.ctl, cap, DI_MOVES);
-  }
-  const dim3 gq(dt_capped_grid(N, 2048));
-  for (int r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(k_di_mark, dim3(1), dim3(1), 0, s, L.ctl);
-    hipLaunchKernelGGL(k_di_flow<false>, gq, b, 0, s, angle, L.word, (int)H, (int)W, L.queue, L.ctl, cap, DI_MOVES);
-  }
-  if (finish)
-    hipLaunchKernelGGL(k_di_out, dim3((unsigned)((N + 255) / 256)), b, 0, s, angle, wt, L.word, (long long)N, frac_bits,
-                       qmax, L.ctl, out, status);
-  return DT_OK;
-}
-
-// the control words of the accumulation in `scratch` (device pointer to DI_C_WORDS uint32: tail, lo, hi, queue rounds
-// that found work, the largest window, two-receiver cells)
-const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W) {
-  return di_layout(H * W, scratch).ctl;
+  return cd_run(
+      s, N, L.ctl, start, rounds, finish,
+      [&] {
+        int tiles_x;
+        const unsigned nt = di_tiles(H, W, tiles_x);
+        hipLaunchKernelGGL(k_di_init, dim3(nt), b, 0, s, angle, wt, (int)H, (int)W, tiles_x, di_vec_ok(angle, W),
+                           frac_bits, qmax, L.word, L.ctl, status);
+      },
+      [&](bool scan, dim3 g) {
+        auto *flow = scan ? k_di_flow<true> : k_di_flow<false>;
+        hipLaunchKernelGGL(flow, g, b, 0, s, angle, L.word, (int)H, (int)W, L.queue, L.ctl, cap, DI_MOVES);
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL(k_di_out, g, b, 0, s, angle, wt, L.word, (long long)N, frac_bits, qmax, L.ctl, out, status);
+      });
 }

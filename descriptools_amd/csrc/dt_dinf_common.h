@@ -1,7 +1,10 @@
-// dt_dinf_common.h -- what the D-infinity kernels share (dt_dinf.hip: direction and contributing area;
-// dt_dinf_dist.hip: distance to the stream): the 128 x 8 staging tile with its one-cell halo, the octant steps and the
-// decoding of an angle into receivers (descriptools_amd/dinf.py holds the definition).
+// dt_dinf_common.h -- what the kernels on D-infinity's tile geometry share (dt_dinf.hip: direction and contributing
+// area; dt_dinf_dist.hip: distance to the stream; dt_mfd.hip: MFD shares and contributing area): the 128 x 8 staging
+// tile with its one-cell halo and its launch geometry, the octant steps, the validity of a height, the D8 codes of a
+// lane's four cells and the decoding of an angle into receivers (descriptools_amd/dinf.py holds the definition).
 #pragma once
+#include <cmath>
+
 #include "dt_kernels.h"
 
 #define DI_TX 128
@@ -14,6 +17,34 @@
 // dy / dx of octant k (angle k pi / 4 counter-clockwise from east, rows grow to the south), packed as DT_PK8 packs
 #define DI_DX_PACK DT_PK8(1, 1, 0, -1, -1, -1, 0, 1)
 #define DI_DY_PACK DT_PK8(0, -1, -1, -1, 0, 1, 1, 1)
+
+// finite and > -100 (false for NaN)
+__device__ __forceinline__ bool di_valid(float v) { return v > -100.0f && v < INFINITY; }
+
+// the tiles of an H x W raster: one workgroup each
+static inline unsigned di_tiles(int64_t H, int64_t W, int &tiles_x) {
+  tiles_x = (int)((W + DI_TX - 1) / DI_TX);
+  return (unsigned)(((H + DI_TY - 1) / DI_TY) * tiles_x);
+}
+// a float raster of width W at p may be read and written four cells (16 bytes) at a time
+static inline int di_vec_ok(const void *p, int64_t W) { return W % 4 == 0 && ((uintptr_t)p & 15u) == 0; }
+
+// the D8 codes of the lane's four cells from gx on (flat index o), one per byte; 0 without `fdr` and beyond the row.
+// full: the four lie in the row and fdr + o is 4-byte aligned
+__device__ __forceinline__ uint32_t di_load_codes(const uint8_t *__restrict__ fdr, long long o, int gx, int W,
+                                                  bool full) {
+  uint32_t codes = 0u;
+  if (fdr) {
+    if (full) {
+      codes = *reinterpret_cast<const uint32_t *>(fdr + o);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (gx + k < W) codes |= (uint32_t)fdr[o + k] << (8 * k);
+    }
+  }
+  return codes;
+}
 
 // stage (DI_TY + 2) x (DI_TX + 2) cells of src around the tile at (y0, x0); `fill` outside the raster.  The caller
 // synchronises.

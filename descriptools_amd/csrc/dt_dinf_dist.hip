@@ -341,11 +341,10 @@ int dt_launch_dinf_distance(hipStream_t s, const float *angle, const int8_t *riv
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
   const dim3 b(256);
   if (start) {
-    const int tiles_x = (int)((W + DI_TX - 1) / DI_TX);
-    const unsigned nt = (unsigned)(((H + DI_TY - 1) / DI_TY) * tiles_x);
-    const int vec_ok = W % 4 == 0 && ((uintptr_t)angle & 15u) == 0;
-    hipLaunchKernelGGL(k_dd_init, dim3(nt), b, 0, s, angle, river, (int)H, (int)W, tiles_x, vec_ok, L.st, h, v, sf,
-                       status);
+    int tiles_x;
+    const unsigned nt = di_tiles(H, W, tiles_x);
+    hipLaunchKernelGGL(k_dd_init, dim3(nt), b, 0, s, angle, river, (int)H, (int)W, tiles_x, di_vec_ok(angle, W), L.st,
+                       h, v, sf, status);
     DT_HIP(hipMemsetAsync(L.visits, 0, sizeof(uint32_t) * (size_t)L.tiles_x * (size_t)L.tiles_y, s));
   }
   if (rounds) DT_HIP(hipMemsetAsync(L.ctl + DD_C_FLAGS, 0, sizeof(uint32_t) * DT_DINF_DIST_BATCH_MAX, s));

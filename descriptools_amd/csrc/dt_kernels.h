@@ -262,7 +262,8 @@ int dt_launch_inundate(hipStream_t s, const int32_t *catch_, const void *hand, i
                        int64_t N, int64_t R, float *depth);
 
 // D-infinity (dt_dinf.hip): flow angle / slope on the eight triangular facets (fdr, slope may be NULL), and the
-// contributing area of an angle raster (wt may be NULL: 1 everywhere).  The accumulation keeps its state in `scratch`:
+// contributing area of an angle raster (wt may be NULL: 1 everywhere).  The accumulation is an in-degree countdown
+// (dt_countdown.h holds the protocol, the workspace and the host sequence) and keeps its state in `scratch`:
 // start != 0 sets it up and runs round 0 (from the sources), `rounds` queue rounds follow, finish != 0 writes `out`
 // (and raises DT_STATUS_NOT_CONVERGED on `status` when queued work is left).  stack_cap: 0 the default (a lane holds the
 // cell it carries on with and DI_STACK more), n > 0: at most n cells, the one it carries on with included, so 1 sends
@@ -274,8 +275,8 @@ size_t dt_dinf_accumulate_scratch(int64_t H, int64_t W);
 int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *wt, int64_t H, int64_t W, int frac_bits,
                               int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
                               double *out, int *status);
-// the accumulation's control words in `scratch` (8 x uint32 on the device): queued, window lo, window hi, queue rounds
-// that found work, the largest window, two-receiver cells
+// the accumulation's control words in `scratch` (8 x uint32 on the device, dt_countdown.h's CD_C_*): queued, window lo,
+// window hi, queue rounds that found work, the largest window, two-receiver cells
 const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 
 // D-infinity distance down to the stream (dt_dinf_dist.hip; dinf.py holds the definition): the horizontal distance h
@@ -299,18 +300,17 @@ const uint32_t *dt_dinf_distance_ctl(void *scratch, int64_t H, int64_t W);
 
 // Multiple flow direction (dt_mfd.hip; mfd.py holds the definition): the share raster of a DEM (eight uint16 per cell
 // by octant, units of 2^-15, 16-byte aligned; fdr may be NULL; exponent in [0, 64]), and the contributing area of a
-// share raster (wt may be NULL: 1 everywhere).  The accumulation keeps its state in `scratch` and takes start, rounds
-// and finish as dt_launch_dinf_accumulate does; a share word outside the contract raises DT_STATUS_BAD_SHARES on
-// `status`.  The environment variable DT_DBG_MFD_STACK = n > 0 caps the complete cells a lane holds at n, the one it
-// carries on with included (tests).  Nothing synchronises.  H * W < 2^31.
+// share raster (wt may be NULL: 1 everywhere).  The accumulation is the same countdown (dt_countdown.h): it keeps its
+// state in `scratch` and takes start, rounds, finish and stack_cap as dt_launch_dinf_accumulate does (the environment
+// variable DT_DBG_MFD_STACK; tests); a share word outside the contract raises DT_STATUS_BAD_SHARES on `status`.
+// Nothing synchronises.  H * W < 2^31.
 int dt_launch_mfd_shares(hipStream_t s, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double exponent,
                          int contour, uint16_t *shares);
 size_t dt_mfd_accumulate_scratch(int64_t H, int64_t W);
 int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double *wt, int64_t H, int64_t W,
-                             int frac_bits, int start, int rounds, int finish, void *scratch, size_t scratch_bytes,
-                             double *out, int *status);
-// the accumulation's control words in `scratch` (8 x uint32 on the device): queued, window lo, window hi, queue rounds
-// that found work, the largest window, cells with two or more receivers
+                             int frac_bits, int start, int rounds, int finish, int stack_cap, void *scratch,
+                             size_t scratch_bytes, double *out, int *status);
+// the accumulation's control words in `scratch`, as dt_dinf_accumulate_ctl's (cells with two or more receivers)
 const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 
 // Euclidean proximity (dt_proximity.hip): for every cell the nearest source (river == 1 and, with nod, nod > -100) by

@@ -7,49 +7,33 @@
 // the shares in units of 2^-15 as eight uint16 by octant: one 16-byte store per cell.  The integer exponents (repeated
 // multiplication, IEEE-exact) and the others (pow) are two template instances.
 //
-// Accumulation: D-infinity's in-degree countdown (dt_dinf.hip) with up to eight receivers.  One 64-bit word per cell,
-//   bits 0-55 sum (q, then q + what has arrived) | 56-59 pending donors (0..8) | 60 source | 61 nodata
-// and one byte per cell: bit k = the edge to the receiver in octant k exists (the share is > 0, the receiver lies in
-// the raster and is not nodata).
+// Accumulation: the in-degree countdown of dt_countdown.h (the protocol is written out there) on a DAG of out-degree
+// <= 8.  The word's own flag: 61 nodata.  One byte per cell beside it: bit k = the edge to the receiver in octant k
+// exists (the share is > 0, the receiver lies in the raster and is not nodata).
 // k_mf_init   classifies the share words of a 128 x 8 tile and its halo into LDS (receiver mask, nodata, bad), then
 //             every cell gathers its in-degree from slot (k + 4) & 7 of neighbour k (no atomics), works out its own
 //             edges, quantises its weight and writes word and edge byte.  A word outside the contract raises
 //             DT_STATUS_BAD_SHARES and counts as no receiver.
-// k_mf_flow   a lane that owns a complete cell (pending 0) splits its total T, m_k = floor(T * P_k / 2^15) to every
-//             receiver but the main one and the rest to the main one, and adds m - 2^56 to each receiver's word with a
-//             returning 64-bit atomic; all of a cell's atomics are issued before any answer is looked at.  The arrival
-//             that reads pending == 1 owns the receiver's complete total.  The complete cells a lane holds wait in a
-//             ring of MF_STACK cells in LDS and are taken in the order they completed (a lane that holds nothing
-//             else carries straight on with the receiver it completed); a full ring spills to the global queue.
-//             First in, first out and not a stack: a cell completes only after ALL its donors, so the critical path
-//             runs through cells that a lane following one branch to its end would leave waiting (measured:
-//             DESIGN.md 4.15).  Round 0 starts from the sources; each later round drains what was queued before
-//             k_mf_mark ran.  A start completes at most MF_MOVES cells in a round and then queues what it holds.  No
-//             lane waits for another; every loop is bounded by its trip count.  A cell is queued only when it is
-//             complete and not yet sent on, which happens once: a queue of N entries cannot overflow.
-// k_mf_out    ldexp(T - q, -s) as float64; -100 on nodata and where pending != 0 (on or below a cycle, or -- on the
-//             device tier -- not reached within the budget of rounds, which raises DT_STATUS_NOT_CONVERGED).
-// Integer sums are order-free and the split is a function of the complete T alone, so the result does not depend on
-// the order of arrival, the stack size or the number of rounds.
+// k_mf_flow   a complete cell sends m_k = floor(T * P_k / 2^15) to every receiver but the main one and the rest to the
+//             main one; all of a cell's atomics are issued before any answer is looked at.  The complete cells a lane
+//             holds wait in a RING of MF_STACK cells in LDS and are taken in the order they completed (a lane that
+//             holds nothing else carries straight on with the receiver it completed); a full ring spills to the
+//             queue.  First in, first out and not a stack: a cell completes only after ALL its donors, so the critical
+//             path runs through cells that a lane following one branch to its end would leave waiting.  A start
+//             completes at most MF_MOVES = 32 cells in a round (both measured: DESIGN.md 4.15).
+// k_mf_out    nodata is read from the word.
 #include <cmath>
-#include <cstdlib>
 
+#include "dt_countdown.h"
 #include "dt_dinf_common.h"
 
-#define MF_SUM_MASK ((1ull << 56) - 1ull)
-#define MF_ONE_PEND (1ull << 56)
-#define MF_F_SRC (1ull << 60)
 #define MF_F_NODATA (1ull << 61)
-#define MF_NONE 0xFFFFFFFFu
 #define MF_MOVES 32  // cells one start (a source, a queue entry) may complete in a round before it hands on
 #define MF_STACK 8   // complete cells a lane holds in its ring in LDS (a power of two)
 #define MF_UNIT 32768u
 // a share word as k_mf_init classifies it: bits 0-7 the octants with a share > 0
 #define MF_CL_NODATA 0x100u
 #define MF_CL_BAD 0x200u
-
-// finite and > -100 (false for NaN)
-__device__ __forceinline__ bool mf_valid(float v) { return v > -100.0f && v < INFINITY; }
 
 __device__ __forceinline__ void mf_unpack(const uint4 w, uint32_t (&P)[8]) {
   P[0] = w.x & 0xFFFFu;
@@ -73,12 +57,12 @@ __device__ __forceinline__ uint4 mf_cell(float c, const float (&n)[8], double p,
                                          uint32_t code) {
   if (c <= DT_NODATA) return make_uint4(~0u, ~0u, ~0u, ~0u);
   uint32_t P[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-  if (!mf_valid(c)) return mf_pack(P);  // NaN, +inf: no receiver
+  if (!di_valid(c)) return mf_pack(P);  // NaN, +inf: no receiver
   const double z0 = (double)c;
   double g[8], gmax = 0.0;
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    const bool rec = mf_valid(n[k]) && n[k] < c;
+    const bool rec = di_valid(n[k]) && n[k] < c;
     const double d = z0 - (double)n[k];
     g[k] = rec ? ((k & 1) ? d / 1.4142135623730951 : d) : 0.0;  // > 0 for every receiver
     gmax = g[k] > gmax ? g[k] : gmax;
@@ -125,7 +109,7 @@ __device__ __forceinline__ uint4 mf_cell(float c, const float (&n)[8], double p,
     const int k = (8 - (__ffs((int)code) - 1)) & 7;  // valid cell
 #pragma unroll
     for (int j = 0; j < 8; j++)
-      if (j == k && mf_valid(n[j])) P[j] = MF_UNIT;
+      if (j == k && di_valid(n[j])) P[j] = MF_UNIT;
   }
   return mf_pack(P);
 }
@@ -147,16 +131,7 @@ __global__ __launch_bounds__(256) void k_mfd_shares(const float *__restrict__ de
   di_load_row(t, ly + 1, cx, b);
   di_load_row(t, ly + 2, cx, c);
   const long long o = (long long)gy * W + gx;
-  uint32_t codes = 0u;
-  if (fdr) {
-    if (vec_ok && gx + 3 < W) {
-      codes = *reinterpret_cast<const uint32_t *>(fdr + o);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-        if (gx + k < W) codes |= (uint32_t)fdr[o + k] << (8 * k);
-    }
-  }
+  const uint32_t codes = di_load_codes(fdr, o, gx, W, vec_ok && gx + 3 < W);
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     if (gx + k >= W) continue;
@@ -167,25 +142,6 @@ __global__ __launch_bounds__(256) void k_mfd_shares(const float *__restrict__ de
 }
 
 // ---- accumulation --------------------------------------------------------------------------------------------------
-// control words of one accumulation (k_di_flow's)
-enum { MF_C_TAIL = 0, MF_C_LO = 1, MF_C_HI = 2, MF_C_ROUNDS = 3, MF_C_HIGH = 4, MF_C_MULTI = 5, MF_C_WORDS = 8 };
-
-// q = rint(w * 2^s), flowacc_weighted's rule: a weight outside the contract is bad and counts as 0
-__device__ __forceinline__ unsigned long long mf_quant(const double *__restrict__ wt, long long c, int sbits,
-                                                       unsigned long long qmax, bool &bad) {
-  const double v = wt ? wt[c] : 1.0;
-  if (!(v >= 0.0)) {
-    bad = true;
-    return 0ull;
-  }
-  const double q = rint(ldexp(v, sbits));
-  if (!(q <= (double)qmax)) {
-    bad = true;
-    return 0ull;
-  }
-  return (unsigned long long)q;
-}
-
 // receiver mask | MF_CL_NODATA | MF_CL_BAD of one share word: nodata is eight 0xFFFF; otherwise every slot is <= 2^15
 // and the slots sum to 0 or 2^15, anything else is bad and has no receiver
 __device__ __forceinline__ uint32_t mf_classify(const uint4 w) {
@@ -242,26 +198,15 @@ __global__ __launch_bounds__(256) void k_mf_init(const uint4 *__restrict__ share
       }
       bad_s |= (me & MF_CL_BAD) != 0u;
       multi += __popc(me & 0xFFu) >= 2 ? 1u : 0u;
-      wv = mf_quant(wt, o, sbits, qmax, bad_w) | ((unsigned long long)pending << 56);
-      if (pending == 0u) wv |= MF_F_SRC;
+      wv = cd_quant(wt, o, sbits, qmax, bad_w) | ((unsigned long long)pending << 56);
+      if (pending == 0u) wv |= CD_F_SRC;
     }
     word[o] = wv;
     edges[o] = (uint8_t)emask;
   }
   if (status && (bad_s || bad_w))
     atomicOr(status, (bad_s ? DT_STATUS_BAD_SHARES : 0) | (bad_w ? DT_STATUS_BAD_WEIGHT : 0));
-  if (multi) atomicAdd(&ctl[MF_C_MULTI], multi);
-}
-
-// the window of the next queue round: what was queued before this kernel ran and has not been drained
-__global__ void k_mf_mark(uint32_t *ctl) {
-  const uint32_t lo = ctl[MF_C_HI], hi = ctl[MF_C_TAIL];
-  ctl[MF_C_LO] = lo;
-  ctl[MF_C_HI] = hi;
-  if (hi > lo) {
-    ctl[MF_C_ROUNDS] += 1u;
-    if (hi - lo > ctl[MF_C_HIGH]) ctl[MF_C_HIGH] = hi - lo;
-  }
+  if (multi) atomicAdd(&ctl[CD_C_MULTI], multi);
 }
 
 // floor(T * P / 2^15), T < 2^56, P <= 2^15, in 64 bits
@@ -272,7 +217,7 @@ __device__ __forceinline__ unsigned long long mf_share(unsigned long long T, uin
 // a complete cell that this lane cannot keep goes on the queue; n = its slots (a cell is queued once, so the guard
 // never refuses: it keeps a mistake elsewhere from becoming a store out of bounds)
 __device__ __forceinline__ void mf_enqueue(uint32_t *queue, uint32_t *ctl, uint32_t n, uint32_t c) {
-  const uint32_t i = atomicAdd(&ctl[MF_C_TAIL], 1u);
+  const uint32_t i = atomicAdd(&ctl[CD_C_TAIL], 1u);
   if (i < n) queue[i] = c;
 }
 
@@ -281,7 +226,7 @@ __global__ __launch_bounds__(256) void k_mf_flow(const uint4 *__restrict__ share
                                                  unsigned long long *word, int W, uint32_t n, uint32_t *queue,
                                                  uint32_t *ctl, int cap, int moves_max) {
   __shared__ uint32_t s_ring[MF_STACK * 256];
-  const uint32_t lo = SCAN ? 0u : ctl[MF_C_LO], hi = SCAN ? n : min(ctl[MF_C_HI], n);
+  const uint32_t lo = SCAN ? 0u : ctl[CD_C_LO], hi = SCAN ? n : min(ctl[CD_C_HI], n);
   for (unsigned long long i = (unsigned long long)lo + (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < hi;
        i += (unsigned long long)gridDim.x * 256ull) {
     uint32_t c;
@@ -289,18 +234,18 @@ __global__ __launch_bounds__(256) void k_mf_flow(const uint4 *__restrict__ share
     if (SCAN) {
       c = (uint32_t)i;
       wv = word[c];  // a source's word receives nothing; the flag bits of any word never change
-      if (!(wv & MF_F_SRC)) continue;
+      if (!(wv & CD_F_SRC)) continue;
     } else {
       c = queue[i];
       wv = __hip_atomic_load(&word[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     int held = 0, head = 0;  // the ring: `held` cells from slot `head` on
     for (int moves = 0;;) {  // c is complete and wv is its word
-      uint32_t next = MF_NONE;
+      uint32_t next = CD_NONE;
       unsigned long long nextw = 0ull;
       const uint32_t em = edges[c];
       if (em) {
-        const unsigned long long T = wv & MF_SUM_MASK;
+        const unsigned long long T = wv & CD_SUM_MASK;
         uint32_t P[8];
         mf_unpack(shares[c], P);
         int mk = 0;
@@ -323,16 +268,16 @@ __global__ __launch_bounds__(256) void k_mf_flow(const uint4 *__restrict__ share
 #pragma unroll
         for (int k = 0; k < 8; k++) {
           const int dx = (int)((DI_DX_PACK >> (2 * k)) & 3u) - 1, dy = (int)((DI_DY_PACK >> (2 * k)) & 3u) - 1;
-          add[k] = (k == mk ? T - others : m[k]) - MF_ONE_PEND;
+          add[k] = (k == mk ? T - others : m[k]) - CD_ONE_PEND;
           old[k] = 0ull;
           if (em & (1u << k)) old[k] = atomicAdd(&word[(long long)c + (long long)dy * W + dx], add[k]);
         }
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-          if (((old[k] >> 56) & 0xFull) != 1ull) continue;  // no edge, or donors of the receiver are still to come
+          if (cd_pending(old[k]) != 1ull) continue;  // no edge, or donors of the receiver are still to come
           const int dx = (int)((DI_DX_PACK >> (2 * k)) & 3u) - 1, dy = (int)((DI_DY_PACK >> (2 * k)) & 3u) - 1;
           const uint32_t r = (uint32_t)((long long)c + (long long)dy * W + dx);
-          if (next == MF_NONE) {
+          if (next == CD_NONE) {
             next = r;
             nextw = old[k] + add[k];
           } else if (held < cap) {
@@ -343,18 +288,18 @@ __global__ __launch_bounds__(256) void k_mf_flow(const uint4 *__restrict__ share
         }
       }
       if (++moves >= moves_max) {  // this entry's share of the round is used up: the next round carries on
-        if (next != MF_NONE) mf_enqueue(queue, ctl, n, next);
+        if (next != CD_NONE) mf_enqueue(queue, ctl, n, next);
         while (held > 0) mf_enqueue(queue, ctl, n, s_ring[((head + --held) & (MF_STACK - 1)) * 256 + threadIdx.x]);
         break;
       }
-      if (next != MF_NONE && held > 0) {  // cells wait in the ring: this one goes behind them
+      if (next != CD_NONE && held > 0) {  // cells wait in the ring: this one goes behind them
         if (held < cap)
           s_ring[((head + held++) & (MF_STACK - 1)) * 256 + threadIdx.x] = next;
         else
           mf_enqueue(queue, ctl, n, next);
-        next = MF_NONE;
+        next = CD_NONE;
       }
-      if (next != MF_NONE) {
+      if (next != CD_NONE) {
         c = next;
         wv = nextw;
       } else if (held > 0) {
@@ -373,53 +318,22 @@ __global__ __launch_bounds__(256) void k_mf_out(const double *__restrict__ wt,
                                                 unsigned long long qmax, const uint32_t *__restrict__ ctl,
                                                 double *__restrict__ out, int *__restrict__ status) {
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (c == 0 && status && ctl[MF_C_TAIL] != ctl[MF_C_HI]) atomicOr(status, DT_STATUS_NOT_CONVERGED);
+  cd_not_converged(c == 0, ctl, status);
   if (c >= N) return;
   const unsigned long long wv = word[c];
   double v = -100.0;
-  if (!(wv & MF_F_NODATA) && ((wv >> 56) & 0xFull) == 0ull) {
+  if (!(wv & MF_F_NODATA) && cd_pending(wv) == 0ull) {
     bool ignore = false;
-    const unsigned long long q = mf_quant(wt, c, sbits, qmax, ignore);
-    v = ldexp((double)(long long)((wv & MF_SUM_MASK) - q), -sbits);
+    v = cd_result(wv, cd_quant(wt, c, sbits, qmax, ignore), sbits);
   }
   out[c] = v;
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
-struct MfLayout {
-  uint32_t *ctl;
-  unsigned long long *word;
-  uint32_t *queue;
-  uint8_t *edges;
-  size_t bytes;
-};
-static MfLayout mf_layout(int64_t N, void *scratch) {
-  MfLayout L = {};
-  DtCarver c(scratch);
-  L.ctl = c.take<uint32_t>(MF_C_WORDS);
-  L.word = c.take<unsigned long long>((size_t)N);
-  L.queue = c.take<uint32_t>((size_t)N);
-  L.edges = c.take<uint8_t>((size_t)N);
-  L.bytes = c.bytes();
-  return L;
-}
-size_t dt_mfd_accumulate_scratch(int64_t H, int64_t W) { return mf_layout(H * W, nullptr).bytes; }
-
-static unsigned mf_tiles(int64_t H, int64_t W, int &tiles_x) {
-  tiles_x = (int)((W + DI_TX - 1) / DI_TX);
-  return (unsigned)(((H + DI_TY - 1) / DI_TY) * tiles_x);
-}
-
-// the cells a lane of k_mf_flow holds in its ring: MF_STACK, or n - 1 with the environment variable DT_DBG_MFD_STACK
-// = n > 0 (tests: 1 sends every completion but the one the lane carries on with to the queue)
-static int mf_stack_cap() {
-  static int env = -1;
-  if (env < 0) {
-    const char *e = getenv("DT_DBG_MFD_STACK");
-    env = e ? atoi(e) : 0;
-    if (env < 0) env = 0;
-  }
-  return env > 0 && env - 1 < MF_STACK ? env - 1 : MF_STACK;
+size_t dt_mfd_accumulate_scratch(int64_t H, int64_t W) { return cd_layout(H * W, nullptr, true).bytes; }
+// the control words of the accumulation in `scratch` (device pointer to CD_C_WORDS uint32)
+const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W) {
+  return cd_layout(H * W, scratch, true).ctl;
 }
 
 int dt_launch_mfd_shares(hipStream_t s, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double exponent,
@@ -428,7 +342,7 @@ int dt_launch_mfd_shares(hipStream_t s, const float *dem, const uint8_t *fdr, in
   DT_REQUIRE(exponent >= 0.0 && exponent <= 64.0, "exponent must lie in [0, 64]");
   DT_REQUIRE(((uintptr_t)shares & 15u) == 0, "the share raster must be 16-byte aligned");
   int tiles_x;
-  const unsigned nt = mf_tiles(H, W, tiles_x);
+  const unsigned nt = di_tiles(H, W, tiles_x);
   const int vec_ok = W % 4 == 0 && ((uintptr_t)dem & 15u) == 0 && (!fdr || ((uintptr_t)fdr & 3u) == 0);
   const double ce = contour ? 0.5 : 1.0, co = contour ? 0.35355339059327373 : 1.0;
   const bool int_p = exponent == std::floor(exponent);
@@ -441,40 +355,32 @@ int dt_launch_mfd_shares(hipStream_t s, const float *dem, const uint8_t *fdr, in
   return DT_OK;
 }
 
-// start != 0: the set-up and round 0 first; then `rounds` queue rounds; finish != 0: k_mf_out
+// start, rounds and finish: cd_run's
 int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double *wt, int64_t H, int64_t W,
-                             int frac_bits, int start, int rounds, int finish, void *scratch, size_t scratch_bytes,
-                             double *out, int *status) {
+                             int frac_bits, int start, int rounds, int finish, int stack_cap, void *scratch,
+                             size_t scratch_bytes, double *out, int *status) {
   if (H == 0 || W == 0) return DT_OK;
   const int64_t N = H * W;
-  MfLayout L = mf_layout(N, scratch);
+  const CdLayout L = cd_layout(N, scratch, true);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
   DT_REQUIRE(((uintptr_t)shares & 15u) == 0, "the share raster must be 16-byte aligned");
-  const unsigned long long qmax = (1ull << 52) / (unsigned long long)N;
-  const int cap = mf_stack_cap();
+  const unsigned long long qmax = cd_qmax(N);
+  const int cap = cd_stack_cap(stack_cap, MF_STACK);
   const uint4 *sh = (const uint4 *)shares;
   const dim3 b(256);
-  if (start) {
-    DT_HIP(hipMemsetAsync(L.ctl, 0, sizeof(uint32_t) * MF_C_WORDS, s));
-    int tiles_x;
-    const unsigned nt = mf_tiles(H, W, tiles_x);
-    hipLaunchKernelGGL(k_mf_init, dim3(nt), b, 0, s, sh, wt, (int)H, (int)W, tiles_x, frac_bits, qmax, L.word, L.edges,
-                       L.ctl, status);
-    hipLaunchKernelGGL(k_mf_flow<true>, dim3((unsigned)((N + 255) / 256)), b, 0, s, sh, L.edges, L.word, (int)W,
-                       (uint32_t)N, L.queue, L.ctl, cap, MF_MOVES);
-  }
-  const dim3 gq(dt_capped_grid(N, 2048));
-  for (int r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(k_mf_mark, dim3(1), dim3(1), 0, s, L.ctl);
-    hipLaunchKernelGGL(k_mf_flow<false>, gq, b, 0, s, sh, L.edges, L.word, (int)W, (uint32_t)N, L.queue, L.ctl, cap,
-                       MF_MOVES);
-  }
-  if (finish)
-    hipLaunchKernelGGL(k_mf_out, dim3((unsigned)((N + 255) / 256)), b, 0, s, wt, L.word, (long long)N, frac_bits, qmax,
-                       L.ctl, out, status);
-  return DT_OK;
+  return cd_run(
+      s, N, L.ctl, start, rounds, finish,
+      [&] {
+        int tiles_x;
+        const unsigned nt = di_tiles(H, W, tiles_x);
+        hipLaunchKernelGGL(k_mf_init, dim3(nt), b, 0, s, sh, wt, (int)H, (int)W, tiles_x, frac_bits, qmax, L.word,
+                           L.edges, L.ctl, status);
+      },
+      [&](bool scan, dim3 g) {
+        auto *flow = scan ? k_mf_flow<true> : k_mf_flow<false>;
+        hipLaunchKernelGGL(flow, g, b, 0, s, sh, L.edges, L.word, (int)W, (uint32_t)N, L.queue, L.ctl, cap, MF_MOVES);
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL(k_mf_out, g, b, 0, s, wt, L.word, (long long)N, frac_bits, qmax, L.ctl, out, status);
+      });
 }
-
-// the control words of the accumulation in `scratch` (device pointer to MF_C_WORDS uint32: tail, lo, hi, queue rounds
-// that found work, the largest window, cells with two or more receivers)
-const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W) { return mf_layout(H * W, scratch).ctl; }

@@ -64,7 +64,7 @@ import numpy as np
 
 from . import _args, _lib
 from ._lib import c_f32p, c_f64p, c_i8p, c_i64p, c_u8p, check, ptr
-from .flowacc import _weights_f64
+from .flowacc import _countdown_accumulate, _specific_area
 
 F2PI = np.float32(2.0 * math.pi)
 
@@ -123,16 +123,7 @@ def _angles_f32(angle):
 def _accumulate(angle, weights, frac_bits):
     """-> (acc, w or None, s, info): info = {rounds, queue_high, queued, two_receiver_cells}"""
     a = _angles_f32(angle)
-    H, W = a.shape
-    n = H * W
-    w = None if weights is None else _weights_f64(weights, a.shape)
-    wmax = 1.0 if w is None else (float(w.max()) if n else 0.0)
-    s = _args.frac_bits(n, wmax, frac_bits, " for these weights: N * rint(max(weights) * 2^frac_bits)",
-                        "the default is")
-    acc = np.empty((H, W), np.float64)
-    info = np.zeros(4, np.int64)
-    check(_lib.lib().dt_dinf_accumulate(ptr(a, c_f32p), ptr(w, c_f64p), H, W, s, ptr(acc, c_f64p), ptr(info, c_i64p)))
-    return acc, w, s, dict(zip(("rounds", "queue_high", "queued", "two_receiver_cells"), (int(v) for v in info)))
+    return _countdown_accumulate("dt_dinf_accumulate", a, c_f32p, a.shape, weights, frac_bits, "two_receiver_cells")
 
 
 def accumulate(angle, weights=None, frac_bits=None):
@@ -149,8 +140,7 @@ def specific_catchment_area(angle, px, weights=None, frac_bits=None):
     contour length with the cell itself included, TauDEM's `sca` for unit weights; -100 where accumulate gives -100."""
     p = _args.pixel_size(px)
     acc, w, s, _ = _accumulate(angle, weights, frac_bits)
-    own = 1.0 if w is None else np.ldexp(np.rint(np.ldexp(w, s)), -s)
-    return np.where(acc == -100.0, -100.0, (acc + own) * p)
+    return _specific_area(acc, w, s, p)
 
 
 _STATS = {"ave": 0, "min": 1, "max": 2}

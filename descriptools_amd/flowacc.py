@@ -42,6 +42,29 @@ def _weights_f64(weights, shape=None):
     return d
 
 
+def _countdown_accumulate(entry, raster, raster_type, shape, weights, frac_bits, fourth):
+    """What dinf.accumulate and mfd.accumulate do once their direction raster is validated: the weights, frac_bits,
+    the library's `entry` (by name) on `raster` -> (acc, w or None, s, info), info = {rounds, queue_high, queued, and
+    the count the caller calls `fourth`}"""
+    H, W = shape
+    n = H * W
+    w = None if weights is None else _weights_f64(weights, (H, W))
+    wmax = 1.0 if w is None else (float(w.max()) if n else 0.0)
+    s = _args.frac_bits(n, wmax, frac_bits, " for these weights: N * rint(max(weights) * 2^frac_bits)",
+                        "the default is")
+    acc = np.empty((H, W), np.float64)
+    info = np.zeros(4, np.int64)
+    check(getattr(_lib.lib(), entry)(ptr(raster, raster_type), ptr(w, c_f64p), H, W, s, ptr(acc, c_f64p),
+                                     ptr(info, c_i64p)))
+    return acc, w, s, dict(zip(("rounds", "queue_high", "queued", fourth), (int(v) for v in info)))
+
+
+def _specific_area(acc, w, s, px):
+    """(acc + the cell's own quantised weight) * px, -100 where acc is -100"""
+    own = 1.0 if w is None else np.ldexp(np.rint(np.ldexp(w, s)), -s)
+    return np.where(acc == -100.0, -100.0, (acc + own) * px)
+
+
 def weight_frac_bits(weights):
     """The fixed-point scale accumulate_weighted uses by default: the largest s for which every partial sum of the
     quantised weights rint(w * 2^s) over the raster's N cells stays <= 2^52,

@@ -37,8 +37,8 @@ import math
 import numpy as np
 
 from . import _args, _lib
-from ._lib import c_f32p, c_f64p, c_i64p, c_u8p, c_u16p, check, ptr
-from .flowacc import _weights_f64
+from ._lib import c_f32p, c_u8p, c_u16p, check, ptr
+from .flowacc import _countdown_accumulate, _specific_area
 
 UNIT = 32768
 NODATA_SLOT = 0xFFFF
@@ -108,16 +108,8 @@ def _shares_u16(shares):
 def _accumulate(shares, weights, frac_bits):
     """-> (acc, w or None, s, info): info = {rounds, queue_high, queued, multi_receiver_cells}"""
     sh = _shares_u16(shares)
-    H, W = sh.shape[:2]
-    n = H * W
-    w = None if weights is None else _weights_f64(weights, (H, W))
-    wmax = 1.0 if w is None else (float(w.max()) if n else 0.0)
-    s = _args.frac_bits(n, wmax, frac_bits, " for these weights: N * rint(max(weights) * 2^frac_bits)",
-                        "the default is")
-    acc = np.empty((H, W), np.float64)
-    info = np.zeros(4, np.int64)
-    check(_lib.lib().dt_mfd_accumulate(ptr(sh, c_u16p), ptr(w, c_f64p), H, W, s, ptr(acc, c_f64p), ptr(info, c_i64p)))
-    return acc, w, s, dict(zip(("rounds", "queue_high", "queued", "multi_receiver_cells"), (int(v) for v in info)))
+    return _countdown_accumulate("dt_mfd_accumulate", sh, c_u16p, sh.shape[:2], weights, frac_bits,
+                                 "multi_receiver_cells")
 
 
 def accumulate(shares, weights=None, frac_bits=None):
@@ -135,5 +127,4 @@ def specific_catchment_area(shares, px, weights=None, frac_bits=None):
     np.log(sca / np.tan(slope_radians)) on it."""
     p = _args.pixel_size(px)
     acc, w, s, _ = _accumulate(shares, weights, frac_bits)
-    own = 1.0 if w is None else np.ldexp(np.rint(np.ldexp(w, s)), -s)
-    return np.where(acc == -100.0, -100.0, (acc + own) * p)
+    return _specific_area(acc, w, s, p)

@@ -285,6 +285,51 @@ def test_accumulate_d8_shares_equal_flowacc():
     _bits_equal("D8 shares", got, acc.astype(np.float64))
 
 
+def _short_path_d8(H, W, nodata_pct):
+    """D8 codes down an egg-crate surface with basins of 16 x 16 cells (the lowest neighbour when it is strictly
+    lower, so no cycle; 0 in the pits), `nodata_pct` % of the cells nodata -> (fdr, nodata mask).  Checked here: no
+    flow path has more than 32 cells, the fewest either op lets a start complete in a round (MF_MOVES; DI_MOVES is
+    128), and a D8 cell completes at most one receiver -- so nothing is queued, whatever the order of arrival."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    z = np.cos(2 * np.pi * yy / 16) + np.cos(2 * np.pi * xx / 16)
+    nod = np.random.default_rng(12).random((H, W)) < nodata_pct / 100
+    steps = ((0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1), (1, 0), (1, 1))  # (dy, dx) by octant
+    zp = np.pad(z, 1, constant_values=np.inf)
+    nb = np.stack([zp[1 + dy:1 + dy + H, 1 + dx:1 + dx + W] for dy, dx in steps])
+    k = nb.argmin(axis=0)
+    flows = nb.min(axis=0) < z
+    fdr = np.where(flows, np.array(mfd.OCTANT_CODES, np.uint8)[k], 0).astype(np.uint8)
+    cell = np.arange(H * W).reshape(H, W)
+    to = cell + np.array([dy * W + dx for dy, dx in steps])[k]
+    nxt = np.where(flows & ~nod, to, cell).reshape(-1)
+    nxt = np.where(nod.reshape(-1)[nxt], cell.reshape(-1), nxt)  # a share into nodata leaves the domain
+    pos = cell.reshape(-1)
+    for _ in range(31):
+        pos = nxt[pos]
+    assert (nxt[pos] == pos).all(), "a flow path has more than 32 cells"
+    return fdr, nod
+
+
+def test_accumulate_d8_equals_dinf_byte_for_byte():
+    """the two ops run one countdown (dt_countdown.h): on the same D8 raster, as float32(k pi / 4) angles and as
+    single-receiver shares, they give the same bytes (the reference's) and neither queues a cell"""
+    import _dinf_ref
+    from descriptools_amd import dinf
+    fdr, nod = _short_path_d8(33, 130, 5)
+    assert 0.03 < nod.mean() < 0.07 and (fdr[~nod] != 0).mean() > 0.9
+    a = _dinf_ref.d8_angles(fdr)
+    a[nod] = -100
+    s = mfd.d8_shares(fdr)
+    s[nod] = mfd.NODATA_SLOT
+    ref = R.accumulate(s, None, 0)
+    assert (ref[nod] == -100).all() and (ref[~nod] >= 0).all() and ref.max() >= 16
+    acc_d, _, _, info_d = dinf._accumulate(a, None, 0)
+    acc_m, _, _, info_m = mfd._accumulate(s, None, 0)
+    _bits_equal("MFD on D8 shares", acc_m, ref)
+    _bits_equal("D-infinity on D8 angles against MFD on D8 shares", acc_d, acc_m)
+    assert info_d["queued"] == 0 and info_m["queued"] == 0, (info_d, info_m)
+
+
 def test_mass_conservation_with_nodata():
     """sum of q over the live cells = the totals held by the cells without an edge + what left the domain; the left
     side from the reference's bookkeeping, the right side from the device's raster"""

@@ -12,8 +12,9 @@ dead or stay unsettled, the tile visits per tile and the bytes a visit moves, co
 The device time comes from a second run of its own, `rocprofv3 --kernel-trace --stats -- python
 tools/dinf_distance_bench.py --profile-only` (one call of each op), summarised by `--trace DIR`: the dispatches are
 grouped into calls at each k_dd_init, per call the span from the first launch to the last end, the three kernels'
-totals and the rounds one by one (four launches, one per colour, each); the accumulation's k_di_* and the flow-path
-kernels of flow_hand_index beside them.  Prints one JSON line (and writes it to --out)."""
+totals and the rounds one by one (four launches, one per colour, each); the accumulation's k_di_* with the countdown's
+k_cd_mark (no other op of this tool's run launches it) and the flow-path kernels of flow_hand_index beside them.
+Prints one JSON line (and writes it to --out)."""
 import ctypes
 import csv
 import glob
@@ -62,8 +63,8 @@ def summarise_trace(d, out_txt):
     lines.append("other kernels: total ms, launches")
     for k, (tot, n) in sorted(other.items(), key=lambda kv: -kv[1][0])[:24]:
         lines.append("%9.3f %4d %s" % (tot * 1e-6, n, k))
-    for tag, pat in (("dinf.accumulate kernels (k_di_*)", "k_di_"), ("flow_hand_index kernels (k_fh_*, k_i32_to_i64)",
-                                                                      ("k_fh_", "k_i32_to_i64"))):
+    for tag, pat in (("dinf.accumulate kernels (k_di_*, k_cd_mark)", ("k_di_", "k_cd_mark")),
+                     ("flow_hand_index kernels (k_fh_*, k_i32_to_i64)", ("k_fh_", "k_i32_to_i64"))):
         pats = (pat,) if isinstance(pat, str) else pat
         tot = sum(t1 - t0 for name, t0, t1 in ker if any(p in name for p in pats))
         lines.append("%s in all: %.3f ms" % (tag, tot * 1e-6))

@@ -4,7 +4,8 @@ For each source file, both trees are compiled with build.py's flags plus `--cuda
 -Rpass-analysis=kernel-resource-usage` (no GPU needed).  A kernel's instructions are the lines of its body up to its
 .Lfunc_end label, directives and comments dropped, local labels normalised; IDENTICAL = the same instruction text.  The
 resource-usage remarks give VGPRs, LDS, scratch and occupancy per kernel.  Kernels only in the new build are listed as
-added; a kernel of the base build that is missing or differs is reported, and the exit status is 1.
+added; a kernel of the base build that is missing (with the base build's figures, for a kernel that moved or was
+renamed) or differs is reported, and the exit status is 1.  A file that only one tree has counts as one without kernels.
 
 usage: python tools/isa_compare.py BASE_TREE NEW_TREE file.hip [file.hip ...] [--out report.txt]"""
 import os
@@ -23,6 +24,8 @@ LABEL = re.compile(r"\.L[A-Za-z_]*\d+(_\d+)?")
 def compile_asm(tree, src, out_dir):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     s = os.path.join(out_dir, os.path.basename(src) + ".s")
+    if not os.path.exists(os.path.join(tree, "descriptools_amd", "csrc", src)):
+        return "", ""
     flags = [f for f in FLAGS if f not in ("-fPIC", "-Wall")]
     r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
                                           os.path.join(tree, "descriptools_amd", "csrc", src), "-o", s],
@@ -78,7 +81,9 @@ def main():
             lines.append("%s: kernels in base %d, in this change %d, added %s" % (f, len(ka), len(kb), added))
             for n in sorted(ka):
                 if n not in kb:
-                    lines.append("  MISSING   %s" % n)
+                    r = ra.get(n, {})
+                    lines.append("  MISSING   %-70s instr %5d        VGPRs %3s LDS %6s B scratch %s waves/SIMD %s" % (
+                        n, len(ka[n]), r.get("VGPRs"), r.get("LDS"), r.get("ScratchSize"), r.get("Occupancy")))
                     bad += 1
                     continue
                 same = ka[n] == kb[n]
@@ -90,7 +95,7 @@ def main():
                     r.get("ScratchSize"), r.get("Occupancy"), "" if rsame else "  (resources differ: %s)" % ra.get(n)))
             for n in added:
                 r = rb.get(n, {})
-                lines.append("  new       %-70s instr %5d  VGPRs %3s LDS %6s B scratch %s waves/SIMD %s" % (
+                lines.append("  new       %-70s instr       %5d  VGPRs %3s LDS %6s B scratch %s waves/SIMD %s" % (
                     n, len(kb[n]), r.get("VGPRs"), r.get("LDS"), r.get("ScratchSize"), r.get("Occupancy")))
     lines.append("base kernels that differ or are missing: %d" % bad)
     text = "\n".join(lines) + "\n"
