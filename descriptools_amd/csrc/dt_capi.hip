@@ -749,6 +749,25 @@ extern "C" int dt_dev_mfd_accumulate_info(dt_ctx *c, int64_t *info4) {
   return dev_countdown_info(c, DT_OWNER_MFD, "MFD", dt_mfd_accumulate_ctl, info4);
 }
 
+static int dt_check_terrain(int radius, double sx, double sy, double sz) {
+  DT_REQUIRE(radius >= 1 && radius <= DT_TERRAIN_RADIUS_MAX, "radius must lie in [1, 32]");
+  DT_REQUIRE(std::isfinite(sx) && std::isfinite(sy) && std::isfinite(sz), "the sun vector must be finite");
+  return DT_OK;
+}
+extern "C" int dt_dev_terrain(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, int radius, double sx,
+                              double sy, double sz, float *gradient, float *aspect, float *profile, float *plan,
+                              float *tangential, float *mean, float *laplacian, float *hillshade) {
+  DT_DEV(d, c, H, W, px);
+  DT_TRY(dt_check_terrain(radius, sx, sy, sz));
+  if (H * W == 0) return DT_OK;
+  float *const out[DT_TERRAIN_OUTPUTS] = {gradient, aspect, profile, plan, tangential, mean, laplacian, hillshade};
+  bool any = false;
+  for (float *o : out) any = any || o != nullptr;
+  DT_REQUIRE(any, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  return d.done(dt_launch_terrain(c->stream, dem, H, W, px, radius, sx, sy, sz, out));
+}
+
 // reaches: reach ids and flat indices travel in 31 bits
 static int dt_check_reach_count(int64_t R) {
   DT_REQUIRE(R >= 0 && R < (1ll << 31), "the number of reaches must lie in [0, 2^31)");
@@ -2155,6 +2174,28 @@ extern "C" int dt_mfd_accumulate(const uint16_t *shares, const double *w, int64_
              "a share word is not eight 0xFFFF and has a slot above 32768 or a sum that is neither 0 nor 32768");
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
   if (info4) memcpy(info4, got, sizeof(got));
+  return hc.finish();
+}
+
+extern "C" int dt_terrain(const float *dem, int64_t H, int64_t W, double px, int radius, double sx, double sy,
+                          double sz, float *gradient, float *aspect, float *profile, float *plan, float *tangential,
+                          float *mean, float *laplacian, float *hillshade) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_TRY(dt_check_terrain(radius, sx, sy, sz));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  float *const host[DT_TERRAIN_OUTPUTS] = {gradient, aspect, profile, plan, tangential, mean, laplacian, hillshade};
+  bool any = false;
+  for (float *o : host) any = any || o != nullptr;
+  DT_REQUIRE(any, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  float *d[DT_TERRAIN_OUTPUTS];
+  for (int o = 0; o < DT_TERRAIN_OUTPUTS; o++) d[o] = hc.out(host[o], n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_terrain(hc.c, d_dem, H, W, px, radius, sx, sy, sz, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]));
   return hc.finish();
 }
 

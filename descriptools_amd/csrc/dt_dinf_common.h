@@ -1,5 +1,6 @@
 // dt_dinf_common.h -- what the kernels on D-infinity's tile geometry share (dt_dinf.hip: direction and contributing
-// area; dt_dinf_dist.hip: distance to the stream; dt_mfd.hip: MFD shares and contributing area): the 128 x 8 staging
+// area; dt_dinf_dist.hip: distance to the stream; dt_mfd.hip: MFD shares and contributing area; dt_terrain.hip: the
+// radius-1 terrain attributes): the 128 x 8 staging
 // tile with its one-cell halo and its launch geometry, the octant steps, the validity of a height, the D8 codes of a
 // lane's four cells and the decoding of an angle into receivers (descriptools_amd/dinf.py holds the definition).
 #pragma once

@@ -313,6 +313,17 @@ int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double
 // the accumulation's control words in `scratch`, as dt_dinf_accumulate_ctl's (cells with two or more receivers)
 const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 
+// Local terrain attributes (dt_terrain.hip; terrain.py holds the definition): the quadratic fitted by least squares
+// over the (2 radius + 1)^2 window of every cell, from separable float64 moment sums, and what is derived from its
+// first and second derivatives.  out[8] = gradient, aspect, profile, plan, tangential, mean, laplacian, hillshade
+// (DT_TERRAIN_OUTPUTS): a NULL entry is neither computed nor stored, at least one is given; -100 wherever the window is
+// not complete.  (sx, sy, sz) is the unit vector to the sun (east, north, up).  1 <= radius <= DT_TERRAIN_RADIUS_MAX.
+// One launch, no scratch; nothing synchronises.  H * W < 2^31.
+#define DT_TERRAIN_OUTPUTS 8
+#define DT_TERRAIN_RADIUS_MAX 32
+int dt_launch_terrain(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, int radius, double sx,
+                      double sy, double sz, float *const out[DT_TERRAIN_OUTPUTS]);
+
 // Euclidean proximity (dt_proximity.hip): for every cell the nearest source (river == 1 and, with nod, nod > -100) by
 // exact squared distance, ties to the smallest flat index -> distance = float32(px * sqrt(float64(d2))) and indices =
 // the source's flat index; -100 where nod <= -100 and when there is no source.  nod may be NULL.  The row pass, the

@@ -258,6 +258,28 @@ int dt_mfd_shares(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, do
  * cells one round drained, cells queued in all, cells with two or more receivers}. */
 int dt_mfd_accumulate(const uint16_t *shares, const double *w, int64_t H, int64_t W, int frac_bits, double *acc,
                       int64_t *info4);
+/* Net-new: local terrain attributes of the quadratic fitted by least squares over the (2 radius + 1)^2 window of
+ * every cell (Evans 1980, Wood 1996; descriptools_amd/terrain.py holds the full definition).  A height is valid when
+ * it is finite and > -100; a cell has a value when all n^2 heights of its window (n = 2 radius + 1) lie in the raster
+ * and are valid, and holds -100 in every output otherwise.  All arithmetic is IEEE float64, sums from their first term
+ * in ascending offset (i: columns, east positive; j: rows, south positive; -radius .. radius), the integer factor
+ * converted and multiplied before each addition: C0 = sum_j z, C1 = sum_j (-j) z, C2 = sum_j (j j) z down a column,
+ * then M00 = sum_i C0, M10 = sum_i i C0, M20 = sum_i (i i) C0, M01 = sum_i C1, M11 = sum_i i C1, M02 = sum_i C2 along
+ * the row.  With S2 = r(r+1)(2r+1)/3, S4 = r(r+1)(2r+1)(3r^2+3r-1)/15, D = n S4 - S2^2, h = px: den1 = (double)(n S2) h,
+ * den2 = (double)(S2^2) (h h), den3 = (double)(n D) (h h); p = M10 / den1, q = M01 / den1 (x east, y north),
+ * s = M11 / den2, r = 2 ((n M20 - S2 M00) / den3), t = 2 ((n M02 - S2 M00) / den3).  w = p p + q q, g1 = 1 + w,
+ * pq2 = 2 (p q); each output is (float) of: gradient sqrt(w) (rise over run); aspect, degrees clockwise from north of
+ * the downslope direction: a = atan2(-p, -q) 57.29577951308232, + 360 when a < 0, 0 when (float)a >= 360, -1 when
+ * w == 0; profile -(((p p) r + pq2 s) + (q q) t) / (w (g1 sqrt(g1))); plan -(((q q) r - pq2 s) + (p p) t) / (w sqrt(w));
+ * tangential the same numerator over w sqrt(g1) (the three are 0 when w == 0); mean -(((1 + q q) r - pq2 s) +
+ * (1 + p p) t) / (2 (g1 sqrt(g1))); laplacian r + t; hillshade ((sz - p sx) - q sy) / sqrt(g1), 0 when that is not > 0,
+ * (sx, sy, sz) the unit vector to the sun (east, north, up).  Positive curvature is convex.  Every output but aspect is
+ * a pure function of the heights in this association: bit for bit the numpy reference of the test suite.  Each output
+ * may be NULL (it is then neither computed nor stored) but not all of them.  radius must lie in [1, 32], the sun
+ * vector must be finite; rasters of 2^31 cells or more and a px that is not finite and > 0 are refused. */
+int dt_terrain(const float *dem, int64_t H, int64_t W, double px, int radius, double sx, double sy, double sz,
+               float *gradient, float *aspect, float *profile, float *plan, float *tangential, float *mean,
+               float *laplacian, float *hillshade);
 /* Net-new: exact Euclidean proximity to the river network.  A source is a cell with river == 1 that is not nodata;
  * nodata is a cell with nod <= -100, where nod (may be NULL: no nodata) is any float32 raster of the shape: a float32
  * DEM, or for heights float32 cannot hold the -100 / 0 mask of the DEM's own comparison (descriptools_amd._lib.
@@ -496,6 +518,13 @@ int dt_dev_mfd_shares(dt_ctx *ctx, const float *dem, const uint8_t *fdr, int64_t
 int dt_dev_mfd_accumulate(dt_ctx *ctx, const uint16_t *shares, const double *w, int64_t rows, int64_t cols,
                           int frac_bits, int rounds, double *acc);
 int dt_dev_mfd_accumulate_info(dt_ctx *ctx, int64_t *info4);
+/* dt_terrain on device rasters (rows x cols = H x W), on the context's stream: one launch, no synchronisation, and
+ * none of the context's scratch (a two-phase op started on the context stays continuable).  Output pointers may be
+ * NULL, not all of them; a radius outside [1, 32] and a sun vector that is not finite are DT_EINVAL; H * W == 0 is
+ * DT_OK.  16-byte aligned rasters with cols % 4 == 0 are read and written 16 bytes at a time at radius 1. */
+int dt_dev_terrain(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double px, int radius, double sx,
+                   double sy, double sz, float *gradient, float *aspect, float *profile, float *plan,
+                   float *tangential, float *mean, float *laplacian, float *hillshade);
 /* The reach calls on device rasters, on the context's stream: none synchronises.  idx is int32 (idx_bytes 4, the
  * resident chain's raster) or int64 (8); n_reaches (may be NULL) is one int64 on the device; heads entries from R on
  * are left as they were.  dt_dev_reach_tables takes `stages` from the host (they travel as kernel arguments) and the
