@@ -768,6 +768,25 @@ extern "C" int dt_dev_terrain(dt_ctx *c, const float *dem, int64_t H, int64_t W,
   return d.done(dt_launch_terrain(c->stream, dem, H, W, px, radius, sx, sy, sz, out));
 }
 
+// lines of sight (dt_horizon.hip): the ranges of radius, skip and the flatness tangent
+static int dt_check_horizon(int radius, int skip, double flat_tan) {
+  DT_REQUIRE(radius >= 1 && radius <= DT_HORIZON_RADIUS_MAX, "radius must lie in [1, 64]");
+  DT_REQUIRE(skip >= 0 && skip < radius, "skip must lie in [0, radius - 1]");
+  DT_REQUIRE(std::isfinite(flat_tan) && flat_tan >= 0.0, "flat_tan must be finite and >= 0");
+  return DT_OK;
+}
+extern "C" int dt_dev_horizon(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, int radius, int skip,
+                              double flat_tan, uint8_t *landform, uint16_t *pattern, float *positive, float *negative,
+                              float *sky_view) {
+  DT_DEV(d, c, H, W, px);
+  DT_TRY(dt_check_horizon(radius, skip, flat_tan));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(landform || pattern || positive || negative || sky_view, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  return d.done(dt_launch_horizon(c->stream, dem, H, W, px, radius, skip, flat_tan, landform, pattern, positive,
+                                  negative, sky_view));
+}
+
 // reaches: reach ids and flat indices travel in 31 bits
 static int dt_check_reach_count(int64_t R) {
   DT_REQUIRE(R >= 0 && R < (1ll << 31), "the number of reaches must lie in [0, 2^31)");
@@ -2196,6 +2215,25 @@ extern "C" int dt_terrain(const float *dem, int64_t H, int64_t W, double px, int
   for (int o = 0; o < DT_TERRAIN_OUTPUTS; o++) d[o] = hc.out(host[o], n);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_terrain(hc.c, d_dem, H, W, px, radius, sx, sy, sz, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]));
+  return hc.finish();
+}
+
+extern "C" int dt_horizon(const float *dem, int64_t H, int64_t W, double px, int radius, int skip, double flat_tan,
+                          uint8_t *landform, uint16_t *pattern, float *positive, float *negative, float *sky_view) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_TRY(dt_check_horizon(radius, skip, flat_tan));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(landform || pattern || positive || negative || sky_view, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  uint8_t *d_form = hc.out(landform, n);
+  uint16_t *d_pat = hc.out(pattern, n);
+  float *d_pos = hc.out(positive, n), *d_neg = hc.out(negative, n), *d_sky = hc.out(sky_view, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_horizon(hc.c, d_dem, H, W, px, radius, skip, flat_tan, d_form, d_pat, d_pos, d_neg, d_sky));
   return hc.finish();
 }
 

@@ -324,6 +324,19 @@ const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 int dt_launch_terrain(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, int radius, double sx,
                       double sy, double sz, float *const out[DT_TERRAIN_OUTPUTS]);
 
+// Lines of sight (dt_horizon.hip; horizon.py holds the definition): from every cell the largest and the smallest tangent
+// of the elevation angle to the samples skip + 1 .. radius of each of the eight compass directions, t = (z_k - z0) *
+// (1 / (k step)) in float64 with the reciprocals tabulated here on the host and handed to the kernel by value, and what
+// derives from them: landform (uint8, 1 .. 10) and pattern (uint16, the eight ternary digits against flat_tan = tan of
+// the flatness angle), positive and negative openness (float32, radians) and the sky-view factor (float32).  A NULL
+// output is neither computed nor stored, at least one is given; 0 / 65535 / -100 wherever the centre is not valid or a
+// direction has no valid sample.  1 <= radius <= DT_HORIZON_RADIUS_MAX, 0 <= skip < radius, flat_tan finite and >= 0.
+// One launch, no scratch; nothing synchronises.  H * W < 2^31.
+#define DT_HORIZON_RADIUS_MAX 64
+int dt_launch_horizon(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, int radius, int skip,
+                      double flat_tan, uint8_t *landform, uint16_t *pattern, float *positive, float *negative,
+                      float *sky_view);
+
 // Euclidean proximity (dt_proximity.hip): for every cell the nearest source (river == 1 and, with nod, nod > -100) by
 // exact squared distance, ties to the smallest flat index -> distance = float32(px * sqrt(float64(d2))) and indices =
 // the source's flat index; -100 where nod <= -100 and when there is no source.  nod may be NULL.  The row pass, the

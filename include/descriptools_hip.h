@@ -280,6 +280,30 @@ int dt_mfd_accumulate(const uint16_t *shares, const double *w, int64_t H, int64_
 int dt_terrain(const float *dem, int64_t H, int64_t W, double px, int radius, double sx, double sy, double sz,
                float *gradient, float *aspect, float *profile, float *plan, float *tangential, float *mean,
                float *laplacian, float *hillshade);
+/* Net-new: what a cell sees along eight lines of sight -- geomorphon landforms and patterns (Jasiewicz & Stepinski
+ * 2013), positive and negative topographic openness (Yokoyama et al. 2002), the sky-view factor (Zaksek et al. 2011);
+ * descriptools_amd/horizon.py holds the full definition.  A height is valid when it is finite and > -100.  Directions
+ * d = 0..7 = N, NE, E, SE, S, SW, W, NW with row / column steps (-1,0) (-1,1) (0,1) (1,1) (1,0) (1,-1) (0,-1) (-1,-1).
+ * For a valid centre z0 the samples of direction d are the cells k = skip + 1 .. radius steps away that lie in the
+ * raster and are valid; cells that are not are skipped, the line of sight goes on past them.  IEEE float64 on the
+ * float32 heights: step[0] = px, step[1] = px * 1.4142135623730951 (diagonals), inv[c][k] = 1.0 / ((double)k *
+ * step[c]) (tabulated on the host by the entry), t = ((double)z_k - (double)z0) * inv[c][k] -- a multiplication by the
+ * tabulated reciprocal, by definition; tmax_d / tmin_d = the largest / smallest t of direction d.  A cell has a value
+ * iff its centre is valid and every direction has a sample; any other cell holds 0 in landform, 65535 in pattern and
+ * -100 in the float outputs.  Digit of a direction against flat_tan = tan(flatness angle): +1 if |tmax| > |tmin| and
+ * |tmax| > flat_tan; else -1 if |tmin| > flat_tan and |tmax| <= |tmin|; else 0.  pattern = sum_d (digit_d + 1) 3^d
+ * (0..6560).  landform = 1 flat, 2 peak, 3 ridge, 4 shoulder, 5 spur, 6 slope, 7 hollow, 8 footslope, 9 valley,
+ * 10 pit, from the numbers m of -1 digits and p of +1 digits by the table of horizon.py (rows m = 0..8, columns
+ * p = 0..8-m: 1 1 1 8 8 9 9 9 10 / 1 1 8 8 8 9 9 9 / 1 4 6 6 7 7 9 / 4 4 6 6 6 7 / 4 4 5 6 6 / 3 3 5 5 / 3 3 3 /
+ * 3 3 / 2).  positive = (float)((sum_d (pi/2 - atan(tmax_d))) / 8.0), negative = (float)((sum_d (pi/2 + atan(tmin_d)))
+ * / 8.0), radians, summed over d = 0..7 in order; sky_view = (float)(1.0 - (sum_d s_d) / 8.0) with s_d = tmax_d /
+ * sqrt(1.0 + tmax_d tmax_d) when tmax_d > 0, else 0.  landform, pattern and sky_view are pure functions of the heights
+ * in this association: bit for bit the numpy reference of the test suite; the two openness rasters hold eight atan
+ * each and are within one float32 spacing of it.  Each output may be NULL (it is then neither computed nor stored)
+ * but not all of them.  radius must lie in [1, 64], skip in [0, radius - 1], flat_tan must be finite and >= 0;
+ * rasters of 2^31 cells or more and a px that is not finite and > 0 are refused. */
+int dt_horizon(const float *dem, int64_t H, int64_t W, double px, int radius, int skip, double flat_tan,
+               uint8_t *landform, uint16_t *pattern, float *positive, float *negative, float *sky_view);
 /* Net-new: exact Euclidean proximity to the river network.  A source is a cell with river == 1 that is not nodata;
  * nodata is a cell with nod <= -100, where nod (may be NULL: no nodata) is any float32 raster of the shape: a float32
  * DEM, or for heights float32 cannot hold the -100 / 0 mask of the DEM's own comparison (descriptools_amd._lib.
@@ -525,6 +549,14 @@ int dt_dev_mfd_accumulate_info(dt_ctx *ctx, int64_t *info4);
 int dt_dev_terrain(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double px, int radius, double sx,
                    double sy, double sz, float *gradient, float *aspect, float *profile, float *plan,
                    float *tangential, float *mean, float *laplacian, float *hillshade);
+/* dt_horizon on device rasters (rows x cols = H x W), on the context's stream: one launch, no device allocation, no
+ * copy (the 2 x 64 reciprocal table travels as a kernel argument), no synchronisation, and none of the context's
+ * scratch, so it may stand anywhere on a context's stream.  Checked in this order: the context, shape and px, radius /
+ * skip / flat_tan (DT_EINVAL outside [1, 64], [0, radius - 1], finite and >= 0); H * W == 0 is DT_OK; then at least
+ * one output, a non-NULL dem. */
+int dt_dev_horizon(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double px, int radius, int skip,
+                   double flat_tan, uint8_t *landform, uint16_t *pattern, float *positive, float *negative,
+                   float *sky_view);
 /* The reach calls on device rasters, on the context's stream: none synchronises.  idx is int32 (idx_bytes 4, the
  * resident chain's raster) or int64 (8); n_reaches (may be NULL) is one int64 on the device; heads entries from R on
  * are left as they were.  dt_dev_reach_tables takes `stages` from the host (they travel as kernel arguments) and the
