@@ -41,6 +41,11 @@ WRITE_GROUPS = (("slope", "ti", "mti"), ("fdist", "idx", "hand", "gfi", "lnhlh")
 # the marked cells (microseconds on terrain): dem 4 + fac 4 are no longer read a second time, and a per-op rate
 # computed from the 20 B/cell of "slope_twi" means nothing for that chain.  The kernel names are the r4
 # profile's, not the live ones: the stencil pair is k_slope_twi<true, false, int> and k_slope_twi_fix<int> today.
+# Since round 13 a single raster's "flowacc_flowhand_local" (this chain, external_fdr and float64 heights included; not
+# the ranks) runs the walk form, k_fa3fh1w_twi / k_fa3fh1w<ND>: HAND's half walks the fed perimeter entries and writes
+# no word cache, and k_fh_tile1 is not launched; "flowhand_gfi_finish" is then k_fh_tile3_solve, which reads the codes
+# and the river mask (2 B/cell in place of the 4 B/cell cache) and solves the tile itself, followed by
+# k_fh_tile1_marked and k_fh_tile3_marked for the tiles it gives up (none on terrain) -- DESIGN.md 4.3.
 OPS = (
     ("d8", 5, ["k_d8<false>", "k_d8_fix"]),
     ("downslope", 9, ["k_downslope_win<24>"]),

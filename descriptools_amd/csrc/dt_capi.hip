@@ -1382,9 +1382,10 @@ static int dev_flowacc_river_flowhand_local(dt_ctx *c, const uint8_t *fdr, const
   d.scratch(need, need2, &scr, &scr2);
   DT_TRY(d.rc);
   DT_TRY(dt_launch_fa_local(c->stream, d.w, fdr, scr, need, acc32, 0));
+  int walked = 0;  // the launcher's choice of HAND's pass 1 (the walk form where the fused tile pass applies)
   DT_TRY(d.done(dt_launch_fa_finish_fh_local(c->stream, d.w, fdr, dem, scr, scr2, need2, nullptr, threshold, acc32, 0,
-                                             river, c->status, nod4, dt_nodata4_ld(W), twi)));
-  dt_scratch_claim(c, DT_OWNER_HAND, H, W, scr2);
+                                             river, c->status, nod4, dt_nodata4_ld(W), twi, &walked)));
+  dt_scratch_claim(c, walked ? DT_OWNER_HAND_WALK : DT_OWNER_HAND, H, W, scr2);
   return DT_OK;
 }
 extern "C" int dt_dev_flowacc_river_flowhand_local(dt_ctx *c, const uint8_t *fdr, const float *dem, int64_t H, int64_t W,
@@ -1514,13 +1515,16 @@ static int dev_flowhand_finish_w(dt_ctx *c, const dt_window *win, const float *d
   DT_REQUIRE(!fused || (dem && acc && gfi && lnhlh), "NULL raster");
   DT_REQUIRE(!res_ok || (res_nc && res_nd && rem_gidx && rem_zr && rem_ar), "incomplete rank-exit results");
   const DtScratchClaim *k;
-  DT_TRY(dt_scratch_claimed(c, DT_OWNER_HAND, &d.w, false,
+  // the claim says which form pass 1 took: the walk form's is the single raster's, whole
+  const bool walked = c->claim.owner == DT_OWNER_HAND_WALK && d.w.halo == 0 && d.w.gy0 == 0 && d.w.gx0 == 0 &&
+                      d.w.H == d.w.Hg && d.w.W == d.w.Wg;
+  DT_TRY(dt_scratch_claimed(c, walked ? DT_OWNER_HAND_WALK : DT_OWNER_HAND, &d.w, false,
                             "flowhand finish without a matching dt_dev_flowhand_local_w on this context (another call "
                             "has used the context's scratch in between)", &k));
   return d.done(dt_launch_fh_finish(c->stream, d.w, dem, fdr, river, acc, acc64, px, k->ptr, res_ok, res_nc, res_nd,
                                     (const long long *)rem_gidx, rem_zr, (const long long *)rem_ar, fdist, idx32,
                                     (long long *)idx64, hand, a_river, fused ? gfi : nullptr, fused ? lnhlh : nullptr,
-                                    n_gfi, b, px));
+                                    n_gfi, b, px, walked ? 1 : 0));
 }
 extern "C" int dt_dev_flowhand_finish_w(dt_ctx *c, const dt_window *win, const float *dem, const uint8_t *fdr,
                                         const int8_t *river, const int32_t *acc32, double px,

@@ -60,7 +60,9 @@ int dt_debug_get(int key);
 // Which multi-call op's state lives in the context's `scratch`, and where.  The op's first phase claims it (*_local_w,
 // the first rounds of dt_dev_dinf_accumulate), every dt_scratch_reset drops the claim, the later phases (*_finish_w, a
 // continuation) require it -- dt_scratch_claim / dt_scratch_claimed in dt_capi.hip are the only code that touches it.
-enum DtScratchOwner { DT_OWNER_NONE = 0, DT_OWNER_FLOWACC, DT_OWNER_HAND, DT_OWNER_DINF, DT_OWNER_MFD };
+// DT_OWNER_HAND_WALK: HAND's state as the walk form of pass 1 leaves it (node words of the fed entries, no word cache: the
+// last pass solves the tiles) -- the first phase that launched that form claims it, so the last pass cannot be told wrong.
+enum DtScratchOwner { DT_OWNER_NONE = 0, DT_OWNER_FLOWACC, DT_OWNER_HAND, DT_OWNER_DINF, DT_OWNER_MFD, DT_OWNER_HAND_WALK };
 struct DtScratchClaim {
   DtScratchOwner owner;
   int64_t h, w;       // the core shape of the raster the state belongs to

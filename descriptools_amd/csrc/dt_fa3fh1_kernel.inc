@@ -9,11 +9,20 @@
 // one patch), which k_d8_slope has initialised with the slope flags and k_slope_twi_fix consumes afterwards.  One
 // text for both, through the preprocessor, so that k_fa3fh1<ND> stays the code it was instruction for instruction
 // (tools/isa_compare.py).
+// FA3_WALK 1 (k_fa3fh1w<ND>, k_fa3fh1w_twi; included twice more): the same accumulation half, and HAND's half as
+// walks of the fed perimeter entries (fh_walk_body) instead of the tile solve -- no cache words, the last pass solves.
+#if FA3_WALK
+#define FA3_NAME(n) n##w
+#define FA3_NAME_TWI(n) n##w_twi
+#else
+#define FA3_NAME(n) n
+#define FA3_NAME_TWI(n) n##_twi
+#endif
 #if FA3_TWI
-__global__ __launch_bounds__(256, 6) void k_fa3fh1_twi(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+__global__ __launch_bounds__(256, 6) void FA3_NAME_TWI(k_fa3fh1)(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
 #else
 template <int ND>
-__global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+__global__ __launch_bounds__(256, 6) void FA3_NAME(k_fa3fh1)(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
 #endif
                                                   const uint8_t *__restrict__ nod4, int ldm, DtWin w, int tiles_x,
                                                   const unsigned long long *__restrict__ rec,
@@ -30,11 +39,15 @@ __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ f
 #else
                                                   uint8_t *__restrict__ cache_wide) {
 #endif
+#undef FA3_NAME
+#undef FA3_NAME_TWI
 #define P3(c) ((uint32_t)(c) + (((uint32_t)(c) >> 6) << 2))
 #define NT3 (TH * (TW + 4))
   __shared__ __attribute__((aligned(16))) unsigned char smem[NT3 * 6];  // 26112 bytes
   __shared__ unsigned long long s_in;
+#if !FA3_WALK
   __shared__ int s_ovf;
+#endif
   // accumulation half: delta raster + padded successor indices
   uint32_t *s_delta = reinterpret_cast<uint32_t *>(smem);
   uint16_t *s_nxt = reinterpret_cast<uint16_t *>(smem + NT3 * 4);
@@ -94,7 +107,18 @@ __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ f
   }
   // the feeders' words have been in flight behind the staging
   if (rec) e = fa_inflow(fa_gather(c2, y0, x0, threadIdx.x, tiles_x, rec, state), e);
+#if FA3_WALK
+  // fed: some neighbour outside the tile points back at this perimeter cell (the launcher takes this form only with
+  // the gathered inflow, rec != NULL, so the codes are loaded) -- from the codes, not from the inflow's value
+  // (kept as the wave's ballot, in scalar registers: the accumulation half has no vector register to spare)
+  bool fed_now = false;
+#pragma unroll
+  for (int q = 0; q < 8; q++) fed_now = fed_now || c2[q] == fa_back(q);
+  const unsigned long long fed_mask = __ballot(fed_now);
+#endif
+#if !FA3_WALK
   if (threadIdx.x == 0) s_ovf = 0;
+#endif
   // (its barrier also publishes the staging)
   if (__syncthreads_or(!(e & FA_CYCLE) && FA_VALUE(e) >= (1ull << 22))) {  // see k_fa_tile3
     if (threadIdx.x == 0) s_in = 0ull;
@@ -170,7 +194,27 @@ __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ f
     }
 #endif
   }
-  __syncthreads();  // everybody is done with the delta raster: the same LDS now holds HAND's arrays
+#if FA3_WALK
+  // river cells end HAND's walks: terminals of the successor table (the accumulation walks are over)
+#pragma unroll
+  for (int u = 0; u < VPT; u++) {
+    if (!riv4[u]) continue;
+    const uint32_t pc = P3(4 * (threadIdx.x + 256 * u));
+    uint2 nx = *reinterpret_cast<const uint2 *>(&s_nxt[pc]);
+    if (riv4[u] & 0x1u) nx.x = (nx.x & 0xFFFF0000u) | NX_RIVER;
+    if (riv4[u] & 0x100u) nx.x = (nx.x & 0xFFFFu) | (NX_RIVER << 16);
+    if (riv4[u] & 0x10000u) nx.y = (nx.y & 0xFFFF0000u) | NX_RIVER;
+    if (riv4[u] & 0x1000000u) nx.y = (nx.y & 0xFFFFu) | (NX_RIVER << 16);
+    *reinterpret_cast<uint2 *>(&s_nxt[pc]) = nx;
+  }
+#endif
+  __syncthreads();  // everybody is done with the delta raster (and the river cells are in the table)
+#if FA3_WALK
+  fh_walk_body(s_nxt, fdr, ((fed_mask >> (threadIdx.x & 63u)) & 1ull) != 0ull, w, tile, tiles_x, y0, x0, nodes, cache_wide);
+#undef P3
+#undef NT3
+}
+#else
 #undef P3
 #undef NT3
   uint32_t *s_w = reinterpret_cast<uint32_t *>(smem);             // 16 KiB
@@ -182,3 +226,4 @@ __global__ __launch_bounds__(256, 6) void k_fa3fh1(const uint8_t *__restrict__ f
   __syncthreads();
   fh_tile1n_body(s_fdr, s_w, s_kind, &s_ovf, s_lut, riv4, w, tile, tiles_x, y0, x0, nnodes, nodes, cache, cache_wide);
 }
+#endif

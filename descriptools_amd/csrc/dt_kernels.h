@@ -147,7 +147,8 @@ struct DtTwiEpilogue {
 int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, void *fa_scratch,
                                  void *fh_scratch, size_t fh_bytes, const unsigned long long *ext_perim,
                                  int64_t river_thr, void *acc, int acc64, int8_t *river, int *status,
-                                 const uint8_t *nod4 = nullptr, int ldm = 0, const DtTwiEpilogue *twi = nullptr);
+                                 const uint8_t *nod4 = nullptr, int ldm = 0, const DtTwiEpilogue *twi = nullptr,
+                                 int *walked = nullptr);
 bool dt_twi_epilogue_ok(const DtWin &w, const void *acc, const int8_t *river, const DtTwiEpilogue *twi);
 int dt_launch_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const int8_t *river, void *scratch,
                        size_t scratch_bytes);
@@ -158,7 +159,8 @@ int dt_launch_fh_finish(hipStream_t s, const DtWin &w, const float *dem, const u
                         const uint8_t *res_ok, const int32_t *res_nc, const int32_t *res_nd,
                         const long long *rem_gidx, const float *rem_zr, const long long *rem_ar, float *fdist,
                         int32_t *idx32, long long *idx64, float *hand, void *a_river, float *gfi = nullptr,
-                        float *lnhlh = nullptr, double n_gfi = 0.0, double b_gfi = 1.0, double size = 1.0);
+                        float *lnhlh = nullptr, double n_gfi = 0.0, double b_gfi = 1.0, double size = 1.0,
+                        int walked = 0);
 int dt_launch_gfi_both(hipStream_t s, const float *hand, const void *a_river, const void *fac, int acc64,
                        int64_t n, double expo, double b, double size, float *gfi, float *lnhlh);
 int dt_launch_unique_extremes(hipStream_t s, const float *x, int64_t n, uint32_t *work4, float *out3);

@@ -1467,23 +1467,20 @@ __device__ __forceinline__ unsigned long long fh_cache_get(const unsigned long l
 // `cache` keeps every cell's resolved in-tile word (tile-major: slot cache[tile * NT ...]) so that
 // pass 3 does not have to solve the tile again: 16 bytes / cell of streaming HBM traffic instead of a
 // second LDS-bound pointer doubling.
-__global__ __launch_bounds__(256) void k_fh_tile1(const uint8_t *__restrict__ fdr,
-                                                 const int8_t *__restrict__ river, DtWin w, int tiles_x,
-                                                 uint32_t nnodes, unsigned long long *__restrict__ nodes,
-                                                 unsigned long long *__restrict__ cache,
-                                                 uint8_t *__restrict__ cache_wide, int only_marked, int ntiles) {
-  __shared__ __attribute__((aligned(16))) uint8_t s_fdr[NT];
-  __shared__ uint8_t s_halo[2 * (TW + 2) + 2 * TH];
-  __shared__ __attribute__((aligned(16))) unsigned long long s_st[NT];
-  // grid-stride over the tiles: launched over all of them as the 64-bit solve, over a small grid as the redo of
-  // the tiles the narrow kernel gave up (usually none: 2048 workgroups look at 32 flags each and leave)
-  for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
-  if (only_marked && cache_wide[tile] != 2) continue;  // block-uniform: k_fh_tile1n did this tile
+// one tile of it; NODES false: the redo after the perimeter node doubling (k_fh_tile1_marked), which leaves the node
+// words alone -- they are resolved by then, and a neighbouring tile's last pass reads them
+template <bool NODES>
+__device__ __forceinline__ void fh_tile1_tile(uint8_t *s_fdr, uint8_t *s_halo, unsigned long long *s_st, int tile,
+                                              const uint8_t *__restrict__ fdr, const int8_t *__restrict__ river,
+                                              const DtWin &w, int tiles_x, uint32_t nnodes,
+                                              unsigned long long *__restrict__ nodes,
+                                              unsigned long long *__restrict__ cache,
+                                              uint8_t *__restrict__ cache_wide) {
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;
   FhTile T{s_fdr, s_halo, s_st};
   fht_solve_tile(T, fdr, river, w, y0, x0);
-  if (threadIdx.x < PS) {
+  if (NODES && threadIdx.x < PS) {
     int ly, lx;
     dt_cell_of_slot(threadIdx.x, ly, lx);
     unsigned long long s = s_st[ly * TW + lx];
@@ -1524,7 +1521,41 @@ __global__ __launch_bounds__(256) void k_fh_tile1(const uint8_t *__restrict__ fd
     for (int j = 0; j < CPT; j++) c32[threadIdx.x + 256 * j] = fh_cache_pack(wv[j]);
   }
   __syncthreads();  // the LDS images are reused by the next tile
+}
+__global__ __launch_bounds__(256) void k_fh_tile1(const uint8_t *__restrict__ fdr,
+                                                 const int8_t *__restrict__ river, DtWin w, int tiles_x,
+                                                 uint32_t nnodes, unsigned long long *__restrict__ nodes,
+                                                 unsigned long long *__restrict__ cache,
+                                                 uint8_t *__restrict__ cache_wide, int only_marked, int ntiles) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_fdr[NT];
+  __shared__ uint8_t s_halo[2 * (TW + 2) + 2 * TH];
+  __shared__ __attribute__((aligned(16))) unsigned long long s_st[NT];
+  // grid-stride over the tiles: launched over all of them as the 64-bit solve, over a small grid as the redo of
+  // the tiles the narrow kernel gave up (usually none: 2048 workgroups look at 32 flags each and leave)
+  for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
+    if (only_marked && cache_wide[tile] != 2) continue;  // block-uniform: k_fh_tile1n did this tile
+    fh_tile1_tile<true>(s_fdr, s_halo, s_st, tile, fdr, river, w, tiles_x, nnodes, nodes, cache, cache_wide);
   }
+}
+// The redo of the tiles HAND's LAST pass gave up (k_fh_tile3_solve marks them 2): a workgroup reads the flags of 256
+// tiles, one per lane, and leaves when none is marked -- microseconds for the launch that finds nothing.  Marked tiles
+// get their 64-bit words into the cache (flag 1: such a tile has a count above 255); the node words stay.
+__global__ __launch_bounds__(256) void k_fh_tile1_marked(const uint8_t *__restrict__ fdr,
+                                                        const int8_t *__restrict__ river, DtWin w, int tiles_x,
+                                                        uint32_t nnodes, unsigned long long *__restrict__ nodes,
+                                                        unsigned long long *__restrict__ cache,
+                                                        uint8_t *cache_wide, int ntiles) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_fdr[NT];
+  __shared__ uint8_t s_halo[2 * (TW + 2) + 2 * TH];
+  __shared__ __attribute__((aligned(16))) unsigned long long s_st[NT];
+  __shared__ uint8_t s_flag[256];
+  const int base = (int)blockIdx.x * 256, mine = base + (int)threadIdx.x;
+  const uint8_t flag = mine < ntiles ? cache_wide[mine] : (uint8_t)0;
+  s_flag[threadIdx.x] = flag;
+  if (!__syncthreads_or(flag == 2)) return;
+  for (int i = 0; i < 256; i++)
+    if (s_flag[i] == 2)  // block-uniform
+      fh_tile1_tile<false>(s_fdr, s_halo, s_st, base + i, fdr, river, w, tiles_x, nnodes, nodes, cache, cache_wide);
 }
 
 // ---- pass 1, narrow form -----------------------------------------------------------------------------
@@ -1553,12 +1584,12 @@ __device__ __forceinline__ uint32_t fh_lut_entry(uint32_t code) {
   dt_d8_delta(code, dy, dx);
   return ((uint32_t)(dy * TW + dx) << FN_PTR_SH) + ((dy != 0 && dx != 0) ? (1u << 9) : 1u);
 }
-__device__ __forceinline__ void fh_tile1n_body(uint8_t *s_fdr, uint32_t *s_w, uint8_t *s_kind, int *s_ovf_p,
-                                               const uint32_t *s_lut, const uint32_t (&riv4)[NT / 4 / 256],
-                                               const DtWin &w, int tile, int tiles_x, int y0, int x0, uint32_t nnodes,
-                                               unsigned long long *__restrict__ nodes,
-                                               unsigned long long *__restrict__ cache,
-                                               uint8_t *__restrict__ cache_wide) {
+// Two halves, because HAND's last pass solves tiles too (k_fh_tile3_solve): fh_tile1n_solve sets the words up and
+// doubles them -- afterwards s_w holds every cell's word, own[] the lane's pairs, s_kind the end kinds; false
+// (block-uniform) when a count passed 255 -- and fh_tile1n_body, which emits the cache words and the node words.
+__device__ __forceinline__ bool fh_tile1n_solve(uint8_t *s_fdr, uint32_t *s_w, uint8_t *s_kind, int *s_ovf_p,
+                                                const uint32_t *s_lut, const uint32_t (&riv4)[NT / 4 / 256],
+                                                const DtWin &w, int y0, int x0, uint2 (&own)[CPT / 2]) {
 #define s_ovf (*s_ovf_p)
   // A lane sets up the 4 x 4 cells  4 (t + 256 u) + k  whose river mask it holds (riv4, one byte per cell): codes,
   // words and kinds move as 32 / 128-bit LDS accesses, and nobody else touches these cells before the barrier.
@@ -1619,7 +1650,6 @@ __device__ __forceinline__ void fh_tile1n_body(uint8_t *s_fdr, uint32_t *s_w, ui
   // pointer doubling in place; ONE addition of the low 19 bits adds both counts and inherits the done bit
   uint2 *s_w2 = reinterpret_cast<uint2 *>(s_w);  // lane owns adjacent cell pairs
   // a lane's own words change only by its own hand: they live in registers, LDS gets the copies others gather
-  uint2 own[CPT / 2];
 #pragma unroll
   for (int j = 0; j < CPT / 2; j++) own[j] = s_w2[threadIdx.x + 256 * j];
   for (int round = 0; round < 13; round++) {
@@ -1653,18 +1683,31 @@ __device__ __forceinline__ void fh_tile1n_body(uint8_t *s_fdr, uint32_t *s_w, ui
     if (!__syncthreads_or(changed)) break;
     if (s_ovf) break;  // block-uniform: written before the barrier
   }
-  if (s_ovf) {
+  return !s_ovf;
+#undef s_ovf
+}
+// the cache's narrow word of cell c from its final word v; cells unfinished after 13 rounds run into an in-tile D8
+// cycle: dead (flowhand.py:830-837)
+__device__ __forceinline__ uint32_t fh_narrow_word(uint32_t v, uint32_t c, const uint8_t *s_kind) {
+  uint32_t f = v >> FN_PTR_SH, kind = s_kind[f];
+  if (!(v & FN_DONE)) { f = c; kind = K_DEAD; v = 0; }
+  return f | (kind << 12) | (((v >> 9) & 0xFFu) << 15) | ((v & 0xFFu) << 23);
+}
+__device__ __forceinline__ void fh_tile1n_body(uint8_t *s_fdr, uint32_t *s_w, uint8_t *s_kind, int *s_ovf_p,
+                                               const uint32_t *s_lut, const uint32_t (&riv4)[NT / 4 / 256],
+                                               const DtWin &w, int tile, int tiles_x, int y0, int x0, uint32_t nnodes,
+                                               unsigned long long *__restrict__ nodes,
+                                               unsigned long long *__restrict__ cache,
+                                               uint8_t *__restrict__ cache_wide) {
+  uint2 own[CPT / 2];
+  if (!fh_tile1n_solve(s_fdr, s_w, s_kind, s_ovf_p, s_lut, riv4, w, y0, x0, own)) {
     if (threadIdx.x == 0) cache_wide[tile] = 2;  // for k_fh_tile1
     return;
   }
-  // cells unfinished after 13 rounds run into an in-tile D8 cycle: dead (flowhand.py:830-837).  The final words of a
-  // lane's pairs are in its registers and the last round ended with a barrier: the cache's narrow words go straight
-  // into s_w (cache store, perimeter lanes), the kinds of the paths' ends are the only gathers left.
-  auto narrow = [&](uint32_t v, uint32_t c) -> uint32_t {
-    uint32_t f = v >> FN_PTR_SH, kind = s_kind[f];
-    if (!(v & FN_DONE)) { f = c; kind = K_DEAD; v = 0; }
-    return f | (kind << 12) | (((v >> 9) & 0xFFu) << 15) | ((v & 0xFFu) << 23);
-  };
+  // The final words of a lane's pairs are in its registers and the last round ended with a barrier: the cache's narrow
+  // words go straight into s_w (cache store, perimeter lanes), the kinds of the paths' ends are the only gathers left.
+  uint2 *s_w2 = reinterpret_cast<uint2 *>(s_w);
+  auto narrow = [&](uint32_t v, uint32_t c) -> uint32_t { return fh_narrow_word(v, c, s_kind); };
 #pragma unroll
   for (int j = 0; j < CPT / 2; j++) {
     const int c2 = threadIdx.x + 256 * j;
@@ -1698,7 +1741,57 @@ __device__ __forceinline__ void fh_tile1n_body(uint8_t *s_fdr, uint32_t *s_w, ui
     }
     nodes[(size_t)tile * PS + threadIdx.x] = o;
   }
-#undef s_ovf
+}
+
+// ---- pass 1, walk form ---------------------------------------------------------------------------------------------
+// What the other tiles ever read of a tile's pass 1 is the node word of a FED entry: a perimeter cell that some
+// neighbouring tile's exit steps onto (k_fh_tile3 looks up nodes[dt_node_of(successor of an exit cell)], and a node
+// pointer has the same form).  So the fused pass (dt_fa3fh1_kernel.inc, FA3_WALK) solves no tile: every fed perimeter
+// lane walks its in-tile path over the successor table the accumulation half has built, as that half's entry walks
+// do, and writes its node word -- the word fh_tile1n_body writes for the cell, with the counts straight in the 64-bit
+// fields (no 255 limit).  River cells are terminals of the table (NX_RIVER, set once the river mask exists); the code of
+// the cell a walk ends on -- the exit's direction, "a river cell with code 0 is dead" -- is one read of the raster
+// after the walk, as k_fh_tile3 reads its exit cells' codes.  Unfed slots get a finished dead word, which the node doubling
+// skips; the tile's flag says "solve in the last pass" (FH_SOLVE_LATER) and no cache word is written.
+#define NX_RIVER 0xFFFCu      /* successor table, walk form: a river cell */
+#define FH_SOLVE_LATER 3      /* cache_wide: pass 1 walked, k_fh_tile3_solve solves the tile */
+__device__ __forceinline__ void fh_walk_body(const uint16_t *s_nxt, const uint8_t *__restrict__ fdr, bool fed, const DtWin &w,
+                                             int tile, int tiles_x, int y0, int x0,
+                                             unsigned long long *__restrict__ nodes,
+                                             uint8_t *__restrict__ cache_wide) {
+  constexpr uint32_t PW = TW + 4, NTP = TH * PW;  // the padded rows of the successor table
+  if (threadIdx.x == 0) cache_wide[tile] = (uint8_t)FH_SOLVE_LATER;
+  if (threadIdx.x >= PS) return;
+  unsigned long long o = fht_pack(FHT_DEAD, 0, FHT_DONE);
+  if (fed) {
+    int ly, lx;
+    dt_cell_of_slot(threadIdx.x, ly, lx);
+    uint32_t c = (uint32_t)ly * PW + (uint32_t)lx, nc = 0, nd = 0;
+    // an acyclic in-tile path makes < NT moves: whoever has not met a terminal after NT cells is on an in-tile cycle
+    // and stays dead (flowhand.py:830-837)
+    uint32_t n = 0;
+    for (int it = 0; it < NT; it++) {
+      n = s_nxt[c];
+      if (n >= NTP) break;
+      const uint32_t d = n > c ? n - c : c - n;  // 1 or a row: a cardinal move
+      if (d == 1u || d == PW) nc++;
+      else nd++;
+      c = n;
+    }
+    if (n == NX_RIVER || n == NX_EXIT) {  // else: code 0, not a D8 code, a step off the raster, a cycle
+      const int fy = (int)(c / PW), fx = (int)(c % PW);
+      const uint32_t code = fdr[(long long)(y0 + fy) * w.ld + x0 + fx];
+      if (n == NX_EXIT) {
+        int dy, dx;
+        dt_d8_delta(code, dy, dx);
+        const bool diag = dy != 0 && dx != 0;
+        o = fht_pack(dt_node_of(y0 + fy + dy, x0 + fx + dx, tiles_x), nd + (diag ? 1u : 0u), nc + (diag ? 0u : 1u));
+      } else if (code != 0u) {  // a river cell whose code is 0 is dead all the same (flowhand.py:601)
+        o = fht_pack((uint32_t)((y0 + fy) * w.W + x0 + fx), nd, nc | FHT_DONE);
+      }
+    }
+  }
+  nodes[(size_t)tile * PS + threadIdx.x] = o;
 }
 
 __global__ __launch_bounds__(256, 6) void k_fh_tile1n(const uint8_t *__restrict__ fdr,
@@ -1747,12 +1840,23 @@ struct TwiOut {
   int stiles_x;         // stencil tiles per row
 };
 typedef float fa_v4f __attribute__((ext_vector_type(4)));
+#define FA3_WALK 0
 #define FA3_TWI 0
 #include "dt_fa3fh1_kernel.inc"
 #undef FA3_TWI
 #define FA3_TWI 1
 #include "dt_fa3fh1_kernel.inc"
 #undef FA3_TWI
+#undef FA3_WALK
+// the same two with HAND's half in its walk form (fh_walk_body): k_fa3fh1w<ND>, k_fa3fh1w_twi -- the single raster's
+#define FA3_WALK 1
+#define FA3_TWI 0
+#include "dt_fa3fh1_kernel.inc"
+#undef FA3_TWI
+#define FA3_TWI 1
+#include "dt_fa3fh1_kernel.inc"
+#undef FA3_TWI
+#undef FA3_WALK
 
 // ghost g of ring cell i: a fixed point (ptr = itself, no moves, not done) until resolved
 __global__ __launch_bounds__(256) void k_fh_ghost_init(unsigned long long *__restrict__ nodes, uint32_t nnodes,
@@ -1917,33 +2021,52 @@ __device__ __forceinline__ void fh_store4(long long *p, long long a, long long b
 
 // RANKED: the multi-GPU form (rank-exit payloads `rem`, ghost nodes, global int64 river indices); the
 // single-raster form leaves all of that out of the register budget
-template <bool RANKED, int VH, int MINW, typename AccT>
-__global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restrict__ fdr,
-                                                 const float *__restrict__ dem,
-                                                 const AccT *__restrict__ acc32, DtWin w, int tiles_x,
-                                                 uint32_t nnodes, const unsigned long long *__restrict__ nodes,
-                                                 const unsigned long long *__restrict__ cache,
-                                                 const uint8_t *__restrict__ cache_wide,
-                                                 FhRemote rem, double px, float *__restrict__ fdist,
-                                                 int32_t *__restrict__ idx32, long long *__restrict__ idx64,
-                                                 float *__restrict__ hand, AccT *__restrict__ a_river,
-                                                 FhGfi G) {
-  // per exit slot: the resolved word of the node the exit cell steps onto (+ the step), and the payload
-  // {river height, river accumulation} of the river cell it resolves to.  4 KiB of LDS: the kernel streams
-  // 28 B/cell and needs the occupancy, not a 32 KiB per-cell table.
-  __shared__ unsigned long long s_x[PS];
-  __shared__ FhPay<AccT> s_pay;
-  __shared__ DtLogEntry s_tab[DT_LOGTAB_N];  // 2 KiB: the GFI epilogue's logarithm table
-  if (G.gfi) dt_math_stage(G.tab, s_tab);  // before the barrier every path below passes
-  const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
+// One tile of it, the text of k_fh_tile3 (cached words), k_fh_tile3_marked (the same, on the tiles the solving form
+// gave up) and k_fh_tile3_solve (SOLVE: pass 1 walked the fed entries and cached nothing -- the tile's words are
+// solved here, in LDS, behind the kernel's memory stream; false when a count passed 255 and nothing was stored).
+// The kernels own the LDS: s_x / s_pay / s_tab below, and for SOLVE the arrays of the narrow tile solve.
+struct FhSolveLds {
+  uint8_t *fdr;   // [NT]
+  uint32_t *w;    // [NT]
+  uint8_t *kind;  // [NT]: first the river mask, then the end kinds
+  uint32_t *lut;  // [256]
+  int *ovf;
+};
+template <bool RANKED, int VH, typename AccT, bool SOLVE>
+__device__ __forceinline__ bool fh_tile3_tile(unsigned long long *s_x, FhPay<AccT> &s_pay, DtLogEntry *s_tab,
+                                              const FhSolveLds &L, const int8_t *__restrict__ river, int tile,
+                                              const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                              const AccT *__restrict__ acc32, const DtWin &w, int tiles_x,
+                                              uint32_t nnodes, const unsigned long long *__restrict__ nodes,
+                                              const unsigned long long *__restrict__ cache, bool wide,
+                                              const FhRemote &rem, double px, float *__restrict__ fdist,
+                                              int32_t *__restrict__ idx32, long long *__restrict__ idx64,
+                                              float *__restrict__ hand, AccT *__restrict__ a_river,
+                                              const FhGfi &G) {
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;
-  const bool wide = cache_wide[tile] != 0;  // block-uniform
+  if (SOLVE) {
+    // the tile's codes and its river mask, 2 B/cell where the cache was 4: k_fh_tile1n's staging and solve
+    const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
+    const uint4 v_riv = dt_tile_fetch16(reinterpret_cast<const uint8_t *>(river), w, y0, x0);
+    dt_tile_put16(L.fdr, v_fdr);
+    dt_tile_put16(L.kind, v_riv);
+    L.lut[threadIdx.x] = fh_lut_entry(threadIdx.x);
+    if (threadIdx.x == 0) *L.ovf = 0;
+    __syncthreads();
+    uint32_t riv4[NT / 4 / 256];
+#pragma unroll
+    for (int u = 0; u < NT / 4 / 256; u++) riv4[u] = *reinterpret_cast<const uint32_t *>(&L.kind[4 * (threadIdx.x + 256 * u)]);
+    uint2 own[CPT / 2];
+    if (!fh_tile1n_solve(L.fdr, L.w, L.kind, L.ovf, L.lut, riv4, w, y0, x0, own)) return false;
+  }
+  // cell c's cached narrow word: from the cache, or from the word the solve left in LDS
+  auto solved = [&](uint32_t v, int c) -> uint32_t { return fh_narrow_word(v, (uint32_t)c, L.kind); };
   if (threadIdx.x < PS) {
     int ly, lx;
     dt_cell_of_slot(threadIdx.x, ly, lx);
     int f = ly * TW + lx;
-    unsigned long long s = fh_cache_get(cache, wide, tile, f);
+    unsigned long long s = SOLVE ? fh_cache_unpack(solved(L.w[f], f)) : fh_cache_get(cache, wide, tile, f);
     uint32_t sp = (uint32_t)(s >> 32);
     unsigned long long o = fht_pack(FHT_DEAD, 0, FHT_DONE);
     float zr = DT_NODATA;
@@ -1952,7 +2075,7 @@ __global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restric
     bool ex = sp == ((uint32_t)f | (K_EXIT << 12)), rex = sp == ((uint32_t)f | (K_REXIT << 12));
     if (ex || rex) {
       int dy, dx;
-      dt_d8_delta(fdr[(long long)(y0 + ly) * w.ld + x0 + lx], dy, dx);
+      dt_d8_delta(SOLVE ? (uint32_t)L.fdr[f] : (uint32_t)fdr[(long long)(y0 + ly) * w.ld + x0 + lx], dy, dx);
       size_t node = ex ? (size_t)dt_node_of(y0 + ly + dy, x0 + lx + dx, tiles_x)
                        : (size_t)nnodes + (size_t)dt_perim_index(w.H, w.W, y0 + ly, x0 + lx);
       unsigned long long ns = nodes[node];
@@ -2072,7 +2195,13 @@ __global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restric
           wa[u] = cp[0];
           wb[u] = cp[1];
         } else {  // four narrow words in one 16-byte load
-          uint4 v = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint32_t *>(cache + (size_t)tile * NT) + c);
+          uint4 v;
+          if (SOLVE) {
+            v = *reinterpret_cast<const uint4 *>(&L.w[c]);
+            v = make_uint4(solved(v.x, c), solved(v.y, c + 1), solved(v.z, c + 2), solved(v.w, c + 3));
+          } else {
+            v = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint32_t *>(cache + (size_t)tile * NT) + c);
+          }
           unsigned long long a = fh_cache_unpack(v.x), b2 = fh_cache_unpack(v.y), c2 = fh_cache_unpack(v.z),
                              d2 = fh_cache_unpack(v.w);
           wa[u] = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b2, (uint32_t)(b2 >> 32));
@@ -2128,7 +2257,7 @@ __global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restric
         __builtin_amdgcn_sched_barrier(0);  // finish this group of 4 cells before the next one starts
       }
     }
-    return;
+    return true;
   }
   // ragged tiles and unaligned rasters: one cell at a time (rare: keep it small, not fast)
   __syncthreads();
@@ -2138,7 +2267,8 @@ __global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restric
     int y = y0 + c / TW, x = x0 + c % TW;
     if (y >= w.H || x >= w.W) continue;
     long long o = (long long)y * w.ld + x;
-    CellOut r = solve(fh_cache_get(cache, wide, tile, c), dem ? dem[o] : DT_NODATA);
+    CellOut r = solve(SOLVE ? fh_cache_unpack(solved(L.w[c], c)) : fh_cache_get(cache, wide, tile, c),
+                      dem ? dem[o] : DT_NODATA);
     if (fdist) fdist[o] = r.fd;
     if (idx32) idx32[o] = r.i32;
     if (RANKED && idx64) idx64[o] = r.i64;
@@ -2151,6 +2281,97 @@ __global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restric
       G.lnhlh[o] = l;
     }
   }
+  return true;
+}
+
+template <bool RANKED, int VH, int MINW, typename AccT>
+__global__ __launch_bounds__(256, MINW) void k_fh_tile3(const uint8_t *__restrict__ fdr,
+                                                 const float *__restrict__ dem,
+                                                 const AccT *__restrict__ acc32, DtWin w, int tiles_x,
+                                                 uint32_t nnodes, const unsigned long long *__restrict__ nodes,
+                                                 const unsigned long long *__restrict__ cache,
+                                                 const uint8_t *__restrict__ cache_wide,
+                                                 FhRemote rem, double px, float *__restrict__ fdist,
+                                                 int32_t *__restrict__ idx32, long long *__restrict__ idx64,
+                                                 float *__restrict__ hand, AccT *__restrict__ a_river,
+                                                 FhGfi G) {
+  // per exit slot: the resolved word of the node the exit cell steps onto (+ the step), and the payload
+  // {river height, river accumulation} of the river cell it resolves to.  4 KiB of LDS: the kernel streams
+  // 28 B/cell and needs the occupancy, not a 32 KiB per-cell table.
+  __shared__ unsigned long long s_x[PS];
+  __shared__ FhPay<AccT> s_pay;
+  __shared__ DtLogEntry s_tab[DT_LOGTAB_N];  // 2 KiB: the GFI epilogue's logarithm table
+  if (G.gfi) dt_math_stage(G.tab, s_tab);  // before the barrier every path below passes
+  const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
+  const bool wide = cache_wide[tile] != 0;  // block-uniform
+  fh_tile3_tile<RANKED, VH, AccT, false>(s_x, s_pay, s_tab, FhSolveLds{}, nullptr, tile, fdr, dem, acc32, w, tiles_x,
+                                         nnodes, nodes, cache, wide, rem, px, fdist, idx32, idx64, hand, a_river, G);
+}
+
+// The solving form (single raster, int32 accumulation): 2 B/cell of codes and river bytes in place of the 4 B/cell
+// cache, the narrow tile solve in 25 KiB of LDS beside the 6 KiB above -- five workgroups per CU as before.  A tile
+// with a path of more than 255 moves of a kind cannot be solved in narrow words: its workgroup marks it
+// (cache_wide = 2) and stores nothing; k_fh_tile1_marked and k_fh_tile3_marked redo exactly those.
+__global__ __launch_bounds__(256, 5) void k_fh_tile3_solve(const uint8_t *__restrict__ fdr,
+                                                          const int8_t *__restrict__ river,
+                                                          const float *__restrict__ dem,
+                                                          const int32_t *__restrict__ acc32, DtWin w, int tiles_x,
+                                                          uint32_t nnodes,
+                                                          const unsigned long long *__restrict__ nodes,
+                                                          uint8_t *__restrict__ cache_wide, double px,
+                                                          float *__restrict__ fdist, int32_t *__restrict__ idx32,
+                                                          float *__restrict__ hand, int32_t *__restrict__ a_river,
+                                                          FhGfi G) {
+  __shared__ unsigned long long s_x[PS];
+  __shared__ FhPay<int32_t> s_pay;
+  __shared__ DtLogEntry s_tab[DT_LOGTAB_N];
+  __shared__ __attribute__((aligned(16))) uint8_t s_fdr[NT];
+  __shared__ __attribute__((aligned(16))) uint32_t s_w[NT];
+  __shared__ __attribute__((aligned(16))) uint8_t s_kind[NT];
+  __shared__ uint32_t s_lut[256];
+  __shared__ int s_ovf;
+  if (G.gfi) dt_math_stage(G.tab, s_tab);
+  const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
+  const bool ok = fh_tile3_tile<false, 1, int32_t, true>(
+      s_x, s_pay, s_tab, FhSolveLds{s_fdr, s_w, s_kind, s_lut, &s_ovf}, river, tile, fdr, dem, acc32, w, tiles_x, nnodes,
+      nodes, nullptr, false, FhRemote{nullptr, nullptr, nullptr}, px, fdist, idx32, nullptr, hand, a_river, G);
+  if (!ok && threadIdx.x == 0) cache_wide[tile] = 2;
+}
+
+// The cached form on the tiles the solving form gave up and k_fh_tile1_marked has cached since (their flag is no
+// longer FH_SOLVE_LATER): a workgroup reads 256 flags, one per lane, and leaves when it finds none -- microseconds.
+__global__ __launch_bounds__(256) void k_fh_tile3_marked(const uint8_t *__restrict__ fdr,
+                                                           const float *__restrict__ dem,
+                                                           const int32_t *__restrict__ acc32, DtWin w, int tiles_x,
+                                                           uint32_t nnodes,
+                                                           const unsigned long long *__restrict__ nodes,
+                                                           const unsigned long long *__restrict__ cache,
+                                                           const uint8_t *__restrict__ cache_wide, int ntiles,
+                                                           double px, float *__restrict__ fdist,
+                                                           int32_t *__restrict__ idx32, float *__restrict__ hand,
+                                                           int32_t *__restrict__ a_river, FhGfi G) {
+  __shared__ unsigned long long s_x[PS];
+  __shared__ FhPay<int32_t> s_pay;
+  __shared__ DtLogEntry s_tab[DT_LOGTAB_N];
+  __shared__ uint8_t s_flag[256];
+  const int base = (int)blockIdx.x * 256, mine = base + (int)threadIdx.x;
+  const uint8_t flag = mine < ntiles ? cache_wide[mine] : (uint8_t)FH_SOLVE_LATER;
+  s_flag[threadIdx.x] = flag;
+  if (!__syncthreads_or(flag != FH_SOLVE_LATER)) return;
+  if (G.gfi) dt_math_stage(G.tab, s_tab);
+  for (int i = 0; i < 256; i++) {
+    if (s_flag[i] == FH_SOLVE_LATER) continue;  // block-uniform
+    fh_tile3_tile<false, 1, int32_t, false>(s_x, s_pay, s_tab, FhSolveLds{}, nullptr, base + i, fdr, dem, acc32, w,
+                                            tiles_x, nnodes, nodes, cache, s_flag[i] != 0, FhRemote{nullptr, nullptr, nullptr},
+                                            px, fdist, idx32, nullptr, hand, a_river, G);
+    __syncthreads();  // the exit table is reused by the next tile
+  }
+}
+// every tile of a walked pass 1 marked for the redo: the way back to the cached kernels for a last pass the solving
+// form does not serve (rank-exit results, 64-bit river indices or accumulation)
+__global__ __launch_bounds__(256) void k_fh_mark_all(uint8_t *__restrict__ cache_wide, int ntiles) {
+  const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (t < ntiles && cache_wide[t] == FH_SOLVE_LATER) cache_wide[t] = 2;
 }
 
 struct FhScratch {
@@ -2178,11 +2399,14 @@ static FhScratch fh_layout(const DtWin &w, void *scratch) {
 size_t dt_flowhand_tiled_scratch(int64_t H, int64_t W) { return fh_layout(dt_full_window(H, W), nullptr).bytes; }
 
 // what follows the narrow tile pass in phase 1: the 64-bit solve for the tiles it had to give up (usually none: the
-// launch is 2048 workgroups that look at 32 flags each and leave), the ghosts, the perimeter node doubling
-static int fh_local_tail(hipStream_t s, const DtWin &w, const uint8_t *fdr, const int8_t *river, const FhScratch &f) {
+// launch is 2048 workgroups that look at 32 flags each and leave), the ghosts, the perimeter node doubling.
+// walked: pass 1 was the walk form, which gives no tile up -- no 64-bit solve here.
+static int fh_local_tail(hipStream_t s, const DtWin &w, const uint8_t *fdr, const int8_t *river, const FhScratch &f,
+                         bool walked = false) {
   dim3 gt((unsigned)f.ntiles), b(256);
-  hipLaunchKernelGGL(k_fh_tile1, dim3(gt.x < 2048u ? gt.x : 2048u), b, 0, s, fdr, river, w, f.tiles_x,
-                     (uint32_t)f.nnodes, f.nodes, f.cache, f.cache_wide, 1, (int)f.ntiles);
+  if (!walked)
+    hipLaunchKernelGGL(k_fh_tile1, dim3(gt.x < 2048u ? gt.x : 2048u), b, 0, s, fdr, river, w, f.tiles_x,
+                       (uint32_t)f.nnodes, f.nodes, f.cache, f.cache_wide, 1, (int)f.ntiles);
   hipLaunchKernelGGL(k_fh_ghost_init, dim3((unsigned)((f.P + 255) / 256)), b, 0, s, f.nodes, (uint32_t)f.nnodes, f.P);
   // 8 launches of 3 jumps resolve every chain of <= 20000 moves (each node hop is >= 1 move; the resolved
   // distance at least quadruples per launch: 4^8 > 20000).  HAND's first phase at 16384^2: 1.40 ms with 15 x 1,
@@ -2223,7 +2447,8 @@ bool dt_twi_epilogue_ok(const DtWin &w, const void *acc, const int8_t *river, co
 int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *fdr, const float *dem, void *fa_scratch,
                                  void *fh_scratch, size_t fh_bytes, const unsigned long long *ext_perim,
                                  int64_t river_thr, void *acc, int acc64, int8_t *river, int *status,
-                                 const uint8_t *nod4, int ldm, const DtTwiEpilogue *twi) {
+                                 const uint8_t *nod4, int ldm, const DtTwiEpilogue *twi, int *walked) {
+  if (walked) *walked = 0;
   if (w.H == 0 || w.W == 0) return DT_OK;
   DT_REQUIRE(river != nullptr, "HAND needs the river mask");
   FaScratch f = fa_layout(w, fa_scratch);
@@ -2244,6 +2469,29 @@ int dt_launch_fa_finish_fh_local(hipStream_t s, const DtWin &w, const uint8_t *f
     int32_t thr = river_thr > 2147483647ll ? 2147483647 : (river_thr < -2147483647ll ? -2147483647 : (int32_t)river_thr);
     // the single raster's window starts on the mask's 4-cell grid; a rank's window need not: the DEM there
     const bool use_mask = nod4 != nullptr && w.halo == 0 && w.gx0 == 0 && w.gy0 == 0;
+    // HAND's half as walks of the fed entries (k_fa3fh1w*): a single raster whose caller can pass the form on to the
+    // last pass (walked != NULL), with the gathered inflow (the walks take "fed" from its neighbour codes)
+    const bool walk = walked != nullptr && !ext_perim && in.rec != nullptr && w.halo == 0 && w.gx0 == 0 && w.gy0 == 0 &&
+                      w.H == w.Hg && w.W == w.Wg;
+    if (walk) *walked = 1;
+#define FA3_GO(K)                                                                                                      \
+  hipLaunchKernelGGL(K, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16, (int32_t *)acc, \
+                     thr, river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide)
+    if (walk) {
+      if (twi) {
+        DT_REQUIRE(dt_twi_epilogue_ok(w, acc, river, twi) && use_mask,
+                   "the TI / MTI epilogue takes a single raster with its nodata mask (dt_twi_epilogue_ok)");
+        const int64_t stx = (w.W + 255) / 256, sntiles = stx * ((w.H + 15) / 16);  // the stencil's 256 x 16 tiles
+        const DtStencilAux S = dt_stencil_aux_layout(sntiles, twi->marks);
+        TwiOut tw{twi->slope, twi->ti, twi->mti, twi->n_top, log(twi->px * twi->px), S.mark, (uint32_t *)S.lmask, (int)stx};
+        hipLaunchKernelGGL(k_fa3fh1w_twi, gt, b, 0, s, fdr, dem, nod4, ldm, w, f.tiles_x, in.rec, in.state, in.ext, f.loc16,
+                           (int32_t *)acc, thr, river, status, (uint32_t)h.nnodes, h.nodes, h.cache, h.cache_wide, tw);
+      } else if (use_mask) FA3_GO(k_fa3fh1w<2>);
+      else if (dem) FA3_GO(k_fa3fh1w<1>);
+      else FA3_GO(k_fa3fh1w<0>);
+      return fh_local_tail(s, w, fdr, river, h, true);
+    }
+#undef FA3_GO
     if (twi) {
       DT_REQUIRE(dt_twi_epilogue_ok(w, acc, river, twi) && use_mask && !ext_perim,
                  "the TI / MTI epilogue takes a single raster with its nodata mask (dt_twi_epilogue_ok)");
@@ -2296,7 +2544,7 @@ int dt_launch_fh_finish(hipStream_t s, const DtWin &w, const float *dem, const u
                         const uint8_t *res_ok, const int32_t *res_nc, const int32_t *res_nd,
                         const long long *rem_gidx, const float *rem_zr, const long long *rem_ar, float *fdist,
                         int32_t *idx32, long long *idx64, float *hand, void *a_river, float *gfi,
-                        float *lnhlh, double n_gfi, double b_gfi, double size) {
+                        float *lnhlh, double n_gfi, double b_gfi, double size, int walked) {
   if (w.H == 0 || w.W == 0) return DT_OK;
   FhScratch f = fh_layout(w, scratch);
   dim3 gt((unsigned)f.ntiles), b(256), gn((unsigned)((f.nnodes + f.P + 255) / 256));
@@ -2311,8 +2559,27 @@ int dt_launch_fh_finish(hipStream_t s, const DtWin &w, const float *dem, const u
     DT_REQUIRE(dem && acc, "fused GFI needs dem and the accumulation raster");
     G = FhGfi{gfi, lnhlh, n_gfi, log(b_gfi) + n_gfi * log(size * size), dt_math_device_table(s)};
   }
-  (void)river;
   const bool ranked = res_ok || idx64;
+  if (walked) {
+    // Pass 1 walked the fed entries (dt_launch_fa_finish_fh_local said so; the tiles' flags are FH_SOLVE_LATER and the
+    // cache is empty).  The solving form, then the redo of the tiles it marked -- two launches that find nothing on
+    // terrain; a last pass it does not serve has every tile marked first and goes on to the cached kernels below.
+    DT_REQUIRE(river != nullptr, "HAND needs the river mask");
+    const dim3 gm((unsigned)((f.ntiles + 255) / 256));
+    const bool solve = !ranked && !acc64;
+    if (solve)
+      hipLaunchKernelGGL(k_fh_tile3_solve, gt, b, 0, s, fdr, river, dem, (const int32_t *)acc, w, f.tiles_x,
+                         (uint32_t)f.nnodes, f.nodes, f.cache_wide, px, fdist, idx32, hand, (int32_t *)a_river, G);
+    else
+      hipLaunchKernelGGL(k_fh_mark_all, gm, b, 0, s, f.cache_wide, (int)f.ntiles);
+    hipLaunchKernelGGL(k_fh_tile1_marked, gm, b, 0, s, fdr, river, w, f.tiles_x, (uint32_t)f.nnodes, f.nodes, f.cache,
+                       f.cache_wide, (int)f.ntiles);
+    if (solve) {
+      hipLaunchKernelGGL(k_fh_tile3_marked, gm, b, 0, s, fdr, dem, (const int32_t *)acc, w, f.tiles_x, (uint32_t)f.nnodes,
+                         f.nodes, f.cache, f.cache_wide, (int)f.ntiles, px, fdist, idx32, hand, (int32_t *)a_river, G);
+      return DT_OK;
+    }
+  }
 #define FH_GO(R, MW, T)                                                                                                \
   hipLaunchKernelGGL((k_fh_tile3<R, 1, MW, T>), gt, b, 0, s, fdr, dem, (const T *)acc, w, f.tiles_x, (uint32_t)f.nnodes, \
                      f.nodes, f.cache, f.cache_wide, rem, px, fdist, idx32, idx64, hand, (T *)a_river, G)
