@@ -89,6 +89,7 @@ _SIGS = {
     "dt_gfi_f64h": (ci, [c_f64p, c_i64p, c_i64p, i64, f64, f64, f64, ci, c_f32p]),
     "dt_d8_f64": (ci, [c_f64p, i64, i64, f64, c_u8p, c_f32p]),
     "dt_confusion_multi": (ci, [c_f64p, c_i8p, i64, f64, c_f64p, ci, ci, c_i64p]),
+    "dt_threshold_hist": (ci, [c_f64p, c_i8p, i64, f64, c_f64p, ci, ci, c_i64p]),
     "dt_synth_dem": (ci, [u32, i64, i64, i64, i64, i64, i64, ci, c_f32p]),
     # device tier
     "dt_dev_malloc": (ci, [vp, i64, C.POINTER(vp)]),
@@ -136,6 +137,7 @@ _SIGS = {
     "dt_dev_downslope_queued": (ci, [vp, vp, C.POINTER(i64)]),
     "dt_dev_downslope_finish": (ci, [vp, vp, vp, i64, i64, f64, f64, ci, vp, vp, i64, vp, i64]),
     "dt_dev_confusion_multi": (ci, [vp, vp, vp, i64, f64, c_f64p, ci, ci, vp]),
+    "dt_dev_threshold_hist": (ci, [vp, vp, vp, i64, f64, vp, ci, ci, vp]),
     "dt_perim_cells": (i64, [i64, i64]),
     "dt_dev_slope_d8_w": (ci, [vp, vp, vp, f64, vp, vp, vp]),
     "dt_dev_slope_twi_w": (ci, [vp, vp, vp, vp, f64, f64, vp, vp, vp, vp]),

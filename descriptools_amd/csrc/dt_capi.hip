@@ -1077,6 +1077,15 @@ extern "C" int dt_dev_confusion_multi(dt_ctx *c, const double *desc, const int8_
                                     (unsigned long long *)counts4_dev));
 }
 
+extern "C" int dt_dev_threshold_hist(dt_ctx *c, const double *desc, const int8_t *flood, int64_t N,
+                                     double nodata_value, const double *th_dev, int K, int under, int64_t *hist_dev) {
+  DT_DEV(d, c);
+  DT_REQUIRE(th_dev && hist_dev, "NULL thresholds / histogram");
+  DT_REQUIRE((desc && flood) || N == 0, "NULL raster");
+  return d.done(dt_launch_threshold_hist(c->stream, desc, flood, N, nodata_value, th_dev, K, under,
+                                         (unsigned long long *)hist_dev));
+}
+
 // out3 = {smallest, second-smallest distinct, largest} value of x: np.unique(x)[0], [1], [-1] with one documented
 // difference, the NaN rule.  np.unique sorts NaN last, so one NaN cell would make the largest value NaN and the raster
 // impossible to scale; here NaN cells are skipped (a HAND with NaN cells still calibrates).  A slot that has no value
@@ -2686,6 +2695,24 @@ extern "C" int dt_confusion_multi(const double *desc, const int8_t *flood, int64
     DT_TRY(dt_dev_confusion_multi(hc.c, d_d, d_f, N, nodata_value, th + t0, k, under, d_c));
     DT_TRY(hc.download(counts4 + (size_t)t0 * 4, d_c, (size_t)k * 4));
   }
+  return hc.finish();
+}
+
+extern "C" int dt_threshold_hist(const double *desc, const int8_t *flood, int64_t N, double nodata_value,
+                                 const double *th, int K, int under, int64_t *hist) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_REQUIRE(N >= 0 && th && hist && K >= 1 && K <= 65535, "bad arguments");
+  DT_REQUIRE((desc && flood) || N == 0, "NULL raster");
+  // what the device entry takes as a precondition: t[k] <= t[k + 1] is false for a descending pair and for a NaN
+  DT_REQUIRE(th[0] == th[0], "a threshold is NaN");
+  for (int k = 0; k + 1 < K; k++) DT_REQUIRE(th[k] <= th[k + 1], "thresholds are not sorted ascending (or one is NaN)");
+  const double *d_d = hc.in(desc, N);
+  const int8_t *d_f = hc.in(flood, N);
+  const double *d_t = hc.in(th, K);
+  int64_t *d_h = hc.out(hist, 2 * ((size_t)K + 1) + 1);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_threshold_hist(hc.c, d_d, d_f, N, nodata_value, d_t, K, under, d_h));
   return hc.finish();
 }
 

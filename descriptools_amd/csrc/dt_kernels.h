@@ -117,6 +117,9 @@ int dt_launch_ds_walk_seed_f64(hipStream_t s, const DtWin &w, const double *dem,
 int dt_launch_confusion(hipStream_t s, const double *desc, const int8_t *flood, int64_t n,
                         double nodata, const double *th_host, int nth, int under,
                         unsigned long long *counts4);
+// dt_curve.hip: hist = uint64[2 (K + 1) + 1], zeroed here; th_dev = K sorted thresholds on the device
+int dt_launch_threshold_hist(hipStream_t s, const double *desc, const int8_t *flood, int64_t n, double nodata,
+                             const double *th_dev, int K, int under, unsigned long long *hist);
 int dt_launch_i32_to_i64(hipStream_t s, const int32_t *a, int64_t n, int64_t *b);
 int dt_launch_i64_to_i32(hipStream_t s, const int64_t *a, int64_t n, int32_t *b);
 

@@ -6,7 +6,13 @@ Every raster-returning function is an H2D -> kernel -> D2H shim like the other m
 once (k_confusion); counts are exact integers, so the returned threshold is identical.  The numpy dtype rules of the
 reference's expressions are kept at the boundary (which arithmetic a float16 / float32 / integer raster is scaled and
 compared in, Python numbers rounded to the raster's dtype as numpy's weak scalars are, int64 maps out,
-the in-place remap of the benchmark map)."""
+the in-place remap of the benchmark map).
+
+Net-new beside the reference's functions: `threshold_counts`, `curve`, `calibration_exhaustive` and `curve_resident` --
+the confusion counts at every threshold of a sorted table from one pass (k_threshold_hist), and from them the ROC curve,
+its area, and the best threshold of the whole lattice k / steps instead of the four-stage search's 61 samples of it."""
+import collections
+
 import numpy as np
 
 from . import _lib
@@ -195,6 +201,154 @@ def calibration(descriptor_matrix, comparison_matrix, under):
         return _grid_search(cal.fits)
     finally:
         cal.close()
+
+
+# ---- threshold curves (net-new) ----------------------------------------------------------------------
+CURVE_K_MAX = 65535
+
+Curve = collections.namedtuple("Curve", "thresholds counts correctness fpr fit tss kappa auc")
+Curve.__doc__ = """One descriptor against one benchmark map at K sorted thresholds.  thresholds: float64[K] as given;
+counts: int64[K, 4], the classes 0..3 of avaliacao (both dry, descriptor only, benchmark only, both flooded);
+correctness (the true-positive rate), fpr, fit, tss (correctness - fpr) and kappa (Cohen's): float64[K] quotients of
+those integers, NaN for 0/0; auc: the area under (fpr, correctness) closed to (0, 0) and (1, 1), ties counted half."""
+
+
+def _curve_thresholds(thresholds, round_to):
+    """float64[K] as the kernel compares them: rounded to a float16 / float32 descriptor's dtype first (numpy's weak
+    Python scalars, as _Calibrator.fits), then checked -- ValueError for a count outside 1..65535, a NaN, a descent"""
+    th = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    if not 1 <= th.size <= CURVE_K_MAX:
+        raise ValueError("%d thresholds: a curve takes 1 to %d" % (th.size, CURVE_K_MAX))
+    if np.isnan(th).any():
+        raise ValueError("threshold %d is NaN" % int(np.argmax(np.isnan(th))))
+    if round_to is not None:
+        with np.errstate(over='ignore'):
+            th = th.astype(round_to).astype(np.float64)
+    if not (th[:-1] <= th[1:]).all():
+        k = int(np.argmin(th[:-1] <= th[1:]))
+        raise ValueError("thresholds are not sorted ascending: %r at %d is followed by %r" % (th[k], k, th[k + 1]))
+    return th
+
+
+def _hist_counts(hist, K, under):
+    """int64[K, 4] from the two bin histograms (dt_threshold_hist): a cell of bin j floods at every k >= j ('under') or
+    at every k < j, so the flooded cells at k are a prefix sum; ValueError when the extra counter is not 0"""
+    hist = np.asarray(hist, np.int64)
+    if hist[2 * K + 2]:
+        raise ValueError("%d cells of the benchmark map hold a value other than -100, 0 and 1" % int(hist[2 * K + 2]))
+    counts = np.empty((K, 4), np.int64)
+    for col, h in ((0, hist[:K + 1]), (2, hist[K + 1:2 * K + 2])):
+        below = np.cumsum(h)[:K]
+        wet = below if under else h.sum() - below
+        counts[:, col], counts[:, col + 1] = h.sum() - wet, wet
+    return counts
+
+
+def _hist_auc(hist, K, under):
+    """num / (2 P N) in Python integers, num = sum_j h0[j] (2 S2(j) + h2[j]) with S2(j) the benchmark-flooded cells in
+    the bins that flood before bin j: every (flooded, dry) pair of benchmark cells counts 2 when the descriptor floods
+    the flooded one first and 1 when both flood at the same threshold.  NaN when P N = 0."""
+    h0 = [int(v) for v in hist[:K + 1]]
+    h2 = [int(v) for v in hist[K + 1:2 * K + 2]]
+    if not under:
+        h0.reverse()
+        h2.reverse()
+    num = before = 0
+    for a, b in zip(h0, h2):
+        num += a * (2 * before + b)
+        before += b
+    den = 2 * before * sum(h0)
+    return num / den if den else float('nan')
+
+
+def _curve_of(thresholds, hist, under):
+    K = len(thresholds)
+    counts = _hist_counts(hist, K, under)
+    c0, c1, c2, c3 = (counts[:, i].astype(np.float64) for i in range(4))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        tpr, fpr = correctness(counts.T), c1 / (c0 + c1)
+        kappa = 2 * (c3 * c0 - c1 * c2) / ((c3 + c1) * (c1 + c0) + (c3 + c2) * (c2 + c0))
+        return Curve(np.array(thresholds, np.float64), counts, tpr, fpr, fit(counts.T), tpr - fpr, kappa,
+                     _hist_auc(hist, K, under))
+
+
+def _threshold_hist(descriptor_matrix, comparison_matrix, thresholds, under):
+    """(thresholds as compared, the histograms of dt_threshold_hist) of a host descriptor against a host benchmark map"""
+    desc = np.asarray(descriptor_matrix)
+    if desc.shape != np.shape(comparison_matrix):
+        raise ValueError("the descriptor has shape %s, the benchmark map %s" % (desc.shape, np.shape(comparison_matrix)))
+    th = _curve_thresholds(thresholds, desc.dtype.type if desc.dtype in (np.float16, np.float32) else None)
+    nodata = float(desc.reshape(-1)[0]) if desc.size else 0.0
+    d64 = np.ascontiguousarray(desc, np.float64)
+    cmp8 = np.ascontiguousarray(comparison_matrix, np.int8)
+    # the kernel remaps 1 -> 2 as avaliacao does and so takes a raw 2 for a flooded cell; a value beyond int8 would wrap
+    if (cmp8 == 2).any() or not np.array_equal(cmp8, comparison_matrix):
+        raise ValueError("the benchmark map holds a value other than -100, 0 and 1")
+    hist = np.empty(2 * (len(th) + 1) + 1, np.int64)
+    check(_lib.lib().dt_threshold_hist(ptr(d64, c_f64p), ptr(cmp8, c_i8p), d64.size, nodata, ptr(th, c_f64p), len(th),
+                                       1 if under == 'under' else 0, ptr(hist, c_i64p)))
+    return th, hist
+
+
+def threshold_counts(descriptor_matrix, comparison_matrix, thresholds, under):
+    """int64[K, 4]: the class counts 0..3 that avaliacao(binary_map(descriptor_matrix, t, under), comparison_matrix)
+    counts, for every t of the ascending `thresholds` (1 to 65535 of them), from one pass over the rasters
+    (k_threshold_hist).  As in binary_map the descriptor's first cell is its nodata, and a float16 / float32 descriptor
+    compares with the thresholds rounded to its dtype.  comparison_matrix is left as it is.  ValueError for thresholds
+    that are unsorted or NaN, for rasters of different shapes, for a benchmark value outside {-100, 0, 1}."""
+    th, hist = _threshold_hist(descriptor_matrix, comparison_matrix, thresholds, under)
+    return _hist_counts(hist, len(th), under == 'under')
+
+
+def curve(descriptor_matrix, comparison_matrix, under, steps=10000, thresholds=None):
+    """The Curve of a scaled descriptor against a benchmark map at `thresholds` (default: the lattice k / steps,
+    k = 0..steps, that `calibration` searches a part of); the rules of threshold_counts."""
+    if thresholds is None:
+        thresholds = np.arange(int(steps) + 1) / int(steps)
+    given = np.array(thresholds, np.float64).reshape(-1)
+    _, hist = _threshold_hist(descriptor_matrix, comparison_matrix, given, under)
+    return _curve_of(given, hist, under == 'under')
+
+
+CURVE_OBJECTIVES = ("fit", "tss", "kappa")
+
+
+def calibration_exhaustive(descriptor_matrix, comparison_matrix, under, steps=10000, objective="fit"):
+    """The threshold k / steps, k = 0..steps, with the largest Fit index ("fit"), true skill statistic ("tss") or Cohen's
+    kappa ("kappa"); the smallest such k on a tie, NaN counting as worst, ValueError when the objective is NaN at every
+    k.  With steps = 10000 the lattice holds every threshold in [0, 1] that `calibration`'s four-stage search can
+    return, so this Fit is never below that one's.  comparison_matrix is left as it is."""
+    if objective not in CURVE_OBJECTIVES:
+        raise ValueError("objective must be one of %s, not %r" % (CURVE_OBJECTIVES, objective))
+    if int(steps) < 1:
+        raise ValueError("steps must be at least 1")
+    c = curve(descriptor_matrix, comparison_matrix, under, steps=steps)
+    score = getattr(c, objective)
+    if np.isnan(score).all():
+        raise ValueError("the %s objective is NaN at every threshold" % objective)
+    return int(np.argmax(np.where(np.isnan(score), -np.inf, score))) / int(steps)
+
+
+def curve_resident(ctx, desc_ptr, flood_ptr, n, thresholds, under, nodata_value, reduce_hist=None):
+    """The Curve of rasters that are already in HBM: desc the scaled float64 descriptor that
+    evaluate_resident(desc_ptr=...) leaves behind, flood the int8 benchmark map, both flat device pointers of n cells.
+    thresholds are compared in float64 as given (evaluate_resident rounds its own to float32 for a raster scaled in
+    float32).  nodata_value: the scaled value at global cell [0, 0], as evaluate_resident's nodata_first.
+    reduce_hist(int64 array) -> int64 array hooks in the sum all-reduce of a multi-rank run: the histograms are
+    integers, so every rank gets the whole raster's curve.  ValueError for a benchmark value the kernel does not know
+    (it knows -100, 0, 1 and, like k_confusion, takes a raw 2 for what 1 is remapped to)."""
+    th = _curve_thresholds(thresholds, None)
+    d_th, d_hist = ctx.to_device(th), ctx.empty(2 * (len(th) + 1) + 1, np.int64)
+    try:
+        check(_lib.lib().dt_dev_threshold_hist(ctx.h, desc_ptr, flood_ptr, n, float(nodata_value), d_th.ptr, len(th),
+                                               1 if under == 'under' else 0, d_hist.ptr))
+        hist = d_hist.to_host()
+    finally:
+        d_th.free()
+        d_hist.free()
+    if reduce_hist is not None:
+        hist = np.asarray(reduce_hist(hist), np.int64)
+    return _curve_of(th, hist, under == 'under')
 
 
 def combine_extremes(per_rank):

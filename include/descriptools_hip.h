@@ -437,6 +437,19 @@ int dt_d8_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, 
 int dt_confusion_multi(const double *desc, const int8_t *flood, int64_t N, double nodata_value,
                        const double *th, int nth, int under, int64_t *counts4);
 
+/* The same counts at every threshold of a sorted table from ONE pass: the histogram of the bin at which
+ * a cell's classification changes.  th: K thresholds, 1 <= K <= 65535, ascending by `<=` (equal neighbours, -0.0 beside
+ * +0.0 and +-inf are fine), none NaN -- checked here.  hist = int64[2 (K + 1) + 1]:
+ *   under != 0: a cell's bin j = #{k : th[k] <  v}, it floods at every k >= j; nodata / NaN cells get j = K
+ *   under == 0:             j = #{k : th[k] <= v}, it floods at every k <  j; nodata / NaN cells get j = 0
+ *   hist[j] counts the cells whose remapped benchmark value is 0, hist[K + 1 + j] those where it is 2, hist[2K + 2] the
+ *   cells with any other benchmark value (which dt_confusion_multi counts by their sum; here they are only reported).
+ * Cell semantics (nodata_value, NaN, the remap of flood) as dt_confusion_multi.  With c0 / c2 the inclusive prefix sums
+ * of the two histograms and T0 / T2 their totals, counts4[k] = {T0 - f0, f0, T2 - f2, f2} where f = c[k] (under) or
+ * T - c[k] (otherwise). */
+int dt_threshold_hist(const double *desc, const int8_t *flood, int64_t N, double nodata_value,
+                      const double *th, int K, int under, int64_t *hist);
+
 /* evaluation.minMaxScale (evaluation.py:5-9): out = NaN where x == nodata or x is NaN, else (x - mn) / (mx - mn),
  * in float32 for a float32 raster (is_f32) and float64 otherwise -- numpy's arithmetic for those dtypes. */
 int dt_minmax_scale(const void *x, int is_f32, int64_t N, double mn, double mx, double nodata, void *out);
@@ -689,6 +702,13 @@ int dt_dev_downslope_finish(dt_ctx *ctx, const float *dem, const uint8_t *fdr, i
 int dt_dev_confusion_multi(dt_ctx *ctx, const double *desc, const int8_t *flood, int64_t N,
                            double nodata_value, const double *th_host, int nth, int under,
                            int64_t *counts4_dev);
+/* dt_threshold_hist on resident rasters: th_dev = device float64[K], hist_dev = device int64[2 (K + 1) + 1], zeroed by
+ * the call.  PRECONDITIONS, not checked: th_dev is ascending by `<=` and holds no NaN (the search counts a prefix of the
+ * table; on an unsorted table the bins are meaningless, though every access stays inside the arrays).  N <= 2^39.  One
+ * memset and one launch on the context's stream while K + 1 <= 18432 bins fit the workgroup's LDS, one launch per 18432
+ * bins above; no scratch. */
+int dt_dev_threshold_hist(dt_ctx *ctx, const double *desc, const int8_t *flood, int64_t N, double nodata_value,
+                          const double *th_dev, int K, int under, int64_t *hist_dev);
 /* ---- windowed device tier: the same kernels on one rank's window of a larger raster (multi-GPU).
  * Flow accumulation and HAND are split in two phases so the ranks can exchange one summary row per
  * cell of their core ring in between (descriptools_amd/tiling.py).  Ring order: top row, bottom row,
