@@ -768,6 +768,34 @@ extern "C" int dt_dev_terrain(dt_ctx *c, const float *dem, int64_t H, int64_t W,
   return d.done(dt_launch_terrain(c->stream, dem, H, W, px, radius, sx, sy, sz, out));
 }
 
+// focal statistics (dt_focal.hip): the radius table, frac_bits, origin, and which outputs go with how many radii
+static int dt_check_focal(double origin, int frac_bits, const int32_t *radii, int n_radii, bool stats, bool any) {
+  DT_REQUIRE(n_radii >= 1 && n_radii <= DT_FOCAL_RADII_MAX && radii, "1..32 radii per call");
+  for (int k = 0; k < n_radii; k++) {
+    DT_REQUIRE(radii[k] >= 1 && radii[k] <= DT_FOCAL_RADIUS_MAX, "a radius must lie in [1, 4096]");
+    DT_REQUIRE(k == 0 || radii[k] > radii[k - 1], "radii must be strictly increasing");
+  }
+  DT_REQUIRE(frac_bits >= 0 && frac_bits <= DT_FOCAL_FRAC_BITS_MAX, "frac_bits must lie in [0, 24]");
+  DT_REQUIRE(std::isfinite(origin), "origin must be finite");
+  DT_REQUIRE(n_radii == 1 || !stats, "with more than one radius only dev and scale are defined");
+  DT_REQUIRE(any, "no output raster");
+  return DT_OK;
+}
+extern "C" int dt_dev_focal(dt_ctx *c, const float *dem, int64_t H, int64_t W, double origin, int frac_bits,
+                            const int32_t *radii, int n_radii, int32_t *count, float *mean, float *std_, float *tpi,
+                            float *dev, uint16_t *scale) {
+  DT_DEV(d, c, H, W, 1.0);
+  const bool stats = count || mean || std_ || tpi;
+  DT_TRY(dt_check_focal(origin, frac_bits, radii, n_radii, stats, stats || dev || scale));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(dem, "NULL raster");
+  const size_t need = dt_focal_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_focal(c->stream, dem, H, W, origin, frac_bits, radii, n_radii, scr, need, count, mean, std_,
+                                tpi, dev, scale, c->status));
+}
+
 // lines of sight (dt_horizon.hip): the ranges of radius, skip and the flatness tangent
 static int dt_check_horizon(int radius, int skip, double flat_tan) {
   DT_REQUIRE(radius >= 1 && radius <= DT_HORIZON_RADIUS_MAX, "radius must lie in [1, 64]");
@@ -2228,6 +2256,36 @@ extern "C" int dt_terrain(const float *dem, int64_t H, int64_t W, double px, int
   for (int o = 0; o < DT_TERRAIN_OUTPUTS; o++) d[o] = hc.out(host[o], n);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_terrain(hc.c, d_dem, H, W, px, radius, sx, sy, sz, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]));
+  return hc.finish();
+}
+
+extern "C" int dt_focal(const float *dem, int64_t H, int64_t W, double origin, int frac_bits, const int32_t *radii,
+                        int n_radii, int32_t *count, float *mean, float *std_, float *tpi, float *dev,
+                        uint16_t *scale) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  const bool stats = count || mean || std_ || tpi;
+  DT_TRY(dt_check_focal(origin, frac_bits, radii, n_radii, stats, stats || dev || scale));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  int32_t *d_count = hc.out(count, n);
+  float *d_mean = hc.out(mean, n), *d_std = hc.out(std_, n), *d_tpi = hc.out(tpi, n), *d_dev = hc.out(dev, n);
+  uint16_t *d_scale = hc.out(scale, n);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  DT_TRY(dt_dev_focal(hc.c, d_dem, H, W, origin, frac_bits, radii, n_radii, d_count, d_mean, d_std, d_tpi, d_dev,
+                      d_scale));
+  DT_TRY(dt_ctx_status(hc.c, &st));
+  if (st & DT_STATUS_BAD_HEIGHT) {
+    dt_set_error("invalid argument: a valid height is outside the contract of origin=%.17g, frac_bits=%d: "
+                 "0 <= rint((z - origin) * 2^frac_bits) <= %lld (the bound of radius %d)",
+                 origin, frac_bits, (long long)dt_focal_qmax(radii[n_radii - 1]), (int)radii[n_radii - 1]);
+    return DT_EINVAL;
+  }
   return hc.finish();
 }
 

@@ -329,6 +329,22 @@ const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 int dt_launch_terrain(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, int radius, double sx,
                       double sy, double sz, float *const out[DT_TERRAIN_OUTPUTS]);
 
+// Focal statistics at any radius (dt_focal.hip; focal.py holds the definition): summed-area tables of [valid], q and q^2
+// (q = rint((z - origin) * 2^frac_bits), the latter two modulo 2^64) in `scratch`, then per cell and radius the
+// four-corner window sums and a float64 stage.  n_radii == 1: count, mean, std, tpi, dev (and scale = the radius) of
+// that window, each where its pointer is not NULL; n_radii > 1: DEVmax over the strictly increasing table `radii`
+// (host memory) into dev and scale.  A valid height with q outside [0, dt_focal_qmax(radii[n_radii - 1])] raises
+// DT_STATUS_BAD_HEIGHT on `status` and counts as q = 0.  Four launches whatever the rasters hold, nothing
+// synchronises.  H * W < 2^31.
+#define DT_FOCAL_RADIUS_MAX 4096
+#define DT_FOCAL_RADII_MAX 32
+#define DT_FOCAL_FRAC_BITS_MAX 24
+size_t dt_focal_scratch(int64_t H, int64_t W);
+int64_t dt_focal_qmax(int radius);  // the largest q with (2 radius + 1)^2 q^2 < 2^63
+int dt_launch_focal(hipStream_t s, const float *dem, int64_t H, int64_t W, double origin, int frac_bits,
+                    const int32_t *radii, int n_radii, void *scratch, size_t scratch_bytes, int32_t *count,
+                    float *mean, float *std_, float *tpi, float *dev, uint16_t *scale, int *status);
+
 // Lines of sight (dt_horizon.hip; horizon.py holds the definition): from every cell the largest and the smallest tangent
 // of the elevation angle to the samples skip + 1 .. radius of each of the eight compass directions, t = (z_k - z0) *
 // (1 / (k step)) in float64 with the reciprocals tabulated here on the host and handed to the kernel by value, and what

@@ -182,6 +182,9 @@ class Context:
         if st & 4:
             raise ValueError("dt_dev_flowacc_weighted met a weight that is negative, not finite or over the bound of "
                              "its frac_bits (DT_STATUS_BAD_WEIGHT): the weighted accumulation is not valid")
+        if st & 64:
+            raise ValueError("dt_dev_focal met a valid height below its origin or over the bound of its frac_bits and "
+                             "largest radius (DT_STATUS_BAD_HEIGHT): the focal statistics of that call are not valid")
 
     def fork(self, child):
         """`child`'s stream waits (on the device) for everything enqueued so far on this context's stream."""

@@ -106,6 +106,10 @@ int dt_graph_destroy(dt_graph *graph);
 /* DT_STATUS_BAD_SHARES: dt_dev_mfd_accumulate met a share word outside its contract (not eight 0xFFFF, and a slot above
  * 32768 or slots that sum to neither 0 nor 32768); that cell was taken as having no receiver. */
 #define DT_STATUS_BAD_SHARES 32
+/* DT_STATUS_BAD_HEIGHT: dt_dev_focal met a valid height whose quantised value rint((z - origin) * 2^frac_bits) is
+ * negative or over the bound of the call's largest radius; that cell counted as 0 and the rasters of that call are not
+ * valid. */
+#define DT_STATUS_BAD_HEIGHT 64
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
 
@@ -304,6 +308,28 @@ int dt_terrain(const float *dem, int64_t H, int64_t W, double px, int radius, do
  * rasters of 2^31 cells or more and a px that is not finite and > 0 are refused. */
 int dt_horizon(const float *dem, int64_t H, int64_t W, double px, int radius, int skip, double flat_tan,
                uint8_t *landform, uint16_t *pattern, float *positive, float *negative, float *sky_view);
+/* Net-new: focal statistics at any radius -- count, mean and standard deviation of the heights in the (2 R + 1)^2 window
+ * of every cell, the topographic position index TPI (Weiss 2001), the deviation from mean elevation DEV (De Reu et al.
+ * 2013) and the multi-scale DEVmax with its scale (Lindsay et al. 2015); descriptools_amd/focal.py holds the full
+ * definition.  A height is valid when it is finite and > -100.  Quantisation: q = (int64)rint(((double)z - origin) *
+ * 2^frac_bits), rint to even, of a valid cell; the window of radius R is the square clipped to the raster, invalid
+ * cells in it are skipped, and a cell has a value iff its own height is valid.  With q_c the centre's q, over the valid
+ * cells i of the window: n the count, A = sum (q_i - q_c), B = sum (q_i - q_c)^2, exact integers.  They come from the
+ * inclusive two-dimensional prefix sums of [valid], q and q^2, the latter two uint64 with wrap-around: a window sum is
+ * the four-corner difference modulo 2^64, A = S1 - n q_c, B = S2 - 2 q_c S1 + n q_c^2 modulo 2^64, read as int64.
+ * Contract: 0 <= q <= qmax(R_max), the largest integer with (2 R_max + 1)^2 qmax^2 < 2^63, R_max the call's largest
+ * radius; a valid height outside it raises DT_STATUS_BAD_HEIGHT, counts as q = 0 and fails the call.  Float stage,
+ * IEEE float64 in this association: nf = (double)n, a = (double)A / nf, b = (double)B / nf, var = b - a a (0 when
+ * negative), sd = sqrt(var), u = 2^-frac_bits.  count = n (int32; 0 without a value), mean = (float)(origin +
+ * ((double)q_c + a) u) and std = (float)(sd u) (population; -100 without a value), tpi = (float)((-a) u) and dev =
+ * (float)((-a) / sd), 0.0 when sd == 0 (NaN without a value).  radii is a strictly increasing table of n_radii radii
+ * (1..32, each in [1, 4096]) in host memory.  n_radii == 1: each of count, mean, std, tpi, dev, scale may be NULL, not
+ * all; scale = the radius (uint16; 0 without a value).  n_radii > 1 (DEVmax): only dev and scale may be given; per
+ * cell d_k = (-a_k) / sd_k (0 when sd_k == 0) in float64 for every radius, the one of largest |d_k| is kept, a tie
+ * keeps the smaller radius; dev = (float)d_k, scale = that radius.  frac_bits must lie in [0, 24], origin must be
+ * finite; rasters of 2^31 cells or more are refused.  Every output is the numpy reference's bit for bit. */
+int dt_focal(const float *dem, int64_t H, int64_t W, double origin, int frac_bits, const int32_t *radii, int n_radii,
+             int32_t *count, float *mean, float *std, float *tpi, float *dev, uint16_t *scale);
 /* Net-new: exact Euclidean proximity to the river network.  A source is a cell with river == 1 that is not nodata;
  * nodata is a cell with nod <= -100, where nod (may be NULL: no nodata) is any float32 raster of the shape: a float32
  * DEM, or for heights float32 cannot hold the -100 / 0 mask of the DEM's own comparison (descriptools_amd._lib.
@@ -570,6 +596,16 @@ int dt_dev_terrain(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, do
 int dt_dev_horizon(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double px, int radius, int skip,
                    double flat_tan, uint8_t *landform, uint16_t *pattern, float *positive, float *negative,
                    float *sky_view);
+/* dt_focal on device rasters (rows x cols = H x W; radii in host memory, it travels as a kernel argument), on the
+ * context's stream: four launches whatever the rasters hold, no synchronisation.  The tables (22.5 bytes per cell: a
+ * uint32 and two uint64 planes, and the column sums of every band of 8 rows) are the context's scratch; nothing is kept
+ * between calls.  Checked in this order: the context and shape, the radius table, frac_bits, origin, the outputs that
+ * go with n_radii, at least one output; rows * cols == 0 is DT_OK; then a non-NULL dem.  A valid height outside the
+ * contract raises DT_STATUS_BAD_HEIGHT on the context (dt_ctx_status) and counts as q = 0: the rasters of that call
+ * are not valid. */
+int dt_dev_focal(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double origin, int frac_bits,
+                 const int32_t *radii, int n_radii, int32_t *count, float *mean, float *std, float *tpi, float *dev,
+                 uint16_t *scale);
 /* The reach calls on device rasters, on the context's stream: none synchronises.  idx is int32 (idx_bytes 4, the
  * resident chain's raster) or int64 (8); n_reaches (may be NULL) is one int64 on the device; heads entries from R on
  * are left as they were.  dt_dev_reach_tables takes `stages` from the host (they travel as kernel arguments) and the
