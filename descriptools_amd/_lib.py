@@ -59,6 +59,9 @@ _SIGS = {
     "dt_terrain": (ci, [c_f32p, i64, i64, f64, ci, f64, f64, f64] + [c_f32p] * 8),
     "dt_horizon": (ci, [c_f32p, i64, i64, f64, ci, ci, f64, c_u8p, c_u16p, c_f32p, c_f32p, c_f32p]),
     "dt_focal": (ci, [c_f32p, i64, i64, f64, ci, c_i32p, ci, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u16p]),
+    "dt_mrvbf": (ci, [c_f32p, i64, i64, f64, f64, ci, f64, f64, c_f64p, c_f32p, c_f32p]),
+    "dt_percentile": (ci, [c_f32p, i64, i64, ci, c_f32p, c_f32p]),
+    "dt_coarsen": (ci, [c_f32p, i64, i64, f64, c_f64p, c_f32p, c_f32p]),
     "dt_proximity": (ci, [c_i8p, c_f32p, i64, i64, f64, c_f32p, c_i64p]),
     "dt_reach_catchments": (ci, [c_i64p, c_i64p, i64, i64, c_i32p, c_i32p, c_i64p, i64, c_i64p]),
     "dt_reach_channels": (ci, [c_u8p, c_i32p, i64, i64, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
@@ -115,6 +118,9 @@ _SIGS = {
     "dt_dev_terrain": (ci, [vp, vp, i64, i64, f64, ci, f64, f64, f64] + [vp] * 8),
     "dt_dev_horizon": (ci, [vp, vp, i64, i64, f64, ci, ci, f64] + [vp] * 5),
     "dt_dev_focal": (ci, [vp, vp, i64, i64, f64, ci, c_i32p, ci] + [vp] * 6),
+    "dt_dev_mrvbf": (ci, [vp, vp, i64, i64, f64, f64, ci, f64, f64, c_f64p, vp, vp]),
+    "dt_dev_percentile": (ci, [vp, vp, i64, i64, ci, vp, vp]),
+    "dt_dev_coarsen": (ci, [vp, vp, i64, i64, f64, c_f64p, vp, vp]),
     "dt_dev_reach_catchments": (ci, [vp, vp, vp, ci, i64, i64, vp, vp, vp, i64, vp]),
     "dt_dev_reach_channels": (ci, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "dt_dev_reach_tables": (ci, [vp, vp, vp, ci, vp, i64, i64, c_f64p, ci, i64, ci, vp, vp, vp]),

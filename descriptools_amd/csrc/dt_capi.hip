@@ -815,6 +815,61 @@ extern "C" int dt_dev_horizon(dt_ctx *c, const float *dem, int64_t H, int64_t W,
                                   negative, sky_view));
 }
 
+// valley bottom / ridge top flatness (dt_mrvbf.hip): the ranges of the thresholds, the levels and the exponent table
+static int dt_check_mrvbf(double slope_threshold, int levels, double pctl_valley, double pctl_ridge, const double *p) {
+  DT_REQUIRE(std::isfinite(slope_threshold) && slope_threshold > 0.0, "slope_threshold must be finite and > 0");
+  DT_REQUIRE(levels >= 2 && levels <= DT_MRVBF_LEVELS_MAX, "levels must lie in [2, 10]");
+  DT_REQUIRE(pctl_valley > 0.0 && pctl_valley <= 1.0 && pctl_ridge > 0.0 && pctl_ridge <= 1.0,
+             "pctl_valley and pctl_ridge must lie in (0, 1]");
+  DT_REQUIRE(p, "the exponent table is NULL");
+  for (int k = 0; k < levels - 1; k++) {
+    DT_REQUIRE(std::isfinite(p[k]) && p[k] > 0.0, "an exponent must be finite and > 0");
+  }
+  return DT_OK;
+}
+extern "C" int dt_dev_mrvbf(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, double slope_threshold,
+                            int levels, double pctl_valley, double pctl_ridge, const double *p, float *mrvbf,
+                            float *mrrtf) {
+  DT_DEV(d, c, H, W, px);
+  DT_TRY(dt_check_mrvbf(slope_threshold, levels, pctl_valley, pctl_ridge, p));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(mrvbf || mrrtf, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const size_t need = dt_mrvbf_scratch(H, W, levels);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_mrvbf(c->stream, dem, H, W, px, slope_threshold, levels, pctl_valley, pctl_ridge, p, scr,
+                                need, mrvbf, mrrtf));
+}
+static int dt_check_percentile(int radius) {
+  DT_REQUIRE(radius >= 1 && radius <= DT_PERCENTILE_RADIUS_MAX, "radius must lie in [1, 16]");
+  return DT_OK;
+}
+extern "C" int dt_dev_percentile(dt_ctx *c, const float *dem, int64_t H, int64_t W, int radius, float *lower,
+                                 float *higher) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_percentile(radius));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(lower || higher, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  return d.done(dt_launch_percentile(c->stream, dem, H, W, radius, lower, higher));
+}
+static int dt_check_coarsen(const double *g6) {
+  DT_REQUIRE(g6, "the Gaussian weights are NULL");
+  for (int k = 0; k < 6; k++) {
+    DT_REQUIRE(std::isfinite(g6[k]) && g6[k] > 0.0, "a Gaussian weight must be finite and > 0");
+  }
+  return DT_OK;
+}
+extern "C" int dt_dev_coarsen(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, const double *g6,
+                              float *dem3, float *slope3) {
+  DT_DEV(d, c, H, W, px);
+  DT_TRY(dt_check_coarsen(g6));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(dem && dem3 && slope3, "NULL raster");
+  return d.done(dt_launch_coarsen(c->stream, dem, H, W, px, g6, dem3, slope3));
+}
+
 // reaches: reach ids and flat indices travel in 31 bits
 static int dt_check_reach_count(int64_t R) {
   DT_REQUIRE(R >= 0 && R < (1ll << 31), "the number of reaches must lie in [0, 2^31)");
@@ -2305,6 +2360,55 @@ extern "C" int dt_horizon(const float *dem, int64_t H, int64_t W, double px, int
   float *d_pos = hc.out(positive, n), *d_neg = hc.out(negative, n), *d_sky = hc.out(sky_view, n);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_horizon(hc.c, d_dem, H, W, px, radius, skip, flat_tan, d_form, d_pat, d_pos, d_neg, d_sky));
+  return hc.finish();
+}
+
+extern "C" int dt_mrvbf(const float *dem, int64_t H, int64_t W, double px, double slope_threshold, int levels,
+                        double pctl_valley, double pctl_ridge, const double *p, float *mrvbf, float *mrrtf) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_TRY(dt_check_mrvbf(slope_threshold, levels, pctl_valley, pctl_ridge, p));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(mrvbf || mrrtf, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  float *d_v = hc.out(mrvbf, n), *d_r = hc.out(mrrtf, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_mrvbf(hc.c, d_dem, H, W, px, slope_threshold, levels, pctl_valley, pctl_ridge, p, d_v, d_r));
+  return hc.finish();
+}
+
+extern "C" int dt_percentile(const float *dem, int64_t H, int64_t W, int radius, float *lower, float *higher) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_TRY(dt_check_percentile(radius));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(lower || higher, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  float *d_lo = hc.out(lower, n), *d_hi = hc.out(higher, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_percentile(hc.c, d_dem, H, W, radius, d_lo, d_hi));
+  return hc.finish();
+}
+
+extern "C" int dt_coarsen(const float *dem, int64_t H, int64_t W, double px, const double *g6, float *dem3,
+                          float *slope3) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_TRY(dt_check_coarsen(g6));
+  const size_t n = (size_t)H * W, nc = (size_t)((H + 2) / 3) * (size_t)((W + 2) / 3);
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem && dem3 && slope3, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  float *d_z = hc.out(dem3, nc), *d_s = hc.out(slope3, nc);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_coarsen(hc.c, d_dem, H, W, px, g6, d_z, d_s));
   return hc.finish();
 }
 

@@ -345,6 +345,26 @@ int dt_launch_focal(hipStream_t s, const float *dem, int64_t H, int64_t W, doubl
                     const int32_t *radii, int n_radii, void *scratch, size_t scratch_bytes, int32_t *count,
                     float *mean, float *std_, float *tpi, float *dev, uint16_t *scale, int *status);
 
+// Valley bottom and ridge top flatness (dt_mrvbf.hip; mrvbf.py holds the definition).  dt_launch_percentile: per cell
+// the shares of the valid cells of the clipped disc of `radius` that are strictly lower / strictly higher (a NULL
+// output is neither computed nor stored, at least one is given; -100 where the centre is not valid).
+// dt_launch_coarsen: one generalisation step of a raster of cell size px with the Gaussian weights g6[k] =
+// exp(-k^2 / 18) (host memory) -> the smoothed height and its slope in percent at a third of the resolution, rasters of
+// ceil(H / 3) x ceil(W / 3) cells.  dt_launch_mrvbf: MRVBF and / or MRRTF over `levels` levels (2 .. 10) with the
+// exponents p[L - 2] of the levels L = 2 .. levels (host memory); the pyramid of the levels >= 3 lives in `scratch`
+// (16 B per coarse cell), 2 (levels - 2) launches build it and one launch at base resolution writes the outputs.
+// Nothing synchronises.  H * W < 2^31.
+#define DT_PERCENTILE_RADIUS_MAX 16
+#define DT_MRVBF_LEVELS_MAX 10
+int dt_launch_percentile(hipStream_t s, const float *dem, int64_t H, int64_t W, int radius, float *lower,
+                         float *higher);
+int dt_launch_coarsen(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, const double *g6, float *dem3,
+                      float *slope3);
+size_t dt_mrvbf_scratch(int64_t H, int64_t W, int levels);
+int dt_launch_mrvbf(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, double slope_threshold,
+                    int levels, double pctl_valley, double pctl_ridge, const double *p, void *scratch,
+                    size_t scratch_bytes, float *mrvbf, float *mrrtf);
+
 // Lines of sight (dt_horizon.hip; horizon.py holds the definition): from every cell the largest and the smallest tangent
 // of the elevation angle to the samples skip + 1 .. radius of each of the eight compass directions, t = (z_k - z0) *
 // (1 / (k step)) in float64 with the reciprocals tabulated here on the host and handed to the kernel by value, and what

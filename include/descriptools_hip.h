@@ -330,6 +330,29 @@ int dt_horizon(const float *dem, int64_t H, int64_t W, double px, int radius, in
  * finite; rasters of 2^31 cells or more are refused.  Every output is the numpy reference's bit for bit. */
 int dt_focal(const float *dem, int64_t H, int64_t W, double origin, int frac_bits, const int32_t *radii, int n_radii,
              int32_t *count, float *mean, float *std, float *tpi, float *dev, uint16_t *scale);
+/* Net-new: the multi-resolution valley bottom flatness MRVBF and ridge top flatness MRRTF (Gallant & Dowling 2003) and
+ * their two building blocks; descriptools_amd/mrvbf.py holds the full definition.  A height is valid when it is finite
+ * and > -100; all arithmetic is IEEE float64 on the float32 heights, the rasters of a pyramid level are float32.
+ * dt_percentile: over the disc dx^2 + dy^2 <= radius^2 clipped to the raster, centre included, n valid cells, l of them
+ * strictly lower and h strictly higher than the centre (compared as float32): lower = (float)((double)l / n), higher =
+ * (float)((double)h / n), -100 where the centre is not valid.  Each may be NULL, not both; radius in [1, 16].
+ * dt_coarsen: one generalisation step of a raster of cell size px.  g6[k] = exp(-k^2 / 18), k = 0..5 (host memory).
+ * Row sums of g z over the valid cells of the 11 taps, k ascending -5..5, then column sums of those, again ascending;
+ * the same of g [valid]; the smoothed height of a valid cell is their quotient, its slope (percent) takes central
+ * differences over 2 px where both neighbours are valid, one-sided ones over px where one is, 0 where none is, S = 100
+ * sqrt(p p + q q).  dem3 / slope3[I][J] = the mean of the smoothed height / of the slope over the valid cells of rows
+ * 3I..3I+2 and columns 3J..3J+2 (clipped, row-major sum over count), -100 where the block has none; both are rasters of
+ * ceil(H / 3) x ceil(W / 3) cells.  Both ops equal the numpy reference of the tests bit for bit.
+ * dt_mrvbf: the index over `levels` levels (2..10; levels 1 and 2 are the base raster, level L >= 3 the raster
+ * coarsened L - 2 times) with the first slope threshold slope_threshold (percent, finite and > 0), the percentile
+ * thresholds pctl_valley and pctl_ridge in (0, 1] and the exponents p[L - 2] of the levels L = 2..levels (host memory;
+ * log10((L - 0.5) / 0.1) / log10(1.5)).  mrvbf and mrrtf may each be NULL (then neither computed nor stored), not
+ * both; -100 where the height is not valid.  One pow per level and output: the tests hold it to one float32 spacing of
+ * the reference.  Rasters of 2^31 cells or more and a px that is not finite and > 0 are refused. */
+int dt_mrvbf(const float *dem, int64_t H, int64_t W, double px, double slope_threshold, int levels, double pctl_valley,
+             double pctl_ridge, const double *p, float *mrvbf, float *mrrtf);
+int dt_percentile(const float *dem, int64_t H, int64_t W, int radius, float *lower, float *higher);
+int dt_coarsen(const float *dem, int64_t H, int64_t W, double px, const double *g6, float *dem3, float *slope3);
 /* Net-new: exact Euclidean proximity to the river network.  A source is a cell with river == 1 that is not nodata;
  * nodata is a cell with nod <= -100, where nod (may be NULL: no nodata) is any float32 raster of the shape: a float32
  * DEM, or for heights float32 cannot hold the -100 / 0 mask of the DEM's own comparison (descriptools_amd._lib.
@@ -606,6 +629,19 @@ int dt_dev_horizon(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, do
 int dt_dev_focal(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double origin, int frac_bits,
                  const int32_t *radii, int n_radii, int32_t *count, float *mean, float *std, float *tpi, float *dev,
                  uint16_t *scale);
+/* dt_mrvbf, dt_percentile and dt_coarsen on device rasters (rows x cols = H x W; p and g6 in host memory, they travel
+ * as kernel arguments), on the context's stream, no synchronisation.  dt_dev_mrvbf keeps the pyramid of the levels >= 3
+ * (float32 height, slope, lower and higher percentile: 16 bytes per coarse cell, about 2 bytes per base cell over all
+ * levels) in the context's scratch: two launches per level >= 3 build it, one launch at base resolution writes the
+ * outputs; nothing is kept between calls.  dt_dev_percentile and dt_dev_coarsen are one launch each and take no
+ * scratch; dem3 and slope3 hold ceil(rows / 3) x ceil(cols / 3) cells.  Checked in this order: the context and shape
+ * (and px), the op's own arguments; rows * cols == 0 is DT_OK; then the outputs and a non-NULL dem. */
+int dt_dev_mrvbf(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double px, double slope_threshold,
+                 int levels, double pctl_valley, double pctl_ridge, const double *p, float *mrvbf, float *mrrtf);
+int dt_dev_percentile(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, int radius, float *lower,
+                      float *higher);
+int dt_dev_coarsen(dt_ctx *ctx, const float *dem, int64_t rows, int64_t cols, double px, const double *g6,
+                   float *dem3, float *slope3);
 /* The reach calls on device rasters, on the context's stream: none synchronises.  idx is int32 (idx_bytes 4, the
  * resident chain's raster) or int64 (8); n_reaches (may be NULL) is one int64 on the device; heads entries from R on
  * are left as they were.  dt_dev_reach_tables takes `stages` from the host (they travel as kernel arguments) and the
