@@ -67,6 +67,10 @@ _SIGS = {
     "dt_reach_channels": (ci, [c_u8p, c_i32p, i64, i64, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
     "dt_reach_tables": (ci, [c_i32p, vp, ci, c_f32p, i64, i64, c_f64p, ci, i64, ci, c_i64p, c_i64p, c_i64p]),
     "dt_inundate": (ci, [c_i32p, vp, ci, c_f64p, i64, i64, i64, c_f32p]),
+    "dt_zonal_compact": (ci, [vp, ci, i64, i64, i64, c_i32p, c_i64p, i64, c_i64p]),
+    "dt_zonal_tables": (ci, [c_i32p, vp, ci, i64, i64, i64, f64, ci, ci, f64, c_i64p, c_i64p, vp, vp, vp, vp]),
+    "dt_zonal_counts": (ci, [c_i32p, vp, ci, i64, i64, i64, c_f64p, ci, ci, f64, c_i64p]),
+    "dt_zonal_paint": (ci, [vp, ci, i64, c_i32p, i64, i64, vp, vp]),
     "dt_regions_label": (ci, [c_u8p, i64, i64, ci, c_i64p, c_i64p]),
     "dt_regions_select": (ci, [c_u8p, c_u8p, i64, i64, ci, i64, c_u8p]),
     "dt_inundate_connected": (ci, [c_i32p, vp, ci, c_f64p, c_i8p, i64, i64, i64, ci, c_f32p]),
@@ -125,6 +129,10 @@ _SIGS = {
     "dt_dev_reach_channels": (ci, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "dt_dev_reach_tables": (ci, [vp, vp, vp, ci, vp, i64, i64, c_f64p, ci, i64, ci, vp, vp, vp]),
     "dt_dev_inundate": (ci, [vp, vp, vp, ci, vp, i64, i64, i64, vp]),
+    "dt_dev_zonal_compact": (ci, [vp, vp, ci, i64, i64, i64, vp, vp, i64, vp]),
+    "dt_dev_zonal_tables": (ci, [vp, vp, vp, ci, i64, i64, i64, f64, ci, ci, f64, vp, vp, vp, vp, vp, vp]),
+    "dt_dev_zonal_counts": (ci, [vp, vp, vp, ci, i64, i64, i64, c_f64p, ci, ci, f64, vp]),
+    "dt_dev_zonal_paint": (ci, [vp, vp, ci, i64, vp, i64, i64, vp, vp]),
     "dt_dev_regions_label": (ci, [vp, vp, i64, i64, ci, vp, vp]),
     "dt_dev_regions_select": (ci, [vp, vp, vp, i64, i64, ci, i64, vp]),
     "dt_dev_inundate_connected": (ci, [vp, vp, vp, ci, vp, vp, i64, i64, i64, ci, vp]),

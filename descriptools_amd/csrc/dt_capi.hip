@@ -944,6 +944,96 @@ extern "C" int dt_dev_inundate(dt_ctx *c, const int32_t *catch_, const void *han
   return d.done(dt_launch_inundate(c->stream, catch_, hand, hand_bytes, stage, H * W, R, depth));
 }
 
+// zonal statistics: zone ids and labels travel in 31 bits
+static int dt_check_zone_count(int64_t n_zones) {
+  DT_REQUIRE(n_zones >= 0 && n_zones < (1ll << 31), "the number of zones must lie in [0, 2^31)");
+  return DT_OK;
+}
+static int dt_check_zonal_compact(int label_bytes, int64_t limit, int64_t cap) {
+  DT_REQUIRE(label_bytes == 4 || label_bytes == 8, "the labels' element size must be 4 or 8");
+  DT_REQUIRE(limit >= 1 && limit < (1ll << 31), "limit must lie in [1, 2^31)");
+  DT_REQUIRE(cap >= 0, "negative capacity");
+  return DT_OK;
+}
+static int dt_check_zonal_tables(int64_t n_zones, int value_bytes, double origin, int frac_bits, const void *s2_lo,
+                                 const void *s2_hi) {
+  DT_TRY(dt_check_zone_count(n_zones));
+  DT_REQUIRE(value_bytes == 4 || value_bytes == 8, "the values' element size must be 4 or 8");
+  DT_REQUIRE(frac_bits >= 0 && frac_bits <= 24, "frac_bits must lie in [0, 24]");
+  DT_REQUIRE(std::isfinite(origin), "origin must be finite");
+  DT_REQUIRE((s2_lo == nullptr) == (s2_hi == nullptr), "s2_lo and s2_hi go together");
+  return DT_OK;
+}
+static int dt_check_zonal_counts(int64_t n_zones, int value_bytes, const double *edges, int K) {
+  DT_TRY(dt_check_zone_count(n_zones));
+  DT_REQUIRE(value_bytes == 0 || value_bytes == 4 || value_bytes == 8, "the values' element size must be 0, 4 or 8");
+  DT_REQUIRE(K >= 1 && K <= 1024, "1..1024 columns per call");
+  DT_REQUIRE(n_zones * (int64_t)K * 8 <= (1ll << 31), "the table n_zones * K * 8 bytes exceeds 2 GiB");
+  if (value_bytes != 0) {
+    DT_REQUIRE(edges, "NULL edges");
+    for (int k = 0; k <= K; k++)
+      DT_REQUIRE(std::isfinite(edges[k]) && (k == 0 || edges[k] > edges[k - 1]),
+                 "edges must be finite and strictly increasing");
+  }
+  return DT_OK;
+}
+
+extern "C" int dt_dev_zonal_compact(dt_ctx *c, const void *labels, int label_bytes, int64_t H, int64_t W,
+                                    int64_t limit, int32_t *zones, int64_t *labels_of, int64_t cap, int64_t *n_zones) {
+  DT_DEV(d, c, H, W);
+  DT_TRY(dt_check_zonal_compact(label_bytes, limit, cap));
+  const int64_t N = H * W;
+  DT_REQUIRE(labels || N == 0, "NULL raster");
+  DT_REQUIRE(labels_of || cap == 0, "a capacity without labels_of");
+  const size_t need = dt_zonal_compact_scratch(limit);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_zonal_compact(c->stream, labels, label_bytes, N, limit, scr, need, zones,
+                                        cap ? labels_of : nullptr, cap, n_zones));
+}
+
+extern "C" int dt_dev_zonal_tables(dt_ctx *c, const int32_t *zones, const void *values, int value_bytes, int64_t H,
+                                   int64_t W, int64_t n_zones, double origin, int frac_bits, int has_nodata,
+                                   double nodata, int64_t *count, int64_t *s1, uint64_t *s2_lo, uint64_t *s2_hi,
+                                   void *vmin, void *vmax) {
+  DT_DEV(d, c, H, W);
+  DT_TRY(dt_check_zonal_tables(n_zones, value_bytes, origin, frac_bits, s2_lo, s2_hi));
+  if (n_zones == 0) return DT_OK;
+  DT_REQUIRE((zones && values) || H * W == 0, "NULL raster");
+  DT_REQUIRE(count || s1 || s2_lo || vmin || vmax, "no table");
+  return d.done(dt_launch_zonal_tables(c->stream, zones, values, value_bytes, H, W, n_zones, origin, frac_bits,
+                                       has_nodata != 0, nodata, count, s1, s2_lo, s2_hi, vmin, vmax, c->status,
+                                       dt_debug_get(DT_DBG_RC_SLOTS)));
+}
+
+extern "C" int dt_dev_zonal_counts(dt_ctx *c, const int32_t *zones, const void *values, int value_bytes, int64_t H,
+                                   int64_t W, int64_t n_zones, const double *edges, int K, int has_nodata,
+                                   double nodata, int64_t *counts) {
+  DT_DEV(d, c, H, W);
+  DT_TRY(dt_check_zonal_counts(n_zones, value_bytes, edges, K));
+  if (n_zones == 0) return DT_OK;
+  DT_REQUIRE((zones && values) || H * W == 0, "NULL raster");
+  DT_REQUIRE(counts, "NULL table");
+  const size_t need = dt_zonal_counts_scratch(K);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_zonal_counts(c->stream, zones, values, value_bytes, H, W, n_zones, edges, K, has_nodata != 0,
+                                       nodata, scr, need, counts, c->status, dt_debug_get(DT_DBG_RC_SLOTS)));
+}
+
+extern "C" int dt_dev_zonal_paint(dt_ctx *c, const void *table, int elem_bytes, int64_t n_table, const int32_t *zones,
+                                  int64_t H, int64_t W, const void *fill, void *out) {
+  DT_DEV(d, c, H, W);
+  DT_TRY(dt_check_zone_count(n_table));
+  DT_REQUIRE(elem_bytes == 4 || elem_bytes == 8, "the table's element size must be 4 or 8");
+  DT_REQUIRE(fill, "NULL fill");
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(zones && out && (table || n_table == 0), "NULL raster");
+  uint64_t bits = 0;
+  memcpy(&bits, fill, (size_t)elem_bytes);
+  return d.done(dt_launch_zonal_paint(c->stream, table, elem_bytes, n_table, zones, H * W, bits, out));
+}
+
 // connected regions: flat indices travel in int32
 static int dt_check_regions(int connectivity, int64_t min_cells) {
   DT_REQUIRE(connectivity == 4 || connectivity == 8, "connectivity must be 4 or 8");
@@ -2585,6 +2675,99 @@ extern "C" int dt_inundate(const int32_t *catch_, const void *hand, int hand_byt
   float *d_d = hc.out(depth, n);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_inundate(hc.c, d_c, d_h, hand_bytes, d_s, H, W, R, d_d));
+  return hc.finish();
+}
+
+extern "C" int dt_zonal_compact(const void *labels, int label_bytes, int64_t H, int64_t W, int64_t limit,
+                                int32_t *zones, int64_t *labels_of, int64_t cap, int64_t *n_zones) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_zonal_compact(label_bytes, limit, cap));
+  DT_REQUIRE(n_zones && (labels_of || cap == 0), "bad arguments");
+  *n_zones = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(labels, "NULL raster");
+  if (cap > limit) cap = limit;
+  const unsigned char *d_l = hc.in((const unsigned char *)labels, n * (size_t)label_bytes);
+  int32_t *d_z = hc.out(zones, n);
+  int64_t *d_o = cap ? hc.out(labels_of, (size_t)cap) : nullptr;
+  int64_t *d_n = hc.scratch<int64_t>(1);
+  DT_TRY(hc.rc);
+  if (d_o) DT_HIP(hipMemsetAsync(d_o, 0xFF, (size_t)cap * 8, hc.c->stream));  // -1 beyond the last zone
+  DT_TRY(dt_dev_zonal_compact(hc.c, d_l, label_bytes, H, W, limit, d_z, d_o, cap, d_n));
+  DT_TRY(hc.download(n_zones, (const int64_t *)d_n, 1));
+  return hc.finish();
+}
+
+extern "C" int dt_zonal_tables(const int32_t *zones, const void *values, int value_bytes, int64_t H, int64_t W,
+                               int64_t n_zones, double origin, int frac_bits, int has_nodata, double nodata,
+                               int64_t *count, int64_t *s1, uint64_t *s2_lo, uint64_t *s2_hi, void *vmin, void *vmax) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_zonal_tables(n_zones, value_bytes, origin, frac_bits, s2_lo, s2_hi));
+  if (n_zones == 0) return DT_OK;
+  DT_REQUIRE(count || s1 || s2_lo || vmin || vmax, "no table");
+  const size_t n = (size_t)H * W, z = (size_t)n_zones;
+  DT_REQUIRE((zones && values) || n == 0, "NULL raster");
+  const int32_t *d_z = hc.in(zones, n);
+  const unsigned char *d_v = hc.in((const unsigned char *)values, n * (size_t)value_bytes);
+  int64_t *d_c = hc.out(count, z), *d_s1 = hc.out(s1, z);
+  uint64_t *d_lo = hc.out(s2_lo, z), *d_hi = hc.out(s2_hi, z);
+  unsigned char *d_mn = hc.out((unsigned char *)vmin, z * (size_t)value_bytes);
+  unsigned char *d_mx = hc.out((unsigned char *)vmax, z * (size_t)value_bytes);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  DT_TRY(dt_dev_zonal_tables(hc.c, d_z, d_v, value_bytes, H, W, n_zones, origin, frac_bits, has_nodata, nodata, d_c,
+                             d_s1, d_lo, d_hi, d_mn, d_mx));
+  DT_TRY(dt_ctx_status(hc.c, &st));
+  DT_REQUIRE(!(st & DT_STATUS_BAD_HEIGHT), "a value's |rint((v - origin) * 2^frac_bits)| exceeds 2^31 - 1");
+  DT_REQUIRE(!(st & DT_STATUS_ZONE_RANGE), "a zone id is >= the number of zones");
+  return hc.finish();
+}
+
+extern "C" int dt_zonal_counts(const int32_t *zones, const void *values, int value_bytes, int64_t H, int64_t W,
+                               int64_t n_zones, const double *edges, int K, int has_nodata, double nodata,
+                               int64_t *counts) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_zonal_counts(n_zones, value_bytes, edges, K));
+  if (n_zones == 0) return DT_OK;
+  DT_REQUIRE(counts, "NULL table");
+  const size_t n = (size_t)H * W;
+  DT_REQUIRE((zones && values) || n == 0, "NULL raster");
+  const int32_t *d_z = hc.in(zones, n);
+  const unsigned char *d_v = hc.in((const unsigned char *)values, n * (size_t)(value_bytes ? value_bytes : 4));
+  int64_t *d_c = hc.out(counts, (size_t)n_zones * (size_t)K);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  DT_TRY(dt_dev_zonal_counts(hc.c, d_z, d_v, value_bytes, H, W, n_zones, edges, K, has_nodata, nodata, d_c));
+  DT_TRY(dt_ctx_status(hc.c, &st));
+  DT_REQUIRE(!(st & DT_STATUS_ZONE_RANGE), "a zone id is >= the number of zones (or a column >= K)");
+  return hc.finish();
+}
+
+extern "C" int dt_zonal_paint(const void *table, int elem_bytes, int64_t n_table, const int32_t *zones, int64_t H,
+                              int64_t W, const void *fill, void *out) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_hw(H, W));
+  DT_TRY(dt_check_zone_count(n_table));
+  DT_REQUIRE(elem_bytes == 4 || elem_bytes == 8, "the table's element size must be 4 or 8");
+  DT_REQUIRE(fill, "NULL fill");
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(zones && out && (table || n_table == 0), "NULL raster");
+  const unsigned char *d_t = hc.in((const unsigned char *)table, (size_t)n_table * (size_t)elem_bytes);
+  const int32_t *d_z = hc.in(zones, n);
+  unsigned char *d_o = hc.out((unsigned char *)out, n * (size_t)elem_bytes);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_zonal_paint(hc.c, d_t, elem_bytes, n_table, d_z, H, W, fill, d_o));
   return hc.finish();
 }
 

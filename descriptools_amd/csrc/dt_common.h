@@ -145,6 +145,36 @@ __device__ __forceinline__ uint32_t dt_block_scan_256(uint32_t v, uint32_t *s_w,
   return before + x - v;
 }
 
+// four consecutive values of a float32 / float64 raster, 16-byte loads (f a multiple of 4, the raster 16-byte aligned)
+template <typename HT>
+__device__ __forceinline__ void dt_load4(const HT *__restrict__ src, int64_t f, HT (&hh)[4]) {
+  if (sizeof(HT) == 4) {
+    const float4 q = *reinterpret_cast<const float4 *>(src + f);
+    hh[0] = (HT)q.x; hh[1] = (HT)q.y; hh[2] = (HT)q.z; hh[3] = (HT)q.w;
+  } else {
+    const double2 q0 = *reinterpret_cast<const double2 *>(src + f);
+    const double2 q1 = *reinterpret_cast<const double2 *>(src + f + 2);
+    hh[0] = (HT)q0.x; hh[1] = (HT)q0.y; hh[2] = (HT)q1.x; hh[3] = (HT)q1.y;
+  }
+}
+
+// The slot of id r in a workgroup's LDS table of S slots (the reach and the zonal tables), -1 when every slot belongs
+// to another id: linear probing from r mod S.  A key goes from empty (-1) to an id once and stays, so a slot found, or
+// found wanting, is final.
+__device__ __forceinline__ int dt_claim_slot(int *s_key, int S, int r) {
+  int j = S > 0 ? (int)((uint32_t)r % (uint32_t)S) : 0;
+  for (int i = 0; i < S; i++) {
+    int k = s_key[j];
+    if (k == -1) {
+      k = atomicCAS(&s_key[j], -1, r);
+      if (k == -1) return j;
+    }
+    if (k == r) return j;
+    if (++j == S) j = 0;
+  }
+  return -1;
+}
+
 // ---- D8 decoding (flowhand.py:801-824 / downslope.py:490-513) -------------------------------
 // code -> bit index: 1=E 2=SE 4=S 8=SW 16=W 32=NW 64=N 128=NE
 __device__ __forceinline__ bool dt_d8_valid(uint32_t code) {

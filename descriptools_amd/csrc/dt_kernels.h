@@ -400,3 +400,28 @@ int dt_launch_regions(hipStream_t s, const uint8_t *mask, const uint8_t *seeds, 
 int dt_launch_inundate_connected(hipStream_t s, const int32_t *catch_, const void *hand, int hand_bytes,
                                  const double *stage, const int8_t *river, int64_t H, int64_t W, int64_t R,
                                  int connectivity, void *scratch, size_t scratch_bytes, float *depth);
+
+// n doubles from host memory into device memory as kernel arguments, 128 per launch: no host copy, so the caller's
+// array may go away at once (the stages of the reach tables, the edges of the zonal histogram; dt_reaches.hip)
+void dt_launch_host_doubles(hipStream_t s, const double *src_host, int n, double *dst);
+
+// zonal statistics (dt_zonal.hip): label compaction, per-zone integer tables, per-zone histograms / cross-tabulation
+// and painting a table back onto its zones; definitions in include/descriptools_hip.h.  Nothing synchronises.
+// H * W < 2^31.  labels is int32 (label_bytes 4) or int64 (8); values is float32 (value_bytes 4) or float64 (8), and
+// for dt_launch_zonal_counts an int32 column raster with value_bytes 0 (cross-tabulation, K columns, edges unused).
+// Tables that are NULL are not computed.  slots: 0 the default LDS table, n > 0 at most n slots, < 0 no LDS table
+// (DT_DBG_RC_SLOTS).
+size_t dt_zonal_compact_scratch(int64_t limit);
+int dt_launch_zonal_compact(hipStream_t s, const void *labels, int label_bytes, int64_t N, int64_t limit,
+                            void *scratch, size_t scratch_bytes, int32_t *zones, int64_t *labels_of, int64_t cap,
+                            int64_t *n_zones_dev);
+int dt_launch_zonal_tables(hipStream_t s, const int32_t *zones, const void *values, int value_bytes, int64_t H,
+                           int64_t W, int64_t n_zones, double origin, int frac_bits, int has_nodata, double nodata,
+                           int64_t *count, int64_t *s1, uint64_t *s2_lo, uint64_t *s2_hi, void *vmin, void *vmax,
+                           int *status, int slots);
+size_t dt_zonal_counts_scratch(int K);
+int dt_launch_zonal_counts(hipStream_t s, const int32_t *zones, const void *values, int value_bytes, int64_t H,
+                           int64_t W, int64_t n_zones, const double *edges_host, int K, int has_nodata, double nodata,
+                           void *scratch, size_t scratch_bytes, int64_t *counts, int *status, int slots);
+int dt_launch_zonal_paint(hipStream_t s, const void *table, int elem_bytes, int64_t n_table, const int32_t *zones,
+                          int64_t N, uint64_t fill_bits, void *out);

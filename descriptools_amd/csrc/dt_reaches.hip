@@ -30,19 +30,6 @@
 #define RC_STAGE_CHUNK 128
 #define RC_NONE (-100)
 
-// four consecutive heights of an HT raster, 16-byte loads (f a multiple of 4, the raster 16-byte aligned)
-template <typename HT>
-__device__ __forceinline__ void rc_load4(const HT *__restrict__ hand, int64_t f, HT (&hh)[4]) {
-  if (sizeof(HT) == 4) {
-    const float4 q = *reinterpret_cast<const float4 *>(hand + f);
-    hh[0] = (HT)q.x; hh[1] = (HT)q.y; hh[2] = (HT)q.z; hh[3] = (HT)q.w;
-  } else {
-    const double2 q0 = *reinterpret_cast<const double2 *>(hand + f);
-    const double2 q1 = *reinterpret_cast<const double2 *>(hand + f + 2);
-    hh[0] = (HT)q0.x; hh[1] = (HT)q0.y; hh[2] = (HT)q1.x; hh[3] = (HT)q1.y;
-  }
-}
-
 // ---- catchments ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rc_count(const int64_t *__restrict__ link, int64_t N,
                                                   uint32_t *__restrict__ bcount) {
@@ -207,6 +194,15 @@ __global__ void k_rc_stages(RcStageChunk ch, int n, double *__restrict__ dst) {
   if ((int)threadIdx.x < n) dst[threadIdx.x] = ch.v[threadIdx.x];
 }
 
+void dt_launch_host_doubles(hipStream_t s, const double *src_host, int n, double *dst) {
+  for (int base = 0; base < n; base += RC_STAGE_CHUNK) {
+    RcStageChunk ch;
+    const int m = n - base < RC_STAGE_CHUNK ? n - base : RC_STAGE_CHUNK;
+    for (int i = 0; i < RC_STAGE_CHUNK; i++) ch.v[i] = i < m ? src_host[base + i] : 0.0;
+    hipLaunchKernelGGL(k_rc_stages, dim3(1), dim3(RC_STAGE_CHUNK), 0, s, ch, m, dst + base);
+  }
+}
+
 struct RcTablesArgs {
   int64_t H, W, R;
   int K, S, sbits, uniform;
@@ -260,22 +256,6 @@ __device__ __forceinline__ void rc_flush_run(const RcRun &run, uint32_t *s_c, un
   }
 }
 
-// the slot of reach r in this workgroup's table, -1 when every slot belongs to another reach.  A key goes from empty
-// (-1) to a reach id once and stays, so a slot found, or found wanting, is final.
-__device__ __forceinline__ int rc_slot(int *s_key, int S, int r) {
-  int j = S > 0 ? (int)((uint32_t)r % (uint32_t)S) : 0;
-  for (int i = 0; i < S; i++) {
-    int k = s_key[j];
-    if (k == -1) {
-      k = atomicCAS(&s_key[j], -1, r);
-      if (k == -1) return j;
-    }
-    if (k == r) return j;
-    if (++j == S) j = 0;
-  }
-  return -1;
-}
-
 template <typename HT, bool SLOPE, bool VEC>
 __global__ __launch_bounds__(256) void k_rc_tables(const int32_t *__restrict__ catch_, const HT *__restrict__ hand,
                                                    const float *__restrict__ slope,
@@ -317,7 +297,7 @@ __global__ __launch_bounds__(256) void k_rc_tables(const int32_t *__restrict__ c
     if (VEC) {  // W is a multiple of 4 and the rasters are 16-B aligned
       const int4 v = *reinterpret_cast<const int4 *>(catch_ + f);
       rr[0] = v.x; rr[1] = v.y; rr[2] = v.z; rr[3] = v.w;
-      rc_load4(hand, f, hh);
+      dt_load4(hand, f, hh);
       if (SLOPE) {
         const float4 q = *reinterpret_cast<const float4 *>(slope + f);
         ss[0] = q.x; ss[1] = q.y; ss[2] = q.z; ss[3] = q.w;
@@ -353,7 +333,7 @@ __global__ __launch_bounds__(256) void k_rc_tables(const int32_t *__restrict__ c
       }
       if (r != last_r) {
         last_r = r;
-        last_slot = rc_slot(s_key, a.S, r);
+        last_slot = dt_claim_slot(s_key, a.S, r);
       }
       const long long key = last_slot >= 0 ? (long long)last_slot * a.K + k : ~((long long)r * a.K + k);
       if (key != run.key) {
@@ -453,12 +433,7 @@ int dt_launch_reach_tables(hipStream_t s, const int32_t *catch_, const void *han
   if (N == 0) return DT_OK;
   DT_REQUIRE(scratch_bytes >= dt_reach_tables_scratch(K), "scratch too small");
   double *d_st = (double *)scratch;
-  for (int base = 0; base < K; base += RC_STAGE_CHUNK) {
-    RcStageChunk ch;
-    const int n = K - base < RC_STAGE_CHUNK ? K - base : RC_STAGE_CHUNK;
-    for (int i = 0; i < RC_STAGE_CHUNK; i++) ch.v[i] = i < n ? stages_host[base + i] : 0.0;
-    hipLaunchKernelGGL(k_rc_stages, dim3(1), dim3(RC_STAGE_CHUNK), 0, s, ch, n, d_st + base);
-  }
+  dt_launch_host_doubles(s, stages_host, K, d_st);
   RcTablesArgs a;
   a.H = H; a.W = W; a.R = R; a.K = K; a.sbits = frac_bits;
   a.S = rc_slots(K, slope != nullptr);
@@ -507,7 +482,7 @@ __global__ __launch_bounds__(256) void k_rc_inundate(const int32_t *__restrict__
   if (VEC && f + 4 <= N) {
     const int4 v = *reinterpret_cast<const int4 *>(catch_ + f);
     HT hh[4];
-    rc_load4(hand, f, hh);
+    dt_load4(hand, f, hh);
     *reinterpret_cast<float4 *>(depth + f) = make_float4(rc_depth(v.x, hh[0], stage, R), rc_depth(v.y, hh[1], stage, R),
                                                          rc_depth(v.z, hh[2], stage, R), rc_depth(v.w, hh[3], stage, R));
     return;

@@ -184,7 +184,11 @@ class Context:
                              "its frac_bits (DT_STATUS_BAD_WEIGHT): the weighted accumulation is not valid")
         if st & 64:
             raise ValueError("dt_dev_focal met a valid height below its origin or over the bound of its frac_bits and "
-                             "largest radius (DT_STATUS_BAD_HEIGHT): the focal statistics of that call are not valid")
+                             "largest radius, or dt_dev_zonal_tables a value beyond the bound of its frac_bits "
+                             "(DT_STATUS_BAD_HEIGHT): the statistics of that call are not valid")
+        if st & 128:
+            raise ValueError("dt_dev_zonal_tables or dt_dev_zonal_counts met a zone id (or column) >= the number it was "
+                             "given (DT_STATUS_ZONE_RANGE): those cells were left out of the tables")
 
     def fork(self, child):
         """`child`'s stream waits (on the device) for everything enqueued so far on this context's stream."""

@@ -108,8 +108,12 @@ int dt_graph_destroy(dt_graph *graph);
 #define DT_STATUS_BAD_SHARES 32
 /* DT_STATUS_BAD_HEIGHT: dt_dev_focal met a valid height whose quantised value rint((z - origin) * 2^frac_bits) is
  * negative or over the bound of the call's largest radius; that cell counted as 0 and the rasters of that call are not
- * valid. */
+ * valid.  dt_dev_zonal_tables raises it for a participating value whose |rint((v - origin) * 2^frac_bits)| exceeds
+ * 2^31 - 1; that cell was left out of the tables. */
 #define DT_STATUS_BAD_HEIGHT 64
+/* DT_STATUS_ZONE_RANGE: dt_dev_zonal_tables or dt_dev_zonal_counts met a zone id >= the number of zones it was given
+ * (or a cross-tabulation column >= the number of columns); that cell was left out of the tables. */
+#define DT_STATUS_ZONE_RANGE 128
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
 
@@ -417,6 +421,36 @@ int dt_regions_select(const uint8_t *mask, const uint8_t *seeds, int64_t H, int6
  * (under `connectivity`) holds no seed; cells with hand == -100 keep -100. */
 int dt_inundate_connected(const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
                           const int8_t *river, int64_t H, int64_t W, int64_t R, int connectivity, float *depth);
+/* Net-new: zonal statistics -- label compaction, per-zone integer tables, per-zone histograms / cross-tabulation and
+ * painting a table back onto its zones (descriptools_amd/zonal.py holds the definitions in full).  Rasters are H x W,
+ * row-major, H * W < 2^31.
+ * dt_zonal_compact.  labels is int32 (label_bytes 4) or int64 (8); a label is valid when 0 <= l < limit, 1 <= limit <=
+ * 2^31 - 1.  *n_zones = the number of distinct valid labels; labels_of[r] (int64, the first `cap` of them; may be NULL
+ * with cap 0) = the r-th smallest; zones (int32, may be NULL) = the rank of the cell's label, -100 where it is not valid.
+ * dt_zonal_tables.  zones is int32: a cell has a zone when 0 <= z < n_zones, negative values have none, z >= n_zones
+ * fails the call.  values is float32 (value_bytes 4) or float64 (8).  A cell takes part when it has a zone, its value is
+ * finite and (with has_nodata) not equal to nodata as float64; -0.0 counts as +0.0.  q = rint((float64(v) - origin) *
+ * 2^frac_bits), round to even, 0 <= frac_bits <= 24, origin finite; |q| <= 2^31 - 1, a value beyond fails the call.
+ * Per zone, over its participating cells, each table [n_zones] and NULL when not wanted (at least one is): count =
+ * their number; s1 = sum q (int64); s2_lo = sum (q^2 mod 2^32) and s2_hi = sum (q^2 div 2^32) (uint64, wanted
+ * together: sum q^2 = s2_hi 2^32 + s2_lo); vmin / vmax = the smallest / largest value in the dtype of values, NaN on
+ * a zone without a participating cell.
+ * dt_zonal_counts.  counts is int64[n_zones][K], 1 <= K <= 1024, n_zones * K * 8 <= 2^31.  value_bytes 4 / 8: values
+ * is a float32 / float64 raster and edges float64[K + 1], finite and strictly increasing; a participating cell (as
+ * above) counts in bin k when edges[k] <= v < edges[k + 1], the last bin also takes v == edges[K] (compared as
+ * float64).  value_bytes 0: values is a second int32 zone raster and the column is its cell, 0 <= b < K (edges unused;
+ * negative b counts nowhere, b >= K fails the call like z >= n_zones).
+ * dt_zonal_paint.  out[c] = table[zones[c]] where 0 <= zones[c] < n_table, else *fill; table, fill and out are words
+ * of elem_bytes (4 or 8) bytes, moved as they are. */
+int dt_zonal_compact(const void *labels, int label_bytes, int64_t H, int64_t W, int64_t limit, int32_t *zones,
+                     int64_t *labels_of, int64_t cap, int64_t *n_zones);
+int dt_zonal_tables(const int32_t *zones, const void *values, int value_bytes, int64_t H, int64_t W, int64_t n_zones,
+                    double origin, int frac_bits, int has_nodata, double nodata, int64_t *count, int64_t *s1,
+                    uint64_t *s2_lo, uint64_t *s2_hi, void *vmin, void *vmax);
+int dt_zonal_counts(const int32_t *zones, const void *values, int value_bytes, int64_t H, int64_t W, int64_t n_zones,
+                    const double *edges, int K, int has_nodata, double nodata, int64_t *counts);
+int dt_zonal_paint(const void *table, int elem_bytes, int64_t n_table, const int32_t *zones, int64_t H, int64_t W,
+                   const void *fill, void *out);
 
 /* flowhand.flow_distance_index_cpu + flow_distance_index_gpu (flowhand.py:476-846, untiled
  * call: out = 0, row_start = col_start = 0, matrix_columns = W) and flowhand.hand_calculator
@@ -656,6 +690,22 @@ int dt_dev_reach_tables(dt_ctx *ctx, const int32_t *catch_, const void *hand, in
                         int64_t *Hq, int64_t *Bq);
 int dt_dev_inundate(dt_ctx *ctx, const int32_t *catch_, const void *hand, int hand_bytes, const double *stage,
                     int64_t H, int64_t W, int64_t R, float *depth);
+/* The zonal calls on device rasters (rows x cols = H x W), on the context's stream: none synchronises.  n_zones of
+ * dt_dev_zonal_compact (may be NULL) is one int64 on the device; labels_of entries from n_zones on are left as they
+ * were; its workspace (the bitmap, the word ranks and the block counts: limit / 4 bytes) is the context's scratch.
+ * The tables are on the device; the entry zeroes them.  A value outside the bound of frac_bits raises
+ * DT_STATUS_BAD_HEIGHT, a zone id (or column) out of range DT_STATUS_ZONE_RANGE; either cell is left out
+ * (dt_ctx_status).  edges and fill are read on the host (they travel as kernel arguments). */
+int dt_dev_zonal_compact(dt_ctx *ctx, const void *labels, int label_bytes, int64_t rows, int64_t cols, int64_t limit,
+                         int32_t *zones, int64_t *labels_of, int64_t cap, int64_t *n_zones);
+int dt_dev_zonal_tables(dt_ctx *ctx, const int32_t *zones, const void *values, int value_bytes, int64_t rows,
+                        int64_t cols, int64_t n_zones, double origin, int frac_bits, int has_nodata, double nodata,
+                        int64_t *count, int64_t *s1, uint64_t *s2_lo, uint64_t *s2_hi, void *vmin, void *vmax);
+int dt_dev_zonal_counts(dt_ctx *ctx, const int32_t *zones, const void *values, int value_bytes, int64_t rows,
+                        int64_t cols, int64_t n_zones, const double *edges, int K, int has_nodata, double nodata,
+                        int64_t *counts);
+int dt_dev_zonal_paint(dt_ctx *ctx, const void *table, int elem_bytes, int64_t n_table, const int32_t *zones,
+                       int64_t rows, int64_t cols, const void *fill, void *out);
 /* dt_regions_label, dt_regions_select and dt_inundate_connected on device rasters (rows x cols = H x W), on the
  * context's stream: three to five launches whatever the rasters hold, none synchronises.  The workspace (12 bytes per
  * cell, 14 for the inundation) is the context's scratch; nothing is kept between calls.  size and seeds may be NULL. */
