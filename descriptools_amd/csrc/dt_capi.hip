@@ -724,6 +724,22 @@ extern "C" int dt_dev_dinf_accumulate_info(dt_ctx *c, int64_t *info4) {
   return dev_countdown_info(c, DT_OWNER_DINF, "D-infinity", dt_dinf_accumulate_ctl, info4);
 }
 
+extern "C" int dt_dev_cost_distance(dt_ctx *c, const float *friction, const int8_t *sources, int64_t H, int64_t W,
+                                    double px, int connectivity, int visit_limit, int rounds, double *cost,
+                                    int64_t *indices, uint8_t *backlink) {
+  DT_DEV(d, c, H, W, px);
+  DT_REQUIRE(connectivity == 4 || connectivity == 8, "connectivity is 4 or 8");
+  DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
+  DT_REQUIRE(rounds >= 1 && rounds <= DT_COST_ROUNDS_MAX, "rounds must lie in [1, 4096]");
+  DT_REQUIRE((friction && sources && cost) || H * W == 0, "NULL raster");
+  if (H * W == 0) return DT_OK;
+  const size_t need = dt_cost_distance_scratch(H, W, indices != nullptr);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_cost_distance(c->stream, friction, sources, H, W, px, connectivity, visit_limit, 1, rounds, 1,
+                                        scr, need, cost, indices, backlink, c->status));
+}
+
 static int dt_check_mfd_exponent(double exponent) {
   DT_REQUIRE(std::isfinite(exponent) && exponent >= 0.0 && exponent <= 64.0, "exponent must be finite and in [0, 64]");
   return DT_OK;
@@ -2566,6 +2582,57 @@ extern "C" int dt_dinf_distance_down(const float *angle, const int8_t *river, co
   }
   t_dinf_distance_visits = (int64_t)cnt[4] | (int64_t)cnt[5] << 32;
   return hc.finish();
+}
+
+// (the batches of dt_dinf_distance_down: 8, 16, 32, then 64 rounds between two looks at the flags)
+extern "C" int dt_cost_distance(const float *friction, const int8_t *sources, int64_t H, int64_t W, double px,
+                                int connectivity, int visit_limit, double *cost, int64_t *indices, uint8_t *backlink,
+                                int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_REQUIRE(connectivity == 4 || connectivity == 8, "connectivity is 4 or 8");
+  DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(friction && sources && cost, "NULL raster");
+  const float *d_f = hc.in(friction, n);
+  const int8_t *d_s = hc.in(sources, n);
+  double *d_c = hc.out(cost, n);
+  int64_t *d_i = hc.out(indices, n);
+  uint8_t *d_b = hc.out(backlink, n);
+  const int alloc = indices != nullptr;
+  const size_t need = dt_cost_distance_scratch(H, W, alloc);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  const uint32_t *ctl = dt_cost_distance_ctl(scr, H, W, alloc);
+  uint32_t flags[DT_DINF_DIST_BATCH_MAX];
+  int64_t rounds = 0;
+  int batch = DT_DINF_DIST_BATCH0;
+  for (int start = 1;; start = 0) {
+    DT_TRY(dt_launch_cost_distance(hc.c->stream, d_f, d_s, H, W, px, connectivity, visit_limit, start, batch, 0, scr,
+                                   need, d_c, d_i, d_b, nullptr));
+    DT_TRY(hc.download(flags, ctl, (size_t)batch));
+    DT_HIP(hipStreamSynchronize(hc.c->stream));
+    int used = 0;
+    while (used < batch && flags[used]) used++;
+    rounds += used;
+    if (used < batch) break;  // a quiet round: nothing is left to lower
+    if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
+  }
+  DT_TRY(dt_launched(dt_launch_cost_distance(hc.c->stream, d_f, d_s, H, W, px, connectivity, visit_limit, 0, 0, 1, scr,
+                                             need, d_c, d_i, d_b, nullptr)));
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  DT_TRY(hc.download(cnt, ctl + DT_COST_CTL_COUNTS, 4));
+  DT_TRY(hc.finish());  // (synchronises: cnt is here)
+  if (info4) {
+    info4[0] = rounds;
+    info4[1] = cnt[0];
+    info4[2] = cnt[1];
+    info4[3] = (int64_t)cnt[2] | (int64_t)cnt[3] << 32;
+  }
+  return DT_OK;
 }
 
 extern "C" int dt_proximity(const int8_t *river, const float *nod, int64_t H, int64_t W, double px, float *distance,

@@ -386,6 +386,28 @@ size_t dt_proximity_scratch(int64_t H, int64_t W);
 int dt_launch_proximity(hipStream_t s, const int8_t *river, const float *nod, int64_t H, int64_t W, double px,
                         void *scratch, size_t scratch_bytes, float *distance, int64_t *indices);
 
+// Cost distance (dt_cost.hip; cost.py holds the definition): the least accumulated cost over `friction` (passable: 0 <
+// f < +inf) from the sources (sources == 1 and passable) under connectivity 4 or 8, the flat index of the source a cell
+// is reached from (indices, may be NULL) and the ESRI D8 code of its first step towards it (backlink, may be NULL);
+// -100 / -100 / 0 on barriers and unreached cells.  The state lives in `cost` and in `scratch` (laid out with the parent
+// plane when indices is given: alloc != 0): start != 0 sets it up, `rounds` (0..DT_COST_ROUNDS_MAX) rounds of tile
+// visits follow, round r raising control word r when it lowered something (a round that follows a quiet one returns at
+// once), finish != 0 computes the back-links, the fills and the allocation and counts the reached cells, the reached
+// non-source cells without a back-link and the tile visits of the call (64 bits) into control words
+// DT_COST_CTL_COUNTS + 0, + 1 and + 2-3; with rounds in the same call it raises DT_STATUS_NOT_CONVERGED on `status` when
+// the last round still lowered something, and DT_STATUS_NO_BACKLINK for a cell without a back-link (status may be NULL).
+// visit_limit: 0, or the sweeps a workgroup makes over its tile per visit at most (tests); the result does not depend
+// on it.  Nothing synchronises.  H * W < 2^31.
+#define DT_COST_ROUNDS_MAX 4096  // rounds one launcher call takes at most: its flag words
+#define DT_COST_CTL_COUNTS (DT_COST_ROUNDS_MAX + 32)
+size_t dt_cost_distance_scratch(int64_t H, int64_t W, int alloc);
+int dt_launch_cost_distance(hipStream_t s, const float *friction, const int8_t *sources, int64_t H, int64_t W,
+                            double px, int connectivity, int visit_limit, int start, int rounds, int finish,
+                            void *scratch, size_t scratch_bytes, double *cost, int64_t *indices, uint8_t *backlink,
+                            int *status);
+// the control words in `scratch` (DT_COST_CTL_COUNTS + 8 x uint32 on the device)
+const uint32_t *dt_cost_distance_ctl(void *scratch, int64_t H, int64_t W, int alloc);
+
 // Connected regions (dt_regions.hip; regions.py holds the definition): label = the smallest flat index of the cell's
 // region of mask != 0 under connectivity 4 or 8 (-100 on background), size = its cell count (0 on background), keep =
 // foreground, seeded (seeds NULL: every region is) and size >= min_cells.  label, size and keep may each be NULL (seeds

@@ -189,6 +189,10 @@ class Context:
         if st & 128:
             raise ValueError("dt_dev_zonal_tables or dt_dev_zonal_counts met a zone id (or column) >= the number it was "
                              "given (DT_STATUS_ZONE_RANGE): those cells were left out of the tables")
+        if st & 256:
+            raise RuntimeError("dt_dev_cost_distance left a reached cell without a back-link: rounding absorbed a "
+                               "whole edge cost (DT_STATUS_NO_BACKLINK); backlink is 0 and indices -100 there and "
+                               "upstream of it")
 
     def fork(self, child):
         """`child`'s stream waits (on the device) for everything enqueued so far on this context's stream."""

@@ -114,6 +114,9 @@ int dt_graph_destroy(dt_graph *graph);
 /* DT_STATUS_ZONE_RANGE: dt_dev_zonal_tables or dt_dev_zonal_counts met a zone id >= the number of zones it was given
  * (or a cross-tabulation column >= the number of columns); that cell was left out of the tables. */
 #define DT_STATUS_ZONE_RANGE 128
+/* DT_STATUS_NO_BACKLINK: dt_dev_cost_distance left a reached non-source cell without a back-link (rounding absorbed a
+ * whole edge cost): backlink is 0 there, and indices is -100 there and on every cell whose links lead to it. */
+#define DT_STATUS_NO_BACKLINK 256
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
 
@@ -368,6 +371,24 @@ int dt_coarsen(const float *dem, int64_t H, int64_t W, double px, const double *
  * is not finite and > 0 are refused.  HAND above the nearest source: dt_hand_f32 / dt_hand_f64 on indices. */
 int dt_proximity(const int8_t *river, const float *nod, int64_t H, int64_t W, double px, float *distance,
                  int64_t *indices);
+/* Net-new: cost distance, cost allocation and back-links over a friction raster (the GIS cost distance / allocation /
+ * back link, GRASS r.cost; descriptools_amd/cost.py and the test suite's Dijkstra are the definition).  A cell is
+ * passable iff 0 < friction < +inf (zero, negatives, NaN and +inf are barriers; a diagonal move between two barriers
+ * is allowed); a source is a passable cell with sources == 1.  Adjacent passable cells u, v (connectivity 8, or 4:
+ * cardinal moves only) are joined by w(u, v) = step * ((f(u) + f(v)) * 0.5) in float64, one rounding per operation,
+ * step = px (cardinal) or px * 1.4142135623730951 (diagonal).  cost = A, the greatest solution of A(s) = 0 at the
+ * sources and A(v) = min over neighbours u of fl(A(u) + w(u, v)) elsewhere: what Dijkstra returns, to the bit, whatever
+ * the schedule.  backlink(v) = the ESRI D8 code (1 E, 2 SE, 4 S, 8 SW, 16 W, 32 NW, 64 N, 128 NE) of the first
+ * neighbour u in the order NW, N, NE, W, E, SW, S, SE with A(u) < A(v) and fl(A(u) + w(u, v)) == A(v); 0 on sources.
+ * indices(v) = the flat index of the source at the root of v's back-link tree (a source: itself).  Barriers and
+ * unreached cells hold cost -100, indices -100, backlink 0.  A reached non-source cell without such a neighbour (rounding
+ * absorbed a whole edge cost) is counted: backlink 0, indices -100 there and on the cells whose links lead to it.
+ * cost is float64, indices int64, backlink uint8; indices, backlink and info4 may be NULL.  visit_limit: 0, or n >= 1
+ * caps the sweeps a workgroup makes over its tile per visit (tests: the outputs do not depend on it).  info4 = {rounds
+ * that lowered something, reached cells, reached non-source cells without a back-link, tile visits}.  The call ends
+ * when a round lowers nothing.  Rasters of 2^31 cells or more and a px that is not finite and > 0 are refused. */
+int dt_cost_distance(const float *friction, const int8_t *sources, int64_t H, int64_t W, double px, int connectivity,
+                     int visit_limit, double *cost, int64_t *indices, uint8_t *backlink, int64_t *info4);
 /* Net-new: reaches (the HAND synthetic-rating-curve method).  Rasters are H x W with fewer than 2^31 cells, flat index
  * y * W + x; results are exact integers (and depth one float32 rounding), independent of order and run.
  *
@@ -706,6 +727,16 @@ int dt_dev_zonal_counts(dt_ctx *ctx, const int32_t *zones, const void *values, i
                         int64_t *counts);
 int dt_dev_zonal_paint(dt_ctx *ctx, const void *table, int elem_bytes, int64_t n_table, const int32_t *zones,
                        int64_t rows, int64_t cols, const void *fill, void *out);
+/* dt_cost_distance on device rasters (rows x cols = H x W), on the context's stream, without a host synchronisation:
+ * the initialisation, `rounds` (1..4096) rounds of tile visits -- a round that follows a quiet one returns at once --
+ * then the back-links, the fills and the allocation.  When the last round still lowered something the budget was too
+ * small: DT_STATUS_NOT_CONVERGED is raised on the context (dt_ctx_status) and the three rasters are not valid; call
+ * again with a larger budget.  DT_STATUS_NO_BACKLINK says that a reached cell has no back-link.  The
+ * workspace (4 bytes per cell when indices is given, a few bytes per tile of 64 x 64) is the context's scratch; nothing
+ * is kept between calls.  indices and backlink may be NULL. */
+int dt_dev_cost_distance(dt_ctx *ctx, const float *friction, const int8_t *sources, int64_t rows, int64_t cols,
+                         double px, int connectivity, int visit_limit, int rounds, double *cost, int64_t *indices,
+                         uint8_t *backlink);
 /* dt_regions_label, dt_regions_select and dt_inundate_connected on device rasters (rows x cols = H x W), on the
  * context's stream: three to five launches whatever the rasters hold, none synchronises.  The workspace (12 bytes per
  * cell, 14 for the inundation) is the context's scratch; nothing is kept between calls.  size and seeds may be NULL. */
