@@ -51,6 +51,9 @@ _SIGS = {
     "dt_stream_order": (ci, [c_u8p, c_i8p, i64, i64, c_i8p, c_i64p, c_i64p]),
     "dt_drainage": (ci, [c_u8p, c_f32p, c_i64p, i64, i64, f64, c_i64p, c_f64p, c_i64p]),
     "dt_upslope_length": (ci, [c_u8p, c_f32p, i64, i64, f64, c_f64p]),
+    "dt_flowpath_upslope": (ci, [c_u8p, c_f32p, c_f32p, i64, i64, ci, c_f32p, c_i64p]),
+    "dt_flowpath_downstream": (ci, [c_u8p, c_f32p, c_f32p, c_u8p, i64, i64, ci, c_f32p, c_i64p]),
+    "dt_carve": (ci, [c_f32p, i64, i64, f64, f64, c_u8p, c_f32p, c_f32p, c_i32p]),
     "dt_dinf_direction": (ci, [c_f32p, c_u8p, i64, i64, f64, c_f32p, c_f32p]),
     "dt_dinf_accumulate": (ci, [c_f32p, c_f64p, i64, i64, ci, c_f64p, c_i64p]),
     "dt_dinf_distance_down": (ci, [c_f32p, c_i8p, c_f32p, i64, i64, f64, ci, ci, ci, c_f64p, c_f64p, c_f64p, c_i64p]),
@@ -114,6 +117,9 @@ _SIGS = {
     "dt_dev_stream_order": (ci, [vp, vp, vp, i64, i64, vp, vp, vp]),
     "dt_dev_drainage": (ci, [vp, vp, vp, vp, i64, i64, f64, vp, vp, vp]),
     "dt_dev_upslope_length": (ci, [vp, vp, vp, i64, i64, f64, vp]),
+    "dt_dev_flowpath_upslope": (ci, [vp, vp, vp, vp, i64, i64, ci, vp, vp]),
+    "dt_dev_flowpath_downstream": (ci, [vp, vp, vp, vp, vp, i64, i64, ci, vp, vp]),
+    "dt_dev_carve_blend": (ci, [vp, vp, vp, vp, i64, i64, f64, vp]),
     "dt_dev_dinf_direction": (ci, [vp, vp, vp, i64, i64, f64, vp, vp]),
     "dt_dev_dinf_accumulate": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
     "dt_dev_dinf_accumulate_info": (ci, [vp, c_i64p]),

@@ -630,6 +630,45 @@ extern "C" int dt_dev_upslope_length(dt_ctx *c, const uint8_t *fdr, const float 
   return d.done(dt_launch_upslope_length(c->stream, fdr, dem, H, W, px, scr, need, length));
 }
 
+// flow-path extremes and the carving blend: dt_check_ws's shape rule (they take no pixel size)
+static int dt_check_fp(int64_t rows, int64_t cols) { return dt_check_ws(rows, cols, 1.0); }
+#define DT_FP_KIND(kind) DT_REQUIRE((kind) == 0 || (kind) == 1, "kind must be 0 (max) or 1 (min)")
+
+extern "C" int dt_dev_flowpath_upslope(dt_ctx *c, const uint8_t *fdr, const float *dem, const float *values,
+                                       int64_t rows, int64_t cols, int kind, float *value, int64_t *where) {
+  DT_DEV(d, c, rows, cols, dt_check_fp);
+  DT_FP_KIND(kind);
+  DT_REQUIRE((fdr && values) || rows * cols == 0, "NULL raster");
+  if (rows * cols == 0 || (!value && !where)) return DT_OK;
+  const size_t need = dt_flowpath_scratch(rows, cols, 1);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_flowpath_upslope(c->stream, fdr, dem, values, rows, cols, kind, scr, need, value, where));
+}
+
+extern "C" int dt_dev_flowpath_downstream(dt_ctx *c, const uint8_t *fdr, const float *dem, const float *values,
+                                          const uint8_t *stop, int64_t rows, int64_t cols, int kind, float *value,
+                                          int64_t *where) {
+  DT_DEV(d, c, rows, cols, dt_check_fp);
+  DT_FP_KIND(kind);
+  DT_REQUIRE((fdr && values) || rows * cols == 0, "NULL raster");
+  if (rows * cols == 0 || (!value && !where)) return DT_OK;
+  const size_t need = dt_flowpath_scratch(rows, cols, 0);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_flowpath_downstream(c->stream, fdr, dem, values, stop, rows, cols, kind, scr, need, value,
+                                              where));
+}
+
+extern "C" int dt_dev_carve_blend(dt_ctx *c, const float *dem, const float *filled, const float *lowest, int64_t rows,
+                                  int64_t cols, double max_cut, float *carved) {
+  DT_DEV(d, c, rows, cols, dt_check_fp);
+  DT_REQUIRE(std::isfinite(max_cut) && max_cut >= 0.0, "max_cut must be finite and >= 0");
+  DT_REQUIRE((dem && filled && lowest) || rows * cols == 0, "NULL raster");
+  if (rows * cols == 0 || !carved) return DT_OK;
+  return d.done(dt_launch_carve_blend(c->stream, dem, filled, lowest, rows * cols, (float)max_cut, carved));
+}
+
 extern "C" int dt_dev_dinf_direction(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                                      float *angle, float *slope) {
   DT_DEV(d, c, H, W, px);
@@ -3222,4 +3261,67 @@ extern "C" int dt_d8_conditioned_f32(const float *dem, int64_t H, int64_t W, dou
 extern "C" int dt_d8_conditioned_f64(const double *dem, int64_t H, int64_t W, double px, uint8_t *fdr, double *filled,
                                      int32_t *info3) {
   return host_d8_conditioned(dem, H, W, px, fdr, filled, info3, dt_dev_condition_d8_f64);
+}
+
+// flow-path extremes, host tier
+extern "C" int dt_flowpath_upslope(const uint8_t *fdr, const float *dem, const float *values, int64_t H, int64_t W,
+                                   int kind, float *value, int64_t *where) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_FP_KIND(kind);
+  const size_t n = (size_t)H * W;
+  if (n == 0 || (!value && !where)) return DT_OK;
+  DT_REQUIRE(fdr && values, "NULL raster");
+  const uint8_t *d_f = hc.in(fdr, n);
+  const float *d_dem = hc.in(dem, n);
+  const float *d_v = hc.in(values, n);
+  float *d_o = hc.out(value, n);
+  int64_t *d_w = hc.out(where, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_flowpath_upslope(hc.c, d_f, d_dem, d_v, H, W, kind, d_o, d_w));
+  return hc.finish();
+}
+
+extern "C" int dt_flowpath_downstream(const uint8_t *fdr, const float *dem, const float *values, const uint8_t *stop,
+                                      int64_t H, int64_t W, int kind, float *value, int64_t *where) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_FP_KIND(kind);
+  const size_t n = (size_t)H * W;
+  if (n == 0 || (!value && !where)) return DT_OK;
+  DT_REQUIRE(fdr && values, "NULL raster");
+  const uint8_t *d_f = hc.in(fdr, n);
+  const float *d_dem = hc.in(dem, n);
+  const float *d_v = hc.in(values, n);
+  const uint8_t *d_s = hc.in(stop, n);
+  float *d_o = hc.out(value, n);
+  int64_t *d_w = hc.out(where, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_flowpath_downstream(hc.c, d_f, d_dem, d_v, d_s, H, W, kind, d_o, d_w));
+  return hc.finish();
+}
+
+// depression carving, host tier: conditioned D8, the upslope minimum of the DEM over its tree, and the blend with the
+// filled surface when the cut is limited (max_cut +inf: no limit)
+extern "C" int dt_carve(const float *dem, int64_t H, int64_t W, double px, double max_cut, uint8_t *fdr, float *carved,
+                        float *filled, int32_t *info3) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_REQUIRE(max_cut >= 0.0, "max_cut must be >= 0 (+inf: no limit)");
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(dem && fdr && carved, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  uint8_t *d_f = hc.out(fdr, n);
+  float *d_c = hc.out(carved, n);
+  float *d_w = filled ? hc.out(filled, n) : hc.scratch<float>(n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_condition_d8(hc.c, d_dem, H, W, px, d_w, d_f, info3));
+  DT_TRY(dt_dev_flowpath_upslope(hc.c, d_f, d_dem, d_dem, H, W, 1, d_c, nullptr));
+  DT_TRY(dt_launched(dt_launch_carve_blend(hc.c->stream, d_dem, std::isinf(max_cut) ? nullptr : d_w, d_c, (int64_t)n,
+                                           (float)max_cut, d_c)));
+  return hc.finish();
 }

@@ -1,0 +1,569 @@
+// dt_flowpath.hip -- flow-path extremes: the max / min of a value raster over everything upslope of a cell, or along
+// its path downstream, and the pointwise blend of depression carving (net-new; descriptools_amd/flowpath.py and
+// flowdir.d8_carved hold the definitions).
+//
+// Graph: dt_watershed.hip's drainage graph.  c -> d when c's code is one of the eight D8 codes, d lies in the raster
+// and (with a DEM) neither c nor d is nodata (dem <= -100).  A valid cell with no edge is a terminal.
+//
+// Key.  A cell's value travels as one 64-bit word: the order-preserving uint32 key of the float (dt_zonal.hip's,
+// complemented for a minimum) in the high half, 0xFFFFFFFF - flat index in the low half.  The larger word is the
+// better value and, between equal values, the smaller flat index, for both kinds; NaN has no word (0: "no value";
+// a real word is never 0 because the flat index stays below 2^31).  -0.0 is keyed as +0.0.  Every fold is therefore
+// an unsigned 64-bit max: one native LDS / global atomic per send upslope, a plain compare downstream.
+//
+// Tiles.  64 x 64 cells, one workgroup of 256 lanes per tile, 16 cells per lane (cell l = k * 256 + lane).  A tile's
+// paths are resolved in LDS by pointer doubling on one 32-bit word per cell: bits 0-11 a local pointer, bits 12-14 the
+// kind.  PTR: the pointer is a cell further down the path inside the tile.  STOP / EXIT / FAIL / NOSTOP: the path's
+// end inside the tile (a terminal or stop cell; a cell whose successor lies in another tile; nodata; a terminal of a
+// call that has a stop raster).  As long as a word is PTR its pointer after round r is exactly the 2^r-th successor;
+// an acyclic in-tile path makes < 4096 moves, so 12 rounds resolve it, and a word still PTR after 12 rounds is on or
+// drains into an in-tile D8 cycle.  Only the 252 perimeter cells of a tile enter a global graph (node = tile * 256 +
+// slot).
+//
+// Upslope fold (k_fp_up_tile1, k_fp_up_node x R, k_fp_up_tile3): U(c) = the max word over every cell whose path
+// contains c.  Pointer doubling with scatter: in round r every PTR cell sends its word to its pointer with an atomic
+// max, then doubles the pointer.  By induction the word of d holds, after round r, every cell at most 2^(r+1) - 1
+// moves above d (the cell 2^r moves above d is PTR with pointer d, and held everything < 2^r moves above itself); a
+// max is idempotent and monotone, so the words are updated in place and a word read early or late only carries more
+// of what belongs there.  A resolved cell stops sending and delivers its word to its path's end once, after the
+// rounds.  A cycle is no special case: its cells stay PTR and send in all 12 rounds, which cover the < 4096 moves
+// between any two cells of one tile.  The perimeter nodes form a graph of exact pointers (the node 2^r node-moves
+// down, or none): an exit cell points at its successor's node, any other perimeter cell at the exit its in-tile path
+// reaches.  Every round sends S(n) to its pointer by atomic max on one global word (one word, so no fence) and
+// doubles the pointer into the other buffer.  R = max(2, ceil(log2 N) + 1) rounds: a node-path that repeats no node
+// is shorter than the number of real nodes <= N <= 2^(R-1), so after R rounds every node holds every node above it,
+// round a cycle included -- on a cycle the pointers never run out, all R rounds run, and that is enough for the same
+// reason.  Entries and exits of a path are all on its node path, so S at an exit cell is complete; a perimeter cell
+// that a path merely passes is not, which is why k_fp_up_tile3 takes each perimeter cell's inflow from its feeders in
+// other tiles (exits of theirs), folds the tile once more and writes the decoded value and its cell.
+//
+// Downstream fold (k_fp_dn_tile1, k_fp_dn_node x R, k_fp_dn_tile3): D(c) = the max word over c's path up to where it
+// stops.  A gather without atomics: v(c) = max(v(c), v(ptr(c))), ptr(c) = ptr(ptr(c)), both read before a barrier and
+// written after it, so every round reads the state of the round before.  After round r, v(c) covers the 2^(r+1) cells
+// from c on (or the path to its end, end included); a cell on or draining into an in-tile cycle has its whole tail and
+// the cycle after 12 rounds.  The perimeter records are {pointer, tag, word} (16 bytes): pointer < 2^31 another node,
+// FP_RES the path has stopped and the word is final, FP_FAILP it ended without a stop cell.  The rounds ping-pong
+// between two record buffers as k_dr_node does (a record resolved in round r is written again in round r + 1, then
+// skipped), so a cycle never reads a half-updated record.  Without a stop raster a record still open after R rounds
+// lies on or drains into a cycle and its word is complete (R rounds cover N node-moves); with one, such a path met
+// no stop cell and gets no value.
+#include "dt_kernels.h"
+
+#define FP_T 64
+#define FP_CPT 16
+#define FP_SLOTS 256
+#define FP_ROUNDS 12
+#define FP_K_PTR 0u
+#define FP_K_STOP 1u
+#define FP_K_EXIT 2u
+#define FP_K_FAIL 3u
+#define FP_K_NOSTOP 4u
+#define FP_NONE 0xFFFFFFFFu
+#define FP_RES 0x80000000u
+#define FP_FAILP 0xFFFFFFFFu
+#define FP_OPEN 0xFFFFFFFEu  // tag of a record that is still a pointer
+
+typedef unsigned long long fp_u64;
+
+__device__ __forceinline__ uint32_t fp_ptr(uint32_t w) { return w & 0xFFFu; }
+__device__ __forceinline__ uint32_t fp_kind(uint32_t w) { return w >> 12; }
+__device__ __forceinline__ uint32_t fp_word(uint32_t ptr, uint32_t kind) { return ptr | (kind << 12); }
+
+// the word of value v at flat index c (0: NaN), and back.  MIN: the order of the float key is reversed
+template <bool MIN>
+__device__ __forceinline__ fp_u64 fp_key(float v, int64_t c) {
+  if (v != v) return 0ull;
+  const uint32_t b = v == 0.0f ? 0u : __float_as_uint(v);
+  uint32_t k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  if (MIN) k = ~k;
+  return ((fp_u64)k << 32) | (fp_u64)(0xFFFFFFFFu - (uint32_t)c);
+}
+template <bool MIN>
+__device__ __forceinline__ float fp_value(fp_u64 key) {
+  uint32_t k = (uint32_t)(key >> 32);
+  if (MIN) k = ~k;
+  return key == 0ull ? __uint_as_float(0x7FC00000u)
+                     : __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+__device__ __forceinline__ int64_t fp_where(fp_u64 key) {
+  return key == 0ull ? -100 : (int64_t)(0xFFFFFFFFu - (uint32_t)key);
+}
+
+// perimeter slot of a local cell (-1 inside): row 0, row 63, column 0, column 63; and the local cell of slot j < 252
+__device__ __forceinline__ int fp_slot(int ly, int lx) {
+  if (ly == 0) return lx;
+  if (ly == FP_T - 1) return 64 + lx;
+  if (lx == 0) return 127 + ly;
+  if (lx == FP_T - 1) return 189 + ly;
+  return -1;
+}
+__device__ __forceinline__ int fp_slot_cell(int j) {
+  if (j < 64) return j;
+  if (j < 128) return (FP_T - 1) * FP_T + (j - 64);
+  if (j < 190) return (j - 127) * FP_T;
+  return (j - 189) * FP_T + FP_T - 1;
+}
+__device__ __forceinline__ uint32_t fp_node(int64_t y, int64_t x, int64_t TX) {
+  return (uint32_t)(((y >> 6) * TX + (x >> 6)) * FP_SLOTS + fp_slot((int)(y & 63), (int)(x & 63)));
+}
+
+// the starting word of local cell l of the tile at (y0, x0); stop may be NULL (terminals are then the stop cells)
+__device__ __forceinline__ uint32_t fp_init(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                            const uint8_t *__restrict__ stop, int64_t H, int64_t W, int64_t y0,
+                                            int64_t x0, int l) {
+  const int64_t y = y0 + (l >> 6), x = x0 + (l & 63);
+  if (y >= H || x >= W) return fp_word((uint32_t)l, FP_K_FAIL);
+  const int64_t c = y * W + x;
+  if (dem && dem[c] <= -100.0f) return fp_word((uint32_t)l, FP_K_FAIL);
+  if (stop && stop[c] != 0) return fp_word((uint32_t)l, FP_K_STOP);
+  const uint32_t term = stop ? FP_K_NOSTOP : FP_K_STOP;
+  const uint32_t code = fdr[c];
+  if (!dt_d8_valid(code)) return fp_word((uint32_t)l, term);
+  int dy, dx;
+  dt_d8_delta(code, dy, dx);
+  const int64_t ny = y + dy, nx = x + dx;
+  if (ny < 0 || ny >= H || nx < 0 || nx >= W) return fp_word((uint32_t)l, term);
+  if (dem && dem[ny * W + nx] <= -100.0f) return fp_word((uint32_t)l, term);
+  const int64_t ly = ny - y0, lx = nx - x0;
+  if (ly < 0 || ly >= FP_T || lx < 0 || lx >= FP_T) return fp_word((uint32_t)l, FP_K_EXIT);
+  return fp_word((uint32_t)(ly * FP_T + lx), FP_K_PTR);
+}
+
+// the words w[] (= s_w) and the value words s_v of the tile at T, for a fold of `values`; after a barrier both are set
+struct FpTile {
+  int64_t ty, tx, y0, x0;
+};
+__device__ __forceinline__ FpTile fp_tile(int64_t TX) {
+  FpTile T;
+  T.ty = (int64_t)blockIdx.x / TX;
+  T.tx = (int64_t)blockIdx.x - T.ty * TX;
+  T.y0 = T.ty * FP_T;
+  T.x0 = T.tx * FP_T;
+  return T;
+}
+template <bool MIN>
+__device__ __forceinline__ fp_u64 fp_cell_key(const float *__restrict__ values, uint32_t w, int64_t H, int64_t W,
+                                              int64_t y0, int64_t x0, int l) {
+  if (fp_kind(w) == FP_K_FAIL) return 0ull;  // outside the raster, or nodata
+  const int64_t c = (y0 + (l >> 6)) * W + x0 + (l & 63);
+  return fp_key<MIN>(values[c], c);
+}
+
+// Upslope: pointer doubling with scatter.  s_w holds w[], s_v the cells' own words (and, in pass 3, the inflow of the
+// entries), after a barrier.  On return (after a barrier) s_v[l] is the max over everything above l inside the tile.
+__device__ __forceinline__ void fp_fold_up(uint32_t *s_w, fp_u64 *s_v, uint32_t (&w)[FP_CPT]) {
+  const int t = (int)threadIdx.x;
+  for (int r = 0; r < FP_ROUNDS; r++) {
+    uint32_t tg[FP_CPT];
+#pragma unroll
+    for (int k = 0; k < FP_CPT; k++) {
+      const int l = k * 256 + t;
+      tg[k] = 0u;
+      if (fp_kind(w[k]) == FP_K_PTR) {
+        const uint32_t p = fp_ptr(w[k]);
+        if (p != (uint32_t)l) {
+          const fp_u64 v = __hip_atomic_load(&s_v[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (v) atomicMax(&s_v[p], v);
+        }
+        tg[k] = s_w[p];
+      }
+    }
+    __syncthreads();
+    int pend = 0;
+#pragma unroll
+    for (int k = 0; k < FP_CPT; k++) {
+      if (fp_kind(w[k]) == FP_K_PTR) {
+        w[k] = tg[k];
+        s_w[k * 256 + t] = w[k];
+        pend |= fp_kind(w[k]) == FP_K_PTR;
+      }
+    }
+    if (!__syncthreads_or(pend)) break;
+  }
+  // every resolved cell delivers to its path's end, once
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    const uint32_t kd = fp_kind(w[k]), p = fp_ptr(w[k]);
+    if (kd != FP_K_FAIL && kd != FP_K_PTR && p != (uint32_t)l) {
+      const fp_u64 v = __hip_atomic_load(&s_v[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (v) atomicMax(&s_v[p], v);
+    }
+  }
+  __syncthreads();
+}
+
+// Downstream: pointer doubling with gather.  s_w holds w[], s_v holds v[], after a barrier.  On return (after a
+// barrier) v[] / s_v hold the max over each cell's in-tile path, its end included.
+__device__ __forceinline__ void fp_fold_down(uint32_t *s_w, fp_u64 *s_v, uint32_t (&w)[FP_CPT], fp_u64 (&v)[FP_CPT]) {
+  const int t = (int)threadIdx.x;
+  for (int r = 0; r < FP_ROUNDS; r++) {
+    uint32_t tg[FP_CPT];
+    fp_u64 tv[FP_CPT];
+#pragma unroll
+    for (int k = 0; k < FP_CPT; k++) {
+      const bool open = fp_kind(w[k]) == FP_K_PTR;
+      tg[k] = open ? s_w[fp_ptr(w[k])] : 0u;
+      tv[k] = open ? s_v[fp_ptr(w[k])] : 0ull;
+    }
+    __syncthreads();
+    int pend = 0;
+#pragma unroll
+    for (int k = 0; k < FP_CPT; k++) {
+      if (fp_kind(w[k]) == FP_K_PTR) {
+        w[k] = tg[k];
+        v[k] = tv[k] > v[k] ? tv[k] : v[k];
+        s_w[k * 256 + t] = w[k];
+        s_v[k * 256 + t] = v[k];
+        pend |= fp_kind(w[k]) == FP_K_PTR;
+      }
+    }
+    if (!__syncthreads_or(pend)) break;
+  }
+}
+
+// ---- upslope -----------------------------------------------------------------------------------------------------
+template <bool MIN>
+__global__ __launch_bounds__(256) void k_fp_up_tile1(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                                     const float *__restrict__ values, int64_t H, int64_t W,
+                                                     int64_t TX, uint32_t *__restrict__ uptr,
+                                                     fp_u64 *__restrict__ S) {
+  __shared__ uint32_t s_w[FP_T * FP_T];
+  __shared__ fp_u64 s_v[FP_T * FP_T];
+  const FpTile T = fp_tile(TX);
+  const int t = (int)threadIdx.x;
+  uint32_t w[FP_CPT];
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    w[k] = fp_init(fdr, dem, nullptr, H, W, T.y0, T.x0, l);
+    s_w[l] = w[k];
+    s_v[l] = fp_cell_key<MIN>(values, w[k], H, W, T.y0, T.x0, l);
+  }
+  __syncthreads();
+  fp_fold_up(s_w, s_v, w);
+  // one perimeter slot per lane
+  uint32_t p_out = FP_NONE;
+  fp_u64 s_out = 0ull;
+  if (t < 252) {
+    const int l = fp_slot_cell(t);
+    const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
+    if (y < H && x < W) {
+      const uint32_t v = s_w[l];
+      const uint32_t p = fp_ptr(v);
+      s_out = s_v[l];
+      if (fp_kind(v) == FP_K_EXIT && p == (uint32_t)l) {
+        int dy, dx;
+        dt_d8_delta(fdr[y * W + x], dy, dx);
+        p_out = fp_node(y + dy, x + dx, TX);
+      } else if (fp_kind(v) == FP_K_EXIT) {
+        p_out = (uint32_t)(blockIdx.x * FP_SLOTS + fp_slot((int)(p >> 6), (int)(p & 63)));
+      }
+    }
+  }
+  const int64_t n = (int64_t)blockIdx.x * FP_SLOTS + t;
+  uptr[n] = p_out;
+  S[n] = s_out;
+}
+
+// one round of pointer doubling with scatter over the perimeter nodes (exact pointers: NONE past a root).
+// flags[r + 1] = 1 when a pointer is left after this round.
+__global__ __launch_bounds__(256) void k_fp_up_node(const uint32_t *__restrict__ psrc, uint32_t *__restrict__ pdst,
+                                                    fp_u64 *S, int64_t NN, uint32_t *flags, int r) {
+  if (r > 0 && flags[r] == 0u) return;
+  bool pend = false;
+  for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < NN; n += (int64_t)gridDim.x * 256) {
+    const uint32_t p = psrc[n];
+    if (p == FP_NONE) {
+      pdst[n] = FP_NONE;
+      continue;
+    }
+    // most sends of the later rounds bring nothing new: a load tells, and only a word that raises S(p) is sent
+    const fp_u64 sv = __hip_atomic_load(&S[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sv > __hip_atomic_load(&S[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&S[p], sv);
+    const uint32_t p2 = psrc[p];
+    pdst[n] = p2;
+    pend |= p2 != FP_NONE;
+  }
+  if (__ballot(pend) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(&flags[r + 1], 1u);
+}
+
+template <bool MIN>
+__global__ __launch_bounds__(256) void k_fp_up_tile3(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                                     const float *__restrict__ values, int64_t H, int64_t W,
+                                                     int64_t TX, const fp_u64 *__restrict__ S,
+                                                     float *__restrict__ value, int64_t *__restrict__ where) {
+  __shared__ uint32_t s_w[FP_T * FP_T];
+  __shared__ fp_u64 s_v[FP_T * FP_T];
+  const FpTile T = fp_tile(TX);
+  const int t = (int)threadIdx.x;
+  uint32_t w[FP_CPT];
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    w[k] = fp_init(fdr, dem, nullptr, H, W, T.y0, T.x0, l);
+    s_w[l] = w[k];
+    s_v[l] = fp_cell_key<MIN>(values, w[k], H, W, T.y0, T.x0, l);
+  }
+  __syncthreads();
+  // entry inflow: S(f) of each feeder f in another tile (an exit of its tile, so a perimeter node whose S is complete)
+  if (t < 252) {
+    const int l = fp_slot_cell(t);
+    const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
+    if (y < H && x < W && !(dem && dem[y * W + x] <= -100.0f)) {
+      fp_u64 ext = s_v[l];
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        int dy, dx;
+        dt_nb_delta(i, dy, dx);
+        const int64_t fy = y + dy, fx = x + dx;
+        if (fy < 0 || fy >= H || fx < 0 || fx >= W) continue;
+        if ((fy >> 6) == T.ty && (fx >> 6) == T.tx) continue;
+        const int64_t f = fy * W + fx;
+        if (fdr[f] != (uint8_t)dt_nb_back_code(i)) continue;  // f's code points back at this cell
+        if (dem && dem[f] <= -100.0f) continue;
+        const fp_u64 v = S[fp_node(fy, fx, TX)];
+        ext = v > ext ? v : ext;
+      }
+      s_v[l] = ext;
+    }
+  }
+  __syncthreads();
+  fp_fold_up(s_w, s_v, w);
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
+    if (y >= H || x >= W) continue;
+    const fp_u64 v = s_v[l];
+    if (value) value[y * W + x] = fp_value<MIN>(v);
+    if (where) where[y * W + x] = fp_where(v);
+  }
+}
+
+// ---- downstream --------------------------------------------------------------------------------------------------
+template <bool MIN>
+__global__ __launch_bounds__(256) void k_fp_dn_tile1(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                                     const float *__restrict__ values,
+                                                     const uint8_t *__restrict__ stop, int64_t H, int64_t W, int64_t TX,
+                                                     uint4 *__restrict__ rec) {
+  __shared__ uint32_t s_w[FP_T * FP_T];
+  __shared__ fp_u64 s_v[FP_T * FP_T];
+  const FpTile T = fp_tile(TX);
+  const int t = (int)threadIdx.x;
+  uint32_t w[FP_CPT];
+  fp_u64 v[FP_CPT];
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    w[k] = fp_init(fdr, dem, stop, H, W, T.y0, T.x0, l);
+    v[k] = fp_cell_key<MIN>(values, w[k], H, W, T.y0, T.x0, l);
+    s_w[l] = w[k];
+    s_v[l] = v[k];
+  }
+  __syncthreads();
+  fp_fold_down(s_w, s_v, w, v);
+  // one perimeter slot per lane
+  uint4 o = make_uint4(FP_FAILP, 0xFFFFFFFFu, 0u, 0u);
+  if (t < 252) {
+    const int l = fp_slot_cell(t);
+    const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
+    if (y < H && x < W) {
+      const uint32_t q = s_w[l];
+      const uint32_t kd = fp_kind(q), p = fp_ptr(q);
+      const fp_u64 key = s_v[l];
+      const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
+      if (kd == FP_K_EXIT && p == (uint32_t)l) {
+        int dy, dx;
+        dt_d8_delta(fdr[y * W + x], dy, dx);
+        o = make_uint4(fp_node(y + dy, x + dx, TX), FP_OPEN, lo, hi);
+      } else if (kd == FP_K_EXIT) {
+        o = make_uint4((uint32_t)(blockIdx.x * FP_SLOTS + fp_slot((int)(p >> 6), (int)(p & 63))), FP_OPEN, lo, hi);
+      } else if (kd == FP_K_STOP || (kd == FP_K_PTR && !stop)) {
+        o = make_uint4(FP_RES, 0xFFFFFFFFu, lo, hi);  // stopped; or an in-tile cycle of a call without stop cells
+      }
+    }
+  }
+  rec[(int64_t)blockIdx.x * FP_SLOTS + t] = o;
+}
+
+// one doubling round src -> dst over the perimeter records; tag = the round a record was resolved in (-1: pass 1).
+// flags[r + 1] = 1 when this round left a record open.
+__global__ __launch_bounds__(256) void k_fp_dn_node(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t NN,
+                                                    uint32_t *flags, int r) {
+  if (r >= 2 && flags[r - 1] == 0u) return;
+  bool pend = false;
+  for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < NN; n += (int64_t)gridDim.x * 256) {
+    const uint4 s = src[n];
+    if (s.x & FP_RES) {
+      if ((int32_t)s.y > r - 2) dst[n] = s;
+      continue;
+    }
+    const uint4 q = src[s.x];
+    const fp_u64 a = (fp_u64)s.z | ((fp_u64)s.w << 32), b = (fp_u64)q.z | ((fp_u64)q.w << 32);
+    const fp_u64 m = a > b ? a : b;
+    uint4 o;
+    if (q.x == FP_FAILP) {
+      o = make_uint4(FP_FAILP, (uint32_t)r, 0u, 0u);
+    } else if (q.x & FP_RES) {
+      o = make_uint4(FP_RES, (uint32_t)r, (uint32_t)m, (uint32_t)(m >> 32));
+    } else {
+      o = make_uint4(q.x, FP_OPEN, (uint32_t)m, (uint32_t)(m >> 32));
+      pend = true;
+    }
+    dst[n] = o;
+  }
+  if (__ballot(pend) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(&flags[r + 1], 1u);
+}
+
+template <bool MIN>
+__global__ __launch_bounds__(256) void k_fp_dn_tile3(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                                     const float *__restrict__ values,
+                                                     const uint8_t *__restrict__ stop, int64_t H, int64_t W, int64_t TX,
+                                                     const uint4 *__restrict__ rec, float *__restrict__ value,
+                                                     int64_t *__restrict__ where) {
+  __shared__ uint32_t s_w[FP_T * FP_T];
+  __shared__ fp_u64 s_v[FP_T * FP_T];
+  __shared__ uint4 s_x[FP_SLOTS];
+  const FpTile T = fp_tile(TX);
+  const int t = (int)threadIdx.x;
+  uint32_t w[FP_CPT];
+  fp_u64 v[FP_CPT];
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    w[k] = fp_init(fdr, dem, stop, H, W, T.y0, T.x0, l);
+    v[k] = fp_cell_key<MIN>(values, w[k], H, W, T.y0, T.x0, l);
+    s_w[l] = w[k];
+    s_v[l] = v[k];
+  }
+  s_x[t] = rec[(int64_t)blockIdx.x * FP_SLOTS + t];
+  __syncthreads();
+  fp_fold_down(s_w, s_v, w, v);
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
+    if (y >= H || x >= W) continue;
+    const uint32_t kd = fp_kind(w[k]), p = fp_ptr(w[k]);
+    fp_u64 out = 0ull;
+    if (kd == FP_K_STOP || (kd == FP_K_PTR && !stop)) {
+      out = v[k];
+    } else if (kd == FP_K_EXIT) {
+      // the exit's record: everything from the exit cell on, and whether that path stopped
+      const uint4 q = s_x[fp_slot((int)(p >> 6), (int)(p & 63))];
+      const fp_u64 b = (fp_u64)q.z | ((fp_u64)q.w << 32);
+      if (stop ? q.x == FP_RES : q.x != FP_FAILP) out = b > v[k] ? b : v[k];
+    }
+    if (value) value[y * W + x] = fp_value<MIN>(out);
+    if (where) where[y * W + x] = fp_where(out);
+  }
+}
+
+// ---- carving: carved = max(lowest, filled - cut) in float32, the DEM's own value on nodata -------------------------
+// filled NULL: no limit on the cut (carved = lowest).  carved may alias lowest.
+__global__ __launch_bounds__(256) void k_carve_blend(const float *__restrict__ dem, const float *__restrict__ filled,
+                                                     const float *lowest, int64_t N, float cut, float *carved) {
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < N; c += (int64_t)gridDim.x * 256) {
+    const float d = dem[c];
+    float o = d;
+    if (!(d <= -100.0f)) {
+      o = lowest[c];
+      if (filled) {
+        const float floor_ = filled[c] - cut;
+        o = floor_ > o ? floor_ : o;
+      }
+    }
+    carved[c] = o;
+  }
+}
+
+// ---- launchers ---------------------------------------------------------------------------------------------------
+struct FpLayout {
+  int64_t TY, TX, NN;
+  uint32_t *flags;
+  uint32_t *uptr[2];  // upslope
+  fp_u64 *S;
+  uint4 *rec[2];  // downstream
+  size_t bytes;
+};
+
+static FpLayout fp_layout(int64_t H, int64_t W, bool upslope, void *scratch) {
+  FpLayout L = {};
+  L.TY = (H + FP_T - 1) / FP_T;
+  L.TX = (W + FP_T - 1) / FP_T;
+  L.NN = L.TY * L.TX * FP_SLOTS;
+  DtCarver c(scratch);
+  L.flags = c.take<uint32_t>(64);
+  if (upslope) {
+    for (int i = 0; i < 2; i++) L.uptr[i] = c.take<uint32_t>((size_t)L.NN);
+    L.S = c.take<fp_u64>((size_t)L.NN);
+  } else {
+    for (int i = 0; i < 2; i++) L.rec[i] = c.take<uint4>((size_t)L.NN);
+  }
+  L.bytes = c.bytes();
+  return L;
+}
+
+size_t dt_flowpath_scratch(int64_t H, int64_t W, int upslope) { return fp_layout(H, W, upslope != 0, nullptr).bytes; }
+
+template <bool MIN>
+static void fp_launch_up(hipStream_t s, const FpLayout &L, const uint8_t *fdr, const float *dem, const float *values,
+                         int64_t H, int64_t W, int R, float *value, int64_t *where) {
+  dim3 b(256), gt((unsigned)(L.TY * L.TX));
+  hipLaunchKernelGGL(k_fp_up_tile1<MIN>, gt, b, 0, s, fdr, dem, values, H, W, L.TX, L.uptr[0], L.S);
+  const dim3 gn(dt_capped_grid(L.NN, 8192));
+  for (int r = 0; r < R; r++)
+    hipLaunchKernelGGL(k_fp_up_node, gn, b, 0, s, L.uptr[r & 1], L.uptr[(r & 1) ^ 1], L.S, L.NN, L.flags, r);
+  hipLaunchKernelGGL(k_fp_up_tile3<MIN>, gt, b, 0, s, fdr, dem, values, H, W, L.TX, L.S, value, where);
+}
+
+template <bool MIN>
+static void fp_launch_down(hipStream_t s, const FpLayout &L, const uint8_t *fdr, const float *dem, const float *values,
+                           const uint8_t *stop, int64_t H, int64_t W, int R, float *value, int64_t *where) {
+  dim3 b(256), gt((unsigned)(L.TY * L.TX));
+  hipLaunchKernelGGL(k_fp_dn_tile1<MIN>, gt, b, 0, s, fdr, dem, values, stop, H, W, L.TX, L.rec[0]);
+  const dim3 gn(dt_capped_grid(L.NN, 8192));
+  for (int r = 0; r < R; r++)
+    hipLaunchKernelGGL(k_fp_dn_node, gn, b, 0, s, L.rec[r & 1], L.rec[(r & 1) ^ 1], L.NN, L.flags, r);
+  // round R - 1 wrote rec[R & 1]; when the rounds ended early both buffers are complete
+  hipLaunchKernelGGL(k_fp_dn_tile3<MIN>, gt, b, 0, s, fdr, dem, values, stop, H, W, L.TX, L.rec[R & 1], value, where);
+}
+
+int dt_launch_flowpath_upslope(hipStream_t s, const uint8_t *fdr, const float *dem, const float *values, int64_t H,
+                               int64_t W, int kind, void *scratch, size_t scratch_bytes, float *value,
+                               int64_t *where) {
+  DT_REQUIRE(kind == 0 || kind == 1, "kind must be 0 (max) or 1 (min)");
+  if (H == 0 || W == 0 || (!value && !where)) return DT_OK;
+  FpLayout L = fp_layout(H, W, true, scratch);
+  DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
+  DT_REQUIRE(L.NN < (1ll << 31), "too many tiles: node ids travel in 31 bits");
+  const int R = std::max(2, dt_doubling_rounds(H * W));
+  DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 64, s));
+  if (kind == 1) fp_launch_up<true>(s, L, fdr, dem, values, H, W, R, value, where);
+  else fp_launch_up<false>(s, L, fdr, dem, values, H, W, R, value, where);
+  return DT_OK;
+}
+
+int dt_launch_flowpath_downstream(hipStream_t s, const uint8_t *fdr, const float *dem, const float *values,
+                                  const uint8_t *stop, int64_t H, int64_t W, int kind, void *scratch,
+                                  size_t scratch_bytes, float *value, int64_t *where) {
+  DT_REQUIRE(kind == 0 || kind == 1, "kind must be 0 (max) or 1 (min)");
+  if (H == 0 || W == 0 || (!value && !where)) return DT_OK;
+  FpLayout L = fp_layout(H, W, false, scratch);
+  DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
+  DT_REQUIRE(L.NN < (1ll << 31), "too many tiles: node ids travel in 31 bits");
+  const int R = std::max(2, dt_doubling_rounds(H * W));
+  DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 64, s));
+  if (kind == 1) fp_launch_down<true>(s, L, fdr, dem, values, stop, H, W, R, value, where);
+  else fp_launch_down<false>(s, L, fdr, dem, values, stop, H, W, R, value, where);
+  return DT_OK;
+}
+
+int dt_launch_carve_blend(hipStream_t s, const float *dem, const float *filled, const float *lowest, int64_t N,
+                          float cut, float *carved) {
+  if (N == 0) return DT_OK;
+  hipLaunchKernelGGL(k_carve_blend, dim3(dt_capped_grid(N, 8192)), dim3(256), 0, s, dem, filled, lowest, N, cut,
+                     carved);
+  return DT_OK;
+}

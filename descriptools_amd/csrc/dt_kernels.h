@@ -247,6 +247,19 @@ int dt_launch_drainage(hipStream_t s, const uint8_t *fdr, const float *dem, cons
 int dt_launch_upslope_length(hipStream_t s, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                              void *scratch, size_t scratch_bytes, double *length);
 
+// flow-path extremes and the carving blend (dt_flowpath.hip; flowpath.py and flowdir.d8_carved hold the definitions).
+// kind: 0 max, 1 min.  dem (nodata mask: <= -100) and stop (!= 0: a stop cell) may be NULL, so may value or where
+// (both NULL: nothing runs).  filled NULL: no limit on the cut; carved may alias lowest.  Nothing synchronises.
+// H * W < 2^31.
+size_t dt_flowpath_scratch(int64_t H, int64_t W, int upslope);
+int dt_launch_flowpath_upslope(hipStream_t s, const uint8_t *fdr, const float *dem, const float *values, int64_t H,
+                               int64_t W, int kind, void *scratch, size_t scratch_bytes, float *value, int64_t *where);
+int dt_launch_flowpath_downstream(hipStream_t s, const uint8_t *fdr, const float *dem, const float *values,
+                                  const uint8_t *stop, int64_t H, int64_t W, int kind, void *scratch,
+                                  size_t scratch_bytes, float *value, int64_t *where);
+int dt_launch_carve_blend(hipStream_t s, const float *dem, const float *filled, const float *lowest, int64_t N,
+                          float cut, float *carved);
+
 // reaches (dt_reaches.hip): the rank of every link head (reach ids), reach / catchment rasters, per-reach channel
 // counts, stage tables and inundation depth; definitions in include/descriptools_hip.h.  Nothing synchronises.
 // H * W < 2^31.  reach / catch / heads may be NULL (own_reach: reach is NULL and the launcher keeps the head ranks in

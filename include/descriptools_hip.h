@@ -196,6 +196,35 @@ int dt_drainage(const uint8_t *fdr, const float *dem, const int64_t *pour, int64
  * float64(n_card) * px + float64(n_diag) * (px * sqrt(2.0)).  -100 on nodata and on cells of a D8 cycle; cells that
  * drain into a cycle get their value.  Same refusals as dt_drainage. */
 int dt_upslope_length(const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px, double *length);
+/* Net-new: flow-path extremes of the float32 raster `values` on dt_drainage's graph.  kind 0: the maximum, 1: the
+ * minimum (anything else: DT_EINVAL).  A NaN is no value and is skipped, -0.0 counts as +0.0 (and comes back as +0.0),
+ * +-inf are ordinary values; between equal values the cell with the smallest flat index holds the extreme.
+ *   dt_flowpath_upslope:    the extreme of values[s] over every valid cell s whose path contains c, s = c included.
+ *                           Cells on a D8 cycle get the extreme over everything that reaches the cycle, the cycle
+ *                           included.
+ *   dt_flowpath_downstream: the extreme over the cells of c's path, from c to where it stops, both included.  Without
+ *                           `stop` the path stops at its terminal; when it enters a D8 cycle the extreme is over its
+ *                           tail and the whole cycle.  With `stop` (stop[i] != 0: a stop cell; on nodata: ignored) it
+ *                           stops at the first stop cell, c included, and a cell whose path ends at a terminal or runs
+ *                           round a cycle without meeting one has no value (where dt_drainage with these pour points
+ *                           gives -100).
+ *   value (float32): the extreme, NaN on nodata and where there is no value.
+ *   where (int64):   the flat index y * W + x of the cell that holds it, -100 where value is NaN.
+ * dem and stop may be NULL, so may value or where (not computed).  Exact: no arithmetic touches a value.  Rasters of
+ * 2^31 cells or more are refused. */
+int dt_flowpath_upslope(const uint8_t *fdr, const float *dem, const float *values, int64_t H, int64_t W, int kind,
+                        float *value, int64_t *where);
+int dt_flowpath_downstream(const uint8_t *fdr, const float *dem, const float *values, const uint8_t *stop, int64_t H,
+                           int64_t W, int kind, float *value, int64_t *where);
+/* Net-new: depression carving (Soille 2004; the complete form of breaching).  fdr and filled as dt_d8_conditioned_f32
+ * gives them for dem; lowest = dt_flowpath_upslope(fdr, dem, dem, kind 1): the lowest height above or at each cell on
+ * the conditioned D8 tree, which is non-increasing along every edge and <= dem.  carved = lowest when max_cut is +inf,
+ * else max(lowest, filled - float32(max_cut)), subtraction and maximum in float32: at most max_cut is cut and the rest
+ * filled; max_cut 0 gives filled.  Nodata cells (dem <= -100) keep their dem value.  filled may be NULL; info3 as in
+ * dt_d8_conditioned_f32.  A negative or NaN max_cut is refused, and what dt_drainage refuses.  NaN and +inf heights
+ * are outside the contract, as they are for the conditioning. */
+int dt_carve(const float *dem, int64_t H, int64_t W, double px, double max_cut, uint8_t *fdr, float *carved,
+             float *filled, int32_t *info3);
 /* Net-new: D-infinity (Tarboton 1997) flow direction.  angle (float32): radians counter-clockwise from east, rows
  * growing to the south, so octant k = 0..7 (the neighbour at k pi / 4) is E, NE, N, NW, W, SW, S, SE (D8 codes 1, 128,
  * 64, 32, 16, 8, 4, 2).  A height is valid when it is finite and > -100.  For a valid centre e0 the eight facets
@@ -627,6 +656,18 @@ int dt_dev_drainage(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const int
                     double px, int64_t *target, double *length, int64_t *label);
 int dt_dev_upslope_length(dt_ctx *ctx, const uint8_t *fdr, const float *dem, int64_t H, int64_t W, double px,
                           double *length);
+/* dt_flowpath_upslope and dt_flowpath_downstream on device rasters (rows x cols), on the context's stream: they do
+ * not synchronise and take their scratch from the context.  dem and stop may be NULL; a NULL output is not computed.
+ * dt_dev_carve_blend: carved = max(lowest, filled - float32(max_cut)) in float32, the dem value on nodata cells -- the
+ * last step of dt_carve for a finite max_cut >= 0 (anything else: DT_EINVAL); carved may alias lowest.  On a resident
+ * chain: lowest = dt_dev_flowpath_upslope(fdr, dem, dem, kind 1) on the chain's own codes. */
+int dt_dev_flowpath_upslope(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const float *values, int64_t rows,
+                            int64_t cols, int kind, float *value, int64_t *where);
+int dt_dev_flowpath_downstream(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const float *values,
+                               const uint8_t *stop, int64_t rows, int64_t cols, int kind, float *value,
+                               int64_t *where);
+int dt_dev_carve_blend(dt_ctx *ctx, const float *dem, const float *filled, const float *lowest, int64_t rows,
+                       int64_t cols, double max_cut, float *carved);
 /* dt_dinf_direction and dt_dinf_accumulate on device rasters, on the context's stream: neither synchronises.  fdr,
  * slope and w may be NULL.  dt_dev_dinf_accumulate enqueues round 0 (from the cells without donors) and rounds - 1
  * rounds that drain the queue of cells handed on (1 <= rounds <= 4096; a round that finds the queue empty returns at
