@@ -45,6 +45,17 @@ def pixel_size(px):
     return p
 
 
+def positive(v, what):
+    """v as a float; ValueError unless it is a number (not a bool), finite and > 0"""
+    try:
+        p = math.nan if isinstance(v, (bool, np.bool_)) else float(v)
+    except (TypeError, ValueError):
+        p = math.nan
+    if not (math.isfinite(p) and p > 0):
+        raise ValueError("%s must be a finite number > 0, not %r" % (what, v))
+    return p
+
+
 def _is_int(v):
     return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 

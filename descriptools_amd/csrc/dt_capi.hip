@@ -779,6 +779,36 @@ extern "C" int dt_dev_cost_distance(dt_ctx *c, const float *friction, const int8
                                         scr, need, cost, indices, backlink, c->status));
 }
 
+// harmonic interpolation: the shape rule of dt_check_ws, and what both tiers require of tol and the budget
+static int dt_check_harmonic(double tol, int max_rounds) {
+  DT_REQUIRE(std::isfinite(tol) && tol > 0.0, "tol must be finite and > 0");
+  DT_REQUIRE(max_rounds >= 1 && max_rounds <= DT_HARMONIC_ROUNDS_MAX, "max_rounds must lie in [1, 4096]");
+  return DT_OK;
+}
+// DT_DBG_HARMONIC_LEVELS=n (n >= 1): the pyramid has n levels at most (benchmarks; 0: as many as the raster needs)
+static int dt_harmonic_level_cap() {
+  const char *e = getenv("DT_DBG_HARMONIC_LEVELS");
+  const int v = e ? atoi(e) : 0;
+  return v > 0 ? v : 0;
+}
+extern "C" int dt_dev_harmonic(dt_ctx *c, const float *values, const int8_t *fixed, const int8_t *domain, int64_t rows,
+                               int64_t cols, double tol, int max_rounds, double *out, int64_t *info) {
+  DT_DEV(d, c, rows, cols, dt_check_fp);
+  DT_TRY(dt_check_harmonic(tol, max_rounds));
+  DT_REQUIRE((values && fixed && out) || rows * cols == 0, "NULL raster");
+  if (rows * cols == 0) return DT_OK;
+  const int cap = dt_harmonic_level_cap();
+  const size_t need = dt_harmonic_scratch(rows, cols, max_rounds, cap);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  DT_TRY(dt_launch_harmonic_setup(c->stream, values, fixed, domain, rows, cols, max_rounds, cap, scr, need, out));
+  for (int l = dt_harmonic_levels(rows, cols, cap) - 1; l >= 0; l--) {
+    DT_TRY(dt_launch_harmonic_rounds(c->stream, rows, cols, max_rounds, cap, l, 0, max_rounds, tol, scr, need, out));
+    if (l) DT_TRY(dt_launch_harmonic_prolong(c->stream, rows, cols, max_rounds, cap, l, scr, need, out));
+  }
+  return d.done(dt_launch_harmonic_finish(c->stream, rows, cols, max_rounds, cap, tol, scr, need, info, c->status));
+}
+
 static int dt_check_mfd_exponent(double exponent) {
   DT_REQUIRE(std::isfinite(exponent) && exponent >= 0.0 && exponent <= 64.0, "exponent must be finite and in [0, 64]");
   return DT_OK;
@@ -2671,6 +2701,52 @@ extern "C" int dt_cost_distance(const float *friction, const int8_t *sources, in
     info4[2] = cnt[1];
     info4[3] = (int64_t)cnt[2] | (int64_t)cnt[3] << 32;
   }
+  return DT_OK;
+}
+
+// (the batches of dt_dinf_distance_down, per level of the pyramid)
+extern "C" int dt_harmonic(const float *values, const int8_t *fixed, const int8_t *domain, int64_t H, int64_t W,
+                           double tol, int max_rounds, double *out, int64_t *info) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_TRY(dt_check_harmonic(tol, max_rounds));
+  if (info) memset(info, 0, sizeof(int64_t) * DT_HARMONIC_INFO);
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(values && fixed && out, "NULL raster");
+  const float *d_v = hc.in(values, n);
+  const int8_t *d_f = hc.in(fixed, n);
+  const int8_t *d_d = hc.in(domain, n);
+  double *d_o = hc.out(out, n);
+  const int cap = dt_harmonic_level_cap();
+  const size_t need = dt_harmonic_scratch(H, W, max_rounds, cap);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  hipStream_t s = hc.c->stream;
+  DT_TRY(dt_launch_harmonic_setup(s, d_v, d_f, d_d, H, W, max_rounds, cap, scr, need, d_o));
+  unsigned long long keys[DT_DINF_DIST_BATCH_MAX];
+  unsigned long long tol_key;
+  memcpy(&tol_key, &tol, sizeof(tol_key));
+  for (int l = dt_harmonic_levels(H, W, cap) - 1; l >= 0; l--) {
+    const unsigned long long *d_keys = dt_harmonic_keys(scr, H, W, max_rounds, cap, l);
+    int batch = DT_DINF_DIST_BATCH0;
+    for (int first = 0; first < max_rounds;) {
+      const int b = batch < max_rounds - first ? batch : max_rounds - first;
+      DT_TRY(dt_launch_harmonic_rounds(s, H, W, max_rounds, cap, l, first, b, tol, scr, need, d_o));
+      DT_TRY(hc.download(keys, d_keys + first, (size_t)b));
+      DT_HIP(hipStreamSynchronize(s));
+      if (keys[b - 1] <= tol_key) break;  // (a round behind one that met tol hands its key on)
+      first += b;
+      if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
+    }
+    if (l) DT_TRY(dt_launch_harmonic_prolong(s, H, W, max_rounds, cap, l, scr, need, d_o));
+  }
+  DT_TRY(dt_launched(dt_launch_harmonic_finish(s, H, W, max_rounds, cap, tol, scr, need, nullptr, nullptr)));
+  int64_t got[DT_HARMONIC_INFO];
+  DT_TRY(hc.download(got, dt_harmonic_info(scr, H, W, max_rounds, cap), (size_t)DT_HARMONIC_INFO));
+  DT_TRY(hc.finish());  // (synchronises: got is here)
+  if (info) memcpy(info, got, sizeof(got));
   return DT_OK;
 }
 

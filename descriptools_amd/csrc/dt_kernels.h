@@ -421,6 +421,39 @@ int dt_launch_cost_distance(hipStream_t s, const float *friction, const int8_t *
 // the control words in `scratch` (DT_COST_CTL_COUNTS + 8 x uint32 on the device)
 const uint32_t *dt_cost_distance_ctl(void *scratch, int64_t H, int64_t W, int alloc);
 
+// Harmonic interpolation (dt_harmonic.hip; harmonic.py holds the definition): out = the discrete harmonic function on
+// the domain with the fixed cells held (fixed == 1 and a finite value; domain NULL: everywhere), NaN outside the domain.
+// Nested iteration on a pyramid by 2 whose level 0 is `out` itself; the other levels, the masks, the flags and the key
+// words live in `scratch`.  level_cap: 0, or the number of levels at most (1: no pyramid; benchmarks).  A call is
+// setup -- the masks, the pyramid, the coarsest level's start -- then, from the coarsest level (dt_harmonic_levels - 1)
+// down to level 0, rounds [first_round, first_round + rounds) of tile visits, each followed by its residual into key
+// word r of the level (the bits of max r; launches behind a round whose key is <= tol's return at once and hand the key
+// on), and `prolong` from `level` to level - 1; finish writes DT_HARMONIC_INFO words to `info` (NULL: into the scratch,
+// dt_harmonic_info) and raises DT_STATUS_NOT_CONVERGED on `status` (may be NULL) when level 0's last residual exceeds
+// tol.  info: 0 levels, 1 rounds on level 0, 2 rounds on all levels, 3 tile visits, 4 the last residual of level 0 as
+// a double's bits, 5 whether that is <= tol, DT_HARMONIC_INFO_LEVEL0 + l the rounds on level l.  Precondition: every
+// free cell of the domain is joined to a fixed cell through the domain (4-connected); without it those cells hold an
+// unspecified constant.  Nothing synchronises.  0 < H * W < 2^31, 1 <= max_rounds <= DT_HARMONIC_ROUNDS_MAX.
+#define DT_HARMONIC_ROUNDS_MAX 4096
+#define DT_HARMONIC_LEVELS_MAX 32
+#define DT_HARMONIC_INFO_LEVEL0 8
+#define DT_HARMONIC_INFO (DT_HARMONIC_INFO_LEVEL0 + DT_HARMONIC_LEVELS_MAX)
+size_t dt_harmonic_scratch(int64_t H, int64_t W, int max_rounds, int level_cap);
+int dt_harmonic_levels(int64_t H, int64_t W, int level_cap);
+const unsigned long long *dt_harmonic_keys(void *scratch, int64_t H, int64_t W, int max_rounds, int level_cap,
+                                           int level);
+const int64_t *dt_harmonic_info(void *scratch, int64_t H, int64_t W, int max_rounds, int level_cap);
+int dt_launch_harmonic_setup(hipStream_t s, const float *values, const int8_t *fixed, const int8_t *domain, int64_t H,
+                             int64_t W, int max_rounds, int level_cap, void *scratch, size_t scratch_bytes,
+                             double *out);
+int dt_launch_harmonic_rounds(hipStream_t s, int64_t H, int64_t W, int max_rounds, int level_cap, int level,
+                              int first_round, int rounds, double tol, void *scratch, size_t scratch_bytes,
+                              double *out);
+int dt_launch_harmonic_prolong(hipStream_t s, int64_t H, int64_t W, int max_rounds, int level_cap, int level,
+                               void *scratch, size_t scratch_bytes, double *out);
+int dt_launch_harmonic_finish(hipStream_t s, int64_t H, int64_t W, int max_rounds, int level_cap, double tol,
+                              void *scratch, size_t scratch_bytes, int64_t *info, int *status);
+
 // Connected regions (dt_regions.hip; regions.py holds the definition): label = the smallest flat index of the cell's
 // region of mask != 0 under connectivity 4 or 8 (-100 on background), size = its cell count (0 on background), keep =
 // foreground, seeded (seeds NULL: every region is) and size >= min_cells.  label, size and keep may each be NULL (seeds
