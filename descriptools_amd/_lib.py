@@ -68,6 +68,8 @@ _SIGS = {
     "dt_proximity": (ci, [c_i8p, c_f32p, i64, i64, f64, c_f32p, c_i64p]),
     "dt_cost_distance": (ci, [c_f32p, c_i8p, i64, i64, f64, ci, ci, c_f64p, c_i64p, c_u8p, c_i64p]),
     "dt_harmonic": (ci, [c_f32p, c_i8p, c_i8p, i64, i64, f64, ci, c_f64p, c_i64p]),
+    "dt_inundation": (ci, [c_f32p, c_f32p, c_f32p, i64, i64, c_f64p, ci, c_i64p, c_f64p, c_f64p, ci, ci, i64, i64, ci,
+                           c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i64p]),
     "dt_reach_catchments": (ci, [c_i64p, c_i64p, i64, i64, c_i32p, c_i32p, c_i64p, i64, c_i64p]),
     "dt_reach_channels": (ci, [c_u8p, c_i32p, i64, i64, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
     "dt_reach_tables": (ci, [c_i32p, vp, ci, c_f32p, i64, i64, c_f64p, ci, i64, ci, c_i64p, c_i64p, c_i64p]),
@@ -129,6 +131,8 @@ _SIGS = {
     "dt_dev_mfd_accumulate_info": (ci, [vp, c_i64p]),
     "dt_dev_cost_distance": (ci, [vp, vp, vp, i64, i64, f64, ci, ci, ci, vp, vp, vp]),
     "dt_dev_harmonic": (ci, [vp, vp, vp, vp, i64, i64, f64, ci, vp, vp]),
+    "dt_dev_inundation": (ci, [vp, vp, vp, vp, i64, i64, c_f64p, ci, vp, vp, vp, ci, ci, i64, i64, vp, vp, vp, vp, vp,
+                               vp]),
     "dt_dev_terrain": (ci, [vp, vp, i64, i64, f64, ci, f64, f64, f64] + [vp] * 8),
     "dt_dev_horizon": (ci, [vp, vp, i64, i64, f64, ci, ci, f64] + [vp] * 5),
     "dt_dev_focal": (ci, [vp, vp, i64, i64, f64, ci, c_i32p, ci] + [vp] * 6),

@@ -809,6 +809,64 @@ extern "C" int dt_dev_harmonic(dt_ctx *c, const float *values, const int8_t *fix
   return d.done(dt_launch_harmonic_finish(c->stream, rows, cols, max_rounds, cap, tol, scr, need, info, c->status));
 }
 
+// flood inundation: what both tiers require of the scalars (the shape rule is dt_check_ws's, with px), and the call's
+// description for the launchers
+static int dt_check_inundation(const double *par, const float *manning, const float *rain, int boundary, int K, int T,
+                               int64_t steps0) {
+  DT_REQUIRE(par, "NULL parameters");
+  const double *p = par;
+  DT_REQUIRE(std::isfinite(p[1]) && p[1] >= 0.0, "t0 must be finite and >= 0");
+  DT_REQUIRE(std::isfinite(p[2]) && p[2] > 0.0, "t_end must be finite and > 0");
+  DT_REQUIRE(manning || (std::isfinite(p[3]) && p[3] > 0.0), "manning must be finite and > 0");
+  DT_REQUIRE(rain || (std::isfinite(p[4]) && p[4] >= 0.0), "rain must be finite and >= 0");
+  DT_REQUIRE(std::isfinite(p[5]) && p[5] > 0.0 && p[5] <= 1.0, "alpha must lie in (0, 1]");
+  DT_REQUIRE(std::isfinite(p[6]) && p[6] > 0.0, "dt_max must be finite and > 0");
+  DT_REQUIRE(std::isfinite(p[7]) && p[7] >= 0.0, "dry must be finite and >= 0");
+  DT_REQUIRE(std::isfinite(p[8]) && p[8] > 0.0, "boundary_slope must be finite and > 0");
+  DT_REQUIRE(std::isfinite(p[9]) && p[9] >= 0.0, "arrival_depth must be finite and >= 0");
+  DT_REQUIRE(boundary == 0 || boundary == 1, "boundary is 0 (closed) or 1 (open)");
+  DT_REQUIRE(K >= 0 && K <= DT_INUNDATION_INFLOW_MAX, "inflow cells must number 0 to 4096");
+  DT_REQUIRE(K == 0 || (T >= 1 && T <= (1 << 20)), "inflow times must number 1 to 2^20");
+  DT_REQUIRE(steps0 >= 0, "steps0 is negative");
+  return DT_OK;
+}
+static DtInundation dt_inundation_call(const float *z, const float *manning, const float *rain, int64_t H, int64_t W,
+                                       const double *p, int boundary, const int64_t *cells, const double *times,
+                                       const double *discharge, int K, int T, int64_t max_steps, double *h, double *qx,
+                                       double *qy, double *max_depth, double *arrival) {
+  DtInundation d;
+  d.z = z; d.manning = manning; d.rain = rain;
+  d.H = H; d.W = W;
+  d.px = p[0]; d.t_end = p[2]; d.n = p[3]; d.rain_s = p[4]; d.alpha = p[5]; d.dt_max = p[6]; d.dry = p[7];
+  d.slope = p[8]; d.arrival_depth = p[9];
+  d.open = boundary;
+  d.cells = cells; d.times = times; d.discharge = discharge;
+  d.K = K; d.T = K ? T : 0;
+  d.max_steps = max_steps;
+  d.h = h; d.qx = qx; d.qy = qy; d.max_depth = max_depth; d.arrival = arrival;
+  return d;
+}
+extern "C" int dt_dev_inundation(dt_ctx *c, const float *z, const float *manning, const float *rain, int64_t rows,
+                                 int64_t cols, const double *par, int boundary, const int64_t *cells,
+                                 const double *times, const double *discharge, int K, int T, int64_t steps0,
+                                 int64_t max_steps, double *h, double *qx, double *qy, double *max_depth,
+                                 double *arrival, int64_t *info) {
+  DT_DEV(d, c, rows, cols, par ? par[0] : 0.0);
+  DT_TRY(dt_check_inundation(par, manning, rain, boundary, K, T, steps0));
+  DT_REQUIRE(max_steps >= 0 && max_steps <= DT_INUNDATION_DEV_STEPS_MAX, "max_steps must lie in [0, 2^20]");
+  DT_REQUIRE((z && h && qx && qy) || rows * cols == 0, "NULL raster");
+  DT_REQUIRE(K == 0 || (cells && times && discharge), "NULL inflow table");
+  if (rows * cols == 0) return DT_OK;
+  const size_t need = dt_inundation_scratch(rows, cols);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  const DtInundation call = dt_inundation_call(z, manning, rain, rows, cols, par, boundary, cells, times, discharge, K,
+                                               T, max_steps, h, qx, qy, max_depth, arrival);
+  DT_TRY(dt_launch_inundation_begin(c->stream, call, par[1], steps0, scr, need));
+  DT_TRY(dt_launch_inundation_steps(c->stream, call, (int)max_steps, scr, need));
+  return d.done(dt_launch_inundation_finish(c->stream, call, scr, need, info));
+}
+
 static int dt_check_mfd_exponent(double exponent) {
   DT_REQUIRE(std::isfinite(exponent) && exponent >= 0.0 && exponent <= 64.0, "exponent must be finite and in [0, 64]");
   return DT_OK;
@@ -2745,6 +2803,61 @@ extern "C" int dt_harmonic(const float *values, const int8_t *fixed, const int8_
   DT_TRY(dt_launched(dt_launch_harmonic_finish(s, H, W, max_rounds, cap, tol, scr, need, nullptr, nullptr)));
   int64_t got[DT_HARMONIC_INFO];
   DT_TRY(hc.download(got, dt_harmonic_info(scr, H, W, max_rounds, cap), (size_t)DT_HARMONIC_INFO));
+  DT_TRY(hc.finish());  // (synchronises: got is here)
+  if (info) memcpy(info, got, sizeof(got));
+  return DT_OK;
+}
+
+// (batches of sync_every guarded steps; the control block's "no step is left" word is read back after each)
+extern "C" int dt_inundation(const float *z, const float *manning, const float *rain, int64_t H, int64_t W,
+                             const double *par, int boundary, const int64_t *cells, const double *times,
+                             const double *discharge, int K, int T, int64_t steps0, int64_t max_steps, int sync_every,
+                             double *h, double *qx, double *qy, double *max_depth, double *arrival, int64_t *info) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, par ? par[0] : 0.0));
+  DT_TRY(dt_check_inundation(par, manning, rain, boundary, K, T, steps0));
+  DT_REQUIRE(max_steps >= -1, "max_steps must be >= 0, or -1 for no limit");
+  DT_REQUIRE(sync_every >= 1 && sync_every <= 1024, "sync_every must lie in [1, 1024]");
+  if (info) memset(info, 0, sizeof(int64_t) * DT_INUNDATION_INFO_WORDS);
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(z && h && qx && qy, "NULL raster");
+  DT_REQUIRE(K == 0 || (cells && times && discharge), "NULL inflow table");
+  for (int j = 0; j < K; j++) DT_REQUIRE(cells[j] >= 0 && (size_t)cells[j] < n, "inflow cell outside the raster");
+  for (int j = 1; j < (K ? T : 0); j++) DT_REQUIRE(times[j] > times[j - 1], "inflow times must ascend strictly");
+  for (size_t j = 0; j < (size_t)K * (size_t)T; j++)
+    DT_REQUIRE(std::isfinite(discharge[j]) && discharge[j] >= 0.0, "discharge must be finite and >= 0");
+  const float *d_z = hc.in(z, n), *d_m = hc.in(manning, n), *d_r = hc.in(rain, n);
+  double *d_h = hc.in(h, n), *d_qx = hc.in(qx, n), *d_qy = hc.in(qy, n);
+  double *d_md = hc.in(max_depth, n), *d_ar = hc.in(arrival, n);
+  const int64_t *d_c = K ? hc.in(cells, (size_t)K) : nullptr;
+  const double *d_t = K ? hc.in(times, (size_t)T) : nullptr;
+  const double *d_q = K ? hc.in(discharge, (size_t)K * (size_t)T) : nullptr;
+  int64_t *d_info = hc.scratch<int64_t>(DT_INUNDATION_INFO_WORDS);
+  const size_t need = dt_inundation_scratch(H, W);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  hipStream_t s = hc.c->stream;
+  const DtInundation call = dt_inundation_call(d_z, d_m, d_r, H, W, par, boundary, d_c, d_t, d_q, K, T, max_steps, d_h,
+                                               d_qx, d_qy, d_md, d_ar);
+  DT_TRY(dt_launch_inundation_begin(s, call, par[1], steps0, scr, need));
+  const unsigned long long *d_ctl = dt_inundation_ctl(scr, H, W);
+  unsigned long long ctl[DT_IN_CTL];
+  for (;;) {
+    DT_TRY(hc.download(ctl, d_ctl, (size_t)DT_IN_CTL));
+    DT_HIP(hipStreamSynchronize(s));
+    if (ctl[3]) break;  // no step is left
+    DT_TRY(dt_launched(dt_launch_inundation_steps(s, call, sync_every, scr, need)));
+  }
+  DT_TRY(dt_launched(dt_launch_inundation_finish(s, call, scr, need, d_info)));
+  int64_t got[DT_INUNDATION_INFO_WORDS];
+  DT_TRY(hc.download(got, (const int64_t *)d_info, (size_t)DT_INUNDATION_INFO_WORDS));
+  DT_TRY(hc.download(h, (const double *)d_h, n));
+  DT_TRY(hc.download(qx, (const double *)d_qx, n));
+  DT_TRY(hc.download(qy, (const double *)d_qy, n));
+  if (max_depth) DT_TRY(hc.download(max_depth, (const double *)d_md, n));
+  if (arrival) DT_TRY(hc.download(arrival, (const double *)d_ar, n));
   DT_TRY(hc.finish());  // (synchronises: got is here)
   if (info) memcpy(info, got, sizeof(got));
   return DT_OK;

@@ -454,6 +454,36 @@ int dt_launch_harmonic_prolong(hipStream_t s, int64_t H, int64_t W, int max_roun
 int dt_launch_harmonic_finish(hipStream_t s, int64_t H, int64_t W, int max_rounds, int level_cap, double tol,
                               void *scratch, size_t scratch_bytes, int64_t *info, int *status);
 
+// Local-inertial flood inundation (dt_inundation.hip; inundation.py holds the scheme).  The state h, qx, qy (float64,
+// H x W) is the caller's and is updated in place; its second copy and the control block (DT_IN_CTL words of 8 bytes:
+// 0 t, 1 the next step's dt, 2 the time after it, 3 whether no step is left, 4 the steps of this call, 5 the steps in
+// all, 6 the smallest dt, 7 the last dt, 8 the steps the limiter acted in, 9 the largest depth, 10-11 accumulators,
+// 12 whether t >= t_end; doubles as their bits) live in `scratch`.  z: float32 heights, NaN on a wall; manning, rain:
+// float32 rasters, or NULL for the scalars n and rain_s; max_depth, arrival: updated in place, or NULL; cells, times,
+// discharge: the inflow table on the device (K may be 0).  begin opens a call at (t0, steps0), `steps` enqueues that
+// many guarded steps (one that comes after the end returns at once), finish moves the state back into h, qx, qy when
+// it sits in the second copy and writes DT_INUNDATION_INFO_WORDS words to `info` (on the device; may be NULL).
+// Nothing synchronises.  0 < H * W < 2^31.
+#define DT_IN_CTL 16
+struct DtInundation {
+  const float *z, *manning, *rain;
+  int64_t H, W;
+  double px, t_end, n, rain_s, alpha, dt_max, dry, slope, arrival_depth;
+  int open;
+  const int64_t *cells;
+  const double *times, *discharge;
+  int K, T;
+  int64_t max_steps;  // of this call; < 0: no limit
+  double *h, *qx, *qy, *max_depth, *arrival;
+};
+size_t dt_inundation_scratch(int64_t H, int64_t W);
+const unsigned long long *dt_inundation_ctl(void *scratch, int64_t H, int64_t W);
+int dt_launch_inundation_begin(hipStream_t s, const DtInundation &d, double t0, int64_t steps0, void *scratch,
+                               size_t scratch_bytes);
+int dt_launch_inundation_steps(hipStream_t s, const DtInundation &d, int steps, void *scratch, size_t scratch_bytes);
+int dt_launch_inundation_finish(hipStream_t s, const DtInundation &d, void *scratch, size_t scratch_bytes,
+                                int64_t *info);
+
 // Connected regions (dt_regions.hip; regions.py holds the definition): label = the smallest flat index of the cell's
 // region of mask != 0 under connectivity 4 or 8 (-100 on background), size = its cell count (0 on background), keep =
 // foreground, seeded (seeds NULL: every region is) and size >= min_cells.  label, size and keep may each be NULL (seeds

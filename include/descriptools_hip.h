@@ -437,6 +437,29 @@ int dt_cost_distance(const float *friction, const int8_t *sources, int64_t H, in
 #define DT_HARMONIC_INFO_WORDS 40
 int dt_harmonic(const float *values, const int8_t *fixed, const int8_t *domain, int64_t H, int64_t W, double tol,
                 int max_rounds, double *out, int64_t *info);
+/* Net-new: local-inertial 2-D flood inundation (Bates, Horritt & Fewtrell 2010; descriptools_amd/inundation.py holds
+ * the scheme and its association, which is the contract: the state is a numpy restatement's bit for bit).  Rasters are
+ * H x W with fewer than 2^31 cells.  z: float32 heights, NaN on a wall (nodata).  manning, rain: float32 rasters, or
+ * NULL for the scalars in par.  par (double[DT_INUNDATION_PAR], host memory in both tiers): 0 px, 1 the time the call
+ * starts at, 2 t_end, 3 Manning's n, 4 the rain rate (m/s), 5 alpha, 6 dt_max, 7 the dry depth, 8 the slope of the open
+ * boundary, 9 the arrival depth.  boundary: 0 closed, 1 open.  The inflow table: cells int64[K] (flat indices of valid
+ * cells, no duplicates, K <= DT_INUNDATION_INFLOW_MAX, may be 0), times double[T] ascending strictly, discharge
+ * double[K * T] in m^3/s, finite and >= 0.  h, qx, qy (float64) are the state, read and written in place: h >= 0 on
+ * valid cells (what walls hold is ignored and comes back 0), qx / qy the unit-width discharge over the east / south
+ * face.  max_depth and arrival (float64, may each be NULL) are updated in place.  steps0: the steps taken before this
+ * call; max_steps: the steps of this call at most, -1 for no limit; sync_every (1..1024): the guarded steps enqueued
+ * between two read-backs of the control block -- the result does not depend on it.  info
+ * (int64[DT_INUNDATION_INFO_WORDS], may be NULL): 0 the steps in all, 1 the steps of this call, 2 t, 3 the smallest
+ * dt, 4 the last dt, 5 the largest depth (2-5: a double's bits), 6 the steps in which the limiter acted, 7 whether
+ * t >= t_end. */
+#define DT_INUNDATION_PAR 10
+#define DT_INUNDATION_INFO_WORDS 8
+#define DT_INUNDATION_INFLOW_MAX 4096
+#define DT_INUNDATION_DEV_STEPS_MAX (1 << 20)
+int dt_inundation(const float *z, const float *manning, const float *rain, int64_t H, int64_t W, const double *par,
+                  int boundary, const int64_t *cells, const double *times, const double *discharge, int K, int T,
+                  int64_t steps0, int64_t max_steps, int sync_every, double *h, double *qx, double *qy,
+                  double *max_depth, double *arrival, int64_t *info);
 /* Net-new: reaches (the HAND synthetic-rating-curve method).  Rasters are H x W with fewer than 2^31 cells, flat index
  * y * W + x; results are exact integers (and depth one float32 rounding), independent of order and run.
  *
@@ -806,6 +829,16 @@ int dt_dev_cost_distance(dt_ctx *ctx, const float *friction, const int8_t *sourc
  * cell and 8 bytes per level and round) is the context's scratch; nothing is kept between calls.  domain may be NULL. */
 int dt_dev_harmonic(dt_ctx *ctx, const float *values, const int8_t *fixed, const int8_t *domain, int64_t rows,
                     int64_t cols, double tol, int max_rounds, double *out, int64_t *info);
+/* dt_inundation on device rasters (rows x cols = H x W; the inflow table on the device too, par in host memory), on
+ * the context's stream, without a host synchronisation: exactly max_steps (0..DT_INUNDATION_DEV_STEPS_MAX) guarded
+ * steps are enqueued, two launches each, and those that come after t_end return at once -- info[7] says whether t_end
+ * was reached; call again with steps0 = info[0] and par[1] = t to go on.  info (int64[DT_INUNDATION_INFO_WORDS] ON
+ * THE DEVICE, may be NULL) is written by the last launch.  The workspace (24 bytes per cell: the second copy of the
+ * state) is the context's scratch; nothing is kept between calls. */
+int dt_dev_inundation(dt_ctx *ctx, const float *z, const float *manning, const float *rain, int64_t rows, int64_t cols,
+                      const double *par, int boundary, const int64_t *cells, const double *times,
+                      const double *discharge, int K, int T, int64_t steps0, int64_t max_steps, double *h, double *qx,
+                      double *qy, double *max_depth, double *arrival, int64_t *info);
 /* dt_regions_label, dt_regions_select and dt_inundate_connected on device rasters (rows x cols = H x W), on the
  * context's stream: three to five launches whatever the rasters hold, none synchronises.  The workspace (12 bytes per
  * cell, 14 for the inundation) is the context's scratch; nothing is kept between calls.  size and seeds may be NULL. */
