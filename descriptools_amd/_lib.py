@@ -53,6 +53,8 @@ _SIGS = {
     "dt_upslope_length": (ci, [c_u8p, c_f32p, i64, i64, f64, c_f64p]),
     "dt_flowpath_upslope": (ci, [c_u8p, c_f32p, c_f32p, i64, i64, ci, c_f32p, c_i64p]),
     "dt_flowpath_downstream": (ci, [c_u8p, c_f32p, c_f32p, c_u8p, i64, i64, ci, c_f32p, c_i64p]),
+    "dt_flowpath_downstream_sum": (ci, [c_u8p, c_f32p, c_f64p, c_u8p, i64, i64, ci, c_f64p]),
+    "dt_flowpath_upslope_longest": (ci, [c_u8p, c_f32p, c_f64p, i64, i64, ci, c_f64p]),
     "dt_carve": (ci, [c_f32p, i64, i64, f64, f64, c_u8p, c_f32p, c_f32p, c_i32p]),
     "dt_dinf_direction": (ci, [c_f32p, c_u8p, i64, i64, f64, c_f32p, c_f32p]),
     "dt_dinf_accumulate": (ci, [c_f32p, c_f64p, i64, i64, ci, c_f64p, c_i64p]),
@@ -123,6 +125,8 @@ _SIGS = {
     "dt_dev_flowpath_upslope": (ci, [vp, vp, vp, vp, i64, i64, ci, vp, vp]),
     "dt_dev_flowpath_downstream": (ci, [vp, vp, vp, vp, vp, i64, i64, ci, vp, vp]),
     "dt_dev_carve_blend": (ci, [vp, vp, vp, vp, i64, i64, f64, vp]),
+    "dt_dev_flowpath_downstream_sum": (ci, [vp, vp, vp, vp, vp, i64, i64, ci, vp]),
+    "dt_dev_flowpath_upslope_longest": (ci, [vp, vp, vp, vp, i64, i64, ci, vp]),
     "dt_dev_dinf_direction": (ci, [vp, vp, vp, i64, i64, f64, vp, vp]),
     "dt_dev_dinf_accumulate": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
     "dt_dev_dinf_accumulate_info": (ci, [vp, c_i64p]),

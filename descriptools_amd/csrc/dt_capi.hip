@@ -669,6 +669,33 @@ extern "C" int dt_dev_carve_blend(dt_ctx *c, const float *dem, const float *fill
   return d.done(dt_launch_carve_blend(c->stream, dem, filled, lowest, rows * cols, (float)max_cut, carved));
 }
 
+// weighted flow-path sums: the weights' contract and frac_bits are dt_dev_flowacc_weighted's
+extern "C" int dt_dev_flowpath_downstream_sum(dt_ctx *c, const uint8_t *fdr, const float *dem, const double *w,
+                                              const uint8_t *stop, int64_t rows, int64_t cols, int frac_bits,
+                                              double *out) {
+  DT_DEV(d, c, rows, cols, dt_check_fp);
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  DT_REQUIRE((fdr && w) || rows * cols == 0, "NULL raster");
+  if (rows * cols == 0 || !out) return DT_OK;
+  const size_t need = dt_pathsum_scratch(rows, cols, 0);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_pathsum_downstream(c->stream, fdr, dem, w, stop, rows, cols, frac_bits, scr, need, out,
+                                             c->status));
+}
+
+extern "C" int dt_dev_flowpath_upslope_longest(dt_ctx *c, const uint8_t *fdr, const float *dem, const double *w,
+                                               int64_t rows, int64_t cols, int frac_bits, double *out) {
+  DT_DEV(d, c, rows, cols, dt_check_fp);
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  DT_REQUIRE((fdr && w) || rows * cols == 0, "NULL raster");
+  if (rows * cols == 0 || !out) return DT_OK;
+  const size_t need = dt_pathsum_scratch(rows, cols, 1);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_pathsum_longest(c->stream, fdr, dem, w, rows, cols, frac_bits, scr, need, out, c->status));
+}
+
 extern "C" int dt_dev_dinf_direction(dt_ctx *c, const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double px,
                                      float *angle, float *slope) {
   DT_DEV(d, c, H, W, px);
@@ -3490,6 +3517,39 @@ extern "C" int dt_flowpath_downstream(const uint8_t *fdr, const float *dem, cons
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_flowpath_downstream(hc.c, d_f, d_dem, d_v, d_s, H, W, kind, d_o, d_w));
   return hc.finish();
+}
+
+// weighted flow-path sums, host tier (stop NULL and longest: dt_flowpath_upslope_longest)
+static int host_pathsum(const uint8_t *fdr, const float *dem, const double *w, const uint8_t *stop, int64_t H,
+                        int64_t W, int frac_bits, bool longest, double *out) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  const size_t n = (size_t)H * W;
+  if (n == 0 || !out) return DT_OK;
+  DT_REQUIRE(fdr && w, "NULL raster");
+  const uint8_t *d_f = hc.in(fdr, n);
+  const float *d_dem = hc.in(dem, n);
+  const double *d_w = hc.in(w, n);
+  const uint8_t *d_s = hc.in(stop, n);
+  double *d_o = hc.out(out, n);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
+  if (longest) DT_TRY(dt_dev_flowpath_upslope_longest(hc.c, d_f, d_dem, d_w, H, W, frac_bits, d_o));
+  else DT_TRY(dt_dev_flowpath_downstream_sum(hc.c, d_f, d_dem, d_w, d_s, H, W, frac_bits, d_o));
+  DT_TRY(dt_ctx_status(hc.c, &st));
+  DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
+  return hc.finish();
+}
+extern "C" int dt_flowpath_downstream_sum(const uint8_t *fdr, const float *dem, const double *w, const uint8_t *stop,
+                                          int64_t H, int64_t W, int frac_bits, double *out) {
+  return host_pathsum(fdr, dem, w, stop, H, W, frac_bits, false, out);
+}
+extern "C" int dt_flowpath_upslope_longest(const uint8_t *fdr, const float *dem, const double *w, int64_t H, int64_t W,
+                                           int frac_bits, double *out) {
+  return host_pathsum(fdr, dem, w, nullptr, H, W, frac_bits, true, out);
 }
 
 // depression carving, host tier: conditioned D8, the upslope minimum of the DEM over its tree, and the blend with the

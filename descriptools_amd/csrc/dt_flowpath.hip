@@ -1,6 +1,6 @@
 // dt_flowpath.hip -- flow-path extremes: the max / min of a value raster over everything upslope of a cell, or along
-// its path downstream, and the pointwise blend of depression carving (net-new; descriptools_amd/flowpath.py and
-// flowdir.d8_carved hold the definitions).
+// its path downstream, the pointwise blend of depression carving, and the weighted sums along a path: travel time
+// and time of concentration (net-new; descriptools_amd/flowpath.py and flowdir.d8_carved hold the definitions).
 //
 // Graph: dt_watershed.hip's drainage graph.  c -> d when c's code is one of the eight D8 codes, d lies in the raster
 // and (with a DEM) neither c nor d is nodata (dem <= -100).  A valid cell with no edge is a terminal.
@@ -47,6 +47,17 @@
 // skipped), so a cycle never reads a half-updated record.  Without a stop raster a record still open after R rounds
 // lies on or drains into a cycle and its word is complete (R rounds cover N node-moves); with one, such a path met
 // no stop cell and gets no value.
+//
+// Path sums (k_ps_dn_tile1, k_ps_dn_node x R, k_ps_dn_tile3; the upslope kernels above with a raw key): T(c) = the sum
+// of q = rint(w * 2^s) over the moves of c's path down to where it stops, and U(c) = the longest such sum that ends at
+// c.  The downstream sum is the downstream fold with an unsigned 64-bit add in place of the max: v(c) += v(ptr(c)),
+// where v(c) is the cost of the moves from c up to, not including, its pointer (an end carries 0, and an exit cell's
+// own move travels in its perimeter record, so nothing is added twice).  A sum, unlike a max, is not idempotent: a
+// path that never stops (a D8 cycle) doubles its sum every round, the wrap is that of unsigned arithmetic, and the
+// value is discarded -- such a cell has no target and gets -100, as watershed.drainage gives it, with or without a
+// stop raster.  U rests on T(s) = D(s -> c) + T(c) for every s above c: U(c) = M(c) - T(c), M the upslope max of T,
+// which is the upslope fold on the raw key T + 1 (0: no value), so cycles need no special case there either and no
+// sum can exceed the largest T.  Sums stay <= 2^52 under the caller's bound N * rint(max w * 2^s) <= 2^52.
 #include "dt_kernels.h"
 
 #define FP_T 64
@@ -149,6 +160,36 @@ __device__ __forceinline__ fp_u64 fp_cell_key(const float *__restrict__ values, 
   return fp_key<MIN>(values[c], c);
 }
 
+// What an upslope fold folds: key(c) the word of cell c (0: no value), put(c, v) the outputs of cell c from the fold's
+// word v.  FpExtreme: a float raster's max / min and the cell that holds it.
+template <bool MIN>
+struct FpExtreme {
+  const float *__restrict__ values;
+  float *__restrict__ value;
+  int64_t *__restrict__ where;
+  __device__ __forceinline__ fp_u64 key(int64_t c) const { return fp_key<MIN>(values[c], c); }
+  __device__ __forceinline__ void put(int64_t c, fp_u64 v) const {
+    if (value) value[c] = fp_value<MIN>(v);
+    if (where) where[c] = fp_where(v);
+  }
+};
+// PsLongest: the raw key T + 1 of a downstream-sum plane (T < 0: no value); out = (M - T) * 2^-s, -100 without a T
+struct PsLongest {
+  const int64_t *__restrict__ T;
+  double *__restrict__ out;
+  int sbits;
+  __device__ __forceinline__ fp_u64 key(int64_t c) const { return (fp_u64)(T[c] + 1); }
+  __device__ __forceinline__ void put(int64_t c, fp_u64 m) const {
+    const int64_t t = T[c];
+    out[c] = (t < 0 || m == 0ull) ? -100.0 : ldexp((double)(int64_t)(m - 1ull - (fp_u64)t), -sbits);
+  }
+};
+template <class P>
+__device__ __forceinline__ fp_u64 fp_cell_key(const P &p, uint32_t w, int64_t W, int64_t y0, int64_t x0, int l) {
+  if (fp_kind(w) == FP_K_FAIL) return 0ull;  // outside the raster, or nodata
+  return p.key((y0 + (l >> 6)) * W + x0 + (l & 63));
+}
+
 // Upslope: pointer doubling with scatter.  s_w holds w[], s_v the cells' own words (and, in pass 3, the inflow of the
 // entries), after a barrier.  On return (after a barrier) s_v[l] is the max over everything above l inside the tile.
 __device__ __forceinline__ void fp_fold_up(uint32_t *s_w, fp_u64 *s_v, uint32_t (&w)[FP_CPT]) {
@@ -194,7 +235,8 @@ __device__ __forceinline__ void fp_fold_up(uint32_t *s_w, fp_u64 *s_v, uint32_t 
 }
 
 // Downstream: pointer doubling with gather.  s_w holds w[], s_v holds v[], after a barrier.  On return (after a
-// barrier) v[] / s_v hold the max over each cell's in-tile path, its end included.
+// barrier) v[] / s_v hold the max over each cell's in-tile path, its end included (SUM: the sum, modulo 2^64).
+template <bool SUM = false>
 __device__ __forceinline__ void fp_fold_down(uint32_t *s_w, fp_u64 *s_v, uint32_t (&w)[FP_CPT], fp_u64 (&v)[FP_CPT]) {
   const int t = (int)threadIdx.x;
   for (int r = 0; r < FP_ROUNDS; r++) {
@@ -212,7 +254,7 @@ __device__ __forceinline__ void fp_fold_down(uint32_t *s_w, fp_u64 *s_v, uint32_
     for (int k = 0; k < FP_CPT; k++) {
       if (fp_kind(w[k]) == FP_K_PTR) {
         w[k] = tg[k];
-        v[k] = tv[k] > v[k] ? tv[k] : v[k];
+        v[k] = SUM ? v[k] + tv[k] : (tv[k] > v[k] ? tv[k] : v[k]);
         s_w[k * 256 + t] = w[k];
         s_v[k * 256 + t] = v[k];
         pend |= fp_kind(w[k]) == FP_K_PTR;
@@ -223,11 +265,10 @@ __device__ __forceinline__ void fp_fold_down(uint32_t *s_w, fp_u64 *s_v, uint32_
 }
 
 // ---- upslope -----------------------------------------------------------------------------------------------------
-template <bool MIN>
+template <class P>
 __global__ __launch_bounds__(256) void k_fp_up_tile1(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
-                                                     const float *__restrict__ values, int64_t H, int64_t W,
-                                                     int64_t TX, uint32_t *__restrict__ uptr,
-                                                     fp_u64 *__restrict__ S) {
+                                                     const P fold, int64_t H, int64_t W, int64_t TX,
+                                                     uint32_t *__restrict__ uptr, fp_u64 *__restrict__ S) {
   __shared__ uint32_t s_w[FP_T * FP_T];
   __shared__ fp_u64 s_v[FP_T * FP_T];
   const FpTile T = fp_tile(TX);
@@ -238,7 +279,7 @@ __global__ __launch_bounds__(256) void k_fp_up_tile1(const uint8_t *__restrict__
     const int l = k * 256 + t;
     w[k] = fp_init(fdr, dem, nullptr, H, W, T.y0, T.x0, l);
     s_w[l] = w[k];
-    s_v[l] = fp_cell_key<MIN>(values, w[k], H, W, T.y0, T.x0, l);
+    s_v[l] = fp_cell_key(fold, w[k], W, T.y0, T.x0, l);
   }
   __syncthreads();
   fp_fold_up(s_w, s_v, w);
@@ -288,11 +329,10 @@ __global__ __launch_bounds__(256) void k_fp_up_node(const uint32_t *__restrict__
   if (__ballot(pend) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(&flags[r + 1], 1u);
 }
 
-template <bool MIN>
+template <class P>
 __global__ __launch_bounds__(256) void k_fp_up_tile3(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
-                                                     const float *__restrict__ values, int64_t H, int64_t W,
-                                                     int64_t TX, const fp_u64 *__restrict__ S,
-                                                     float *__restrict__ value, int64_t *__restrict__ where) {
+                                                     const P fold, int64_t H, int64_t W, int64_t TX,
+                                                     const fp_u64 *__restrict__ S) {
   __shared__ uint32_t s_w[FP_T * FP_T];
   __shared__ fp_u64 s_v[FP_T * FP_T];
   const FpTile T = fp_tile(TX);
@@ -303,7 +343,7 @@ __global__ __launch_bounds__(256) void k_fp_up_tile3(const uint8_t *__restrict__
     const int l = k * 256 + t;
     w[k] = fp_init(fdr, dem, nullptr, H, W, T.y0, T.x0, l);
     s_w[l] = w[k];
-    s_v[l] = fp_cell_key<MIN>(values, w[k], H, W, T.y0, T.x0, l);
+    s_v[l] = fp_cell_key(fold, w[k], W, T.y0, T.x0, l);
   }
   __syncthreads();
   // entry inflow: S(f) of each feeder f in another tile (an exit of its tile, so a perimeter node whose S is complete)
@@ -335,9 +375,7 @@ __global__ __launch_bounds__(256) void k_fp_up_tile3(const uint8_t *__restrict__
     const int l = k * 256 + t;
     const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
     if (y >= H || x >= W) continue;
-    const fp_u64 v = s_v[l];
-    if (value) value[y * W + x] = fp_value<MIN>(v);
-    if (where) where[y * W + x] = fp_where(v);
+    fold.put(y * W + x, s_v[l]);
   }
 }
 
@@ -389,8 +427,10 @@ __global__ __launch_bounds__(256) void k_fp_dn_tile1(const uint8_t *__restrict__
 
 // one doubling round src -> dst over the perimeter records; tag = the round a record was resolved in (-1: pass 1).
 // flags[r + 1] = 1 when this round left a record open.
-__global__ __launch_bounds__(256) void k_fp_dn_node(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t NN,
-                                                    uint32_t *flags, int r) {
+// SUM: the words are sums (modulo 2^64) instead of keys.
+template <bool SUM>
+__device__ __forceinline__ void fp_dn_round(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t NN,
+                                            uint32_t *flags, int r) {
   if (r >= 2 && flags[r - 1] == 0u) return;
   bool pend = false;
   for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < NN; n += (int64_t)gridDim.x * 256) {
@@ -401,7 +441,7 @@ __global__ __launch_bounds__(256) void k_fp_dn_node(const uint4 *__restrict__ sr
     }
     const uint4 q = src[s.x];
     const fp_u64 a = (fp_u64)s.z | ((fp_u64)s.w << 32), b = (fp_u64)q.z | ((fp_u64)q.w << 32);
-    const fp_u64 m = a > b ? a : b;
+    const fp_u64 m = SUM ? a + b : (a > b ? a : b);
     uint4 o;
     if (q.x == FP_FAILP) {
       o = make_uint4(FP_FAILP, (uint32_t)r, 0u, 0u);
@@ -414,6 +454,14 @@ __global__ __launch_bounds__(256) void k_fp_dn_node(const uint4 *__restrict__ sr
     dst[n] = o;
   }
   if (__ballot(pend) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(&flags[r + 1], 1u);
+}
+__global__ __launch_bounds__(256) void k_fp_dn_node(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t NN,
+                                                    uint32_t *flags, int r) {
+  fp_dn_round<false>(src, dst, NN, flags, r);
+}
+__global__ __launch_bounds__(256) void k_ps_dn_node(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t NN,
+                                                    uint32_t *flags, int r) {
+  fp_dn_round<true>(src, dst, NN, flags, r);
 }
 
 template <bool MIN>
@@ -460,7 +508,130 @@ __global__ __launch_bounds__(256) void k_fp_dn_tile3(const uint8_t *__restrict__
   }
 }
 
-// ---- carving: carved = max(lowest, filled - cut) in float32, the DEM's own value on nodata -------------------------
+// ---- downstream sum ----------------------------------------------------------------------------------------------
+// q = rint(w * 2^s), round half to even, as dt_tiles.hip's weighted accumulation quantises: a weight that is negative,
+// not finite or over qmax is bad and counts as 0
+__device__ __forceinline__ fp_u64 ps_quant(double v, int sbits, fp_u64 qmax, bool &bad) {
+  if (!(v >= 0.0)) {
+    bad = true;
+    return 0ull;
+  }
+  const double q = rint(ldexp(v, sbits));
+  if (!(q <= (double)qmax)) {
+    bad = true;
+    return 0ull;
+  }
+  return (fp_u64)q;
+}
+// the starting sum of local cell l with word w: the cost of its move when that move stays in the tile, else 0 (an exit
+// cell's move is its record's).  Every weight inside the raster is looked at, so a bad one is found wherever it lies.
+__device__ __forceinline__ fp_u64 ps_cell_cost(const double *__restrict__ wt, uint32_t w, int64_t H, int64_t W,
+                                               int64_t y0, int64_t x0, int l, int sbits, fp_u64 qmax, bool &bad) {
+  const int64_t y = y0 + (l >> 6), x = x0 + (l & 63);
+  if (y >= H || x >= W) return 0ull;
+  const fp_u64 q = ps_quant(wt[y * W + x], sbits, qmax, bad);
+  return fp_kind(w) == FP_K_PTR ? q : 0ull;
+}
+// what a cell with the sum T gets (ok: its path stopped): T * 2^-s as float64 and -100, or T itself and -1
+__device__ __forceinline__ void ps_put(double *__restrict__ out, int64_t c, bool ok, fp_u64 T, int sbits) {
+  out[c] = ok ? ldexp((double)(int64_t)T, -sbits) : -100.0;
+}
+__device__ __forceinline__ void ps_put(int64_t *__restrict__ out, int64_t c, bool ok, fp_u64 T, int) {
+  out[c] = ok ? (int64_t)T : -1;
+}
+
+__global__ __launch_bounds__(256) void k_ps_dn_tile1(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                                     const double *__restrict__ wt, const uint8_t *__restrict__ stop,
+                                                     int64_t H, int64_t W, int64_t TX, int sbits, fp_u64 qmax,
+                                                     uint4 *__restrict__ rec, int *__restrict__ status) {
+  __shared__ uint32_t s_w[FP_T * FP_T];
+  __shared__ fp_u64 s_v[FP_T * FP_T];
+  const FpTile T = fp_tile(TX);
+  const int t = (int)threadIdx.x;
+  uint32_t w[FP_CPT];
+  fp_u64 v[FP_CPT];
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    w[k] = fp_init(fdr, dem, stop, H, W, T.y0, T.x0, l);
+    v[k] = ps_cell_cost(wt, w[k], H, W, T.y0, T.x0, l, sbits, qmax, bad);
+    s_w[l] = w[k];
+    s_v[l] = v[k];
+  }
+  if (bad && status) atomicOr(status, DT_STATUS_BAD_WEIGHT);
+  __syncthreads();
+  fp_fold_down<true>(s_w, s_v, w, v);
+  // one perimeter slot per lane: the sum from the cell up to, not including, the node its record points at
+  uint4 o = make_uint4(FP_FAILP, 0xFFFFFFFFu, 0u, 0u);
+  if (t < 252) {
+    const int l = fp_slot_cell(t);
+    const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
+    if (y < H && x < W) {
+      const uint32_t q = s_w[l];
+      const uint32_t kd = fp_kind(q), p = fp_ptr(q);
+      const fp_u64 sum = s_v[l];
+      if (kd == FP_K_EXIT && p == (uint32_t)l) {
+        int dy, dx;
+        dt_d8_delta(fdr[y * W + x], dy, dx);
+        bool again = false;
+        const fp_u64 own = ps_quant(wt[y * W + x], sbits, qmax, again);  // the move out of the tile
+        o = make_uint4(fp_node(y + dy, x + dx, TX), FP_OPEN, (uint32_t)own, (uint32_t)(own >> 32));
+      } else if (kd == FP_K_EXIT) {
+        o = make_uint4((uint32_t)(blockIdx.x * FP_SLOTS + fp_slot((int)(p >> 6), (int)(p & 63))), FP_OPEN,
+                       (uint32_t)sum, (uint32_t)(sum >> 32));
+      } else if (kd == FP_K_STOP) {
+        o = make_uint4(FP_RES, 0xFFFFFFFFu, (uint32_t)sum, (uint32_t)(sum >> 32));
+      }  // still a pointer: on or into an in-tile cycle, which never stops
+    }
+  }
+  rec[(int64_t)blockIdx.x * FP_SLOTS + t] = o;
+}
+
+// OUT double: T * 2^-s and -100; OUT int64_t: the plane of the longest fold, T and -1
+template <typename OUT>
+__global__ __launch_bounds__(256) void k_ps_dn_tile3(const uint8_t *__restrict__ fdr, const float *__restrict__ dem,
+                                                     const double *__restrict__ wt, const uint8_t *__restrict__ stop,
+                                                     int64_t H, int64_t W, int64_t TX, int sbits, fp_u64 qmax,
+                                                     const uint4 *__restrict__ rec, OUT *__restrict__ out) {
+  __shared__ uint32_t s_w[FP_T * FP_T];
+  __shared__ fp_u64 s_v[FP_T * FP_T];
+  __shared__ uint4 s_x[FP_SLOTS];
+  const FpTile T = fp_tile(TX);
+  const int t = (int)threadIdx.x;
+  uint32_t w[FP_CPT];
+  fp_u64 v[FP_CPT];
+  bool bad = false;  // pass 1 has reported it
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    w[k] = fp_init(fdr, dem, stop, H, W, T.y0, T.x0, l);
+    v[k] = ps_cell_cost(wt, w[k], H, W, T.y0, T.x0, l, sbits, qmax, bad);
+    s_w[l] = w[k];
+    s_v[l] = v[k];
+  }
+  s_x[t] = rec[(int64_t)blockIdx.x * FP_SLOTS + t];
+  __syncthreads();
+  fp_fold_down<true>(s_w, s_v, w, v);
+#pragma unroll
+  for (int k = 0; k < FP_CPT; k++) {
+    const int l = k * 256 + t;
+    const int64_t y = T.y0 + (l >> 6), x = T.x0 + (l & 63);
+    if (y >= H || x >= W) continue;
+    const uint32_t kd = fp_kind(w[k]), p = fp_ptr(w[k]);
+    bool ok = kd == FP_K_STOP;
+    fp_u64 sum = v[k];
+    if (kd == FP_K_EXIT) {
+      // the exit's record: its own move and everything after it, when that path stopped
+      const uint4 q = s_x[fp_slot((int)(p >> 6), (int)(p & 63))];
+      ok = q.x == FP_RES;
+      sum += (fp_u64)q.z | ((fp_u64)q.w << 32);
+    }
+    ps_put(out, y * W + x, ok, sum, sbits);
+  }
+}
+
+// ---- carving: carved =max(lowest, filled - cut) in float32, the DEM's own value on nodata -------------------------
 // filled NULL: no limit on the cut (carved = lowest).  carved may alias lowest.
 __global__ __launch_bounds__(256) void k_carve_blend(const float *__restrict__ dem, const float *__restrict__ filled,
                                                      const float *lowest, int64_t N, float cut, float *carved) {
@@ -507,15 +678,17 @@ static FpLayout fp_layout(int64_t H, int64_t W, bool upslope, void *scratch) {
 
 size_t dt_flowpath_scratch(int64_t H, int64_t W, int upslope) { return fp_layout(H, W, upslope != 0, nullptr).bytes; }
 
-template <bool MIN>
-static void fp_launch_up(hipStream_t s, const FpLayout &L, const uint8_t *fdr, const float *dem, const float *values,
-                         int64_t H, int64_t W, int R, float *value, int64_t *where) {
-  dim3 b(256), gt((unsigned)(L.TY * L.TX));
-  hipLaunchKernelGGL(k_fp_up_tile1<MIN>, gt, b, 0, s, fdr, dem, values, H, W, L.TX, L.uptr[0], L.S);
-  const dim3 gn(dt_capped_grid(L.NN, 8192));
+// the upslope fold of `fold` (FpExtreme, PsLongest) on the node buffers uptr[2], S and `flags` (zeroed)
+template <class P>
+static void fp_launch_up(hipStream_t s, int64_t tiles, int64_t TX, int64_t NN, uint32_t *const uptr[2], fp_u64 *S,
+                         uint32_t *flags, const uint8_t *fdr, const float *dem, const P &fold, int64_t H, int64_t W,
+                         int R) {
+  dim3 b(256), gt((unsigned)tiles);
+  hipLaunchKernelGGL(k_fp_up_tile1<P>, gt, b, 0, s, fdr, dem, fold, H, W, TX, uptr[0], S);
+  const dim3 gn(dt_capped_grid(NN, 8192));
   for (int r = 0; r < R; r++)
-    hipLaunchKernelGGL(k_fp_up_node, gn, b, 0, s, L.uptr[r & 1], L.uptr[(r & 1) ^ 1], L.S, L.NN, L.flags, r);
-  hipLaunchKernelGGL(k_fp_up_tile3<MIN>, gt, b, 0, s, fdr, dem, values, H, W, L.TX, L.S, value, where);
+    hipLaunchKernelGGL(k_fp_up_node, gn, b, 0, s, uptr[r & 1], uptr[(r & 1) ^ 1], S, NN, flags, r);
+  hipLaunchKernelGGL(k_fp_up_tile3<P>, gt, b, 0, s, fdr, dem, fold, H, W, TX, S);
 }
 
 template <bool MIN>
@@ -540,8 +713,11 @@ int dt_launch_flowpath_upslope(hipStream_t s, const uint8_t *fdr, const float *d
   DT_REQUIRE(L.NN < (1ll << 31), "too many tiles: node ids travel in 31 bits");
   const int R = std::max(2, dt_doubling_rounds(H * W));
   DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 64, s));
-  if (kind == 1) fp_launch_up<true>(s, L, fdr, dem, values, H, W, R, value, where);
-  else fp_launch_up<false>(s, L, fdr, dem, values, H, W, R, value, where);
+  const int64_t tiles = L.TY * L.TX;
+  if (kind == 1)
+    fp_launch_up(s, tiles, L.TX, L.NN, L.uptr, L.S, L.flags, fdr, dem, FpExtreme<true>{values, value, where}, H, W, R);
+  else
+    fp_launch_up(s, tiles, L.TX, L.NN, L.uptr, L.S, L.flags, fdr, dem, FpExtreme<false>{values, value, where}, H, W, R);
   return DT_OK;
 }
 
@@ -557,6 +733,79 @@ int dt_launch_flowpath_downstream(hipStream_t s, const uint8_t *fdr, const float
   DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 64, s));
   if (kind == 1) fp_launch_down<true>(s, L, fdr, dem, values, stop, H, W, R, value, where);
   else fp_launch_down<false>(s, L, fdr, dem, values, stop, H, W, R, value, where);
+  return DT_OK;
+}
+
+// path sums: the records of the downstream sum and, for the longest fold, the int64 plane of T.  The upslope fold
+// runs after the sum has been written out, so its 16 bytes per node lie over the first record buffer.
+struct PsLayout {
+  int64_t TY, TX, NN;
+  uint32_t *flags;  // [0, 64) the sum's rounds, [64, 128) the upslope fold's
+  int64_t *plane;
+  uint4 *rec[2];
+  uint32_t *uptr[2];
+  fp_u64 *S;
+  size_t bytes;
+};
+
+static PsLayout ps_layout(int64_t H, int64_t W, bool longest, void *scratch) {
+  PsLayout L = {};
+  L.TY = (H + FP_T - 1) / FP_T;
+  L.TX = (W + FP_T - 1) / FP_T;
+  L.NN = L.TY * L.TX * FP_SLOTS;
+  DtCarver c(scratch);
+  L.flags = c.take<uint32_t>(128);
+  if (longest) L.plane = c.take<int64_t>((size_t)(H * W));
+  for (int i = 0; i < 2; i++) L.rec[i] = c.take<uint4>((size_t)L.NN);
+  if (longest && scratch) {
+    L.uptr[0] = (uint32_t *)L.rec[0];
+    L.uptr[1] = L.uptr[0] + L.NN;
+    L.S = (fp_u64 *)L.rec[0] + L.NN;
+  }
+  L.bytes = c.bytes();
+  return L;
+}
+
+size_t dt_pathsum_scratch(int64_t H, int64_t W, int longest) { return ps_layout(H, W, longest != 0, nullptr).bytes; }
+
+template <typename OUT>
+static void ps_launch_down(hipStream_t s, const PsLayout &L, const uint8_t *fdr, const float *dem, const double *wt,
+                           const uint8_t *stop, int64_t H, int64_t W, int frac_bits, int R, OUT *out, int *status) {
+  const fp_u64 qmax = (1ull << 52) / (fp_u64)(H * W);
+  dim3 b(256), gt((unsigned)(L.TY * L.TX));
+  hipLaunchKernelGGL(k_ps_dn_tile1, gt, b, 0, s, fdr, dem, wt, stop, H, W, L.TX, frac_bits, qmax, L.rec[0], status);
+  const dim3 gn(dt_capped_grid(L.NN, 8192));
+  for (int r = 0; r < R; r++)
+    hipLaunchKernelGGL(k_ps_dn_node, gn, b, 0, s, L.rec[r & 1], L.rec[(r & 1) ^ 1], L.NN, L.flags, r);
+  hipLaunchKernelGGL(k_ps_dn_tile3<OUT>, gt, b, 0, s, fdr, dem, wt, stop, H, W, L.TX, frac_bits, qmax, L.rec[R & 1],
+                     out);
+}
+
+int dt_launch_pathsum_downstream(hipStream_t s, const uint8_t *fdr, const float *dem, const double *wt,
+                                 const uint8_t *stop, int64_t H, int64_t W, int frac_bits, void *scratch,
+                                 size_t scratch_bytes, double *out, int *status) {
+  if (H == 0 || W == 0 || !out) return DT_OK;
+  PsLayout L = ps_layout(H, W, false, scratch);
+  DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
+  DT_REQUIRE(L.NN < (1ll << 31), "too many tiles: node ids travel in 31 bits");
+  const int R = std::max(2, dt_doubling_rounds(H * W));
+  DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 128, s));
+  ps_launch_down(s, L, fdr, dem, wt, stop, H, W, frac_bits, R, out, status);
+  return DT_OK;
+}
+
+int dt_launch_pathsum_longest(hipStream_t s, const uint8_t *fdr, const float *dem, const double *wt, int64_t H,
+                              int64_t W, int frac_bits, void *scratch, size_t scratch_bytes, double *out,
+                              int *status) {
+  if (H == 0 || W == 0 || !out) return DT_OK;
+  PsLayout L = ps_layout(H, W, true, scratch);
+  DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
+  DT_REQUIRE(L.NN < (1ll << 31), "too many tiles: node ids travel in 31 bits");
+  const int R = std::max(2, dt_doubling_rounds(H * W));
+  DT_HIP(hipMemsetAsync(L.flags, 0, sizeof(uint32_t) * 128, s));
+  ps_launch_down(s, L, fdr, dem, wt, nullptr, H, W, frac_bits, R, L.plane, status);
+  fp_launch_up(s, L.TY * L.TX, L.TX, L.NN, L.uptr, L.S, L.flags + 64, fdr, dem, PsLongest{L.plane, out, frac_bits},
+               H, W, R);
   return DT_OK;
 }
 

@@ -259,6 +259,16 @@ int dt_launch_flowpath_downstream(hipStream_t s, const uint8_t *fdr, const float
                                   size_t scratch_bytes, float *value, int64_t *where);
 int dt_launch_carve_blend(hipStream_t s, const float *dem, const float *filled, const float *lowest, int64_t N,
                           float cut, float *carved);
+// weighted flow-path sums (dt_flowpath.hip; flowpath.py holds the definitions): the sum of q = rint(wt * 2^frac_bits)
+// along each path down to its terminal or first stop cell, and the longest such sum that ends at a cell, as float64
+// (-100: no value).  dem and stop may be NULL; out NULL: nothing runs.  Raises DT_STATUS_BAD_WEIGHT on `status` for a
+// weight outside dt_launch_flowacc_weighted's contract.  Nothing synchronises.  H * W < 2^31.
+size_t dt_pathsum_scratch(int64_t H, int64_t W, int longest);
+int dt_launch_pathsum_downstream(hipStream_t s, const uint8_t *fdr, const float *dem, const double *wt,
+                                 const uint8_t *stop, int64_t H, int64_t W, int frac_bits, void *scratch,
+                                 size_t scratch_bytes, double *out, int *status);
+int dt_launch_pathsum_longest(hipStream_t s, const uint8_t *fdr, const float *dem, const double *wt, int64_t H,
+                              int64_t W, int frac_bits, void *scratch, size_t scratch_bytes, double *out, int *status);
 
 // reaches (dt_reaches.hip): the rank of every link head (reach ids), reach / catchment rasters, per-reach channel
 // counts, stage tables and inundation depth; definitions in include/descriptools_hip.h.  Nothing synchronises.

@@ -216,6 +216,27 @@ int dt_flowpath_upslope(const uint8_t *fdr, const float *dem, const float *value
                         float *value, int64_t *where);
 int dt_flowpath_downstream(const uint8_t *fdr, const float *dem, const float *values, const uint8_t *stop, int64_t H,
                            int64_t W, int kind, float *value, int64_t *where);
+/* Net-new: weighted flow-path sums on dt_drainage's graph (travel time with w = step length / velocity).  The weights
+ * (float64, finite, >= 0) are quantised as dt_flowacc_weighted quantises them, q(c) = rint(w(c) * 2^frac_bits), round
+ * half to even, under the same bound H * W * rint(max w * 2^frac_bits) <= 2^52 (a path has fewer than H * W moves, so
+ * every sum converts to float64 exactly), and summed in unsigned 64-bit integers: exact, and independent of order,
+ * tiling and run.  q(c) is the cost of the move out of c; the weight of the cell where a path stops is never counted.
+ *   dt_flowpath_downstream_sum: T(target) = 0, T(c) = q(c) + T(succ(c)); the target is the path's terminal or, with
+ *                               `stop` (stop[i] != 0; on nodata: ignored), the first stop cell on the path, c included.
+ *                               out = T * 2^-frac_bits, and -100 exactly where dt_drainage (with stop as its pour
+ *                               points) gives target -100: on nodata, where the path enters a D8 cycle before it
+ *                               stops, and (with stop) where it reaches a terminal without meeting a stop cell.
+ *   dt_flowpath_upslope_longest: U(c) = the largest sum of q over the cells of s's path from s up to, not including,
+ *                               c, over every cell s whose path contains c (s = c: 0, so a source has 0); it equals
+ *                               M(c) - T(c), M the largest stop-less T upslope of c.  out = U * 2^-frac_bits, and -100
+ *                               wherever the stop-less T(c) is -100 -- wider than dt_upslope_length, which keeps the
+ *                               cells that drain into a cycle.
+ * dem and stop may be NULL; out NULL: nothing runs.  A frac_bits outside [-2200, 2200], a weight outside the contract
+ * and rasters of 2^31 cells or more are refused. */
+int dt_flowpath_downstream_sum(const uint8_t *fdr, const float *dem, const double *weights, const uint8_t *stop,
+                               int64_t H, int64_t W, int frac_bits, double *out);
+int dt_flowpath_upslope_longest(const uint8_t *fdr, const float *dem, const double *weights, int64_t H, int64_t W,
+                                int frac_bits, double *out);
 /* Net-new: depression carving (Soille 2004; the complete form of breaching).  fdr and filled as dt_d8_conditioned_f32
  * gives them for dem; lowest = dt_flowpath_upslope(fdr, dem, dem, kind 1): the lowest height above or at each cell on
  * the conditioned D8 tree, which is non-increasing along every edge and <= dem.  carved = lowest when max_cut is +inf,
@@ -710,6 +731,14 @@ int dt_dev_flowpath_downstream(dt_ctx *ctx, const uint8_t *fdr, const float *dem
                                int64_t *where);
 int dt_dev_carve_blend(dt_ctx *ctx, const float *dem, const float *filled, const float *lowest, int64_t rows,
                        int64_t cols, double max_cut, float *carved);
+/* dt_flowpath_downstream_sum and dt_flowpath_upslope_longest on device rasters (rows x cols), on the context's stream:
+ * they do not synchronise and take their scratch from the context (32 B per perimeter node of the 64 x 64 tiles, and
+ * 8 B per cell more for the longest fold).  dem and stop may be NULL; out NULL: nothing runs.  A weight outside the
+ * contract counts as 0 and raises DT_STATUS_BAD_WEIGHT (dt_ctx_status). */
+int dt_dev_flowpath_downstream_sum(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const double *weights,
+                                   const uint8_t *stop, int64_t rows, int64_t cols, int frac_bits, double *out);
+int dt_dev_flowpath_upslope_longest(dt_ctx *ctx, const uint8_t *fdr, const float *dem, const double *weights,
+                                    int64_t rows, int64_t cols, int frac_bits, double *out);
 /* dt_dinf_direction and dt_dinf_accumulate on device rasters, on the context's stream: neither synchronises.  fdr,
  * slope and w may be NULL.  dt_dev_dinf_accumulate enqueues round 0 (from the cells without donors) and rounds - 1
  * rounds that drain the queue of cells handed on (1 <= rounds <= 4096; a round that finds the queue empty returns at
