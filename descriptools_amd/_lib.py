@@ -64,6 +64,9 @@ _SIGS = {
     "dt_terrain": (ci, [c_f32p, i64, i64, f64, ci, f64, f64, f64] + [c_f32p] * 8),
     "dt_horizon": (ci, [c_f32p, i64, i64, f64, ci, ci, f64, c_u8p, c_u16p, c_f32p, c_f32p, c_f32p]),
     "dt_focal": (ci, [c_f32p, i64, i64, f64, ci, c_i32p, ci, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u16p]),
+    "dt_filter_extremes": (ci, [c_f32p, i64, i64, ci] + [c_f32p] * 5),
+    "dt_filter_rank": (ci, [c_f32p, i64, i64, ci, c_u16p, ci, c_f32p]),
+    "dt_filter_denoise": (ci, [c_f32p, i64, i64, f64, ci, f64, ci, f64, c_f32p]),
     "dt_mrvbf": (ci, [c_f32p, i64, i64, f64, f64, ci, f64, f64, c_f64p, c_f32p, c_f32p]),
     "dt_percentile": (ci, [c_f32p, i64, i64, ci, c_f32p, c_f32p]),
     "dt_coarsen": (ci, [c_f32p, i64, i64, f64, c_f64p, c_f32p, c_f32p]),
@@ -140,6 +143,9 @@ _SIGS = {
     "dt_dev_terrain": (ci, [vp, vp, i64, i64, f64, ci, f64, f64, f64] + [vp] * 8),
     "dt_dev_horizon": (ci, [vp, vp, i64, i64, f64, ci, ci, f64] + [vp] * 5),
     "dt_dev_focal": (ci, [vp, vp, i64, i64, f64, ci, c_i32p, ci] + [vp] * 6),
+    "dt_dev_filter_extremes": (ci, [vp, vp, i64, i64, ci] + [vp] * 5),
+    "dt_dev_filter_rank": (ci, [vp, vp, i64, i64, ci, c_u16p, ci, vp]),
+    "dt_dev_filter_denoise": (ci, [vp, vp, i64, i64, f64, ci, f64, ci, f64, vp]),
     "dt_dev_mrvbf": (ci, [vp, vp, i64, i64, f64, f64, ci, f64, f64, c_f64p, vp, vp]),
     "dt_dev_percentile": (ci, [vp, vp, i64, i64, ci, vp, vp]),
     "dt_dev_coarsen": (ci, [vp, vp, i64, i64, f64, c_f64p, vp, vp]),

@@ -966,6 +966,63 @@ extern "C" int dt_dev_focal(dt_ctx *c, const float *dem, int64_t H, int64_t W, d
                                 tpi, dev, scale, c->status));
 }
 
+// DEM filters (dt_filters.hip): the radius of the extremes; the radius and the rank table of the rank filter; the
+// radius, threshold cosine, iterations and largest change of the denoising
+static int dt_check_filter_extremes(int radius) {
+  DT_REQUIRE(radius >= 1 && radius <= DT_FILTER_RADIUS_MAX, "radius must lie in [1, 4096]");
+  return DT_OK;
+}
+static int dt_check_filter_rank(int radius, const uint16_t *table, int n_table) {
+  DT_REQUIRE(radius >= 1 && radius <= DT_FILTER_RANK_RADIUS_MAX, "radius must lie in [1, 16]");
+  const int cells = (2 * radius + 1) * (2 * radius + 1);
+  DT_REQUIRE(table && n_table == cells + 1, "the rank table must hold (2 radius + 1)^2 + 1 entries");
+  for (int n = 0; n <= cells; n++) DT_REQUIRE((int)table[n] < (n > 1 ? n : 1), "rank table: k[n] must be below n");
+  return DT_OK;
+}
+static int dt_check_filter_denoise(int radius, double cos_threshold, int iterations, double max_change) {
+  DT_REQUIRE(radius >= 1 && radius <= DT_FILTER_DENOISE_RADIUS_MAX, "radius must lie in [1, 16]");
+  DT_REQUIRE(cos_threshold > 0.0 && cos_threshold < 1.0, "cos_threshold must lie in (0, 1)");
+  DT_REQUIRE(iterations >= 1 && iterations <= DT_FILTER_DENOISE_ITERATIONS_MAX, "iterations must lie in [1, 32]");
+  DT_REQUIRE(std::isfinite(max_change) && max_change > 0.0, "max_change must be finite and > 0");
+  return DT_OK;
+}
+extern "C" int dt_dev_filter_extremes(dt_ctx *c, const float *dem, int64_t H, int64_t W, int radius, float *minimum,
+                                      float *maximum, float *range, float *opening, float *closing) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_filter_extremes(radius));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(minimum || maximum || range || opening || closing, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const size_t need = dt_filter_extremes_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_filter_extremes(c->stream, dem, H, W, radius, scr, need, minimum, maximum, range, opening,
+                                          closing));
+}
+extern "C" int dt_dev_filter_rank(dt_ctx *c, const float *dem, int64_t H, int64_t W, int radius, const uint16_t *table,
+                                  int n_table, float *out) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_filter_rank(radius, table, n_table));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(out, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  return d.done(dt_launch_filter_rank(c->stream, dem, H, W, radius, table, n_table, out));
+}
+extern "C" int dt_dev_filter_denoise(dt_ctx *c, const float *dem, int64_t H, int64_t W, double px, int radius,
+                                     double cos_threshold, int iterations, double max_change, float *out) {
+  DT_DEV(d, c, H, W, px);
+  DT_TRY(dt_check_filter_denoise(radius, cos_threshold, iterations, max_change));
+  if (H * W == 0) return DT_OK;
+  DT_REQUIRE(out, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  DT_REQUIRE(out != dem, "out must not be dem");
+  const size_t need = dt_filter_denoise_scratch(H, W);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_filter_denoise(c->stream, dem, H, W, px, radius, cos_threshold, iterations, max_change, scr,
+                                         need, out));
+}
+
 // lines of sight (dt_horizon.hip): the ranges of radius, skip and the flatness tangent
 static int dt_check_horizon(int radius, int skip, double flat_tan) {
   DT_REQUIRE(radius >= 1 && radius <= DT_HORIZON_RADIUS_MAX, "radius must lie in [1, 64]");
@@ -2601,6 +2658,58 @@ extern "C" int dt_focal(const float *dem, int64_t H, int64_t W, double origin, i
                  origin, frac_bits, (long long)dt_focal_qmax(radii[n_radii - 1]), (int)radii[n_radii - 1]);
     return DT_EINVAL;
   }
+  return hc.finish();
+}
+
+extern "C" int dt_filter_extremes(const float *dem, int64_t H, int64_t W, int radius, float *minimum, float *maximum,
+                                  float *range, float *opening, float *closing) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_TRY(dt_check_filter_extremes(radius));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(minimum || maximum || range || opening || closing, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  float *d_min = hc.out(minimum, n), *d_max = hc.out(maximum, n), *d_range = hc.out(range, n);
+  float *d_open = hc.out(opening, n), *d_close = hc.out(closing, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_filter_extremes(hc.c, d_dem, H, W, radius, d_min, d_max, d_range, d_open, d_close));
+  return hc.finish();
+}
+
+extern "C" int dt_filter_rank(const float *dem, int64_t H, int64_t W, int radius, const uint16_t *table, int n_table,
+                              float *out) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_TRY(dt_check_filter_rank(radius, table, n_table));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(out, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  float *d_out = hc.out(out, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_filter_rank(hc.c, d_dem, H, W, radius, table, n_table, d_out));
+  return hc.finish();
+}
+
+extern "C" int dt_filter_denoise(const float *dem, int64_t H, int64_t W, double px, int radius, double cos_threshold,
+                                 int iterations, double max_change, float *out) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_ws(H, W, px));
+  DT_TRY(dt_check_filter_denoise(radius, cos_threshold, iterations, max_change));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(out, "no output raster");
+  DT_REQUIRE(dem, "NULL raster");
+  const float *d_dem = hc.in(dem, n);
+  float *d_out = hc.out(out, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_filter_denoise(hc.c, d_dem, H, W, px, radius, cos_threshold, iterations, max_change, d_out));
   return hc.finish();
 }
 

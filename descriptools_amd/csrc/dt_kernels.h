@@ -368,6 +368,32 @@ int dt_launch_focal(hipStream_t s, const float *dem, int64_t H, int64_t W, doubl
                     const int32_t *radii, int n_radii, void *scratch, size_t scratch_bytes, int32_t *count,
                     float *mean, float *std_, float *tpi, float *dev, uint16_t *scale, int *status);
 
+// DEM filters (dt_filters.hip; filters.py holds the definition).  dt_launch_filter_extremes: the minimum, maximum and
+// range (maximum - minimum, float64 difference) of the valid heights of the clipped (2 radius + 1)^2 window, the opening
+// (the maximum of the minimum raster) and the closing (the minimum of the maximum raster); a NULL output is neither
+// computed nor stored, at least one is given; -100 where the cell's own height is not valid.  Three launches per window
+// pass (van Herk / Gil-Werman running extremes along rows, then columns), the planes in `scratch` (24 B per cell).
+// dt_launch_filter_rank: the height of index table[n] among the n valid heights of the window, sorted ascending
+// (table: (2 radius + 1)^2 + 1 entries in host memory, table[n] < max(n, 1)); one launch, no scratch.
+// dt_launch_filter_denoise: Sun et al.'s feature-preserving denoising -- unit normals, their thresholded weighted mean
+// over the window (cos_threshold = the cosine of the angle threshold), `iterations` Jacobi steps of the heights, each
+// change bounded by max_change against the input; 2 + iterations launches, 28 B per cell of `scratch`; `out` must not
+// be `dem`.  Nothing synchronises.  H * W < 2^31.
+#define DT_FILTER_RADIUS_MAX 4096
+#define DT_FILTER_RANK_RADIUS_MAX 16
+#define DT_FILTER_DENOISE_RADIUS_MAX 16
+#define DT_FILTER_DENOISE_ITERATIONS_MAX 32
+size_t dt_filter_extremes_scratch(int64_t H, int64_t W);
+int dt_launch_filter_extremes(hipStream_t s, const float *dem, int64_t H, int64_t W, int radius, void *scratch,
+                              size_t scratch_bytes, float *minimum, float *maximum, float *range, float *opening,
+                              float *closing);
+int dt_launch_filter_rank(hipStream_t s, const float *dem, int64_t H, int64_t W, int radius, const uint16_t *table,
+                          int n_table, float *out);
+size_t dt_filter_denoise_scratch(int64_t H, int64_t W);
+int dt_launch_filter_denoise(hipStream_t s, const float *dem, int64_t H, int64_t W, double px, int radius,
+                             double cos_threshold, int iterations, double max_change, void *scratch,
+                             size_t scratch_bytes, float *out);
+
 // Valley bottom and ridge top flatness (dt_mrvbf.hip; mrvbf.py holds the definition).  dt_launch_percentile: per cell
 // the shares of the valid cells of the clipped disc of `radius` that are strictly lower / strictly higher (a NULL
 // output is neither computed nor stored, at least one is given; -100 where the centre is not valid).
