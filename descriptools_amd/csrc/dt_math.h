@@ -219,6 +219,20 @@ __device__ __forceinline__ void dt_gfi_both_cell(float h, IT ar, IT f, double ex
   l_out = nod ? DT_NODATA : (float)l;
 }
 
+// The same with  ar_term = expo * dt_log_sel((double)ar, s_tab)  computed by the caller: A_river belongs to the river
+// cell a path ends on, so a caller that knows it per group of cells evaluates that logarithm once per group.  The
+// product is rounded before the sum (-ffp-contract=off; no fma here): the same bits as dt_gfi_both_cell.
+template <typename IT>
+__device__ __forceinline__ void dt_gfi_both_cell_term(float h, double ar_term, IT f, double expo, double c0,
+                                                      const DtLogEntry *s_tab, float &g_out, float &l_out) {
+  const double lh = c0 - dt_log_sel((double)h + 0.01, s_tab);
+  const double g = lh + ar_term;
+  const double l = lh + (f == 0 ? 0.0 : expo * dt_log_sel((double)f, s_tab));
+  const bool nod = h <= DT_NODATA;
+  g_out = nod ? DT_NODATA : (float)g;
+  l_out = nod ? DT_NODATA : (float)l;
+}
+
 // TI / MTI of one cell (topoindexes.py:234-295); float64 inside, float32 out.
 //   TI  = ln(A / t)   = ln A - ln t,      A = a * px^2 (a = fac, 0 -> 1), t = tan(slope + 0.01)
 //   MTI = ln(A^n / t) = n ln A - ln t

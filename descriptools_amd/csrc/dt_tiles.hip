@@ -2031,6 +2031,7 @@ struct FhSolveLds {
   uint8_t *kind;  // [NT]: first the river mask, then the end kinds
   uint32_t *lut;  // [256]
   int *ovf;
+  double *term;   // [PS], over fdr (dead once the solve has set its words up): n ln(A_river) per exit slot
 };
 template <bool RANKED, int VH, typename AccT, bool SOLVE>
 __device__ __forceinline__ bool fh_tile3_tile(unsigned long long *s_x, FhPay<AccT> &s_pay, DtLogEntry *s_tab,
@@ -2045,37 +2046,79 @@ __device__ __forceinline__ bool fh_tile3_tile(unsigned long long *s_x, FhPay<Acc
                                               const FhGfi &G) {
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;
+  // block-uniform: whole 64-cell rows of this tile are inside the core and every raster row is 16-byte
+  // aligned -> each lane handles 4 consecutive cells with 16-byte loads and stores
+  const bool vec = x0 + TW <= w.W && (w.ld & 3) == 0 && (!dem || ((uintptr_t)dem & 15) == 0) &&
+                   (!fdist || ((uintptr_t)fdist & 15) == 0) && (!idx32 || ((uintptr_t)idx32 & 15) == 0) &&
+                   (!idx64 || ((uintptr_t)idx64 & 15) == 0) && (!hand || ((uintptr_t)hand & 15) == 0) &&
+                   (!a_river || ((uintptr_t)a_river & 15) == 0) &&
+                   (!G.gfi || ((((uintptr_t)G.gfi | (uintptr_t)G.lnhlh | (uintptr_t)acc32) & 15) == 0));
+  // SOLVE, vec: the heights / own accumulation of the lane's group u of 4 cells (rows past the core: nodata / 0)
+  [[maybe_unused]] auto load_z4 = [&](int u) -> float4 {
+    const int c = 4 * (threadIdx.x + 256 * u), y = y0 + c / TW;
+    float4 z = make_float4(DT_NODATA, DT_NODATA, DT_NODATA, DT_NODATA);
+    if (dem && y < w.H) z = *reinterpret_cast<const float4 *>(dem + (long long)y * w.ld + x0 + c % TW);
+    return z;
+  };
+  [[maybe_unused]] auto load_f4 = [&](int u) -> int4 {
+    const int c = 4 * (threadIdx.x + 256 * u), y = y0 + c / TW;
+    int4 f = make_int4(0, 0, 0, 0);
+    if (G.gfi && y < w.H) f = *reinterpret_cast<const int4 *>(acc32 + (long long)y * w.ld + x0 + c % TW);
+    return f;
+  };
+  float4 z4_first = make_float4(DT_NODATA, DT_NODATA, DT_NODATA, DT_NODATA);
+  int4 f4_first = make_int4(0, 0, 0, 0);
+  int slot_ly = 0, slot_lx = 0;
+  if (threadIdx.x < PS) dt_cell_of_slot(threadIdx.x, slot_ly, slot_lx);
+  uint32_t slot_code = 0;  // SOLVE: the code of this lane's perimeter cell, read before L.fdr is given to L.term
+  bool has_river = true;   // SOLVE, block-uniform: false when no path of the tile can end on a river cell of its own
   if (SOLVE) {
     // the tile's codes and its river mask, 2 B/cell where the cache was 4: k_fh_tile1n's staging and solve
     const uint4 v_fdr = dt_tile_fetch16(fdr, w, y0, x0);
     const uint4 v_riv = dt_tile_fetch16(reinterpret_cast<const uint8_t *>(river), w, y0, x0);
+    if (vec) {  // the stream's first group: on its way behind the solve
+      z4_first = load_z4(0);
+      f4_first = load_f4(0);
+    }
     dt_tile_put16(L.fdr, v_fdr);
     dt_tile_put16(L.kind, v_riv);
     L.lut[threadIdx.x] = fh_lut_entry(threadIdx.x);
     if (threadIdx.x == 0) *L.ovf = 0;
-    __syncthreads();
+    // K_RIVER needs a river byte of 1: a tile whose river bytes are all 0 has none (a byte that is neither is rare
+    // and only sends the tile through the river arm)
+    has_river = __syncthreads_or((v_riv.x | v_riv.y | v_riv.z | v_riv.w) != 0u) != 0;
+    if (threadIdx.x < PS) slot_code = L.fdr[slot_ly * TW + slot_lx];
     uint32_t riv4[NT / 4 / 256];
 #pragma unroll
     for (int u = 0; u < NT / 4 / 256; u++) riv4[u] = *reinterpret_cast<const uint32_t *>(&L.kind[4 * (threadIdx.x + 256 * u)]);
     uint2 own[CPT / 2];
     if (!fh_tile1n_solve(L.fdr, L.w, L.kind, L.ovf, L.lut, riv4, w, y0, x0, own)) return false;
   }
-  // cell c's cached narrow word: from the cache, or from the word the solve left in LDS
+  // cell c's cached narrow word from the word the solve left in LDS (SOLVE: the ragged path only)
   auto solved = [&](uint32_t v, int c) -> uint32_t { return fh_narrow_word(v, (uint32_t)c, L.kind); };
   if (threadIdx.x < PS) {
-    int ly, lx;
-    dt_cell_of_slot(threadIdx.x, ly, lx);
+    const int ly = slot_ly, lx = slot_lx;
     int f = ly * TW + lx;
-    unsigned long long s = SOLVE ? fh_cache_unpack(solved(L.w[f], f)) : fh_cache_get(cache, wide, tile, f);
-    uint32_t sp = (uint32_t)(s >> 32);
+    // only exit cells (a finished word pointing at itself with kind EXIT / REXIT) are looked up
+    bool ex, rex;
+    if (SOLVE) {
+      // straight from the solve's word: fh_narrow_word's rule (not FN_DONE: a dead end at the cell itself)
+      const uint32_t v = L.w[f];
+      const bool self = (v & FN_DONE) != 0u && (v >> FN_PTR_SH) == (uint32_t)f;
+      const uint32_t kind = L.kind[f];
+      ex = self && kind == K_EXIT;
+      rex = self && kind == K_REXIT;
+    } else {
+      const uint32_t sp = (uint32_t)(fh_cache_get(cache, wide, tile, f) >> 32);
+      ex = sp == ((uint32_t)f | (K_EXIT << 12));
+      rex = sp == ((uint32_t)f | (K_REXIT << 12));
+    }
     unsigned long long o = fht_pack(FHT_DEAD, 0, FHT_DONE);
     float zr = DT_NODATA;
     AccT ar = -100;
-    // only exit cells (a finished word pointing at itself with kind EXIT / REXIT) are looked up
-    bool ex = sp == ((uint32_t)f | (K_EXIT << 12)), rex = sp == ((uint32_t)f | (K_REXIT << 12));
     if (ex || rex) {
       int dy, dx;
-      dt_d8_delta(SOLVE ? (uint32_t)L.fdr[f] : (uint32_t)fdr[(long long)(y0 + ly) * w.ld + x0 + lx], dy, dx);
+      dt_d8_delta(SOLVE ? slot_code : (uint32_t)fdr[(long long)(y0 + ly) * w.ld + x0 + lx], dy, dx);
       size_t node = ex ? (size_t)dt_node_of(y0 + ly + dy, x0 + lx + dx, tiles_x)
                        : (size_t)nnodes + (size_t)dt_perim_index(w.H, w.W, y0 + ly, x0 + lx);
       unsigned long long ns = nodes[node];
@@ -2111,14 +2154,10 @@ __device__ __forceinline__ bool fh_tile3_tile(unsigned long long *s_x, FhPay<Acc
     }
     s_x[threadIdx.x] = o;
     s_pay.set((int)threadIdx.x, zr, ar);
+    // GFI's  n ln(A_river)  belongs to the river cell: once per exit slot, not once per cell behind it (a dead
+    // slot's term is never used: its cells are nodata).  L.term lies over L.fdr, which nobody reads after the solve.
+    if (SOLVE && G.gfi) L.term[threadIdx.x] = G.expo * dt_log_sel((double)ar, s_tab);
   }
-  // block-uniform: whole 64-cell rows of this tile are inside the core and every raster row is 16-byte
-  // aligned -> each lane handles 4 consecutive cells with 16-byte loads and stores
-  const bool vec = x0 + TW <= w.W && (w.ld & 3) == 0 && (!dem || ((uintptr_t)dem & 15) == 0) &&
-                   (!fdist || ((uintptr_t)fdist & 15) == 0) && (!idx32 || ((uintptr_t)idx32 & 15) == 0) &&
-                   (!idx64 || ((uintptr_t)idx64 & 15) == 0) && (!hand || ((uintptr_t)hand & 15) == 0) &&
-                   (!a_river || ((uintptr_t)a_river & 15) == 0) &&
-                   (!G.gfi || ((((uintptr_t)G.gfi | (uintptr_t)G.lnhlh | (uintptr_t)acc32) & 15) == 0));
   const double dcard = px, ddiag = px * sqrt(2.0);
   struct CellOut {
     float fd, h;
@@ -2179,6 +2218,100 @@ __device__ __forceinline__ bool fh_tile3_tile(unsigned long long *s_x, FhPay<Acc
     o.ar = ok ? pa : (AccT)-100;
     return o;
   };
+  if constexpr (SOLVE) {
+    if (vec) {
+      // The solving form's stream: a cell goes from the solve's word and the end kind straight to its outputs, on
+      // one straight-line path.  The exit-slot look-up (resolved word, payload, GFI term) is made for every cell --
+      // dt_slot_of's arithmetic gives a slot in range for any cell -- and `ok` selects.  Only a tile with river
+      // cells (has_river, block-uniform) compiles the K_RIVER arm in: its two gathers and its own logarithm.
+      auto cell = [&](auto RIV, uint32_t v, float z, int32_t fown, float &fd, int32_t &i32, float &h, int32_t &ar,
+                      float &g, float &l) {
+        const bool done = (v & FN_DONE) != 0u;  // not done: a dead end (fh_narrow_word)
+        const uint32_t e = v >> FN_PTR_SH, ey = e / TW, ex = e % TW;
+        const uint32_t kind = L.kind[e];
+        const uint32_t slot = ey == 0u ? ex
+                                       : (ey == TH - 1u ? TW + ex
+                                                        : (ex == 0u ? 2u * TW - 1u + ey : 2u * TW + TH - 3u + ey));
+        const unsigned long long xs = s_x[slot];
+        uint32_t ridx = (uint32_t)(xs >> 32);
+        uint32_t nc = (v & 0xFFu) + (uint32_t)(xs & 0x7FFFu), nd = ((v >> 9) & 0xFFu) + (uint32_t)((xs >> 16) & 0xFFFFu);
+        bool ok = done && (kind == K_EXIT || kind == K_REXIT) && ridx != FHT_DEAD && nc + nd <= FHT_CAP;  // flowhand.py:834-837
+        float pz;
+        int32_t pa;
+        s_pay.get((int)slot, pz, pa);
+        double term = G.gfi ? L.term[slot] : 0.0;
+        if (decltype(RIV)::value) {
+          if (done && kind == K_RIVER) {
+            // the path ends on a river cell of this tile: its own height / accumulation (a gather inside the
+            // tile's own rows)
+            ok = true;
+            nc = v & 0xFFu;
+            nd = (v >> 9) & 0xFFu;
+            ridx = (uint32_t)((y0 + (int)ey) * w.W + x0 + (int)ex);
+            const long long ro = (long long)(y0 + (int)ey) * w.ld + x0 + (int)ex;
+            pz = dem ? dem[ro] : DT_NODATA;
+            pa = acc32 ? acc32[ro] : -100;
+            if (G.gfi) term = G.expo * dt_log_sel((double)pa, s_tab);
+          }
+        }
+        fd = ok ? (float)(dcard * (double)nc + ddiag * (double)nd) : DT_NODATA;
+        i32 = ok ? (int32_t)ridx : -100;
+        h = DT_NODATA;
+        if (z != DT_NODATA && ok) {  // flowhand.py:436
+          h = z - pz;
+          if (h < 0.0f && h != DT_NODATA) h = 0.0f;  // flowhand.py:438
+        }
+        ar = ok ? pa : -100;
+        if (G.gfi) dt_gfi_both_cell_term(h, term, fown, G.expo, G.c0, s_tab, g, l);
+      };
+      auto stream = [&](auto RIV) {
+        // a group's heights and own accumulation are on their way while the group before it is computed (group 0's:
+        // since before the solve)
+        float4 z4 = z4_first;
+        int4 f4 = f4_first;
+#pragma unroll 1
+        for (int u = 0; u < NT / 4 / 256; u++) {
+          const int c = 4 * (threadIdx.x + 256 * u);
+          const int y = y0 + c / TW;
+          const long long o = (long long)y * w.ld + x0 + c % TW;
+          const uint4 v = *reinterpret_cast<const uint4 *>(&L.w[c]);
+          const float4 z4_cur = z4;
+          int4 f4_cur = f4;
+          if (u + 1 < NT / 4 / 256) {
+            z4 = load_z4(u + 1);
+            f4 = load_f4(u + 1);
+          }
+          if (u == 0) __syncthreads();  // s_x / s_pay / L.term
+          // (a use on every path: without it the wait for a load whose only use is behind `if (G.gfi)` lands on the
+          // loop's head, where it also waits for the stores of the group before)
+          asm volatile("" : "+v"(f4_cur.x), "+v"(f4_cur.y), "+v"(f4_cur.z), "+v"(f4_cur.w));
+          if (y >= w.H) continue;
+          float4 fd, hh, g, l;
+          int4 ix, ar;
+          cell(RIV, v.x, z4_cur.x, f4_cur.x, fd.x, ix.x, hh.x, ar.x, g.x, l.x);
+          __builtin_amdgcn_sched_barrier(0);  // one cell after the other: four float64 chains at once cost registers
+          cell(RIV, v.y, z4_cur.y, f4_cur.y, fd.y, ix.y, hh.y, ar.y, g.y, l.y);
+          __builtin_amdgcn_sched_barrier(0);
+          cell(RIV, v.z, z4_cur.z, f4_cur.z, fd.z, ix.z, hh.z, ar.z, g.z, l.z);
+          __builtin_amdgcn_sched_barrier(0);
+          cell(RIV, v.w, z4_cur.w, f4_cur.w, fd.w, ix.w, hh.w, ar.w, g.w, l.w);
+          // every output byte is written once and not read again by this kernel: non-temporal stores
+          if (fdist) fh_store4(fdist + o, fd.x, fd.y, fd.z, fd.w);
+          if (idx32) fh_store4(idx32 + o, ix.x, ix.y, ix.z, ix.w);
+          if (hand) fh_store4(hand + o, hh.x, hh.y, hh.z, hh.w);
+          if (a_river) fh_store4(a_river + o, ar.x, ar.y, ar.z, ar.w);
+          if (G.gfi) {
+            fh_store4(G.gfi + o, g.x, g.y, g.z, g.w);
+            fh_store4(G.lnhlh + o, l.x, l.y, l.z, l.w);
+          }
+          __builtin_amdgcn_sched_barrier(0);  // finish this group of 4 cells before the next one starts
+        }
+      };
+      if (has_river) stream(std::integral_constant<bool, true>{});
+      else stream(std::integral_constant<bool, false>{});
+      return true;
+    }
+  }
   if (vec) {
     // 4 groups of 4 cells per lane, two at a time: 24 registers of loads in flight per lane and twice the
     // waves per SIMD instead of 48 and half of them
@@ -2333,7 +2466,7 @@ __global__ __launch_bounds__(256, 5) void k_fh_tile3_solve(const uint8_t *__rest
   if (G.gfi) dt_math_stage(G.tab, s_tab);
   const int tile = dt_tile_of_block((int)blockIdx.x, (int)gridDim.x);
   const bool ok = fh_tile3_tile<false, 1, int32_t, true>(
-      s_x, s_pay, s_tab, FhSolveLds{s_fdr, s_w, s_kind, s_lut, &s_ovf}, river, tile, fdr, dem, acc32, w, tiles_x, nnodes,
+      s_x, s_pay, s_tab, FhSolveLds{s_fdr, s_w, s_kind, s_lut, &s_ovf, reinterpret_cast<double *>(s_fdr)}, river, tile, fdr, dem, acc32, w, tiles_x, nnodes,
       nodes, nullptr, false, FhRemote{nullptr, nullptr, nullptr}, px, fdist, idx32, nullptr, hand, a_river, G);
   if (!ok && threadIdx.x == 0) cache_wide[tile] = 2;
 }
