@@ -56,6 +56,17 @@ def positive(v, what):
     return p
 
 
+def at_least(v, what, lo, strict=False):
+    """v as a float; ValueError unless it is a number (not a bool), finite and >= lo (`strict`: > lo)"""
+    try:
+        p = math.nan if isinstance(v, (bool, np.bool_)) else float(v)
+    except (TypeError, ValueError):
+        p = math.nan
+    if not (math.isfinite(p) and (p > lo if strict else p >= lo)):
+        raise ValueError("%s must be a finite number %s %g, not %r" % (what, ">" if strict else ">=", lo, v))
+    return p
+
+
 def _is_int(v):
     return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 

@@ -72,6 +72,9 @@ _SIGS = {
     "dt_coarsen": (ci, [c_f32p, i64, i64, f64, c_f64p, c_f32p, c_f32p]),
     "dt_proximity": (ci, [c_i8p, c_f32p, i64, i64, f64, c_f32p, c_i64p]),
     "dt_cost_distance": (ci, [c_f32p, c_i8p, i64, i64, f64, ci, ci, c_f64p, c_i64p, c_u8p, c_i64p]),
+    "dt_wetness_suction": (ci, [c_f32p, i64, i64, f64, f64, f64, f64, c_f32p]),
+    "dt_wetness_modified_area": (ci, [c_f64p, c_f32p, i64, i64, ci, c_f64p, c_i64p]),
+    "dt_wetness_saga": (ci, [c_f64p, c_f32p, i64, i64, f64, f64, f64, f64, ci, c_f32p, c_f64p, c_f32p, c_i64p]),
     "dt_harmonic": (ci, [c_f32p, c_i8p, c_i8p, i64, i64, f64, ci, c_f64p, c_i64p]),
     "dt_inundation": (ci, [c_f32p, c_f32p, c_f32p, i64, i64, c_f64p, ci, c_i64p, c_f64p, c_f64p, ci, ci, i64, i64, ci,
                            c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i64p]),
@@ -137,6 +140,9 @@ _SIGS = {
     "dt_dev_mfd_accumulate": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
     "dt_dev_mfd_accumulate_info": (ci, [vp, c_i64p]),
     "dt_dev_cost_distance": (ci, [vp, vp, vp, i64, i64, f64, ci, ci, ci, vp, vp, vp]),
+    "dt_dev_wetness_suction": (ci, [vp, vp, i64, i64, f64, f64, f64, f64, vp]),
+    "dt_dev_wetness_modified_area": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
+    "dt_dev_wetness_index": (ci, [vp, vp, vp, i64, i64, f64, f64, vp]),
     "dt_dev_harmonic": (ci, [vp, vp, vp, vp, i64, i64, f64, ci, vp, vp]),
     "dt_dev_inundation": (ci, [vp, vp, vp, vp, i64, i64, c_f64p, ci, vp, vp, vp, ci, ci, i64, i64, vp, vp, vp, vp, vp,
                                vp]),

@@ -806,6 +806,49 @@ extern "C" int dt_dev_cost_distance(dt_ctx *c, const float *friction, const int8
                                         scr, need, cost, indices, backlink, c->status));
 }
 
+// SAGA wetness index: what both tiers require of the suction's parameters; `index`: the offset and the minimum must
+// not both be zero (tan b > 0)
+static int dt_check_wetness(double t, double weight, double offset, double minimum, bool suction, bool index) {
+  if (suction) {
+    DT_REQUIRE(std::isfinite(t) && t > 1.0, "t must be finite and > 1");
+    DT_REQUIRE(std::isfinite(weight) && weight > 0.0, "slope_weight must be finite and > 0");
+  }
+  DT_REQUIRE(std::isfinite(offset) && offset >= 0.0, "slope_offset must be finite and >= 0");
+  DT_REQUIRE(std::isfinite(minimum) && minimum >= 0.0, "slope_min must be finite and >= 0");
+  DT_REQUIRE(!index || offset + minimum > 0.0, "slope_offset and slope_min must not both be 0");
+  return DT_OK;
+}
+
+extern "C" int dt_dev_wetness_suction(dt_ctx *c, const float *slope, int64_t H, int64_t W, double t, double weight,
+                                      double offset, double minimum, float *suction) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_wetness(t, weight, offset, minimum, true, false));
+  DT_REQUIRE((slope && suction) || H * W == 0, "NULL raster");
+  return d.done(dt_launch_wetness_suction(c->stream, slope, H * W, std::log(t), weight, offset, minimum, suction));
+}
+
+extern "C" int dt_dev_wetness_modified_area(dt_ctx *c, const double *area, const float *suction, int64_t H, int64_t W,
+                                            int visit_limit, int rounds, double *modified) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
+  DT_REQUIRE(rounds >= 1 && rounds <= DT_WETNESS_ROUNDS_MAX, "rounds must lie in [1, 4096]");
+  DT_REQUIRE((area && suction && modified) || H * W == 0, "NULL raster");
+  if (H * W == 0) return DT_OK;
+  const size_t need = dt_wetness_scratch(H, W, 0, 0);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_wetness_area(c->stream, area, suction, H, W, visit_limit, 1, rounds, 1, scr, need, modified,
+                                       c->status));
+}
+
+extern "C" int dt_dev_wetness_index(dt_ctx *c, const double *modified, const float *slope, int64_t H, int64_t W,
+                                    double offset, double minimum, float *swi) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_wetness(0.0, 0.0, offset, minimum, false, true));
+  DT_REQUIRE((modified && slope && swi) || H * W == 0, "NULL raster");
+  return d.done(dt_launch_wetness_index(c->stream, modified, slope, H * W, offset, minimum, swi));
+}
+
 // harmonic interpolation: the shape rule of dt_check_ws, and what both tiers require of tol and the budget
 static int dt_check_harmonic(double tol, int max_rounds) {
   DT_REQUIRE(std::isfinite(tol) && tol > 0.0, "tol must be finite and > 0");
@@ -2895,6 +2938,111 @@ extern "C" int dt_cost_distance(const float *friction, const int8_t *sources, in
     info4[2] = cnt[1];
     info4[3] = (int64_t)cnt[2] | (int64_t)cnt[3] << 32;
   }
+  return DT_OK;
+}
+
+// The modified area of device rasters within a host call: batches of rounds until a quiet one (the batches of
+// dt_dinf_distance_down), then the fills and the counts -> cnt4 = {rounds that raised something, raised cells, tile
+// visits, 0}.  Synchronises.
+static int host_wetness_area(HostCall &hc, const double *d_a, const float *d_s, int64_t H, int64_t W, int visit_limit,
+                             char *scr, size_t need, double *d_m, int64_t *cnt4) {
+  const uint32_t *ctl = dt_wetness_ctl(scr, H, W);
+  uint32_t flags[DT_DINF_DIST_BATCH_MAX];
+  int64_t rounds = 0;
+  int batch = DT_DINF_DIST_BATCH0;
+  for (int start = 1;; start = 0) {
+    DT_TRY(dt_launch_wetness_area(hc.c->stream, d_a, d_s, H, W, visit_limit, start, batch, 0, scr, need, d_m, nullptr));
+    DT_TRY(hc.download(flags, ctl, (size_t)batch));
+    DT_HIP(hipStreamSynchronize(hc.c->stream));
+    int used = 0;
+    while (used < batch && flags[used]) used++;
+    rounds += used;
+    if (used < batch) break;  // a quiet round: nothing is left to raise
+    if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
+  }
+  DT_TRY(dt_launched(dt_launch_wetness_area(hc.c->stream, d_a, d_s, H, W, visit_limit, 0, 0, 1, scr, need, d_m,
+                                            nullptr)));
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  DT_TRY(hc.download(cnt, ctl + DT_WETNESS_CTL_COUNTS, 4));
+  DT_HIP(hipStreamSynchronize(hc.c->stream));
+  cnt4[0] = rounds;
+  cnt4[1] = cnt[0];
+  cnt4[2] = (int64_t)cnt[2] | (int64_t)cnt[3] << 32;
+  cnt4[3] = 0;
+  return DT_OK;
+}
+
+extern "C" int dt_wetness_suction(const float *slope, int64_t H, int64_t W, double t, double weight, double offset,
+                                  double minimum, float *suction) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_TRY(dt_check_wetness(t, weight, offset, minimum, true, false));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(slope && suction, "NULL raster");
+  const float *d_sl = hc.in(slope, n);
+  float *d_s = hc.out(suction, n);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launched(dt_launch_wetness_suction(hc.c->stream, d_sl, (int64_t)n, std::log(t), weight, offset, minimum,
+                                               d_s)));
+  return hc.finish();
+}
+
+extern "C" int dt_wetness_modified_area(const double *area, const float *suction, int64_t H, int64_t W,
+                                        int visit_limit, double *modified, int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(area && suction && modified, "NULL raster");
+  const double *d_a = hc.in(area, n);
+  const float *d_s = hc.in(suction, n);
+  double *d_m = hc.out(modified, n);
+  const size_t need = dt_wetness_scratch(H, W, 0, 0);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  int64_t cnt4[4];
+  DT_TRY(host_wetness_area(hc, d_a, d_s, H, W, visit_limit, scr, need, d_m, cnt4));
+  DT_TRY(hc.finish());
+  if (info4) memcpy(info4, cnt4, sizeof(cnt4));
+  return DT_OK;
+}
+
+extern "C" int dt_wetness_saga(const double *area, const float *slope, int64_t H, int64_t W, double t, double weight,
+                               double offset, double minimum, int visit_limit, float *swi, double *modified,
+                               float *suction, int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_TRY(dt_check_wetness(t, weight, offset, minimum, true, true));
+  DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(area && slope && swi, "NULL raster");
+  const double *d_a = hc.in(area, n);
+  const float *d_sl = hc.in(slope, n);
+  float *d_w = hc.out(swi, n);
+  // the planes the caller does not ask for live in the scratch; nothing crosses PCIe between the three stages
+  double *d_m = hc.out(modified, n);
+  float *d_s = hc.out(suction, n);
+  const int own_s = d_s == nullptr, own_m = d_m == nullptr;
+  const size_t need = dt_wetness_scratch(H, W, own_s, own_m);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  if (own_s) d_s = dt_wetness_suction_plane(scr, H, W);
+  if (own_m) d_m = dt_wetness_m_plane(scr, H, W, own_s);
+  DT_TRY(dt_launched(dt_launch_wetness_suction(hc.c->stream, d_sl, (int64_t)n, std::log(t), weight, offset, minimum,
+                                               d_s)));
+  int64_t cnt4[4];
+  DT_TRY(host_wetness_area(hc, d_a, d_s, H, W, visit_limit, scr, need, d_m, cnt4));
+  DT_TRY(dt_launched(dt_launch_wetness_index(hc.c->stream, d_m, d_sl, (int64_t)n, offset, minimum, d_w)));
+  DT_TRY(hc.finish());
+  if (info4) memcpy(info4, cnt4, sizeof(cnt4));
   return DT_OK;
 }
 

@@ -457,6 +457,29 @@ int dt_launch_cost_distance(hipStream_t s, const float *friction, const int8_t *
 // the control words in `scratch` (DT_COST_CTL_COUNTS + 8 x uint32 on the device)
 const uint32_t *dt_cost_distance_ctl(void *scratch, int64_t H, int64_t W, int alloc);
 
+// SAGA wetness index (dt_wetness.hip; wetness.py holds the definition).  suction: s of a slope raster (log_t = ln t,
+// taken by the caller).  index: swi = float32(log(M / tan(b))) from a modified area.  area: M = the least solution of
+// M(v) = max(A(v), fl(s(v) * max over the valid neighbours of M)), -100 on nodata.  The state lives in `modified` and in
+// `scratch`: start != 0 sets it up, `rounds` (0..DT_WETNESS_ROUNDS_MAX) rounds of tile visits follow, round r raising
+// control word r when it raised something (a round that follows a quiet one returns at once), finish != 0 writes the
+// fills and counts the raised cells and the tile visits of the call (64 bits) into control words DT_WETNESS_CTL_COUNTS
+// + 0 and + 2-3; with rounds in the same call it raises DT_STATUS_NOT_CONVERGED on `status` (may be NULL) when the last
+// round still raised something.  The scratch may carry a suction plane and an M plane behind the control block (the
+// composite call's).  visit_limit as for the cost distance.  Nothing synchronises.  H * W < 2^31.
+#define DT_WETNESS_ROUNDS_MAX 4096  // rounds one launcher call takes at most: its flag words
+#define DT_WETNESS_CTL_COUNTS DT_WETNESS_ROUNDS_MAX
+size_t dt_wetness_scratch(int64_t H, int64_t W, int suction_plane, int m_plane);
+const uint32_t *dt_wetness_ctl(void *scratch, int64_t H, int64_t W);
+float *dt_wetness_suction_plane(void *scratch, int64_t H, int64_t W);
+double *dt_wetness_m_plane(void *scratch, int64_t H, int64_t W, int suction_plane);
+int dt_launch_wetness_suction(hipStream_t s, const float *slope, int64_t N, double log_t, double weight, double offset,
+                              double minimum, float *suction);
+int dt_launch_wetness_index(hipStream_t s, const double *modified, const float *slope, int64_t N, double offset,
+                            double minimum, float *swi);
+int dt_launch_wetness_area(hipStream_t s, const double *area, const float *suction, int64_t H, int64_t W,
+                           int visit_limit, int start, int rounds, int finish, void *scratch, size_t scratch_bytes,
+                           double *modified, int *status);
+
 // Harmonic interpolation (dt_harmonic.hip; harmonic.py holds the definition): out = the discrete harmonic function on
 // the domain with the fixed cells held (fixed == 1 and a finite value; domain NULL: everywhere), NaN outside the domain.
 // Nested iteration on a pyramid by 2 whose level 0 is `out` itself; the other levels, the masks, the flags and the key
