@@ -796,7 +796,7 @@ extern "C" int dt_dev_cost_distance(dt_ctx *c, const float *friction, const int8
   DT_DEV(d, c, H, W, px);
   DT_REQUIRE(connectivity == 4 || connectivity == 8, "connectivity is 4 or 8");
   DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
-  DT_REQUIRE(rounds >= 1 && rounds <= DT_COST_ROUNDS_MAX, "rounds must lie in [1, 4096]");
+  DT_REQUIRE(rounds >= 1 && rounds <= DT_TILE_ROUNDS_MAX, "rounds must lie in [1, 4096]");
   DT_REQUIRE((friction && sources && cost) || H * W == 0, "NULL raster");
   if (H * W == 0) return DT_OK;
   const size_t need = dt_cost_distance_scratch(H, W, indices != nullptr);
@@ -831,7 +831,7 @@ extern "C" int dt_dev_wetness_modified_area(dt_ctx *c, const double *area, const
                                             int visit_limit, int rounds, double *modified) {
   DT_DEV(d, c, H, W, 1.0);
   DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
-  DT_REQUIRE(rounds >= 1 && rounds <= DT_WETNESS_ROUNDS_MAX, "rounds must lie in [1, 4096]");
+  DT_REQUIRE(rounds >= 1 && rounds <= DT_TILE_ROUNDS_MAX, "rounds must lie in [1, 4096]");
   DT_REQUIRE((area && suction && modified) || H * W == 0, "NULL raster");
   if (H * W == 0) return DT_OK;
   const size_t need = dt_wetness_scratch(H, W, 0, 0);
@@ -852,7 +852,7 @@ extern "C" int dt_dev_wetness_index(dt_ctx *c, const double *modified, const flo
 // harmonic interpolation: the shape rule of dt_check_ws, and what both tiers require of tol and the budget
 static int dt_check_harmonic(double tol, int max_rounds) {
   DT_REQUIRE(std::isfinite(tol) && tol > 0.0, "tol must be finite and > 0");
-  DT_REQUIRE(max_rounds >= 1 && max_rounds <= DT_HARMONIC_ROUNDS_MAX, "max_rounds must lie in [1, 4096]");
+  DT_REQUIRE(max_rounds >= 1 && max_rounds <= DT_TILE_ROUNDS_MAX, "max_rounds must lie in [1, 4096]");
   return DT_OK;
 }
 // DT_DBG_HARMONIC_LEVELS=n (n >= 1): the pyramid has n levels at most (benchmarks; 0: as many as the raster needs)
@@ -2824,10 +2824,26 @@ extern "C" int dt_coarsen(const float *dem, int64_t H, int64_t W, double px, con
   return hc.finish();
 }
 
-// rounds of tile visits between two looks at their flags: 8, 16, 32, then 64 (a round that follows a quiet one costs a
-// few microseconds; a path that winds through many tiles wants few host round trips per round)
-// (DT_DINF_DIST_BATCH_MAX, dt_kernels.h: what one launcher call takes)
-#define DT_DINF_DIST_BATCH0 8
+// Batches of tile rounds (dt_tile_rounds.h) until a quiet one: launch(start, batch) enqueues `batch` rounds, round r of
+// them raising the device word d_flags[r]; 8, 16, 32, then 64 rounds between two looks at the flags (a round that
+// follows a quiet one costs a few microseconds; a path that winds through many tiles wants few host round trips per
+// round).  *rounds counts the rounds that did something, also while the batches run (launch may look).  Synchronises.
+template <typename Launch>
+static int host_tile_rounds(HostCall &hc, const uint32_t *d_flags, int64_t *rounds, Launch launch) {
+  uint32_t flags[DT_TILE_ROUNDS_BATCH_MAX];
+  *rounds = 0;
+  int batch = DT_TILE_ROUNDS_BATCH0;
+  for (int start = 1;; start = 0) {
+    DT_TRY(launch(start, batch));
+    DT_TRY(hc.download(flags, d_flags, (size_t)batch));
+    DT_HIP(hipStreamSynchronize(hc.c->stream));
+    int used = 0;
+    while (used < batch && flags[used]) used++;
+    *rounds += used;
+    if (used < batch) return DT_OK;  // a quiet round: nothing is left to do
+    if (batch < DT_TILE_ROUNDS_BATCH_MAX) batch *= 2;
+  }
+}
 // A private diagnostic, not part of the C ABI (not in descriptools_hip.h, not bound by _lib): the tile visits of the
 // last dt_dinf_distance_down call that THIS THREAD made and that succeeded -- per thread, so that another thread's
 // call cannot land between a call and the question.  tools/dinf_distance_bench.py asks it by name.
@@ -2859,25 +2875,16 @@ extern "C" int dt_dinf_distance_down(const float *angle, const int8_t *river, co
   DT_TRY(hc.rc);
   int32_t st = 0;
   DT_TRY(dt_ctx_status(hc.c, &st));  // this call's status only
-  uint32_t flags[DT_DINF_DIST_BATCH_MAX];
-  int64_t rounds = 0;
-  int batch = DT_DINF_DIST_BATCH0;
-  for (int start = 1;; start = 0) {
-    DT_TRY(dt_launch_dinf_distance(hc.c->stream, d_a, d_r, d_z, H, W, px, stat, check_edges, visit_limit, start,
-                                   batch, 0, scr, need, d_h, d_v, d_s, hc.c->status));
-    DT_TRY(hc.download(flags, dt_dinf_distance_ctl(scr, H, W), (size_t)batch));
-    DT_HIP(hipStreamSynchronize(hc.c->stream));
-    int used = 0;
-    while (used < batch && flags[used]) used++;
-    rounds += used;
-    if (used < batch) break;  // a quiet round: nothing is left that can settle
+  int64_t rounds;
+  DT_TRY(host_tile_rounds(hc, dt_dinf_distance_ctl(scr, H, W), &rounds, [&](int start, int batch) -> int {
     DT_REQUIRE(rounds <= (int64_t)n, "more rounds than cells (a defect: every round but the last settles a cell)");
-    if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
-  }
+    return dt_launch_dinf_distance(hc.c->stream, d_a, d_r, d_z, H, W, px, stat, check_edges, visit_limit, start, batch,
+                                   0, scr, need, d_h, d_v, d_s, hc.c->status);
+  }));
   DT_TRY(dt_launched(dt_launch_dinf_distance(hc.c->stream, d_a, d_r, d_z, H, W, px, stat, check_edges, visit_limit, 0,
                                              0, 1, scr, need, d_h, d_v, d_s, hc.c->status)));
   uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
-  DT_TRY(hc.download(cnt, dt_dinf_distance_ctl(scr, H, W) + DT_DINF_DIST_BATCH_MAX, 6));
+  DT_TRY(hc.download(cnt, dt_dinf_distance_ctl(scr, H, W) + DT_TILE_ROUNDS_BATCH_MAX, 6));
   DT_TRY(dt_ctx_status(hc.c, &st));  // (synchronises)
   DT_REQUIRE(!(st & DT_STATUS_BAD_ANGLE), "an angle is neither -1, -100 nor in [0, float32(2 pi)]");
   if (info4) {
@@ -2890,7 +2897,6 @@ extern "C" int dt_dinf_distance_down(const float *angle, const int8_t *river, co
   return hc.finish();
 }
 
-// (the batches of dt_dinf_distance_down: 8, 16, 32, then 64 rounds between two looks at the flags)
 extern "C" int dt_cost_distance(const float *friction, const int8_t *sources, int64_t H, int64_t W, double px,
                                 int connectivity, int visit_limit, double *cost, int64_t *indices, uint8_t *backlink,
                                 int64_t *info4) {
@@ -2913,20 +2919,11 @@ extern "C" int dt_cost_distance(const float *friction, const int8_t *sources, in
   char *scr = hc.scratch<char>(need);
   DT_TRY(hc.rc);
   const uint32_t *ctl = dt_cost_distance_ctl(scr, H, W, alloc);
-  uint32_t flags[DT_DINF_DIST_BATCH_MAX];
-  int64_t rounds = 0;
-  int batch = DT_DINF_DIST_BATCH0;
-  for (int start = 1;; start = 0) {
-    DT_TRY(dt_launch_cost_distance(hc.c->stream, d_f, d_s, H, W, px, connectivity, visit_limit, start, batch, 0, scr,
-                                   need, d_c, d_i, d_b, nullptr));
-    DT_TRY(hc.download(flags, ctl, (size_t)batch));
-    DT_HIP(hipStreamSynchronize(hc.c->stream));
-    int used = 0;
-    while (used < batch && flags[used]) used++;
-    rounds += used;
-    if (used < batch) break;  // a quiet round: nothing is left to lower
-    if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
-  }
+  int64_t rounds;
+  DT_TRY(host_tile_rounds(hc, ctl, &rounds, [&](int start, int batch) {
+    return dt_launch_cost_distance(hc.c->stream, d_f, d_s, H, W, px, connectivity, visit_limit, start, batch, 0, scr,
+                                   need, d_c, d_i, d_b, nullptr);
+  }));
   DT_TRY(dt_launched(dt_launch_cost_distance(hc.c->stream, d_f, d_s, H, W, px, connectivity, visit_limit, 0, 0, 1, scr,
                                              need, d_c, d_i, d_b, nullptr)));
   uint32_t cnt[4] = {0, 0, 0, 0};
@@ -2941,25 +2938,15 @@ extern "C" int dt_cost_distance(const float *friction, const int8_t *sources, in
   return DT_OK;
 }
 
-// The modified area of device rasters within a host call: batches of rounds until a quiet one (the batches of
-// dt_dinf_distance_down), then the fills and the counts -> cnt4 = {rounds that raised something, raised cells, tile
-// visits, 0}.  Synchronises.
+// The modified area of device rasters within a host call: batches of rounds until a quiet one, then the fills and the
+// counts -> cnt4 = {rounds that raised something, raised cells, tile visits, 0}.  Synchronises.
 static int host_wetness_area(HostCall &hc, const double *d_a, const float *d_s, int64_t H, int64_t W, int visit_limit,
                              char *scr, size_t need, double *d_m, int64_t *cnt4) {
   const uint32_t *ctl = dt_wetness_ctl(scr, H, W);
-  uint32_t flags[DT_DINF_DIST_BATCH_MAX];
-  int64_t rounds = 0;
-  int batch = DT_DINF_DIST_BATCH0;
-  for (int start = 1;; start = 0) {
-    DT_TRY(dt_launch_wetness_area(hc.c->stream, d_a, d_s, H, W, visit_limit, start, batch, 0, scr, need, d_m, nullptr));
-    DT_TRY(hc.download(flags, ctl, (size_t)batch));
-    DT_HIP(hipStreamSynchronize(hc.c->stream));
-    int used = 0;
-    while (used < batch && flags[used]) used++;
-    rounds += used;
-    if (used < batch) break;  // a quiet round: nothing is left to raise
-    if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
-  }
+  int64_t rounds;
+  DT_TRY(host_tile_rounds(hc, ctl, &rounds, [&](int start, int batch) {
+    return dt_launch_wetness_area(hc.c->stream, d_a, d_s, H, W, visit_limit, start, batch, 0, scr, need, d_m, nullptr);
+  }));
   DT_TRY(dt_launched(dt_launch_wetness_area(hc.c->stream, d_a, d_s, H, W, visit_limit, 0, 0, 1, scr, need, d_m,
                                             nullptr)));
   uint32_t cnt[4] = {0, 0, 0, 0};
@@ -3046,7 +3033,7 @@ extern "C" int dt_wetness_saga(const double *area, const float *slope, int64_t H
   return DT_OK;
 }
 
-// (the batches of dt_dinf_distance_down, per level of the pyramid)
+// (the batches of host_tile_rounds per level of the pyramid, on residual keys and within the budget of rounds)
 extern "C" int dt_harmonic(const float *values, const int8_t *fixed, const int8_t *domain, int64_t H, int64_t W,
                            double tol, int max_rounds, double *out, int64_t *info) {
   HostCall hc;
@@ -3067,12 +3054,12 @@ extern "C" int dt_harmonic(const float *values, const int8_t *fixed, const int8_
   DT_TRY(hc.rc);
   hipStream_t s = hc.c->stream;
   DT_TRY(dt_launch_harmonic_setup(s, d_v, d_f, d_d, H, W, max_rounds, cap, scr, need, d_o));
-  unsigned long long keys[DT_DINF_DIST_BATCH_MAX];
+  unsigned long long keys[DT_TILE_ROUNDS_BATCH_MAX];
   unsigned long long tol_key;
   memcpy(&tol_key, &tol, sizeof(tol_key));
   for (int l = dt_harmonic_levels(H, W, cap) - 1; l >= 0; l--) {
     const unsigned long long *d_keys = dt_harmonic_keys(scr, H, W, max_rounds, cap, l);
-    int batch = DT_DINF_DIST_BATCH0;
+    int batch = DT_TILE_ROUNDS_BATCH0;
     for (int first = 0; first < max_rounds;) {
       const int b = batch < max_rounds - first ? batch : max_rounds - first;
       DT_TRY(dt_launch_harmonic_rounds(s, H, W, max_rounds, cap, l, first, b, tol, scr, need, d_o));
@@ -3080,7 +3067,7 @@ extern "C" int dt_harmonic(const float *values, const int8_t *fixed, const int8_
       DT_HIP(hipStreamSynchronize(s));
       if (keys[b - 1] <= tol_key) break;  // (a round behind one that met tol hands its key on)
       first += b;
-      if (batch < DT_DINF_DIST_BATCH_MAX) batch *= 2;
+      if (batch < DT_TILE_ROUNDS_BATCH_MAX) batch *= 2;
     }
     if (l) DT_TRY(dt_launch_harmonic_prolong(s, H, W, max_rounds, cap, l, scr, need, d_o));
   }

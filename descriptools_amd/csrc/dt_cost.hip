@@ -5,18 +5,17 @@
 // The cost A is the greatest solution of A(s) = 0 at the sources and A(v) = min over the passable neighbours u of
 // fl(A(u) + w(u, v)) elsewhere, w(u, v) = step * ((f(u) + f(v)) * 0.5) in float64, one rounding per operation.  fl(a + w)
 // is monotone in a and w >= 0, so any relaxation that starts at +inf reaches that solution, in any order and any tiling:
-// the schedule is the D-infinity distance's (dt_dinf_dist.hip, dt_tile_rounds.h), the value of a cell is lowered many
-// times instead of settled once.
+// the schedule is dt_tile_rounds.h's, the value of a cell is lowered many times instead of settled once (the D-infinity
+// distance, dt_dinf_dist.hip, settles each cell once on the same schedule).
 // k_cost_init   A = 0 at the sources (passable and sources == 1), +inf everywhere else.  A lives in the cost raster.
 // k_cost_round  one workgroup per tile of 64 x 64 cells with a one-cell halo: A (float64) and the friction (float32, 0
 //               on barriers and beyond the raster) of tile and halo go to LDS, 53 KB.  A sweep is two steps with a
 //               barrier between them: every lane pulls the minimum over the neighbours of its 16 cells from LDS into
 //               registers, then the lanes that found a lower value write it -- no lane reads what another is writing, no
 //               atomics.  Sweeps repeat until one lowers nothing or `visit_limit` is reached; the cells that were
-//               lowered go back to the cost raster.  The tile leaves an activity byte: HY_CHANGED when a cell of its
-//               outer ring was lowered (what its neighbours read), HY_OPEN when the limit stopped it; a round visits the
-//               tiles that are open or have a changed neighbour, in four launches by colour, flags in place.  A round
-//               raises its flag word when it lowered anything; a round that follows a quiet one returns at once.
+//               lowered go back to the cost raster.  The tile leaves an activity byte (dt_tile_rounds.h): HY_CHANGED
+//               when a cell of its outer ring was lowered (what its neighbours read), HY_OPEN when the limit stopped
+//               it; the round raises its flag word when it lowered anything.
 // k_cost_link   from the final A: backlink = the ESRI code of the first neighbour u, in the order NW, N, NE, W, E, SW,
 //               S, SE, with A(u) < A(v) and fl(A(u) + w(u, v)) == A(v) -- the same expression the rounds evaluated, so
 //               tightness is a comparison of bits; that neighbour's flat index goes to the parent plane (a source is
@@ -41,8 +40,8 @@
 
 // control words of one call
 enum {
-  CD_C_FLAGS = 0,  // DT_COST_ROUNDS_MAX of them: round r raises word r when it lowered something
-  CD_C_JUMP = DT_COST_ROUNDS_MAX,  // CD_JUMPS + 1 of them: pass p raises word p when it moved a pointer
+  CD_C_FLAGS = 0,  // DT_TILE_ROUNDS_MAX of them: round r raises word r when it lowered something
+  CD_C_JUMP = DT_TILE_ROUNDS_MAX,  // CD_JUMPS + 1 of them: pass p raises word p when it moved a pointer
   CD_C_REACH = DT_COST_CTL_COUNTS,  // (CD_C_JUMP + 32)
   CD_C_NOLINK,
   CD_C_VISITS,  // 64 bits (8-byte aligned: CD_C_REACH is even)
@@ -67,24 +66,14 @@ __global__ __launch_bounds__(256) void k_cost_init(const float *__restrict__ fri
 // DIAG: connectivity 8
 template <bool DIAG>
 __global__ __launch_bounds__(256) void k_cost_round(const float *__restrict__ friction, double *__restrict__ cost,
-                                                    int H, int W, int tiles_x, int tiles_y, double px, double pxd,
-                                                    int visit_limit, int *__restrict__ changed,
-                                                    const int *__restrict__ prev,
-                                                    const uint8_t *__restrict__ act_prev,
-                                                    uint8_t *__restrict__ act_cur, uint32_t *__restrict__ visits,
-                                                    int colour) {
+                                                    int H, int W, double px, double pxd, int visit_limit,
+                                                    const HyRound rnd) {
   __shared__ double s_a[CD_CELLS];
   __shared__ float s_f[CD_CELLS];
-  // (the previous round's flag was written by the previous kernel: a plain load sees it)
-  if (prev && *prev == 0) return;
   int ty, tx;
-  hy_tile_of_block(colour, tiles_x, ty, tx);
-  const int tile = ty * tiles_x + tx;
+  if (!hy_round_enter(rnd, ty, tx)) return;
+  const int tile = ty * rnd.tiles_x + tx;
   const int y0 = ty * CD_T, x0 = tx * CD_T;
-  if (!hy_tile_active(act_prev, ty, tx, tiles_x, tiles_y)) {
-    if (threadIdx.x == 0) act_cur[tile] = 0;
-    return;
-  }
   // tile and halo: friction 0 (a barrier) beyond the raster and on every cell that is not passable
   for (int i = threadIdx.x; i < CD_LD * CD_LD; i += 256) {
     const int r = i / CD_LD, c = i - r * CD_LD;
@@ -156,12 +145,8 @@ __global__ __launch_bounds__(256) void k_cost_round(const float *__restrict__ fr
   }
   const int any = __syncthreads_or(dirty != 0u);
   ring = __syncthreads_or(ring);
-  if (threadIdx.x == 0) {
-    // open: the limit ended the visit while a sweep still lowered something
-    act_cur[tile] = (uint8_t)((ring ? HY_CHANGED : 0) | (open ? HY_OPEN : 0));
-    if (any) *changed = 1;
-    visits[tile] += 1u;  // (a diagnostic: nobody else touches this tile's word during the launch)
-  }
+  // open: the limit ended the visit while a sweep still lowered something
+  hy_round_leave(rnd, tile, (ring ? HY_CHANGED : 0) | (open ? HY_OPEN : 0), any);
 }
 
 // last_flag: the flag word of the last round enqueued before this kernel (NULL: the caller looked at the flags itself)
@@ -173,8 +158,6 @@ __global__ __launch_bounds__(256) void k_cost_link(const float *__restrict__ fri
                                                    const uint32_t *__restrict__ visits, int tiles,
                                                    const int *__restrict__ last_flag, uint32_t *__restrict__ ctl,
                                                    int *__restrict__ status) {
-  __shared__ uint32_t s_visits;
-  if (threadIdx.x == 0) s_visits = 0u;
   const long long N = (long long)H * W;
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   bool reached = false, nolink = false;
@@ -217,10 +200,8 @@ __global__ __launch_bounds__(256) void k_cost_link(const float *__restrict__ fri
     if (parent) parent[c] = par;
   }
   const int nr = __syncthreads_count(reached), nl = __syncthreads_count(nolink);
-  if (c < tiles && visits[c]) atomicAdd(&s_visits, visits[c]);  // (after the barriers above: s_visits is zero by now)
-  __syncthreads();
+  hy_visits_sum(visits, tiles, &ctl[CD_C_VISITS]);
   if (threadIdx.x == 0) {
-    if (s_visits) atomicAdd((unsigned long long *)&ctl[CD_C_VISITS], (unsigned long long)s_visits);
     if (nr) atomicAdd(&ctl[CD_C_REACH], (uint32_t)nr);
     if (nl) atomicAdd(&ctl[CD_C_NOLINK], (uint32_t)nl);
     if (status && nl) atomicOr(status, DT_STATUS_NO_BACKLINK);
@@ -265,28 +246,21 @@ __global__ __launch_bounds__(256) void k_cost_index(const int32_t *__restrict__ 
 
 // ---- launcher ------------------------------------------------------------------------------------------------------
 struct CdLayout {
-  uint32_t *ctl;
-  uint8_t *act;
-  uint32_t *visits;  // per tile: how often a workgroup staged it
-  int32_t *parent;   // with `alloc` only
-  int tiles_x, tiles_y;
+  HyRoundsScratch r;
+  int32_t *parent;  // with `alloc` only
   size_t bytes;
 };
 static CdLayout cd_layout(int64_t H, int64_t W, bool alloc, void *scratch) {
   CdLayout L = {};
-  L.tiles_x = (int)((W + CD_T - 1) / CD_T);
-  L.tiles_y = (int)((H + CD_T - 1) / CD_T);
   DtCarver c(scratch);
-  L.ctl = c.take<uint32_t>(CD_C_WORDS);
-  L.act = c.take<uint8_t>((size_t)L.tiles_x * (size_t)L.tiles_y);
-  L.visits = c.take<uint32_t>((size_t)L.tiles_x * (size_t)L.tiles_y);
+  L.r = hy_rounds_take(c, H, W, CD_T, CD_C_WORDS);
   L.parent = alloc ? c.take<int32_t>((size_t)(H * W)) : nullptr;
   L.bytes = c.bytes();
   return L;
 }
 size_t dt_cost_distance_scratch(int64_t H, int64_t W, int alloc) { return cd_layout(H, W, alloc != 0, nullptr).bytes; }
 const uint32_t *dt_cost_distance_ctl(void *scratch, int64_t H, int64_t W, int alloc) {
-  return cd_layout(H, W, alloc != 0, scratch).ctl;
+  return cd_layout(H, W, alloc != 0, scratch).r.ctl;
 }
 
 int dt_launch_cost_distance(hipStream_t s, const float *friction, const int8_t *sources, int64_t H, int64_t W,
@@ -296,7 +270,7 @@ int dt_launch_cost_distance(hipStream_t s, const float *friction, const int8_t *
   if (H == 0 || W == 0) return DT_OK;
   DT_REQUIRE(connectivity == 4 || connectivity == 8, "connectivity is 4 or 8");
   DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
-  DT_REQUIRE(rounds >= 0 && rounds <= DT_COST_ROUNDS_MAX, "bad number of rounds");
+  DT_REQUIRE(rounds >= 0 && rounds <= DT_TILE_ROUNDS_MAX, "bad number of rounds");
   const int64_t N = H * W;
   const CdLayout L = cd_layout(H, W, indices != nullptr, scratch);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
@@ -304,41 +278,28 @@ int dt_launch_cost_distance(hipStream_t s, const float *friction, const int8_t *
   const dim3 cells((unsigned)((N + 255) / 256));
   const bool diag = connectivity == 8;
   const double pxd = px * 1.4142135623730951;
-  const size_t tiles = (size_t)L.tiles_x * (size_t)L.tiles_y;
-  if (start) {
-    hipLaunchKernelGGL(k_cost_init, cells, b, 0, s, friction, sources, (long long)N, cost);
-    DT_HIP(hipMemsetAsync(L.visits, 0, sizeof(uint32_t) * tiles, s));
-  }
-  if (rounds) DT_HIP(hipMemsetAsync(L.ctl + CD_C_FLAGS, 0, sizeof(uint32_t) * (size_t)rounds, s));
-  for (int r = 0; r < rounds; r++) {
-    int *flag = (int *)L.ctl + CD_C_FLAGS + r;
-    const int *prev = r ? flag - 1 : nullptr;
-    const uint8_t *act_prev = (start && r == 0) ? nullptr : L.act;
-    for (int c = 0; c < 4; c++) {
-      const unsigned nb = hy_colour_blocks(c, L.tiles_x, L.tiles_y);
-      if (!nb) continue;
-      if (diag)
-        hipLaunchKernelGGL(k_cost_round<true>, dim3(nb), b, 0, s, friction, cost, (int)H, (int)W, L.tiles_x, L.tiles_y,
-                           px, pxd, visit_limit, flag, prev, act_prev, L.act, L.visits, c);
-      else
-        hipLaunchKernelGGL(k_cost_round<false>, dim3(nb), b, 0, s, friction, cost, (int)H, (int)W, L.tiles_x,
-                           L.tiles_y, px, pxd, visit_limit, flag, prev, act_prev, L.act, L.visits, c);
-    }
-  }
+  uint32_t *ctl = L.r.ctl;
+  if (start) hipLaunchKernelGGL(k_cost_init, cells, b, 0, s, friction, sources, (long long)N, cost);
+  DT_TRY(hy_launch_rounds(s, L.r, ctl + CD_C_FLAGS, start, rounds, [&](dim3 blocks, const HyRound &rnd) {
+    if (diag)
+      hipLaunchKernelGGL(k_cost_round<true>, blocks, b, 0, s, friction, cost, (int)H, (int)W, px, pxd, visit_limit, rnd);
+    else
+      hipLaunchKernelGGL(k_cost_round<false>, blocks, b, 0, s, friction, cost, (int)H, (int)W, px, pxd, visit_limit, rnd);
+  }));
   if (finish) {
-    DT_HIP(hipMemsetAsync(L.ctl + CD_C_JUMP, 0, sizeof(uint32_t) * (CD_C_WORDS - CD_C_JUMP), s));
+    DT_HIP(hipMemsetAsync(ctl + CD_C_JUMP, 0, sizeof(uint32_t) * (CD_C_WORDS - CD_C_JUMP), s));
     // (finish with rounds: the device tier, which says so when its last round still lowered something)
-    const int *last = rounds ? (const int *)L.ctl + CD_C_FLAGS + rounds - 1 : nullptr;
+    const int *last = rounds ? (const int *)ctl + CD_C_FLAGS + rounds - 1 : nullptr;
     if (diag)
       hipLaunchKernelGGL(k_cost_link<true>, cells, b, 0, s, friction, sources, (const double *)cost, (int)H, (int)W, px,
-                         pxd, backlink, L.parent, (const uint32_t *)L.visits, (int)tiles, last, L.ctl, status);
+                         pxd, backlink, L.parent, (const uint32_t *)L.r.visits, (int)L.r.tiles(), last, ctl, status);
     else
       hipLaunchKernelGGL(k_cost_link<false>, cells, b, 0, s, friction, sources, (const double *)cost, (int)H, (int)W,
-                         px, pxd, backlink, L.parent, (const uint32_t *)L.visits, (int)tiles, last, L.ctl, status);
+                         px, pxd, backlink, L.parent, (const uint32_t *)L.r.visits, (int)L.r.tiles(), last, ctl, status);
     hipLaunchKernelGGL(k_cost_fill, cells, b, 0, s, friction, (long long)N, cost);
     if (indices) {
       for (int p = 0; p < CD_JUMPS; p++) {
-        int *moved = (int *)L.ctl + CD_C_JUMP + p;
+        int *moved = (int *)ctl + CD_C_JUMP + p;
         hipLaunchKernelGGL(k_cost_jump, cells, b, 0, s, L.parent, (long long)N, moved, p ? moved - 1 : nullptr);
       }
       hipLaunchKernelGGL(k_cost_index, cells, b, 0, s, (const int32_t *)L.parent, (long long)N, indices);

@@ -4,8 +4,8 @@
 //
 // The drainage graph is a DAG of out-degree <= 2 and a cell's value is a function of its receivers' final values:
 // values are PULLED up the graph from the targets (dt_dinf.hip pushes mass down it).  The chain of dependencies is a
-// hillslope flow path to the nearest stream cell, a few hundred cells, so the schedule is the conditioning rounds' one
-// (dt_hydro.hip), not a countdown:
+// hillslope flow path to the nearest stream cell, a few hundred cells, so the schedule is that of dt_tile_rounds.h (the
+// conditioning rounds' one), not a countdown:
 // k_dd_init   decodes every angle once (the 128 x 8 tile of dt_dinf_common.h) and writes one state byte per cell,
 //               bits 0-1 DD_UNSET / DD_REACH / DD_DEAD / DD_NODATA | 2, 3 the edge to the first / second receiver exists
 //               | 4 a share leaves the domain
@@ -18,10 +18,8 @@
 //             settles nothing (at most 32 * 32 + 1 of them: each but the last settles a cell) or `visit_limit` is
 //             reached.  The newly settled cells go to the state raster and the output rasters, which double as the
 //             store of settled values: settling is write-once.  The tile leaves an activity byte (dt_tile_rounds.h):
-//             HY_CHANGED when it settled something, HY_OPEN when the limit stopped it; a round visits the tiles that
-//             are open or have a changed neighbour, in four launches by colour, flags in place.  A round raises its
-//             flag when it settled anything; a round that follows a quiet one returns at once, so a batch of rounds is
-//             enqueued without a host synchronisation.
+//             HY_CHANGED when it settled something (anywhere in the tile, not only on its outer ring), HY_OPEN when the
+//             limit stopped it; the round raises its flag word when it settled anything.
 // k_dd_final  -100 on everything that does not reach; counts the reaching, dead and unsettled cells.
 // No data passes between workgroups inside a launch, nothing waits for another workgroup, no float atomics: every
 // value is computed once, by one lane, from final values, in the association the definition gives -- the result does
@@ -49,8 +47,8 @@
 // control words of one call: the flags of a batch of rounds, then the final kernel's counts
 // (and, as one 64-bit word, the tile visits of the call)
 enum {
-  DD_C_FLAGS = 0,  // DT_DINF_DIST_BATCH_MAX of them
-  DD_C_REACH = DT_DINF_DIST_BATCH_MAX,
+  DD_C_FLAGS = 0,  // DT_TILE_ROUNDS_BATCH_MAX of them
+  DD_C_REACH = DT_TILE_ROUNDS_BATCH_MAX,
   DD_C_DEAD,
   DD_C_UNSET,
   DD_C_VISITS = DD_C_REACH + 4,  // 8-byte aligned
@@ -117,26 +115,17 @@ template <bool Z>
 __global__ __launch_bounds__(256) void k_dd_round(const float *__restrict__ angle, const float *__restrict__ dem,
                                                   uint8_t *__restrict__ st, double *__restrict__ oh,
                                                   double *__restrict__ ov, double *__restrict__ os, int H, int W,
-                                                  int tiles_x, int tiles_y, double px, double pxd, int stat,
-                                                  int check_edges, int visit_limit, int *__restrict__ changed,
-                                                  const int *__restrict__ prev, const uint8_t *__restrict__ act_prev,
-                                                  uint8_t *__restrict__ act_cur, uint32_t *__restrict__ visits,
-                                                  int colour) {
+                                                  double px, double pxd, int stat, int check_edges, int visit_limit,
+                                                  const HyRound rnd) {
   __shared__ double s_h[DD_CELLS];
   __shared__ double s_v[Z ? DD_CELLS : 1];
   __shared__ double s_s[Z ? DD_CELLS : 1];
   __shared__ float s_z[Z ? DD_CELLS : 1];
   __shared__ uint8_t s_st[DD_CELLS];
-  // (the previous round's flag was written by the previous kernel: a plain load sees it)
-  if (prev && *prev == 0) return;
   int ty, tx;
-  hy_tile_of_block(colour, tiles_x, ty, tx);
-  const int tile = ty * tiles_x + tx;
+  if (!hy_round_enter(rnd, ty, tx)) return;
+  const int tile = ty * rnd.tiles_x + tx;
   const int y0 = ty * DD_T, x0 = tx * DD_T;
-  if (!hy_tile_active(act_prev, ty, tx, tiles_x, tiles_y)) {
-    if (threadIdx.x == 0) act_cur[tile] = 0;
-    return;
-  }
   // tile and halo: the state of every cell (nodata beyond the raster) and the values of the cells that reach
   for (int i = threadIdx.x; i < DD_LD * DD_LD; i += 256) {
     const int r = i / DD_LD, c = i - r * DD_LD;
@@ -266,20 +255,14 @@ __global__ __launch_bounds__(256) void k_dd_round(const float *__restrict__ angl
       }
     }
   }
-  if (threadIdx.x == 0) {
-    // open: the limit ended the visit while a sweep still settled something
-    act_cur[tile] = (uint8_t)(settled ? HY_CHANGED | (open ? HY_OPEN : 0) : 0);
-    if (settled) *changed = 1;
-    visits[tile] += 1u;  // (a diagnostic: nobody else touches this tile's word during the launch)
-  }
+  // open: the limit ended the visit while a sweep still settled something
+  hy_round_leave(rnd, tile, settled ? HY_CHANGED | (open ? HY_OPEN : 0) : 0, settled);
 }
 
 __global__ __launch_bounds__(256) void k_dd_final(const uint8_t *__restrict__ st, long long N, double *__restrict__ oh,
                                                   double *__restrict__ ov, double *__restrict__ os,
                                                   const uint32_t *__restrict__ visits, int tiles,
                                                   uint32_t *__restrict__ ctl) {
-  __shared__ uint32_t s_visits;
-  if (threadIdx.x == 0) s_visits = 0u;
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   uint32_t sv = DD_NODATA;
   if (c < N) {
@@ -292,10 +275,8 @@ __global__ __launch_bounds__(256) void k_dd_final(const uint8_t *__restrict__ st
   }
   const int nr = __syncthreads_count(sv == DD_REACH), nd = __syncthreads_count(sv == DD_DEAD),
             nu = __syncthreads_count(sv == DD_UNSET);
-  if (c < tiles && visits[c]) atomicAdd(&s_visits, visits[c]);  // (after the barriers above: s_visits is zero by now)
-  __syncthreads();
+  hy_visits_sum(visits, tiles, &ctl[DD_C_VISITS]);
   if (threadIdx.x == 0) {
-    if (s_visits) atomicAdd((unsigned long long *)&ctl[DD_C_VISITS], (unsigned long long)s_visits);
     if (nr) atomicAdd(&ctl[DD_C_REACH], (uint32_t)nr);
     if (nd) atomicAdd(&ctl[DD_C_DEAD], (uint32_t)nd);
     if (nu) atomicAdd(&ctl[DD_C_UNSET], (uint32_t)nu);
@@ -304,26 +285,19 @@ __global__ __launch_bounds__(256) void k_dd_final(const uint8_t *__restrict__ st
 
 // ---- launcher ------------------------------------------------------------------------------------------------------
 struct DdLayout {
-  uint32_t *ctl;
-  uint8_t *st, *act;
-  uint32_t *visits;  // per tile: how often a workgroup staged it (a diagnostic)
-  int tiles_x, tiles_y;
+  HyRoundsScratch r;
+  uint8_t *st;  // the state byte of every cell
   size_t bytes;
 };
 static DdLayout dd_layout(int64_t H, int64_t W, void *scratch) {
   DdLayout L = {};
-  L.tiles_x = (int)((W + DD_T - 1) / DD_T);
-  L.tiles_y = (int)((H + DD_T - 1) / DD_T);
   DtCarver c(scratch);
-  L.ctl = c.take<uint32_t>(DD_C_WORDS);
-  L.st = c.take<uint8_t>((size_t)(H * W));
-  L.act = c.take<uint8_t>((size_t)L.tiles_x * (size_t)L.tiles_y);
-  L.visits = c.take<uint32_t>((size_t)L.tiles_x * (size_t)L.tiles_y);
+  L.r = hy_rounds_take(c, H, W, DD_T, DD_C_WORDS, &L.st);
   L.bytes = c.bytes();
   return L;
 }
 size_t dt_dinf_distance_scratch(int64_t H, int64_t W) { return dd_layout(H, W, nullptr).bytes; }
-const uint32_t *dt_dinf_distance_ctl(void *scratch, int64_t H, int64_t W) { return dd_layout(H, W, scratch).ctl; }
+const uint32_t *dt_dinf_distance_ctl(void *scratch, int64_t H, int64_t W) { return dd_layout(H, W, scratch).r.ctl; }
 
 // start != 0: k_dd_init first, and the first of the rounds visits every tile; `rounds` (<= 64) rounds, round r raising
 // control word r when it settled something; finish != 0: k_dd_final, its counts in control words 64-66 and the tile
@@ -334,7 +308,7 @@ int dt_launch_dinf_distance(hipStream_t s, const float *angle, const int8_t *riv
                             int *status) {
   if (H == 0 || W == 0) return DT_OK;
   DT_REQUIRE(stat >= 0 && stat <= 2 && (check_edges == 0 || check_edges == 1) && visit_limit >= 0, "bad stat, check_edges or visit_limit");
-  DT_REQUIRE(rounds >= 0 && rounds <= DT_DINF_DIST_BATCH_MAX, "bad number of rounds");
+  DT_REQUIRE(rounds >= 0 && rounds <= DT_TILE_ROUNDS_BATCH_MAX, "bad number of rounds");
   DT_REQUIRE(dem ? (v && sf) : (!v && !sf), "heights go with both the vertical and the surface raster");
   const int64_t N = H * W;
   const DdLayout L = dd_layout(H, W, scratch);
@@ -345,29 +319,20 @@ int dt_launch_dinf_distance(hipStream_t s, const float *angle, const int8_t *riv
     const unsigned nt = di_tiles(H, W, tiles_x);
     hipLaunchKernelGGL(k_dd_init, dim3(nt), b, 0, s, angle, river, (int)H, (int)W, tiles_x, di_vec_ok(angle, W), L.st,
                        h, v, sf, status);
-    DT_HIP(hipMemsetAsync(L.visits, 0, sizeof(uint32_t) * (size_t)L.tiles_x * (size_t)L.tiles_y, s));
   }
-  if (rounds) DT_HIP(hipMemsetAsync(L.ctl + DD_C_FLAGS, 0, sizeof(uint32_t) * DT_DINF_DIST_BATCH_MAX, s));
   const double pxd = px * 1.4142135623730951;
-  for (int r = 0; r < rounds; r++) {
-    int *flag = (int *)L.ctl + DD_C_FLAGS + r;
-    const int *prev = r ? flag - 1 : nullptr;
-    const uint8_t *act_prev = (start && r == 0) ? nullptr : L.act;
-    for (int c = 0; c < 4; c++) {
-      const unsigned nb = hy_colour_blocks(c, L.tiles_x, L.tiles_y);
-      if (!nb) continue;
-      if (dem)
-        hipLaunchKernelGGL(k_dd_round<true>, dim3(nb), b, 0, s, angle, dem, L.st, h, v, sf, (int)H, (int)W, L.tiles_x,
-                           L.tiles_y, px, pxd, stat, check_edges, visit_limit, flag, prev, act_prev, L.act, L.visits, c);
-      else
-        hipLaunchKernelGGL(k_dd_round<false>, dim3(nb), b, 0, s, angle, dem, L.st, h, v, sf, (int)H, (int)W, L.tiles_x,
-                           L.tiles_y, px, pxd, stat, check_edges, visit_limit, flag, prev, act_prev, L.act, L.visits, c);
-    }
-  }
+  DT_TRY(hy_launch_rounds(s, L.r, L.r.ctl + DD_C_FLAGS, start, rounds, [&](dim3 blocks, const HyRound &rnd) {
+    if (dem)
+      hipLaunchKernelGGL(k_dd_round<true>, blocks, b, 0, s, angle, dem, L.st, h, v, sf, (int)H, (int)W, px, pxd, stat,
+                         check_edges, visit_limit, rnd);
+    else
+      hipLaunchKernelGGL(k_dd_round<false>, blocks, b, 0, s, angle, dem, L.st, h, v, sf, (int)H, (int)W, px, pxd, stat,
+                         check_edges, visit_limit, rnd);
+  }));
   if (finish) {
-    DT_HIP(hipMemsetAsync(L.ctl + DD_C_REACH, 0, sizeof(uint32_t) * (DD_C_WORDS - DD_C_REACH), s));
+    DT_HIP(hipMemsetAsync(L.r.ctl + DD_C_REACH, 0, sizeof(uint32_t) * (DD_C_WORDS - DD_C_REACH), s));
     hipLaunchKernelGGL(k_dd_final, dim3((unsigned)((N + 255) / 256)), b, 0, s, (const uint8_t *)L.st, (long long)N, h, v,
-                       sf, (const uint32_t *)L.visits, L.tiles_x * L.tiles_y, L.ctl);
+                       sf, (const uint32_t *)L.r.visits, (int)L.r.tiles(), L.r.ctl);
   }
   return DT_OK;
 }

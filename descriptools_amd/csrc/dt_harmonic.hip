@@ -48,10 +48,10 @@
 //                Each single update lowers the energy of the symmetric positive definite system for any factor in
 //                (0, 2) and any order of the cells, so the rounds converge whatever the tiling.  A tile in which no
 //                solved cell has three neighbours never divides.  Changed cells go back to global memory.
-//                The schedule is dt_tile_rounds.h's: four launches per round, one per tile colour, flags in place; a
-//                tile rests while neither it (HY_OPEN: its last sweep still changed a bit) nor its halo (HY_CHANGED: a
-//                neighbour's outer ring changed) moved.  HM_DIRTY says that the visit wrote anything at all (the
-//                residual's reuse rule).
+//                The schedule is dt_tile_rounds.h's, with the residual key of the round before in place of its flag
+//                word: a tile rests while neither it (HY_OPEN: its last sweep still changed a bit) nor its halo
+//                (HY_CHANGED: a neighbour's outer ring changed) moved.  HM_DIRTY says that the visit wrote anything at
+//                all (the residual's reuse rule).
 // k_hm_residual  after each round: the maximum of r over the level's solved cells, one workgroup per tile, one 64-bit
 //                integer atomic maximum per workgroup on the bits of r (r >= 0: its bits order as it does) into the
 //                round's key word, skipped when the word already holds as much.  A tile whose cells and halo did not
@@ -276,25 +276,18 @@ __device__ __forceinline__ int hm_sweeps(double *s_u, const uint32_t (&codes)[2]
   return open;
 }
 
-// prev_key: the key word of the round before this one (NULL: the level's first round)
+// prev_key: the key word of the round before this one (NULL: the level's first round); rnd: without flag words
 __global__ __launch_bounds__(256) void k_hm_round(double *__restrict__ u, const uint8_t *__restrict__ m, int H, int W,
-                                                  int tiles_x, int tiles_y, const hm_key_t *__restrict__ prev_key,
-                                                  hm_key_t tol_key, const hm_key_t *__restrict__ range,
-                                                  const uint8_t *__restrict__ act_prev,
-                                                  uint8_t *__restrict__ act_cur, uint32_t *__restrict__ visits,
-                                                  int sweeps, int colour) {
+                                                  const hm_key_t *__restrict__ prev_key, hm_key_t tol_key,
+                                                  const hm_key_t *__restrict__ range, int sweeps, const HyRound rnd) {
   __shared__ double s_u[HM_CELLS];
   __shared__ uint8_t s_m[HM_CELLS];
   // (the previous round's key was completed by the previous kernels: a plain load sees it)
   if (prev_key && *prev_key <= tol_key) return;
   int ty, tx;
-  hy_tile_of_block(colour, tiles_x, ty, tx);
-  const int tile = ty * tiles_x + tx;
+  if (!hy_round_tile(rnd, ty, tx)) return;
+  const int tile = ty * rnd.tiles_x + tx;
   const int y0 = ty * HM_T, x0 = tx * HM_T;
-  if (!hy_tile_active(act_prev, ty, tx, tiles_x, tiles_y)) {
-    if (threadIdx.x == 0) act_cur[tile] = 0;
-    return;
-  }
   // tile and halo: beyond the raster nothing is in the domain
   for (int i = threadIdx.x; i < HM_LD * HM_LD; i += 256) {
     const int r = i / HM_LD, c = i - r * HM_LD;
@@ -351,10 +344,7 @@ __global__ __launch_bounds__(256) void k_hm_round(double *__restrict__ u, const 
     }
   const int any = __syncthreads_or(dirty != 0u);
   ring = __syncthreads_or(ring);
-  if (threadIdx.x == 0) {
-    act_cur[tile] = (uint8_t)((ring ? HY_CHANGED : 0) | (open ? HY_OPEN : 0) | (any ? HM_DIRTY : 0));
-    visits[tile] += 1u;  // (nobody else touches this tile's word during the launch)
-  }
+  hy_round_leave(rnd, tile, (ring ? HY_CHANGED : 0) | (open ? HY_OPEN : 0) | (any ? HM_DIRTY : 0), 0);
 }
 
 // One workgroup per tile.  first: the level's first round (no tile has a stored value yet).
@@ -370,15 +360,10 @@ __global__ __launch_bounds__(256) void k_hm_residual(const double *__restrict__ 
   }
   const int tile = (int)blockIdx.x;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  // evaluate again when the tile's last visit wrote a cell or a neighbour's wrote its outer ring
-  int again = first;
-  if (threadIdx.x < 9) {
-    const int y = ty + (int)threadIdx.x / 3 - 1, x = tx + (int)threadIdx.x % 3 - 1;
-    if (y >= 0 && y < tiles_y && x >= 0 && x < tiles_x)
-      again |= act[(size_t)y * tiles_x + x] & (threadIdx.x == 4 ? HM_DIRTY : HY_CHANGED);
-  }
   if (threadIdx.x == 0) s_k = 0ull;
-  again = __syncthreads_or(again);
+  // evaluate again when the tile's last visit wrote a cell or a neighbour's wrote its outer ring (act is never NULL:
+  // the test ends on the barrier that s_k needs)
+  const bool again = hy_tile_active(act, ty, tx, tiles_x, tiles_y, HM_DIRTY) || first;
   if (again) {
     const int lx = (int)threadIdx.x & (HM_T - 1), x = tx * HM_T + lx;
     hm_key_t k = 0ull;
@@ -506,7 +491,7 @@ static HmLayout hm_layout(int64_t H, int64_t W, int max_rounds, int level_cap, v
 }
 static int hm_check(int64_t H, int64_t W, int max_rounds, int level_cap) {
   DT_REQUIRE(H > 0 && W > 0 && H * W < (1ll << 31), "bad raster shape");
-  DT_REQUIRE(max_rounds >= 1 && max_rounds <= DT_HARMONIC_ROUNDS_MAX, "max_rounds must lie in [1, 4096]");
+  DT_REQUIRE(max_rounds >= 1 && max_rounds <= DT_TILE_ROUNDS_MAX, "max_rounds must lie in [1, 4096]");
   DT_REQUIRE(level_cap >= 0, "level_cap is negative");
   return DT_OK;
 }
@@ -577,13 +562,12 @@ int dt_launch_harmonic_rounds(hipStream_t s, int64_t H, int64_t W, int max_round
   const int sweeps = v.tiles_x * v.tiles_y == 1 ? HM_SWEEPS_ONE : HM_SWEEPS;
   for (int r = first_round; r < first_round + rounds; r++) {
     const hm_key_t *prev = r ? v.keys + r - 1 : nullptr;
-    const uint8_t *act_prev = r ? v.act : nullptr;
-    for (int c = 0; c < 4; c++) {
-      const unsigned nb = hy_colour_blocks(c, v.tiles_x, v.tiles_y);
-      if (!nb) continue;
-      hipLaunchKernelGGL(k_hm_round, dim3(nb), b, 0, s, v.u, (const uint8_t *)v.m, v.H, v.W, v.tiles_x, v.tiles_y, prev,
-                         tol_key, (const hm_key_t *)L.range, act_prev, v.act, v.visits, sweeps, c);
-    }
+    // (the level's first round visits every tile)
+    hy_launch_colours(HyRound{nullptr, nullptr, r ? v.act : nullptr, v.act, v.visits, v.tiles_x, v.tiles_y, 0},
+                      [&](dim3 blocks, const HyRound &rnd) {
+                        hipLaunchKernelGGL(k_hm_round, blocks, b, 0, s, v.u, (const uint8_t *)v.m, v.H, v.W, prev,
+                                           tol_key, (const hm_key_t *)L.range, sweeps, rnd);
+                      });
     hipLaunchKernelGGL(k_hm_residual, dim3((unsigned)(v.tiles_x * v.tiles_y)), b, 0, s, (const double *)v.u,
                        (const uint8_t *)v.m, v.H, v.W, v.tiles_x, v.tiles_y, (const uint8_t *)v.act, r == 0 ? 1 : 0,
                        v.tile_key, prev, tol_key, v.keys + r);

@@ -307,17 +307,22 @@ int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *w
 // window hi, queue rounds that found work, the largest window, two-receiver cells
 const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 
+// The ops on the tile-round schedule (dt_tile_rounds.h): the D-infinity distance, the cost distance, the modified
+// catchment area and the harmonic smoother.
+#define DT_TILE_ROUNDS_MAX 4096      // rounds a call takes at most (the flag words of a launcher call, harmonic's budget)
+#define DT_TILE_ROUNDS_BATCH0 8      // the host tier's rounds between two looks at their flags: 8, 16, 32, then ...
+#define DT_TILE_ROUNDS_BATCH_MAX 64  // ... 64: also what one dt_launch_dinf_distance call takes at most
+
 // D-infinity distance down to the stream (dt_dinf_dist.hip; dinf.py holds the definition): the horizontal distance h
 // and, with heights, the vertical drop v and the surface distance s along the D-infinity flow field to the targets
 // (river == 1 and not nodata), stat 0 / 1 / 2 = average / minimum / maximum over the two receivers; the outputs hold
 // -100 where a cell does not reach.  dem NULL: h alone (v and s NULL); otherwise v and s are both given.  The state
-// lives in `scratch`: start != 0 sets it up, `rounds` (0..DT_DINF_DIST_BATCH_MAX) rounds of tile visits follow, round r raising control
+// lives in `scratch`: start != 0 sets it up, `rounds` (0..DT_TILE_ROUNDS_BATCH_MAX) rounds of tile visits follow, round r raising control
 // word r when it settled something (a round that follows a quiet one returns at once), finish != 0 writes -100 on what
 // does not reach and counts the reaching / dead / unsettled cells into control words 64 / 65 / 66 and the tile visits
 // of the call (64 bits) into words 68-69.  visit_limit: 0, or
 // the sweeps a workgroup makes over its tile per visit at most (tests); the result does not depend on it.  An angle
 // outside the contract raises DT_STATUS_BAD_ANGLE on `status`.  Nothing synchronises.  H * W < 2^31.
-#define DT_DINF_DIST_BATCH_MAX 64  // rounds one launcher call takes at most: the flag words of a batch
 size_t dt_dinf_distance_scratch(int64_t H, int64_t W);
 int dt_launch_dinf_distance(hipStream_t s, const float *angle, const int8_t *river, const float *dem, int64_t H,
                             int64_t W, double px, int stat, int check_edges, int visit_limit, int start, int rounds,
@@ -439,7 +444,7 @@ int dt_launch_proximity(hipStream_t s, const int8_t *river, const float *nod, in
 // f < +inf) from the sources (sources == 1 and passable) under connectivity 4 or 8, the flat index of the source a cell
 // is reached from (indices, may be NULL) and the ESRI D8 code of its first step towards it (backlink, may be NULL);
 // -100 / -100 / 0 on barriers and unreached cells.  The state lives in `cost` and in `scratch` (laid out with the parent
-// plane when indices is given: alloc != 0): start != 0 sets it up, `rounds` (0..DT_COST_ROUNDS_MAX) rounds of tile
+// plane when indices is given: alloc != 0): start != 0 sets it up, `rounds` (0..DT_TILE_ROUNDS_MAX) rounds of tile
 // visits follow, round r raising control word r when it lowered something (a round that follows a quiet one returns at
 // once), finish != 0 computes the back-links, the fills and the allocation and counts the reached cells, the reached
 // non-source cells without a back-link and the tile visits of the call (64 bits) into control words
@@ -447,8 +452,7 @@ int dt_launch_proximity(hipStream_t s, const int8_t *river, const float *nod, in
 // the last round still lowered something, and DT_STATUS_NO_BACKLINK for a cell without a back-link (status may be NULL).
 // visit_limit: 0, or the sweeps a workgroup makes over its tile per visit at most (tests); the result does not depend
 // on it.  Nothing synchronises.  H * W < 2^31.
-#define DT_COST_ROUNDS_MAX 4096  // rounds one launcher call takes at most: its flag words
-#define DT_COST_CTL_COUNTS (DT_COST_ROUNDS_MAX + 32)
+#define DT_COST_CTL_COUNTS (DT_TILE_ROUNDS_MAX + 32)
 size_t dt_cost_distance_scratch(int64_t H, int64_t W, int alloc);
 int dt_launch_cost_distance(hipStream_t s, const float *friction, const int8_t *sources, int64_t H, int64_t W,
                             double px, int connectivity, int visit_limit, int start, int rounds, int finish,
@@ -460,14 +464,13 @@ const uint32_t *dt_cost_distance_ctl(void *scratch, int64_t H, int64_t W, int al
 // SAGA wetness index (dt_wetness.hip; wetness.py holds the definition).  suction: s of a slope raster (log_t = ln t,
 // taken by the caller).  index: swi = float32(log(M / tan(b))) from a modified area.  area: M = the least solution of
 // M(v) = max(A(v), fl(s(v) * max over the valid neighbours of M)), -100 on nodata.  The state lives in `modified` and in
-// `scratch`: start != 0 sets it up, `rounds` (0..DT_WETNESS_ROUNDS_MAX) rounds of tile visits follow, round r raising
+// `scratch`: start != 0 sets it up, `rounds` (0..DT_TILE_ROUNDS_MAX) rounds of tile visits follow, round r raising
 // control word r when it raised something (a round that follows a quiet one returns at once), finish != 0 writes the
 // fills and counts the raised cells and the tile visits of the call (64 bits) into control words DT_WETNESS_CTL_COUNTS
 // + 0 and + 2-3; with rounds in the same call it raises DT_STATUS_NOT_CONVERGED on `status` (may be NULL) when the last
 // round still raised something.  The scratch may carry a suction plane and an M plane behind the control block (the
 // composite call's).  visit_limit as for the cost distance.  Nothing synchronises.  H * W < 2^31.
-#define DT_WETNESS_ROUNDS_MAX 4096  // rounds one launcher call takes at most: its flag words
-#define DT_WETNESS_CTL_COUNTS DT_WETNESS_ROUNDS_MAX
+#define DT_WETNESS_CTL_COUNTS DT_TILE_ROUNDS_MAX
 size_t dt_wetness_scratch(int64_t H, int64_t W, int suction_plane, int m_plane);
 const uint32_t *dt_wetness_ctl(void *scratch, int64_t H, int64_t W);
 float *dt_wetness_suction_plane(void *scratch, int64_t H, int64_t W);
@@ -492,8 +495,7 @@ int dt_launch_wetness_area(hipStream_t s, const double *area, const float *sucti
 // tol.  info: 0 levels, 1 rounds on level 0, 2 rounds on all levels, 3 tile visits, 4 the last residual of level 0 as
 // a double's bits, 5 whether that is <= tol, DT_HARMONIC_INFO_LEVEL0 + l the rounds on level l.  Precondition: every
 // free cell of the domain is joined to a fixed cell through the domain (4-connected); without it those cells hold an
-// unspecified constant.  Nothing synchronises.  0 < H * W < 2^31, 1 <= max_rounds <= DT_HARMONIC_ROUNDS_MAX.
-#define DT_HARMONIC_ROUNDS_MAX 4096
+// unspecified constant.  Nothing synchronises.  0 < H * W < 2^31, 1 <= max_rounds <= DT_TILE_ROUNDS_MAX.
 #define DT_HARMONIC_LEVELS_MAX 32
 #define DT_HARMONIC_INFO_LEVEL0 8
 #define DT_HARMONIC_INFO (DT_HARMONIC_INFO_LEVEL0 + DT_HARMONIC_LEVELS_MAX)

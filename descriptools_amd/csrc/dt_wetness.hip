@@ -4,7 +4,7 @@
 // The modified area M is the least solution of M(v) = max(A(v), fl(s(v) * max over the valid neighbours u of M(u))),
 // s in [0, 1] in float32, the product in float64.  The product is monotone in M(u) and never exceeds it, so any
 // relaxation that starts at M = A reaches that solution, in any order and any tiling: the (max, x) twin of the cost
-// distance's (min, +) relaxation, on its schedule (dt_cost.hip, dt_tile_rounds.h).
+// distance's (min, +) relaxation (dt_cost.hip), on the schedule of dt_tile_rounds.h.
 // k_wet_suction  s = float32(exp(-((e * exp(exp(e * L))) * L))), e = weight * max(slope + offset, minimum), L = ln t
 //                taken once on the host; -100 where the slope is NaN or not in [0, pi/2).
 // k_wet_init     M = A on valid cells (0 < A < +inf and 0 <= s <= 1), -inf elsewhere.  M lives in the output raster.
@@ -15,7 +15,7 @@
 //                barrier between them: every lane walks down its column with the maxima of three rows of three cells in
 //                registers (54 LDS reads for 16 cells), then the lanes that found a larger value write it -- no lane
 //                reads what another is writing, no atomics.  Sweeps repeat until one raises nothing or `visit_limit` is
-//                reached; the raised cells go back to the raster.  Activity bytes, colours, flag words: dt_cost.hip's.
+//                reached; the raised cells go back to the raster.  Activity bytes, colours, flag words: dt_tile_rounds.h.
 // k_wet_finish   -100 on nodata cells; counts the raised cells (M > A) and sums the tile visits.
 // k_wet_index    swi = float32(log(M / tan(b))), b = max(slope + offset, minimum); -100 on nodata and where b >= pi/2.
 #include <cfloat>
@@ -35,7 +35,7 @@
 
 // control words of one call
 enum {
-  WT_C_FLAGS = 0,  // DT_WETNESS_ROUNDS_MAX of them: round r raises word r when it raised something
+  WT_C_FLAGS = 0,  // DT_TILE_ROUNDS_MAX of them: round r raises word r when it raised something
   WT_C_RAISED = DT_WETNESS_CTL_COUNTS,
   WT_C_VISITS = WT_C_RAISED + 2,  // 64 bits (8-byte aligned: WT_C_RAISED is even)
   WT_C_WORDS = WT_C_RAISED + 8
@@ -76,22 +76,12 @@ __global__ __launch_bounds__(256) void k_wet_init(const double *__restrict__ are
 }
 
 __global__ __launch_bounds__(256) void k_wet_round(const float *__restrict__ suction, double *__restrict__ m, int H,
-                                                   int W, int tiles_x, int tiles_y, int visit_limit,
-                                                   int *__restrict__ changed, const int *__restrict__ prev,
-                                                   const uint8_t *__restrict__ act_prev,
-                                                   uint8_t *__restrict__ act_cur, uint32_t *__restrict__ visits,
-                                                   int colour) {
+                                                   int W, int visit_limit, const HyRound rnd) {
   __shared__ double s_m[WT_CELLS];
-  // (the previous round's flag was written by the previous kernel: a plain load sees it)
-  if (prev && *prev == 0) return;
   int ty, tx;
-  hy_tile_of_block(colour, tiles_x, ty, tx);
-  const int tile = ty * tiles_x + tx;
+  if (!hy_round_enter(rnd, ty, tx)) return;
+  const int tile = ty * rnd.tiles_x + tx;
   const int y0 = ty * WT_T, x0 = tx * WT_T;
-  if (!hy_tile_active(act_prev, ty, tx, tiles_x, tiles_y)) {
-    if (threadIdx.x == 0) act_cur[tile] = 0;
-    return;
-  }
   // this lane's cells: column lx, rows ly0 ... ly0 + WT_CPT - 1
   const int lx = (int)threadIdx.x & (WT_T - 1), ly0 = ((int)threadIdx.x >> 6) * WT_CPT;
   // every load of the visit before the first use: M of tile and halo (-inf beyond the raster), s of the lane's cells
@@ -173,12 +163,8 @@ __global__ __launch_bounds__(256) void k_wet_round(const float *__restrict__ suc
   }
   const int any = __syncthreads_or(dirty != 0u);
   ring = __syncthreads_or(ring);
-  if (threadIdx.x == 0) {
-    // open: the limit ended the visit while a sweep still raised something
-    act_cur[tile] = (uint8_t)((ring ? HY_CHANGED : 0) | (open ? HY_OPEN : 0));
-    if (any) *changed = 1;
-    visits[tile] += 1u;  // (a diagnostic: nobody else touches this tile's word during the launch)
-  }
+  // open: the limit ended the visit while a sweep still raised something
+  hy_round_leave(rnd, tile, (ring ? HY_CHANGED : 0) | (open ? HY_OPEN : 0), any);
 }
 
 // last_flag: the flag word of the last round enqueued before this kernel (NULL: the caller looked at the flags itself)
@@ -186,8 +172,6 @@ __global__ __launch_bounds__(256) void k_wet_finish(const double *__restrict__ a
                                                     long long N, const uint32_t *__restrict__ visits, int tiles,
                                                     const int *__restrict__ last_flag, uint32_t *__restrict__ ctl,
                                                     int *__restrict__ status) {
-  __shared__ uint32_t s_visits;
-  if (threadIdx.x == 0) s_visits = 0u;
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   bool raised = false;
   if (c < N) {
@@ -196,10 +180,8 @@ __global__ __launch_bounds__(256) void k_wet_finish(const double *__restrict__ a
     else m[c] = -100.0;
   }
   const int nr = __syncthreads_count(raised);
-  if (c < tiles && visits[c]) atomicAdd(&s_visits, visits[c]);  // (after the barrier above: s_visits is zero by now)
-  __syncthreads();
+  hy_visits_sum(visits, tiles, &ctl[WT_C_VISITS]);
   if (threadIdx.x == 0) {
-    if (s_visits) atomicAdd((unsigned long long *)&ctl[WT_C_VISITS], (unsigned long long)s_visits);
     if (nr) atomicAdd(&ctl[WT_C_RAISED], (uint32_t)nr);
     if (status && blockIdx.x == 0 && last_flag && *last_flag) atomicOr(status, DT_STATUS_NOT_CONVERGED);
   }
@@ -222,22 +204,15 @@ __global__ __launch_bounds__(256) void k_wet_index(const double *__restrict__ m,
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
 struct WtLayout {
-  uint32_t *ctl;
-  uint8_t *act;
-  uint32_t *visits;  // per tile: how often a workgroup staged it
-  float *suction;    // the composite call's planes
+  HyRoundsScratch r;
+  float *suction;  // the composite call's planes
   double *m;
-  int tiles_x, tiles_y;
   size_t bytes;
 };
 static WtLayout wt_layout(int64_t H, int64_t W, bool suction_plane, bool m_plane, void *scratch) {
   WtLayout L = {};
-  L.tiles_x = (int)((W + WT_T - 1) / WT_T);
-  L.tiles_y = (int)((H + WT_T - 1) / WT_T);
   DtCarver c(scratch);
-  L.ctl = c.take<uint32_t>(WT_C_WORDS);
-  L.act = c.take<uint8_t>((size_t)L.tiles_x * (size_t)L.tiles_y);
-  L.visits = c.take<uint32_t>((size_t)L.tiles_x * (size_t)L.tiles_y);
+  L.r = hy_rounds_take(c, H, W, WT_T, WT_C_WORDS);
   L.suction = suction_plane ? c.take<float>((size_t)(H * W)) : nullptr;
   L.m = m_plane ? c.take<double>((size_t)(H * W)) : nullptr;
   L.bytes = c.bytes();
@@ -246,7 +221,7 @@ static WtLayout wt_layout(int64_t H, int64_t W, bool suction_plane, bool m_plane
 size_t dt_wetness_scratch(int64_t H, int64_t W, int suction_plane, int m_plane) {
   return wt_layout(H, W, suction_plane != 0, m_plane != 0, nullptr).bytes;
 }
-const uint32_t *dt_wetness_ctl(void *scratch, int64_t H, int64_t W) { return wt_layout(H, W, false, false, scratch).ctl; }
+const uint32_t *dt_wetness_ctl(void *scratch, int64_t H, int64_t W) { return wt_layout(H, W, false, false, scratch).r.ctl; }
 float *dt_wetness_suction_plane(void *scratch, int64_t H, int64_t W) {
   return wt_layout(H, W, true, false, scratch).suction;
 }
@@ -275,35 +250,23 @@ int dt_launch_wetness_area(hipStream_t s, const double *area, const float *sucti
                            double *modified, int *status) {
   if (H == 0 || W == 0) return DT_OK;
   DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
-  DT_REQUIRE(rounds >= 0 && rounds <= DT_WETNESS_ROUNDS_MAX, "bad number of rounds");
+  DT_REQUIRE(rounds >= 0 && rounds <= DT_TILE_ROUNDS_MAX, "bad number of rounds");
   const int64_t N = H * W;
   const WtLayout L = wt_layout(H, W, false, false, scratch);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
   const dim3 b(256);
   const dim3 cells((unsigned)((N + 255) / 256));
-  const size_t tiles = (size_t)L.tiles_x * (size_t)L.tiles_y;
-  if (start) {
-    hipLaunchKernelGGL(k_wet_init, cells, b, 0, s, area, suction, (long long)N, modified);
-    DT_HIP(hipMemsetAsync(L.visits, 0, sizeof(uint32_t) * tiles, s));
-  }
-  if (rounds) DT_HIP(hipMemsetAsync(L.ctl + WT_C_FLAGS, 0, sizeof(uint32_t) * (size_t)rounds, s));
-  for (int r = 0; r < rounds; r++) {
-    int *flag = (int *)L.ctl + WT_C_FLAGS + r;
-    const int *prev = r ? flag - 1 : nullptr;
-    const uint8_t *act_prev = (start && r == 0) ? nullptr : L.act;
-    for (int c = 0; c < 4; c++) {
-      const unsigned nb = hy_colour_blocks(c, L.tiles_x, L.tiles_y);
-      if (!nb) continue;
-      hipLaunchKernelGGL(k_wet_round, dim3(nb), b, 0, s, suction, modified, (int)H, (int)W, L.tiles_x, L.tiles_y,
-                         visit_limit, flag, prev, act_prev, L.act, L.visits, c);
-    }
-  }
+  uint32_t *ctl = L.r.ctl;
+  if (start) hipLaunchKernelGGL(k_wet_init, cells, b, 0, s, area, suction, (long long)N, modified);
+  DT_TRY(hy_launch_rounds(s, L.r, ctl + WT_C_FLAGS, start, rounds, [&](dim3 blocks, const HyRound &rnd) {
+    hipLaunchKernelGGL(k_wet_round, blocks, b, 0, s, suction, modified, (int)H, (int)W, visit_limit, rnd);
+  }));
   if (finish) {
-    DT_HIP(hipMemsetAsync(L.ctl + WT_C_RAISED, 0, sizeof(uint32_t) * (WT_C_WORDS - WT_C_RAISED), s));
+    DT_HIP(hipMemsetAsync(ctl + WT_C_RAISED, 0, sizeof(uint32_t) * (WT_C_WORDS - WT_C_RAISED), s));
     // (finish with rounds: the device tier, which says so when its last round still raised something)
-    const int *last = rounds ? (const int *)L.ctl + WT_C_FLAGS + rounds - 1 : nullptr;
-    hipLaunchKernelGGL(k_wet_finish, cells, b, 0, s, area, modified, (long long)N, (const uint32_t *)L.visits,
-                       (int)tiles, last, L.ctl, status);
+    const int *last = rounds ? (const int *)ctl + WT_C_FLAGS + rounds - 1 : nullptr;
+    hipLaunchKernelGGL(k_wet_finish, cells, b, 0, s, area, modified, (long long)N, (const uint32_t *)L.r.visits,
+                       (int)L.r.tiles(), last, ctl, status);
   }
   return DT_OK;
 }
