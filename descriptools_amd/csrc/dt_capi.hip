@@ -849,6 +849,40 @@ extern "C" int dt_dev_wetness_index(dt_ctx *c, const double *modified, const flo
   return d.done(dt_launch_wetness_index(c->stream, modified, slope, H * W, offset, minimum, swi));
 }
 
+// geodesic reconstruction: what both tiers require of the marker mode and its parameters
+static int dt_check_morph(int mode, int erosion, int connectivity, double h, int radius, int visit_limit) {
+  DT_REQUIRE(mode >= DT_MORPH_MARKER && mode <= DT_MORPH_WINDOW, "mode must be one of DT_MORPH_*");
+  DT_REQUIRE(erosion == 0 || erosion == 1, "erosion is 0 or 1");
+  DT_REQUIRE(connectivity == 4 || connectivity == 8, "connectivity must be 4 or 8");
+  DT_REQUIRE(mode != DT_MORPH_SHIFT || (std::isfinite(h) && h > 0.0), "h must be finite and > 0");
+  DT_REQUIRE(mode != DT_MORPH_WINDOW || (radius >= 1 && radius <= DT_FILTER_RADIUS_MAX), "radius must lie in [1, 4096]");
+  DT_REQUIRE(visit_limit >= 0, "visit_limit is negative");
+  return DT_OK;
+}
+// ... and of the rasters of a call with cells
+static int dt_check_morph_rasters(int mode, const float *mask, const float *marker, const float *out,
+                                  const uint8_t *out8) {
+  DT_REQUIRE((out != nullptr) != (out8 != nullptr), "exactly one of out and out8 is given");
+  DT_REQUIRE(mask && (mode != DT_MORPH_MARKER || marker), "NULL raster");
+  DT_REQUIRE(!out || (out != mask && out != marker), "out must be neither mask nor marker");
+  return DT_OK;
+}
+
+extern "C" int dt_dev_morph_reconstruct(dt_ctx *c, int mode, int erosion, int connectivity, const float *mask,
+                                        const float *marker, const uint8_t *seeds, double h, int radius, int64_t H,
+                                        int64_t W, int visit_limit, int rounds, float *out, uint8_t *out8) {
+  DT_DEV(d, c, H, W, 1.0);
+  DT_TRY(dt_check_morph(mode, erosion, connectivity, h, radius, visit_limit));
+  DT_REQUIRE(rounds >= 1 && rounds <= DT_TILE_ROUNDS_MAX, "rounds must lie in [1, 4096]");
+  if (H * W == 0) return DT_OK;
+  DT_TRY(dt_check_morph_rasters(mode, mask, marker, out, out8));
+  const size_t need = dt_morph_scratch(H, W, mode, out8 != nullptr);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  return d.done(dt_launch_morph(c->stream, mode, erosion, connectivity, mask, marker, seeds, h, radius, H, W,
+                                visit_limit, 1, rounds, 1, scr, need, out, out8, c->status));
+}
+
 // harmonic interpolation: the shape rule of dt_check_ws, and what both tiers require of tol and the budget
 static int dt_check_harmonic(double tol, int max_rounds) {
   DT_REQUIRE(std::isfinite(tol) && tol > 0.0, "tol must be finite and > 0");
@@ -3030,6 +3064,45 @@ extern "C" int dt_wetness_saga(const double *area, const float *slope, int64_t H
   DT_TRY(dt_launched(dt_launch_wetness_index(hc.c->stream, d_m, d_sl, (int64_t)n, offset, minimum, d_w)));
   DT_TRY(hc.finish());
   if (info4) memcpy(info4, cnt4, sizeof(cnt4));
+  return DT_OK;
+}
+
+// geodesic reconstruction: batches of rounds until a quiet one, then the output and the counts
+extern "C" int dt_morph_reconstruct(int mode, int erosion, int connectivity, const float *mask, const float *marker,
+                                    const uint8_t *seeds, double h, int radius, int64_t H, int64_t W, int visit_limit,
+                                    float *out, uint8_t *out8, int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_fp(H, W));
+  DT_TRY(dt_check_morph(mode, erosion, connectivity, h, radius, visit_limit));
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_TRY(dt_check_morph_rasters(mode, mask, marker, out, out8));
+  const float *d_mask = hc.in(mask, n);
+  const float *d_marker = mode == DT_MORPH_MARKER ? hc.in(marker, n) : nullptr;
+  const uint8_t *d_seeds = mode == DT_MORPH_OUTLETS ? hc.in(seeds, n) : nullptr;
+  float *d_out = hc.out(out, n);
+  uint8_t *d_out8 = hc.out(out8, n);
+  const size_t need = dt_morph_scratch(H, W, mode, out8 != nullptr);
+  char *scr = hc.scratch<char>(need);
+  DT_TRY(hc.rc);
+  const uint32_t *ctl = dt_morph_ctl(scr, H, W);
+  int64_t rounds;
+  DT_TRY(host_tile_rounds(hc, ctl, &rounds, [&](int start, int batch) {
+    return dt_launch_morph(hc.c->stream, mode, erosion, connectivity, d_mask, d_marker, d_seeds, h, radius, H, W,
+                           visit_limit, start, batch, 0, scr, need, d_out, d_out8, nullptr);
+  }));
+  DT_TRY(dt_launched(dt_launch_morph(hc.c->stream, mode, erosion, connectivity, d_mask, d_marker, d_seeds, h, radius, H,
+                                     W, visit_limit, 0, 0, 1, scr, need, d_out, d_out8, nullptr)));
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  DT_TRY(hc.download(cnt, ctl + DT_MORPH_CTL_COUNTS, 4));
+  DT_TRY(hc.finish());
+  if (info4) {
+    info4[0] = rounds;
+    info4[1] = cnt[0];
+    info4[2] = (int64_t)cnt[2] | (int64_t)cnt[3] << 32;
+  }
   return DT_OK;
 }
 

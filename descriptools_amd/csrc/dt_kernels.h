@@ -308,7 +308,7 @@ int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *w
 const uint32_t *dt_dinf_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 
 // The ops on the tile-round schedule (dt_tile_rounds.h): the D-infinity distance, the cost distance, the modified
-// catchment area and the harmonic smoother.
+// catchment area, the geodesic reconstruction and the harmonic smoother.
 #define DT_TILE_ROUNDS_MAX 4096      // rounds a call takes at most (the flag words of a launcher call, harmonic's budget)
 #define DT_TILE_ROUNDS_BATCH0 8      // the host tier's rounds between two looks at their flags: 8, 16, 32, then ...
 #define DT_TILE_ROUNDS_BATCH_MAX 64  // ... 64: also what one dt_launch_dinf_distance call takes at most
@@ -482,6 +482,28 @@ int dt_launch_wetness_index(hipStream_t s, const double *modified, const float *
 int dt_launch_wetness_area(hipStream_t s, const double *area, const float *suction, int64_t H, int64_t W,
                            int visit_limit, int start, int rounds, int finish, void *scratch, size_t scratch_bytes,
                            double *modified, int *status);
+
+// Geodesic reconstruction (dt_morphology.hip; morphology.py holds the definition): the reconstruction by dilation
+// (erosion != 0: by erosion) of a marker under `mask`, on order-preserving keys; -100 on invalid cells and on valid
+// cells that no marker reaches.  mode (DT_MORPH_*, descriptools_hip.h) says what the marker is: `marker` (MARKER), the
+// mask shifted by `h` (SHIFT), the mask's key +- 1 (STEP), the mask on the outlet cells -- `seeds` != 0, or seeds NULL:
+// the raster's edge and the 8-neighbours of invalid cells -- (OUTLETS), or the window minimum / maximum of the mask at
+// `radius` (WINDOW: dt_launch_filter_extremes into a plane of the scratch).  One output: `out` (float32; it holds the
+// keys while the rounds run) or `out8` (uint8, 1 where the result differs from the mask; the keys live in the scratch).
+// The state lives in the output and in `scratch`: start != 0 sets it up, `rounds` (0..DT_TILE_ROUNDS_MAX) rounds of
+// tile visits follow, round r raising control word r when it stored something (a round that follows a quiet one returns
+// at once), finish != 0 writes the output and counts the valid cells whose result is not their start value and the tile
+// visits of the call (64 bits) into control words DT_MORPH_CTL_COUNTS + 0 and + 2-3; with rounds in the same call it
+// raises DT_STATUS_NOT_CONVERGED on `status` (may be NULL) when the last round still stored something.  Every call of
+// one reconstruction names the same arguments.  visit_limit as for the cost distance.  Nothing synchronises.
+// H * W < 2^31.
+#define DT_MORPH_CTL_COUNTS DT_TILE_ROUNDS_MAX
+size_t dt_morph_scratch(int64_t H, int64_t W, int mode, int to_u8);
+const uint32_t *dt_morph_ctl(void *scratch, int64_t H, int64_t W);
+int dt_launch_morph(hipStream_t s, int mode, int erosion, int connectivity, const float *mask, const float *marker,
+                    const uint8_t *seeds, double h, int radius, int64_t H, int64_t W, int visit_limit, int start,
+                    int rounds, int finish, void *scratch, size_t scratch_bytes, float *out, uint8_t *out8,
+                    int *status);
 
 // Harmonic interpolation (dt_harmonic.hip; harmonic.py holds the definition): out = the discrete harmonic function on
 // the domain with the fixed cells held (fixed == 1 and a finite value; domain NULL: everywhere), NaN outside the domain.

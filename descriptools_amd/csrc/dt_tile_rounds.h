@@ -18,8 +18,8 @@
 // Users: the conditioning rounds (dt_hydro.hip: the three helpers below, with a window, an uncoloured form and ping-pong
 // activity arrays of their own), and on the scaffold (HyRound, hy_round_enter / _leave, hy_visits_sum, HyRoundsScratch,
 // hy_launch_rounds) the D-infinity distance (dt_dinf_dist.hip), the cost distance (dt_cost.hip), the modified catchment
-// area (dt_wetness.hip) and the harmonic smoother (dt_harmonic.hip: its rounds end on a residual key, not a flag, so it
-// has its own round loop around hy_launch_colours).  The host tier's batches are host_tile_rounds in dt_capi.hip.
+// area (dt_wetness.hip), the geodesic reconstruction (dt_morphology.hip) and the harmonic smoother (dt_harmonic.hip: its
+// rounds end on a residual key, not a flag, so it has its own round loop around hy_launch_colours).  The host tier's batches are host_tile_rounds in dt_capi.hip.
 #pragma once
 #include "dt_common.h"
 

@@ -180,7 +180,8 @@ class Context:
                                "(DT_STATUS_NOT_CONVERGED): the rasters of this step are not valid -- raise "
                                "Chain(condition_rounds=...) or use flowdir.d8_conditioned, which iterates to the end.  "
                                "dt_dev_wetness_modified_area raises the same bit when its last round still raised a "
-                               "cell: call it again with more rounds, or use wetness.modified_catchment_area")
+                               "cell: call it again with more rounds, or use wetness.modified_catchment_area.  "
+                               "dt_dev_morph_reconstruct likewise: more rounds, or morphology.reconstruct")
         if st & 4:
             raise ValueError("dt_dev_flowacc_weighted met a weight that is negative, not finite or over the bound of "
                              "its frac_bits (DT_STATUS_BAD_WEIGHT): the weighted accumulation is not valid")

@@ -18,7 +18,8 @@ extreme and every rank is the bit pattern of one particular height of the window
 float32(float64(max) - float64(min)).  opening is the maximum of the minimum raster and closing the minimum of the
 maximum raster: the second pass runs on the first pass's raster, whose no-value cells are invalid, so the validity mask
 of both passes is the input's.  The cost per cell does not depend on the radius (running extremes over segments of
-2 R + 1 cells along the rows, then along the columns).
+2 R + 1 cells along the rows, then along the columns).  morphology.opening_by_reconstruction / closing_by_reconstruction
+are the forms that remove the same objects and give every other cell back bit for bit.
 
 2. Percentile (radius in [1, 16], q finite and in [0, 100]).  With n the number of valid cells of the window, the output
 is the element of index
