@@ -61,6 +61,8 @@ _SIGS = {
     "dt_dinf_distance_down": (ci, [c_f32p, c_i8p, c_f32p, i64, i64, f64, ci, ci, ci, c_f64p, c_f64p, c_f64p, c_i64p]),
     "dt_mfd_shares": (ci, [c_f32p, c_u8p, i64, i64, f64, ci, c_u16p]),
     "dt_mfd_accumulate": (ci, [c_u16p, c_f64p, i64, i64, ci, c_f64p, c_i64p]),
+    "dt_mfd_route": (ci, [c_u16p, c_f64p, c_f64p, i64, i64, ci, ci] + [c_f64p] * 4 + [c_i64p]),
+    "dt_dinf_route": (ci, [c_f32p, c_f64p, c_f64p, i64, i64, ci, ci] + [c_f64p] * 4 + [c_i64p]),
     "dt_terrain": (ci, [c_f32p, i64, i64, f64, ci, f64, f64, f64] + [c_f32p] * 8),
     "dt_horizon": (ci, [c_f32p, i64, i64, f64, ci, ci, f64, c_u8p, c_u16p, c_f32p, c_f32p, c_f32p]),
     "dt_focal": (ci, [c_f32p, i64, i64, f64, ci, c_i32p, ci, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u16p]),
@@ -140,6 +142,8 @@ _SIGS = {
     "dt_dev_mfd_shares": (ci, [vp, vp, vp, i64, i64, f64, ci, vp]),
     "dt_dev_mfd_accumulate": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
     "dt_dev_mfd_accumulate_info": (ci, [vp, c_i64p]),
+    "dt_dev_mfd_route": (ci, [vp, vp, vp, vp, i64, i64, ci, ci, ci] + [vp] * 4),
+    "dt_dev_dinf_route": (ci, [vp, vp, vp, vp, i64, i64, ci, ci, ci] + [vp] * 4),
     "dt_dev_cost_distance": (ci, [vp, vp, vp, i64, i64, f64, ci, ci, ci, vp, vp, vp]),
     "dt_dev_wetness_suction": (ci, [vp, vp, i64, i64, f64, f64, f64, f64, vp]),
     "dt_dev_wetness_modified_area": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),

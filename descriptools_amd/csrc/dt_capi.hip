@@ -335,8 +335,9 @@ static int dt_check_ws(int64_t H, int64_t W, double px) {
 // another op's bytes.  p2: a second region reserved beside the first (HAND's, beside flow accumulation's); in0 / in1 /
 // frac_bits: what a D-infinity continuation must name again.
 static void dt_scratch_claim(dt_ctx *c, DtScratchOwner owner, int64_t H, int64_t W, void *p, void *p2 = nullptr,
-                             const void *in0 = nullptr, const void *in1 = nullptr, int frac_bits = 0) {
-  c->claim = DtScratchClaim{owner, H, W, (char *)p, (char *)p2, {in0, in1}, frac_bits};
+                             const void *in0 = nullptr, const void *in1 = nullptr, int frac_bits = 0,
+                             const void *param = nullptr, int mode = 0) {
+  c->claim = DtScratchClaim{owner, H, W, (char *)p, (char *)p2, {in0, in1}, frac_bits, param, mode};
 }
 // the claim of `owner` on a raster of w's core shape (w NULL: of any shape), with both regions when `two`; fails with
 // the entry's own message
@@ -731,12 +732,15 @@ static void dt_countdown_info4(const uint32_t *ctl, int64_t *info4) {
 
 // Start (rounds > 0: round 0 and rounds - 1 queue rounds) or continue (rounds < 0: -rounds queue rounds) an
 // accumulation on the rasters `in` (an `raster` raster, in the messages of `entry`) and w, each time with the out step.
-// launch(start, rounds, scr, need) is the op's launcher on them, `scratch` its size function.
+// launch(start, rounds, scr, need) is the op's launcher on them, `scratch` its size function.  acc: the output (of a
+// routing run: any of those it writes).  param, mode: the parameter raster and the mode of a routing run, NULL and 0
+// for an accumulation; a continuation names them again, so neither continues the other.
 #define DT_DINF_ROUNDS_MAX 4096
 template <typename Launch>
 static int dev_countdown(dt_ctx *c, DtScratchOwner owner, const char *entry, const char *raster, const void *in,
                          const double *w, int64_t H, int64_t W, int frac_bits, int rounds, double *acc,
-                         size_t (*scratch)(int64_t, int64_t), Launch launch) {
+                         size_t (*scratch)(int64_t, int64_t), Launch launch, const double *param = nullptr,
+                         int mode = 0) {
   DT_DEV(d, c, H, W, 1.0);
   DT_REQUIRE((in && acc) || H * W == 0, "NULL raster");
   DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
@@ -748,7 +752,7 @@ static int dev_countdown(dt_ctx *c, DtScratchOwner owner, const char *entry, con
     void *scr = d.scratch(need);
     DT_TRY(d.rc);
     DT_TRY(launch(1, rounds - 1, scr, need));
-    dt_scratch_claim(c, owner, H, W, scr, nullptr, in, w, frac_bits);
+    dt_scratch_claim(c, owner, H, W, scr, nullptr, in, w, frac_bits, param, mode);
     return d.done();
   }
   char msg[256];
@@ -759,6 +763,9 @@ static int dev_countdown(dt_ctx *c, DtScratchOwner owner, const char *entry, con
   snprintf(msg, sizeof(msg), "%s continues with another %s raster, weight raster or frac_bits than it was started with",
            entry, raster);
   DT_REQUIRE(k->in[0] == in && k->in[1] == w && k->frac_bits == frac_bits, msg);
+  snprintf(msg, sizeof(msg), "%s continues with another parameter raster or mode than it was started with (a routing "
+           "run and an accumulation do not continue each other)", entry);
+  DT_REQUIRE(k->param == param && k->mode == mode, msg);
   return d.done(launch(0, -rounds, k->ptr, need));
 }
 // info4 of the `name` accumulation last enqueued on the context, from its control words (synchronises)
@@ -785,6 +792,38 @@ extern "C" int dt_dev_dinf_accumulate(dt_ctx *c, const float *angle, const doubl
                          return dt_launch_dinf_accumulate(c->stream, angle, w, H, W, frac_bits, start, n, 1,
                                                           dt_dinf_stack_cap(), scr, need, acc, c->status);
                        });
+}
+// What the two routing entries refuse before dev_countdown takes over: a mode that is none, and on a raster with cells
+// a NULL parameter raster, no output at all, an output that is an input or that is named twice.  *any: an output.
+static int dt_check_route(int64_t H, int64_t W, const void *in, const double *w, const double *param, int mode,
+                          double *const (&out)[4], double **any) {
+  DT_REQUIRE(mode == DT_ROUTE_DECAY || mode == DT_ROUTE_RETAIN || mode == DT_ROUTE_LIMIT,
+             "mode must be DT_ROUTE_DECAY, DT_ROUTE_RETAIN or DT_ROUTE_LIMIT");
+  *any = nullptr;
+  if (H <= 0 || W <= 0) return DT_OK;  // dev_countdown's checks say the rest
+  DT_REQUIRE(param != nullptr, "param is NULL");
+  for (int i = 0; i < 4; i++) {
+    if (!out[i]) continue;
+    *any = out[i];
+    DT_REQUIRE((const void *)out[i] != in && out[i] != w && out[i] != param, "an output raster is one of the inputs");
+    for (int j = 0; j < i; j++) DT_REQUIRE(out[j] != out[i], "two outputs are the same raster");
+  }
+  DT_REQUIRE(*any != nullptr, "all four outputs are NULL");
+  return DT_OK;
+}
+extern "C" int dt_dev_dinf_route(dt_ctx *c, const float *angle, const double *w, const double *param, int64_t H,
+                                 int64_t W, int frac_bits, int mode, int rounds, double *inflow, double *load,
+                                 double *outflow, double *retained) {
+  DT_CTX(c);
+  double *const out[4] = {inflow, load, outflow, retained};
+  double *any;
+  DT_TRY(dt_check_route(H, W, angle, w, param, mode, out, &any));
+  return dev_countdown(c, DT_OWNER_DINF, "dt_dev_dinf_route", "angle", angle, w, H, W, frac_bits, rounds, any,
+                       dt_dinf_accumulate_scratch, [&](int start, int n, void *scr, size_t need) {
+                         return dt_launch_dinf_route(c->stream, angle, w, param, H, W, frac_bits, mode, start, n, 1,
+                                                     dt_dinf_stack_cap(), scr, need, inflow, load, outflow, retained,
+                                                     c->status);
+                       }, param, mode);
 }
 extern "C" int dt_dev_dinf_accumulate_info(dt_ctx *c, int64_t *info4) {
   return dev_countdown_info(c, DT_OWNER_DINF, "D-infinity", dt_dinf_accumulate_ctl, info4);
@@ -991,6 +1030,20 @@ extern "C" int dt_dev_mfd_accumulate(dt_ctx *c, const uint16_t *shares, const do
                          return dt_launch_mfd_accumulate(c->stream, shares, w, H, W, frac_bits, start, n, 1,
                                                          dt_mfd_stack_cap(), scr, need, acc, c->status);
                        });
+}
+extern "C" int dt_dev_mfd_route(dt_ctx *c, const uint16_t *shares, const double *w, const double *param, int64_t H,
+                                int64_t W, int frac_bits, int mode, int rounds, double *inflow, double *load,
+                                double *outflow, double *retained) {
+  DT_CTX(c);
+  double *const out[4] = {inflow, load, outflow, retained};
+  double *any;
+  DT_TRY(dt_check_route(H, W, shares, w, param, mode, out, &any));
+  return dev_countdown(c, DT_OWNER_MFD, "dt_dev_mfd_route", "share", shares, w, H, W, frac_bits, rounds, any,
+                       dt_mfd_accumulate_scratch, [&](int start, int n, void *scr, size_t need) {
+                         return dt_launch_mfd_route(c->stream, shares, w, param, H, W, frac_bits, mode, start, n, 1,
+                                                    dt_mfd_stack_cap(), scr, need, inflow, load, outflow, retained,
+                                                    c->status);
+                       }, param, mode);
 }
 extern "C" int dt_dev_mfd_accumulate_info(dt_ctx *c, int64_t *info4) {
   return dev_countdown_info(c, DT_OWNER_MFD, "MFD", dt_mfd_accumulate_ctl, info4);
@@ -2637,6 +2690,87 @@ extern "C" int dt_dinf_accumulate(const float *angle, const double *w, int64_t H
   DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
   if (info4) memcpy(info4, got, sizeof(got));
   return hc.finish();
+}
+
+// The host tier of a routing run, after the flow raster: the weights, the parameter and the outputs on the device, the
+// rounds (host_countdown) and the status.  launch(d_w, d_p, d_out, start, rounds, finish) is the op's launcher.
+template <typename Launch>
+static int host_route(HostCall &hc, const double *w, const double *param, size_t n, double *const (&host)[4],
+                      const uint32_t *d_ctl, int bad_flow_bit, const char *bad_flow_msg, int64_t *info4,
+                      Launch launch) {
+  const double *d_w = hc.in(w, n);
+  const double *d_p = hc.in(param, n);
+  double *d_o[4];
+  for (int i = 0; i < 4; i++) d_o[i] = hc.out(host[i], n);
+  DT_TRY(hc.rc);
+  int32_t st = 0;
+  int64_t got[4];
+  DT_TRY(host_countdown(hc, d_ctl, &st, got, [&](int start, int rounds, int finish) {
+    return launch(d_w, d_p, d_o, start, rounds, finish);
+  }));
+  DT_REQUIRE(!(st & bad_flow_bit), bad_flow_msg);
+  DT_REQUIRE(!(st & DT_STATUS_BAD_WEIGHT), "a weight is negative, not finite, or over the bound of frac_bits");
+  DT_REQUIRE(!(st & DT_STATUS_BAD_PARAM), "a parameter is NaN, negative or (decay) above 1");
+  if (info4) memcpy(info4, got, sizeof(got));
+  return hc.finish();
+}
+// what both host entries check first
+static int dt_check_route_host(int64_t H, int64_t W, int frac_bits, int mode, int64_t *info4) {
+  DT_TRY(dt_check_ws(H, W, 1.0));
+  DT_REQUIRE(frac_bits >= -DT_FRAC_BITS_MAX && frac_bits <= DT_FRAC_BITS_MAX, "frac_bits out of range");
+  DT_REQUIRE(mode == DT_ROUTE_DECAY || mode == DT_ROUTE_RETAIN || mode == DT_ROUTE_LIMIT,
+             "mode must be DT_ROUTE_DECAY, DT_ROUTE_RETAIN or DT_ROUTE_LIMIT");
+  if (info4) info4[0] = info4[1] = info4[2] = info4[3] = 0;
+  return DT_OK;
+}
+
+extern "C" int dt_dinf_route(const float *angle, const double *w, const double *param, int64_t H, int64_t W,
+                             int frac_bits, int mode, double *inflow, double *load, double *outflow, double *retained,
+                             int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_route_host(H, W, frac_bits, mode, info4));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(angle && param, "NULL raster");
+  DT_REQUIRE(inflow || load || outflow || retained, "all four outputs are NULL");
+  double *const host[4] = {inflow, load, outflow, retained};
+  const float *d_a = hc.in(angle, n);
+  const size_t need = dt_dinf_accumulate_scratch(H, W);
+  char *scr = hc.scratch<char>(need);
+  const int cap = dt_dinf_stack_cap();
+  return host_route(hc, w, param, n, host, dt_dinf_accumulate_ctl(scr, H, W), DT_STATUS_BAD_ANGLE,
+                    "an angle is neither -1, -100 nor in [0, float32(2 pi)]", info4,
+                    [&](const double *d_w, const double *d_p, double *const *d_o, int start, int rounds, int finish) {
+                      return dt_launch_dinf_route(hc.c->stream, d_a, d_w, d_p, H, W, frac_bits, mode, start, rounds,
+                                                  finish, cap, scr, need, d_o[0], d_o[1], d_o[2], d_o[3],
+                                                  hc.c->status);
+                    });
+}
+
+extern "C" int dt_mfd_route(const uint16_t *shares, const double *w, const double *param, int64_t H, int64_t W,
+                            int frac_bits, int mode, double *inflow, double *load, double *outflow, double *retained,
+                            int64_t *info4) {
+  HostCall hc;
+  DT_TRY(hc.rc);
+  DT_TRY(dt_check_route_host(H, W, frac_bits, mode, info4));
+  const size_t n = (size_t)H * W;
+  if (n == 0) return DT_OK;
+  DT_REQUIRE(shares && param, "NULL raster");
+  DT_REQUIRE(inflow || load || outflow || retained, "all four outputs are NULL");
+  double *const host[4] = {inflow, load, outflow, retained};
+  const uint16_t *d_s = hc.in(shares, n * 8);
+  const size_t need = dt_mfd_accumulate_scratch(H, W);
+  char *scr = hc.scratch<char>(need);
+  const int cap = dt_mfd_stack_cap();
+  return host_route(hc, w, param, n, host, dt_mfd_accumulate_ctl(scr, H, W), DT_STATUS_BAD_SHARES,
+                    "a share word is not eight 0xFFFF and has a slot above 32768 or a sum that is neither 0 nor 32768",
+                    info4,
+                    [&](const double *d_w, const double *d_p, double *const *d_o, int start, int rounds, int finish) {
+                      return dt_launch_mfd_route(hc.c->stream, d_s, d_w, d_p, H, W, frac_bits, mode, start, rounds,
+                                                 finish, cap, scr, need, d_o[0], d_o[1], d_o[2], d_o[3],
+                                                 hc.c->status);
+                    });
 }
 
 extern "C" int dt_mfd_shares(const float *dem, const uint8_t *fdr, int64_t H, int64_t W, double exponent, int contour,

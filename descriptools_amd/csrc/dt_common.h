@@ -71,6 +71,8 @@ struct DtScratchClaim {
                       // of the other are fused (the region then becomes HAND's `ptr`)
   const void *in[2];  // D-infinity, MFD: the angle (share) and weight rasters the accumulation was started on,
   int frac_bits;      // and its frac_bits: a continuation must name the same
+  const void *param;  // a routing run on that state: its parameter raster and its mode (NULL and 0: an accumulation)
+  int mode;
 };
 struct dt_ctx {
   int device;

@@ -27,6 +27,9 @@
 //        raises DT_STATUS_NOT_CONVERGED (cd_not_converged).
 // Integer sums are order-free and the split is a function of the complete T alone, so the result does not depend on
 // the order of arrival, on how many cells a lane holds or on the number of rounds.
+// Routing (routing.py) puts a transfer function between "complete" and "split": the flow kernels' MODE instances split
+// O = cd_transfer(T, the cell's parameter) <= T, the out kernels' take O again from the final word.  The word, the
+// control words and the workspace are the accumulation's, whose kernels are the CD_T_NONE instances.
 #pragma once
 #include <cmath>
 
@@ -68,6 +71,70 @@ __device__ __forceinline__ void cd_not_converged(bool first, const uint32_t *__r
 // the result of a complete cell: what arrived, its own q (cd_quant's, taken again) excluded
 __device__ __forceinline__ double cd_result(unsigned long long wv, unsigned long long q, int sbits) {
   return ldexp((double)(long long)((wv & CD_SUM_MASK) - q), -sbits);
+}
+
+// ---- routing: a transfer function between "complete" and "split" (routing.py holds the definition) ----
+// A complete cell with load T passes on O = f(T, p) <= T and keeps R = T - O; the receivers get the op's split of O.
+// The modes are the C ABI's DT_ROUTE_*; CD_T_NONE is the accumulation (O = T, no parameter raster is read).
+enum { CD_T_NONE = 0, CD_T_DECAY = DT_ROUTE_DECAY, CD_T_RETAIN = DT_ROUTE_RETAIN, CD_T_LIMIT = DT_ROUTE_LIMIT };
+#define CD_CAP_MAX (1ull << 53)  // a capacity is held to this: above every T (<= 2^52), so +inf never binds
+
+// O of a load T < 2^56 under the parameter value p; a p outside its contract is `bad` and acts as the identity
+//   decay   D = rint(p * 2^30) in [0, 2^30]: floor(T * D / 2^30), the product split as mf_share splits its own
+//   retain  C = min(rint(p * 2^s), 2^53):    T - C above the capacity, else 0
+//   limit   the same C:                      min(T, C)
+__device__ __forceinline__ unsigned long long cd_transfer_value(int mode, unsigned long long T, double p, int sbits,
+                                                                bool &bad) {
+  if (mode == CD_T_DECAY) {
+    if (!(p >= 0.0 && p <= 1.0)) {
+      bad = true;
+      return T;
+    }
+    const unsigned long long D = (unsigned long long)rint(ldexp(p, 30));
+    return (T >> 30) * D + (((T & ((1ull << 30) - 1ull)) * D) >> 30);
+  }
+  if (mode == CD_T_RETAIN || mode == CD_T_LIMIT) {
+    if (!(p >= 0.0)) {
+      bad = true;
+      return T;
+    }
+    const double c = rint(ldexp(p, sbits));
+    const unsigned long long C = c >= (double)CD_CAP_MAX ? CD_CAP_MAX : (unsigned long long)c;
+    if (mode == CD_T_RETAIN) return T > C ? T - C : 0ull;
+    return T < C ? T : C;
+  }
+  return T;
+}
+// the same on the parameter raster: the flow and the out kernels take O of cell c from here (the flow kernels that
+// have the value in a register already, loaded ahead of its use, call cd_transfer_value on it)
+__device__ __forceinline__ unsigned long long cd_transfer(int mode, unsigned long long T,
+                                                          const double *__restrict__ param, long long c, int sbits,
+                                                          bool &bad) {
+  return mode == CD_T_NONE ? T : cd_transfer_value(mode, T, param[c], sbits, bad);
+}
+
+// the four rasters of a routing run, each NULL when it is not wanted: what arrived (T - q), T, O and T - O
+struct CdRouteOut {
+  double *inflow, *load, *outflow, *retained;
+};
+// one complete cell of an out kernel: O and R are taken again from the final word and the parameter
+__device__ __forceinline__ void cd_route_store(int mode, const CdRouteOut &o, long long c, bool complete,
+                                               unsigned long long wv, unsigned long long q,
+                                               const double *__restrict__ param, int sbits) {
+  double vi = -100.0, vl = -100.0, vo = -100.0, vr = -100.0;
+  if (complete) {
+    const unsigned long long T = wv & CD_SUM_MASK;
+    bool ignore = false;  // the init kernel has reported it
+    const unsigned long long O = cd_transfer(mode, T, param, c, sbits, ignore);
+    vi = ldexp((double)(long long)(T - q), -sbits);
+    vl = ldexp((double)(long long)T, -sbits);
+    vo = ldexp((double)(long long)O, -sbits);
+    vr = ldexp((double)(long long)(T - O), -sbits);
+  }
+  if (o.inflow) o.inflow[c] = vi;
+  if (o.load) o.load[c] = vl;
+  if (o.outflow) o.outflow[c] = vo;
+  if (o.retained) o.retained[c] = vr;
 }
 
 // the workspace: control words, one word and one queue slot per cell and, with `edges`, one byte per cell

@@ -18,6 +18,8 @@
 //             everything queued behind it would wait (measured: DESIGN.md 4.11).  The receivers' angles are asked for
 //             beside the atomics.
 // k_di_out    nodata is read from the angle raster.
+// The three are templates on dt_countdown.h's transfer mode: CD_T_NONE is the accumulation (no parameter raster is
+// read), the others are routing.py's decay / retain / limit, which split O = cd_transfer(T) and write up to four rasters.
 #include <cmath>
 
 #include "dt_countdown.h"
@@ -126,8 +128,11 @@ __global__ __launch_bounds__(256) void k_dinf(const float *__restrict__ dem, con
 }
 
 // ---- accumulation --------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle, const double *__restrict__ wt, int H,
-                                                 int W, int tiles_x, int vec_ok, int sbits, unsigned long long qmax,
+// MODE: dt_countdown.h's transfer mode; a routing run (MODE != CD_T_NONE) checks its parameter raster here
+template <int MODE>
+__global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle, const double *__restrict__ wt,
+                                                 const double *__restrict__ param, int H, int W, int tiles_x,
+                                                 int vec_ok, int sbits, unsigned long long qmax,
                                                  unsigned long long *__restrict__ word, uint32_t *__restrict__ ctl,
                                                  int *__restrict__ status) {
   __shared__ __attribute__((aligned(16))) float t[(DI_TY + 2) * DI_LDW];
@@ -137,7 +142,7 @@ __global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle
   __syncthreads();
   const int cx = ((int)threadIdx.x & 31) * 4, ly = (int)threadIdx.x >> 5;
   const int gy = y0 + ly, gx = x0 + cx;
-  bool bad_a = false, bad_w = false;
+  bool bad_a = false, bad_w = false, bad_p = false;
   uint32_t two = 0u;
   if (gy < H && gx < W) {
     float a[6], b[6], c[6];
@@ -167,12 +172,14 @@ __global__ __launch_bounds__(256) void k_di_init(const float *__restrict__ angle
         if (d.kind >= 1 && n[d.k] != DT_NODATA) wv |= DI_F_E0;
         if (d.kind == 2 && n[(d.k + 1) & 7] != DT_NODATA) wv |= DI_F_E1;
         two += d.kind == 2 ? 1u : 0u;
+        if (MODE != CD_T_NONE) (void)cd_transfer(MODE, 0ull, param, o + k, sbits, bad_p);
       }
       word[o + k] = wv;
     }
   }
-  if (status && (bad_a || bad_w))
-    atomicOr(status, (bad_a ? DT_STATUS_BAD_ANGLE : 0) | (bad_w ? DT_STATUS_BAD_WEIGHT : 0));
+  if (status && (bad_a || bad_w || bad_p))
+    atomicOr(status, (bad_a ? DT_STATUS_BAD_ANGLE : 0) | (bad_w ? DT_STATUS_BAD_WEIGHT : 0) |
+                         (bad_p ? DT_STATUS_BAD_PARAM : 0));
   if (two) atomicAdd(&ctl[CD_C_MULTI], two);
 }
 
@@ -182,9 +189,12 @@ __device__ __forceinline__ unsigned long long di_share(unsigned long long T, uin
   return (hi << 34) | (lo >> 30);
 }
 
-template <bool SCAN>
-__global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle, unsigned long long *word, int H,
-                                                 int W, uint32_t *queue, uint32_t *ctl, int cap, int moves_max) {
+// MODE != CD_T_NONE: the cell splits O = cd_transfer(T) instead of T; a cell's parameter travels with its angle (asked
+// for wherever the angle is: at a start, beside the atomics for the receivers, at a pop)
+template <bool SCAN, int MODE>
+__global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle, const double *__restrict__ param,
+                                                 int sbits, unsigned long long *word, int H, int W, uint32_t *queue,
+                                                 uint32_t *ctl, int cap, int moves_max) {
   __shared__ uint32_t s_stack[DI_STACK * 256];
   const uint32_t lo = SCAN ? 0u : ctl[CD_C_LO], hi = SCAN ? (uint32_t)((long long)H * W) : ctl[CD_C_HI];
   for (unsigned long long i = (unsigned long long)lo + (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < hi;
@@ -200,14 +210,16 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
       wv = __hip_atomic_load(&word[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     float ac = angle[c];
+    double pc = MODE != CD_T_NONE ? param[c] : 0.0;
     int sp = 0;
-    for (int moves = 0;;) {  // c is complete, wv is its word and ac its angle
+    for (int moves = 0;;) {  // c is complete, wv is its word, ac its angle and pc its parameter
       uint32_t next = CD_NONE;
       unsigned long long nextw = 0ull;
       float nexta = 0.0f;
+      double nextp = 0.0;
       if (wv & (DI_F_E0 | DI_F_E1)) {
-        const unsigned long long T = wv & CD_SUM_MASK;
         bool ignore = false;
+        const unsigned long long T = cd_transfer_value(MODE, wv & CD_SUM_MASK, pc, sbits, ignore);
         const DiDec d = di_decode(ac, ignore);
         const unsigned long long m2 = d.kind == 2 ? di_share(T, d.p2) : 0ull;
         const unsigned long long m1 = T - m2;
@@ -215,12 +227,14 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
         // move then costs one memory round trip, not two in a row
         uint32_t rr[2];
         float ra[2];
+        double rp[2] = {0.0, 0.0};
 #pragma unroll
         for (int e = 0; e < 2; e++) {
           const int k = (d.k + e) & 7;
           const int dx = (int)((DI_DX_PACK >> (2 * k)) & 3u) - 1, dy = (int)((DI_DY_PACK >> (2 * k)) & 3u) - 1;
           rr[e] = (uint32_t)((long long)c + (long long)dy * W + dx);
           ra[e] = (wv & (e ? DI_F_E1 : DI_F_E0)) ? angle[rr[e]] : 0.0f;
+          if (MODE != CD_T_NONE) rp[e] = (wv & (e ? DI_F_E1 : DI_F_E0)) ? param[rr[e]] : 0.0;
         }
         // both atomics are in flight before either answer is looked at
         unsigned long long add[2], old[2] = {0ull, 0ull};
@@ -237,6 +251,7 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
             next = r;
             nextw = old[e] + add[e];
             nexta = ra[e];
+            nextp = rp[e];
           } else if (sp < cap) {
             s_stack[sp++ * 256 + threadIdx.x] = r;
           } else {
@@ -253,10 +268,12 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
         c = next;
         wv = nextw;
         ac = nexta;
+        pc = nextp;
       } else if (sp > 0) {
         c = s_stack[--sp * 256 + threadIdx.x];
         wv = __hip_atomic_load(&word[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ac = angle[c];
+        if (MODE != CD_T_NONE) pc = param[c];
       } else {
         break;
       }
@@ -264,20 +281,24 @@ __global__ __launch_bounds__(256) void k_di_flow(const float *__restrict__ angle
   }
 }
 
+// MODE == CD_T_NONE writes the accumulation (o.inflow alone, never NULL); a routing run any subset of the four
+template <int MODE>
 __global__ __launch_bounds__(256) void k_di_out(const float *__restrict__ angle, const double *__restrict__ wt,
+                                                const double *__restrict__ param,
                                                 const unsigned long long *__restrict__ word, long long N, int sbits,
                                                 unsigned long long qmax, const uint32_t *__restrict__ ctl,
-                                                double *__restrict__ out, int *__restrict__ status) {
+                                                CdRouteOut o, int *__restrict__ status) {
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   cd_not_converged(c == 0, ctl, status);
   if (c >= N) return;
   const unsigned long long wv = word[c];
-  double v = -100.0;
-  if (angle[c] != DT_NODATA && cd_pending(wv) == 0ull) {
-    bool ignore = false;
-    v = cd_result(wv, cd_quant(wt, c, sbits, qmax, ignore), sbits);
+  const bool complete = angle[c] != DT_NODATA && cd_pending(wv) == 0ull;
+  bool ignore = false;
+  if (MODE == CD_T_NONE) {
+    o.inflow[c] = complete ? cd_result(wv, cd_quant(wt, c, sbits, qmax, ignore), sbits) : -100.0;
+    return;
   }
-  out[c] = v;
+  cd_route_store(MODE, o, c, complete, wv, complete ? cd_quant(wt, c, sbits, qmax, ignore) : 0ull, param, sbits);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
@@ -299,11 +320,11 @@ int dt_launch_dinf_direction(hipStream_t s, const float *dem, const uint8_t *fdr
   return DT_OK;
 }
 
-// start, rounds and finish: cd_run's
-int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *wt, int64_t H, int64_t W, int frac_bits,
-                              int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
-                              double *out, int *status) {
-  if (H == 0 || W == 0) return DT_OK;
+// one countdown run of the mode: start, rounds and finish are cd_run's
+template <int MODE>
+static int di_run(hipStream_t s, const float *angle, const double *wt, const double *param, int64_t H, int64_t W,
+                  int frac_bits, int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
+                  CdRouteOut o, int *status) {
   const int64_t N = H * W;
   const CdLayout L = cd_layout(N, scratch, false);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
@@ -315,14 +336,46 @@ int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *w
       [&] {
         int tiles_x;
         const unsigned nt = di_tiles(H, W, tiles_x);
-        hipLaunchKernelGGL(k_di_init, dim3(nt), b, 0, s, angle, wt, (int)H, (int)W, tiles_x, di_vec_ok(angle, W),
-                           frac_bits, qmax, L.word, L.ctl, status);
+        hipLaunchKernelGGL(k_di_init<MODE>, dim3(nt), b, 0, s, angle, wt, param, (int)H, (int)W, tiles_x,
+                           di_vec_ok(angle, W), frac_bits, qmax, L.word, L.ctl, status);
       },
       [&](bool scan, dim3 g) {
-        auto *flow = scan ? k_di_flow<true> : k_di_flow<false>;
-        hipLaunchKernelGGL(flow, g, b, 0, s, angle, L.word, (int)H, (int)W, L.queue, L.ctl, cap, DI_MOVES);
+        auto *flow = scan ? k_di_flow<true, MODE> : k_di_flow<false, MODE>;
+        hipLaunchKernelGGL(flow, g, b, 0, s, angle, param, frac_bits, L.word, (int)H, (int)W, L.queue, L.ctl, cap,
+                           DI_MOVES);
       },
       [&](dim3 g) {
-        hipLaunchKernelGGL(k_di_out, g, b, 0, s, angle, wt, L.word, (long long)N, frac_bits, qmax, L.ctl, out, status);
+        hipLaunchKernelGGL(k_di_out<MODE>, g, b, 0, s, angle, wt, param, L.word, (long long)N, frac_bits, qmax, L.ctl,
+                           o, status);
       });
+}
+
+int dt_launch_dinf_accumulate(hipStream_t s, const float *angle, const double *wt, int64_t H, int64_t W, int frac_bits,
+                              int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
+                              double *out, int *status) {
+  if (H == 0 || W == 0) return DT_OK;
+  return di_run<CD_T_NONE>(s, angle, wt, nullptr, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                           scratch_bytes, CdRouteOut{out, nullptr, nullptr, nullptr}, status);
+}
+
+int dt_launch_dinf_route(hipStream_t s, const float *angle, const double *wt, const double *param, int64_t H,
+                         int64_t W, int frac_bits, int mode, int start, int rounds, int finish, int stack_cap,
+                         void *scratch, size_t scratch_bytes, double *inflow, double *load, double *outflow,
+                         double *retained, int *status) {
+  if (H == 0 || W == 0) return DT_OK;
+  DT_REQUIRE(param != nullptr, "NULL parameter raster");
+  const CdRouteOut o = {inflow, load, outflow, retained};
+  switch (mode) {
+    case CD_T_DECAY:
+      return di_run<CD_T_DECAY>(s, angle, wt, param, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                                scratch_bytes, o, status);
+    case CD_T_RETAIN:
+      return di_run<CD_T_RETAIN>(s, angle, wt, param, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                                 scratch_bytes, o, status);
+    case CD_T_LIMIT:
+      return di_run<CD_T_LIMIT>(s, angle, wt, param, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                                scratch_bytes, o, status);
+  }
+  DT_REQUIRE(false, "mode must be DT_ROUTE_DECAY, DT_ROUTE_RETAIN or DT_ROUTE_LIMIT");
+  return DT_EINVAL;
 }

@@ -346,6 +346,21 @@ int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double
 // the accumulation's control words in `scratch`, as dt_dinf_accumulate_ctl's (cells with two or more receivers)
 const uint32_t *dt_mfd_accumulate_ctl(void *scratch, int64_t H, int64_t W);
 
+// Routing (routing.py holds the definition): the same countdowns with a transfer function between "complete" and
+// "split": a complete cell with load T passes on O = f(T, param) <= T (mode: DT_ROUTE_DECAY / _RETAIN / _LIMIT) and the
+// receivers get the op's split of O.  The workspace, the control words and start / rounds / finish / stack_cap are the
+// accumulation's (the *_accumulate_scratch and *_accumulate_ctl functions serve both); the out step writes any of
+// inflow (T - q), load (T), outflow (O) and retained (T - O), a NULL pointer is an output not wanted.  A parameter
+// outside its contract raises DT_STATUS_BAD_PARAM on `status` and acts as the identity.  Nothing synchronises.
+int dt_launch_dinf_route(hipStream_t s, const float *angle, const double *wt, const double *param, int64_t H,
+                         int64_t W, int frac_bits, int mode, int start, int rounds, int finish, int stack_cap,
+                         void *scratch, size_t scratch_bytes, double *inflow, double *load, double *outflow,
+                         double *retained, int *status);
+int dt_launch_mfd_route(hipStream_t s, const uint16_t *shares, const double *wt, const double *param, int64_t H,
+                        int64_t W, int frac_bits, int mode, int start, int rounds, int finish, int stack_cap,
+                        void *scratch, size_t scratch_bytes, double *inflow, double *load, double *outflow,
+                        double *retained, int *status);
+
 // Local terrain attributes (dt_terrain.hip; terrain.py holds the definition): the quadratic fitted by least squares
 // over the (2 radius + 1)^2 window of every cell, from separable float64 moment sums, and what is derived from its
 // first and second derivatives.  out[8] = gradient, aspect, profile, plan, tangential, mean, laplacian, hillshade

@@ -22,6 +22,8 @@
 //             path runs through cells that a lane following one branch to its end would leave waiting.  A start
 //             completes at most MF_MOVES = 32 cells in a round (both measured: DESIGN.md 4.15).
 // k_mf_out    nodata is read from the word.
+// The three are templates on dt_countdown.h's transfer mode: CD_T_NONE is the accumulation (no parameter raster is
+// read), the others are routing.py's decay / retain / limit, which split O = cd_transfer(T) and write up to four rasters.
 #include <cmath>
 
 #include "dt_countdown.h"
@@ -160,8 +162,11 @@ __device__ __forceinline__ uint32_t mf_classify(const uint4 w) {
 }
 
 #define MF_TW (DI_TX + 2)  // the classified tile: (DI_TY + 2) rows of DI_TX + 2 cells
+// MODE: dt_countdown.h's transfer mode; a routing run (MODE != CD_T_NONE) checks its parameter raster here
+template <int MODE>
 __global__ __launch_bounds__(256) void k_mf_init(const uint4 *__restrict__ shares, const double *__restrict__ wt,
-                                                 int H, int W, int tiles_x, int sbits, unsigned long long qmax,
+                                                 const double *__restrict__ param, int H, int W, int tiles_x,
+                                                 int sbits, unsigned long long qmax,
                                                  unsigned long long *__restrict__ word, uint8_t *__restrict__ edges,
                                                  uint32_t *__restrict__ ctl, int *__restrict__ status) {
   __shared__ uint16_t t[(DI_TY + 2) * MF_TW];
@@ -175,7 +180,7 @@ __global__ __launch_bounds__(256) void k_mf_init(const uint4 *__restrict__ share
     t[i] = (uint16_t)cl;
   }
   __syncthreads();
-  bool bad_s = false, bad_w = false;
+  bool bad_s = false, bad_w = false, bad_p = false;
   uint32_t multi = 0u;
 #pragma unroll
   for (int v = 0; v < 4; v++) {
@@ -200,12 +205,14 @@ __global__ __launch_bounds__(256) void k_mf_init(const uint4 *__restrict__ share
       multi += __popc(me & 0xFFu) >= 2 ? 1u : 0u;
       wv = cd_quant(wt, o, sbits, qmax, bad_w) | ((unsigned long long)pending << 56);
       if (pending == 0u) wv |= CD_F_SRC;
+      if (MODE != CD_T_NONE) (void)cd_transfer(MODE, 0ull, param, o, sbits, bad_p);
     }
     word[o] = wv;
     edges[o] = (uint8_t)emask;
   }
-  if (status && (bad_s || bad_w))
-    atomicOr(status, (bad_s ? DT_STATUS_BAD_SHARES : 0) | (bad_w ? DT_STATUS_BAD_WEIGHT : 0));
+  if (status && (bad_s || bad_w || bad_p))
+    atomicOr(status, (bad_s ? DT_STATUS_BAD_SHARES : 0) | (bad_w ? DT_STATUS_BAD_WEIGHT : 0) |
+                         (bad_p ? DT_STATUS_BAD_PARAM : 0));
   if (multi) atomicAdd(&ctl[CD_C_MULTI], multi);
 }
 
@@ -221,8 +228,10 @@ __device__ __forceinline__ void mf_enqueue(uint32_t *queue, uint32_t *ctl, uint3
   if (i < n) queue[i] = c;
 }
 
-template <bool SCAN>
+// MODE != CD_T_NONE: the cell splits O = cd_transfer(T) instead of T; its parameter is asked for beside its shares
+template <bool SCAN, int MODE>
 __global__ __launch_bounds__(256) void k_mf_flow(const uint4 *__restrict__ shares, const uint8_t *__restrict__ edges,
+                                                 const double *__restrict__ param, int sbits,
                                                  unsigned long long *word, int W, uint32_t n, uint32_t *queue,
                                                  uint32_t *ctl, int cap, int moves_max) {
   __shared__ uint32_t s_ring[MF_STACK * 256];
@@ -245,9 +254,14 @@ __global__ __launch_bounds__(256) void k_mf_flow(const uint4 *__restrict__ share
       unsigned long long nextw = 0ull;
       const uint32_t em = edges[c];
       if (em) {
-        const unsigned long long T = wv & CD_SUM_MASK;
+        unsigned long long T = wv & CD_SUM_MASK;
+        const uint4 sw = shares[c];
+        if (MODE != CD_T_NONE) {
+          bool ignore = false;
+          T = cd_transfer(MODE, T, param, c, sbits, ignore);
+        }
         uint32_t P[8];
-        mf_unpack(shares[c], P);
+        mf_unpack(sw, P);
         int mk = 0;
         uint32_t pbest = 0u;
 #pragma unroll
@@ -313,20 +327,23 @@ __global__ __launch_bounds__(256) void k_mf_flow(const uint4 *__restrict__ share
   }
 }
 
-__global__ __launch_bounds__(256) void k_mf_out(const double *__restrict__ wt,
+// MODE == CD_T_NONE writes the accumulation (o.inflow alone, never NULL); a routing run any subset of the four
+template <int MODE>
+__global__ __launch_bounds__(256) void k_mf_out(const double *__restrict__ wt, const double *__restrict__ param,
                                                 const unsigned long long *__restrict__ word, long long N, int sbits,
                                                 unsigned long long qmax, const uint32_t *__restrict__ ctl,
-                                                double *__restrict__ out, int *__restrict__ status) {
+                                                CdRouteOut o, int *__restrict__ status) {
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   cd_not_converged(c == 0, ctl, status);
   if (c >= N) return;
   const unsigned long long wv = word[c];
-  double v = -100.0;
-  if (!(wv & MF_F_NODATA) && cd_pending(wv) == 0ull) {
-    bool ignore = false;
-    v = cd_result(wv, cd_quant(wt, c, sbits, qmax, ignore), sbits);
+  const bool complete = !(wv & MF_F_NODATA) && cd_pending(wv) == 0ull;
+  bool ignore = false;
+  if (MODE == CD_T_NONE) {
+    o.inflow[c] = complete ? cd_result(wv, cd_quant(wt, c, sbits, qmax, ignore), sbits) : -100.0;
+    return;
   }
-  out[c] = v;
+  cd_route_store(MODE, o, c, complete, wv, complete ? cd_quant(wt, c, sbits, qmax, ignore) : 0ull, param, sbits);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
@@ -355,11 +372,11 @@ int dt_launch_mfd_shares(hipStream_t s, const float *dem, const uint8_t *fdr, in
   return DT_OK;
 }
 
-// start, rounds and finish: cd_run's
-int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double *wt, int64_t H, int64_t W,
-                             int frac_bits, int start, int rounds, int finish, int stack_cap, void *scratch,
-                             size_t scratch_bytes, double *out, int *status) {
-  if (H == 0 || W == 0) return DT_OK;
+// one countdown run of the mode: start, rounds and finish are cd_run's
+template <int MODE>
+static int mf_run(hipStream_t s, const uint16_t *shares, const double *wt, const double *param, int64_t H, int64_t W,
+                  int frac_bits, int start, int rounds, int finish, int stack_cap, void *scratch, size_t scratch_bytes,
+                  CdRouteOut o, int *status) {
   const int64_t N = H * W;
   const CdLayout L = cd_layout(N, scratch, true);
   DT_REQUIRE(scratch_bytes >= L.bytes, "scratch too small");
@@ -373,14 +390,46 @@ int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double
       [&] {
         int tiles_x;
         const unsigned nt = di_tiles(H, W, tiles_x);
-        hipLaunchKernelGGL(k_mf_init, dim3(nt), b, 0, s, sh, wt, (int)H, (int)W, tiles_x, frac_bits, qmax, L.word,
-                           L.edges, L.ctl, status);
+        hipLaunchKernelGGL(k_mf_init<MODE>, dim3(nt), b, 0, s, sh, wt, param, (int)H, (int)W, tiles_x, frac_bits, qmax,
+                           L.word, L.edges, L.ctl, status);
       },
       [&](bool scan, dim3 g) {
-        auto *flow = scan ? k_mf_flow<true> : k_mf_flow<false>;
-        hipLaunchKernelGGL(flow, g, b, 0, s, sh, L.edges, L.word, (int)W, (uint32_t)N, L.queue, L.ctl, cap, MF_MOVES);
+        auto *flow = scan ? k_mf_flow<true, MODE> : k_mf_flow<false, MODE>;
+        hipLaunchKernelGGL(flow, g, b, 0, s, sh, L.edges, param, frac_bits, L.word, (int)W, (uint32_t)N, L.queue,
+                           L.ctl, cap, MF_MOVES);
       },
       [&](dim3 g) {
-        hipLaunchKernelGGL(k_mf_out, g, b, 0, s, wt, L.word, (long long)N, frac_bits, qmax, L.ctl, out, status);
+        hipLaunchKernelGGL(k_mf_out<MODE>, g, b, 0, s, wt, param, L.word, (long long)N, frac_bits, qmax, L.ctl, o,
+                           status);
       });
+}
+
+int dt_launch_mfd_accumulate(hipStream_t s, const uint16_t *shares, const double *wt, int64_t H, int64_t W,
+                             int frac_bits, int start, int rounds, int finish, int stack_cap, void *scratch,
+                             size_t scratch_bytes, double *out, int *status) {
+  if (H == 0 || W == 0) return DT_OK;
+  return mf_run<CD_T_NONE>(s, shares, wt, nullptr, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                           scratch_bytes, CdRouteOut{out, nullptr, nullptr, nullptr}, status);
+}
+
+int dt_launch_mfd_route(hipStream_t s, const uint16_t *shares, const double *wt, const double *param, int64_t H,
+                        int64_t W, int frac_bits, int mode, int start, int rounds, int finish, int stack_cap,
+                        void *scratch, size_t scratch_bytes, double *inflow, double *load, double *outflow,
+                        double *retained, int *status) {
+  if (H == 0 || W == 0) return DT_OK;
+  DT_REQUIRE(param != nullptr, "NULL parameter raster");
+  const CdRouteOut o = {inflow, load, outflow, retained};
+  switch (mode) {
+    case CD_T_DECAY:
+      return mf_run<CD_T_DECAY>(s, shares, wt, param, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                                scratch_bytes, o, status);
+    case CD_T_RETAIN:
+      return mf_run<CD_T_RETAIN>(s, shares, wt, param, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                                 scratch_bytes, o, status);
+    case CD_T_LIMIT:
+      return mf_run<CD_T_LIMIT>(s, shares, wt, param, H, W, frac_bits, start, rounds, finish, stack_cap, scratch,
+                                scratch_bytes, o, status);
+  }
+  DT_REQUIRE(false, "mode must be DT_ROUTE_DECAY, DT_ROUTE_RETAIN or DT_ROUTE_LIMIT");
+  return DT_EINVAL;
 }

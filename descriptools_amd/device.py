@@ -196,6 +196,9 @@ class Context:
             raise RuntimeError("dt_dev_cost_distance left a reached cell without a back-link: rounding absorbed a "
                                "whole edge cost (DT_STATUS_NO_BACKLINK); backlink is 0 and indices -100 there and "
                                "upstream of it")
+        if st & 512:
+            raise ValueError("dt_dev_mfd_route or dt_dev_dinf_route met a parameter that is NaN, negative or (decay) "
+                             "above 1 (DT_STATUS_BAD_PARAM): that cell passed its whole load on")
 
     def fork(self, child):
         """`child`'s stream waits (on the device) for everything enqueued so far on this context's stream."""
