@@ -147,6 +147,22 @@ __device__ __forceinline__ uint32_t dt_block_scan_256(uint32_t v, uint32_t *s_w,
   return before + x - v;
 }
 
+// The fixed-point weight of the integer sums (weighted flow accumulation, the countdowns, the path sums): q = rint(v *
+// 2^sbits), exact scaling and round half to even.  A weight that is negative, not finite or over qmax is `bad` and
+// counts as 0.
+__device__ __forceinline__ unsigned long long dt_quant_weight(double v, int sbits, unsigned long long qmax, bool &bad) {
+  if (!(v >= 0.0)) {  // negative or NaN
+    bad = true;
+    return 0ull;
+  }
+  const double q = rint(ldexp(v, sbits));
+  if (!(q <= (double)qmax)) {  // inf, or over the bound
+    bad = true;
+    return 0ull;
+  }
+  return (unsigned long long)q;
+}
+
 // four consecutive values of a float32 / float64 raster, 16-byte loads (f a multiple of 4, the raster 16-byte aligned)
 template <typename HT>
 __device__ __forceinline__ void dt_load4(const HT *__restrict__ src, int64_t f, HT (&hh)[4]) {

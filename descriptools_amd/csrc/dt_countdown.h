@@ -47,20 +47,10 @@ enum { CD_C_TAIL = 0, CD_C_LO = 1, CD_C_HI = 2, CD_C_ROUNDS = 3, CD_C_HIGH = 4, 
 // donors of the word's cell that have not arrived yet
 __device__ __forceinline__ unsigned long long cd_pending(unsigned long long wv) { return (wv >> 56) & 0xFull; }
 
-// q = rint(w * 2^s), flowacc_weighted's rule: a weight outside the contract is bad and counts as 0
+// dt_quant_weight of cell c's weight; wt NULL: 1 everywhere
 __device__ __forceinline__ unsigned long long cd_quant(const double *__restrict__ wt, long long c, int sbits,
                                                        unsigned long long qmax, bool &bad) {
-  const double v = wt ? wt[c] : 1.0;
-  if (!(v >= 0.0)) {
-    bad = true;
-    return 0ull;
-  }
-  const double q = rint(ldexp(v, sbits));
-  if (!(q <= (double)qmax)) {
-    bad = true;
-    return 0ull;
-  }
-  return (unsigned long long)q;
+  return dt_quant_weight(wt ? wt[c] : 1.0, sbits, qmax, bad);
 }
 
 // the out kernels, one lane of them (`first`): queued work is left

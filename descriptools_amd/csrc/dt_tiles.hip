@@ -958,19 +958,6 @@ int dt_launch_fa_finish(hipStream_t s, const DtWin &w, const uint8_t *fdr, const
 #define FAW_LOC_CYC (~0ull)       /* in-tile sum of a cell on an in-tile D8 cycle */
 #define FAW_CYC (1ull << 63)      /* delta raster: the cell lies on a D8 cycle spanning tiles */
 
-__device__ __forceinline__ unsigned long long faw_quant(double v, int sbits, unsigned long long qmax, bool &bad) {
-  if (!(v >= 0.0)) {  // negative or NaN
-    bad = true;
-    return 0ull;
-  }
-  const double q = rint(ldexp(v, sbits));  // exact scaling, round half to even
-  if (!(q <= (double)qmax)) {              // inf, or over the bound
-    bad = true;
-    return 0ull;
-  }
-  return (unsigned long long)q;
-}
-
 // 45 KiB of LDS: three tiles per CU
 __global__ __launch_bounds__(256, 3) void k_faw_tile1(const uint8_t *__restrict__ fdr, const double *__restrict__ wt,
                                                      DtWin w, int tiles_x, int sbits, unsigned long long qmax,
@@ -997,7 +984,7 @@ __global__ __launch_bounds__(256, 3) void k_faw_tile1(const uint8_t *__restrict_
     const int c = threadIdx.x + 256 * j;
     const int y = y0 + c / TW, x = x0 + c % TW;
     const double wv = (y < w.H && x < w.W) ? wt[(long long)y * w.ld + x] : 0.0;
-    q[j] = faw_quant(wv, sbits, qmax, bad);
+    q[j] = dt_quant_weight(wv, sbits, qmax, bad);
   }
   if (bad && status) atomicOr(status, DT_STATUS_BAD_WEIGHT);
   dt_tile_put16(s_fdr, v_fdr);

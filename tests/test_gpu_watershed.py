@@ -258,3 +258,67 @@ def test_device_tier_on_chain_fdr_and_null_outputs():
     t, l, _ = R.drainage(fdr, 10.0)
     np.testing.assert_array_equal(runs[0][0], t)
     np.testing.assert_array_equal(runs[0][1], R.upslope_length(fdr, 10.0))
+
+
+def test_one_graph_for_every_path_operator():
+    """drainage, the downstream extreme and the downstream sum stop on the same graph (dt_path_tiles.h's pt_classify):
+    with pour = stop, the cells with a target, with a `where` and with a sum are one set, on the host tier and on the
+    device tier, and `where` of the raster that is 1 on the stop cells is the target.  130 x 67 is 3 x 2 tiles, both
+    edges partial; the field has diagonal moves, in-tile cycles, a ring of 200 cells through four tiles (planted again
+    over the nodata, so it crosses a tile border in both directions), nodata, codes that point out of the raster, stops
+    on nodata (ignored) and a stop on the ring."""
+    import _pathsum_ref as PR
+    from descriptools_amd import _lib, device, flowpath as fp, watershed as ws
+    H, W = 130, 67
+    fdr, dem = PR.field(H, W, 24, cycles=6, nodata=True, ring=(50, 50))
+    y0, x0 = H // 3, W // 4
+    ring = np.zeros((H, W), bool)
+    ring[y0, x0:x0 + 50], fdr[y0, x0:x0 + 50] = True, R.E
+    ring[y0:y0 + 50, x0 + 50], fdr[y0:y0 + 50, x0 + 50] = True, R.S
+    ring[y0 + 50, x0 + 1:x0 + 51], fdr[y0 + 50, x0 + 1:x0 + 51] = True, R.W_
+    ring[y0 + 1:y0 + 51, x0], fdr[y0 + 1:y0 + 51, x0] = True, R.N
+    dem[ring] = 1.0
+    nod = dem <= -100
+    on_cycle = (R.upslope_length(fdr, 1.0, dem) == -100) & ~nod
+    # the whole ring is a cycle of valid cells through four tiles, and there are cycles beside it
+    assert ring.sum() == 200 and on_cycle[ring].all() and (on_cycle & ~ring).sum() >= 4
+    assert {(y // 64, x // 64) for y, x in np.argwhere(ring)} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    rng = np.random.default_rng(1024)
+    stop = (rng.random((H, W)) < 0.01).astype(np.uint8)
+    on_nodata = np.argwhere(nod)[::50]
+    stop[on_nodata[:, 0], on_nodata[:, 1]] = 1
+    stop[ring] = 0
+    stop[y0, 20] = 1  # the one stop on the ring
+    assert len(on_nodata) > 10
+    pour = stop.astype(np.int64)
+    values = stop.astype(np.float32)
+    weights = rng.random((H, W))
+
+    def same_set(target, where, total):
+        has = target >= 0
+        np.testing.assert_array_equal(where >= 0, has)
+        np.testing.assert_array_equal(total != -100, has)
+        assert has.any() and not has.all()
+        np.testing.assert_array_equal(where[has], target[has])
+        assert has[ring].all() and not has[nod].any()
+
+    same_set(ws.drainage(fdr, 1.0, dem, pour).target,
+             fp.downstream_extreme(fdr, values, "max", dem, stop, where=True).where,
+             fp.downstream_sum(fdr, weights, dem, stop))
+
+    ctx = device.Context()
+    L = _lib.lib()
+    ins = [ctx.to_device(a) for a in (fdr, _lib.nodata_mask(dem, fdr.shape), pour, stop, values, weights)]
+    f_d, d_d, p_d, s_d, v_d, w_d = (a.ptr for a in ins)
+    tg_d, wh_d, sum_d = ctx.empty((H, W), np.int64), ctx.empty((H, W), np.int64), ctx.empty((H, W), np.float64)
+    try:
+        _lib.check(L.dt_dev_drainage(ctx.h, f_d, d_d, p_d, H, W, 1.0, tg_d.ptr, None, None))
+        _lib.check(L.dt_dev_flowpath_downstream(ctx.h, f_d, d_d, v_d, s_d, H, W, 0, None, wh_d.ptr))
+        _lib.check(L.dt_dev_flowpath_downstream_sum(ctx.h, f_d, d_d, w_d, s_d, H, W, fp.path_frac_bits(weights),
+                                                    sum_d.ptr))
+        ctx.sync()
+        same_set(tg_d.to_host(), wh_d.to_host(), sum_d.to_host())
+    finally:
+        for a in ins + [tg_d, wh_d, sum_d]:
+            a.free()
+        ctx.close()
