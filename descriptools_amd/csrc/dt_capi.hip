@@ -888,6 +888,16 @@ extern "C" int dt_dev_wetness_index(dt_ctx *c, const double *modified, const flo
   return d.done(dt_launch_wetness_index(c->stream, modified, slope, H * W, offset, minimum, swi));
 }
 
+// resampling: the two rasters have shapes of their own, so the call opens on the context alone and
+// dt_check_resample holds the shape rules
+extern "C" int dt_dev_resample(dt_ctx *c, const void *src, int dtype, int64_t Hs, int64_t Ws, const double *matrix,
+                               int method, int64_t nodata, uint64_t fill_bits, void *dst, int64_t Hd, int64_t Wd) {
+  DT_DEV(d, c);
+  DT_TRY(dt_check_resample(dtype, Hs, Ws, matrix, method, nodata, Hd, Wd));
+  DT_REQUIRE(src && dst, "NULL raster");
+  return d.done(dt_launch_resample(c->stream, src, dtype, Hs, Ws, matrix, method, nodata, fill_bits, dst, Hd, Wd));
+}
+
 // geodesic reconstruction: what both tiers require of the marker mode and its parameters
 static int dt_check_morph(int mode, int erosion, int connectivity, double h, int radius, int visit_limit) {
   DT_REQUIRE(mode >= DT_MORPH_MARKER && mode <= DT_MORPH_WINDOW, "mode must be one of DT_MORPH_*");
@@ -3199,6 +3209,22 @@ extern "C" int dt_wetness_saga(const double *area, const float *slope, int64_t H
   DT_TRY(hc.finish());
   if (info4) memcpy(info4, cnt4, sizeof(cnt4));
   return DT_OK;
+}
+
+// resampling: a bad argument is refused before the device is asked for
+extern "C" int dt_resample(const void *src, int dtype, int64_t Hs, int64_t Ws, const double *matrix, int method,
+                           int64_t nodata, uint64_t fill_bits, void *dst, int64_t Hd, int64_t Wd) {
+  DT_TRY(dt_check_resample(dtype, Hs, Ws, matrix, method, nodata, Hd, Wd));
+  DT_REQUIRE(src && dst, "NULL raster");
+  HostCall hc;
+  DT_TRY(hc.rc);
+  const size_t es = dtype == 32 ? 4 : dtype == 64 ? 8 : (size_t)dtype;
+  const unsigned char *d_src = hc.in((const unsigned char *)src, (size_t)Hs * Ws * es);
+  unsigned char *d_dst = hc.out((unsigned char *)dst, (size_t)Hd * Wd * es);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_launched(dt_launch_resample(hc.c->stream, d_src, dtype, Hs, Ws, matrix, method, nodata, fill_bits, d_dst,
+                                        Hd, Wd)));
+  return hc.finish();
 }
 
 // geodesic reconstruction: batches of rounds until a quiet one, then the output and the counts

@@ -621,3 +621,12 @@ int dt_launch_zonal_counts(hipStream_t s, const int32_t *zones, const void *valu
                            void *scratch, size_t scratch_bytes, int64_t *counts, int *status, int slots);
 int dt_launch_zonal_paint(hipStream_t s, const void *table, int elem_bytes, int64_t n_table, const int32_t *zones,
                           int64_t N, uint64_t fill_bits, void *out);
+
+// Resampling (dt_resample.hip; resample.py holds the definition).  dt_check_resample: what both tiers require of a
+// call, pointers aside; each entry runs it once.  dt_launch_resample takes arguments that have passed it and launches
+// one kernel: the six matrix entries are read from the host pointer and passed by value.  Nothing synchronises, nothing
+// is allocated.
+int dt_check_resample(int dtype, int64_t Hs, int64_t Ws, const double *matrix, int method, int64_t nodata, int64_t Hd,
+                      int64_t Wd);
+int dt_launch_resample(hipStream_t s, const void *src, int dtype, int64_t Hs, int64_t Ws, const double *matrix,
+                       int method, int64_t nodata, uint64_t fill_bits, void *dst, int64_t Hd, int64_t Wd);
