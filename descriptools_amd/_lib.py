@@ -43,6 +43,7 @@ _SIGS = {
     "dt_graph_destroy": (ci, [vp]),
     "dt_ctx_status": (ci, [vp, c_i32p]),
     "dt_ctx_scratch_bytes": (i64, [vp]),
+    "dt_ctx_scratch_ptr": (vp, [vp]),
     # host tier
     "dt_slope_f32": (ci, [c_f32p, i64, i64, f64, c_f32p]),
     "dt_d8_f32": (ci, [c_f32p, i64, i64, f64, c_u8p, c_f32p]),
@@ -78,6 +79,8 @@ _SIGS = {
     "dt_wetness_modified_area": (ci, [c_f64p, c_f32p, i64, i64, ci, c_f64p, c_i64p]),
     "dt_wetness_saga": (ci, [c_f64p, c_f32p, i64, i64, f64, f64, f64, f64, ci, c_f32p, c_f64p, c_f32p, c_i64p]),
     "dt_resample": (ci, [vp, ci, i64, i64, c_f64p, ci, i64, C.c_uint64, vp, i64, i64]),
+    "dt_rasterize": (ci, [ci, c_f64p, c_i64p, c_i32p, i64, i64, i64, ci, ci, c_i32p, c_i64p]),
+    "dt_rasterize_count": (ci, [ci, c_f64p, c_i64p, i64, i64, i64, c_i64p, c_i64p]),
     "dt_morph_reconstruct": (ci, [ci, ci, ci, c_f32p, c_f32p, c_u8p, f64, ci, i64, i64, ci, c_f32p, c_u8p, c_i64p]),
     "dt_harmonic": (ci, [c_f32p, c_i8p, c_i8p, i64, i64, f64, ci, c_f64p, c_i64p]),
     "dt_inundation": (ci, [c_f32p, c_f32p, c_f32p, i64, i64, c_f64p, ci, c_i64p, c_f64p, c_f64p, ci, ci, i64, i64, ci,
@@ -150,6 +153,8 @@ _SIGS = {
     "dt_dev_wetness_modified_area": (ci, [vp, vp, vp, i64, i64, ci, ci, vp]),
     "dt_dev_wetness_index": (ci, [vp, vp, vp, i64, i64, f64, f64, vp]),
     "dt_dev_resample": (ci, [vp, vp, ci, i64, i64, c_f64p, ci, i64, C.c_uint64, vp, i64, i64]),
+    "dt_dev_rasterize": (ci, [vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, ci, i64, vp, vp]),
+    "dt_dev_rasterize_timed": (ci, [vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, ci, i64, vp, vp, c_f64p]),
     "dt_dev_morph_reconstruct": (ci, [vp, ci, ci, ci, vp, vp, vp, f64, ci, i64, i64, ci, ci, vp, vp]),
     "dt_dev_harmonic": (ci, [vp, vp, vp, vp, i64, i64, f64, ci, vp, vp]),
     "dt_dev_inundation": (ci, [vp, vp, vp, vp, i64, i64, c_f64p, ci, vp, vp, vp, ci, ci, i64, i64, vp, vp, vp, vp, vp,

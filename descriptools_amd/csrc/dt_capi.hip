@@ -237,6 +237,7 @@ extern "C" int dt_ctx_status(dt_ctx *c, int32_t *out) {
   return DT_OK;
 }
 extern "C" int64_t dt_ctx_scratch_bytes(dt_ctx *c) { return c ? (int64_t)c->scratch_bytes : 0; }
+extern "C" void *dt_ctx_scratch_ptr(dt_ctx *c) { return c ? (void *)c->scratch : nullptr; }
 
 int dt_scratch_reset(dt_ctx *c, size_t total) {
   total = dt_align256(total) + 256;
@@ -896,6 +897,59 @@ extern "C" int dt_dev_resample(dt_ctx *c, const void *src, int dtype, int64_t Hs
   DT_TRY(dt_check_resample(dtype, Hs, Ws, matrix, method, nodata, Hd, Wd));
   DT_REQUIRE(src && dst, "NULL raster");
   return d.done(dt_launch_resample(c->stream, src, dtype, Hs, Ws, matrix, method, nodata, fill_bits, dst, Hd, Wd));
+}
+
+// vector rasterisation: the geometry has a length of its own, so the call opens on the context alone and
+// dt_check_rasterize holds the rules; `capacity` crossing slots of scratch, which the kernels never write past
+static int dev_rasterize(dt_ctx *c, int kind, const double *coords, const int64_t *parts, const int32_t *ids, int64_t P,
+                         int64_t N, int64_t H, int64_t W, int connectivity, int all_touched, int64_t capacity,
+                         int32_t *label, int64_t *info, hipEvent_t *ev) {
+  DT_DEV(d, c);
+  DT_TRY(dt_check_rasterize(kind, P, N, H, W, connectivity, all_touched, capacity));
+  DT_REQUIRE(label && info, "NULL label or info");
+  DT_REQUIRE((coords && parts && ids) || P == 0 || N == 0, "NULL geometry");
+  const size_t need = dt_rasterize_scratch(H, capacity);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  DT_REQUIRE(scr, "scratch reservation failed");
+  return d.done(dt_launch_rasterize(c->stream, kind, coords, parts, ids, P, N, H, W, connectivity, all_touched, capacity,
+                                    scr, need, label, info, ev));
+}
+extern "C" int dt_dev_rasterize(dt_ctx *c, int kind, const double *coords, const int64_t *parts, const int32_t *ids,
+                                int64_t P, int64_t N, int64_t H, int64_t W, int connectivity, int all_touched,
+                                int64_t capacity, int32_t *label, int64_t *info) {
+  return dev_rasterize(c, kind, coords, parts, ids, P, N, H, W, connectivity, all_touched, capacity, label, info,
+                       nullptr);
+}
+// the same call between events, then a synchronisation: phase_ms[7] = the device time of clear, count, scan, emit,
+// sort, fill and lines / points, written only when the call succeeds (tools/vector_bench.py)
+extern "C" int dt_dev_rasterize_timed(dt_ctx *c, int kind, const double *coords, const int64_t *parts,
+                                      const int32_t *ids, int64_t P, int64_t N, int64_t H, int64_t W, int connectivity,
+                                      int all_touched, int64_t capacity, int32_t *label, int64_t *info,
+                                      double *phase_ms) {
+  DT_CTX(c);
+  DT_REQUIRE(phase_ms, "phase_ms is NULL");
+  hipEvent_t ev[8] = {};
+  int rc = DT_OK;
+  for (int k = 0; k < 8 && rc == DT_OK; k++)
+    if (hipEventCreate(&ev[k]) != hipSuccess) {
+      dt_set_error("hipEventCreate failed: %s", hipGetErrorString(hipGetLastError()));
+      rc = DT_EHIP;
+    }
+  if (rc == DT_OK)
+    rc = dev_rasterize(c, kind, coords, parts, ids, P, N, H, W, connectivity, all_touched, capacity, label, info, ev);
+  float t[7] = {};
+  if (rc == DT_OK) {
+    if (hipEventSynchronize(ev[7]) != hipSuccess) rc = DT_EHIP;
+    for (int k = 0; k < 7 && rc == DT_OK; k++)
+      if (hipEventElapsedTime(&t[k], ev[k], ev[k + 1]) != hipSuccess) rc = DT_EHIP;
+    if (rc != DT_OK) dt_set_error("event timing failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  for (int k = 0; k < 8; k++)
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+  if (rc == DT_OK)
+    for (int k = 0; k < 7; k++) phase_ms[k] = (double)t[k];
+  return rc;
 }
 
 // geodesic reconstruction: what both tiers require of the marker mode and its parameters
@@ -3224,6 +3278,52 @@ extern "C" int dt_resample(const void *src, int dtype, int64_t Hs, int64_t Ws, c
   DT_TRY(hc.rc);
   DT_TRY(dt_launched(dt_launch_resample(hc.c->stream, d_src, dtype, Hs, Ws, matrix, method, nodata, fill_bits, d_dst,
                                         Hd, Wd)));
+  return hc.finish();
+}
+
+// vector rasterisation: what the host entries require of the geometry's host arrays before they read them
+static int dt_check_parts(const double *coords, const int64_t *parts, int64_t P, int64_t *N) {
+  DT_REQUIRE(P >= 0 && P < (1ll << 31), "P must be in [0, 2^31)");
+  *N = 0;
+  if (P == 0) return DT_OK;
+  DT_REQUIRE(parts, "parts is NULL");
+  DT_REQUIRE(parts[0] == 0, "parts must start at 0");
+  for (int64_t p = 0; p < P; p++) DT_REQUIRE(parts[p] <= parts[p + 1], "parts must not decrease");
+  DT_REQUIRE(parts[P] < (1ll << 31), "2^31 vertices or more");
+  DT_REQUIRE(coords || parts[P] == 0, "coords is NULL");
+  *N = parts[P];
+  return DT_OK;
+}
+// the exact work count of a geometry: pure host arithmetic, no device is asked for
+extern "C" int dt_rasterize_count(int kind, const double *coords, const int64_t *parts, int64_t P, int64_t H, int64_t W,
+                                  int64_t *total, int64_t *largest_row) {
+  int64_t N = 0;
+  DT_TRY(dt_check_parts(coords, parts, P, &N));
+  DT_TRY(dt_check_rasterize(kind, P, N, H, W, 8, 0, 0));
+  DT_REQUIRE(total && largest_row, "NULL result");
+  *total = *largest_row = 0;
+  if (kind == 0 && N > 0) dt_rasterize_count_host(coords, parts, P, H, total, largest_row);
+  return DT_OK;
+}
+// a bad argument is refused before the device is asked for; the scratch is sized from the exact count
+extern "C" int dt_rasterize(int kind, const double *coords, const int64_t *parts, const int32_t *ids, int64_t P,
+                            int64_t H, int64_t W, int connectivity, int all_touched, int32_t *label, int64_t *info4) {
+  int64_t N = 0, total = 0, largest = 0;
+  DT_TRY(dt_check_parts(coords, parts, P, &N));
+  DT_TRY(dt_check_rasterize(kind, P, N, H, W, connectivity, all_touched, 0));
+  DT_REQUIRE(label && (ids || P == 0), "NULL label or ids");
+  if (kind == 0 && N > 0) dt_rasterize_count_host(coords, parts, P, H, &total, &largest);
+  DT_REQUIRE(total < (1ll << 31), "the geometry crosses the rows' centre lines 2^31 times or more");
+  HostCall hc;
+  DT_TRY(hc.rc);
+  const double *d_c = hc.in(coords, (size_t)N * 2);
+  const int64_t *d_p = hc.in(parts, (size_t)P + 1);
+  const int32_t *d_i = hc.in(ids, (size_t)P);
+  int32_t *d_l = hc.out(label, (size_t)H * W);
+  int64_t scratch4[4];
+  int64_t *d_info = hc.out(info4 ? info4 : scratch4, 4);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_rasterize(hc.c, kind, d_c, d_p, d_i, P, N, H, W, connectivity, all_touched, total, d_l, d_info));
   return hc.finish();
 }
 

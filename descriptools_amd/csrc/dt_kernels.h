@@ -630,3 +630,18 @@ int dt_check_resample(int dtype, int64_t Hs, int64_t Ws, const double *matrix, i
                       int64_t Wd);
 int dt_launch_resample(hipStream_t s, const void *src, int dtype, int64_t Hs, int64_t Ws, const double *matrix,
                        int method, int64_t nodata, uint64_t fill_bits, void *dst, int64_t Hd, int64_t Wd);
+
+// Vector rasterisation (dt_vector.hip; vector.py holds the definition).  dt_check_rasterize: what both tiers require of
+// a call, pointers aside; each entry runs it once.  dt_rasterize_count_host: a polygon geometry's crossings and the most
+// on one row, host arithmetic, no device.  dt_rasterize_scratch: the bytes of 4 H + 8 capacity, each rounded up to 256.
+// dt_launch_rasterize takes arguments that have passed the check; info is int64[4] on the device, ev NULL or 8 events
+// recorded around the seven phases.  Nothing synchronises, nothing is allocated.
+int dt_check_rasterize(int kind, int64_t P, int64_t N, int64_t H, int64_t W, int connectivity, int all_touched,
+                       int64_t capacity);
+void dt_rasterize_count_host(const double *coords, const int64_t *parts, int64_t P, int64_t H, int64_t *total,
+                             int64_t *largest);
+size_t dt_rasterize_scratch(int64_t H, int64_t capacity);
+int dt_launch_rasterize(hipStream_t s, int kind, const double *coords, const int64_t *parts, const int32_t *ids,
+                        int64_t P, int64_t N, int64_t H, int64_t W, int connectivity, int all_touched,
+                        int64_t capacity, void *scratch, size_t scratch_bytes, int32_t *label, int64_t *info,
+                        hipEvent_t *ev);

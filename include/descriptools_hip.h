@@ -127,6 +127,9 @@ int dt_graph_destroy(dt_graph *graph);
 #define DT_STATUS_BAD_PARAM 512
 int dt_ctx_status(dt_ctx *ctx, int32_t *out);
 int64_t dt_ctx_scratch_bytes(dt_ctx *ctx);
+/* the base of that scratch (NULL before the first call that takes some): a device pointer that the next call which
+ * needs more may free.  For tests that put guard bytes around what an entry carves out of it. */
+void *dt_ctx_scratch_ptr(dt_ctx *ctx);
 
 /* ---- host-pointer tier (drop-in for the reference's *_cpu shims) -----------------------
  * Device blocks behind these calls are cached per process (dt_host_trim frees the idle ones); dt_host_alloc /
@@ -535,6 +538,24 @@ int dt_wetness_saga(const double *area, const float *slope, int64_t H, int64_t W
  * with a2 != 0, b1 != 0, a1 <= 0 or b2 <= 0, or with a1 > 256 or b2 > 256 (chain two calls). */
 int dt_resample(const void *src, int dtype, int64_t Hs, int64_t Ws, const double *matrix, int method, int64_t nodata,
                 uint64_t fill_bits, void *dst, int64_t Hd, int64_t Wd);
+/* Net-new: vector rasterisation (descriptools_amd/vector.py holds the definition, the test suite's numpy reference
+ * matches it bit for bit): one kind of geometry burnt onto an H x W int32 label raster, -1 where nothing burns, the
+ * largest id where several parts do.  kind: 0 polygon (even-odd over all rings of an id, a cell is inside when its
+ * centre is), 1 line, 2 point.  coords: float64[N][2], (x, y) in pixel-corner coordinates; parts: int64[P + 1], the
+ * offsets of the parts (rings, linestrings, runs of points), non-decreasing from 0 to N; ids: int32[P] in [0, 2^30].
+ * connectivity (4 or 8): how a line is drawn; all_touched (0 or 1): a polygon's rings are burnt on top of its interior
+ * as connectivity-4 lines.  info4 (may be NULL): crossings of ring edges with row centre lines, the most on one row,
+ * the rows sorted in global memory because they do not fit LDS, the overflow flag (always 0 here).  Refused: a kind,
+ * connectivity or all_touched outside these lists, an empty shape or 2^31 cells or more, parts that do not start at 0
+ * or decrease, 2^31 vertices, parts or crossings or more.  The caller vouches for finite coordinates and ids in range
+ * (vector.py checks both). */
+int dt_rasterize(int kind, const double *coords, const int64_t *parts, const int32_t *ids, int64_t P, int64_t H,
+                 int64_t W, int connectivity, int all_touched, int32_t *label, int64_t *info4);
+/* The exact work count of dt_rasterize in host arithmetic, no device needed: *total = the crossings of a polygon
+ * geometry's edges with the centre lines of the H rows (8 bytes of scratch each), *largest_row = the most on one row.
+ * Both 0 for lines and points. */
+int dt_rasterize_count(int kind, const double *coords, const int64_t *parts, int64_t P, int64_t H, int64_t W,
+                       int64_t *total, int64_t *largest_row);
 /* Net-new: greyscale geodesic reconstruction (Vincent 1993; descriptools_amd/morphology.py holds the definition): a
  * marker spreads under `mask` until it stops.  mask, marker and out float32, seeds and out8 uint8, H x W with fewer than
  * 2^31 cells.  A cell is valid iff its mask height is finite and > -100; every other cell is nobody's neighbour, holds
@@ -1021,6 +1042,19 @@ int dt_dev_wetness_index(dt_ctx *ctx, const double *modified, const float *slope
  * must not overlap src. */
 int dt_dev_resample(dt_ctx *ctx, const void *src, int dtype, int64_t Hs, int64_t Ws, const double *matrix, int method,
                     int64_t nodata, uint64_t fill_bits, void *dst, int64_t Hd, int64_t Wd);
+/* dt_rasterize on device arrays (N = parts[P] vertices), on the context's stream, without a host synchronisation.
+ * The raster is rows x cols = H x W.  Scratch is the context's: 4 H + 8 capacity bytes.  capacity: the crossing slots the caller vouches for
+ * (dt_rasterize_count gives the exact number); the kernels never write past it, and a geometry with more crossings
+ * leaves label all -1 and says so in info.  info: int64[4] on the device, required: crossings found, the most on one
+ * row, rows sorted in global memory, overflow flag. */
+int dt_dev_rasterize(dt_ctx *ctx, int kind, const double *coords, const int64_t *parts, const int32_t *ids, int64_t P,
+                     int64_t N, int64_t rows, int64_t cols, int connectivity, int all_touched, int64_t capacity,
+                     int32_t *label, int64_t *info);
+/* dt_dev_rasterize between events, followed by a synchronisation: phase_ms (host, double[7]) = the device time of the
+ * clear, count, scan, emit, sort, fill and line / point phases.  A measuring tool's entry. */
+int dt_dev_rasterize_timed(dt_ctx *ctx, int kind, const double *coords, const int64_t *parts, const int32_t *ids,
+                           int64_t P, int64_t N, int64_t rows, int64_t cols, int connectivity, int all_touched,
+                           int64_t capacity, int32_t *label, int64_t *info, double *phase_ms);
 /* dt_morph_reconstruct on device rasters (rows x cols = H x W), on the context's stream, without a host
  * synchronisation: the start keys, `rounds` (1..4096) rounds of tile visits -- a round that follows a quiet one returns
  * at once -- then the output.  When the last round still stored something the budget was too small:
