@@ -81,6 +81,8 @@ _SIGS = {
     "dt_resample": (ci, [vp, ci, i64, i64, c_f64p, ci, i64, C.c_uint64, vp, i64, i64]),
     "dt_rasterize": (ci, [ci, c_f64p, c_i64p, c_i32p, i64, i64, i64, ci, ci, c_i32p, c_i64p]),
     "dt_rasterize_count": (ci, [ci, c_f64p, c_i64p, i64, i64, i64, c_i64p, c_i64p]),
+    "dt_polygonize": (ci, [c_i32p, i64, i64, i64, i64, c_f64p, c_i64p, c_i32p, c_i32p, c_i64p]),
+    "dt_polygonize_count": (ci, [c_i32p, i64, i64, c_i64p]),
     "dt_morph_reconstruct": (ci, [ci, ci, ci, c_f32p, c_f32p, c_u8p, f64, ci, i64, i64, ci, c_f32p, c_u8p, c_i64p]),
     "dt_harmonic": (ci, [c_f32p, c_i8p, c_i8p, i64, i64, f64, ci, c_f64p, c_i64p]),
     "dt_inundation": (ci, [c_f32p, c_f32p, c_f32p, i64, i64, c_f64p, ci, c_i64p, c_f64p, c_f64p, ci, ci, i64, i64, ci,
@@ -155,6 +157,8 @@ _SIGS = {
     "dt_dev_resample": (ci, [vp, vp, ci, i64, i64, c_f64p, ci, i64, C.c_uint64, vp, i64, i64]),
     "dt_dev_rasterize": (ci, [vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, ci, i64, vp, vp]),
     "dt_dev_rasterize_timed": (ci, [vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, ci, i64, vp, vp, c_f64p]),
+    "dt_dev_polygonize": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "dt_dev_polygonize_timed": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, c_f64p]),
     "dt_dev_morph_reconstruct": (ci, [vp, ci, ci, ci, vp, vp, vp, f64, ci, i64, i64, ci, ci, vp, vp]),
     "dt_dev_harmonic": (ci, [vp, vp, vp, vp, i64, i64, f64, ci, vp, vp]),
     "dt_dev_inundation": (ci, [vp, vp, vp, vp, i64, i64, c_f64p, ci, vp, vp, vp, ci, ci, i64, i64, vp, vp, vp, vp, vp,

@@ -11,7 +11,7 @@ SOURCES = ["dt_kernels.hip", "dt_stencil.hip", "dt_tiles.hip", "dt_hydro.hip", "
            "dt_terrain.hip", "dt_horizon.hip", "dt_proximity.hip", "dt_regions.hip", "dt_curve.hip",
            "dt_focal.hip", "dt_mrvbf.hip", "dt_zonal.hip", "dt_cost.hip", "dt_wetness.hip", "dt_morphology.hip",
            "dt_flowpath.hip", "dt_harmonic.hip", "dt_inundation.hip", "dt_filters.hip", "dt_resample.hip",
-           "dt_vector.hip", "dt_capi.hip"]
+           "dt_vector.hip", "dt_polygonize.hip", "dt_capi.hip"]
 HEADERS = ["dt_common.h", "dt_kernels.h", "dt_countdown.h", "dt_dinf_common.h", "dt_tile_rounds.h", "dt_path_tiles.h",
            "dt_math.h", "dt_math_coeffs.h", "dt_reach_wet.h", "dt_d8_kernel.inc", "dt_fa3fh1_kernel.inc",
            os.path.join("..", "..", "include", "descriptools_hip.h")]

@@ -952,6 +952,58 @@ extern "C" int dt_dev_rasterize_timed(dt_ctx *c, int kind, const double *coords,
   return rc;
 }
 
+// polygonisation: the rings have lengths of their own, so the call opens on the context alone and dt_check_polygonize
+// holds the rules; the scratch is sized by cap_edges, which the kernels never write past.  count_only: the count phase
+// alone, info[0] = edges and info[1] = corners (the host entries size their calls with it)
+static int dev_polygonize(dt_ctx *c, const int32_t *labels, int64_t H, int64_t W, int64_t cap_edges,
+                          int64_t cap_vertices, int64_t cap_rings, int count_only, double *coords, int64_t *parts,
+                          int32_t *ids, int32_t *shell, int64_t *info, hipEvent_t *ev) {
+  DT_DEV(d, c);
+  DT_TRY(dt_check_polygonize(H, W, cap_edges, cap_vertices, cap_rings));
+  DT_REQUIRE(labels, "NULL labels");
+  DT_REQUIRE(info && (count_only || (coords && parts && ids && shell)), "NULL coords, parts, ids, shell or info");
+  const size_t need = dt_polygonize_scratch(H, W, cap_edges, count_only);
+  void *scr = d.scratch(need);
+  DT_TRY(d.rc);
+  DT_REQUIRE(scr, "scratch reservation failed");
+  return d.done(dt_launch_polygonize(c->stream, labels, H, W, cap_edges, cap_vertices, cap_rings, count_only, scr, need,
+                                     coords, parts, ids, shell, info, ev));
+}
+extern "C" int dt_dev_polygonize(dt_ctx *c, const int32_t *labels, int64_t H, int64_t W, int64_t cap_edges,
+                                 int64_t cap_vertices, int64_t cap_rings, double *coords, int64_t *parts, int32_t *ids,
+                                 int32_t *shell, int64_t *info) {
+  return dev_polygonize(c, labels, H, W, cap_edges, cap_vertices, cap_rings, 0, coords, parts, ids, shell, info, nullptr);
+}
+// the same call between events, then a synchronisation: phase_ms[7] = the device time of count, link, leaders, ranks,
+// rings, emit and shells, written only when the call succeeds (tools/vector_bench.py)
+extern "C" int dt_dev_polygonize_timed(dt_ctx *c, const int32_t *labels, int64_t H, int64_t W, int64_t cap_edges,
+                                       int64_t cap_vertices, int64_t cap_rings, double *coords, int64_t *parts,
+                                       int32_t *ids, int32_t *shell, int64_t *info, double *phase_ms) {
+  DT_CTX(c);
+  DT_REQUIRE(phase_ms, "phase_ms is NULL");
+  hipEvent_t ev[8] = {};
+  int rc = DT_OK;
+  for (int k = 0; k < 8 && rc == DT_OK; k++)
+    if (hipEventCreate(&ev[k]) != hipSuccess) {
+      dt_set_error("hipEventCreate failed: %s", hipGetErrorString(hipGetLastError()));
+      rc = DT_EHIP;
+    }
+  if (rc == DT_OK)
+    rc = dev_polygonize(c, labels, H, W, cap_edges, cap_vertices, cap_rings, 0, coords, parts, ids, shell, info, ev);
+  float t[7] = {};
+  if (rc == DT_OK) {
+    if (hipEventSynchronize(ev[7]) != hipSuccess) rc = DT_EHIP;
+    for (int k = 0; k < 7 && rc == DT_OK; k++)
+      if (hipEventElapsedTime(&t[k], ev[k], ev[k + 1]) != hipSuccess) rc = DT_EHIP;
+    if (rc != DT_OK) dt_set_error("event timing failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  for (int k = 0; k < 8; k++)
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+  if (rc == DT_OK)
+    for (int k = 0; k < 7; k++) phase_ms[k] = (double)t[k];
+  return rc;
+}
+
 // geodesic reconstruction: what both tiers require of the marker mode and its parameters
 static int dt_check_morph(int mode, int erosion, int connectivity, double h, int radius, int visit_limit) {
   DT_REQUIRE(mode >= DT_MORPH_MARKER && mode <= DT_MORPH_WINDOW, "mode must be one of DT_MORPH_*");
@@ -3324,6 +3376,58 @@ extern "C" int dt_rasterize(int kind, const double *coords, const int64_t *parts
   int64_t *d_info = hc.out(info4 ? info4 : scratch4, 4);
   DT_TRY(hc.rc);
   DT_TRY(dt_dev_rasterize(hc.c, kind, d_c, d_p, d_i, P, N, H, W, connectivity, all_touched, total, d_l, d_info));
+  return hc.finish();
+}
+
+// polygonisation: the count phase on the device, info2 = {edges, corners}
+static int host_polygonize_count(HostCall &hc, const int32_t *d_lab, int64_t H, int64_t W, int64_t *info8) {
+  int64_t *d_info = hc.scratch<int64_t>(8);
+  DT_TRY(hc.rc);
+  DT_TRY(dev_polygonize(hc.c, d_lab, H, W, 0, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, d_info, nullptr));
+  DT_TRY(hc.download(info8, d_info, 8));
+  return dt_ctx_sync(hc.c);
+}
+extern "C" int dt_polygonize_count(const int32_t *labels, int64_t H, int64_t W, int64_t *info2) {
+  DT_TRY(dt_check_polygonize(H, W, 0, 0, 0));
+  DT_REQUIRE(labels && info2, "NULL labels or info");
+  HostCall hc;
+  DT_TRY(hc.rc);
+  const int32_t *d_lab = hc.in(labels, (size_t)H * W);
+  int64_t info8[8];
+  DT_TRY(host_polygonize_count(hc, d_lab, H, W, info8));
+  info2[0] = info8[0];
+  info2[1] = info8[1];
+  return hc.finish();
+}
+// a bad argument is refused before the device is asked for; the edge scratch is sized from the count phase.  The rings
+// come back only when they fit: an overflow leaves the outputs untouched and says so in info8[5]
+extern "C" int dt_polygonize(const int32_t *labels, int64_t H, int64_t W, int64_t cap_vertices, int64_t cap_rings,
+                             double *coords, int64_t *parts, int32_t *ids, int32_t *shell, int64_t *info8) {
+  DT_TRY(dt_check_polygonize(H, W, 0, cap_vertices, cap_rings));
+  DT_REQUIRE(labels, "NULL labels");
+  DT_REQUIRE(coords && parts && ids && shell && info8, "NULL coords, parts, ids, shell or info");
+  HostCall hc;
+  DT_TRY(hc.rc);
+  const int32_t *d_lab = hc.in(labels, (size_t)H * W);
+  int64_t cnt[8];
+  DT_TRY(host_polygonize_count(hc, d_lab, H, W, cnt));
+  DT_REQUIRE(cnt[0] < (1ll << 31), "the raster has 2^31 directed boundary edges or more");
+  double *d_c = hc.scratch<double>((size_t)cap_vertices * 2);
+  int64_t *d_p = hc.scratch<int64_t>((size_t)cap_rings + 1);
+  int32_t *d_i = hc.scratch<int32_t>((size_t)cap_rings);
+  int32_t *d_s = hc.scratch<int32_t>((size_t)cap_rings);
+  int64_t *d_info = hc.scratch<int64_t>(8);
+  DT_TRY(hc.rc);
+  DT_TRY(dt_dev_polygonize(hc.c, d_lab, H, W, cnt[0], cap_vertices, cap_rings, d_c, d_p, d_i, d_s, d_info));
+  DT_TRY(hc.download(info8, d_info, 8));
+  DT_TRY(dt_ctx_sync(hc.c));
+  if (info8[5] == 0) {
+    const size_t V = (size_t)info8[1], P = (size_t)info8[2];
+    DT_TRY(hc.download(coords, d_c, V * 2));
+    DT_TRY(hc.download(parts, d_p, P + 1));
+    DT_TRY(hc.download(ids, d_i, P));
+    DT_TRY(hc.download(shell, d_s, P));
+  }
   return hc.finish();
 }
 

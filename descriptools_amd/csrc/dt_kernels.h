@@ -645,3 +645,16 @@ int dt_launch_rasterize(hipStream_t s, int kind, const double *coords, const int
                         int64_t P, int64_t N, int64_t H, int64_t W, int connectivity, int all_touched,
                         int64_t capacity, void *scratch, size_t scratch_bytes, int32_t *label, int64_t *info,
                         hipEvent_t *ev);
+
+// Polygonisation (dt_polygonize.hip; vector.py holds the definition).  dt_check_polygonize: what both tiers require of
+// a call, pointers aside.  dt_polygonize_scratch: 768 bytes of round flags, 2 x 4 bytes per 1024 lattice vertices of
+// block sums, 4 bytes per cell and 20 bytes per edge of capacity (two 8-byte doubling words and the leader), each array
+// rounded up to 256; count_only: the flags and the block sums alone.  dt_launch_polygonize takes arguments that have
+// passed the check; info is int64[8] on the device (edges, vertices, rings, holes, rounds of the leader doubling, the
+// overflow flags 1 edges | 2 vertices | 4 rings, rounds of the rank doubling, rounds of the shell links), ev NULL or 8
+// events recorded around the seven phases.  Nothing synchronises, nothing is allocated.
+int dt_check_polygonize(int64_t H, int64_t W, int64_t cap_edges, int64_t cap_vertices, int64_t cap_rings);
+size_t dt_polygonize_scratch(int64_t H, int64_t W, int64_t cap_edges, int count_only);
+int dt_launch_polygonize(hipStream_t s, const int32_t *labels, int64_t H, int64_t W, int64_t cap_edges,
+                         int64_t cap_vertices, int64_t cap_rings, int count_only, void *scratch, size_t scratch_bytes,
+                         double *coords, int64_t *parts, int32_t *ids, int32_t *shell, int64_t *info, hipEvent_t *ev);

@@ -54,9 +54,55 @@ Recipes (g = vector.from_geojson(path, rasterio_lite.geotransform(meta))):
     cost.cost_distance(np.where(wall, -100, friction), sources, px)       # a barrier
     pour_points = vector.rasterize(g["point"], dem.shape) + 1             # gauges: watersheds wants labels > 0
     zones = vector.rasterize(g["polygon"], dem.shape)                     # admin polygons:
-    zonal.statistics(zones, hand, len(g["properties"]))                   # row k belongs to properties[k]"""
+    zonal.statistics(zones, hand, len(g["properties"]))                   # row k belongs to properties[k]
+
+POLYGONISATION (what gdal_polygonize and rasterio.features.shapes do): the way back off the grid, and the inverse of the
+polygon fill above -- rasterize(polygonize(labels).geometry, labels.shape) equals where(labels >= 0, labels, -1) bit for
+bit.  THIS definition is the contract and tests/_polygonize_ref.py is its reference: the library matches it byte for byte.
+
+polygonize(labels, background=None, return_info=False) -> Polygons(geometry, shell).
+Input.  labels is a 2-D bool or integer raster, H x W, of fewer than 2^31 cells.  A negative value is background;
+background=v makes the value v background too (a mask is polygonize(mask, background=0)); everything else must lie in
+[0, 2^30] (MAX_ID), else ValueError before any library call.  Float rasters are refused as in `regions`: compare first.
+The library is handed int32 with -1 on background.  Outside the raster is background.
+Boundary edges.  A unit edge of the cell lattice, raster border included, between two cells whose labels differ carries
+one directed edge for each side that is not background, directed so that its own cell lies on the right of the direction
+of travel as seen with x to the right and y down: a cell's top edge travels east, its right edge south, its bottom edge
+west, its left edge north.  An edge between two cells of one label carries nothing.
+Successor.  At its head vertex a directed edge of label L goes on into the directed edge of L that leaves that vertex;
+where two leave -- L's cells meet only diagonally there -- the ring turns right.  So a ring stays with its own cell and
+never crosses itself or another ring of L; every 4-connected region of a label has exactly one outer ring (a shell) and
+one ring per hole; regions that touch only diagonally are separate shells of one id that share a vertex, which under
+rasterize's even-odd rule is the same cell set.
+Rings.  Each cycle of the successor relation is one part.  Only the vertices where the direction changes are kept, so
+every ring has an even number of at least 4 vertices, alternately joined by horizontal and vertical runs.  The ring
+starts at its lexicographically smallest (y, x) vertex, which is always a corner, and follows the direction of travel:
+a shell leaves its start eastward and has positive shoelace area in (x, y), a hole leaves it southward and has negative
+area.  With a north-up geotransform the shells are counter-clockwise in world coordinates, as RFC 7946 asks.
+Coordinates are the integers of the lattice as float64 pixel-corner coordinates: geometry is Geometry("polygon", coords,
+parts, ids) with ids[p] the label of ring p.
+Order of parts.  Ascending start vertex y * (W + 1) + x, and at one vertex the shell before the hole (at most one of
+each can start at a vertex: the ring leaves it along the one east edge or the one south edge that start there).
+shell.  int32[P]: the position of the part that is the outer ring of the ring's 4-connected region, the part itself for a
+shell.  For a hole h of label L the cell directly above its start vertex (row y - 1, column x) has label L; walk west
+from it along its row to the first cell that is not L, or to the border; the vertical edge crossed belongs to a ring of
+the same region: a shell, which is h's, or a hole with a strictly smaller start vertex, whose shell h inherits.
+info (return_info=True): {"edges", "vertices", "rings", "holes", "rounds"}: directed edges, kept vertices, parts, the
+parts that are holes, and the rounds of pointer doubling that found the rings' start vertices, the first round that
+lowers no window's smallest start vertex included (round k joins two windows of 2^(k-1) edges).
+An all-background raster gives the empty geometry: P = 0, parts == [0].
+
+from_pixel inverts to_pixel; to_geojson writes Polygons (shells followed by their holes), lines and points as a GeoJSON
+FeatureCollection, one Feature per id.  Recipes:
+    extent = regions.connected(hand <= h, river == 1)                     # a flood extent layer
+    vector.to_geojson(vector.polygonize(extent, background=0), geotransform, path="extent.geojson")
+    zones, table = zonal.compact(watershed.basins(fdr))                   # basins: properties from the table
+    vector.to_geojson(vector.polygonize(zones), geotransform, {k: {"basin": int(v)} for k, v in enumerate(table)})
+    zones, table = zonal.compact(regions.label(mask))                     # one feature per connected region
+    vector.polygonize(zones)"""
 import json
 import math
+from collections import namedtuple
 
 import numpy as np
 
@@ -249,3 +295,134 @@ def burn(geometry, shape, values, fill, connectivity=8, all_touched=False):
     """values[id] burnt where rasterize(...) holds id, `fill` elsewhere and where id >= len(values):
     zonal.paint(values, label, fill), in the dtype of `values`"""
     return zonal.paint(values, rasterize(geometry, shape, connectivity, all_touched), fill)
+
+
+# ---- polygonisation -----------------------------------------------------------------------------------------------------
+Polygons = namedtuple("Polygons", ["geometry", "shell"])
+
+_INFO = ("edges", "vertices", "rings", "holes", "rounds")
+
+
+def _labels(labels, background):
+    """labels as int32 with -1 on background; ValueError for what the module docstring refuses"""
+    a = _args.raster(labels, "labels", kinds="biu")
+    valid = np.ones(a.shape, bool) if a.dtype.kind in "bu" else a >= 0
+    if background is not None:
+        if not isinstance(background, (int, np.integer)) or isinstance(background, (bool, np.bool_)):
+            raise ValueError("background must be an integer or None, not %r" % (background,))
+        valid &= a != background
+    if valid.any() and int(a[valid].max()) > MAX_ID:
+        raise ValueError("labels must lie in [0, 2^30] (or be negative, or equal `background`)")
+    out = np.full(a.shape, -1, np.int32)
+    out[valid] = a[valid]
+    return out
+
+
+def polygonize(labels, background=None, return_info=False):
+    """The rings of a label raster -> Polygons(geometry, shell): geometry a polygon Geometry whose ids are the labels,
+    shell int32[P] the position of each ring's outer ring.  The module docstring holds the definition.
+    return_info=True -> (polygons, {"edges", "vertices", "rings", "holes", "rounds"})."""
+    lab = _labels(labels, background)
+    H, W = lab.shape
+    L = _lib.lib()
+    count = np.zeros(2, np.int64)
+    check(L.dt_polygonize_count(ptr(lab, c_i32p), H, W, ptr(count, c_i64p)))
+    edges, vertices = int(count[0]), int(count[1])
+    if edges >= 2 ** 31:
+        raise ValueError("labels has %d directed boundary edges; polygonize takes fewer than 2^31" % edges)
+    rings = vertices // 4  # a ring has at least 4 vertices
+    coords = host_empty((vertices, 2), np.float64)
+    parts, ids, shell = np.zeros(rings + 1, np.int64), np.empty(rings, np.int32), np.empty(rings, np.int32)
+    info = np.zeros(8, np.int64)
+    check(L.dt_polygonize(ptr(lab, c_i32p), H, W, vertices, rings, ptr(coords, c_f64p), ptr(parts, c_i64p),
+                          ptr(ids, c_i32p), ptr(shell, c_i32p), ptr(info, c_i64p)))
+    if info[5] != 0 or info[1] != vertices:
+        raise RuntimeError("polygonize: the count phase and the call disagree (info = %s)" % info.tolist())
+    P = int(info[2])
+    out = Polygons(Geometry("polygon", coords, parts[:P + 1].copy(), ids[:P].copy()), shell[:P].copy())
+    if return_info:
+        return out, dict(zip(_INFO, (int(v) for v in info[:5])))
+    return out
+
+
+def from_pixel(xy, transform):
+    """Pixel-corner coordinates xy (float64[..., 2], (x, y)) -> world coordinates (X, Y) of the grid with the GDAL-order
+    geotransform (x0, dx, rx, y0, ry, dy), in numpy float64, one rounding per operation, in this association:
+        X = (x0 + dx * x) + rx * y        Y = (y0 + ry * x) + dy * y
+    -- the inverse of to_pixel, exact when the products and sums are (a north-up transform with power-of-two pixels).
+    ValueError as to_pixel."""
+    try:
+        t = tuple(transform)
+    except TypeError:
+        t = None
+    to_pixel(np.zeros((1, 2)), t)  # the checks, singularity included
+    x0, dx, rx, y0, ry, dy = (np.float64(e) for e in t)
+    a = np.asarray(xy, np.float64)
+    if a.ndim < 1 or a.shape[-1] != 2:
+        raise ValueError("xy must have shape (..., 2), not %s" % (a.shape,))
+    x, y = a[..., 0], a[..., 1]
+    return np.stack(((x0 + dx * x) + rx * y, (y0 + ry * x) + dy * y), axis=-1)
+
+
+_GEOJSON_TYPE = {"polygon": ("Polygon", "MultiPolygon"), "line": ("LineString", "MultiLineString"),
+                 "point": ("Point", "MultiPoint")}
+
+
+def to_geojson(polygons_or_geometry, transform=None, properties=None, path=None):
+    """A GeoJSON FeatureCollection (a dict; written to `path` with `json` when one is given) of a Polygons, or of a line
+    or point Geometry: one Feature per distinct id, in ascending id, with properties[id] where `properties` (a mapping or
+    a sequence) holds it, else {"id": id}.  Polygons become Polygon or MultiPolygon: each shell in part order followed by
+    its holes in part order, grouped through `shell`, every ring closed by repeating its first vertex; lines become
+    LineString or MultiLineString, points Point or MultiPoint.  With `transform` (a GDAL geotransform) the coordinates go
+    through from_pixel; without, they stay pixel-corner coordinates.  A polygon Geometry comes without the grouping of
+    its rings and is refused: polygonize returns it as Polygons(geometry, shell)."""
+    if isinstance(polygons_or_geometry, Polygons):
+        g, shell = _geometry(polygons_or_geometry.geometry), np.asarray(polygons_or_geometry.shell)
+        if g.kind != "polygon":
+            raise ValueError("Polygons.geometry must be a polygon geometry, not %r" % g.kind)
+        if shell.shape != g.ids.shape or (shell.size and shell.dtype.kind not in "iu"):
+            raise ValueError("shell must hold one integer per part (%d), not shape %s" % (g.ids.size, shell.shape))
+        if shell.size and (shell.min() < 0 or shell.max() >= shell.size or (shell[shell] != shell).any()
+                           or (g.ids[shell] != g.ids).any()):
+            raise ValueError("shell must name, for every part, a part of the same id that is its own shell")
+    else:
+        g, shell = _geometry(polygons_or_geometry), None
+        if g.kind == "polygon":
+            raise ValueError("a polygon Geometry does not say which rings are holes of which: pass the Polygons(geometry, "
+                             "shell) that vector.polygonize returns")
+    xy = g.coords if transform is None else from_pixel(g.coords, transform)
+    runs = [xy[g.parts[p]:g.parts[p + 1]].tolist() for p in range(g.ids.size)]
+    by_id = {}
+    if g.kind == "polygon":
+        polygon_at = {}
+        for p in range(g.ids.size):      # shells in part order, then every hole behind its shell
+            if shell[p] == p:
+                polygon_at[p] = len(by_id.setdefault(int(g.ids[p]), []))
+                by_id[int(g.ids[p])].append([runs[p] + runs[p][:1]])
+        for p in range(g.ids.size):
+            if shell[p] != p:
+                by_id[int(g.ids[p])][polygon_at[int(shell[p])]].append(runs[p] + runs[p][:1])
+    else:
+        for p in range(g.ids.size):
+            members = by_id.setdefault(int(g.ids[p]), [])
+            if g.kind == "line":
+                members.append(runs[p])
+            else:
+                members.extend(runs[p])
+    features = []
+    for k in sorted(by_id):
+        members = by_id[k]
+        if not members:      # an id whose parts hold no point
+            continue
+        single, multi = _GEOJSON_TYPE[g.kind]
+        geom = {"type": single, "coordinates": members[0]} if len(members) == 1 else {"type": multi, "coordinates": members}
+        try:
+            props = properties[k]
+        except (TypeError, KeyError, IndexError):
+            props = {"id": k}
+        features.append({"type": "Feature", "properties": props, "geometry": geom})
+    out = {"type": "FeatureCollection", "features": features}
+    if path is not None:
+        with open(path, "w") as f:
+            json.dump(out, f)
+    return out

@@ -12,22 +12,80 @@ default, px = 10), in one process, device time between events on resident arrays
 Each case is timed beside a device copy of the label raster's 4 bytes per cell in the same run, the two alternating
 inside a step: that copy is the yardstick, `ratio` = case / copy.  The phases (clear, count, scan, emit, sort, fill,
 lines / points) come from dt_dev_rasterize_timed, which records an event between them; `info` is the call's own count
-(crossings, the most on one row, rows sorted in global memory, overflow).  Prints one JSON line (and writes it to
---out)."""
+(crossings, the most on one row, rows sorted in global memory, overflow).
+
+Polygonisation (--polygonize, a comma-separated list, empty to skip) takes label rasters off the grid
+again with dt_dev_polygonize: `extent` (hand <= 3 as a mask), `landform` (horizon.geomorphons), `basins`
+(zonal.compact(watershed.basins)) and `checkerboard` (two labels, every cell its own ring: 4 edges per cell, the most a
+raster can have).  A first call with capacities 0 is the count; the timed calls get the exact capacities.  Each case
+alternates with a device copy of the int32 label raster and with dt_dev_rasterize of the rings just produced, the round
+trip's other half, whose label must equal the input (`exact`).  The phases (count, link, leaders, ranks, rings, emit,
+shells) come from dt_dev_polygonize_timed; `info` holds the call's counts and rounds.  --skip-rasterize leaves the
+rasterisation cases out.  Prints one JSON line (and writes it to --out)."""
 import ctypes as C
 
 import _bench
 
 PHASES = ("clear", "count", "scan", "emit", "sort", "fill", "lines")
+PG_PHASES = ("count", "link", "leaders", "ranks", "rings", "emit", "shells")
+PG_INFO = ("edges", "vertices", "rings", "holes", "rounds", "overflow", "rank_rounds", "shell_rounds")
 # dx, dy of the D8 codes 1 2 4 8 16 32 64 128 (E SE S SW W NW N NE)
 D8_DX = (1, 1, 0, -1, -1, -1, 0, 1)
 D8_DY = (0, 1, 1, 1, 0, -1, -1, -1)
+
+
+def polygonize_case(ctx, st, dev, L, lab, steps, warmup):
+    """one label raster (int32 on the device) through dt_dev_polygonize, beside its copy and the way back"""
+    import torch
+    from descriptools_amd import _lib
+    H, W = lab.shape
+    info = torch.zeros(8, dtype=torch.int64, device=dev)
+    none = torch.zeros(2, dtype=torch.int64, device=dev)
+    _lib.check(L.dt_dev_polygonize(ctx.h, lab.data_ptr(), H, W, 0, 0, 0, none.data_ptr(), none.data_ptr(),
+                                   none.data_ptr(), none.data_ptr(), info.data_ptr()))     # capacities 0: the count
+    ctx.sync()
+    E, V = info[:2].tolist()
+    if E >= 2 ** 31:
+        return {"edges": E, "vertices": V, "skipped": "2^31 directed edges or more"}
+    R = V // 4
+    coords = torch.empty((max(V, 1), 2), dtype=torch.float64, device=dev)
+    parts = torch.empty(R + 1, dtype=torch.int64, device=dev)
+    ids, shell = (torch.empty(max(R, 1), dtype=torch.int32, device=dev) for _ in range(2))
+    back, dst = torch.empty_like(lab), torch.empty_like(lab)
+    rinfo = torch.zeros(4, dtype=torch.int64, device=dev)
+    args = (ctx.h, lab.data_ptr(), H, W, E, V, R, coords.data_ptr(), parts.data_ptr(), ids.data_ptr(), shell.data_ptr(),
+            info.data_ptr())
+    _lib.check(L.dt_dev_polygonize(*args))
+    ctx.sync()
+    counts = dict(zip(PG_INFO, info.tolist()))
+    P = counts["rings"]
+    # every crossing of a row's centre line is one vertical unit edge: the edges bound the rasteriser's capacity
+    rargs = (ctx.h, 0, coords.data_ptr(), parts.data_ptr(), ids.data_ptr(), P, V, H, W, 8, 0, E, back.data_ptr(),
+             rinfo.data_ptr())
+    calls = {"polygonize": lambda: _lib.check(L.dt_dev_polygonize(*args)), "copy": lambda: dst.copy_(lab),
+             "rasterize": lambda: _lib.check(L.dt_dev_rasterize(*rargs))}
+    tm = _bench.events(ctx, st, calls, steps, warmup)
+    per_phase = []
+    for _ in range(steps):
+        out = (C.c_double * 7)()
+        _lib.check(L.dt_dev_polygonize_timed(*args, out))
+        per_phase.append(list(out))
+    ctx.sync()
+    ms, ms_copy, ms_back = (_bench.summary(tm[k]) for k in ("polygonize", "copy", "rasterize"))
+    return {"info": counts, "ms": ms[0], "ms_min_max": ms[1], "copy_ms": ms_copy[0], "copy_ms_min_max": ms_copy[1],
+            "ratio": round(ms[0] / ms_copy[0], 2), "rasterize_ms": ms_back[0], "rasterize_ms_min_max": ms_back[1],
+            "rasterize_info": dict(zip(("crossings", "largest_row", "slow_rows", "overflow"), rinfo.tolist())),
+            "exact": bool(torch.equal(back, torch.where(lab >= 0, lab, -1))),
+            "scratch_bytes": int(L.dt_ctx_scratch_bytes(ctx.h)),
+            "phase_ms": {p: round(_bench.median([s[k] for s in per_phase]), 3) for k, p in enumerate(PG_PHASES)}}
 
 
 def main(argv=None):
     ap = _bench.parser(steps=5, warmup=2)
     ap.add_argument("--polygons", type=int, default=100000)
     ap.add_argument("--points", type=int, default=1000000)
+    ap.add_argument("--polygonize", default="extent,landform,basins,checkerboard")
+    ap.add_argument("--skip-rasterize", action="store_true")
     a = ap.parse_args(argv)
 
     import numpy as np
@@ -41,9 +99,11 @@ def main(argv=None):
            "device": torch.cuda.get_device_name(0)}
 
     with torch.cuda.stream(st):
-        t = _bench.terrain(ctx, st, dev, S, a.seed, ("fdr", "river", "hand"))
+        pg_cases = [c for c in a.polygonize.split(",") if c]
+        t = _bench.terrain(ctx, st, dev, S, a.seed, ("dem", "fdr", "river", "hand"))
         wet = (t["hand"] <= 3.0) & (t["hand"] > -100.0)
         river, fdr = t["river"] != 0, t["fdr"]
+        dem_host = t["dem"].cpu().numpy() if "landform" in pg_cases else None
         del t
 
         # a rectangle per run of wet cells of a row, in row-major order
@@ -102,7 +162,7 @@ def main(argv=None):
                  ("river_lines_8", 1, segs, seg_parts, seg_ids, 8, 0, river),
                  ("river_lines_4", 1, segs, seg_parts, seg_ids, 4, 0, None),
                  ("points", 2, pts, pt_parts, pt_ids, 8, 0, None)]
-        for name, kind, xy, parts, ids, conn, capacity, truth in cases:
+        for name, kind, xy, parts, ids, conn, capacity, truth in ([] if a.skip_rasterize else cases):
             args = (ctx.h, kind, xy.data_ptr(), parts.data_ptr(), ids.data_ptr(), ids.numel(), xy.shape[0], S, S, conn, 0,
                     capacity, label.data_ptr(), info.data_ptr())
             calls = {"case": lambda: _lib.check(L.dt_dev_rasterize(*args)), "copy": lambda: c_dst.copy_(c_src)}
@@ -123,11 +183,30 @@ def main(argv=None):
             if truth is not None:
                 c["exact"] = bool(torch.equal(label >= 0, truth))
             res["cases"][name] = c
+        del runs, run_parts, run_ids, polys, poly_parts, poly_ids, segs, seg_parts, seg_ids, pts, c_src, c_dst
+        res["polygonize"] = {}
+        for name in pg_cases:
+            if name == "extent":
+                lab = torch.where(wet, 1, -1).to(torch.int32)
+            elif name == "checkerboard":
+                k = torch.arange(S, device=dev, dtype=torch.int32)
+                lab = ((k[:, None] + k[None, :]) & 1).contiguous()
+            elif name == "landform":
+                from descriptools_amd import horizon
+                lab = torch.from_numpy(horizon.geomorphons(dem_host, 10.0).astype(np.int32)).to(dev)
+            elif name == "basins":
+                from descriptools_amd import watershed, zonal
+                lab = torch.from_numpy(np.ascontiguousarray(zonal.compact(watershed.basins(fdr.cpu().numpy())).zones)).to(dev)
+            else:
+                raise SystemExit("unknown polygonize case %r" % name)
+            res["polygonize"][name] = polygonize_case(ctx, st, dev, L, lab, a.steps, a.warmup)
+            del lab
         status = ctx.status()
     res["device_status"] = status
     res["timing"] = ("device time between events on resident arrays, median of --steps after --warmup; copy: a device "
                      "copy of the label raster's 4 bytes per cell, timed alternately with the case; phase_ms: events "
-                     "recorded between the phases of one call (dt_dev_rasterize_timed)")
+                     "recorded between the phases of one call (dt_dev_rasterize_timed, dt_dev_polygonize_timed); "
+                     "polygonize: rasterize_ms is dt_dev_rasterize of the rings just produced, timed in the same steps")
     ctx.close()
     _bench.emit(res, a.out)
 
