@@ -239,6 +239,16 @@ extern "C" int dt_ctx_status(dt_ctx *c, int32_t *out) {
 extern "C" int64_t dt_ctx_scratch_bytes(dt_ctx *c) { return c ? (int64_t)c->scratch_bytes : 0; }
 extern "C" void *dt_ctx_scratch_ptr(dt_ctx *c) { return c ? (void *)c->scratch : nullptr; }
 
+// DT_DBG_POISON (tests): 0x100 | b fills the first `bytes` of a workspace with byte b, on the stream of the call that is
+// about to use it, so the fill is ordered before the op's first kernel and before any upload into the block.  Off (0):
+// this one integer test, nothing enqueued.
+static int dt_poison(hipStream_t s, void *p, size_t bytes) {
+  const int v = dt_debug_get(DT_DBG_POISON);
+  if (!(v & 0x100) || !p || bytes == 0) return DT_OK;
+  DT_HIP(hipMemsetAsync(p, v & 0xFF, bytes, s));
+  return DT_OK;
+}
+
 int dt_scratch_reset(dt_ctx *c, size_t total) {
   total = dt_align256(total) + 256;
   if (total > c->scratch_bytes) {
@@ -253,7 +263,7 @@ int dt_scratch_reset(dt_ctx *c, size_t total) {
   }
   c->scratch_used = 0;
   c->claim = DtScratchClaim{};  // whatever two-phase state was here is about to be overwritten
-  return DT_OK;
+  return dt_poison(c->stream, c->scratch, total);  // what this call asked for, not the whole grown block
 }
 void *dt_scratch_take(dt_ctx *c, size_t bytes) {
   size_t off = c->scratch_used;
@@ -262,7 +272,10 @@ void *dt_scratch_take(dt_ctx *c, size_t bytes) {
   return c->scratch + off;
 }
 
-// grow-only side buffers (scratch2: rank-level solves; aux: stencil marks)
+// grow-only side buffers (scratch2: rank-level solves; aux: stencil marks).  Neither carries state from one call to
+// the next: every entry that reserves aux launches the hot kernel that writes the marks and the fix-up that reads them
+// in the same call, and every rank solve rebuilds its sums and tables from the rows it is given.  So DT_DBG_POISON
+// fills the bytes asked for at every reservation, not only when the block is allocated.
 static int dt_side_reserve(dt_ctx *c, char **buf, size_t *have, size_t bytes) {
   if (bytes > *have) {
     DT_HIP(hipStreamSynchronize(c->stream));
@@ -273,7 +286,7 @@ static int dt_side_reserve(dt_ctx *c, char **buf, size_t *have, size_t bytes) {
     DT_HIP(hipMalloc((void **)buf, bytes));
     *have = bytes;
   }
-  return DT_OK;
+  return dt_poison(c->stream, *buf, bytes);
 }
 
 #define DT_CTX(c)                            \
@@ -432,7 +445,7 @@ extern "C" int dt_dev_malloc(dt_ctx *c, int64_t bytes, void **out) {
       return e == hipErrorOutOfMemory ? DT_ENOMEM : DT_EHIP;
     }
   }
-  return DT_OK;
+  return dt_poison(c->stream, *out, n);
 }
 extern "C" int dt_dev_free(dt_ctx *c, void *p) {
   DT_CTX(c);
@@ -2442,6 +2455,8 @@ struct HostCall {
   void *workspace(size_t bytes) {
     void *p = host_block_take(bytes ? bytes : 16);
     if (p) blocks.push_back(p);
+    // cached or new, over the bytes asked for: scratch<T>, in() before its copy, out()
+    if (p && c && dt_poison(c->stream, p, bytes) != DT_OK && rc == DT_OK) rc = DT_EHIP;
     return p;
   }
   template <typename T>

@@ -52,7 +52,10 @@ enum {
   DT_DBG_DINF_STACK = 11,   /* D-infinity accumulation: n > 0: a lane holds at most n complete cells, the one it carries on
                                with included (1: no stack), so that the spill queue and its rounds run (tests); the
                                environment variable DT_DBG_DINF_STACK sets it too */
-  DT_DBG_COUNT = 12
+  DT_DBG_POISON = 12,       /* 0x100 | b: every workspace the library hands out is filled with byte b on the call's stream
+                               before the op's first kernel (dt_poison in dt_capi.hip; tests).  Read at call time; not
+                               to be set around a graph capture, which would record the memsets */
+  DT_DBG_COUNT = 13
 };
 int dt_debug_get(int key);
 

@@ -55,7 +55,11 @@ int dt_set_flow_impl(int impl);
 /* Test knobs, all 0 by default.  key 0 (DT_DBG_TWI_FLAG_ALL): the fused slope + TI + MTI stencil sends every
  * cell through its exact (cold) path as well as the fast one; keys 8-11: see csrc/dt_common.h.  Keys 1-7 selected
  * kernel variants of finished A/B runs and were retired with them: setting one is an error (DT_EINVAL) and changes
- * nothing. */
+ * nothing.  key 12 (DT_DBG_POISON): 0x100 | b fills every workspace the library hands out with byte b before the
+ * op that asked for it starts -- the context scratch at every reset, the host tier's device blocks (scratch, inputs
+ * before their upload, outputs), the side buffers and dt_dev_malloc's blocks -- with hipMemsetAsync on the call's
+ * stream; read at call time.  No result may depend on it.  Do not set it around dt_graph_begin / dt_graph_end: the
+ * memsets would be recorded into the graph. */
 int dt_debug_set(int key, int value);
 
 /* Context = one device + one stream + grow-only scratch.  `stream` may be NULL (the context

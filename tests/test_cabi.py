@@ -41,18 +41,18 @@ def test_binding_table_matches_header():
 
 def test_debug_keys_retired_and_kept():
     """dt_debug_set: keys 1-7 selected kernel variants that are gone -- setting one fails and says so; keys 0 and
-    8-11 keep their numbers (tests and tools address them by number).  No device needed."""
+    8-12 keep their numbers (tests and tools address them by number).  No device needed."""
     from descriptools_amd import _lib
     L = _lib.lib()
     for k in range(1, 8):
         assert L.dt_debug_set(k, 1) != 0, k
         assert b"retired" in L.dt_last_error(), (k, L.dt_last_error())
-    for k in (0, 8, 9, 10, 11):
+    for k in (0, 8, 9, 10, 11, 12):
         try:
             assert L.dt_debug_set(k, 1) == 0, k
         finally:
             assert L.dt_debug_set(k, 0) == 0, k
-    assert L.dt_debug_set(12, 1) != 0 and L.dt_debug_set(-1, 1) != 0
+    assert L.dt_debug_set(13, 1) != 0 and L.dt_debug_set(-1, 1) != 0
     assert b"retired" not in L.dt_last_error()
 
 
